@@ -13,7 +13,11 @@ the API's own min_new_tokens knob) with product-default sa
 over ranks (replicated weights, no data-path collective); RCCL is used for the barrier, the max-time
 reduction and ONE final result gather.  value = total audio seconds over all ranks / max wall.
 
-The JSON line also carries (all measured in this run unless tagged otherwise):
+A plain run sets up, warms up, times the K steps and prints the line (value, ttfa_ms_p50, ms_per_step = wall of one timed
+step).  `--dump-outputs DIR` writes what the timed path returned in its last step -- the concatenated PCM chunks of rank 0's
+last utterance -- as DIR/audio.npy (float32); with the same arguments the inputs and seeds are the same from run to run.
+
+With `--full` the JSON line also carries (all measured in this run unless tagged otherwise):
   roofline            decode-frame hipGraph (one replay = one 80 ms frame): algorithmic bytes of SURVEY.md
                       section 8(d) / measured replay time (HIP events on the launch stream) vs 8 TB/s
   roofline_mfma       the matrix-core kernels of the path (codec conv GEMMs, prefill GEMMs): FLOPs / event time vs the
@@ -904,7 +908,7 @@ def main():
     ap.add_argument("--steps", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="headline + roofline only (profiling runs)")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: headline + roofline only (profiling runs)")
     ap.add_argument("--batch", type=int, default=128, help="lock-step lanes of the batched figures, <= 128 (0 = skip them)")
     ap.add_argument("--batch-groups", type=int, default=1, help="opt-in: concurrent lock-step batches on one GPU, `batched_groups_one_gpu` (1 = skip; measured: two host-threaded groups of 8 give 159x vs 159x for one)")
     ap.add_argument("--batch-lookahead", type=int, default=None, help="measurement switch: 0 = the batch scheduler waits for every batch of frames right after queuing it (default: it keeps one batch queued ahead)")
@@ -913,12 +917,19 @@ def main():
                     help="extra figure (N=1 only, after the timed region): utterances in flight on one GPU (0 = skip)")
     ap.add_argument("--no-1p7b", action="store_true")
     ap.add_argument("--no-pmc", action="store_true", help="skip the in-run rocprofv3 --pmc FETCH_SIZE pass (roofline.traffic)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beyond the headline: roofline, parity, batched, 1.7B, configs[3..4], CPU baseline "
+                         "(the --no-* / --batch* / --concurrent / --config3-utterances switches shape this part)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the PCM of rank 0's last timed utterance to DIR/audio.npy (float32)")
     ap.add_argument("--stub", action="store_true", help=argparse.SUPPRESS)
     args = ap.parse_args()
     global BATCH_LOOKAHEAD
     BATCH_LOOKAHEAD = args.batch_lookahead
     if args.gpus < 1:
         raise SystemExit("--gpus must be >= 1")
+    if args.steps < 1:
+        raise SystemExit("--steps must be >= 1")
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         # `python bench.py --gpus N` (no launcher): start the N ranks ourselves -- one process per GPU under torchrun, loopback
         # rendezvous -- and hand their exit code back.  Under torchrun (the driver's N > 1 form) this branch is never taken.
@@ -971,7 +982,8 @@ def main():
         run_one = lambda seed: _stub_utterance(seed)
     else:
         cfg, model = build_model(device, codec_precision=HEADLINE_CODEC)         # every figure: the 1e-3-compliant vocoder
-        _c, model_bf16 = build_model(device, share=model)                        # same weight replica, bf16 vocoder (reported beside the headline)
+        if args.full:
+            _c, model_bf16 = build_model(device, share=model)                    # same weight replica, bf16 vocoder (reported beside the headline)
         req = build_request(cfg, device)
         run_one = lambda seed: one_utterance(model, req, seed)
 
@@ -979,7 +991,7 @@ def main():
     #  concurrent-utterance mode -- profiles/r01_concurrent_streams.txt -- so everything stays on default-priority streams)
     for i in range(args.warmup):
         run_one(1000 + i)
-    if not stub:
+    if not stub and args.full:
         prompt = prepared_prompt(model, req)
         frame_ms, p_mid = measure_frame_graph(model, prompt)
 
@@ -991,9 +1003,12 @@ def main():
         ttfas.append(ttfa); rtfs.append(n * FRAME_S / wall); frames_total += n
     barrier()
     elapsed = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        np.save(os.path.join(args.dump_outputs, "audio.npy"), np.asarray(pcm, dtype=np.float32))
 
     extras = {}
-    solo = world == 1 and not stub and not args.no_extras
+    solo = world == 1 and not stub and not args.no_extras and args.full
 
     def guarded(key, fn):
         try:
@@ -1079,7 +1094,7 @@ def main():
     #      ranks take part), through the public generate_custom_voice_batch ----
     c3 = None
     cfg17 = model17 = None
-    if args.config3_utterances > 0 and args.batch > 1 and not args.no_extras:
+    if args.full and args.config3_utterances > 0 and args.batch > 1 and not args.no_extras:
         from fq3hip.sharding import shard_indices
         mine = shard_indices(args.config3_utterances, rank, world)
         # one wave: as many lanes as this rank has utterances (a lock-step frame costs what its token tiles cost, filled or not)
@@ -1149,7 +1164,7 @@ def main():
             "vs_baseline": None, "dtype": "bf16", "data": "synthetic (seeded random weights at 0.6B shapes incl. text embedding / projection; 200-row ICL prompt built from text + 170 synthetic reference frames)",
             "config": {"workload": "configs[1]: Qwen3-TTS-12Hz-0.6B-Base voice-clone streaming chunk_size=8, hipGraph decode",
                        "vocoder": f"codec_precision={HEADLINE_CODEC!r}: the vocoder mode that meets the 1e-3 PCM bound (parity_pcm); the same run with the "
-                                  "bf16 vocoder is in headline_with_bf16_codec",
+                                  "bf16 vocoder is in headline_with_bf16_codec (--full)",
                        "prompt_tokens": PROMPT_LEN, "ref_frames": REF_FRAMES, "frames_per_utterance": FRAMES,
                        "timed_region": "public generate_voice_clone_streaming(): tokenisation (byte-level stand-in tokenizer: no HF tokenizer "
                                        "offline) + prompt build (HIP) + prefill + decode + streaming vocoder, as the reference times it "
@@ -1201,7 +1216,7 @@ def main():
                 out["model_1p7b"] = model_1p7b_block(cfg17, model17, device, lanes=min(max(args.batch, 8), 128))
             except Exception as e:
                 out["model_1p7b"] = {"error": repr(e)}
-        if world == 1 and not stub and not args.no_cpu_baseline:
+        if args.full and world == 1 and not stub and not args.no_cpu_baseline:
             try:
                 out["cpu_baseline"] = cpu_baseline(cfg)
             except Exception as e:          # the baseline is a reported extra; never lose the GPU line to it

@@ -17,6 +17,8 @@ Pins produced
   decode.npz     reference ``fast_generate`` (generate.py:16-215) and ``fast_generate_streaming``
                  (streaming.py:19-188) run over duck-typed graph objects backed by the oracle's layer
                  math (``torch.cuda.synchronize`` patched to a no-op: the container has no GPU)
+                 -- generated with tests/conftest.py's PINNED_CPU_NUMERICS set in the environment, the
+                 CPU paths test_oracle_pins.py checks these bf16 ids on
   codec.npz      transformers sibling vocoder blocks (CausalConvNet, CausalTransConvNet,
                  ConvNeXtBlock, SnakeBeta, DecoderBlock, Code2WavTransformerModel) + oracle full decode
 """

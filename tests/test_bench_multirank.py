@@ -22,7 +22,7 @@ def _run(world, steps=2):
     env = dict(os.environ, FQ3_BENCH_BACKEND="gloo", HSA_ENABLE_IPC_MODE_LEGACY="0")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={world}", "--master-addr", "127.0.0.1",
            "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"), "--gpus", str(world), "--steps", str(steps),
-           "--warmup", "1", "--stub", "--config3-utterances", "10"]
+           "--warmup", "1", "--stub", "--full", "--config3-utterances", "10"]
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
@@ -62,7 +62,7 @@ def test_bench_gpus_flag_alone_launches_the_ranks():
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--stub",
-           "--config3-utterances", "6"]
+           "--full", "--config3-utterances", "6"]
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
@@ -79,3 +79,28 @@ def test_bench_refuses_a_world_that_contradicts_gpus():
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=300)
     assert r.returncode != 0
     assert not [l for l in r.stdout.splitlines() if l.startswith("{")]
+
+
+def test_plain_run_is_headline_only_and_dumps_the_last_step(tmp_path):
+    """Without --full the line holds the headline alone; --dump-outputs writes the last timed step's PCM, the same on every run."""
+    import numpy as np
+    env = dict(os.environ, FQ3_BENCH_BACKEND="gloo")
+    for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
+        env.pop(k, None)
+    dumps = []
+    for run in range(2):
+        out = tmp_path / f"run{run}"
+        cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--stub",
+               "--dump-outputs", str(out)]
+        r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=300)
+        assert r.returncode == 0, r.stderr[-2000:]
+        lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+        assert len(lines) == 1, r.stdout
+        d = json.loads(lines[0])
+        assert d["steps"] == 3 and d["ms_per_step"] > 0 and d["higher_is_better"] is True and d["dtype"] == "bf16"
+        assert {"metric", "value", "unit"} <= set(d)
+        assert not {"config3_sharded_batched", "roofline", "cpu_baseline", "model_1p7b"} & set(d)
+        a = np.load(out / "audio.npy")
+        assert a.dtype == np.float32 and a.size == 1000 + 2002 % 7          # the stub utterance of the last step (seed 2000 + 2)
+        dumps.append(a)
+    assert np.array_equal(dumps[0], dumps[1])

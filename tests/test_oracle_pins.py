@@ -39,19 +39,36 @@ def test_repetition_penalty_kat():
     assert out[0, 0, 8].item() == pytest.approx(-1.1, rel=1e-6)
 
 
+_DECODE_CASES = """
+import json, numpy as np, torch
+from fq3hip.config import tiny_test_config
+from fq3hip.weights import synth_weights, synth_prompt
+from oracle import qwen3tts_oracle as O
+tag, dt, path = %r, torch.%s, %r
+g = np.load(path)
+cfg = tiny_test_config()
+W = synth_weights(cfg, 0, dt)
+out = []
+for case in range(3):
+    plen, tlen, maxnew, minnew, rp = g[f"params_{tag}_{case}"]
+    tie, tam, tth, tpe, _ = synth_prompt(cfg, int(plen), int(tlen), 0, dtype=dt)
+    orc = O.OracleTTS(cfg, W, max_seq_len=96)
+    orc.pred_sampling = dict(do_sample=False, top_k=0, top_p=1.0, temperature=1.0)
+    sp = O.SamplingParams(max_new_tokens=int(maxnew), min_new_tokens=int(minnew), temperature=1.0, top_k=0,
+                          top_p=1.0, do_sample=False, repetition_penalty=float(rp))
+    out.append(orc.generate(tie, tam, tth, tpe, sp).tolist())
+print(json.dumps(out))
+"""
+
+
 @pytest.mark.parametrize("tag,dt", [("f32", torch.float32), ("bf16", torch.bfloat16)])
-def test_decode_codes_and_chunks(tag, dt, golden_dir):
-    g = np.load(os.path.join(golden_dir, "decode.npz"))
+def test_decode_codes_and_chunks(tag, dt, golden_dir, run_pinned_cpu):
+    path = os.path.join(golden_dir, "decode.npz")
+    g = np.load(path)
     cfg = tiny_test_config()
-    W = synth_weights(cfg, 0, dt)
+    decoded = run_pinned_cpu(_DECODE_CASES % (tag, str(dt).split(".")[1], path))      # decode.npz holds the pinned-path ids
     for case in range(3):
-        plen, tlen, maxnew, minnew, rp = g[f"params_{tag}_{case}"]
-        tie, tam, tth, tpe, _ = synth_prompt(cfg, int(plen), int(tlen), 0, dtype=dt)
-        orc = O.OracleTTS(cfg, W, max_seq_len=96)
-        orc.pred_sampling = dict(do_sample=False, top_k=0, top_p=1.0, temperature=1.0)
-        sp = O.SamplingParams(max_new_tokens=int(maxnew), min_new_tokens=int(minnew), temperature=1.0, top_k=0,
-                              top_p=1.0, do_sample=False, repetition_penalty=float(rp))
-        codes = orc.generate(tie, tam, tth, tpe, sp)
+        codes = torch.tensor(decoded[case], dtype=torch.int64)
         ref = torch.from_numpy(g[f"codes_{tag}_{case}"])
         assert torch.equal(codes, ref)
         # structural validity, reference tests/test_e2e_parity.py:40-101

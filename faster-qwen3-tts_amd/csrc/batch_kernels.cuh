@@ -28,6 +28,7 @@ struct LaneTab {
     int* codes[kMaxLanes];
     unsigned char* seen[kMaxLanes];
     void* past_hidden[kMaxLanes];
+    void* ph_hold[kMaxLanes];         // past_hidden as it was when the lane's loop entered a hold (open text table, frame_begin_body)
 };
 struct LaneSt { DecodeState* st[kMaxLanes]; };                    // the loop states alone (batch poll)
 struct LaneForced { const TeacherForcing* tf[kMaxLanes]; };       // teacher-forcing objects of the lanes (parity tests; null in product use)
@@ -37,7 +38,8 @@ struct LaneTabs { const int* t[kMaxLanes]; int blk_stride; };     // talker: eve
 template <typename T>
 __global__ __launch_bounds__(256) void frame_begin_batch_kernel(const LaneTab* __restrict__ t, const T* codec_emb, T* pred_in, int H, int G) {
     const int l = blockIdx.x;
-    frame_begin_body<T>(gptr(t->st[l]), codec_emb, gptr(reinterpret_cast<const T*>(t->past_hidden[l])), pred_in + (size_t)l * 2 * H,
+    frame_begin_body<T>(gptr(t->st[l]), codec_emb, gptr(reinterpret_cast<const T*>(t->past_hidden[l])),
+                        gptr(reinterpret_cast<T*>(t->ph_hold[l])), pred_in + (size_t)l * 2 * H,
                         gptr(t->codes[l]), gptr(t->seen[l]), H, G);
 }
 

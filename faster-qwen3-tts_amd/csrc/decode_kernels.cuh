@@ -724,7 +724,8 @@ __global__ void copy_kernel(T* dst, const T* src, int n) {
 // per frame; the reference does token.item() every frame, generate.py:150).
 // ================================================================================================
 struct DecodeState {
-    int token, frame, pos, gen_step, done;
+    int token, frame, pos, gen_step, done;       // done: 0 running, 1 finished, 2 held (open text table: the frame's text row has not arrived)
+    int text_open;                               // 0: trailing_text is a fixed table; 1: rows may still arrive (fq3_decode_text_append)
     int min_new, max_new, trailing_len, noise_frames, eos_id, max_seq, sup_lo, sup_hi;
     float t_temperature; int t_top_k; float t_top_p; int t_do_sample; float t_rep_penalty;
     float p_temperature; int p_top_k; float p_top_p; int p_do_sample;
@@ -749,15 +750,33 @@ __device__ __forceinline__ int forced_or(const TeacherForcing* tf, int slot, int
 
 // frame prologue: EOS / limit test, record first-codebook id, history bitmap, predictor input
 // [past_hidden ; embed(token)]  (generate.py:150-159)
+// Open text table (fq3_decode_text_open): a frame whose text row has not been published leaves the loop untouched -- done = 2, which
+// every state-changing kernel of the frame treats like done = 1 -- and the first frame that finds the row there goes on from the same
+// state.  The codec-head GEMV of a held frame still overwrites past_hidden (it runs the stack on a stale input), so the frame that
+// enters the hold copies past_hidden to `ph_hold` and the frame that leaves it takes its predictor input from there.
 template <typename T>
-__device__ __forceinline__ void frame_begin_body(DecodeState* st, const T* codec_emb, const T* past_hidden,
+__device__ __forceinline__ void frame_begin_body(DecodeState* st, const T* codec_emb, const T* past_hidden, T* ph_hold,
                                                  T* pred_in, int* codes, unsigned char* seen, int H, int G) {
-    if (st->done) return;
+    const int done = st->done;
+    if (done == 1) return;
     const int tok = st->token;
     if (tok == st->eos_id || st->frame >= st->max_new) {
         __syncthreads();
         if (threadIdx.x == 0) st->done = 1;
         return;
+    }
+    if (st->text_open && st->gen_step >= st->trailing_len) {
+        if (done == 0) {
+            for (int e = threadIdx.x; e < H; e += 256) ph_hold[e] = past_hidden[e];
+            __syncthreads();
+            if (threadIdx.x == 0) st->done = 2;
+        }
+        return;
+    }
+    if (done == 2) {
+        past_hidden = ph_hold;
+        __syncthreads();
+        if (threadIdx.x == 0) st->done = 0;
     }
     if (threadIdx.x == 0) { codes[(size_t)st->frame * G] = tok; seen[tok] = 1; }
     for (int e = threadIdx.x; e < H; e += 256) {
@@ -766,9 +785,9 @@ __device__ __forceinline__ void frame_begin_body(DecodeState* st, const T* codec
     }
 }
 template <typename T>
-__global__ __launch_bounds__(256) void frame_begin_kernel(DecodeState* st, const T* codec_emb, const T* past_hidden,
+__global__ __launch_bounds__(256) void frame_begin_kernel(DecodeState* st, const T* codec_emb, const T* past_hidden, T* ph_hold,
                                                           T* pred_in, int* codes, unsigned char* seen, int H, int G) {
-    frame_begin_body<T>(st, codec_emb, past_hidden, pred_in, codes, seen, H, G);
+    frame_begin_body<T>(st, codec_emb, past_hidden, ph_hold, pred_in, codes, seen, H, G);
 }
 
 // 16-way embedding sum + text/pad embed -> talker input (generate.py:162-171); position limit test

@@ -234,6 +234,7 @@ static int ctx_build(fq3_ctx* c, const fq3_config* cfg, fq3_kv_pool* pool) {
     if ((r = dmalloc(c, &c->act, (size_t)Im * c->esz))) return r;
     if ((r = dmalloc(c, &c->logits, (size_t)Vm * c->esz))) return r;
     if ((r = dmalloc(c, &c->past_hidden, (size_t)t.hidden * c->esz))) return r;
+    if ((r = dmalloc(c, &c->ph_hold, (size_t)t.hidden * c->esz))) return r;
     if ((r = dmalloc(c, &c->pred_in, (size_t)2 * t.hidden * c->esz))) return r;
     if ((r = dmalloc(c, &c->pred_next, (size_t)t.hidden * c->esz))) return r;
     if ((r = dmalloc(c, &c->pred_x, (size_t)p.hidden * c->esz))) return r;
@@ -1046,7 +1047,7 @@ extern "C" int fq3_decode_begin(fq3_ctx* c, const fq3_decode_params* p, void* st
     // the blocks the loop can reach: frame f appends slot prefill_len + f, the loop stops at max_new_tokens or at max_seq_len - 1
     if (int r = fq3_kv_ensure_(c, p->prefill_len + p->max_new_tokens + 1, s)) return r;
     DecodeState h{};
-    h.token = p->first_token; h.frame = 0; h.pos = p->prefill_len; h.gen_step = p->gen_step; h.done = 0;
+    h.token = p->first_token; h.frame = 0; h.pos = p->prefill_len; h.gen_step = p->gen_step; h.done = 0; h.text_open = 0;
     h.min_new = p->min_new_tokens; h.max_new = p->max_new_tokens; h.trailing_len = p->trailing_len;
     h.noise_frames = p->noise_frames > 0 ? p->noise_frames : 1;
     h.eos_id = c->cfg.codec_eos_token_id; h.max_seq = c->cfg.max_seq_len;
@@ -1062,6 +1063,8 @@ extern "C" int fq3_decode_begin(fq3_ctx* c, const fq3_decode_params* p, void* st
     hipLaunchKernelGGL(decode_arm_kernel, dim3(1), dim3(256), 0, s, c->st, h, c->seen, (int)kMaxVocab,
                        (uint32_t*)c->past_hidden, (const uint32_t*)p->past_hidden, (int)((size_t)c->cfg.talker.hidden * c->esz / 4));
     LAUNCH_CHECK();
+    c->armed = true; c->tt_open = false; c->tt_session = false; c->tt_rows = 0; c->tt_cap = 0;
+    c->begin_trailing = p->trailing_text; c->begin_trailing_len = p->trailing_len > 0 ? p->trailing_len : 0;
     return FQ3_OK;
 }
 
@@ -1093,7 +1096,7 @@ static int enqueue_frame_t(fq3_ctx* c, hipStream_t s) {
     const int G = c->cfg.num_code_groups, H = t.hidden;
     DecodeState* st = c->st;
     hipLaunchKernelGGL((frame_begin_kernel<T>), dim3(1), dim3(256), 0, s, st, (const T*)c->wt.codec_embedding,
-                       (const T*)c->past_hidden, (T*)c->pred_in, c->codes, c->seen, H, G);
+                       (const T*)c->past_hidden, (T*)c->ph_hold, (T*)c->pred_in, c->codes, c->seen, H, G);
     if (int r = predictor_passes_t<T>(c, st, c->pred_in, nullptr, nullptr, nullptr, s)) return r;
     EmbTables tabs{};
     tabs.t[0] = c->wt.codec_embedding;
@@ -1150,7 +1153,7 @@ extern "C" int fq3_decode_poll(fq3_ctx* c, int* n_frames_total, int* done, void*
     HIPCHK(hipMemcpyAsync(&h, c->st, sizeof h, hipMemcpyDeviceToHost, s));
     HIPCHK(hipStreamSynchronize(s));
     if (n_frames_total) *n_frames_total = h.frame;
-    if (done) *done = h.done || h.token == h.eos_id;
+    if (done) *done = h.done == 2 ? 2 : (h.done || h.token == h.eos_id);      // 2: held on an open text table (fq3_decode_text_open)
     return FQ3_OK;
 }
 

@@ -258,6 +258,7 @@ static int batch_create_(fq3_ctx* const* lanes, int n_lanes, fq3_batch** out, bo
     for (int l = 0; l < B; ++l) {
         fq3_ctx* c = lanes[l];
         b->tab.st[l] = c->st; b->tab.codes[l] = c->codes; b->tab.seen[l] = c->seen; b->tab.past_hidden[l] = c->past_hidden;
+        b->tab.ph_hold[l] = c->ph_hold;
         b->lst.st[l] = c->st;
     }
     b->tkv.resize(t.n_layers); b->pkv.resize(p.n_layers);
@@ -823,7 +824,7 @@ __global__ void poll_gather_kernel(LaneSt t, int B, int* out) {
     if (l < B) {
         const DecodeState* st = t.st[l];
         out[2 * l] = st->frame;
-        out[2 * l + 1] = (st->done || st->token == st->eos_id) ? 1 : 0;          // fq3_decode_poll's `done`
+        out[2 * l + 1] = st->done == 2 ? 2 : ((st->done || st->token == st->eos_id) ? 1 : 0);      // fq3_decode_poll's `done`
     }
 }
 }

@@ -82,6 +82,15 @@ struct fq3_ctx {
     bool pw_bound = false;
     void *pw_x = nullptr, *pw_h = nullptr;
     int pw_cap = 0;
+    // open text table of the decode loop (fq3_decode_text_open / _append): the table and the append's own projection workspaces are
+    // owned by the context and sized at open; rows / closed are the host's bookkeeping of what has been QUEUED (stream order publishes it)
+    void* ph_hold = nullptr;          // past_hidden as it was when the loop entered a hold (frame_begin_body)
+    void *tt_tab = nullptr, *tt_x = nullptr, *tt_h = nullptr;
+    int tt_alloc = 0;                 // rows the three buffers above hold
+    int tt_cap = 0, tt_rows = 0;      // this session's capacity / rows appended so far (fq3_decode_begin's rows included)
+    bool tt_open = false, tt_session = false;      // table open for appends / a table was opened since the last fq3_decode_begin
+    bool armed = false;               // fq3_decode_begin has run
+    const void* begin_trailing = nullptr; int begin_trailing_len = 0;      // what fq3_decode_begin was given
     // MFMA prefill workspace (lazily allocated, sized for max_seq_len rows)
     void *pf_x = nullptr, *pf_xn = nullptr, *pf_qkv = nullptr, *pf_att = nullptr, *pf_gu = nullptr, *pf_act = nullptr, *pf_ws = nullptr;
 };

@@ -122,6 +122,10 @@ SIGNATURES = {
     "fq3_graph_reset": (C.c_int, [vp]),
     "fq3_bind_prompt_weights": (C.c_int, [vp, C.POINTER(PromptWeights)]),
     "fq3_text_project": (C.c_int, [vp, vp, C.c_int, vp, vp]),
+    "fq3_decode_text_open": (C.c_int, [vp, C.c_int, vp]),
+    "fq3_decode_text_append": (C.c_int, [vp, vp, C.c_int, C.c_int, vp]),
+    "fq3_decode_text_rows": (C.c_int, [vp, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "fq3_decode_text_read": (C.c_int, [vp, C.c_int, C.c_int, vp, vp]),
     "fq3_prompt_rows": (C.c_int, [vp, vp, C.c_int, vp, C.c_int, vp, C.c_int, vp, vp, vp]),
     "fq3_batch_create": (C.c_int, [C.POINTER(vp), C.c_int, C.POINTER(vp)]),
     "fq3_batch_destroy": (C.c_int, [vp]),

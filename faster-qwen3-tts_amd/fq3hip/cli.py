@@ -5,7 +5,8 @@
 ``--voice-cache DIR`` serves ``--ref-audio`` from precomputed voice prompts (``fq3hip/voice_cache.py``), because
 reference-audio analysis is not part of this path; ``--synthetic 0.6b|1.7b`` builds seeded random weights instead of
 loading a checkpoint (smoke runs, throughput measurements); ``serve --lanes N`` decodes up to N queued lines in lock-step
-(``fq3_batch_*``); GGML flags are accepted and refused like the wrapper refuses them."""
+(``fq3_batch_*``); ``custom`` / ``design --text-stdin`` read the text from stdin AS IT ARRIVES, line by line, and decode behind it
+(``FasterQwen3TTS.stream_custom_voice`` / ``stream_voice_design``); GGML flags are accepted and refused like the wrapper refuses them."""
 from __future__ import annotations
 
 import argparse
@@ -67,6 +68,26 @@ def _gen_kwargs(args):
                 repetition_penalty=args.repetition_penalty)
 
 
+def _stdin_pieces(lines=None):
+    """Lines as they arrive (``readline``: iterating a pipe would wait for a full read-ahead buffer)."""
+    if lines is not None:
+        yield from lines
+        return
+    while True:
+        line = sys.stdin.readline()
+        if not line:
+            return
+        yield line
+
+
+def synthesize_text_stream(model, args, pieces):
+    """``--text-stdin``: the text is fed while it arrives -> (waveform, sample_rate)."""
+    kw = dict(chunk_size=args.chunk_size, **_gen_kwargs(args))
+    if args.mode == "custom":
+        return _stream_to_audio(model.stream_custom_voice(pieces, speaker=args.speaker, language=args.language, instruct=args.instruct, **kw))
+    return _stream_to_audio(model.stream_voice_design(pieces, instruct=args.instruct, language=args.language, **kw))
+
+
 def synthesize(model, args, text: str):
     """One text -> (waveform, sample_rate) in the selected mode (``cli.py:81-225``)."""
     kw = _gen_kwargs(args)
@@ -101,12 +122,16 @@ def _check_mode_args(args):
         sys.exit(2)
 
 
-def cmd_once(args, model=None):
+def cmd_once(args, model=None, lines=None):
     from .audio_io import write_wav
     _check_mode_args(args)
+    text_stdin = bool(getattr(args, "text_stdin", False))
+    if text_stdin == (args.text is not None):
+        print("ERROR: give either --text or --text-stdin")
+        sys.exit(2)
     model = model or load_model(args)
     start = time.perf_counter()
-    audio, sr = synthesize(model, args, args.text)
+    audio, sr = synthesize_text_stream(model, args, _stdin_pieces(lines)) if text_stdin else synthesize(model, args, args.text)
     total = time.perf_counter() - start
     write_wav(args.output, audio, sr)
     dur = len(audio) / sr if sr else 0.0
@@ -166,7 +191,7 @@ def build_parser():
     p.add_argument("--voice-cache", help="directory of precomputed voice prompts (<key>.spk/.rvq/.json) serving --ref-audio")
     sub = p.add_subparsers(dest="command", required=True)
 
-    def common(sp, output=True):
+    def common(sp, output=True, text_stdin=False):
         sp.add_argument("--model", default="Qwen/Qwen3-TTS-12Hz-0.6B-Base", help="local checkpoint directory")
         sp.add_argument("--language", default="English")
         sp.add_argument("--max-new-tokens", type=int, default=2048)
@@ -177,7 +202,10 @@ def build_parser():
         sp.add_argument("--streaming", action="store_true")
         sp.add_argument("--chunk-size", type=int, default=12)
         if output:
-            sp.add_argument("--text", required=True)
+            sp.add_argument("--text", required=not text_stdin)
+            if text_stdin:
+                sp.add_argument("--text-stdin", action="store_true",
+                                help="read the text from stdin as it arrives (line by line) and decode behind it")
             sp.add_argument("--output", required=True)
 
     def clone_refs(sp):
@@ -191,9 +219,9 @@ def build_parser():
     c = sub.add_parser("clone", help="voice cloning from reference audio")
     common(c); clone_refs(c); c.set_defaults(mode="clone", func=cmd_once)
     c = sub.add_parser("custom", help="CustomVoice model: predefined speaker")
-    common(c); c.add_argument("--speaker"); c.add_argument("--instruct"); c.set_defaults(mode="custom", func=cmd_once)
+    common(c, text_stdin=True); c.add_argument("--speaker"); c.add_argument("--instruct"); c.set_defaults(mode="custom", func=cmd_once)
     c = sub.add_parser("design", help="VoiceDesign model: voice from an instruction")
-    common(c); c.add_argument("--instruct"); c.set_defaults(mode="design", func=cmd_once)
+    common(c, text_stdin=True); c.add_argument("--instruct"); c.set_defaults(mode="design", func=cmd_once)
     s = sub.add_parser("serve", help="read one text per stdin line, write out_NNNN.wav")
     common(s, output=False); clone_refs(s)
     s.add_argument("--mode", default="clone", choices=["clone", "custom", "design"])

@@ -438,6 +438,46 @@ class Fq3Engine:
         L.check(self.lib.fq3_decode_poll(self.ctx, C.byref(n), C.byref(d), self._stream()))
         return n.value, bool(d.value)
 
+    def decode_poll_state(self):
+        """``(frames, state)`` with the loop's state as an int: 0 running, 1 finished, 2 held on an open text table (the next frame's
+        text row has not been appended).  ``decode_poll`` folds 2 into True."""
+        n, d = C.c_int(0), C.c_int(0)
+        L.check(self.lib.fq3_decode_poll(self.ctx, C.byref(n), C.byref(d), self._stream()))
+        return n.value, int(d.value)
+
+    # ---- incremental text (fq3hip/text_stream.py) ----
+    def decode_text_open(self, capacity_rows: int):
+        """After ``decode_begin``: the loop's trailing-text table becomes an open table of ``capacity_rows`` rows owned by the context
+        (``fq3_decode_text_open``); the rows ``decode_begin`` was given are copied in."""
+        L.check(self.lib.fq3_decode_text_open(self.ctx, int(capacity_rows), self._stream()))
+
+    def decode_text_append(self, ids, final: bool = False):
+        """Project token ids (a list or LongTensor) into the next rows of the open table and publish them in stream order
+        (``fq3_decode_text_append``); ``final`` closes the table.  The id tensor is kept alive until the next append."""
+        if isinstance(ids, torch.Tensor):
+            t = ids.reshape(-1).to(device=self.device, dtype=torch.long).contiguous()
+        else:
+            t = torch.tensor([int(i) for i in ids], dtype=torch.long, device=self.device)
+        n = int(t.numel())
+        # torch's caching allocator hands a freed block back to the same stream only, so the previous tensor may go once this one is queued
+        L.check(self.lib.fq3_decode_text_append(self.ctx, t.data_ptr() if n else None, n, int(bool(final)), self._stream()))
+        self._text_ids_keep = t
+
+    def decode_text_rows(self):
+        """``(rows appended so far, closed)``: host-side bookkeeping, no device round trip."""
+        n, c = C.c_int(0), C.c_int(0)
+        L.check(self.lib.fq3_decode_text_rows(self.ctx, C.byref(n), C.byref(c)))
+        return n.value, bool(c.value)
+
+    def decode_text_read(self, start: int = 0, count: Optional[int] = None) -> torch.Tensor:
+        """A copy of rows ``[start, start + count)`` of the open table (default: every row appended so far), taken in stream order
+        (``fq3_decode_text_read``: tests, tools)."""
+        if count is None:
+            count = self.decode_text_rows()[0] - int(start)
+        out = self.new(int(count), self.cfg.talker.hidden_size)
+        L.check(self.lib.fq3_decode_text_read(self.ctx, int(start), int(count), out.data_ptr(), self._stream()))
+        return out
+
     def decode_codes(self, start: int, count: int) -> torch.Tensor:
         out = torch.empty(count, self.cfg.num_code_groups, dtype=torch.long, device=self.device)
         if count:
@@ -509,6 +549,14 @@ class Fq3Batch:
         a, d = (C.c_int * n)(), (C.c_int * n)()
         L.check(self.lib.fq3_batch_poll_wait(self.handle, int(slot), a, d))
         return list(a), [bool(x) for x in d]
+
+    def poll_wait_states(self, slot: int):
+        """``poll_wait`` with the lanes' states as ints: 0 running, 1 finished, 2 held on an open text table (``decode_text_open``:
+        the lane's next text row has not been appended; it goes on once it has).  ``poll_wait`` folds 2 into True."""
+        n = len(self.lanes)
+        a, d = (C.c_int * n)(), (C.c_int * n)()
+        L.check(self.lib.fq3_batch_poll_wait(self.handle, int(slot), a, d))
+        return list(a), [int(x) for x in d]
 
     def set_group_streams(self, streams):
         """``fq3_batch_set_group_streams``: the caller's own side streams for lane groups 1.. (kept alive here)."""

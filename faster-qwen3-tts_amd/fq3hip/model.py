@@ -10,6 +10,7 @@ decode loop state lives on the GPU.
 from __future__ import annotations
 
 import logging
+import time
 from pathlib import Path
 from typing import Any, Dict, Generator, List, Optional, Tuple, Union
 
@@ -715,8 +716,9 @@ class FasterQwen3TTS:
 
     def _prepare_generation(self, text: str, ref_audio=None, ref_text: str = "", language: str = "English",
                             xvec_only: bool = False, non_streaming_mode: bool = False, append_silence: bool = True,
-                            voice_clone_prompt=None, instruct: Optional[str] = None):
-        input_ids = self.model._tokenize_texts([self.model._build_assistant_text(text)])
+                            voice_clone_prompt=None, instruct: Optional[str] = None, input_ids=None):
+        if input_ids is None:
+            input_ids = self.model._tokenize_texts([self.model._build_assistant_text(text)])
         instruct_ids = [None]
         if instruct:
             instruct_ids = [self.model._tokenize_texts([self.model._build_instruct_text(instruct)])[0]]
@@ -737,8 +739,9 @@ class FasterQwen3TTS:
         return m, talker, config, tie, tam, tth, tpe, ref_codes
 
     def _prepare_generation_custom(self, text: str, language: str, speaker: Optional[str],
-                                   instruct: Optional[str] = None, non_streaming_mode: bool = True):
-        input_ids = self.model._tokenize_texts([self.model._build_assistant_text(text)])
+                                   instruct: Optional[str] = None, non_streaming_mode: bool = True, input_ids=None):
+        if input_ids is None:
+            input_ids = self.model._tokenize_texts([self.model._build_assistant_text(text)])
         instruct_ids = [None if not instruct else
                         self.model._tokenize_texts([self.model._build_instruct_text(instruct)])[0]]
         m = self.model.model
@@ -1254,7 +1257,7 @@ class FasterQwen3TTS:
                                        self._gen_kwargs(max_new_tokens, min_new_tokens, temperature, top_k, top_p,
                                                         do_sample, repetition_penalty), chunk_size, parity_mode)
 
-    def _custom_prepare(self, text, speaker, language, instruct, non_streaming_mode):
+    def _custom_prepare(self, text, speaker, language, instruct, non_streaming_mode, input_ids=None):
         if self.model.model.tts_model_type != "custom_voice":
             raise ValueError("Loaded model does not support custom voice generation")
         self.model._validate_languages([language])
@@ -1263,7 +1266,7 @@ class FasterQwen3TTS:
         if self.model.model.tts_model_size in "0b6":        # 0.6B CustomVoice ignores instruct (model.py:1166-1167)
             instruct = None
         return self._prepare_generation_custom(text=text, language=language, speaker=speaker, instruct=instruct,
-                                               non_streaming_mode=nsm)
+                                               non_streaming_mode=nsm, input_ids=input_ids)
 
     @torch.inference_mode()
     def generate_custom_voice(self, text: str, speaker: str, language: str, instruct: Optional[str] = None,
@@ -1286,13 +1289,13 @@ class FasterQwen3TTS:
                                        self._gen_kwargs(max_new_tokens, min_new_tokens, temperature, top_k, top_p,
                                                         do_sample, repetition_penalty), chunk_size)
 
-    def _design_prepare(self, text, instruct, language, non_streaming_mode):
+    def _design_prepare(self, text, instruct, language, non_streaming_mode, input_ids=None):
         if self.model.model.tts_model_type != "voice_design":
             raise ValueError("Loaded model does not support voice design generation")
         self.model._validate_languages([language])
         nsm = self._resolve_non_streaming_mode(non_streaming_mode, default=True)
         return self._prepare_generation_custom(text=text, language=language, speaker=None, instruct=instruct,
-                                               non_streaming_mode=nsm)
+                                               non_streaming_mode=nsm, input_ids=input_ids)
 
     @torch.inference_mode()
     def generate_voice_design(self, text: str, instruct: str, language: str, non_streaming_mode: Optional[bool] = None,
@@ -1314,3 +1317,124 @@ class FasterQwen3TTS:
         yield from self._run_streaming(m, talker, config, tie, tam, tth, tpe, None,
                                        self._gen_kwargs(max_new_tokens, min_new_tokens, temperature, top_k, top_p,
                                                         do_sample, repetition_penalty), chunk_size)
+
+    # ---- incremental text (extension: the reference takes the whole text before it starts; fq3hip/text_stream.py) ---------
+    def _text_tokenize(self):
+        """str -> token ids of a piece of the text BODY (no chat template around it)."""
+        from .native_model import ByteTokenizer
+        tok = self.model.tokenizer
+        if isinstance(tok, ByteTokenizer):
+            return lambda s: tok(s)[3:-5]
+        if callable(getattr(tok, "encode", None)):
+            return lambda s: list(tok.encode(s))
+        return lambda s: list(tok(s)["input_ids"])
+
+    def _text_session_ids(self, feeder):
+        """Waits for the first text token; returns the ``input_ids`` of the step-by-step prompt: the chat template around that one
+        token (``prompt.py`` puts token 3 into the prompt and needs nothing else of the body)."""
+        first, closed = feeder.take(block=True, limit=1)
+        while not first and not closed:
+            first, closed = feeder.take(block=True, limit=1)
+        if not first:
+            raise ValueError("the text stream ended before its first token")
+        shell = self.model._tokenize_texts([self.model._build_assistant_text("")])[0]
+        from .prompt import host_ids
+        ids = host_ids(shell)
+        if len(ids) != 8:
+            raise ValueError(f"the chat template around an empty text must be 3 + 5 tokens, got {len(ids)}")
+        ids = ids[:3] + [int(first[0])] + ids[3:]
+        tt = torch.tensor([ids], dtype=torch.long, device=self.model.device)
+        tt.fq3_host_ids = (list(ids), None if tt.is_inference() else tt._version)
+        return [tt]
+
+    def _run_text_streaming(self, text_iter, prepare, gen_kwargs, chunk_size: int):
+        """Shared back half of the ``stream_*`` entry points: ``prepare(input_ids)`` builds the step-by-step prompt from the first
+        token; the decode loop runs behind the text as it arrives and ``StreamingVocoder`` turns each code chunk into audio."""
+        from .text_stream import TextFeeder, fast_generate_text_streaming, pump_text
+        if isinstance(text_iter, TextFeeder):
+            feeder = text_iter
+        else:
+            if isinstance(text_iter, str):
+                text_iter = [text_iter]
+            feeder = TextFeeder(self._text_tokenize())
+            pump_text(feeder, text_iter)
+        try:
+            m, talker, config, tie, tam, _tth, tpe = prepare(self._text_session_ids(feeder))
+            tok = m.speech_tokenizer
+            voc = StreamingVocoder(tok, None, chunk_size, self.device, self._vocoder_stream(tok))
+            stream = fast_generate_text_streaming(
+                talker=talker, talker_input_embeds=tie, attention_mask=tam, tts_pad_embed=tpe, config=config,
+                predictor_graph=self.predictor_graph, talker_graph=self.talker_graph, feeder=feeder,
+                tts_eos_id=int(m.config.tts_eos_token_id), chunk_size=chunk_size, **gen_kwargs)
+            for chunk, timing in stream:
+                ev = timing.pop("codes_ready_event", None)
+                new_audio, sr = voc.push(chunk, ev)
+                if "first_text_ms" in timing:
+                    timing["first_text_ms"] = (time.time() - feeder.t_first) * 1000      # first piece received -> first audio
+                yield new_audio, sr, timing
+        finally:
+            # a consumer that went away: stop the loop at the next frame boundary (frames of the look-ahead may be queued)
+            eng = self.talker_graph.engine
+            if torch.cuda.is_available() and getattr(eng, "ctx", None):
+                eng.decode_cancel()
+
+    @torch.inference_mode()
+    def stream_custom_voice(self, text_iter, speaker: str, language: str, instruct: Optional[str] = None, chunk_size: int = 12,
+                            max_new_tokens: int = 2048, min_new_tokens: int = 2, temperature: float = 0.9, top_k: int = 50,
+                            top_p: float = 1.0, do_sample: bool = True,
+                            repetition_penalty: float = 1.05) -> Generator[Tuple[np.ndarray, int, dict], None, None]:
+        """``generate_custom_voice_streaming(..., non_streaming_mode=False)`` for a text that is still arriving: ``text_iter`` is any
+        iterable of ``str`` pieces (a generator driven by an LLM client, a queue reader) or a ``TextFeeder``.  Decoding starts at
+        the first complete word; codes and audio are those of the whole text, whatever the cuts.  The first chunk's timing has
+        ``first_text_ms`` (first piece received -> first audio)."""
+        def prepare(input_ids):
+            m, talker, config, tie, tam, tth, tpe = self._custom_prepare(None, speaker, language, instruct, False, input_ids=input_ids)
+            return m, talker, config, tie, tam, tth, tpe
+        yield from self._run_text_streaming(text_iter, prepare,
+                                            self._gen_kwargs(max_new_tokens, min_new_tokens, temperature, top_k, top_p, do_sample,
+                                                             repetition_penalty), chunk_size)
+
+    @torch.inference_mode()
+    def stream_voice_design(self, text_iter, instruct: str, language: str, chunk_size: int = 12, max_new_tokens: int = 2048,
+                            min_new_tokens: int = 2, temperature: float = 0.9, top_k: int = 50, top_p: float = 1.0,
+                            do_sample: bool = True,
+                            repetition_penalty: float = 1.05) -> Generator[Tuple[np.ndarray, int, dict], None, None]:
+        """``generate_voice_design_streaming(..., non_streaming_mode=False)`` for a text that is still arriving (see
+        ``stream_custom_voice``)."""
+        def prepare(input_ids):
+            return self._design_prepare(None, instruct, language, False, input_ids=input_ids)
+        yield from self._run_text_streaming(text_iter, prepare,
+                                            self._gen_kwargs(max_new_tokens, min_new_tokens, temperature, top_k, top_p, do_sample,
+                                                             repetition_penalty), chunk_size)
+
+    @torch.inference_mode()
+    def stream_voice_clone(self, text_iter, language: str, ref_audio: Optional[Union[str, Path]] = None, chunk_size: int = 12,
+                           max_new_tokens: int = 2048, min_new_tokens: int = 2, temperature: float = 0.9, top_k: int = 50,
+                           top_p: float = 1.0, do_sample: bool = True, repetition_penalty: float = 1.05, xvec_only: bool = True,
+                           append_silence: bool = True, instruct: Optional[str] = None,
+                           voice_clone_prompt: Optional[Union[Dict[str, Any], List[Any]]] = None,
+                           ) -> Generator[Tuple[np.ndarray, int, dict], None, None]:
+        """``generate_voice_clone_streaming(..., non_streaming_mode=False)`` for a text that is still arriving, for x-vector-only
+        voices.  An ICL voice (reference codes + reference text) is refused: there the text is laid against the reference frames
+        inside the prompt, so the prefill itself needs the whole text."""
+        why = ("incremental text needs an x-vector-only voice: an ICL clone lays the text against the reference frames inside the "
+               "prompt, so the prefill needs the whole text (use generate_voice_clone_streaming)")
+        if not xvec_only and voice_clone_prompt is None:
+            raise ValueError(why)
+        if isinstance(voice_clone_prompt, list) and any(bool(it.icl_mode) for it in voice_clone_prompt):
+            raise ValueError(why)
+        if isinstance(voice_clone_prompt, dict):
+            icl = voice_clone_prompt.get("icl_mode", [not bool(v) for v in voice_clone_prompt.get("x_vector_only_mode", [True])])
+            if any(bool(v) for v in icl):
+                raise ValueError(why)
+
+        def prepare(input_ids):
+            m, talker, config, tie, tam, tth, tpe, rc = self._prepare_generation(
+                text=None, language=language, ref_audio=ref_audio, ref_text="", xvec_only=True, non_streaming_mode=False,
+                append_silence=append_silence, voice_clone_prompt=voice_clone_prompt, instruct=instruct, input_ids=input_ids)
+            if rc is not None:
+                raise ValueError(why)
+            return m, talker, config, tie, tam, tth, tpe
+        yield from self._run_text_streaming(text_iter, prepare,
+                                            self._gen_kwargs(max_new_tokens, min_new_tokens, temperature, top_k, top_p, do_sample,
+                                                             repetition_penalty), chunk_size)

@@ -252,7 +252,8 @@ int fq3_decode_set_forced(fq3_ctx* ctx, const int32_t* forced_codes, int32_t* de
  * fq3_graph_capture() has run (talker_graph.py:109-147, predictor_graph.py:169-202), otherwise the
  * same kernels are launched directly.  Frames after EOS / limits are no-ops on device. */
 int fq3_decode_frames(fq3_ctx* ctx, int n_frames, void* stream);
-/* Synchronises the stream and reports: frames emitted so far, done flag; copies codes
+/* Synchronises the stream and reports: frames emitted so far, done flag (0 running, 1 finished; 2 = held: the loop has an open
+ * text table -- fq3_decode_text_open -- and the next frame's text row has not been appended; it goes on once it has); copies codes
  * int64[n, 16] for frames [from, n_frames_total) into out_codes (host or device memory visible to host). */
 int fq3_decode_poll(fq3_ctx* ctx, int* n_frames_total, int* done, void* stream);
 int fq3_decode_codes(fq3_ctx* ctx, int from, int count, int64_t* out_codes_dev, void* stream);
@@ -282,6 +283,25 @@ int fq3_text_project(fq3_ctx* ctx, const int64_t* ids, int n, void* out, void* s
  * out[r] = text part + codec part (one rounding), or the single part that is present. */
 int fq3_prompt_rows(fq3_ctx* ctx, const void* text_rows, int n_text, const int32_t* prog, int n_rows,
                     const int64_t* ref_codes, int n_ref, const void* spk_embed, void* out, void* stream);
+
+/* ---- incremental text: the loop's text table grows while it decodes --------------------------------------------------
+ * In the step-by-step layout frame g adds row g of the trailing table to the talker's input, and a row is a function of its
+ * token id alone, so frame g needs text token g + 1 and nothing later.  An open table lets the rows arrive while the loop runs;
+ * a frame whose row has not been published yet leaves the loop untouched (fq3_decode_poll / fq3_batch_poll_wait report done = 2
+ * for such a loop) and the next frame queued after the append goes on from the same state: the codes are those of the whole table.
+ *
+ * After fq3_decode_begin: the loop's text table becomes an open table of `capacity_rows` rows owned by the context; the
+ * rows fq3_decode_begin was given (possibly none) are copied in.  FQ3_ESTATE without prompt weights or before begin. */
+int fq3_decode_text_open(fq3_ctx* ctx, int capacity_rows, void* stream);
+/* ids int64[n] on the device -> n more rows (text_projection(text_embedding(id))), published in stream order.
+ * final != 0 closes the table (the caller's last id is tts_eos: prompt.py:125); n == 0 is allowed with final.
+ * FQ3_EINVAL past the capacity (nothing is written), FQ3_ESTATE when the table is not open. */
+int fq3_decode_text_append(fq3_ctx* ctx, const int64_t* ids, int n, int final, void* stream);
+/* rows appended so far / whether the table is closed (host-side bookkeeping, no device round trip) */
+int fq3_decode_text_rows(const fq3_ctx* ctx, int* n_rows, int* closed);
+/* copies rows [from, from + count) of the table, T[count, H], to `out` on the device in stream order (tests and tools that
+ * compare rows; the loop reads the table through its own state).  FQ3_EINVAL beyond the rows appended so far. */
+int fq3_decode_text_read(fq3_ctx* ctx, int from, int count, void* out, void* stream);
 
 /* ---- batched decode: B utterances in lock-step over one weight stream ------------------------------
  * No reference equivalent (the reference fixes batch = 1: talker_graph.py:46, predictor_graph.py:70; SURVEY.md

@@ -80,6 +80,10 @@ struct fq3_batch {
     int* poll_host = nullptr;                   // pinned, same layout
     hipEvent_t poll_ev[4] = {nullptr, nullptr, nullptr, nullptr};
     bool poll_armed[4] = {false, false, false, false};
+    // ---- fq3_batch_text_append: ONE projection over the rows of all lanes (gathered ids, fc1 output, projected rows), grown like the
+    // prompt builder's pw_x / pw_h (the old buffers stay owned by the batch: launches still in flight may read them)
+    void *ta_x = nullptr, *ta_h = nullptr, *ta_y = nullptr;
+    int ta_cap = 0;
 };
 constexpr int kPollSlots = 4;
 
@@ -859,6 +863,97 @@ extern "C" int fq3_batch_poll_wait(fq3_batch* b, int slot, int* n_frames_total, 
     for (int l = 0; l < b->B; ++l) {
         if (n_frames_total) n_frames_total[l] = h[2 * l];
         if (done) done[l] = h[2 * l + 1];
+    }
+    return FQ3_OK;
+}
+
+// ---- incremental text for all lanes at once (fq3hip.h: fq3_batch_text_append) ------------------------------------------------------
+// The single-lane append (fq3_prompt.hip) costs four launches per lane and streams text_projection's matrices once per lane.  Here the
+// ids of every lane are projected by ONE gather + ONE fc1 + ONE fc2 into a packed [N][H] buffer; one launch scatters row r to its
+// lane's table and one publishes the new lengths.  Rows before lengths, stream order the only synchronisation -- as in the single lane.
+namespace {
+struct AppendDst { void* dst[kMaxLanes]; int first[kMaxLanes + 1]; };        // item i: packed rows [first[i], first[i + 1]) -> dst[i]
+struct AppendPub { DecodeState* st[kMaxLanes]; int rows[kMaxLanes]; int closes[kMaxLanes]; };
+// one workgroup per packed row, 16-byte pieces (a row is H elements, H a multiple of 32: fq3_bind_prompt_weights)
+__global__ __launch_bounds__(256) void text_scatter_kernel(AppendDst a, int n_items, const u32x4* y, int row_vec) {
+    const int r = blockIdx.x;
+    int lo = 0, hi = n_items - 1;                          // the last item whose first row is <= r (items without rows never match)
+    while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if (a.first[mid] <= r) lo = mid; else hi = mid - 1;
+    }
+    u32x4* d = gptr(reinterpret_cast<u32x4*>(a.dst[lo])) + (size_t)(r - a.first[lo]) * row_vec;
+    const u32x4* src = y + (size_t)r * row_vec;
+    for (int e = threadIdx.x; e < row_vec; e += 256) d[e] = src[e];
+}
+__global__ __launch_bounds__(kMaxLanes) void text_publish_lanes_kernel(AppendPub p, int n_items) {
+    const int i = threadIdx.x;
+    if (i < n_items) {
+        DecodeState* st = gptr(p.st[i]);
+        st->trailing_len = p.rows[i];
+        if (p.closes[i]) st->text_open = 0;
+    }
+}
+}  // namespace
+
+extern "C" int fq3_batch_text_append(fq3_batch* b, int n_items, const int32_t* lane, const int32_t* count, const int32_t* final_,
+                                     const int64_t* ids, void* stream) {
+    if (!b) return fq3_fail_(FQ3_EINVAL, "null batch");
+    if (n_items < 0 || n_items > b->B) return fq3_fail_(FQ3_EINVAL, "n_items must be 0..fq3_batch_size");
+    if (n_items == 0) return FQ3_OK;
+    if (!lane || !count || !final_) return fq3_fail_(FQ3_EINVAL, "null argument");
+    // all or nothing: every item is checked before anything is queued or any bookkeeping changes
+    bool named[kMaxLanes] = {};
+    long total = 0;
+    for (int i = 0; i < n_items; ++i) {
+        if (lane[i] < 0 || lane[i] >= b->B) return fq3_fail_(FQ3_EINVAL, "lane index out of range");
+        if (named[lane[i]]) return fq3_fail_(FQ3_EINVAL, "a lane may be named once per call");
+        named[lane[i]] = true;
+        if (count[i] < 0 || (count[i] == 0 && !final_[i])) return fq3_fail_(FQ3_EINVAL, "every item needs ids, or final with no ids");
+        total += count[i];
+    }
+    for (int i = 0; i < n_items; ++i)
+        if (!b->lanes[lane[i]]->tt_open) return fq3_fail_(FQ3_ESTATE, "a named lane's text table is not open");
+    for (int i = 0; i < n_items; ++i) {
+        const fq3_ctx* c = b->lanes[lane[i]];
+        if (count[i] > c->tt_cap - c->tt_rows) return fq3_fail_(FQ3_EINVAL, "append past the capacity of a lane's text table");
+    }
+    if (total > 0 && !ids) return fq3_fail_(FQ3_EINVAL, "null ids");
+    fq3_ctx* c0 = b->lanes[lane[0]];                       // (an open table implies bound prompt weights; the lanes share one replica)
+    const int Ht = c0->pw.text_hidden, H = c0->cfg.talker.hidden, esz = c0->esz;
+    const int N = (int)total;
+    if (N > b->ta_cap) {
+        // outside the sizes seen so far: new buffers (a device allocation waits for the device -- 256 rows up front keep that out of a
+        // running batch for the appends a scheduler makes, a few ids per lane per poll)
+        const int cap = (N + 255) / 256 * 256;
+        void *x = nullptr, *h = nullptr, *y = nullptr;
+        if (int r = bmalloc(b, &x, (size_t)cap * Ht * esz)) return r;
+        if (int r = bmalloc(b, &h, (size_t)cap * Ht * esz)) return r;
+        if (int r = bmalloc(b, &y, (size_t)cap * H * esz)) return r;
+        b->ta_x = x; b->ta_h = h; b->ta_y = y; b->ta_cap = cap;
+    }
+    hipStream_t s = (hipStream_t)stream;
+    AppendDst d{};
+    AppendPub p{};
+    int first = 0;
+    for (int i = 0; i < n_items; ++i) {
+        fq3_ctx* c = b->lanes[lane[i]];
+        d.dst[i] = (char*)c->tt_tab + (size_t)c->tt_rows * H * esz;
+        d.first[i] = first;
+        first += count[i];
+        p.st[i] = c->st; p.rows[i] = c->tt_rows + count[i]; p.closes[i] = final_[i] ? 1 : 0;
+    }
+    d.first[n_items] = first;
+    if (N > 0) {
+        fq3_text_project_launch_(c0, ids, N, b->ta_x, b->ta_h, b->ta_y, s);
+        hipLaunchKernelGGL(text_scatter_kernel, dim3(N), dim3(256), 0, s, d, n_items, (const u32x4*)b->ta_y, H * esz / 16);
+    }
+    hipLaunchKernelGGL(text_publish_lanes_kernel, dim3(1), dim3(kMaxLanes), 0, s, p, n_items);
+    HIPCHK(hipGetLastError());
+    for (int i = 0; i < n_items; ++i) {
+        fq3_ctx* c = b->lanes[lane[i]];
+        c->tt_rows += count[i];
+        if (final_[i]) c->tt_open = false;
     }
     return FQ3_OK;
 }

@@ -115,3 +115,4 @@ int fq3_prefill_batch_mfma_(fq3_ctx* const* cs, int n, const void* const* embeds
                             void* const* out_hidden, hipStream_t s);
 int fq3_codec_head_launch_(fq3_ctx* c, const void* hidden, void* out_logits, hipStream_t s);
 int fq3_dmalloc_(fq3_ctx* c, void** p, size_t bytes);
+void fq3_text_project_launch_(fq3_ctx* c, const int64_t* ids, int n, void* x, void* h, void* out, hipStream_t s);

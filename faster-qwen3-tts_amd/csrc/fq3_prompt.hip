@@ -120,6 +120,13 @@ __global__ void text_publish_kernel(DecodeState* st, int rows, int final) {
 
 }  // namespace
 
+// text_projection(text_embedding(ids)) into out[n][H] over the caller's workspaces x, h (n rows of text_hidden each): the launches of
+// fq3_text_project / fq3_decode_text_append, for fq3_batch_text_append (fq3_batch.hip)
+void fq3_text_project_launch_(fq3_ctx* c, const int64_t* ids, int n, void* x, void* h, void* out, hipStream_t s) {
+    if (c->cfg.dtype == FQ3_BF16) text_project_launch<bf16_t>(c, ids, n, x, h, out, s);
+    else text_project_launch<float>(c, ids, n, x, h, out, s);
+}
+
 extern "C" int fq3_bind_prompt_weights(fq3_ctx* c, const fq3_prompt_weights* w) {
     if (!c || !w) return fq3_fail_(FQ3_EINVAL, "null argument");
     if (!w->text_embedding || !w->fc1_w || !w->fc1_b || !w->fc2_w || !w->fc2_b) return fq3_fail_(FQ3_EINVAL, "prompt weight table has null entries");

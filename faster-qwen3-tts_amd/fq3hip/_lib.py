@@ -137,6 +137,7 @@ SIGNATURES = {
     "fq3_batch_set_group_streams": (C.c_int, [vp, C.POINTER(vp), C.c_int]),
     "fq3_batch_poll_async": (C.c_int, [vp, C.c_int, vp]),
     "fq3_batch_poll_wait": (C.c_int, [vp, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "fq3_batch_text_append": (C.c_int, [vp, C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32), vp, vp]),
     "fq3_codec_create": (C.c_int, [C.POINTER(CodecConfig), C.POINTER(vp)]),
     "fq3_codec_destroy": (C.c_int, [vp]),
     "fq3_codec_set_option": (C.c_int, [vp, C.c_char_p, C.c_int]),

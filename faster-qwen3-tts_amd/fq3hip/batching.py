@@ -13,9 +13,17 @@ No reference equivalent -- the reference decodes one utterance at a time (``talk
 per-utterance semantics are the reference's (``generate.py:16-215``): same prefill, same first-token sampling, same
 suppress / min_new / repetition-penalty policy, and -- because the batch kernels keep the single-stream arithmetic --
 the same ids as ``fast_generate`` for the same noise.
+
+INCREMENTAL TEXT (``BatchRequest.text_feeder``): a request may be armed on its first text token and fed the rest while it decodes.
+Its lane holds an open text table on the device; before every batch of frames the scheduler drains all feeders and sends ONE
+``Fq3Batch.text_append`` for all lanes.  Appends and frames share one stream, so what the device's hold rule does is known on the
+host: after ``step`` frames such a lane has EMITTED ``min(emitted + step, rows published if open, max_frames)``.  For a text lane
+``_Lane.issued`` is that count (for a whole-text lane launched = emitted, as ever), and the noise rings, the step bound, the frame
+limit and the look-ahead clamp all follow it; every poll is checked against it.
 """
 from __future__ import annotations
 
+import threading
 import time
 from collections import deque
 from dataclasses import dataclass, field
@@ -44,6 +52,23 @@ class BatchRequest:
     tts_pad_embed: torch.Tensor
     config: Any
     gen_kwargs: Dict[str, Any] = field(default_factory=dict)
+    # incremental text: ``talker_input_embeds`` is the step-by-step prompt built from the FIRST text token, ``trailing_text_hiddens`` an
+    # empty [1, 0, H] table, ``text_feeder`` (a ``text_stream.TextFeeder``) yields the ids of every later token and ``tts_eos_id`` is
+    # the row the scheduler appends when the feeder is closed
+    text_feeder: Any = None
+    tts_eos_id: Optional[int] = None
+
+
+@dataclass
+class _TextLane:
+    """Host side of one lane's open text table (what ``text_stream.TextSession`` is to a single stream)."""
+    feeder: Any
+    eos_id: int
+    capacity: int
+    rows: int = 0                # rows appended (published in stream order before the next frames)
+    closed: bool = False
+    refilled_at: int = -1        # the emitted-frame count the noise rings were last refilled for
+    t_last: float = 0.0          # host time the feeder last delivered something (idle rule)
 
 
 @dataclass
@@ -62,6 +87,7 @@ class _Lane:
     prefill_ms: float = 0.0
     first_batch: int = 0         # index of the first batch of frames queued after this tenant was armed (polls of earlier batches show its predecessor)
     copied: Any = None           # event: the last side-stream read of this lane's code buffer (a new tenant is armed after it)
+    text: Optional[_TextLane] = None     # incremental text: `issued` then counts EMITTED frames (the host's model of the hold rule)
 
 
 @dataclass
@@ -132,6 +158,15 @@ class BatchDecoder:
         # the knob is a measurement switch.  What the latency of N simultaneous requests is made of: ~35 ms + 2.35 ms per request
         # (prefill 1.1, first-chunk vocoder 0.6 - 0.7, prompt build 0.33, arming 0.09).
         self.first_wave: Optional[int] = None
+        # INCREMENTAL TEXT.  A feeder that has delivered nothing for `text_idle_timeout_s` seconds is closed by the scheduler: the
+        # utterance ends the way whole text does and its lane and KV blocks come back.  30 s: an LLM that has not produced a token for
+        # that long has stalled or gone, and the longest pause between two pieces of a live stream is well below it.
+        self.text_idle_timeout_s: float = 30.0
+        self.text_wait_s: float = 0.02          # bound of one host wait while no lane can advance (the source is polled in between)
+        self._wake = threading.Event()          # set by every feeder of a text lane when it receives something
+        # counters of the last run(): scheduler iterations, frames() calls, appends sent, host waits with nothing to decode, polls
+        # that showed a held lane, polls that showed held and running lanes together, feeders closed by the idle rule
+        self.text_stats: Dict[str, Any] = {}
 
     def _group_streams(self):
         """When the batch was told to advance several lane groups concurrently (``fq3_batch_set_option("groups")``, a measurement switch:
@@ -183,6 +218,22 @@ class BatchDecoder:
             kw["temperature"], kw["top_k"], kw["top_p"], kw["do_sample"], kw["repetition_penalty"], use_graph=False)
         ln.req, ln.tn, ln.pn, ln.issued, ln.emitted, ln.max_frames = req, tn, pn, 0, 0, max_frames
         ln.t_arm, ln.prefill_ms = t0, (time.time() - t0) * 1000
+        self._open_text(ln)
+
+    def _open_text(self, ln: _Lane):
+        """Right after ``decode_begin``: a text-fed request's lane gets an open table of ``max_frames + 1`` rows (frame g reads row
+        g < max_frames; the closing ``tts_eos`` row fits) and its feeder learns whom to wake."""
+        ln.text = None
+        req = ln.req
+        if getattr(req, "text_feeder", None) is None or ln.max_frames <= 0:
+            return
+        if req.tts_eos_id is None:
+            raise ValueError("a request with a text_feeder needs tts_eos_id")
+        if int(req.trailing_text_hiddens.shape[-2]) != 0:
+            raise ValueError("a request with a text_feeder carries an empty trailing table (the prompt holds the first token)")
+        ln.engine.decode_text_open(ln.max_frames + 1)
+        ln.text = _TextLane(req.text_feeder, int(req.tts_eos_id), ln.max_frames + 1, t_last=time.monotonic())
+        req.text_feeder.waker = self._wake
 
     def _mark(self, engine):
         """Event after which the code tensors just read out are complete (recorded before further frames are queued)."""
@@ -356,6 +407,52 @@ class BatchDecoder:
         ln.req, ln.tn, ln.pn, ln.issued, ln.emitted, ln.max_frames = req, tn, pn, 0, 0, max_frames
         ln.t_arm, ln.prefill_ms = st.t0, st.prefill_ms
         st.req, st.kw, st.hidden = None, None, None
+        self._open_text(ln)
+
+    def _feed_text(self, lanes: List[_Lane]) -> int:
+        """Drain every text lane's feeder without blocking and send ONE append for all of them (the closing ``tts_eos`` row and the
+        capacity clamp are those of ``TextSession._append``).  Returns the number of lanes that received something."""
+        items = []
+        now = time.monotonic()
+        for ln in lanes:
+            t = ln.text
+            if t is None or t.closed:
+                continue
+            waited = getattr(t.feeder, "t_oldest", None)
+            ids, fin = t.feeder.take(block=False)
+            if ids and waited is not None:
+                # arrival of the oldest id -> its append is queued (what the device adds: the frames queued ahead, <= lookahead + 1 batches)
+                ms = (now - waited) * 1000
+                self.text_stats["append_wait_n"] += 1
+                self.text_stats["append_wait_ms_sum"] += ms
+                self.text_stats["append_wait_ms_max"] = max(self.text_stats["append_wait_ms_max"], ms)
+            if ids or fin:
+                t.t_last = now
+            elif now - t.t_last > self.text_idle_timeout_s:
+                t.feeder.close()                                     # a stalled client: the utterance ends like whole text
+                ids, fin = t.feeder.take(block=False)
+                fin = True
+                self.text_stats["idle_closed"] += 1
+            if not (ids or fin):
+                continue
+            room = t.capacity - t.rows
+            if fin:
+                ids = list(ids) + [t.eos_id]
+            if len(ids) >= room:                                     # the loop cannot reach further rows: close here
+                ids, fin = ids[:room], True
+            items.append((ln.index, ids, fin))
+            t.rows += len(ids)
+            t.closed = t.closed or fin
+        if items:
+            self.batch.text_append(items)
+            self.text_stats["appends"] += 1
+        return len(items)
+
+    @staticmethod
+    def _avail(ln: _Lane) -> int:
+        """Frames the lane can have emitted once everything queued so far has run."""
+        t = ln.text
+        return ln.max_frames if t is None or t.closed else min(t.rows, ln.max_frames)
 
     def _drop_blocks(self, x, cancel: bool = False):
         """Return whatever KV blocks lane / stage ``x`` owns to the pool (a lane's device loop is cancelled first when asked: a lane that
@@ -403,7 +500,7 @@ class BatchDecoder:
             if codes is not None:
                 timing["codes_ready_event"] = ready_ev if ready_ev is not None else self._mark(ln.engine)
         rid = ln.req.rid
-        ln.req, ln.tn, ln.pn, ln.emitted = None, None, None, 0
+        ln.req, ln.tn, ln.pn, ln.emitted, ln.text = None, None, None, 0, None
         # the lane's KV blocks go back to the pool now: the poll that found it finished waited for its last frame, and a done lane never
         # touches the cache again -- not in look-ahead frames still in flight either (done-lane guard, csrc/batch_kernels.cuh)
         release = getattr(ln.engine, "kv_release", None)
@@ -462,7 +559,10 @@ class BatchDecoder:
         self._polls.clear()
         self._unsynced = []                               # (first tokens an abandoned run left on the device: their stages are reset below)
         for ln in self.lanes:
-            ln.req, ln.tn, ln.pn, ln.issued, ln.emitted = None, None, None, 0, 0
+            ln.req, ln.tn, ln.pn, ln.issued, ln.emitted, ln.text = None, None, None, 0, 0, None
+        stats = self.text_stats = dict(iterations=0, frames_calls=0, appends=0, idle_waits=0, polls_held=0, polls_mixed=0, idle_closed=0,
+                                       append_wait_n=0, append_wait_ms_sum=0.0, append_wait_ms_max=0.0)
+        self._wake.clear()
         for st in self.stages:
             st.req, st.kw, st.hidden = None, None, None
         pending = deque(stamped(r) for r in requests)
@@ -604,18 +704,41 @@ class BatchDecoder:
         def digest(entry):
             """Read one batch's poll: chunk events and finishes of the lanes that were armed before it was queued."""
             nonlocal active
-            bno, slot, ev_done = entry
+            bno, slot, ev_done, model = entry
             if slot is not None:
                 t_ = clock()
-                n_all, d_all = self.batch.poll_wait(slot)               # waits for THIS batch's frames only: later ones keep running
+                # waits for THIS batch's frames only: later ones keep running.  (With text lanes in the batch the states come as ints:
+                # 2 = held on its open table, which is "running" here -- poll_wait folds it into True.)
+                n_all, d_all = self.batch.poll_wait_states(slot) if model else self.batch.poll_wait(slot)
                 prof["poll_wait"] += clock() - t_
                 self._polls.discard(slot)
             still = []
+            seen_held = seen_run = False
             for ln in active:
                 if ln.first_batch > bno:                                # armed after this batch was queued: the poll shows its predecessor
                     still.append(ln)
                     continue
-                n, done = (n_all[ln.index], d_all[ln.index]) if slot is not None else ln.engine.decode_poll()
+                if slot is not None:
+                    n, done = n_all[ln.index], d_all[ln.index]
+                elif ln.text is not None:
+                    n, done = ln.engine.decode_poll_state()
+                else:
+                    n, done = ln.engine.decode_poll()
+                if ln.index in model:
+                    # the host's model of the hold rule against the device: a lane that ended (EOS, position limit) may be behind
+                    # the model, never ahead; a running or held lane is exactly where the model says
+                    want_n, want_held = model[ln.index]
+                    state = int(done)
+                    ok = (n <= want_n) if state == 1 else (n == want_n and (state == 2) == want_held)
+                    if not ok:
+                        raise RuntimeError(f"lane {ln.index}: the poll shows {n} frames, state {state}; the host's model of the text "
+                                           f"hold rule has {want_n} frames, {'held' if want_held else 'running'} (noise rings out of step)")
+                    seen_held = seen_held or state == 2
+                    seen_run = seen_run or state == 0
+                    done = state == 1                                   # held is running
+                elif slot is not None and model:
+                    seen_run = seen_run or int(done) == 0
+                    done = int(done) == 1
                 fin = done or n >= ln.max_frames
                 if chunked:
                     # whole chunks, one event each (a poll can complete several); a finished utterance's last event carries
@@ -637,6 +760,8 @@ class BatchDecoder:
                     still.append(ln)
             finish_rate[0] = 0.5 * finish_rate[0] + 0.5 * (len(active) - len(still))
             active = still
+            stats["polls_held"] += int(seen_held)
+            stats["polls_mixed"] += int(seen_held and seen_run)
 
         # FIRST WAVE, pipelined (round 5): nothing decodes yet, so the critical path to the first frame is "build the prompts (host)" +
         # "prefill them (GPU)".  They used to run one after the other (128 lanes: 39 ms + 96 ms); now the prompts arrive in slices and
@@ -644,6 +769,7 @@ class BatchDecoder:
         # GPU prefills slice k; one copy fetches all first tokens before the lanes are armed.
         slice_n = max(1, int(getattr(self, "first_slice", 16)))
         while True:
+            stats["iterations"] += 1
             first_wave_phase = bool(self.stages) and not active and not ready and not inflight
             pull(cap=slice_n if first_wave_phase else None, on_main=first_wave_phase)
             if not (pending or active or ready or failed or inflight):
@@ -668,8 +794,10 @@ class BatchDecoder:
                 self.more_in_poll = 0
                 yield rid, None, info
             t_admit = clock()
+            moved = 0                                                 # requests admitted / staged in this iteration
             while free and (ready or (pending and not self.stages)):  # admit at a frame boundary
                 ln = free.popleft()
+                moved += 1
                 try:
                     arm_after_copy(ln)
                     if ready:
@@ -713,16 +841,39 @@ class BatchDecoder:
             # already covered by the frames in flight need no more (they wait for their poll)
             need = [ln for ln in active if ln.issued < ln.max_frames]
             t_ = clock()
+            texted = [ln for ln in active if ln.text is not None]
+            if texted:
+                # text that arrived since the last batch: ONE append for all lanes, in stream order in front of the frames below.  A
+                # text lane whose next row is still missing cannot advance: it neither bounds the step nor -- when no lane can
+                # advance -- gets frames queued at all (they would all be holds)
+                self._wake.clear()
+                self._feed_text(texted)
+                need = [ln for ln in need if self._avail(ln) > ln.issued]
             if need:
                 step = self.poll_every
                 for ln in need:
-                    if ln.issued % NOISE_RING == 0:
+                    if ln.text is None:
+                        if ln.issued % NOISE_RING == 0:
+                            _refill(ln.engine, ln.tn, ln.pn)
+                    elif ln.issued % NOISE_RING == 0 and ln.text.refilled_at != ln.issued:
+                        # once per 64 EMITTED frames: every frame before the boundary is in front of this in the stream, and a lane
+                        # that sat held on the boundary comes here once, when it can go on
                         _refill(ln.engine, ln.tn, ln.pn)
+                        ln.text.refilled_at = ln.issued
                     step = min(step, NOISE_RING - ln.issued % NOISE_RING, max(ln.max_frames - ln.issued, 1))
                 pull()                                                # stamp new arrivals before the frames are queued
                 self.batch.frames(step)
-                for ln in need:
-                    ln.issued += step
+                stats["frames_calls"] += 1
+                model = {}
+                for ln in active:
+                    if ln.text is None:
+                        if ln.issued < ln.max_frames:
+                            ln.issued += step
+                    else:
+                        # the hold rule on the host: the lane emits until its rows (or its frame limit) run out and holds there
+                        got = min(ln.issued + step, self._avail(ln))
+                        model[ln.index] = (got, got < ln.issued + step and got < ln.max_frames)
+                        ln.issued = got
                 slot = ev_done = None
                 if depth:
                     slot = batch_no % 4
@@ -730,7 +881,7 @@ class BatchDecoder:
                     self._polls.add(slot)
                     if self._copy is not None and chunked:
                         ev_done = self._mark(self.lanes[0].engine)
-                inflight.append((batch_no, slot, ev_done))
+                inflight.append((batch_no, slot, ev_done, model))
                 batch_no += 1
             prof["queue"] += clock() - t_
             # the chunks and finishes found by the previous poll go out only now, with the next frames already queued, so
@@ -741,24 +892,32 @@ class BatchDecoder:
             prof["consumer"] += clock() - t_
             if self.stages and active:
                 t_ = clock()
-                stage_ahead(limit=stage_limit())      # prefills fly under the frames queued above
+                moved += stage_ahead(limit=stage_limit())      # prefills fly under the frames queued above
                 prof["stage"] += clock() - t_
             # wait for the oldest batch; for ALL of them when a lane's frame limit falls in the newest (a finish is expected: queuing
             # past it would burn frames on idle lanes) or when nothing more could be queued
             expect = any(ln.issued >= ln.max_frames for ln in active)
-            while inflight and (len(inflight) > depth or expect or not need):
+            while inflight and (len(inflight) > depth or expect or not need):        # (`need`: the lanes that could be given frames)
                 t_, w_ = clock(), prof["poll_wait"]
                 digest(inflight.popleft())
                 prof["digest"] += clock() - t_ - (prof["poll_wait"] - w_)
                 if not active:
                     while inflight:                                   # frames queued past the last finish: nothing left to read in them
-                        _b, slot, _e = inflight.popleft()
+                        _b, slot, _e, _m = inflight.popleft()
                         if slot is not None:
                             self.batch.poll_wait(slot)
                             self._polls.discard(slot)
             if inflight or (not active and not ready and not pending):   # frames are running (or nothing is left to overlap with)
                 while outbox:
                     yield self._more(outbox)
+            if texted and active and not need and not inflight and not moved:
+                # every active lane waits for text and nothing is queued: what the last poll found goes out, then the host sleeps
+                # until a feeder receives something -- bounded, so that the source and the idle rule are looked at in between.
+                # No frame is queued meanwhile: nothing spins on the GPU.
+                while outbox:
+                    yield self._more(outbox)
+                stats["idle_waits"] += 1
+                self._wake.wait(self.text_wait_s)
         while outbox:
             yield self._more(outbox)
         while failed:                                                 # belt and braces: no error event is ever dropped

@@ -205,7 +205,8 @@ def build_parser():
             sp.add_argument("--text", required=not text_stdin)
             if text_stdin:
                 sp.add_argument("--text-stdin", action="store_true",
-                                help="read the text from stdin as it arrives (line by line) and decode behind it")
+                                help="read the text from stdin as it arrives (line by line) and decode behind it "
+                                     "(one stream; many streams at once: the server's /v1/audio/speech/sessions)")
             sp.add_argument("--output", required=True)
 
     def clone_refs(sp):

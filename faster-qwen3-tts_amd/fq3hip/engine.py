@@ -558,6 +558,22 @@ class Fq3Batch:
         L.check(self.lib.fq3_batch_poll_wait(self.handle, int(slot), a, d))
         return list(a), [int(x) for x in d]
 
+    def text_append(self, items):
+        """``fq3_batch_text_append``: ``items`` = ``[(lane index, ids, final), ...]``, every lane named at most once.  All ids are
+        projected by one launch chain (one pass over ``text_projection``) and land in the lanes' open tables in stream order; the
+        packed ids travel in ONE host-to-device copy and the tensor is kept alive until the next call."""
+        items = [(int(l), [int(i) for i in (ids.reshape(-1).tolist() if isinstance(ids, torch.Tensor) else ids)], bool(f)) for l, ids, f in items]
+        n = len(items)
+        if n == 0:
+            return
+        lane = (C.c_int32 * n)(*[it[0] for it in items])
+        count = (C.c_int32 * n)(*[len(it[1]) for it in items])
+        final = (C.c_int32 * n)(*[int(it[2]) for it in items])
+        flat = [i for it in items for i in it[1]]
+        t = torch.tensor(flat, dtype=torch.long, device=self.device) if flat else None
+        L.check(self.lib.fq3_batch_text_append(self.handle, n, lane, count, final, t.data_ptr() if flat else None, self._stream()))
+        self._text_ids_keep = t
+
     def set_group_streams(self, streams):
         """``fq3_batch_set_group_streams``: the caller's own side streams for lane groups 1.. (kept alive here)."""
         self._group_streams = list(streams)

@@ -995,10 +995,13 @@ class FasterQwen3TTS:
             out[rid] = ([a], voc.sample_rate)
         return out
 
-    def _run_batch_streaming(self, prepared, gen_kwargs, chunk_size: int, lanes: int):
+    def _run_batch_streaming(self, prepared, gen_kwargs, chunk_size: int, lanes: int, rounds=None, stamp=None):
         """Streaming form of :meth:`_run_batch_full`: yields ``(index, audio_chunk, sample_rate, timing)`` for every
         ``chunk_size`` frames of any utterance -- per utterance exactly the chunks the single-utterance streaming entry point
-        would produce (same windowing state machine).  ``timing``: ``chunk_index``, ``total_steps_so_far``, ``is_final``."""
+        would produce (same windowing state machine).  ``timing``: ``chunk_index``, ``total_steps_so_far``, ``is_final``.
+        ``rounds`` (incremental text, :meth:`_run_text_batch_streaming`): ``rounds(dec, meta)`` yields the ``(head, source)`` pairs of
+        successive scheduler runs instead of the one pair :meth:`_batch_feed` makes of ``prepared``; ``stamp(index, timing)`` may add
+        keys to a chunk's timing before it goes out."""
         meta: dict = {}
         vocs, n_chunks = {}, {}
         dec = self._batch_decoder(lanes)
@@ -1007,7 +1010,7 @@ class FasterQwen3TTS:
         # first wave does not buy its members a lower latency -- the prefills of the followers run beside their first frames and
         # stretch them (128 lanes: p25 305 ms / p50 395 ms at a wave of 32 against 340 ms for everybody at once) -- so the default stays.
         dec.first_wave = getattr(self, "batch_first_wave_streaming", None)
-        head, source = self._batch_feed(prepared, gen_kwargs, len(dec.lanes), meta, dec.first_wave)
+        pairs = rounds(dec, meta) if rounds is not None else [self._batch_feed(prepared, gen_kwargs, len(dec.lanes), meta, dec.first_wave)]
         tok = self.model.model.speech_tokenizer
         side = self._vocoder_stream(tok)
         batched = side is not None and hasattr(tok, "decode_tensor_batch")
@@ -1072,7 +1075,13 @@ class FasterQwen3TTS:
                 yield from part
             yield from plain
 
-        for rid, codes, info in dec.run(head, source=source, chunk_frames=chunk_size):
+        def out(r, m):
+            if stamp is not None:
+                stamp(r, m)
+            return m
+
+        for head, source in pairs:
+          for rid, codes, info in dec.run(head, source=source, chunk_frames=chunk_size):
             if rid not in vocs:
                 vocs[rid], n_chunks[rid] = self.streaming_vocoder(meta[rid], chunk_size), 0
             ev = info.pop("codes_ready_event", None)
@@ -1093,9 +1102,9 @@ class FasterQwen3TTS:
                 n_chunks[rid] += 1
             if more <= 0:
                 for r, m, audio, _job in flush():
-                    yield r, audio, self.sample_rate, m
-        for r, m, audio, _job in flush():
-            yield r, audio, self.sample_rate, m
+                    yield r, audio, self.sample_rate, out(r, m)
+          for r, m, audio, _job in flush():
+            yield r, audio, self.sample_rate, out(r, m)
 
     @staticmethod
     def _per_text(value, n: int, what: str) -> list:
@@ -1319,6 +1328,21 @@ class FasterQwen3TTS:
                                                         do_sample, repetition_penalty), chunk_size)
 
     # ---- incremental text (extension: the reference takes the whole text before it starts; fq3hip/text_stream.py) ---------
+    @staticmethod
+    def _refuse_icl_text_stream(xvec_only, voice_clone_prompt) -> str:
+        """Raises for a voice that can only be served as an ICL clone; returns the message for the checks that follow the prompt build."""
+        why = ("incremental text needs an x-vector-only voice: an ICL clone lays the text against the reference frames inside the "
+               "prompt, so the prefill needs the whole text (use generate_voice_clone_streaming)")
+        if not xvec_only and voice_clone_prompt is None:
+            raise ValueError(why)
+        if isinstance(voice_clone_prompt, list) and any(bool(it.icl_mode) for it in voice_clone_prompt):
+            raise ValueError(why)
+        if isinstance(voice_clone_prompt, dict):
+            icl = voice_clone_prompt.get("icl_mode", [not bool(v) for v in voice_clone_prompt.get("x_vector_only_mode", [True])])
+            if any(bool(v) for v in icl):
+                raise ValueError(why)
+        return why
+
     def _text_tokenize(self):
         """str -> token ids of a piece of the text BODY (no chat template around it)."""
         from .native_model import ByteTokenizer
@@ -1417,16 +1441,7 @@ class FasterQwen3TTS:
         """``generate_voice_clone_streaming(..., non_streaming_mode=False)`` for a text that is still arriving, for x-vector-only
         voices.  An ICL voice (reference codes + reference text) is refused: there the text is laid against the reference frames
         inside the prompt, so the prefill itself needs the whole text."""
-        why = ("incremental text needs an x-vector-only voice: an ICL clone lays the text against the reference frames inside the "
-               "prompt, so the prefill needs the whole text (use generate_voice_clone_streaming)")
-        if not xvec_only and voice_clone_prompt is None:
-            raise ValueError(why)
-        if isinstance(voice_clone_prompt, list) and any(bool(it.icl_mode) for it in voice_clone_prompt):
-            raise ValueError(why)
-        if isinstance(voice_clone_prompt, dict):
-            icl = voice_clone_prompt.get("icl_mode", [not bool(v) for v in voice_clone_prompt.get("x_vector_only_mode", [True])])
-            if any(bool(v) for v in icl):
-                raise ValueError(why)
+        why = self._refuse_icl_text_stream(xvec_only, voice_clone_prompt)
 
         def prepare(input_ids):
             m, talker, config, tie, tam, tth, tpe, rc = self._prepare_generation(
@@ -1438,3 +1453,139 @@ class FasterQwen3TTS:
         yield from self._run_text_streaming(text_iter, prepare,
                                             self._gen_kwargs(max_new_tokens, min_new_tokens, temperature, top_k, top_p, do_sample,
                                                              repetition_penalty), chunk_size)
+
+    # ---- incremental text in the lock-step batch: many text streams, one decoder ------------------------------------------
+    def _text_feeders(self, text_iters):
+        from .text_stream import TextFeeder, pump_text
+        feeders = []
+        for it in text_iters:
+            if isinstance(it, TextFeeder):
+                feeders.append(it)
+                continue
+            f = TextFeeder(self._text_tokenize())
+            pump_text(f, [it] if isinstance(it, str) else it)
+            feeders.append(f)
+        return feeders
+
+    def _bind_lane_prompt_weights(self, dec):
+        """The lanes of the batch scheduler project text themselves (``fq3_batch_text_append``): they borrow the text embedding and
+        ``text_projection`` this model's own context is bound to."""
+        keep = getattr(self.talker_graph.engine, "_prompt_keep", None)
+        if keep is None:
+            raise RuntimeError("incremental text needs the HIP prompt builder (this model's context has no prompt weights bound)")
+        for ln in dec.lanes:
+            if getattr(ln.engine, "_prompt_keep", None) is None:
+                ln.engine.bind_prompt_weights(*keep)
+
+    def text_batch_request(self, rid, feeder, prepare, gen_kwargs):
+        """The scheduler's request for a text stream whose first token exists: the step-by-step prompt around that token, an empty
+        trailing table, the feeder for every later token.  ``prepare(input_ids)`` is the voice's prompt builder."""
+        from .batching import BatchRequest
+        m, talker, config, tie, tam, _tth, tpe = prepare(self._text_session_ids(feeder))
+        return BatchRequest(rid, talker, tie, tam, tie.new_zeros(1, 0, tie.shape[-1]), tpe, config, dict(gen_kwargs),
+                            text_feeder=feeder, tts_eos_id=int(m.config.tts_eos_token_id))
+
+    def _run_text_batch_streaming(self, text_iters, prepares, gen_kwargs, chunk_size: int, lanes: int):
+        """Shared back half of the ``stream_*_batch`` entry points.  A request enters the scheduler when its first token exists;
+        streams whose first token has not arrived wait beside it and do not block the others."""
+        import threading
+        from collections import deque
+        feeders = self._text_feeders(text_iters)
+        arrived = threading.Event()
+        for f in feeders:
+            f.waker = arrived                                   # (the scheduler puts its own event here when it arms the lane)
+        waiting = deque(range(len(feeders)))
+
+        def rounds(dec, meta):
+            self._bind_lane_prompt_weights(dec)
+
+            def pull():
+                for _ in range(len(waiting)):
+                    i = waiting.popleft()
+                    n, closed = feeders[i].pending()
+                    if n or closed:                             # (closed and empty: _text_session_ids raises, as the single stream does)
+                        meta[i] = None
+                        return self.text_batch_request(i, feeders[i], prepares[i], gen_kwargs)
+                    waiting.append(i)
+                return None
+
+            while waiting:
+                arrived.clear()
+                if not any(sum(feeders[i].pending()) for i in waiting):
+                    arrived.wait(0.05)                          # nothing decodes and no first token yet: sleep until a feeder has one
+                    continue
+                yield [], pull
+
+        def stamp(i, timing):
+            if timing.get("chunk_index") == 0 and feeders[i].t_first is not None:
+                timing["first_text_ms"] = (time.time() - feeders[i].t_first) * 1000      # first piece received -> first audio
+
+        yield from self._run_batch_streaming(None, gen_kwargs, chunk_size, lanes, rounds=rounds, stamp=stamp)
+
+    @torch.inference_mode()
+    def stream_custom_voice_batch(self, text_iters, speaker: Union[str, List[str]], language: Union[str, List[str]] = "English",
+                                  instruct: Optional[Union[str, List[Optional[str]]]] = None, chunk_size: int = 12,
+                                  max_new_tokens: int = 2048, min_new_tokens: int = 2, temperature: float = 0.9, top_k: int = 50,
+                                  top_p: float = 1.0, do_sample: bool = True, repetition_penalty: float = 1.05,
+                                  lanes: int = 16) -> Generator[Tuple[int, np.ndarray, int, dict], None, None]:
+        """``generate_custom_voice_batch_streaming(..., non_streaming_mode=False)`` for texts that are still arriving: every element of
+        ``text_iters`` is an iterable of ``str`` pieces or a ``TextFeeder`` (an LLM's token stream per utterance), and up to ``lanes``
+        of them decode in lock-step while their text comes in.  Yields ``(index, audio_chunk, sample_rate, timing)``; per utterance the
+        chunks are those of the whole text, whatever the cuts and their timing.  The first chunk's timing has ``first_text_ms``."""
+        n = len(text_iters)
+        spks, langs, inss = self._per_text(speaker, n, "speaker"), self._per_text(language, n, "language"), self._per_text(instruct, n, "instruct")
+        if self.model.model.tts_model_type != "custom_voice":
+            raise ValueError("Loaded model does not support custom voice generation")
+        self.model._validate_languages(langs)
+        self.model._validate_speakers(spks)
+
+        def prep(spk, lang, ins):
+            return lambda input_ids: self._custom_prepare(None, spk, lang, ins, False, input_ids=input_ids)
+        yield from self._run_text_batch_streaming(text_iters, [prep(*a) for a in zip(spks, langs, inss)],
+                                                  self._gen_kwargs(max_new_tokens, min_new_tokens, temperature, top_k, top_p, do_sample,
+                                                                   repetition_penalty), chunk_size, lanes)
+
+    @torch.inference_mode()
+    def stream_voice_design_batch(self, text_iters, instruct: Union[str, List[str]], language: Union[str, List[str]] = "English",
+                                  chunk_size: int = 12, max_new_tokens: int = 2048, min_new_tokens: int = 2, temperature: float = 0.9,
+                                  top_k: int = 50, top_p: float = 1.0, do_sample: bool = True, repetition_penalty: float = 1.05,
+                                  lanes: int = 16) -> Generator[Tuple[int, np.ndarray, int, dict], None, None]:
+        """``generate_voice_design_batch_streaming(..., non_streaming_mode=False)`` for texts that are still arriving (see
+        :meth:`stream_custom_voice_batch`)."""
+        n = len(text_iters)
+        inss, langs = self._per_text(instruct, n, "instruct"), self._per_text(language, n, "language")
+        if self.model.model.tts_model_type != "voice_design":
+            raise ValueError("Loaded model does not support voice design generation")
+        self.model._validate_languages(langs)
+
+        def prep(ins, lang):
+            return lambda input_ids: self._design_prepare(None, ins, lang, False, input_ids=input_ids)
+        yield from self._run_text_batch_streaming(text_iters, [prep(*a) for a in zip(inss, langs)],
+                                                  self._gen_kwargs(max_new_tokens, min_new_tokens, temperature, top_k, top_p, do_sample,
+                                                                   repetition_penalty), chunk_size, lanes)
+
+    @torch.inference_mode()
+    def stream_voice_clone_batch(self, text_iters, language: Union[str, List[str]] = "English",
+                                 ref_audio: Optional[Union[str, Path]] = None, chunk_size: int = 12, max_new_tokens: int = 2048,
+                                 min_new_tokens: int = 2, temperature: float = 0.9, top_k: int = 50, top_p: float = 1.0,
+                                 do_sample: bool = True, repetition_penalty: float = 1.05, xvec_only: bool = True,
+                                 append_silence: bool = True, instruct: Optional[str] = None,
+                                 voice_clone_prompt: Optional[Union[Dict[str, Any], List[Any]]] = None,
+                                 lanes: int = 16) -> Generator[Tuple[int, np.ndarray, int, dict], None, None]:
+        """``generate_voice_clone_batch_streaming(..., non_streaming_mode=False)`` for texts that are still arriving, one x-vector-only
+        voice for all of them.  An ICL voice is refused with the message of :meth:`stream_voice_clone`."""
+        why = self._refuse_icl_text_stream(xvec_only, voice_clone_prompt)
+        langs = self._per_text(language, len(text_iters), "language")
+
+        def prep(lang):
+            def prepare(input_ids):
+                m, talker, config, tie, tam, tth, tpe, rc = self._prepare_generation(
+                    text=None, language=lang, ref_audio=ref_audio, ref_text="", xvec_only=True, non_streaming_mode=False,
+                    append_silence=append_silence, voice_clone_prompt=voice_clone_prompt, instruct=instruct, input_ids=input_ids)
+                if rc is not None:
+                    raise ValueError(why)
+                return m, talker, config, tie, tam, tth, tpe
+            return prepare
+        yield from self._run_text_batch_streaming(text_iters, [prep(l) for l in langs],
+                                                  self._gen_kwargs(max_new_tokens, min_new_tokens, temperature, top_k, top_p, do_sample,
+                                                                   repetition_penalty), chunk_size, lanes)

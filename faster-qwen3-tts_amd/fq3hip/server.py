@@ -11,6 +11,11 @@ objects hold a single static context.  Here there are two schedulers:
              ``lanes`` (<= 128) utterances advance in lock-step over ONE pass of the weights per frame; each response is
              sent when its utterance finishes.
 
+With the ``batch`` scheduler a client may also send its text in pieces while the audio is already coming (an LLM's token stream
+into speech): ``POST /v1/audio/speech/sessions`` -> ``{"id"}``, ``POST /v1/audio/speech/sessions/{id}/text`` with
+``{"text", "final"}``, ``GET /v1/audio/speech/sessions/{id}/audio`` -> the streaming wav / pcm body of ``/v1/audio/speech``.  A
+session decodes in a lane like any other request (``BatchWorker.submit_text``); it uses the voice's x-vector only.
+
 ``create_app(model, voices, ...)`` is the testable core; ``main()`` is the command line (same flags as the reference plus
 ``--scheduler/--lanes/--voice-cache/--synthetic``)."""
 from __future__ import annotations
@@ -23,6 +28,8 @@ import os
 import queue
 import sys
 import threading
+import time
+import uuid
 from typing import Any, AsyncGenerator, Dict, Optional
 
 import numpy as np
@@ -43,6 +50,16 @@ class SpeechRequest(BaseModel):
     speed: float = 1.0                     # accepted, not applied (as in the reference)
 
 
+class SessionRequest(BaseModel):
+    voice: str = "alloy"
+    response_format: str = "wav"          # wav | pcm
+
+
+class SessionText(BaseModel):
+    text: str = ""
+    final: bool = False
+
+
 class BatchWorker:
     """One thread owns the model and runs the continuous-batching decoder in streaming mode.  ``submit`` returns a queue that
     receives the utterance's PCM chunks (``np.ndarray``) as they are vocoded, then ``BatchWorker.DONE`` -- or an exception."""
@@ -56,12 +73,26 @@ class BatchWorker:
         # StreamingVocoder is built for the same number (a voice entry's own "chunk_size" only applies to the lock scheduler)
         self.chunk_size = max(1, int(chunk_size))
         self.inbox: "queue.Queue" = queue.Queue()
+        # text sessions whose first token has not arrived: they wait here, beside the scheduler, and block nobody
+        self.parked: list = []
+        self.wake = threading.Event()           # a request arrived / a parked session's feeder received something
+        self.park_timeout_s = 30.0              # a session that never sends a token is answered with an error and dropped
         self.thread = threading.Thread(target=self._run, daemon=True)
         self.thread.start()
 
     def submit(self, voice_cfg: dict, text: str) -> "queue.Queue":
         out: "queue.Queue" = queue.Queue()
         self.inbox.put((voice_cfg, text, out))
+        self.wake.set()
+        return out
+
+    def submit_text(self, voice_cfg: dict, feeder) -> "queue.Queue":
+        """A text session: ``feeder`` (a ``TextFeeder``) receives the text while the utterance decodes.  The request enters the
+        scheduler when its first token exists.  Same reply queue as :meth:`submit`."""
+        out: "queue.Queue" = queue.Queue()
+        feeder.waker = self.wake                 # (the scheduler puts its own event here when it arms the lane)
+        self.inbox.put((voice_cfg, feeder, out))
+        self.wake.set()
         return out
 
     def _run(self):
@@ -69,16 +100,35 @@ class BatchWorker:
         from .batching import BatchRequest
         m = self.model
         while True:
-            first = self.inbox.get()
-            if first is None:
-                return
+            first = None
+            if not self.parked:
+                first = self.inbox.get()
+                if first is None:
+                    return
+            elif not any(sum(it[1].pending()) for it in self.parked):
+                # only sessions without a first token: sleep until one has it (or a request arrives), bounded for the park timeout
+                self.wake.wait(0.05)
+                self.wake.clear()
+                now = time.monotonic()
+                for it in [it for it in self.parked if now - it[3] > self.park_timeout_s]:
+                    self.parked.remove(it)
+                    it[2].put(TimeoutError("the session received no text"))
+                    it[2].put(self.DONE)
+                try:
+                    first = self.inbox.get_nowait()
+                    if first is None:
+                        return
+                except queue.Empty:
+                    continue
             waiting: Dict[int, Any] = {}
             counter = [0]
             try:
                 with torch.inference_mode():
                     def prepare(item):
                         """(voice cfg, text, reply queue) -> BatchRequest, or None when the request failed before decoding."""
-                        cfg, text, out = item
+                        cfg, text, out = item[:3]
+                        if not isinstance(text, str):
+                            return prepare_text(item)
                         try:
                             inner, talker, config, tie, tam, tth, tpe, rc = m._prepare_generation(
                                 text=text, language=cfg.get("language", "Auto"), ref_audio=cfg.get("ref_audio"),
@@ -93,8 +143,45 @@ class BatchWorker:
                         kw = m._gen_kwargs(int(cfg.get("max_new_tokens", 2048)), 2, 0.9, 50, 1.0, True, 1.05)
                         return BatchRequest(i, talker, tie, tam, tth, tpe, config, kw)
 
+                    def prepare_text(item):
+                        """A text session: parked until its first token exists, then a request built around that token."""
+                        cfg, feeder, out = item[:3]
+                        n, closed = feeder.pending()
+                        if not n and not closed:
+                            if len(item) == 3:
+                                self.parked.append((cfg, feeder, out, time.monotonic()))
+                            return None
+                        if len(item) == 4:
+                            self.parked.remove(item)
+                        i = counter[0]
+
+                        def build(input_ids):
+                            inner, talker, config, tie, tam, tth, tpe, rc = m._prepare_generation(
+                                text=None, language=cfg.get("language", "Auto"), ref_audio=cfg.get("ref_audio"), ref_text="",
+                                xvec_only=True, voice_clone_prompt=cfg.get("voice_clone_prompt"), non_streaming_mode=False,
+                                input_ids=input_ids)
+                            if rc is not None:
+                                raise ValueError("text sessions need an x-vector-only voice")
+                            return inner, talker, config, tie, tam, tth, tpe
+                        try:
+                            m._bind_lane_prompt_weights(m._batch_decoder(self.lanes))
+                            kw = m._gen_kwargs(int(cfg.get("max_new_tokens", 2048)), 2, 0.9, 50, 1.0, True, 1.05)
+                            req = m.text_batch_request(i, feeder, build, kw)
+                        except Exception as exc:
+                            out.put(exc)
+                            out.put(self.DONE)
+                            return None
+                        counter[0] += 1
+                        waiting[i] = (out, m.streaming_vocoder(None, self.chunk_size))
+                        return req
+
                     def source():
-                        """Polled by the scheduler at every frame boundary: requests that arrived while the batch was decoding."""
+                        """Polled by the scheduler at every frame boundary: requests that arrived while the batch was decoding,
+                        parked sessions whose first token has come."""
+                        for it in list(self.parked):
+                            req = prepare_text(it)
+                            if req is not None:
+                                return req
                         while True:
                             try:
                                 item = self.inbox.get_nowait()
@@ -107,7 +194,7 @@ class BatchWorker:
                             if req is not None:
                                 return req
 
-                    head = prepare(first)
+                    head = prepare(first) if first is not None else None
                     chunk_frames = self.chunk_size
                     for rid, codes, info in m._batch_decoder(self.lanes).run([head] if head is not None else [], on_error="yield",
                                                                              source=source, chunk_frames=chunk_frames):
@@ -135,13 +222,18 @@ class BatchWorker:
 
 
 def create_app(model, voices: Dict[str, dict], default_voice: Optional[str] = None, scheduler: str = "lock", lanes: int = 8,
-               chunk_size: int = 12):
+               chunk_size: int = 12, worker=None):
+    """``worker``: a ready ``BatchWorker`` (or a stand-in with ``submit`` / ``submit_text``) instead of the one ``scheduler="batch"``
+    would start."""
     from fastapi import FastAPI, HTTPException
     from fastapi.responses import Response, StreamingResponse
 
     app = FastAPI(title="faster-qwen3-tts (MI355X) OpenAI-compatible API")
     lock = threading.Lock()
-    worker = BatchWorker(model, lanes, chunk_size) if scheduler == "batch" else None
+    if worker is None and scheduler == "batch":
+        worker = BatchWorker(model, lanes, chunk_size)
+    sessions: Dict[str, dict] = {}
+    sessions_lock = threading.Lock()
     sample_rate = int(getattr(model, "sample_rate", 24000))
 
     def resolve_voice(name: str) -> dict:
@@ -181,6 +273,111 @@ def create_app(model, voices: Dict[str, dict], default_voice: Optional[str] = No
                 raise item
             yield to_pcm16(item)
 
+    async def box_response(box, fmt: str, on_end=None):
+        """The streaming body of a batch-scheduler reply queue (``BatchWorker.submit`` / ``submit_text``)."""
+        loop = asyncio.get_event_loop()
+
+        async def batch_stream():
+            first = True
+            while True:
+                item = await loop.run_in_executor(None, box.get)
+                if item is BatchWorker.DONE:
+                    break
+                if isinstance(item, Exception):
+                    if first:
+                        raise HTTPException(status_code=500, detail=repr(item))
+                    logger.error("generation failed mid-stream: %r", item)
+                    break
+                if first and fmt == "wav":
+                    yield wav_header(sample_rate)      # unknown data length: streaming
+                first = False
+                yield to_pcm16(item)
+
+        # pull the first event before answering, so that a request that fails outright is a 500, not an empty 200
+        gen = batch_stream()
+        try:
+            head = await gen.__anext__()
+        except StopAsyncIteration:
+            head = None
+        except BaseException:
+            if on_end is not None:
+                on_end()
+            raise
+
+        async def replay():
+            try:
+                if head is not None:
+                    yield head
+                async for raw in gen:
+                    yield raw
+            finally:
+                if on_end is not None:
+                    on_end()
+
+        return StreamingResponse(replay(), media_type=CONTENT_TYPES[fmt])
+
+    # ---- text sessions: the text arrives in pieces while the audio is already streaming (batch scheduler) -----------------------
+    def drop_session(sid: str):
+        with sessions_lock:
+            s = sessions.pop(sid, None)
+        if s is not None:
+            s["feeder"].close()               # a consumer that went away: the utterance ends at the text it has
+
+    def live_session(sid: str) -> dict:
+        with sessions_lock:
+            s = sessions.get(sid)
+        if s is None:
+            raise HTTPException(status_code=404, detail=f"no such session: {sid!r} (unknown, finished or timed out)")
+        return s
+
+    @app.post("/v1/audio/speech/sessions")
+    async def open_session(req: SessionRequest):
+        if model is None:
+            raise HTTPException(status_code=503, detail="Model not loaded")
+        if worker is None or not hasattr(worker, "submit_text"):
+            raise HTTPException(status_code=400, detail="text sessions need --scheduler batch")
+        cfg = resolve_voice(req.voice)
+        fmt = req.response_format.lower()
+        if fmt not in ("wav", "pcm"):
+            raise HTTPException(status_code=400, detail=f"response_format {fmt!r} not supported for sessions. Use: wav, pcm")
+        try:
+            from .model import FasterQwen3TTS
+            FasterQwen3TTS._refuse_icl_text_stream(True, cfg.get("voice_clone_prompt"))
+        except ValueError as exc:
+            raise HTTPException(status_code=400, detail=str(exc))
+        from .text_stream import TextFeeder
+        feeder = TextFeeder(model._text_tokenize())
+        sid = uuid.uuid4().hex
+        now = time.monotonic()
+        with sessions_lock:
+            # sessions nobody ever read: their text ended (the client's `final`, or the scheduler's idle rule) long ago
+            for old in [k for k, s in sessions.items() if not s["reading"] and s["feeder"].closed and now - s["t_closed"] > 60.0]:
+                sessions.pop(old, None)
+            sessions[sid] = dict(feeder=feeder, box=worker.submit_text(cfg, feeder), fmt=fmt, reading=False, t_closed=now)
+        return {"id": sid}
+
+    @app.post("/v1/audio/speech/sessions/{sid}/text")
+    async def session_text(sid: str, req: SessionText):
+        s = live_session(sid)
+        try:
+            if req.text:
+                s["feeder"].feed(req.text)
+            if req.final:
+                s["feeder"].close()
+                s["t_closed"] = time.monotonic()
+        except ValueError as exc:                          # text after `final` (or after the idle rule closed the stream)
+            raise HTTPException(status_code=409, detail=str(exc))
+        return {"id": sid, "final": s["feeder"].closed}
+
+    @app.get("/v1/audio/speech/sessions/{sid}/audio")
+    async def session_audio(sid: str):
+        s = live_session(sid)
+        with sessions_lock:
+            if s["reading"]:
+                raise HTTPException(status_code=409, detail="this session's audio is being read already")
+            s["reading"] = True
+        return await box_response(s["box"], s["fmt"], on_end=lambda: drop_session(sid))
+
     @app.get("/health")
     async def health():
         return {"status": "ok", "model_loaded": model is not None, "scheduler": scheduler, "lanes": lanes if worker else 1}
@@ -197,40 +394,8 @@ def create_app(model, voices: Dict[str, dict], default_voice: Optional[str] = No
             raise HTTPException(status_code=400, detail=f"response_format {fmt!r} not supported. Use: wav, pcm, mp3")
         if fmt == "mp3":
             raise HTTPException(status_code=400, detail="response_format='mp3' needs pydub + ffmpeg, which this image does not ship; use wav or pcm")
-        loop = asyncio.get_event_loop()
         if worker is not None:
-            box = worker.submit(cfg, req.input)
-
-            async def batch_stream():
-                first = True
-                while True:
-                    item = await loop.run_in_executor(None, box.get)
-                    if item is BatchWorker.DONE:
-                        break
-                    if isinstance(item, Exception):
-                        if first:
-                            raise HTTPException(status_code=500, detail=repr(item))
-                        logger.error("generation failed mid-stream: %r", item)
-                        break
-                    if first and fmt == "wav":
-                        yield wav_header(sample_rate)      # unknown data length: streaming
-                    first = False
-                    yield to_pcm16(item)
-
-            # pull the first event before answering, so that a request that fails outright is a 500, not an empty 200
-            gen = batch_stream()
-            try:
-                head = await gen.__anext__()
-            except StopAsyncIteration:
-                head = None
-
-            async def replay():
-                if head is not None:
-                    yield head
-                async for raw in gen:
-                    yield raw
-
-            return StreamingResponse(replay(), media_type=CONTENT_TYPES[fmt])
+            return await box_response(worker.submit(cfg, req.input), fmt)
 
         async def audio_stream():
             if fmt == "wav":

@@ -49,6 +49,8 @@ class TextFeeder:
         self._closed = False
         self.t_first: Optional[float] = None        # host time of the first piece received (first_text_ms)
         self.released: List[str] = []               # the text pieces handed to the tokeniser, in order
+        self.t_oldest: Optional[float] = None       # time.monotonic() at which the oldest id still queued became available
+        self.waker: Optional[threading.Event] = None        # set on every feed / close: the batch scheduler sleeps on it when no lane can advance
 
     def _release(self, text: str):
         if not text:
@@ -57,6 +59,13 @@ class TextFeeder:
             raise ValueError("this TextFeeder has no tokeniser: use feed_ids()")
         self.released.append(text)
         self._ids.extend(int(i) for i in self._tokenize(text))
+
+    def _notify(self):
+        if self._ids and self.t_oldest is None:
+            self.t_oldest = time.monotonic()
+        self._cv.notify_all()
+        if self.waker is not None:
+            self.waker.set()
 
     def feed(self, text: str) -> None:
         with self._cv:
@@ -70,7 +79,7 @@ class TextFeeder:
                 self._release(buf[:cut])
                 buf = buf[cut:]
             self._tail = buf
-            self._cv.notify_all()
+            self._notify()
 
     def feed_ids(self, ids: Iterable[int]) -> None:
         with self._cv:
@@ -79,7 +88,7 @@ class TextFeeder:
             if self.t_first is None:
                 self.t_first = time.time()
             self._ids.extend(int(i) for i in ids)
-            self._cv.notify_all()
+            self._notify()
 
     def close(self) -> None:
         """No more text: releases the held tail.  Idempotent."""
@@ -88,12 +97,17 @@ class TextFeeder:
                 tail, self._tail = self._tail, ""
                 self._release(tail)
                 self._closed = True
-            self._cv.notify_all()
+            self._notify()
 
     @property
     def closed(self) -> bool:
         with self._cv:
             return self._closed
+
+    def pending(self) -> Tuple[int, bool]:
+        """``(ids queued, closed)`` without taking anything: a batch front end admits a request once its first token exists."""
+        with self._cv:
+            return len(self._ids), self._closed
 
     def take(self, block: bool = False, limit: Optional[int] = None, timeout: Optional[float] = None) -> Tuple[List[int], bool]:
         """``(ids, closed)``: the ids queued so far (at most ``limit``) and whether the feeder is closed AND drained.  ``block``:
@@ -103,6 +117,10 @@ class TextFeeder:
                 self._cv.wait_for(lambda: self._ids or self._closed, timeout)
             n = len(self._ids) if limit is None else min(int(limit), len(self._ids))
             ids = [self._ids.popleft() for _ in range(n)]
+            if not self._ids:
+                self.t_oldest = None
+            elif ids:
+                self.t_oldest = time.monotonic()
             return ids, self._closed and not self._ids
 
 

@@ -330,6 +330,16 @@ int fq3_batch_graph_reset(fq3_batch* b);
  * in the slot. */
 int fq3_batch_poll_async(fq3_batch* b, int slot, void* stream);
 int fq3_batch_poll_wait(fq3_batch* b, int slot, int* n_frames_total, int* done);
+/* fq3_decode_text_append for many lanes in one call.  n_items (lane, count, final) triples on the host; ids int64[sum(count)] on the
+ * device, packed in item order.  For every item: `count` more rows of that lane's open table (fq3_decode_text_open on the lane's
+ * context), final != 0 closes it; count == 0 is allowed with final.  All ids are projected by ONE gather, ONE fc1 + SiLU and ONE
+ * fc2 GEMM, one launch scatters the rows to the lanes' tables and one publishes the new lengths in stream order: five launches
+ * whatever the number of lanes.  The rows are bit-identical to fq3_text_project of the same ids.
+ * All or nothing, checked before anything is queued: FQ3_EINVAL for a lane index out of range or named twice, a negative count or
+ * an item with neither ids nor final, and for an item past its lane's capacity; FQ3_ESTATE for a lane whose table is not open.
+ * On error no lane's rows, row count or open flag change. */
+int fq3_batch_text_append(fq3_batch* b, int n_items, const int32_t* lane, const int32_t* count, const int32_t* final_,
+                          const int64_t* ids, void* stream);
 /* "mfma" 0|1: batch GEMVs on the matrix cores (bf16 contexts; default 1: ids checked against the oracle by teacher
  * forcing) or on the VALU kernels (0: every lane bit-identical to the same utterance decoded alone).
  * "skinny" 0|1 (with "mfma" 1, more than 16 lanes): o_proj / down through the weight-stationary kernel of the short-prompt prefill

@@ -767,17 +767,8 @@ template <int BN, int STAGES, typename TE = bf16_t, int NT = 256, int BM = 128, 
 inline void glds_go(const GemmArgs& a, hipStream_t s) {
     const int rows = a.M - a.m_lo;
     const size_t shm = (size_t)STAGES * (BM + BN) * 64 * 2;
-    auto kern = glds_gemm_kernel<BN, STAGES, TE, NT, BM, DBG>;
-    if (shm > 48 * 1024) {
-        // the LDS limit of a kernel is a per-device setting: raised once per instantiation AND device (a process may drive several)
-        static bool raised[16] = {};
-        int dev = 0;
-        if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 16) dev = -1;
-        if (dev < 0 || !raised[dev]) {
-            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm);
-            if (dev >= 0) raised[dev] = true;
-        }
-    }
+    constexpr auto kern = glds_gemm_kernel<BN, STAGES, TE, NT, BM, DBG>;
+    (void)lds_limit_at_least<kern>(shm);
     hipLaunchKernelGGL(kern, dim3((a.N + BN - 1) / BN, (rows + BM - 1) / BM, a.n_seg > 1 ? a.n_seg : 1), dim3(NT), shm, s, a);
 }
 
@@ -1194,35 +1185,18 @@ __global__ __launch_bounds__(512) void big_gemm_kernel(GemmArgs a_in, int tiles_
     }
 }
 
-// A refused launch (e.g. an LDS limit that was not raised on this device) is NOT consumed here: its error stays pending for the
-// hipGetLastError check of the entry point that issued the GEMM (LAUNCH_CHECK in fq3_api.hip, fq3_codec.hip / fq3_batch.hip), so the
-// caller reports the failure instead of returning a stale output.
 template <bool TR, int BN, typename TE = bf16_t>
 inline void big_go_t(const GemmArgs& a, hipStream_t s) {
     const int rows = a.M - a.m_lo, nseg = a.n_seg > 1 ? a.n_seg : 1;
     const int tx = (a.N + BN - 1) / BN, ty = (rows + kBigBM - 1) / kBigBM;
     const size_t shm = (size_t)kBigStages * (kBigBM + BN) * kBigBK * 2;
-    // the LDS limit of a kernel is a per-device setting: raised once per instantiation AND device (as glds_go)
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 16) dev = -1;
-    auto raise = [&](const void* kern, bool (&raised)[16]) {
-        if (dev < 0 || !raised[dev]) {
-            (void)hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm);
-            if (dev >= 0) raised[dev] = true;
-        }
+    auto go = [&](auto pair) {
+        constexpr auto kern = big_gemm_kernel<kBigStages, TR, BN, TE, decltype(pair)::value>;
+        (void)lds_limit_at_least<kern>(shm);
+        hipLaunchKernelGGL(kern, dim3(tx * ty * nseg), dim3(512), shm, s, a, tx, tx * ty, tx * ty * nseg);
     };
     // whole-line copies (PAIR) wherever a group of 64 columns stays inside one tap; the half-line ring of four otherwise (Cin = 96, 160, ...)
-    if (a.big_pair >= 0 && a.Cin % 64 == 0) {
-        static bool raised_p[16] = {};
-        auto kern = big_gemm_kernel<kBigStages, TR, BN, TE, true>;
-        raise(reinterpret_cast<const void*>(kern), raised_p);
-        hipLaunchKernelGGL(kern, dim3(tx * ty * nseg), dim3(512), shm, s, a, tx, tx * ty, tx * ty * nseg);
-        return;
-    }
-    static bool raised[16] = {};
-    auto kern = big_gemm_kernel<kBigStages, TR, BN, TE>;
-    raise(reinterpret_cast<const void*>(kern), raised);
-    hipLaunchKernelGGL(kern, dim3(tx * ty * nseg), dim3(512), shm, s, a, tx, tx * ty, tx * ty * nseg);
+    if (a.big_pair >= 0 && a.Cin % 64 == 0) go(std::true_type{}); else go(std::false_type{});
 }
 // wide plain outputs (prefill qkv / gate_up: 980 vs 872 TFLOP/s) store straight from the transposed accumulators; tall outputs
 // with the full epilogue (codec convs: 661 vs 584) go through the LDS walk with 128-byte row stores

@@ -15,6 +15,7 @@
 // replays (bf16 after every Linear / norm / RoPE / residual add; fp32 inside dot products and softmax).
 #pragma once
 #include "fq3_common.cuh"
+#include <initializer_list>
 
 namespace fq3 {
 
@@ -93,6 +94,13 @@ template <int NCH, int EPI> struct MaxRows {
     static constexpr int NR = EPI == EPI_SWIGLU ? 2 : 1;
     static constexpr int v = NCH >= 12 ? 1 : (NCH >= 6 ? (2 / NR) : 2);
 };
+
+// 512-element chunks per lane (NCH) that cover an inner dimension K, rounded up to a built count; 0 = more than `most`
+inline int gemv_chunks(int K, int most) {
+    const int need = (K + 511) / 512;
+    for (int n : {1, 2, 4, 6, 12}) if (need <= n && n <= most) return n;
+    return 0;
+}
 
 // M = number of tokens that share one pass over the weights (2 only for the code predictor's two-token
 // prefill, predictor_graph.py:121-128: weights are read once, both tokens' dot products are formed).

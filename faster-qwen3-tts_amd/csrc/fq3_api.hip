@@ -394,11 +394,10 @@ extern "C" int fq3_bind_weights(fq3_ctx* c, const fq3_weight_table* w) {
 // -------------------------------------------------------------------------------------------------
 // GEMV dispatch
 // -------------------------------------------------------------------------------------------------
-static thread_local int g_rmax = 2;      // set from the context before a launch sequence (fq3_set_option "rows_per_wave_max")
+// rmax: the context's cap on rows per wave (fq3_set_option "rows_per_wave_max"; 0 = none)
 template <typename T, int NCH, int PRO, int EPI, bool NT, int M = 1>
-static void launch_gemv_n(const GemvArgs& a, hipStream_t s) {
+static void launch_gemv_n(const GemvArgs& a, int rmax, hipStream_t s) {
     // rows per wave: 2 for the big matrices (512-768 workgroups), 1 when N <= 1024 or a row is long
-    const int rmax = g_rmax;
     int R = (a.N + 1023) / 1024;
     if (R > MaxRows<NCH, EPI>::v) R = MaxRows<NCH, EPI>::v;
     if (rmax > 0 && R > rmax) R = rmax;
@@ -415,46 +414,42 @@ static void launch_gemv_n(const GemvArgs& a, hipStream_t s) {
 // registers of both tokens would not fit beyond -- the 12-chunk instantiations of earlier rounds spilled and were never reached by a
 // supported model).
 template <typename T, int PRO, int EPI>
-static int launch_gemv2_t(const GemvArgs& a, hipStream_t s) {
-    const int need = (a.K + 511) / 512;
-    if (need <= 1) launch_gemv_n<T, 1, PRO, EPI, false, 2>(a, s);
-    else if (need <= 2) launch_gemv_n<T, 2, PRO, EPI, false, 2>(a, s);
-    else if (need <= 4) launch_gemv_n<T, 4, PRO, EPI, false, 2>(a, s);
-    else if (PRO != PRO_NORM && need <= 6) { if constexpr (PRO != PRO_NORM) launch_gemv_n<T, 6, PRO, EPI, false, 2>(a, s); }
-    else return fail(FQ3_EUNSUPPORTED, PRO == PRO_NORM ? "code predictor hidden size above 2048" : "code predictor GEMV inner dimension above 3072");
+static int launch_gemv2_t(const GemvArgs& a, int rmax, hipStream_t s) {
+    constexpr int most = PRO == PRO_NORM ? 4 : 6;
+    const int n = gemv_chunks(a.K, most);
+    if (!n) return fail(FQ3_EUNSUPPORTED, PRO == PRO_NORM ? "code predictor hidden size above 2048" : "code predictor GEMV inner dimension above 3072");
+    with_value<1, 2, 4, 6>(n, [&](auto nch) {
+        if constexpr (decltype(nch)::value <= most) launch_gemv_n<T, decltype(nch)::value, PRO, EPI, false, 2>(a, rmax, s);
+    });
     return 0;
 }
 template <int PRO, int EPI>
 static int launch_gemv2(const fq3_ctx* c, const GemvArgs& a, hipStream_t s) {
-    g_rmax = c->opt_rmax;
-    return c->cfg.dtype == FQ3_BF16 ? launch_gemv2_t<bf16_t, PRO, EPI>(a, s) : launch_gemv2_t<float, PRO, EPI>(a, s);
+    return c->cfg.dtype == FQ3_BF16 ? launch_gemv2_t<bf16_t, PRO, EPI>(a, c->opt_rmax, s) : launch_gemv2_t<float, PRO, EPI>(a, c->opt_rmax, s);
 }
 template <typename T, int PRO, int EPI, bool NT>
-static int launch_gemv_t(const GemvArgs& a, hipStream_t s) {
-    const int need = (a.K + 511) / 512;
-    if (need <= 1) launch_gemv_n<T, 1, PRO, EPI, NT>(a, s);
-    else if (need <= 2) launch_gemv_n<T, 2, PRO, EPI, NT>(a, s);
-    else if (need <= 4) launch_gemv_n<T, 4, PRO, EPI, NT>(a, s);
-    else if constexpr (PRO == PRO_NORM) return fail(FQ3_EUNSUPPORTED, "hidden size above 2048");      // a normalising GEMV reads K = hidden
-    else if (need <= 6) launch_gemv_n<T, 6, PRO, EPI, NT>(a, s);
-    else if (need <= 12) launch_gemv_n<T, 12, PRO, EPI, NT>(a, s);
-    else return fail(FQ3_EUNSUPPORTED, "GEMV inner dimension above 6144");
+static int launch_gemv_t(const GemvArgs& a, int rmax, hipStream_t s) {
+    constexpr int most = PRO == PRO_NORM ? 4 : 12;       // a normalising GEMV reads K = hidden
+    const int n = gemv_chunks(a.K, most);
+    if (!n) return fail(FQ3_EUNSUPPORTED, PRO == PRO_NORM ? "hidden size above 2048" : "GEMV inner dimension above 6144");
+    with_value<1, 2, 4, 6, 12>(n, [&](auto nch) {
+        if constexpr (decltype(nch)::value <= most) launch_gemv_n<T, decltype(nch)::value, PRO, EPI, NT>(a, rmax, s);
+    });
     return 0;
 }
 template <int PRO, int EPI>
 static int launch_gemv(const fq3_ctx* c, const GemvArgs& a, bool nt, hipStream_t s) {
-    g_rmax = c->opt_rmax;
+    const int rmax = c->opt_rmax;
     if (c->cfg.dtype == FQ3_BF16)
-        return nt ? launch_gemv_t<bf16_t, PRO, EPI, true>(a, s) : launch_gemv_t<bf16_t, PRO, EPI, false>(a, s);
-    return nt ? launch_gemv_t<float, PRO, EPI, true>(a, s) : launch_gemv_t<float, PRO, EPI, false>(a, s);
+        return nt ? launch_gemv_t<bf16_t, PRO, EPI, true>(a, rmax, s) : launch_gemv_t<bf16_t, PRO, EPI, false>(a, rmax, s);
+    return nt ? launch_gemv_t<float, PRO, EPI, true>(a, rmax, s) : launch_gemv_t<float, PRO, EPI, false>(a, rmax, s);
 }
 
 template <typename T, bool PAGED>
 static void launch_attn_p(const AttnArgs& a, int rep, int workers, hipStream_t s) {
-    dim3 grid(a.n_kv, workers);
-    if (rep == 1) hipLaunchKernelGGL((attn_decode_kernel<T, 1, PAGED>), grid, dim3(256), 0, s, a);
-    else if (rep == 2) hipLaunchKernelGGL((attn_decode_kernel<T, 2, PAGED>), grid, dim3(256), 0, s, a);
-    else hipLaunchKernelGGL((attn_decode_kernel<T, 4, PAGED>), grid, dim3(256), 0, s, a);
+    with_value<1, 2, 4>(rep, [&](auto r) {
+        hipLaunchKernelGGL((attn_decode_kernel<T, decltype(r)::value, PAGED>), dim3(a.n_kv, workers), dim3(256), 0, s, a);
+    });
 }
 template <typename T>
 static void launch_attn_t(const AttnArgs& a, int rep, int workers, hipStream_t s) {

@@ -94,28 +94,25 @@ static int bmalloc(fq3_batch* b, void** p, size_t bytes) {
     return 0;
 }
 
-// the two-panel normalising GEMVs need up to ~83 KB of dynamic LDS: raise the limit of every instantiation once, outside any capture
+// dynamic LDS of the normalising matrix-core GEMVs: `panels` token tiles of K normalised bf16 values (rows padded by 8) + their partial sums
+static size_t norm_panel_lds(int K, int NR, int panels) {
+    return (((size_t)panels * kTokTile * (K + 8) * 2 + 15) & ~(size_t)15) + (size_t)panels * 4 * NR * 256 * sizeof(float);
+}
+// the two-panel form needs up to ~83 KB: the limit of every instantiation is raised in fq3_batch_create, outside any capture
 template <int KS, int EPI>
 static bool norm_dual_attr() {
-    constexpr int NR = EPI == EPI_SWIGLU ? 2 : 1;
-    const size_t shm2 = (((size_t)2 * kTokTile * (KS * 128 + 8) * 2 + 15) & ~(size_t)15) + (size_t)2 * 4 * NR * 256 * sizeof(float);
-    if (shm2 <= 48 * 1024) return true;
-    const bool r2 = hipFuncSetAttribute(reinterpret_cast<const void*>(gemv_batch_mfma_norm_kernel<KS, EPI, 2, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm2) == hipSuccess;
-    const bool r3 = hipFuncSetAttribute(reinterpret_cast<const void*>(gemv_batch_mfma_norm_kernel<KS, EPI, 3, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm2) == hipSuccess;
-    const bool r4 = hipFuncSetAttribute(reinterpret_cast<const void*>(gemv_batch_mfma_norm_kernel<KS, EPI, 4, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm2) == hipSuccess;
-    const bool r0 = hipFuncSetAttribute(reinterpret_cast<const void*>(gemv_batch_mfma_norm_kernel<KS, EPI, 0, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm2) == hipSuccess;
-    return r2 && r3 && r4 && r0;
+    const size_t shm2 = norm_panel_lds(KS * 128, EPI == EPI_SWIGLU ? 2 : 1, 2);
+    const bool r[] = {lds_limit_at_least<gemv_batch_mfma_norm_kernel<KS, EPI, 2, true>>(shm2), lds_limit_at_least<gemv_batch_mfma_norm_kernel<KS, EPI, 3, true>>(shm2),
+                      lds_limit_at_least<gemv_batch_mfma_norm_kernel<KS, EPI, 4, true>>(shm2), lds_limit_at_least<gemv_batch_mfma_norm_kernel<KS, EPI, 0, true>>(shm2)};
+    return r[0] && r[1] && r[2] && r[3];
 }
 static bool norm_dual_prepare() {
-    static int done = -1;
-    if (done < 0) {
-        const bool r[] = {norm_dual_attr<2, EPI_STORE>(), norm_dual_attr<4, EPI_STORE>(), norm_dual_attr<8, EPI_STORE>(),
-                          norm_dual_attr<2, EPI_SWIGLU>(), norm_dual_attr<4, EPI_SWIGLU>(), norm_dual_attr<8, EPI_SWIGLU>()};
-        bool ok = true;
-        for (bool b : r) ok = ok && b;
-        done = ok ? 1 : 0;
-    }
-    return done == 1;
+    // (every instantiation is asked, whatever the earlier ones returned)
+    const bool r[] = {norm_dual_attr<2, EPI_STORE>(), norm_dual_attr<4, EPI_STORE>(), norm_dual_attr<8, EPI_STORE>(),
+                      norm_dual_attr<2, EPI_SWIGLU>(), norm_dual_attr<4, EPI_SWIGLU>(), norm_dual_attr<8, EPI_SWIGLU>()};
+    bool ok = true;
+    for (bool b : r) ok = ok && b;
+    return ok;
 }
 
 extern "C" int fq3_batch_graph_reset(fq3_batch* b) {
@@ -348,35 +345,28 @@ static int launch_gemv_batch_t(BatchGemvArgs a, int esz, hipStream_t s) {
     const size_t shm = (size_t)group * a.K * esz;
     if (shm > 150 * 1024) return fq3_fail_(FQ3_EUNSUPPORTED, "a single token of this inner dimension does not fit the 160 KB LDS");
     a.group = group;
-    auto go = [&](auto nch) -> int {
+    constexpr int most = PRO == PRO_NORM ? 4 : 12;               // a normalising GEMV reads K = hidden
+    const int n = gemv_chunks(a.K, most);
+    if (!n) return fq3_fail_(FQ3_EUNSUPPORTED, PRO == PRO_NORM ? "hidden size above 2048" : "GEMV inner dimension above 6144");
+    return with_value<1, 2, 4, 6, 12>(n, [&](auto nch) -> int {
         constexpr int NCH = decltype(nch)::value;
-        auto kern = gemv_batch_kernel<T, NCH, PRO, EPI>;
-        if (shm > 48 * 1024) HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm));
-        hipLaunchKernelGGL(kern, dim3(grid), dim3(256), shm, s, a);
+        if constexpr (NCH <= most) {
+            constexpr auto kern = gemv_batch_kernel<T, NCH, PRO, EPI>;
+            if (!lds_limit_at_least<kern>(shm)) return fq3_fail_(FQ3_EHIP, "batch GEMV: could not raise the kernel's LDS limit");
+            hipLaunchKernelGGL(kern, dim3(grid), dim3(256), shm, s, a);
+        }
         return 0;
-    };
-    if (need <= 1) return go(std::integral_constant<int, 1>{});
-    if (need <= 2) return go(std::integral_constant<int, 2>{});
-    if (need <= 4) return go(std::integral_constant<int, 4>{});
-    if constexpr (PRO == PRO_NORM) return fq3_fail_(FQ3_EUNSUPPORTED, "hidden size above 2048");      // a normalising GEMV reads K = hidden
-    else {
-        if (need <= 6) return go(std::integral_constant<int, 6>{});
-        if (need <= 12) return go(std::integral_constant<int, 12>{});
-        return fq3_fail_(FQ3_EUNSUPPORTED, "GEMV inner dimension above 6144");
-    }
+    });
 }
 // matrix-core variants: bf16, built step counts; return -1000 when the shape is not covered (the VALU kernel takes over)
-static thread_local int g_batch_norm_dual = 1;   // set per enqueue from fq3_batch::norm_dual
-static thread_local int g_batch_norm_skinny = 1; // set per enqueue from fq3_batch::norm_skinny
-static thread_local int g_batch_norm_skinny_above = 2 * kTokTile;
-static thread_local int g_batch_packed = 1;      // set per enqueue from fq3_batch::packed (fragment-major weight copies, fq3_ctx.h)
+// (every launcher below reads the batch's options -- fq3_batch_set_option -- from the batch it is given)
 template <int EPI>
-static int launch_gemv_batch_mfma_norm(const BatchGemvArgs& a0, hipStream_t s) {
+static int launch_gemv_batch_mfma_norm(const fq3_batch& b, const BatchGemvArgs& a0, hipStream_t s) {
     if (a0.K % 128) return -1000;
     BatchGemvArgs a = a0;                                          // (a copy: the panel path below adds the fragment-major weight pointer)
     // above 32 lanes (three token tiles and more): normalise once, then the weight-stationary GEMM (batch_kernels.cuh::rmsnorm_batch_kernel)
     const int n_w = EPI == EPI_SWIGLU ? 2 * a.N : a.N;                  // weight rows: [gate | up] for SwiGLU
-    if (g_batch_norm_skinny && a.xn_ws && a.B > g_batch_norm_skinny_above && !a.bias && skinny_k_ok(a.K) && a.K <= 2048 && n_w % 32 == 0 &&
+    if (b.norm_skinny && a.xn_ws && a.B > b.norm_skinny_above && !a.bias && skinny_k_ok(a.K) && a.K <= 2048 && n_w % 32 == 0 &&
         a.x_stride % 8 == 0 && a.y_stride % 4 == 0 && (EPI == EPI_STORE || EPI == EPI_SWIGLU)) {
         if (a.ssq_in && !a.xn_out && skinny_norm_ok(a.K, a.B)) {
             // the rows' sum-of-squares partials came with them (the residual GEMM that stored them): normalise inside the GEMM
@@ -384,7 +374,7 @@ static int launch_gemv_batch_mfma_norm(const BatchGemvArgs& a0, hipStream_t s) {
             k.X = reinterpret_cast<const bf16_t*>(a.x); k.ldx = a.x_stride; k.M = a.B; k.W = reinterpret_cast<const bf16_t*>(a.W); k.N = n_w;
             k.Y = reinterpret_cast<bf16_t*>(a.y); k.ldy = a.y_stride;
             k.ssq = a.ssq_in; k.gain = reinterpret_cast<const bf16_t*>(a.norm_w); k.eps = a.eps;
-            if (g_batch_packed) k.Wp = reinterpret_cast<const bf16_t*>(fq3_packed_find_(a.W, EPI == EPI_SWIGLU ? 1 : 0));
+            if (b.packed) k.Wp = reinterpret_cast<const bf16_t*>(fq3_packed_find_(a.W, EPI == EPI_SWIGLU ? 1 : 0));
             if constexpr (EPI == EPI_SWIGLU) skinny_launch<SK_SWIGLU>(k, a.K, s);
             else skinny_launch<SK_STORE>(k, a.K, s);
             return 0;
@@ -396,116 +386,81 @@ static int launch_gemv_batch_mfma_norm(const BatchGemvArgs& a0, hipStream_t s) {
         SkinnyArgs k{};
         k.X = xn; k.ldx = a.K; k.M = a.B; k.W = reinterpret_cast<const bf16_t*>(a.W); k.N = n_w;
         k.Y = reinterpret_cast<bf16_t*>(a.y); k.ldy = a.y_stride;
-        if (g_batch_packed) k.Wp = reinterpret_cast<const bf16_t*>(fq3_packed_find_(a.W, EPI == EPI_SWIGLU ? 1 : 0));
+        if (b.packed) k.Wp = reinterpret_cast<const bf16_t*>(fq3_packed_find_(a.W, EPI == EPI_SWIGLU ? 1 : 0));
         if constexpr (EPI == EPI_SWIGLU) skinny_launch<SK_SWIGLU>(k, a.K, s);
         else skinny_launch<SK_STORE>(k, a.K, s);
         return 0;
     }
     const int grid = (a.N + 15) / 16;
     constexpr int NR = EPI == EPI_SWIGLU ? 2 : 1;
-    const size_t shm = (((size_t)kTokTile * (a.K + 8) * 2 + 15) & ~(size_t)15) + (size_t)4 * NR * 256 * sizeof(float);
-    const int nt = (a.B + kTokTile - 1) / kTokTile;            // token tiles: 1..4
+    const size_t shm = norm_panel_lds(a.K, NR, 1);
     // the panel kernels' weight fragments from the fragment-major copy in 16-row blocks (kind 0), where the shape has whole blocks
-    a.Wp = (g_batch_packed && a.N % 16 == 0 && (EPI != EPI_SWIGLU || a.up_off % 16 == 0)) ? fq3_packed_find_(a.W, 0) : nullptr;
-    auto go = [&](auto ks) -> int {
+    a.Wp = (b.packed && a.N % 16 == 0 && (EPI != EPI_SWIGLU || a.up_off % 16 == 0)) ? fq3_packed_find_(a.W, 0) : nullptr;
+    a.ntiles = (a.B + kTokTile - 1) / kTokTile;                // token tiles: 1..4 unrolled, more (65..128 lanes) by the rolled loop, NT = 0
+    if (!one_of<2, 4, 8, 16>(a.K / 128)) return -1000;         // hidden sizes: 256 (tests), 512, 1024 (0.6B, predictor), 2048 (1.7B)
+    return with_value<2, 4, 8, 16>(a.K / 128, [&](auto ks) -> int {
         constexpr int KS = decltype(ks)::value;
         if constexpr (KS <= 8) {
-            if (nt >= 2 && g_batch_norm_dual) {
-                // two panels + a pair of tiles' partial sums (66 + 8..16 KB at K = 1024; the limit is raised in fq3_batch_create, never
-                // inside a graph capture); three and four tiles repeat the scheme per pair
-                const size_t shm2 = (((size_t)2 * kTokTile * (a.K + 8) * 2 + 15) & ~(size_t)15) + (size_t)2 * 4 * NR * 256 * sizeof(float);
-                if (nt == 2) hipLaunchKernelGGL((gemv_batch_mfma_norm_kernel<KS, EPI, 2, true>), dim3(grid), dim3(256), shm2, s, a);
-                else if (nt == 3) hipLaunchKernelGGL((gemv_batch_mfma_norm_kernel<KS, EPI, 3, true>), dim3(grid), dim3(256), shm2, s, a);
-                else if (nt == 4) hipLaunchKernelGGL((gemv_batch_mfma_norm_kernel<KS, EPI, 4, true>), dim3(grid), dim3(256), shm2, s, a);
-                else { BatchGemvArgs an = a; an.ntiles = nt; hipLaunchKernelGGL((gemv_batch_mfma_norm_kernel<KS, EPI, 0, true>), dim3(grid), dim3(256), shm2, s, an); }   // 65..128 lanes: rolled pair loop
+            if (a.ntiles >= 2 && b.norm_dual) {
+                // two panels + a pair of tiles' partial sums (66 + 8..16 KB at K = 1024; norm_dual_prepare raised the limit); three and
+                // four tiles repeat the scheme per pair
+                with_value<2, 3, 4, 0>(a.ntiles, [&](auto nt) {
+                    hipLaunchKernelGGL((gemv_batch_mfma_norm_kernel<KS, EPI, decltype(nt)::value, true>), dim3(grid), dim3(256), norm_panel_lds(a.K, NR, 2), s, a);
+                });
                 return 0;
             }
         }
-        auto one = [&](auto ntc) -> int {
-            constexpr int NTC = decltype(ntc)::value;
-            auto kern = gemv_batch_mfma_norm_kernel<KS, EPI, NTC>;
-            if (shm > 48 * 1024) HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm));
-            BatchGemvArgs an = a; an.ntiles = nt;
-            hipLaunchKernelGGL(kern, dim3(grid), dim3(256), shm, s, an);
+        return with_value<1, 2, 3, 4, 0>(a.ntiles, [&](auto nt) -> int {
+            constexpr auto kern = gemv_batch_mfma_norm_kernel<KS, EPI, decltype(nt)::value>;
+            if (!lds_limit_at_least<kern>(shm)) return fq3_fail_(FQ3_EHIP, "batch GEMV: could not raise the kernel's LDS limit");
+            hipLaunchKernelGGL(kern, dim3(grid), dim3(256), shm, s, a);
             return 0;
-        };
-        switch (nt) {
-            case 1: return one(std::integral_constant<int, 1>{});
-            case 2: return one(std::integral_constant<int, 2>{});
-            case 3: return one(std::integral_constant<int, 3>{});
-            case 4: return one(std::integral_constant<int, 4>{});
-            default: return one(std::integral_constant<int, 0>{});          // 65..128 lanes: rolled tile loop
-        }
-    };
-    switch (a.K / 128) {                      // hidden sizes: 256 (tests), 512, 1024 (0.6B, predictor), 2048 (1.7B)
-        case 2: return go(std::integral_constant<int, 2>{});
-        case 4: return go(std::integral_constant<int, 4>{});
-        case 8: return go(std::integral_constant<int, 8>{});
-        case 16: return go(std::integral_constant<int, 16>{});
-        default: return -1000;
-    }
+        });
+    });
 }
-static thread_local int g_batch_skinny = 1;      // set per enqueue from fq3_batch::use_skinny
 // does this residual GEMV run on the weight-stationary kernel (whose epilogue can leave the rows' sum-of-squares partials)?
-static bool residual_on_skinny(const BatchGemvArgs& a) {
-    return g_batch_skinny && (a.B > kTokTile || g_batch_skinny >= 2) && !a.bias && skinny_k_ok(a.K) && a.N % 32 == 0 && a.x_stride % 8 == 0 &&
+static bool residual_on_skinny(const fq3_batch& b, const BatchGemvArgs& a) {
+    return b.use_skinny && (a.B > kTokTile || b.use_skinny >= 2) && !a.bias && skinny_k_ok(a.K) && a.N % 32 == 0 && a.x_stride % 8 == 0 &&
            a.y_stride % 4 == 0 && a.res_stride % 4 == 0;
 }
 template <int EPI>
-static int launch_gemv_batch_mfma_plain(const BatchGemvArgs& a, hipStream_t s) {
+static int launch_gemv_batch_mfma_plain(const fq3_batch& b, const BatchGemvArgs& a, hipStream_t s) {
     // 17..32 lanes, residual epilogue (o_proj, down: N = hidden only -- 64 or 128 workgroups of the one-row-block-per-workgroup GEMV, each
     // re-reading every lane's K-long token row): the prefill's weight-stationary kernel splits the two token tiles over workgroups and
     // K over 8 waves with per-wave LDS staging (skinny_gemm.cuh); measured 12.1 -> ~8 us (down) and 9.3 -> ~6.5 us (o_proj) per launch
     if constexpr (EPI == EPI_RESIDUAL) {
-        if (residual_on_skinny(a)) {
+        if (residual_on_skinny(b, a)) {
             SkinnyArgs k{};
             k.ssq_out = a.ssq_out; k.ssq_ld = a.N / 16;
             k.X = reinterpret_cast<const bf16_t*>(a.x); k.ldx = a.x_stride; k.M = a.B; k.W = reinterpret_cast<const bf16_t*>(a.W); k.N = a.N;
             k.res = reinterpret_cast<const bf16_t*>(a.res); k.ldr = a.res_stride; k.Y = reinterpret_cast<bf16_t*>(a.y); k.ldy = a.y_stride;
-            if (g_batch_packed) k.Wp = reinterpret_cast<const bf16_t*>(fq3_packed_find_(a.W, 0));
+            if (b.packed) k.Wp = reinterpret_cast<const bf16_t*>(fq3_packed_find_(a.W, 0));
             skinny_launch<SK_RESIDUAL>(k, a.K, s);
             return 0;
         }
     }
-    const int grid = (a.N + 15) / 16;
-    auto go = [&](auto ks, auto nw) -> int {
-        constexpr int KS = decltype(ks)::value, NW = decltype(nw)::value;
-        BatchGemvArgs an = a;
-        an.Wp = (g_batch_packed && a.N % 16 == 0) ? fq3_packed_find_(a.W, 0) : nullptr;      // fragment-major copy in 16-row blocks, where there is one
-        an.ntiles = (a.B + kTokTile - 1) / kTokTile;         // token tiles
-        switch (an.ntiles) {
-            case 1: hipLaunchKernelGGL((gemv_batch_mfma_plain_kernel<KS, NW, EPI, 1>), dim3(grid), dim3(64 * NW), 0, s, an); break;
-            case 2: hipLaunchKernelGGL((gemv_batch_mfma_plain_kernel<KS, NW, EPI, 2>), dim3(grid), dim3(64 * NW), 0, s, an); break;
-            case 3: hipLaunchKernelGGL((gemv_batch_mfma_plain_kernel<KS, NW, EPI, 3>), dim3(grid), dim3(64 * NW), 0, s, an); break;
-            case 4: hipLaunchKernelGGL((gemv_batch_mfma_plain_kernel<KS, NW, EPI, 4>), dim3(grid), dim3(64 * NW), 0, s, an); break;
-            default: hipLaunchKernelGGL((gemv_batch_mfma_plain_kernel<KS, NW, EPI, 0>), dim3(grid), dim3(64 * NW), 0, s, an); break;   // 65..128 lanes
-        }
-        return 0;
-    };
-#define FQ3_PLAIN(KS, NW) return go(std::integral_constant<int, KS>{}, std::integral_constant<int, NW>{})
-    switch (a.K) {                            // o_proj (q_dim), down (intermediate), small_to_mtp projection (hidden)
-        case 256: FQ3_PLAIN(2, 4);            // tiny test config
-        case 512: FQ3_PLAIN(4, 4);
-        case 768: FQ3_PLAIN(6, 4);
-        case 1024: FQ3_PLAIN(8, 4);
-        case 2048: FQ3_PLAIN(8, 8);
-        case 3072: FQ3_PLAIN(12, 8);
-        case 4096: FQ3_PLAIN(16, 8);
-        case 6144: FQ3_PLAIN(24, 8);
-        default: return -1000;
-    }
-#undef FQ3_PLAIN
+    if (!one_of<256, 512, 768, 1024, 2048, 3072, 4096, 6144>(a.K)) return -1000;      // o_proj (q_dim), down (intermediate), small_to_mtp projection (hidden); 256: tiny test config
+    BatchGemvArgs an = a;
+    an.Wp = (b.packed && a.N % 16 == 0) ? fq3_packed_find_(a.W, 0) : nullptr;      // fragment-major copy in 16-row blocks, where there is one
+    an.ntiles = (a.B + kTokTile - 1) / kTokTile;             // token tiles: 1..4 unrolled, more (65..128 lanes) by the rolled loop, NT = 0
+    with_value<256, 512, 768, 1024, 2048, 3072, 4096, 6144>(a.K, [&](auto k) {
+        constexpr int NW = decltype(k)::value <= 1024 ? 4 : 8, KS = decltype(k)::value / (32 * NW);      // K = 32 KS columns for each of NW waves
+        with_value<1, 2, 3, 4, 0>(an.ntiles, [&](auto nt) {
+            hipLaunchKernelGGL((gemv_batch_mfma_plain_kernel<KS, NW, EPI, decltype(nt)::value>), dim3((a.N + 15) / 16), dim3(64 * NW), 0, s, an);
+        });
+    });
+    return 0;
 }
-static thread_local int g_batch_mfma = 0;        // set per enqueue from fq3_batch::use_mfma
 template <int PRO, int EPI>
-static int launch_gemv_batch(const fq3_ctx* c, const BatchGemvArgs& a, hipStream_t s) {
-    if (g_batch_mfma && c->cfg.dtype == FQ3_BF16) {
+static int launch_gemv_batch(const fq3_batch& b, const BatchGemvArgs& a, hipStream_t s) {
+    const bool bf16 = b.lanes[0]->cfg.dtype == FQ3_BF16;
+    if (b.use_mfma && bf16) {
         int r;
-        if constexpr (PRO == PRO_NORM) r = launch_gemv_batch_mfma_norm<EPI>(a, s);
-        else r = launch_gemv_batch_mfma_plain<EPI>(a, s);
+        if constexpr (PRO == PRO_NORM) r = launch_gemv_batch_mfma_norm<EPI>(b, a, s);
+        else r = launch_gemv_batch_mfma_plain<EPI>(b, a, s);
         if (r != -1000) return r;
     }
-    return c->cfg.dtype == FQ3_BF16 ? launch_gemv_batch_t<bf16_t, PRO, EPI>(a, 2, s) : launch_gemv_batch_t<float, PRO, EPI>(a, 4, s);
+    return bf16 ? launch_gemv_batch_t<bf16_t, PRO, EPI>(a, 2, s) : launch_gemv_batch_t<float, PRO, EPI>(a, 4, s);
 }
 
 struct BatchSrc { const void* x0; int x0_stride; int pos_imm; bool talker; bool kv_only_tail; bool pair = false; };
@@ -525,7 +480,7 @@ static int run_stack_batch(fq3_batch* b, const BatchSrc& src, hipStream_t s) {
     const int q_dim = d.n_heads * kHeadDim, kv_dim = d.n_kv_heads * kHeadDim;
     // RMSNorm inside the GEMM pair (the lane counts that take the weight-stationary form of the normalising GEMVs): the residual GEMMs
     // leave the sum-of-squares partials of the rows of `h`, the next normalising GEMM picks them up
-    const bool fuse = b->norm_fused && g_batch_mfma && c->cfg.dtype == FQ3_BF16 && g_batch_norm_skinny && B > g_batch_norm_skinny_above &&
+    const bool fuse = b->norm_fused && b->use_mfma && c->cfg.dtype == FQ3_BF16 && b->norm_skinny && B > b->norm_skinny_above &&
                       skinny_norm_ok(d.hidden, B) && b->Hm % 64 == 0;
     const float* h_ssq = nullptr;                      // partials of the current rows of b->h, or null
     b->h_ssq = nullptr;
@@ -537,7 +492,7 @@ static int run_stack_batch(fq3_batch* b, const BatchSrc& src, hipStream_t s) {
         g.ssq_in = i == 0 ? nullptr : h_ssq;
         g.B = B; g.eps = d.rms_eps; g.W = w.qkv; g.N = q_dim + 2 * kv_dim; g.K = d.hidden; g.x = xin; g.x_stride = xin_stride;
         g.norm_w = w.input_norm; g.y = b->qkv; g.y_stride = b->qkvm; g.xn_ws = b->xn;
-        if (int r = launch_gemv_batch<PRO_NORM, EPI_STORE>(c, g, s)) return r;
+        if (int r = launch_gemv_batch<PRO_NORM, EPI_STORE>(*b, g, s)) return r;
         const bool tail_skip = src.kv_only_tail && i == d.n_layers - 1;
         AttnArgs a{};
         a.qkv = b->qkv; a.q_norm_w = w.q_norm; a.k_norm_w = w.k_norm; a.eps = d.rms_eps;
@@ -545,7 +500,7 @@ static int run_stack_batch(fq3_batch* b, const BatchSrc& src, hipStream_t s) {
         BatchGemvArgs o{};
         o.B = B; o.W = w.o; o.N = d.hidden; o.K = q_dim; o.y = b->h; o.y_stride = b->Hm; o.res = xin; o.res_stride = xin_stride;
         o.x_stride = b->qkvm;
-        o.ssq_out = fuse && residual_on_skinny(o) ? b->ssq : nullptr;
+        o.ssq_out = fuse && residual_on_skinny(*b, o) ? b->ssq : nullptr;
         if (talker) {
             a.max_seq = c->tk.max_seq; a.part = b->part;
             const dim3 grid(d.n_kv_heads, c->tk.workers, B);
@@ -553,27 +508,25 @@ static int run_stack_batch(fq3_batch* b, const BatchSrc& src, hipStream_t s) {
             const LaneTabs* ttp = b->d_ttab; const LaneTab* tp = b->d_tab;
             // from 64 lanes (bf16, matrix-core path): one workgroup per (kv head, lane) that writes the final head outputs -- no partial
             // slots, no merge launch (batch_kernels.cuh::attn_decode_lane_kernel; "attn_lane": 0 = never, 1 = from attn_lane_from lanes, 2 = always)
-            const bool lane_attn = b->attn_lane == 2 || (b->attn_lane == 1 && g_batch_mfma && c->cfg.dtype == FQ3_BF16 && B >= b->attn_lane_from);
+            const bool lane_attn = b->attn_lane == 2 || (b->attn_lane == 1 && b->use_mfma && c->cfg.dtype == FQ3_BF16 && B >= b->attn_lane_from);
             if (lane_attn) {
                 a.out = b->attn_out;
                 const dim3 lgrid(d.n_kv_heads, B);
-                auto go = [&](auto ni) {
-                    constexpr int NI = decltype(ni)::value;
-                    if (rep == 1) hipLaunchKernelGGL((attn_decode_lane_kernel<T, 1, NI>), lgrid, dim3(256), 0, s, a, kvp, ttp, tp, b->qkvm, b->rope_now, b->qkvm);
-                    else if (rep == 2) hipLaunchKernelGGL((attn_decode_lane_kernel<T, 2, NI>), lgrid, dim3(256), 0, s, a, kvp, ttp, tp, b->qkvm, b->rope_now, b->qkvm);
-                    else hipLaunchKernelGGL((attn_decode_lane_kernel<T, 4, NI>), lgrid, dim3(256), 0, s, a, kvp, ttp, tp, b->qkvm, b->rope_now, b->qkvm);
-                };
-                if (b->attn_lane_keys == 8) go(std::integral_constant<int, 2>{}); else go(std::integral_constant<int, 4>{});
+                with_value<8, 16>(b->attn_lane_keys, [&](auto keys) {
+                    with_value<1, 2, 4>(rep, [&](auto r) {
+                        hipLaunchKernelGGL((attn_decode_lane_kernel<T, decltype(r)::value, decltype(keys)::value / 4>), lgrid, dim3(256), 0, s, a, kvp, ttp, tp, b->qkvm, b->rope_now, b->qkvm);
+                    });
+                });
                 o.x = b->attn_out; o.x_stride = b->qkvm;
-                if (int r = launch_gemv_batch<PRO_PLAIN, EPI_RESIDUAL>(c, o, s)) return r;
+                if (int r = launch_gemv_batch<PRO_PLAIN, EPI_RESIDUAL>(*b, o, s)) return r;
             } else {
-            if (rep == 1) hipLaunchKernelGGL((attn_decode_batch_kernel<T, 1>), grid, dim3(256), 0, s, a, kvp, ttp, tp, b->qkvm, b->rope_now, b->part_stride);
-            else if (rep == 2) hipLaunchKernelGGL((attn_decode_batch_kernel<T, 2>), grid, dim3(256), 0, s, a, kvp, ttp, tp, b->qkvm, b->rope_now, b->part_stride);
-            else hipLaunchKernelGGL((attn_decode_batch_kernel<T, 4>), grid, dim3(256), 0, s, a, kvp, ttp, tp, b->qkvm, b->rope_now, b->part_stride);
+            with_value<1, 2, 4>(rep, [&](auto r) {
+                hipLaunchKernelGGL((attn_decode_batch_kernel<T, decltype(r)::value>), grid, dim3(256), 0, s, a, kvp, ttp, tp, b->qkvm, b->rope_now, b->part_stride);
+            });
             hipLaunchKernelGGL((combine_batch_kernel<T>), dim3((q_dim / 8 + 255) / 256, B), dim3(256), 0, s, (const float*)b->part, b->part_stride,
                                c->tk.workers, rep, q_dim, (T*)b->attn_out, b->qkvm);
             o.x = b->attn_out; o.x_stride = b->qkvm;
-            if (int r = launch_gemv_batch<PRO_PLAIN, EPI_RESIDUAL>(c, o, s)) return r;
+            if (int r = launch_gemv_batch<PRO_PLAIN, EPI_RESIDUAL>(*b, o, s)) return r;
             }
         } else {
             int rp = src.pos_imm; const int rl = c->wt.pred_rope_len;
@@ -584,9 +537,10 @@ static int run_stack_batch(fq3_batch* b, const BatchSrc& src, hipStream_t s) {
             // bit-identical to the one-wave-per-q-head form, 0)
             auto pred_attn = [&](const AttnArgs& aa, int lanes, int stride) {
                 const LaneKV* kvp = b->d_pkv + i;
-                if (b->pred_attn_group && rep == 1) hipLaunchKernelGGL((attn_pred_group_batch_kernel<T, 1>), dim3(d.n_kv_heads, lanes), dim3(64), 0, s, aa, kvp, stride, stride);
-                else if (b->pred_attn_group && rep == 2) hipLaunchKernelGGL((attn_pred_group_batch_kernel<T, 2>), dim3(d.n_kv_heads, lanes), dim3(64), 0, s, aa, kvp, stride, stride);
-                else if (b->pred_attn_group && rep == 4) hipLaunchKernelGGL((attn_pred_group_batch_kernel<T, 4>), dim3(d.n_kv_heads, lanes), dim3(64), 0, s, aa, kvp, stride, stride);
+                if (b->pred_attn_group && one_of<1, 2, 4>(rep))
+                    with_value<1, 2, 4>(rep, [&](auto r) {
+                        hipLaunchKernelGGL((attn_pred_group_batch_kernel<T, decltype(r)::value>), dim3(d.n_kv_heads, lanes), dim3(64), 0, s, aa, kvp, stride, stride);
+                    });
                 else hipLaunchKernelGGL((attn_pred_batch_kernel<T>), dim3(d.n_heads, lanes), dim3(64), 0, s, aa, kvp, stride, stride);
             };
             if (src.pair) {
@@ -602,18 +556,18 @@ static int run_stack_batch(fq3_batch* b, const BatchSrc& src, hipStream_t s) {
             } else pred_attn(a, B, b->qkvm);
             if (tail_skip) break;
             o.x = b->attn_out; o.x_stride = b->qkvm;
-            if (int r = launch_gemv_batch<PRO_PLAIN, EPI_RESIDUAL>(c, o, s)) return r;
+            if (int r = launch_gemv_batch<PRO_PLAIN, EPI_RESIDUAL>(*b, o, s)) return r;
         }
         BatchGemvArgs m{};
         m.B = B; m.eps = d.rms_eps; m.W = w.gate_up; m.N = d.inter; m.K = d.hidden; m.x = b->h; m.x_stride = b->Hm;
         m.norm_w = w.post_norm; m.y = b->act; m.y_stride = b->Im; m.up_off = d.inter; m.xn_ws = b->xn;
         m.ssq_in = o.ssq_out;
-        if (int r = launch_gemv_batch<PRO_NORM, EPI_SWIGLU>(c, m, s)) return r;
+        if (int r = launch_gemv_batch<PRO_NORM, EPI_SWIGLU>(*b, m, s)) return r;
         BatchGemvArgs dn{};
         dn.B = B; dn.W = w.down; dn.N = d.hidden; dn.K = d.inter; dn.x = b->act; dn.x_stride = b->Im; dn.y = b->h; dn.y_stride = b->Hm;
         dn.res = b->h; dn.res_stride = b->Hm;
-        dn.ssq_out = fuse && residual_on_skinny(dn) ? b->ssq : nullptr;
-        if (int r = launch_gemv_batch<PRO_PLAIN, EPI_RESIDUAL>(c, dn, s)) return r;
+        dn.ssq_out = fuse && residual_on_skinny(*b, dn) ? b->ssq : nullptr;
+        if (int r = launch_gemv_batch<PRO_PLAIN, EPI_RESIDUAL>(*b, dn, s)) return r;
         h_ssq = dn.ssq_out;
     }
     b->h_ssq = h_ssq;                                  // for the head that reads `h` next
@@ -633,7 +587,7 @@ static int enqueue_batch_frame_t(fq3_batch* b, hipStream_t s) {
     // the two-token prefill as one pass over 2 B rows ("pred_pair": default from the lane count at which every GEMM of the pass is the
     // weight-stationary kernel anyway -- above norm_skinny_above lanes, bf16, matrix-core path -- where a row's arithmetic does not
     // depend on the row count: bit-identical to the two passes; 0 = two passes at every lane count)
-    const bool pair = b->pred_pair && b->rows2 == 2 && g_batch_mfma && c->cfg.dtype == FQ3_BF16 && g_batch_norm_skinny && g_batch_skinny && B > g_batch_norm_skinny_above &&
+    const bool pair = b->pred_pair && b->rows2 == 2 && b->use_mfma && c->cfg.dtype == FQ3_BF16 && b->norm_skinny && b->use_skinny && B > b->norm_skinny_above &&
                       2 * B <= kSkinnyMaxRows && skinny_k_ok(p.hidden) && p.hidden <= 2048;
     for (int pass = 0; pass < G; ++pass) {
         const bool pp = pair && pass == 0;                 // this iteration runs token A and token B together
@@ -644,7 +598,7 @@ static int enqueue_batch_frame_t(fq3_batch* b, hipStream_t s) {
             BatchGemvArgs g{};
             g.B = pp ? 2 * B : B; g.W = c->wt.proj_w; g.bias = c->wt.proj_b; g.N = p.hidden; g.K = H; g.x = x_talker; g.x_stride = x_stride;
             g.y = b->pred_x; g.y_stride = p.hidden;
-            if (int r = launch_gemv_batch<PRO_PLAIN, EPI_STORE>(c, g, s)) return r;
+            if (int r = launch_gemv_batch<PRO_PLAIN, EPI_STORE>(*b, g, s)) return r;
             x0 = b->pred_x; x0_stride = p.hidden;
         }
         BatchSrc src{x0, x0_stride, pass, false, pass == 0 && !pp, pp};
@@ -659,7 +613,7 @@ static int enqueue_batch_frame_t(fq3_batch* b, hipStream_t s) {
         hg.x = pp ? (const void*)((const T*)b->h + b->Hm) : (const void*)b->h; hg.x_stride = pp ? 2 * b->Hm : b->Hm;
         hg.norm_w = c->wt.predictor_final_norm; hg.y = lg; hg.y_stride = (int)lstride; hg.xn_ws = b->xn;
         hg.ssq_in = pp ? nullptr : b->h_ssq;              // (the partials are indexed by packed row: the strided read of the pair pass normalises in its own launch)
-        if (int r = launch_gemv_batch<PRO_NORM, EPI_STORE>(c, hg, s)) return r;
+        if (int r = launch_gemv_batch<PRO_NORM, EPI_STORE>(*b, hg, s)) return r;
         const T* next_emb = cb + 1 < G - 1 ? (const T*)c->pemb[cb] : nullptr;
         if (Vp <= 2048) hipLaunchKernelGGL((sample_pred_batch_kernel<T, 1>), dim3(B), dim3(256), 0, s, tab, lf, (const T*)lg, lstride, Vp, cb, G, next_emb, (T*)b->pred_next, H);
         else hipLaunchKernelGGL((sample_pred_batch_kernel<T, 2>), dim3(B), dim3(256), 0, s, tab, lf, (const T*)lg, lstride, Vp, cb, G, next_emb, (T*)b->pred_next, H);
@@ -675,7 +629,7 @@ static int enqueue_batch_frame_t(fq3_batch* b, hipStream_t s) {
     g.B = B; g.eps = t.rms_eps; g.W = c->wt.codec_head; g.N = t.vocab; g.K = H; g.x = b->h; g.x_stride = b->Hm;
     g.norm_w = c->wt.talker_final_norm; g.y = b->logits; g.y_stride = t.vocab; g.xn_ws = b->xn;
     g.xn_out = b->d_tab->past_hidden;                  // (an address inside the device table: never dereferenced on the host)
-    if (int r = launch_gemv_batch<PRO_NORM, EPI_STORE>(c, g, s)) return r;
+    if (int r = launch_gemv_batch<PRO_NORM, EPI_STORE>(*b, g, s)) return r;
     if (t.vocab <= 2048) hipLaunchKernelGGL((sample_talker_batch_kernel<T, 1>), dim3(B), dim3(256), 0, s, tab, lf, (const T*)b->logits, t.vocab, G);
     else hipLaunchKernelGGL((sample_talker_batch_kernel<T, 2>), dim3(B), dim3(256), 0, s, tab, lf, (const T*)b->logits, t.vocab, G);
     return 0;
@@ -701,12 +655,6 @@ static int sync_forced(fq3_batch* b, hipStream_t s) {
     return 0;
 }
 static int enqueue_batch_frame(fq3_batch* b, hipStream_t s) {
-    g_batch_mfma = b->use_mfma;
-    g_batch_skinny = b->use_skinny;
-    g_batch_norm_dual = b->norm_dual;
-    g_batch_norm_skinny = b->norm_skinny;
-    g_batch_norm_skinny_above = b->norm_skinny_above;
-    g_batch_packed = b->packed;
     return b->lanes[0]->cfg.dtype == FQ3_BF16 ? enqueue_batch_frame_t<bf16_t>(b, s) : enqueue_batch_frame_t<float>(b, s);
 }
 

@@ -454,9 +454,8 @@ static int decode_t(fq3_codec* c, const int64_t* codes, int NS, int Tn, int64_t 
         if (spw == 0 || C % 8) return cfail(FQ3_EUNSUPPORTED, "output conv: channel count not supported (multiple of 8, window must fit the LDS)");
         o.run = [=](int lo) {
             if (lo >= R) return;
-            auto kern = final_conv_kernel<T>;
-            if (shm > 48 * 1024) (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm);
-            hipLaunchKernelGGL(kern, dim3((R - lo + spw - 1) / spw, NS), dim3(256), shm, s, xin, fw, fb, pcm, lo, R, C, spw);
+            (void)lds_limit_at_least<final_conv_kernel<T>>(shm);
+            hipLaunchKernelGGL(final_conv_kernel<T>, dim3((R - lo + spw - 1) / spw, NS), dim3(256), shm, s, xin, fw, fb, pcm, lo, R, C, spw);
         };
         P.add(std::move(o));
     }

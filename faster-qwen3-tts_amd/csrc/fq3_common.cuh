@@ -250,4 +250,34 @@ template <int NW> __device__ __forceinline__ float block_max(float v, float* red
     return t;
 }
 
+// ---- host-side launch helpers -------------------------------------------------------------------
+// with_value<1, 2, 4>(v, f): f(std::integral_constant<int, V>{}) for the V of the list that equals v, the LAST one for any other v
+// (the ladders' default: the rolled variant, the largest instantiation); returns what f returns.
+template <int V0, int... Vs, typename F>
+inline auto with_value(int v, F&& f) {
+    if constexpr (sizeof...(Vs) == 0) return f(std::integral_constant<int, V0>{});
+    else return v == V0 ? f(std::integral_constant<int, V0>{}) : with_value<Vs...>(v, f);
+}
+template <int... Vs> constexpr bool one_of(int v) { return ((v == Vs) || ...); }
+
+constexpr int kSkMaxDevices = 16;           // devices a process may drive (the LDS limit of a kernel is a per-device setting)
+constexpr size_t kLdsNoRaise = 48 * 1024;   // dynamic LDS a launch may ask for without the kernel's limit having been raised
+// Makes the current device's dynamic-LDS limit of kernel Kern at least `bytes`; returns whether it is.  The only place that sets the
+// attribute.  Per instantiation and device it remembers the largest size granted and the smallest refused (one instantiation is asked
+// for different sizes: the VALU batch GEMV's grow with the lane count), so repeat calls cost one hipGetDevice and a refusal is not
+// retried on every launch; a device outside the table is asked every time.  Launchers that ignore the result leave the refused launch's
+// error pending for the hipGetLastError check of the entry point that issued it, which reports it instead of returning stale output.
+template <auto Kern>
+inline bool lds_limit_at_least(size_t bytes) {
+    if (bytes <= kLdsNoRaise) return true;
+    static size_t granted[kSkMaxDevices] = {}, refused[kSkMaxDevices] = {};
+    int dev = -1;
+    const bool known = hipGetDevice(&dev) == hipSuccess && dev >= 0 && dev < kSkMaxDevices;
+    if (known && bytes <= granted[dev]) return true;
+    if (known && refused[dev] && bytes >= refused[dev]) return false;
+    const bool ok = hipFuncSetAttribute(reinterpret_cast<const void*>(Kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes) == hipSuccess;
+    if (known) (ok ? granted : refused)[dev] = bytes;
+    return ok;
+}
+
 }  // namespace fq3

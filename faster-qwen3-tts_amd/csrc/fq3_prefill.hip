@@ -435,16 +435,7 @@ __global__ __launch_bounds__(256) void qk_norm_rope_kv_pack_kernel(T* qkv, const
     DT<T>::st(dst + lane + 64, x1);
 }
 
-// (the LDS limit of a kernel is a per-DEVICE setting: remembered per device, for a process that drives more than one)
-static bool flash_small_prepare() {
-    static int state[kSkMaxDevices] = {};                 // 0 = not asked yet, 1 = raised, -1 = failed
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= kSkMaxDevices) return false;
-    if (!state[dev])
-        state[dev] = hipFuncSetAttribute(reinterpret_cast<const void*>(&flash_prefill_small_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                         (int)kFsLdsBytes) == hipSuccess ? 1 : -1;
-    return state[dev] > 0;
-}
+static bool flash_small_prepare() { return lds_limit_at_least<flash_prefill_small_kernel>(kFsLdsBytes); }
 // every sequence short enough, one pool, bf16: the packed attention kernels take the whole group (false: the per-prompt launches)
 static bool pack_attention_ok(fq3_ctx* const* cs, int n, const int* L) {
     if (n < 1 || n > kMaxPack || cs[0]->cfg.dtype != FQ3_BF16 || !cs[0]->opt_flash_prefill || !cs[0]->opt_flash_small) return false;

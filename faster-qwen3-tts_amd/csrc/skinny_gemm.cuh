@@ -71,7 +71,6 @@ inline bool skinny_k_ok(int K) { return K == 1024 || K == 2048 || K == 3072 || K
 inline bool skinny_norm_ok(int K, int M) { return (K == 1024 || K == 2048) && M >= 1 && M <= 256; }
 
 // shapes the fragment-major copy serves (the kernels' own: K a multiple of 1024 the kernels are built for, whole 16-row blocks)
-constexpr int kSkMaxDevices = 16;           // devices a process may drive (the LDS limit of a kernel is a per-device setting)
 inline bool skinny_pack_ok(int N, int K) { return skinny_k_ok(K) && N % 16 == 0 && N > 0; }
 
 #ifdef FQ3_SKINNY_EXTERN
@@ -426,17 +425,11 @@ inline void skinny_pack(const bf16_t* W, bf16_t* P, int N, int K, int swiglu_I, 
 }
 
 
-// the kernels need more than the default 64 KB of dynamic LDS: raised once per process and instantiation
+// the kernels need more dynamic LDS than a launch gets unasked: raised once per device and instantiation (lds_limit_at_least)
 template <int K, int RB, int EPI, bool NORM = false>
 inline bool skinny_attr() {
-    constexpr size_t shm = skinny_lds_bytes(RB);
-    static_assert(shm <= 160 * 1024, "LDS");
-    static int state[kSkMaxDevices] = {};                 // per device: 0 = not asked yet, 1 = raised, -1 = failed
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= kSkMaxDevices) return false;
-    if (!state[dev])
-        state[dev] = hipFuncSetAttribute(reinterpret_cast<const void*>(&skinny_gemm_kernel<K, RB, EPI, NORM>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm) == hipSuccess ? 1 : -1;
-    return state[dev] > 0;
+    static_assert(skinny_lds_bytes(RB) <= 160 * 1024, "LDS");
+    return lds_limit_at_least<skinny_gemm_kernel<K, RB, EPI, NORM>>(skinny_lds_bytes(RB));
 }
 template <int K, int RB, int EPI, bool NORM = false>
 inline void skinny_go(const SkinnyArgs& a, hipStream_t s) {
@@ -482,23 +475,19 @@ inline void skinny_launch(const SkinnyArgs& a0, int K, hipStream_t s, int rb_for
     // the normalising form: a.ssq names the rows' sum-of-squares partials (K / 16 per row); K = hidden = 1024 or 2048, M <= kSkNormMaxRows
     if constexpr (EPI != SK_RESIDUAL) {
         if (a.ssq) {
-#define FQ3_SKN(KK) do { if (RB == 3) skinny_go<KK, 3, EPI, true>(a, s); else if (RB == 2) skinny_go<KK, 2, EPI, true>(a, s); \
-                         else skinny_go<KK, 1, EPI, true>(a, s); } while (0)
-            if (K == 1024) FQ3_SKN(1024); else FQ3_SKN(2048);
-#undef FQ3_SKN
+            with_value<1024, 2048>(K, [&](auto k) {
+                with_value<3, 2, 1>(RB, [&](auto rb) { skinny_go<decltype(k)::value, decltype(rb)::value, EPI, true>(a, s); });
+            });
             return;
         }
     }
-#define FQ3_SK(KK) do { if constexpr (KK <= 2048) { if (RB == 3) { skinny_go<KK, 3, EPI>(a, s); break; } } \
-                        if constexpr (KK <= 3072) { if (RB == 2) { skinny_go<KK, 2, EPI>(a, s); break; } } \
-                        skinny_go<KK, 1, EPI>(a, s); } while (0)
-    switch (K) {
-        case 1024: FQ3_SK(1024); break;
-        case 2048: FQ3_SK(2048); break;
-        case 3072: FQ3_SK(3072); break;
-        default:   FQ3_SK(6144); break;
-    }
-#undef FQ3_SK
+    with_value<1024, 2048, 3072, 6144>(K, [&](auto k) {
+        with_value<3, 2, 1>(RB, [&](auto rb) {
+            constexpr int KK = decltype(k)::value, R = decltype(rb)::value;
+            if constexpr (R == 1 || (R == 2 && KK <= 3072) || (R == 3 && KK <= 2048)) skinny_go<KK, R, EPI>(a, s);      // (the register budget above)
+            else skinny_go<KK, 1, EPI>(a, s);
+        });
+    });
 }
 
 

@@ -88,6 +88,36 @@ def test_lanes_equal_single_stream(dtype, graph):
     assert n == 0 and d
 
 
+def test_one_gemv_instantiation_asked_for_growing_lds():
+    """The VALU batch GEMV stages `group` x K tokens in dynamic LDS, so ONE instantiation asks for more as the lane count grows: with
+    fp32 and intermediate size 2048 the residual `down` GEMV (K = 2048) takes 2 x 2048 x 4 = 16 KB for 2 lanes and 8 x 2048 x 4 = 64 KB
+    for 8 (kGroupLanes) -- above what a launch gets without the kernel's limit being raised.  The smaller batch runs FIRST in this
+    process: a launcher that remembered "limit raised" rather than "raised to N bytes" would have the 8-lane launch refused.  A
+    7-lane batch in between (56 KB) makes that hold also for a launcher that leaves small requests alone: it is raised once, to less
+    than the 8 lanes need."""
+    from fq3hip.engine import Fq3Batch
+    dtype = torch.float32
+    cfg = tiny_test_config(hidden=256, layers=1, pred_layers=1)
+    cfg.talker.intermediate_size = cfg.predictor.intermediate_size = 2048
+    W = synth_weights(cfg, 0, dtype)
+    utts = [_utterance(cfg, dtype, 21 + i, 12 + 3 * i, i % 3, 8, 8 if i % 2 else 3, i % 2 == 0) for i in range(8)]
+    solo = _engines(cfg, W, dtype, 1)[0]
+    ref = [_alone(solo, cfg, u, 8) for u in utts]
+    for graph in (False, True):
+        for n_lanes in (2, 7, 8):
+            lanes = _engines(cfg, W, dtype, n_lanes)
+            batch = Fq3Batch(lanes)
+            for e, u in zip(lanes, utts):
+                _arm(e, cfg, u)
+            if graph:
+                batch.graph_capture()
+            batch.frames(8)
+            for i, (e, (codes, done)) in enumerate(zip(lanes, ref)):
+                n, d = e.decode_poll()
+                assert n == codes.shape[0] and d == done, f"{n_lanes} lanes, graph={graph}, lane {i}: {n} frames (done={d}) vs {codes.shape[0]} alone (done={done})"
+                assert torch.equal(e.decode_codes(0, n).cpu(), codes), f"{n_lanes} lanes, graph={graph}: lane {i} ids differ from the single-stream run"
+
+
 @pytest.mark.parametrize("dtype", DTYPES)
 @pytest.mark.parametrize("n_lanes,n_armed", [(16, 13), (32, 27), (48, 41), (64, 59), (96, 83), (128, 121)])
 def test_sixteen_lanes_equal_single_stream(dtype, n_lanes, n_armed):

@@ -326,7 +326,7 @@ __global__ __launch_bounds__(256) void attn_decode_lane_kernel(AttnArgs a, const
             num = fmaf(ww, wo[w][h][d], num);
             den = fmaf(ww, wl[w][h], den);
         }
-        DT<T>::st(out + e, num * (1.0f / den));
+        DT<T>::st(out + e, num * (den > 0.f ? 1.0f / den : 0.f));          // no valid key at all (pos < n_pad): zeros, as the merge
     }
 }
 

@@ -81,7 +81,7 @@ __device__ __forceinline__ void combine_finish(CombineRegs& c, int n_part, float
         const float w = __expf(c.pm[s] - Mx);
         na += c.oa[s] * w; nb += c.ob[s] * w; den = fmaf(w, c.pl[s], den);
     }
-    const float inv = 1.0f / den;
+    const float inv = den > 0.f ? 1.0f / den : 0.f;      // every slot empty (a token below n_pad has no valid key): zeros, not 0 / 0
     f[0] = na.x * inv; f[1] = na.y * inv; f[2] = na.z * inv; f[3] = na.w * inv;
     f[4] = nb.x * inv; f[5] = nb.y * inv; f[6] = nb.z * inv; f[7] = nb.w * inv;
 #pragma unroll
@@ -516,6 +516,8 @@ __device__ __forceinline__ void attn_pred_body(const AttnArgs& a, int head) {
     const float sn[8] = {sgn * sn0.x, sgn * sn0.y, sgn * sn0.z, sgn * sn0.w, sgn * sn1.x, sgn * sn1.y, sgn * sn1.z, sgn * sn1.w};
     // head RMSNorm + RoPE; the rotate_half partner of dim d (d +- 64) lives in lane c ^ 8 of the same row
     auto norm_rope = [&](const Raw8<T>& raw, const Raw8<T>& wraw, float (&out)[8]) {
+#pragma clang fp contract(off)      // fp32: rnd2 is a no-op, and a product fused into the RoPE sum (which of the two is the compiler's
+                                    // choice per kernel) would break the bit identity of the per-head and the group form
         float x[8], w[8];
         unpack(raw, x); unpack(wraw, w);
         float ss = 0.f;
@@ -627,6 +629,8 @@ __device__ __forceinline__ void attn_pred_group_body(const AttnArgs& a, int g) {
     const float cs[8] = {cs0.x, cs0.y, cs0.z, cs0.w, cs1.x, cs1.y, cs1.z, cs1.w};
     const float sn[8] = {sgn * sn0.x, sgn * sn0.y, sgn * sn0.z, sgn * sn0.w, sgn * sn1.x, sgn * sn1.y, sgn * sn1.z, sgn * sn1.w};
     auto norm_rope = [&](const Raw8<T>& raw, const Raw8<T>& wraw, float (&out)[8]) {
+#pragma clang fp contract(off)      // fp32: rnd2 is a no-op, and a product fused into the RoPE sum (which of the two is the compiler's
+                                    // choice per kernel) would break the bit identity of the per-head and the group form
         float x[8], w[8];
         unpack(raw, x); unpack(wraw, w);
         float ss = 0.f;

@@ -16,6 +16,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(os.path.dirname(_HERE), "lib", "libfq3hip.so")
 
 FQ3_BF16, FQ3_F32, FQ3_BF16X2 = 0, 1, 2
+FQ3_PCM_F32, FQ3_PCM_S16, FQ3_PCM_MULAW, FQ3_PCM_ALAW = 0, 1, 2, 3
 FQ3_OK, FQ3_EINVAL, FQ3_EHIP, FQ3_ESTATE, FQ3_ETOOLONG, FQ3_EUNSUPPORTED, FQ3_ENOMEM = 0, -1, -2, -3, -4, -5, -6
 
 vp = C.c_void_p
@@ -68,6 +69,10 @@ class CodecConfig(C.Structure):
                 ("n_layers", i32), ("n_heads", i32), ("head_dim", i32), ("sliding_window", i32),
                 ("rms_eps", C.c_float), ("n_upsample", i32), ("upsampling_ratios", i32 * 4), ("n_rates", i32),
                 ("upsample_rates", i32 * 8), ("decoder_dim", i32), ("max_frames", i32)]
+
+
+class AudioOutConfig(C.Structure):
+    _fields_ = [("in_rate", C.c_int), ("out_rate", C.c_int), ("format", C.c_int), ("zero_crossings", C.c_int)]
 
 
 class RefEncConfig(C.Structure):
@@ -158,6 +163,13 @@ SIGNATURES = {
     "fq3_refenc_num_frames": (C.c_int64, [vp, C.c_int64]),
     "fq3_refenc_encode": (C.c_int, [vp, vp, C.c_int64, vp, vp]),
     "fq3_refenc_speaker": (C.c_int, [vp, vp, C.c_int64, vp, vp, vp]),
+    "fq3_audio_out_design": (C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int),
+                                       C.POINTER(C.c_float), C.c_int64]),
+    "fq3_audio_out_count": (C.c_int64, [C.c_int, C.c_int, C.c_int, C.c_int64, C.c_int]),
+    "fq3_audio_out_create": (C.c_int, [C.POINTER(AudioOutConfig), C.POINTER(vp)]),
+    "fq3_audio_out_destroy": (C.c_int, [vp]),
+    "fq3_audio_out_reset": (C.c_int, [vp, vp]),
+    "fq3_audio_out_push": (C.c_int, [vp, vp, C.c_int64, C.c_int, vp, C.c_int64, C.POINTER(C.c_int64), vp]),
 }
 
 _lib = None

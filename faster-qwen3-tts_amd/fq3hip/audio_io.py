@@ -30,6 +30,32 @@ def wav_header(sample_rate: int, data_len: int = 0xFFFFFFFF) -> bytes:
             b"data" + struct.pack("<I", data_len))
 
 
+_G711_TAGS = {"mulaw": 7, "alaw": 6}      # WAVE_FORMAT_MULAW / WAVE_FORMAT_ALAW
+
+
+def wav_header_for(sample_rate: int, encoding: str, data_len: int = 0xFFFFFFFF) -> bytes:
+    """RIFF/WAVE header for mono audio in one of the output stage's byte encodings (``fq3hip/audio_out.py``): ``s16`` is
+    :func:`wav_header` (format tag 1, 16 bits); ``mulaw`` / ``alaw`` are G.711 (tag 7 / 6, 8 bits) in the non-PCM layout -- an 18-byte
+    ``fmt`` chunk and a ``fact`` chunk with the sample count.  ``data_len = 0xFFFFFFFF``: a stream of unknown size."""
+    if encoding == "s16":
+        return wav_header(sample_rate, data_len)
+    if encoding not in _G711_TAGS:
+        raise ValueError(f"no WAV header for encoding {encoding!r}: one of s16, mulaw, alaw")
+    unknown = data_len == 0xFFFFFFFF
+    riff = 0xFFFFFFFF if unknown else 50 + data_len + (data_len & 1)
+    return (b"RIFF" + struct.pack("<I", riff) + b"WAVE" + b"fmt " +
+            struct.pack("<IHHIIHHH", 18, _G711_TAGS[encoding], 1, sample_rate, sample_rate, 1, 8, 0) +
+            b"fact" + struct.pack("<II", 4, data_len) + b"data" + struct.pack("<I", data_len))
+
+
+def write_wav_encoded(path: str, data: np.ndarray, sample_rate: int, encoding: str) -> None:
+    """A file of already encoded samples (``s16`` int16, ``mulaw`` / ``alaw`` uint8), as the output stage hands them out."""
+    raw = np.ascontiguousarray(data).tobytes()
+    os.makedirs(os.path.dirname(path) or ".", exist_ok=True)
+    with open(path, "wb") as f:
+        f.write(wav_header_for(int(sample_rate), encoding, len(raw)) + raw + (b"\x00" if len(raw) & 1 else b""))
+
+
 def to_wav_bytes(pcm: np.ndarray, sample_rate: int) -> bytes:
     raw = to_pcm16(pcm)
     return wav_header(sample_rate, len(raw)) + raw

@@ -1,0 +1,148 @@
+"""Device audio output stage: the vocoder's float32 PCM is resampled and encoded on the GPU (``fq3_audio_out_*``, one HIP launch
+per chunk) before it is copied to the host, so that a client gets the rate and sample encoding it asked for -- 8 kHz mu-law for
+telephony, 16 kHz s16, 44.1 / 48 kHz -- and only those bytes cross the bus.  The result does not depend on how the stream was cut
+into chunks.
+
+``AudioOutSpec``  what a caller asks for (rate, encoding); host only, validates without a GPU
+``AudioOut``      one stream's resampler + encoder state on a device
+``resample_device``  one-shot form, host array in, host array out"""
+from __future__ import annotations
+
+import ctypes as C
+from dataclasses import dataclass
+from typing import Optional
+
+import numpy as np
+import torch
+
+from . import _lib
+
+ENCODINGS = {"f32": _lib.FQ3_PCM_F32, "s16": _lib.FQ3_PCM_S16, "mulaw": _lib.FQ3_PCM_MULAW, "alaw": _lib.FQ3_PCM_ALAW}
+_DTYPES = {"f32": torch.float32, "s16": torch.int16, "mulaw": torch.uint8, "alaw": torch.uint8}
+NUMPY_DTYPES = {"f32": np.float32, "s16": np.dtype("<i2"), "mulaw": np.uint8, "alaw": np.uint8}
+
+
+@dataclass(frozen=True)
+class AudioOutSpec:
+    """``sample_rate`` None: the model's rate.  ``encoding``: ``f32`` | ``s16`` | ``mulaw`` | ``alaw``."""
+    sample_rate: Optional[int] = None
+    encoding: str = "f32"
+
+    def __post_init__(self):
+        if self.encoding not in ENCODINGS:
+            raise ValueError(f"unknown audio encoding {self.encoding!r}: one of {', '.join(ENCODINGS)}")
+        if self.sample_rate is not None and (isinstance(self.sample_rate, bool) or not isinstance(self.sample_rate, (int, np.integer))):
+            raise ValueError(f"sample_rate must be an integer number of Hz, not {self.sample_rate!r}")
+
+    def out_rate(self, in_rate: int) -> int:
+        return int(in_rate) if self.sample_rate is None else int(self.sample_rate)
+
+    def validate(self, in_rate: int) -> "AudioOutSpec":
+        """Raises ``ValueError`` with the library's reason when the resampler refuses ``in_rate -> sample_rate`` (host only)."""
+        design(int(in_rate), self.out_rate(in_rate), bank=False)
+        return self
+
+
+def design(in_rate: int, out_rate: int, zero_crossings: int = 0, bank: bool = True):
+    """``(L, M, K, bank float32[L, K] or None)`` of a rate pair (``fq3_audio_out_design``; no GPU needed)."""
+    lib = _lib.load()
+    L, M, K = C.c_int(), C.c_int(), C.c_int()
+    rc = lib.fq3_audio_out_design(in_rate, out_rate, zero_crossings, C.byref(L), C.byref(M), C.byref(K), None, 0)
+    if rc != 0:
+        raise ValueError(lib.fq3_last_error().decode("utf-8", "replace"))
+    if not bank:
+        return L.value, M.value, K.value, None
+    b = np.empty((L.value, K.value), dtype=np.float32)
+    _lib.check(lib.fq3_audio_out_design(in_rate, out_rate, zero_crossings, C.byref(L), C.byref(M), C.byref(K),
+                                        b.ctypes.data_as(C.POINTER(C.c_float)), b.size))
+    return L.value, M.value, K.value, b
+
+
+def count(in_rate: int, out_rate: int, n_in: int, final: bool, zero_crossings: int = 0) -> int:
+    """Output samples that exist once ``n_in`` samples of a stream were pushed (``fq3_audio_out_count``)."""
+    n = _lib.load().fq3_audio_out_count(in_rate, out_rate, zero_crossings, n_in, 1 if final else 0)
+    if n < 0:
+        _lib.check(int(n))
+    return int(n)
+
+
+class AudioOut:
+    """One stream through the stage.  ``push(pcm)`` takes the next float32 samples (a device tensor) and returns the output samples
+    they complete as a device tensor (float32 / int16 / uint8); ``push(..., final=True)`` ends the stream and returns the rest.
+    Work is enqueued on ``stream`` (default: the current stream at the time of the call); nothing synchronises."""
+
+    def __init__(self, spec: AudioOutSpec, in_rate: int, device, stream=None, zero_crossings: int = 0):
+        self.spec, self.in_rate, self.out_rate = spec, int(in_rate), spec.out_rate(in_rate)
+        self.dev = torch.device(device) if not isinstance(device, torch.device) else device
+        if self.dev.type != "cuda":
+            raise ValueError("AudioOut runs on the GPU; there is no CPU fallback")
+        if self.dev.index is None:
+            self.dev = torch.device("cuda", torch.cuda.current_device())
+        self.stream, self.zero = stream, int(zero_crossings)
+        self.dtype = _DTYPES[spec.encoding]
+        self._lib = _lib.load()
+        cfg = _lib.AudioOutConfig(self.in_rate, self.out_rate, ENCODINGS[spec.encoding], self.zero)
+        h = C.c_void_p()
+        with torch.cuda.device(self.dev):
+            rc = self._lib.fq3_audio_out_create(C.byref(cfg), C.byref(h))
+        if rc == _lib.FQ3_EINVAL:
+            raise ValueError(self._lib.fq3_last_error().decode("utf-8", "replace"))
+        _lib.check(rc)
+        self._h = h
+        self.n_in = self.n_out = 0
+        self.finished = False
+        self._empty = torch.empty(0, dtype=torch.float32, device=self.dev)
+
+    def __del__(self):
+        h, self._h = getattr(self, "_h", None), None
+        if h:
+            self._lib.fq3_audio_out_destroy(h)
+
+    def _stream(self):
+        return self.stream if self.stream is not None else torch.cuda.current_stream(self.dev)
+
+    def reset(self) -> None:
+        """A new utterance on the same object."""
+        _lib.check(self._lib.fq3_audio_out_reset(self._h, C.c_void_p(self._stream().cuda_stream)))
+        self.n_in = self.n_out = 0
+        self.finished = False
+
+    def push(self, pcm: Optional[torch.Tensor], final: bool = False) -> torch.Tensor:
+        return self.push_into(pcm, final, None)
+
+    def push_into(self, pcm: Optional[torch.Tensor], final: bool, out: Optional[torch.Tensor]) -> torch.Tensor:
+        """``push`` into ``out`` (a device tensor of the stage's dtype with room for the samples this push completes; None: a new
+        tensor of exactly that size).  Returns the part of ``out`` that was written."""
+        if self.finished:
+            # the library's own answer (FQ3_ESTATE, before any launch): the output count below has no meaning past the end
+            _lib.check(self._lib.fq3_audio_out_push(self._h, None, 0, 0, None, 0, C.byref(C.c_int64()), None))
+        s = self._stream()
+        with torch.cuda.device(self.dev), torch.cuda.stream(s):
+            x = self._empty if pcm is None else pcm.reshape(-1)
+            if x.dtype != torch.float32 or x.device != self.dev or not x.is_contiguous():
+                x = x.to(device=self.dev, dtype=torch.float32).contiguous()
+            n = int(x.numel())
+            need = count(self.in_rate, self.out_rate, self.n_in + n, final, self.zero) - self.n_out
+            if out is None:
+                out = torch.empty(need, dtype=self.dtype, device=self.dev)
+            elif out.dtype != self.dtype or out.device != self.dev or not out.is_contiguous() or out.dim() != 1:
+                raise ValueError("out must be a contiguous 1-D device tensor of the stage's dtype")
+            cap = int(out.numel())
+            wrote = C.c_int64()
+            _lib.check(self._lib.fq3_audio_out_push(self._h, C.c_void_p(x.data_ptr() if n else None), n, 1 if final else 0,
+                                                    C.c_void_p(out.data_ptr() if cap else None), cap, C.byref(wrote),
+                                                    C.c_void_p(s.cuda_stream)))
+            assert wrote.value == need
+            if n:
+                x.record_stream(s)
+        self.n_in += n
+        self.n_out += need
+        self.finished = self.finished or bool(final)
+        return out[:need]
+
+
+def resample_device(audio: np.ndarray, sr: int, target_sr: int, device) -> np.ndarray:
+    """``audio`` (host, mono) at ``sr`` -> float32 host array at ``target_sr`` through the device stage, in one shot."""
+    a = np.array(audio, dtype=np.float32).reshape(-1)          # a copy: the caller's array may be read-only
+    stage = AudioOut(AudioOutSpec(int(target_sr), "f32"), int(sr), device)
+    return stage.push(torch.from_numpy(a).to(stage.dev), final=True).cpu().numpy()

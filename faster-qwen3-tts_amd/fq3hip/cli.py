@@ -111,6 +111,25 @@ def synthesize(model, args, text: str):
     return audio_list[0], sr
 
 
+def _output_stage(model, args):
+    """``--out-rate`` / ``--encoding``: the model's ``audio_output`` context (resampling and encoding on the device), or a no-op."""
+    import contextlib
+    rate, enc = getattr(args, "out_rate", None), getattr(args, "encoding", None)
+    if rate is None and enc is None:
+        return contextlib.nullcontext()
+    return model.audio_output(rate, enc or "f32")
+
+
+def _write_output(path, audio, sr, args):
+    """float32 audio as 16-bit PCM (as ever); what the output stage encoded (int16, G.711 bytes) as it is."""
+    from .audio_io import write_wav, write_wav_encoded
+    enc = getattr(args, "encoding", None)
+    if enc in ("s16", "mulaw", "alaw"):
+        write_wav_encoded(path, audio, sr, enc)
+    else:
+        write_wav(path, audio, sr)
+
+
 def _check_mode_args(args):
     if args.mode == "clone":
         validate_clone_refs(args)
@@ -131,9 +150,10 @@ def cmd_once(args, model=None, lines=None):
         sys.exit(2)
     model = model or load_model(args)
     start = time.perf_counter()
-    audio, sr = synthesize_text_stream(model, args, _stdin_pieces(lines)) if text_stdin else synthesize(model, args, args.text)
+    with _output_stage(model, args):
+        audio, sr = synthesize_text_stream(model, args, _stdin_pieces(lines)) if text_stdin else synthesize(model, args, args.text)
     total = time.perf_counter() - start
-    write_wav(args.output, audio, sr)
+    _write_output(args.output, audio, sr, args)
     dur = len(audio) / sr if sr else 0.0
     print(f"Wrote {args.output} (dur {dur:.2f}s, RTF {dur / total if total > 0 else 0.0:.2f})")
 
@@ -166,18 +186,20 @@ def cmd_serve(args, model=None, lines=None):
         if not pending:
             continue
         start = time.perf_counter()
-        if len(pending) > 1 and args.mode == "clone":
+        staged = getattr(args, "out_rate", None) is not None or getattr(args, "encoding", None) is not None
+        if len(pending) > 1 and args.mode == "clone" and not staged:      # (the output stage runs per stream: line by line)
             results = model.generate_voice_clone_batch(pending, language=args.language, ref_audio=args.ref_audio, ref_text=args.ref_text,
                                                        xvec_only=args.xvec_only, non_streaming_mode=args.non_streaming_mode,
                                                        lanes=args.lanes, **_gen_kwargs(args))
             outs = [(r[0][0], r[1]) for r in results]
         else:
-            outs = [synthesize(model, args, t) for t in pending]
+            with _output_stage(model, args):
+                outs = [synthesize(model, args, t) for t in pending]
         total = time.perf_counter() - start
         for audio, sr in outs:
             out_path = os.path.join(args.output_dir, f"out_{idx:04d}.wav")
             idx += 1
-            write_wav(out_path, audio, sr)
+            _write_output(out_path, audio, sr, args)
             dur = len(audio) / sr if sr else 0.0
             print(f"Wrote {out_path} (dur {dur:.2f}s, RTF {dur * len(outs) / total if total > 0 else 0.0:.2f})")
 
@@ -201,6 +223,10 @@ def build_parser():
         sp.add_argument("--greedy", action="store_true")
         sp.add_argument("--streaming", action="store_true")
         sp.add_argument("--chunk-size", type=int, default=12)
+        sp.add_argument("--out-rate", type=int, default=None, metavar="HZ",
+                        help="output sample rate, resampled on the device (e.g. 8000, 16000, 44100, 48000; default: the model's)")
+        sp.add_argument("--encoding", default=None, choices=["f32", "s16", "mulaw", "alaw"],
+                        help="sample encoding done on the device; mulaw / alaw write a G.711 WAV (default: float32, written as 16-bit)")
         if output:
             sp.add_argument("--text", required=not text_stdin)
             if text_stdin:

@@ -9,6 +9,7 @@ decode loop state lives on the GPU.
 """
 from __future__ import annotations
 
+import contextlib
 import logging
 import time
 from pathlib import Path
@@ -228,12 +229,18 @@ class StreamingVocoder:
     phase 1 re-decodes everything (reference codes in front) until >= max(25, chunk) frames exist and calibrates samples
     per frame; phase 2 decodes [25 context frames + the new chunk] and drops the context.  With the HIP tokenizer only the
     samples that are kept are produced (``decode_tensor(codes, first_sample)``: bit-identical to slicing the full decode)
-    and the codec runs on ``side_stream`` so that it overlaps the next frames' decode kernels."""
+    and the codec runs on ``side_stream`` so that it overlaps the next frames' decode kernels.
+
+    ``output`` (an ``AudioOutSpec``; default None: float32 at the model's rate, through the code below unchanged): every chunk's
+    waveform goes through the device output stage (``fq3hip/audio_out.py``) on the vocoder's stream before it is copied to the host,
+    and the rate handed back with a chunk is the output rate.  The stage holds back its look-ahead (about 16 * max(1, in / out) input
+    samples) until ``push(..., final=True)`` or ``flush()``."""
 
     CONTEXT_FRAMES = 25
 
-    def __init__(self, tok, ref_codes, chunk_size: int, device, side_stream=None):
+    def __init__(self, tok, ref_codes, chunk_size: int, device, side_stream=None, output=None):
         self.tok, self.ref_codes, self.side = tok, ref_codes, side_stream
+        self.output, self.stage = output, None
         self.dev = torch.device(device) if not isinstance(device, torch.device) else device
         self.min_cal = max(self.CONTEXT_FRAMES, int(chunk_size))
         self.all_codes: List[torch.Tensor] = []
@@ -244,8 +251,34 @@ class StreamingVocoder:
                        else None)
         self.last_prefix = None          # the prefix the decode returned by the last ``prepare`` may use (None in phase 2)
 
-    def _vocode(self, codes_in, first_sample, ev, prefix=None):
-        """waveform[first_sample:] of codes_in (host array)."""
+    def _stage(self):
+        """the output stage of this utterance, made at its first chunk (on the vocoder's stream; without one, on the current stream)"""
+        if self.stage is None:
+            from .audio_out import AudioOut
+            self.stage = AudioOut(self.output, int(getattr(self.tok, "sample_rate", 24000)), self.dev, self.side)
+        return self.stage
+
+    def _encoded(self, wav, final: bool):
+        """``wav`` (device tensor, or None for the tail alone) through the output stage -> (host array, output rate)"""
+        st = self._stage()
+        if self.side is None:
+            return st.push(wav, final).cpu().numpy(), st.out_rate
+        with torch.cuda.stream(self.side):
+            return st.push(wav, final).cpu().numpy(), st.out_rate
+
+    def flush(self):
+        """With an ``output``: ends the stage's stream and returns ``(tail, rate)`` -- the samples it held back as look-ahead -- for an
+        utterance whose last event carried no codes.  Empty after a ``push(..., final=True)``, and without an ``output``."""
+        if self.output is None:
+            return np.zeros(0, dtype=np.float32), int(getattr(self.tok, "sample_rate", 24000))
+        st = self._stage()
+        if st.finished:
+            from .audio_out import NUMPY_DTYPES
+            return np.zeros(0, dtype=NUMPY_DTYPES[self.output.encoding]), st.out_rate
+        return self._encoded(None, True)
+
+    def _vocode(self, codes_in, first_sample, ev, prefix=None, final=False):
+        """waveform[first_sample:] of codes_in (host array).  On the side stream an ``output`` stage runs here, before the copy."""
         if self.side is None:
             lst, rate = self.tok.decode({"audio_codes": codes_in.unsqueeze(0)})
             return _to_numpy(lst[0])[first_sample:], rate
@@ -255,7 +288,10 @@ class StreamingVocoder:
             self.side.wait_stream(torch.cuda.current_stream(self.dev))
         with torch.cuda.stream(self.side):
             # (.cpu() synchronises the side stream only)
-            out = _to_numpy(self.tok.decode_tensor(codes_in, first_sample, prefix=prefix) if prefix is not None else self.tok.decode_tensor(codes_in, first_sample))
+            wav = self.tok.decode_tensor(codes_in, first_sample, prefix=prefix) if prefix is not None else self.tok.decode_tensor(codes_in, first_sample)
+            if self.output is not None:
+                return self._encoded(wav.flatten().float(), final)
+            out = _to_numpy(wav)
         return out, self.tok.sample_rate
 
     def _ref_on(self, device):
@@ -311,11 +347,12 @@ class StreamingVocoder:
         self.last_prefix = None
         return window, (int(round(n_ctx * self.spf)) if n_ctx > 0 else 0)
 
-    def push(self, chunk: torch.Tensor, ready_event=None):
-        """``chunk`` LongTensor[n_new, 16] (device) -> (new audio as a host array, sample_rate)."""
+    def push(self, chunk: torch.Tensor, ready_event=None, final=False):
+        """``chunk`` LongTensor[n_new, 16] (device) -> (new audio as a host array, sample_rate).  ``final`` (only read with an
+        ``output``): this is the utterance's last chunk, the output stage's tail comes with it."""
         if self.side is not None:
             inp, first = self.prepare(chunk, ready_event)
-            return self._vocode(inp, first, ready_event, self.last_prefix)
+            return self._vocode(inp, first, ready_event, self.last_prefix, final)
         self.all_codes.append(chunk)
         n_new = chunk.shape[0]
         flat = self._cat(self.all_codes, ready_event)
@@ -344,6 +381,9 @@ class StreamingVocoder:
             window = flat[start:]
             n_ctx = window.shape[0] - n_new
             new_audio, sr = self._vocode(window, int(round(n_ctx * self.spf)) if n_ctx > 0 else 0, ready_event)
+        if self.output is not None:
+            # synchronous tokenizer: its audio is on the host; the chunk is uploaded for the stage
+            return self._encoded(torch.from_numpy(np.ascontiguousarray(new_audio, dtype=np.float32)).to(self.dev), final)
         return new_audio, sr
 
 
@@ -361,6 +401,7 @@ class FasterQwen3TTS:
         self.sample_rate = self._infer_sample_rate(base_model)
         self._warmed_up = False
         self._voice_prompt_cache: Dict[Any, Any] = {}
+        self._audio_spec = None          # the AudioOutSpec of an open ``audio_output`` context
 
     # ---- small helpers pinned by the reference's unit tests ------------------------------------------------
     @staticmethod
@@ -752,6 +793,48 @@ class FasterQwen3TTS:
         talker, config = self._after_prepare(m, tie)
         return m, talker, config, tie, tam, tth, tpe
 
+    # ---- audio output stage (opt-in) ---------------------------------------------------------------------------------
+    @contextlib.contextmanager
+    def audio_output(self, sample_rate: Optional[int] = None, encoding: str = "f32"):
+        """Context manager: inside it the single-stream entry points (``generate_*``, ``generate_*_streaming``, ``stream_*``) hand out
+        audio at ``sample_rate`` (None: the model's) in ``encoding`` (``f32`` | ``s16`` | ``mulaw`` | ``alaw``), resampled and encoded
+        on the device before the copy to the host (``fq3hip/audio_out.py``); ``sr`` in what they yield or return is the output rate.
+        The ``*_batch`` entry points raise ``ValueError`` inside it.  Outside it nothing changes."""
+        from .audio_out import AudioOutSpec
+        spec = AudioOutSpec(sample_rate, encoding).validate(self.sample_rate)
+        prev, self._audio_spec = getattr(self, "_audio_spec", None), spec
+        try:
+            yield spec
+        finally:
+            self._audio_spec = prev
+
+    def _refuse_batch_audio_output(self) -> None:
+        if getattr(self, "_audio_spec", None) is not None:
+            raise ValueError("the batch entry points decode their audio in groups and do not run the audio output stage: call them outside "
+                             "audio_output(), or use the single-stream entry points (the server builds one vocoder per request instead)")
+
+    def _one_shot_output(self, wav) -> Tuple[np.ndarray, int]:
+        """A whole utterance's waveform (device tensor or host array) through the output stage of the open context."""
+        from .audio_out import AudioOut
+        dev = torch.device(self.device) if not isinstance(self.device, torch.device) else self.device
+        stage = AudioOut(self._audio_spec, self.sample_rate, wav.device if hasattr(wav, "is_cuda") and wav.is_cuda else dev)
+        x = wav.flatten().float() if hasattr(wav, "cpu") else torch.from_numpy(np.ascontiguousarray(wav, dtype=np.float32).reshape(-1))
+        return stage.push(x.to(stage.dev), final=True).cpu().numpy(), stage.out_rate
+
+    @staticmethod
+    def _tail_event(voc, timing: Optional[dict]):
+        """After a streaming loop with an output stage: the stage's tail as one more chunk, when the last chunk was not marked final
+        (an utterance that ends on a full chunk) -- with that event's timing, no codes, ``is_final``."""
+        if voc.output is None:
+            return None
+        tail, sr = voc.flush()
+        if len(tail) == 0:
+            return None
+        t = dict(timing or {})
+        t.update(chunk_index=t.get("chunk_index", -1) + 1, chunk_steps=0, prefill_ms=0, decode_ms=0.0, is_final=True)
+        t.pop("first_text_ms", None)
+        return tail, sr, t
+
     # ---- shared back halves -------------------------------------------------------------------------------------
     def _run_full(self, m, talker, config, tie, tam, tth, tpe, ref_codes, gen_kwargs) -> Tuple[list, int]:
         from .generate import fast_generate
@@ -761,6 +844,9 @@ class FasterQwen3TTS:
                                           **gen_kwargs)
         if codec_ids is None:
             logger.warning("Generation returned no tokens")
+            if self._audio_spec is not None:
+                a, sr = self._one_shot_output(np.zeros(1, dtype=np.float32))
+                return [a], sr
             return [np.zeros(1, dtype=np.float32)], self.sample_rate
         # ICL: the reference codes go in front so the decoder has acoustic context (model.py:919-937)
         codes = torch.cat([ref_codes.to(codec_ids.device), codec_ids], dim=0) if ref_codes is not None else codec_ids
@@ -771,7 +857,15 @@ class FasterQwen3TTS:
             # decoder produces only that tail (bit-identical to the slice, fq3_codec_decode_tail)
             cut = int(ref_len / max(codes.shape[0], 1) * tok.num_samples_total(codes.shape[0]))
             pf = tok.prefix_for(ref_codes) if hasattr(tok, "prefix_for") else None          # the voice's cached front-end state
-            out, sr = [_to_numpy(tok.decode_tensor(codes, cut, prefix=pf) if pf is not None else tok.decode_tensor(codes, cut))], tok.sample_rate
+            wav = tok.decode_tensor(codes, cut, prefix=pf) if pf is not None else tok.decode_tensor(codes, cut)
+            if self._audio_spec is not None:
+                a, sr = self._one_shot_output(wav)
+                out = [a]
+            else:
+                out, sr = [_to_numpy(wav)], tok.sample_rate
+        elif self._audio_spec is not None and ref_len == 0 and hasattr(tok, "decode_tensor"):
+            a, sr = self._one_shot_output(tok.decode_tensor(codes, 0))
+            out = [a]
         else:
             audio_list, sr = tok.decode({"audio_codes": codes.unsqueeze(0)})
             out = []
@@ -779,6 +873,8 @@ class FasterQwen3TTS:
                 a = _to_numpy(a)
                 if ref_len > 0:
                     a = a[int(ref_len / max(codes.shape[0], 1) * len(a)):]
+                if self._audio_spec is not None:
+                    a, sr = self._one_shot_output(a)
                 out.append(a)
         n = timing["steps"]
         total = timing["prefill_ms"] / 1000 + timing["decode_s"]
@@ -809,10 +905,12 @@ class FasterQwen3TTS:
             self._voc_stream = concurrent_stream(dev, prio)
         return self._voc_stream
 
-    def streaming_vocoder(self, ref_codes, chunk_size: int) -> "StreamingVocoder":
-        """A fresh windowing state for one utterance (used by the streaming entry points and by the batch server)."""
+    def streaming_vocoder(self, ref_codes, chunk_size: int, output=None) -> "StreamingVocoder":
+        """A fresh windowing state for one utterance (used by the streaming entry points and by the batch server).  ``output``: an
+        ``AudioOutSpec`` for this utterance's audio (default: that of the open ``audio_output`` context, if any)."""
         tok = self.model.model.speech_tokenizer
-        return StreamingVocoder(tok, ref_codes, chunk_size, self.device, self._vocoder_stream(tok))
+        return StreamingVocoder(tok, ref_codes, chunk_size, self.device, self._vocoder_stream(tok),
+                                output=output if output is not None else getattr(self, "_audio_spec", None))
 
     def _run_streaming(self, m, talker, config, tie, tam, tth, tpe, ref_codes, gen_kwargs, chunk_size: int,
                        parity_mode: bool = False):
@@ -820,15 +918,19 @@ class FasterQwen3TTS:
         reference's windowing would emit for it."""
         from .streaming import fast_generate_streaming, parity_generate_streaming
         tok = m.speech_tokenizer
-        voc = StreamingVocoder(tok, ref_codes, chunk_size, self.device, self._vocoder_stream(tok))
+        voc = StreamingVocoder(tok, ref_codes, chunk_size, self.device, self._vocoder_stream(tok), output=self._audio_spec)
         fn = parity_generate_streaming if parity_mode else fast_generate_streaming
         stream = fn(talker=talker, talker_input_embeds=tie, attention_mask=tam, trailing_text_hiddens=tth,
                     tts_pad_embed=tpe, config=config, predictor_graph=self.predictor_graph,
                     talker_graph=self.talker_graph, chunk_size=chunk_size, **gen_kwargs)
+        timing = None
         for chunk, timing in stream:
             ev = timing.pop("codes_ready_event", None)
-            new_audio, sr = voc.push(chunk, ev)
+            new_audio, sr = voc.push(chunk, ev, final=bool(timing.get("is_final")))
             yield new_audio, sr, timing
+        tail = self._tail_event(voc, timing)
+        if tail is not None:
+            yield tail
 
     @staticmethod
     def _gen_kwargs(max_new_tokens, min_new_tokens, temperature, top_k, top_p, do_sample, repetition_penalty):
@@ -956,6 +1058,7 @@ class FasterQwen3TTS:
         """The lock-step decode of ``count`` prepared utterances (see :meth:`_batch_feed`) through ``lanes`` lanes, every finished
         utterance vocoded on the side stream (the reference's share of an ICL waveform is cut by not producing it,
         model.py:927-930).  One ``([waveform], sample_rate)`` per entry, in input order."""
+        self._refuse_batch_audio_output()
         meta: dict = {}
         dec = self._batch_decoder(lanes)
         # batch_first_wave (attribute): requests prepared + prefilled + armed before the first frame is queued (BatchDecoder.first_wave);
@@ -1002,6 +1105,7 @@ class FasterQwen3TTS:
         ``rounds`` (incremental text, :meth:`_run_text_batch_streaming`): ``rounds(dec, meta)`` yields the ``(head, source)`` pairs of
         successive scheduler runs instead of the one pair :meth:`_batch_feed` makes of ``prepared``; ``stamp(index, timing)`` may add
         keys to a chunk's timing before it goes out."""
+        self._refuse_batch_audio_output()
         meta: dict = {}
         vocs, n_chunks = {}, {}
         dec = self._batch_decoder(lanes)
@@ -1385,17 +1489,21 @@ class FasterQwen3TTS:
         try:
             m, talker, config, tie, tam, _tth, tpe = prepare(self._text_session_ids(feeder))
             tok = m.speech_tokenizer
-            voc = StreamingVocoder(tok, None, chunk_size, self.device, self._vocoder_stream(tok))
+            voc = StreamingVocoder(tok, None, chunk_size, self.device, self._vocoder_stream(tok), output=self._audio_spec)
             stream = fast_generate_text_streaming(
                 talker=talker, talker_input_embeds=tie, attention_mask=tam, tts_pad_embed=tpe, config=config,
                 predictor_graph=self.predictor_graph, talker_graph=self.talker_graph, feeder=feeder,
                 tts_eos_id=int(m.config.tts_eos_token_id), chunk_size=chunk_size, **gen_kwargs)
+            timing = None
             for chunk, timing in stream:
                 ev = timing.pop("codes_ready_event", None)
-                new_audio, sr = voc.push(chunk, ev)
+                new_audio, sr = voc.push(chunk, ev, final=bool(timing.get("is_final")))
                 if "first_text_ms" in timing:
                     timing["first_text_ms"] = (time.time() - feeder.t_first) * 1000      # first piece received -> first audio
                 yield new_audio, sr, timing
+            tail = self._tail_event(voc, timing)
+            if tail is not None:
+                yield tail
         finally:
             # a consumer that went away: stop the loop at the next frame boundary (frames of the look-ahead may be queued)
             eng = self.talker_graph.engine

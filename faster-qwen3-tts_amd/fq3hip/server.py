@@ -22,6 +22,7 @@ from __future__ import annotations
 
 import argparse
 import asyncio
+import contextlib
 import json
 import logging
 import os
@@ -35,7 +36,7 @@ from typing import Any, AsyncGenerator, Dict, Optional
 import numpy as np
 from pydantic import BaseModel
 
-from .audio_io import to_pcm16, to_wav_bytes, wav_header
+from .audio_io import to_pcm16, to_wav_bytes, wav_header, wav_header_for
 
 logger = logging.getLogger(__name__)
 CONTENT_TYPES = {"wav": "audio/wav", "pcm": "audio/pcm", "mp3": "audio/mpeg"}
@@ -48,11 +49,16 @@ class SpeechRequest(BaseModel):
     voice: str = "alloy"
     response_format: str = "wav"          # wav | pcm | mp3
     speed: float = 1.0                     # accepted, not applied (as in the reference)
+    # extension: the device audio output stage (fq3hip/audio_out.py).  Both absent: 16-bit PCM at the model's rate, as ever
+    sample_rate: Optional[int] = None      # Hz, e.g. 8000, 16000, 44100, 48000
+    encoding: Optional[str] = None         # s16 | mulaw | alaw (f32 is answered as s16)
 
 
 class SessionRequest(BaseModel):
     voice: str = "alloy"
     response_format: str = "wav"          # wav | pcm
+    sample_rate: Optional[int] = None      # as in SpeechRequest
+    encoding: Optional[str] = None
 
 
 class SessionText(BaseModel):
@@ -139,7 +145,9 @@ class BatchWorker:
                             return None
                         i = counter[0]
                         counter[0] += 1
-                        waiting[i] = (out, m.streaming_vocoder(rc, self.chunk_size))
+                        spec = cfg.get("audio_output")            # the request's AudioOutSpec (create_app puts it there), or None
+                        waiting[i] = (out, m.streaming_vocoder(rc, self.chunk_size) if spec is None else
+                                      m.streaming_vocoder(rc, self.chunk_size, output=spec))
                         kw = m._gen_kwargs(int(cfg.get("max_new_tokens", 2048)), 2, 0.9, 50, 1.0, True, 1.05)
                         return BatchRequest(i, talker, tie, tam, tth, tpe, config, kw)
 
@@ -172,7 +180,9 @@ class BatchWorker:
                             out.put(self.DONE)
                             return None
                         counter[0] += 1
-                        waiting[i] = (out, m.streaming_vocoder(None, self.chunk_size))
+                        spec = cfg.get("audio_output")
+                        waiting[i] = (out, m.streaming_vocoder(None, self.chunk_size) if spec is None else
+                                      m.streaming_vocoder(None, self.chunk_size, output=spec))
                         return req
 
                     def source():
@@ -202,6 +212,14 @@ class BatchWorker:
                         final = bool(info.get("is_final")) or "error" in info
                         if "error" in info or (codes is None and final and info.get("steps", 0) == 0):
                             out.put(RuntimeError(info.get("error", "generation returned no tokens")))
+                        elif getattr(voc, "output", None) is not None:
+                            # the request asked for a rate / encoding: the chunk comes back encoded; the last one brings the stage's tail
+                            if codes is not None and codes.shape[0] > 0:
+                                audio, _sr = voc.push(codes, info.get("codes_ready_event"), final=final)
+                            else:
+                                audio, _sr = voc.flush() if final else (np.zeros(0, np.uint8), 0)
+                            if len(audio):
+                                out.put(audio)
                         elif codes is not None and codes.shape[0] > 0:
                             audio, _sr = voc.push(codes, info.get("codes_ready_event"))
                             out.put(np.asarray(audio, dtype=np.float32))
@@ -244,17 +262,29 @@ def create_app(model, voices: Dict[str, dict], default_voice: Optional[str] = No
             return voices[default_voice]
         raise HTTPException(status_code=400, detail=f"Voice {name!r} is not configured. Available voices: {list(voices.keys())}")
 
+    def request_spec(req):
+        """The request's ``AudioOutSpec``, or None when it names neither a rate nor an encoding (today's path).  400 for an unknown
+        encoding or a rate the resampler refuses."""
+        if req.sample_rate is None and req.encoding is None:
+            return None
+        from .audio_out import AudioOutSpec
+        enc = (req.encoding or "s16").lower()
+        try:
+            return AudioOutSpec(req.sample_rate, "s16" if enc == "f32" else enc).validate(sample_rate)
+        except ValueError as exc:
+            raise HTTPException(status_code=400, detail=str(exc))
+
     def clone_kwargs(cfg: dict, text: str) -> dict:
         return dict(text=text, language=cfg.get("language", "Auto"), ref_audio=cfg.get("ref_audio"), ref_text=cfg.get("ref_text", ""),
                     voice_clone_prompt=cfg.get("voice_clone_prompt"))
 
-    async def stream_chunks(cfg: dict, text: str) -> AsyncGenerator[bytes, None]:
+    async def stream_chunks(cfg: dict, text: str, spec=None) -> AsyncGenerator[bytes, None]:
         q: "queue.Queue" = queue.Queue()
         done = object()
 
         def producer():
             try:
-                with lock:
+                with lock, (contextlib.nullcontext() if spec is None else model.audio_output(spec.sample_rate, spec.encoding)):
                     for chunk, _sr, _t in model.generate_voice_clone_streaming(chunk_size=cfg.get("chunk_size", 12),
                                                                                non_streaming_mode=False, **clone_kwargs(cfg, text)):
                         q.put(chunk)
@@ -271,9 +301,9 @@ def create_app(model, voices: Dict[str, dict], default_voice: Optional[str] = No
                 break
             if isinstance(item, Exception):
                 raise item
-            yield to_pcm16(item)
+            yield to_pcm16(item) if spec is None else np.ascontiguousarray(item).tobytes()
 
-    async def box_response(box, fmt: str, on_end=None):
+    async def box_response(box, fmt: str, on_end=None, spec=None):
         """The streaming body of a batch-scheduler reply queue (``BatchWorker.submit`` / ``submit_text``)."""
         loop = asyncio.get_event_loop()
 
@@ -289,9 +319,10 @@ def create_app(model, voices: Dict[str, dict], default_voice: Optional[str] = No
                     logger.error("generation failed mid-stream: %r", item)
                     break
                 if first and fmt == "wav":
-                    yield wav_header(sample_rate)      # unknown data length: streaming
+                    # unknown data length: streaming
+                    yield wav_header(sample_rate) if spec is None else wav_header_for(spec.out_rate(sample_rate), spec.encoding)
                 first = False
-                yield to_pcm16(item)
+                yield to_pcm16(item) if spec is None else np.ascontiguousarray(item).tobytes()
 
         # pull the first event before answering, so that a request that fails outright is a 500, not an empty 200
         gen = batch_stream()
@@ -340,6 +371,9 @@ def create_app(model, voices: Dict[str, dict], default_voice: Optional[str] = No
         fmt = req.response_format.lower()
         if fmt not in ("wav", "pcm"):
             raise HTTPException(status_code=400, detail=f"response_format {fmt!r} not supported for sessions. Use: wav, pcm")
+        spec = request_spec(req)
+        if spec is not None:
+            cfg = dict(cfg, audio_output=spec)
         try:
             from .model import FasterQwen3TTS
             FasterQwen3TTS._refuse_icl_text_stream(True, cfg.get("voice_clone_prompt"))
@@ -353,7 +387,7 @@ def create_app(model, voices: Dict[str, dict], default_voice: Optional[str] = No
             # sessions nobody ever read: their text ended (the client's `final`, or the scheduler's idle rule) long ago
             for old in [k for k, s in sessions.items() if not s["reading"] and s["feeder"].closed and now - s["t_closed"] > 60.0]:
                 sessions.pop(old, None)
-            sessions[sid] = dict(feeder=feeder, box=worker.submit_text(cfg, feeder), fmt=fmt, reading=False, t_closed=now)
+            sessions[sid] = dict(feeder=feeder, box=worker.submit_text(cfg, feeder), fmt=fmt, reading=False, t_closed=now, spec=spec)
         return {"id": sid}
 
     @app.post("/v1/audio/speech/sessions/{sid}/text")
@@ -376,7 +410,7 @@ def create_app(model, voices: Dict[str, dict], default_voice: Optional[str] = No
             if s["reading"]:
                 raise HTTPException(status_code=409, detail="this session's audio is being read already")
             s["reading"] = True
-        return await box_response(s["box"], s["fmt"], on_end=lambda: drop_session(sid))
+        return await box_response(s["box"], s["fmt"], on_end=lambda: drop_session(sid), spec=s["spec"])
 
     @app.get("/health")
     async def health():
@@ -394,13 +428,15 @@ def create_app(model, voices: Dict[str, dict], default_voice: Optional[str] = No
             raise HTTPException(status_code=400, detail=f"response_format {fmt!r} not supported. Use: wav, pcm, mp3")
         if fmt == "mp3":
             raise HTTPException(status_code=400, detail="response_format='mp3' needs pydub + ffmpeg, which this image does not ship; use wav or pcm")
+        spec = request_spec(req)
         if worker is not None:
-            return await box_response(worker.submit(cfg, req.input), fmt)
+            return await box_response(worker.submit(cfg if spec is None else dict(cfg, audio_output=spec), req.input), fmt, spec=spec)
 
         async def audio_stream():
             if fmt == "wav":
-                yield wav_header(sample_rate)          # unknown data length: streaming
-            async for raw in stream_chunks(cfg, req.input):
+                # unknown data length: streaming
+                yield wav_header(sample_rate) if spec is None else wav_header_for(spec.out_rate(sample_rate), spec.encoding)
+            async for raw in stream_chunks(cfg, req.input, spec):
                 yield raw
 
         return StreamingResponse(audio_stream(), media_type=CONTENT_TYPES[fmt])

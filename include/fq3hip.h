@@ -472,6 +472,45 @@ int fq3_refenc_encode(fq3_refenc* r, const float* pcm, int64_t n, int64_t* codes
  * log-mel frames float32[n / hop][mel_dim] the encoder consumed */
 int fq3_refenc_speaker(fq3_refenc* r, const float* pcm, int64_t n, float* embed, float* mel, void* stream);
 
+/* ---- audio output stage: resample and encode the vocoder's PCM before it leaves the device ----------------------------------
+ * The vocoder writes float32 PCM at the model's rate (24 kHz).  This stage turns it, on the device and in ONE launch per chunk, into
+ * what a client asked for: another sample rate (a streaming polyphase resampler) and another sample encoding (16-bit PCM, G.711
+ * mu-law / A-law), so that only the encoded bytes cross to the host.  The result does not depend on how the stream was cut into
+ * pushes: every output sample is computed from the same K input samples with the same fp32 operations in the same order.
+ *
+ * Design (host only, no HIP call): g = gcd(in_rate, out_rate), L = out_rate / g, M = in_rate / g, both at most 320 (else
+ * FQ3_EINVAL).  The prototype is a Kaiser-windowed sinc (beta 8) of half length Z m, m = max(L, M), Z = zero_crossings (0: 16),
+ * cutoff 0.96 / m of the up-sampled Nyquist, computed in double precision and scaled to sum L; K = ceil((2 Z m + 1) / L) taps per
+ * output.  bank (may be NULL; `capacity` floats, at least L K) receives the L phase rows, row p at bank[p K .. p K + K).
+ * Output n stands at input time n M / L (zero phase) and is
+ *     y[n] = sum_k bank[(n M) mod L][k] * x[floor((n M + Z m) / L) - (K - 1) + k]     (x = 0 outside the stream),
+ * accumulated in fp32 from 0.0f with fmaf over k = 0 .. K - 1.  L = M = 1 is the encoder alone: K = 1, bank = {1.0f}, y[n] = x[n]. */
+int fq3_audio_out_design(int in_rate, int out_rate, int zero_crossings, int* L, int* M, int* K, float* bank, int64_t capacity);
+/* Output samples that exist once the first n_in input samples of a stream have been pushed: an output is produced as soon as every
+ * input sample it reads exists; final != 0: the stream ended there, and the count is ceil(n_in L / M) (the samples past the end are
+ * zeros).  A function of the cumulative length alone, non-decreasing in it.  Negative: an FQ3_E* code. */
+int64_t fq3_audio_out_count(int in_rate, int out_rate, int zero_crossings, int64_t n_in, int final);
+
+enum { FQ3_PCM_F32 = 0,      /* float32, the value itself */
+       FQ3_PCM_S16 = 1,      /* int16: y * 32768, clamped to [-32768, 32767], truncated toward zero */
+       FQ3_PCM_MULAW = 2,    /* G.711 mu-law byte of that int16 */
+       FQ3_PCM_ALAW = 3 };   /* G.711 A-law byte of that int16 */
+typedef struct fq3_audio_out fq3_audio_out;
+typedef struct fq3_audio_out_config { int in_rate, out_rate, format, zero_crossings; } fq3_audio_out_config;
+/* One object per stream; it owns the bank and the history (the last K - 1 input samples) on the current device.  NULL or range errors
+ * are answered before any HIP call. */
+int fq3_audio_out_create(const fq3_audio_out_config* cfg, fq3_audio_out** out);
+int fq3_audio_out_destroy(fq3_audio_out* a);                 /* NULL -> 0 */
+/* a new utterance on the same object (nothing is enqueued; `stream` is where the next push will run) */
+int fq3_audio_out_reset(fq3_audio_out* a, void* stream);
+/* pcm: n_in device floats (n_in may be 0), the next samples of the stream; final != 0: the stream ends with them.
+ * out: device buffer of capacity_samples OUTPUT samples (float / int16 / uint8 by format) at any alignment its element type allows.
+ * *n_out = samples written: fq3_audio_out_count(total so far, final) minus what earlier pushes wrote, known before the launch;
+ * above capacity_samples: FQ3_EINVAL and nothing is launched.  One launch on `stream`, no host synchronisation; pcm and out must stay
+ * valid until the stream has run it.  After a final push: FQ3_ESTATE until fq3_audio_out_reset. */
+int fq3_audio_out_push(fq3_audio_out* a, const float* pcm, int64_t n_in, int final, void* out, int64_t capacity_samples,
+                       int64_t* n_out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,0 +1,97 @@
+#!/usr/bin/env python3
+"""Times the device audio output stage (fq3hip/audio_out.py, one launch of audio_out_kernel per push) ALONE, with HIP events:
+8 kHz mu-law and 48 kHz s16 out of 24 kHz float32, for a streaming chunk (8 frames = 15 360 samples) and a 370-frame utterance, the
+median of the timed runs after a warm-up -- each run its own event pair around one push, and the same pushes back to back under one
+pair (the first includes what an event pair around a single short launch costs).  The yardstick, in the same run: the bf16x2
+vocoder's streaming-chunk decode (25 context + 8 new frames, the tail of 8 frames produced) at the real codec shapes.  Also the bytes
+copied to the host with and without the stage.  Writes profiles/audio_out.json.
+usage: audio_out_probe.py [runs=100] [out.json]"""
+import json
+import os
+import statistics
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "faster-qwen3-tts_amd"))
+import torch
+from fq3hip import audio_out as ao
+from fq3hip.codec import HipSpeechTokenizer
+from fq3hip.config import qwen3_tts_0p6b
+from fq3hip.weights import synth_weights
+
+SAMPLES_PER_FRAME = 1920
+SETTINGS = (("8 kHz mulaw", 8000, "mulaw"), ("48 kHz s16", 48000, "s16"))
+SIZES = (("streaming chunk, 8 frames", 8 * SAMPLES_PER_FRAME), ("utterance, 370 frames", 370 * SAMPLES_PER_FRAME))
+
+
+def timed(fn, runs, warmup=10):
+    """(median ms of `runs` single calls, each between its own events; ms per call of `runs` calls between one pair)"""
+    for _ in range(warmup):
+        fn()
+    torch.cuda.synchronize()
+    pairs = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(runs)]
+    for e0, e1 in pairs:
+        e0.record(); fn(); e1.record()
+    torch.cuda.synchronize()
+    single = statistics.median(e0.elapsed_time(e1) for e0, e1 in pairs)
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    for _ in range(runs):
+        fn()
+    e1.record(); torch.cuda.synchronize()
+    return single, e0.elapsed_time(e1) / runs
+
+
+def main():
+    runs = max(50, int(sys.argv[1])) if len(sys.argv) > 1 else 100
+    out_path = sys.argv[2] if len(sys.argv) > 2 else os.path.join(ROOT, "profiles", "audio_out.json")
+    g = torch.Generator().manual_seed(3)
+    res = {"device": torch.cuda.get_device_name(0), "runs": runs, "in_rate": 24000, "stage": [], "notes": []}
+
+    cfg = qwen3_tts_0p6b()
+    W = synth_weights(cfg, 0, torch.bfloat16, parts=("codec",), codec_normalized=True)
+    tok = HipSpeechTokenizer(cfg.codec, W, "cuda", max_frames=400, precision="bf16x2")
+    codes = torch.randint(0, cfg.codec.codebook_size, (33, 16), generator=g).cuda()
+    first = tok.num_samples_total(33) - 8 * SAMPLES_PER_FRAME
+    voc_single, voc_stream = timed(lambda: tok.decode_tensor(codes, first), runs)
+    res["vocoder_bf16x2_streaming_chunk_ms"] = {"median_single_call": round(voc_single, 4), "back_to_back_per_call": round(voc_stream, 4)}
+
+    for size_name, n in SIZES:
+        pcm = (torch.rand(n, generator=g) * 2 - 1).cuda()
+        for name, rate, enc in SETTINGS:
+            spec = ao.AudioOutSpec(rate, enc)
+            stage = ao.AudioOut(spec, 24000, "cuda")
+            L, M, K, _ = ao.design(24000, rate, bank=False)
+            n_out = ao.count(24000, rate, n, True)
+            out = torch.empty(n_out, dtype=stage.dtype, device="cuda")
+
+            def one():
+                # the launch alone: reset (host only) + one final push into a buffer that exists
+                stage.reset()
+                return stage.push_into(pcm, True, out)
+            single, stream = timed(one, runs)
+            bytes_out, bytes_plain = n_out * out.element_size(), n * 4
+            res["stage"].append({
+                "setting": name, "input": size_name, "n_in": n, "n_out": n_out, "L": L, "M": M, "taps_per_output": K,
+                "median_single_push_ms": round(single, 4), "back_to_back_per_push_ms": round(stream, 4),
+                "share_of_vocoder_chunk_back_to_back": round(stream / voc_stream, 5) if n == 8 * SAMPLES_PER_FRAME else None,
+                "flop": 2 * K * n_out, "bytes_to_host_with_stage": bytes_out, "bytes_to_host_float32_24k": bytes_plain,
+                "bytes_ratio": round(bytes_out / bytes_plain, 4)})
+    chunk = [r for r in res["stage"] if r["n_in"] == 8 * SAMPLES_PER_FRAME]
+    worst = max(r["share_of_vocoder_chunk_back_to_back"] for r in chunk)
+    res["notes"].append(f"streaming chunk: the stage is at most {100 * worst:.2f} % of the bf16x2 vocoder's chunk decode (back-to-back figures); "
+                        + ("launch-bound as expected (well under 1 %)" if worst < 0.01 else "NOT under 1 %: the expectation of a stage well under 1 % of the chunk does not hold here"))
+    for name, _rate, _enc in SETTINGS:
+        small, large = (next(r for r in res["stage"] if r["setting"] == name and r["n_in"] == n) for _, n in SIZES)
+        growth = large["back_to_back_per_push_ms"] / small["back_to_back_per_push_ms"]
+        res["notes"].append(f"{name}: {large['n_in'] // small['n_in']}x the input takes {growth:.2f}x the time per push"
+                            + (": the figure is what issuing one push costs (Python, ctypes, one launch), not kernel work" if growth < 1.5 else ""))
+    os.makedirs(os.path.dirname(out_path) or ".", exist_ok=True)
+    with open(out_path, "w") as f:
+        json.dump(res, f, indent=1)
+        f.write("\n")
+    print(json.dumps(res, indent=1))
+
+
+if __name__ == "__main__":
+    main()

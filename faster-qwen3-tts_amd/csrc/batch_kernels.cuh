@@ -395,6 +395,23 @@ struct BatchGemvArgs {
 // 2 tokens x 12 chunks x 8 fp32 per lane next to 96 registers of weights -- sent the kernel to scratch)
 template <typename T> constexpr int batch_group_max_nch(int nch) { return (sizeof(T) == 4 && nch >= 12) ? 4 : kGroupLanes; }
 template <typename T> inline int batch_group_max(int need_chunks) { return batch_group_max_nch<T>(need_chunks > 6 ? 12 : need_chunks); }
+// Launch arithmetic of the batch GEMVs (host; shared by the launchers of fq3_batch.hip and tools/microbench/gemv_probe.hip).
+// tokens per LDS pass of gemv_batch_kernel: as many as fit ~150 KB (16 lanes x K = 6144 x fp32 would need 393 KB), at most kGroupLanes
+constexpr size_t kBatchGemvLdsBudget = 150 * 1024;
+template <typename T>
+inline int batch_gemv_group(int B, int K, int esz) {
+    const int need = (K + 511) / 512;
+    int group = B < batch_group_max<T>(need) ? B : batch_group_max<T>(need);
+    while (group > 1 && (size_t)group * K * esz > kBatchGemvLdsBudget) group = (group + 1) / 2;
+    return group;
+}
+// dynamic LDS of the normalising matrix-core GEMVs: `panels` token tiles of K normalised bf16 values (rows padded by 8) + their partial sums
+inline size_t norm_panel_lds(int K, int NR, int panels) {
+    return (((size_t)panels * kTokTile * (K + 8) * 2 + 15) & ~(size_t)15) + (size_t)panels * 4 * NR * 256 * sizeof(float);
+}
+// gemv_batch_mfma_plain_kernel: K = 32 KSTEPS columns for each of NW waves
+constexpr int plain_mfma_nw(int K) { return K <= 1024 ? 4 : 8; }
+constexpr int plain_mfma_ksteps(int K) { return K / (32 * plain_mfma_nw(K)); }
 
 template <typename T, int NCH, int PRO, int EPI>
 __global__ __launch_bounds__(256) void gemv_batch_kernel(BatchGemvArgs a) {

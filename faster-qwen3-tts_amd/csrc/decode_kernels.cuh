@@ -102,6 +102,27 @@ inline int gemv_chunks(int K, int most) {
     return 0;
 }
 
+// chunks per lane a launch is built for at most: a normalising GEMV reads K = hidden <= 2048 (four chunks); the others q_dim / the
+// intermediate size, up to 6144 for one token (or a batch) and 3072 for a two-token pass (m = 2: both tokens' row registers)
+constexpr int gemv_most_chunks(int pro, int m) { return pro == PRO_NORM ? 4 : (m == 2 ? 6 : 12); }
+
+// Launch arithmetic of gemv_kernel (host; shared by the launchers of fq3_api.hip and tools/microbench/gemv_probe.hip).
+// rows per wave: 2 for the big matrices (512-768 workgroups), 1 when N <= 1024 or a row is long; rmax: a cap (0 = none)
+template <int NCH, int EPI>
+inline int gemv_rows_per_wave(int N, int rmax) {
+    int R = (N + 1023) / 1024;
+    if (R > MaxRows<NCH, EPI>::v) R = MaxRows<NCH, EPI>::v;
+    if (rmax > 0 && R > rmax) R = rmax;
+    if (R < 1) R = 1;
+    return R;
+}
+inline int gemv_grid(int N, int R) { return (N + 4 * R - 1) / (4 * R); }
+// dynamic LDS: the merged attention output of the M tokens (PRO_COMBINE only)
+template <int PRO, int M>
+inline size_t gemv_lds_bytes(int K) { return PRO == PRO_COMBINE ? (size_t)M * K * sizeof(float) : 0; }
+// PRO_COMBINE stages the merged vector with one 8-element slice per thread of the 256-thread workgroup: K = q_dim up to this
+constexpr int kCombineMaxK = 256 * 8;
+
 // M = number of tokens that share one pass over the weights (2 only for the code predictor's two-token
 // prefill, predictor_graph.py:121-128: weights are read once, both tokens' dot products are formed).
 // Order of work (profiles/r01_kernel_chain.txt): the small input-side loads are issued FIRST, the weight rows

@@ -39,7 +39,7 @@ int fq3_dmalloc_(fq3_ctx* c, void** p, size_t bytes) { return dmalloc(c, p, byte
 static bool dims_ok(const fq3_stack_dims& d) {
     return d.head_dim == kHeadDim && d.hidden % 8 == 0 && d.inter % 8 == 0 && d.n_heads % d.n_kv_heads == 0 &&
            (d.n_heads / d.n_kv_heads == 1 || d.n_heads / d.n_kv_heads == 2 || d.n_heads / d.n_kv_heads == 4) &&
-           d.vocab <= kMaxVocab && d.vocab % 8 == 0 && d.hidden <= 2048 && d.inter <= 6144 && d.n_heads * kHeadDim <= 6144 && d.n_layers >= 1;
+           d.vocab <= kMaxVocab && d.vocab % 8 == 0 && d.hidden <= 2048 && d.inter <= 6144 && d.n_heads * kHeadDim <= kCombineMaxK && d.n_layers >= 1;
 }
 
 // -------------------------------------------------------------------------------------------------
@@ -49,7 +49,7 @@ static int cfg_check(const fq3_config* cfg) {
     if (cfg->dtype != FQ3_BF16 && cfg->dtype != FQ3_F32) return fail(FQ3_EINVAL, "dtype must be FQ3_BF16 or FQ3_F32");
     if (!dims_ok(cfg->talker) || !dims_ok(cfg->predictor))
         return fail(FQ3_EUNSUPPORTED, "unsupported dims (need head_dim 128, GQA ratio 1/2/4, vocab <= 4096 and a multiple of 8, "
-                                      "hidden <= 2048 and intermediate <= 6144, both multiples of 8)");
+                                      "hidden <= 2048 and intermediate <= 6144, both multiples of 8, n_heads * 128 <= 2048)");
     if (cfg->num_code_groups < 2 || cfg->num_code_groups > 64) return fail(FQ3_EINVAL, "num_code_groups");
     if (cfg->max_seq_len < 8) return fail(FQ3_EINVAL, "max_seq_len");
     return 0;
@@ -397,13 +397,9 @@ extern "C" int fq3_bind_weights(fq3_ctx* c, const fq3_weight_table* w) {
 // rmax: the context's cap on rows per wave (fq3_set_option "rows_per_wave_max"; 0 = none)
 template <typename T, int NCH, int PRO, int EPI, bool NT, int M = 1>
 static void launch_gemv_n(const GemvArgs& a, int rmax, hipStream_t s) {
-    // rows per wave: 2 for the big matrices (512-768 workgroups), 1 when N <= 1024 or a row is long
-    int R = (a.N + 1023) / 1024;
-    if (R > MaxRows<NCH, EPI>::v) R = MaxRows<NCH, EPI>::v;
-    if (rmax > 0 && R > rmax) R = rmax;
-    if (R < 1) R = 1;
-    const int grid = (a.N + 4 * R - 1) / (4 * R);
-    const size_t shm = PRO == PRO_COMBINE ? (size_t)M * a.K * sizeof(float) : 0;
+    const int R = gemv_rows_per_wave<NCH, EPI>(a.N, rmax);
+    const int grid = gemv_grid(a.N, R);
+    const size_t shm = gemv_lds_bytes<PRO, M>(a.K);
     if constexpr (MaxRows<NCH, EPI>::v >= 2) {
         if (R == 2) { hipLaunchKernelGGL((gemv_kernel<T, NCH, PRO, EPI, NT, M, 2>), dim3(grid), dim3(256), shm, s, a); return; }
     }
@@ -415,7 +411,7 @@ static void launch_gemv_n(const GemvArgs& a, int rmax, hipStream_t s) {
 // supported model).
 template <typename T, int PRO, int EPI>
 static int launch_gemv2_t(const GemvArgs& a, int rmax, hipStream_t s) {
-    constexpr int most = PRO == PRO_NORM ? 4 : 6;
+    constexpr int most = gemv_most_chunks(PRO, 2);
     const int n = gemv_chunks(a.K, most);
     if (!n) return fail(FQ3_EUNSUPPORTED, PRO == PRO_NORM ? "code predictor hidden size above 2048" : "code predictor GEMV inner dimension above 3072");
     with_value<1, 2, 4, 6>(n, [&](auto nch) {
@@ -429,7 +425,7 @@ static int launch_gemv2(const fq3_ctx* c, const GemvArgs& a, hipStream_t s) {
 }
 template <typename T, int PRO, int EPI, bool NT>
 static int launch_gemv_t(const GemvArgs& a, int rmax, hipStream_t s) {
-    constexpr int most = PRO == PRO_NORM ? 4 : 12;       // a normalising GEMV reads K = hidden
+    constexpr int most = gemv_most_chunks(PRO, 1);       // a normalising GEMV reads K = hidden
     const int n = gemv_chunks(a.K, most);
     if (!n) return fail(FQ3_EUNSUPPORTED, PRO == PRO_NORM ? "hidden size above 2048" : "GEMV inner dimension above 6144");
     with_value<1, 2, 4, 6, 12>(n, [&](auto nch) {

@@ -94,10 +94,6 @@ static int bmalloc(fq3_batch* b, void** p, size_t bytes) {
     return 0;
 }
 
-// dynamic LDS of the normalising matrix-core GEMVs: `panels` token tiles of K normalised bf16 values (rows padded by 8) + their partial sums
-static size_t norm_panel_lds(int K, int NR, int panels) {
-    return (((size_t)panels * kTokTile * (K + 8) * 2 + 15) & ~(size_t)15) + (size_t)panels * 4 * NR * 256 * sizeof(float);
-}
 // the two-panel form needs up to ~83 KB: the limit of every instantiation is raised in fq3_batch_create, outside any capture
 template <int KS, int EPI>
 static bool norm_dual_attr() {
@@ -337,15 +333,12 @@ extern "C" int fq3_batch_set_group_streams(fq3_batch* b, void* const* streams, i
 // ---------------------------------------------------------------------------------------------------------------
 template <typename T, int PRO, int EPI>
 static int launch_gemv_batch_t(BatchGemvArgs a, int esz, hipStream_t s) {
-    const int need = (a.K + 511) / 512;
     const int grid = (a.N + 3) / 4;
-    // tokens per LDS pass: as many as fit ~150 KB (16 lanes x K = 6144 x fp32 would need 393 KB), at most kGroupLanes
-    int group = std::min(a.B, batch_group_max<T>(need));
-    while (group > 1 && (size_t)group * a.K * esz > 150 * 1024) group = (group + 1) / 2;
+    const int group = batch_gemv_group<T>(a.B, a.K, esz);        // tokens per LDS pass (batch_kernels.cuh)
     const size_t shm = (size_t)group * a.K * esz;
-    if (shm > 150 * 1024) return fq3_fail_(FQ3_EUNSUPPORTED, "a single token of this inner dimension does not fit the 160 KB LDS");
+    if (shm > kBatchGemvLdsBudget) return fq3_fail_(FQ3_EUNSUPPORTED, "a single token of this inner dimension does not fit the 160 KB LDS");
     a.group = group;
-    constexpr int most = PRO == PRO_NORM ? 4 : 12;               // a normalising GEMV reads K = hidden
+    constexpr int most = gemv_most_chunks(PRO, 1);               // a normalising GEMV reads K = hidden
     const int n = gemv_chunks(a.K, most);
     if (!n) return fq3_fail_(FQ3_EUNSUPPORTED, PRO == PRO_NORM ? "hidden size above 2048" : "GEMV inner dimension above 6144");
     return with_value<1, 2, 4, 6, 12>(n, [&](auto nch) -> int {
@@ -444,7 +437,7 @@ static int launch_gemv_batch_mfma_plain(const fq3_batch& b, const BatchGemvArgs&
     an.Wp = (b.packed && a.N % 16 == 0) ? fq3_packed_find_(a.W, 0) : nullptr;      // fragment-major copy in 16-row blocks, where there is one
     an.ntiles = (a.B + kTokTile - 1) / kTokTile;             // token tiles: 1..4 unrolled, more (65..128 lanes) by the rolled loop, NT = 0
     with_value<256, 512, 768, 1024, 2048, 3072, 4096, 6144>(a.K, [&](auto k) {
-        constexpr int NW = decltype(k)::value <= 1024 ? 4 : 8, KS = decltype(k)::value / (32 * NW);      // K = 32 KS columns for each of NW waves
+        constexpr int NW = plain_mfma_nw(decltype(k)::value), KS = plain_mfma_ksteps(decltype(k)::value);      // K = 32 KS columns for each of NW waves
         with_value<1, 2, 3, 4, 0>(an.ntiles, [&](auto nt) {
             hipLaunchKernelGGL((gemv_batch_mfma_plain_kernel<KS, NW, EPI, decltype(nt)::value>), dim3((a.N + 15) / 16), dim3(64 * NW), 0, s, an);
         });

@@ -64,6 +64,23 @@ def test_null_arguments_are_errors_not_crashes(lib):
     assert lib.fq3_batch_size(None) == 0 and lib.fq3_batch_destroy(None) == 0
 
 
+def test_q_dim_above_2048_is_refused(lib):
+    """The split-KV merge prologue of the o_proj GEMV stages q_dim = n_heads * 128 <= 2048 elements (one 8-element slice per thread of
+    its workgroup): a wider stack is refused when the context is created -- the dims check precedes every HIP call -- and says why."""
+    from fq3hip import _lib as L
+
+    def dims(n_heads, n_kv):
+        return L.StackDims(hidden=1024, inter=3072, n_layers=1, n_heads=n_heads, n_kv_heads=n_kv, head_dim=128, vocab=2048, rms_eps=1e-6)
+    lib.fq3_ctx_create.restype = ctypes.c_int
+    lib.fq3_last_error.restype = ctypes.c_char_p
+    for talker, predictor in ((dims(17, 17), dims(16, 8)), (dims(16, 8), dims(48, 12)), (dims(20, 5), dims(16, 8))):
+        cfg = L.Config(dtype=L.FQ3_BF16, talker=talker, predictor=predictor, num_code_groups=16, max_seq_len=64, codec_eos_token_id=1,
+                       has_projection=0, max_frames=8)
+        h = ctypes.c_void_p()
+        assert lib.fq3_ctx_create(ctypes.byref(cfg), ctypes.byref(h)) == L.FQ3_EUNSUPPORTED
+        assert b"n_heads * 128 <= 2048" in lib.fq3_last_error() and not h.value
+
+
 def test_struct_layout_matches_header_sizes():
     from fq3hip import _lib as L
     assert ctypes.sizeof(L.StackDims) == 32

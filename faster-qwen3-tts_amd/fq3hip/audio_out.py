@@ -1,14 +1,16 @@
 """Device audio output stage: the vocoder's float32 PCM is resampled and encoded on the GPU (``fq3_audio_out_*``, one HIP launch
 per chunk) before it is copied to the host, so that a client gets the rate and sample encoding it asked for -- 8 kHz mu-law for
 telephony, 16 kHz s16, 44.1 / 48 kHz -- and only those bytes cross the bus.  The result does not depend on how the stream was cut
-into chunks.
+into chunks.  A ``speed`` other than 1 puts the time-scale stage in front (``fq3_tsm_*``: WSOLA, one more
+launch per chunk; duration changes, pitch does not), with the same contract.
 
-``AudioOutSpec``  what a caller asks for (rate, encoding); host only, validates without a GPU
-``AudioOut``      one stream's resampler + encoder state on a device
+``AudioOutSpec``  what a caller asks for (rate, encoding, speed); host only, validates without a GPU
+``AudioOut``      one stream's time-scale + resampler + encoder state on a device
 ``resample_device``  one-shot form, host array in, host array out"""
 from __future__ import annotations
 
 import ctypes as C
+import math
 from dataclasses import dataclass
 from typing import Optional
 
@@ -20,15 +22,23 @@ from . import _lib
 ENCODINGS = {"f32": _lib.FQ3_PCM_F32, "s16": _lib.FQ3_PCM_S16, "mulaw": _lib.FQ3_PCM_MULAW, "alaw": _lib.FQ3_PCM_ALAW}
 _DTYPES = {"f32": torch.float32, "s16": torch.int16, "mulaw": torch.uint8, "alaw": torch.uint8}
 NUMPY_DTYPES = {"f32": np.float32, "s16": np.dtype("<i2"), "mulaw": np.uint8, "alaw": np.uint8}
+MIN_SPEED, MAX_SPEED = 0.25, 4.0
 
 
 @dataclass(frozen=True)
 class AudioOutSpec:
-    """``sample_rate`` None: the model's rate.  ``encoding``: ``f32`` | ``s16`` | ``mulaw`` | ``alaw``."""
+    """``sample_rate`` None: the model's rate.  ``encoding``: ``f32`` | ``s16`` | ``mulaw`` | ``alaw``.  ``speed`` in [0.25, 4.0],
+    applied in per-mille steps; 1.0: no time-scale stage at all."""
     sample_rate: Optional[int] = None
     encoding: str = "f32"
+    speed: float = 1.0
 
     def __post_init__(self):
+        sp = self.speed
+        if isinstance(sp, bool) or not isinstance(sp, (int, float, np.integer, np.floating)) or not math.isfinite(sp):
+            raise ValueError(f"speed must be a number in [{MIN_SPEED}, {MAX_SPEED}], not {sp!r}")
+        if not 1000 * MIN_SPEED <= round(float(sp) * 1000) <= 1000 * MAX_SPEED:
+            raise ValueError(f"speed {sp!r} is outside [{MIN_SPEED}, {MAX_SPEED}]")
         if self.encoding not in ENCODINGS:
             raise ValueError(f"unknown audio encoding {self.encoding!r}: one of {', '.join(ENCODINGS)}")
         if self.sample_rate is not None and (isinstance(self.sample_rate, bool) or not isinstance(self.sample_rate, (int, np.integer))):
@@ -37,9 +47,17 @@ class AudioOutSpec:
     def out_rate(self, in_rate: int) -> int:
         return int(in_rate) if self.sample_rate is None else int(self.sample_rate)
 
+    @property
+    def permille(self) -> int:
+        """``speed`` as the library applies it: quantised once, to per-mille"""
+        return int(round(float(self.speed) * 1000))
+
     def validate(self, in_rate: int) -> "AudioOutSpec":
-        """Raises ``ValueError`` with the library's reason when the resampler refuses ``in_rate -> sample_rate`` (host only)."""
+        """Raises ``ValueError`` with the library's reason when the resampler refuses ``in_rate -> sample_rate`` or the time-scale
+        stage refuses ``in_rate`` (host only)."""
         design(int(in_rate), self.out_rate(in_rate), bank=False)
+        if self.permille != 1000:
+            tsm_design(int(in_rate), self.permille, window=False)
         return self
 
 
@@ -66,10 +84,36 @@ def count(in_rate: int, out_rate: int, n_in: int, final: bool, zero_crossings: i
     return int(n)
 
 
+def tsm_design(in_rate: int, permille: int, window: bool = True):
+    """``(N, Hs, delta, window float32[N] or None)`` of the time-scale stage at ``in_rate`` (``fq3_tsm_design``; no GPU needed)."""
+    lib = _lib.load()
+    N, Hs, D = C.c_int(), C.c_int(), C.c_int()
+    rc = lib.fq3_tsm_design(in_rate, permille, C.byref(N), C.byref(Hs), C.byref(D), None, 0)
+    if rc != 0:
+        raise ValueError(lib.fq3_last_error().decode("utf-8", "replace"))
+    if not window:
+        return N.value, Hs.value, D.value, None
+    w = np.empty(N.value, dtype=np.float32)
+    _lib.check(lib.fq3_tsm_design(in_rate, permille, C.byref(N), C.byref(Hs), C.byref(D), w.ctypes.data_as(C.POINTER(C.c_float)), w.size))
+    return N.value, Hs.value, D.value, w
+
+
+def tsm_count(in_rate: int, permille: int, n_in: int, final: bool) -> int:
+    """Time-scaled samples that exist once ``n_in`` samples of a stream were pushed (``fq3_tsm_count``)."""
+    n = _lib.load().fq3_tsm_count(in_rate, permille, n_in, 1 if final else 0)
+    if n < 0:
+        _lib.check(int(n))
+    return int(n)
+
+
 class AudioOut:
     """One stream through the stage.  ``push(pcm)`` takes the next float32 samples (a device tensor) and returns the output samples
     they complete as a device tensor (float32 / int16 / uint8); ``push(..., final=True)`` ends the stream and returns the rest.
-    Work is enqueued on ``stream`` (default: the current stream at the time of the call); nothing synchronises."""
+    Work is enqueued on ``stream`` (default: the current stream at the time of the call); nothing synchronises.
+
+    With a ``speed`` other than 1 the samples first go through the time-scale stage (one launch of its own, one intermediate device
+    tensor per push), which holds back about 30 ms of input (N + delta = 3 hops of in_rate / 100 samples) until the final push.
+    ``n_in`` counts the vocoder's samples, ``n_out`` what has left the chain."""
 
     def __init__(self, spec: AudioOutSpec, in_rate: int, device, stream=None, zero_crossings: int = 0):
         self.spec, self.in_rate, self.out_rate = spec, int(in_rate), spec.out_rate(in_rate)
@@ -80,63 +124,101 @@ class AudioOut:
             self.dev = torch.device("cuda", torch.cuda.current_device())
         self.stream, self.zero = stream, int(zero_crossings)
         self.dtype = _DTYPES[spec.encoding]
+        self.permille = spec.permille
         self._lib = _lib.load()
-        cfg = _lib.AudioOutConfig(self.in_rate, self.out_rate, ENCODINGS[spec.encoding], self.zero)
-        h = C.c_void_p()
+        self._h = self._tsm = None
+        # speed alone (the model's rate, float32): the time-scale stage writes the output itself, no second launch
+        self._encode = self.permille == 1000 or self.out_rate != self.in_rate or spec.encoding != "f32"
         with torch.cuda.device(self.dev):
-            rc = self._lib.fq3_audio_out_create(C.byref(cfg), C.byref(h))
+            if self.permille != 1000:
+                self._tsm = self._create(self._lib.fq3_tsm_create, _lib.TsmConfig(self.in_rate, self.permille))
+            if self._encode:
+                self._h = self._create(self._lib.fq3_audio_out_create,
+                                       _lib.AudioOutConfig(self.in_rate, self.out_rate, ENCODINGS[spec.encoding], self.zero))
+        self.n_in = self.n_mid = self.n_out = 0
+        self.finished = False
+        self._empty = torch.empty(0, dtype=torch.float32, device=self.dev)
+
+    def _create(self, fn, cfg):
+        h = C.c_void_p()
+        rc = fn(C.byref(cfg), C.byref(h))
         if rc == _lib.FQ3_EINVAL:
             raise ValueError(self._lib.fq3_last_error().decode("utf-8", "replace"))
         _lib.check(rc)
-        self._h = h
-        self.n_in = self.n_out = 0
-        self.finished = False
-        self._empty = torch.empty(0, dtype=torch.float32, device=self.dev)
+        return h
 
     def __del__(self):
         h, self._h = getattr(self, "_h", None), None
         if h:
             self._lib.fq3_audio_out_destroy(h)
+        t, self._tsm = getattr(self, "_tsm", None), None
+        if t:
+            self._lib.fq3_tsm_destroy(t)
 
     def _stream(self):
         return self.stream if self.stream is not None else torch.cuda.current_stream(self.dev)
 
     def reset(self) -> None:
         """A new utterance on the same object."""
-        _lib.check(self._lib.fq3_audio_out_reset(self._h, C.c_void_p(self._stream().cuda_stream)))
-        self.n_in = self.n_out = 0
+        s = C.c_void_p(self._stream().cuda_stream)
+        if self._tsm:
+            _lib.check(self._lib.fq3_tsm_reset(self._tsm, s))
+        if self._h:
+            _lib.check(self._lib.fq3_audio_out_reset(self._h, s))
+        self.n_in = self.n_mid = self.n_out = 0
         self.finished = False
 
     def push(self, pcm: Optional[torch.Tensor], final: bool = False) -> torch.Tensor:
         return self.push_into(pcm, final, None)
+
+    def _counts(self, n_in: int, final: bool):
+        """(time-scaled samples, output samples) that exist once ``n_in`` samples of the stream were pushed"""
+        mid = tsm_count(self.in_rate, self.permille, n_in, final) if self._tsm else n_in
+        return mid, (count(self.in_rate, self.out_rate, mid, final, self.zero) if self._encode else mid)
 
     def push_into(self, pcm: Optional[torch.Tensor], final: bool, out: Optional[torch.Tensor]) -> torch.Tensor:
         """``push`` into ``out`` (a device tensor of the stage's dtype with room for the samples this push completes; None: a new
         tensor of exactly that size).  Returns the part of ``out`` that was written."""
         if self.finished:
             # the library's own answer (FQ3_ESTATE, before any launch): the output count below has no meaning past the end
-            _lib.check(self._lib.fq3_audio_out_push(self._h, None, 0, 0, None, 0, C.byref(C.c_int64()), None))
+            if self._h:
+                _lib.check(self._lib.fq3_audio_out_push(self._h, None, 0, 0, None, 0, C.byref(C.c_int64()), None))
+            else:
+                _lib.check(self._lib.fq3_tsm_push(self._tsm, None, 0, 0, None, 0, C.byref(C.c_int64()), None, 0, None))
         s = self._stream()
         with torch.cuda.device(self.dev), torch.cuda.stream(s):
             x = self._empty if pcm is None else pcm.reshape(-1)
             if x.dtype != torch.float32 or x.device != self.dev or not x.is_contiguous():
                 x = x.to(device=self.dev, dtype=torch.float32).contiguous()
-            n = int(x.numel())
-            need = count(self.in_rate, self.out_rate, self.n_in + n, final, self.zero) - self.n_out
+            n = n_pushed = int(x.numel())
+            mid_total, out_total = self._counts(self.n_in + n, final)
+            n_mid, need = mid_total - self.n_mid, out_total - self.n_out
             if out is None:
                 out = torch.empty(need, dtype=self.dtype, device=self.dev)
             elif out.dtype != self.dtype or out.device != self.dev or not out.is_contiguous() or out.dim() != 1:
                 raise ValueError("out must be a contiguous 1-D device tensor of the stage's dtype")
             cap = int(out.numel())
             wrote = C.c_int64()
-            _lib.check(self._lib.fq3_audio_out_push(self._h, C.c_void_p(x.data_ptr() if n else None), n, 1 if final else 0,
-                                                    C.c_void_p(out.data_ptr() if cap else None), cap, C.byref(wrote),
-                                                    C.c_void_p(s.cuda_stream)))
-            assert wrote.value == need
-            if n:
-                x.record_stream(s)
-        self.n_in += n
-        self.n_out += need
+            sp = C.c_void_p(s.cuda_stream)
+            if self._tsm:
+                if self._encode and need > cap:
+                    raise ValueError(f"out has room for {cap} samples, this push completes {need}")
+                mid = torch.empty(n_mid, dtype=torch.float32, device=self.dev) if self._encode else out
+                mid_cap = int(mid.numel())
+                _lib.check(self._lib.fq3_tsm_push(self._tsm, C.c_void_p(x.data_ptr() if n else None), n, 1 if final else 0,
+                                                  C.c_void_p(mid.data_ptr() if mid_cap else None), mid_cap, C.byref(wrote), None, 0, sp))
+                assert wrote.value == n_mid
+                if n:
+                    x.record_stream(s)
+                x, n = mid, n_mid
+            if self._encode:
+                _lib.check(self._lib.fq3_audio_out_push(self._h, C.c_void_p(x.data_ptr() if n else None), n, 1 if final else 0,
+                                                        C.c_void_p(out.data_ptr() if cap else None), cap, C.byref(wrote), sp))
+                assert wrote.value == need
+                if n:
+                    x.record_stream(s)
+        self.n_in += n_pushed
+        self.n_mid, self.n_out = mid_total, out_total
         self.finished = self.finished or bool(final)
         return out[:need]
 

@@ -112,12 +112,13 @@ def synthesize(model, args, text: str):
 
 
 def _output_stage(model, args):
-    """``--out-rate`` / ``--encoding``: the model's ``audio_output`` context (resampling and encoding on the device), or a no-op."""
+    """``--out-rate`` / ``--encoding`` / ``--speed``: the model's ``audio_output`` context (time-scaling, resampling and encoding on
+    the device), or a no-op."""
     import contextlib
-    rate, enc = getattr(args, "out_rate", None), getattr(args, "encoding", None)
-    if rate is None and enc is None:
+    rate, enc, speed = getattr(args, "out_rate", None), getattr(args, "encoding", None), getattr(args, "speed", None)
+    if rate is None and enc is None and speed is None:
         return contextlib.nullcontext()
-    return model.audio_output(rate, enc or "f32")
+    return model.audio_output(rate, enc or "f32", 1.0 if speed is None else speed)
 
 
 def _write_output(path, audio, sr, args):
@@ -186,7 +187,7 @@ def cmd_serve(args, model=None, lines=None):
         if not pending:
             continue
         start = time.perf_counter()
-        staged = getattr(args, "out_rate", None) is not None or getattr(args, "encoding", None) is not None
+        staged = any(getattr(args, k, None) is not None for k in ("out_rate", "encoding", "speed"))
         if len(pending) > 1 and args.mode == "clone" and not staged:      # (the output stage runs per stream: line by line)
             results = model.generate_voice_clone_batch(pending, language=args.language, ref_audio=args.ref_audio, ref_text=args.ref_text,
                                                        xvec_only=args.xvec_only, non_streaming_mode=args.non_streaming_mode,
@@ -227,6 +228,8 @@ def build_parser():
                         help="output sample rate, resampled on the device (e.g. 8000, 16000, 44100, 48000; default: the model's)")
         sp.add_argument("--encoding", default=None, choices=["f32", "s16", "mulaw", "alaw"],
                         help="sample encoding done on the device; mulaw / alaw write a G.711 WAV (default: float32, written as 16-bit)")
+        sp.add_argument("--speed", type=float, default=None, metavar="X",
+                        help="speaking rate, 0.25 to 4.0, time-scaled on the device: duration changes, pitch does not (default: 1.0)")
         if output:
             sp.add_argument("--text", required=not text_stdin)
             if text_stdin:

@@ -234,7 +234,8 @@ class StreamingVocoder:
     ``output`` (an ``AudioOutSpec``; default None: float32 at the model's rate, through the code below unchanged): every chunk's
     waveform goes through the device output stage (``fq3hip/audio_out.py``) on the vocoder's stream before it is copied to the host,
     and the rate handed back with a chunk is the output rate.  The stage holds back its look-ahead (about 16 * max(1, in / out) input
-    samples) until ``push(..., final=True)`` or ``flush()``."""
+    samples; with a ``speed`` other than 1 the time-scale stage in front of it adds about 30 ms of input, three hops of 10 ms, and
+    hands out whole 10 ms segments) until ``push(..., final=True)`` or ``flush()``."""
 
     CONTEXT_FRAMES = 25
 
@@ -795,13 +796,15 @@ class FasterQwen3TTS:
 
     # ---- audio output stage (opt-in) ---------------------------------------------------------------------------------
     @contextlib.contextmanager
-    def audio_output(self, sample_rate: Optional[int] = None, encoding: str = "f32"):
+    def audio_output(self, sample_rate: Optional[int] = None, encoding: str = "f32", speed: float = 1.0):
         """Context manager: inside it the single-stream entry points (``generate_*``, ``generate_*_streaming``, ``stream_*``) hand out
         audio at ``sample_rate`` (None: the model's) in ``encoding`` (``f32`` | ``s16`` | ``mulaw`` | ``alaw``), resampled and encoded
         on the device before the copy to the host (``fq3hip/audio_out.py``); ``sr`` in what they yield or return is the output rate.
-        The ``*_batch`` entry points raise ``ValueError`` inside it.  Outside it nothing changes."""
+        ``speed`` in [0.25, 4.0] (1.0: off) time-scales the audio on the device first: an utterance of n samples becomes
+        ceil(n / speed) samples at the same pitch.  The ``*_batch`` entry points raise ``ValueError`` inside it.  Outside it nothing
+        changes."""
         from .audio_out import AudioOutSpec
-        spec = AudioOutSpec(sample_rate, encoding).validate(self.sample_rate)
+        spec = AudioOutSpec(sample_rate, encoding, speed).validate(self.sample_rate)
         prev, self._audio_spec = getattr(self, "_audio_spec", None), spec
         try:
             yield spec

@@ -48,7 +48,7 @@ class SpeechRequest(BaseModel):
     input: str
     voice: str = "alloy"
     response_format: str = "wav"          # wav | pcm | mp3
-    speed: float = 1.0                     # accepted, not applied (as in the reference)
+    speed: float = 1.0                     # 0.25 .. 4.0, applied on the device after the vocoder (duration changes, pitch does not)
     # extension: the device audio output stage (fq3hip/audio_out.py).  Both absent: 16-bit PCM at the model's rate, as ever
     sample_rate: Optional[int] = None      # Hz, e.g. 8000, 16000, 44100, 48000
     encoding: Optional[str] = None         # s16 | mulaw | alaw (f32 is answered as s16)
@@ -57,7 +57,8 @@ class SpeechRequest(BaseModel):
 class SessionRequest(BaseModel):
     voice: str = "alloy"
     response_format: str = "wav"          # wav | pcm
-    sample_rate: Optional[int] = None      # as in SpeechRequest
+    speed: float = 1.0                     # as in SpeechRequest
+    sample_rate: Optional[int] = None
     encoding: Optional[str] = None
 
 
@@ -263,14 +264,14 @@ def create_app(model, voices: Dict[str, dict], default_voice: Optional[str] = No
         raise HTTPException(status_code=400, detail=f"Voice {name!r} is not configured. Available voices: {list(voices.keys())}")
 
     def request_spec(req):
-        """The request's ``AudioOutSpec``, or None when it names neither a rate nor an encoding (today's path).  400 for an unknown
-        encoding or a rate the resampler refuses."""
-        if req.sample_rate is None and req.encoding is None:
+        """The request's ``AudioOutSpec``, or None when it names neither a rate nor an encoding nor a speed other than 1 (today's
+        path).  400 for an unknown encoding, a rate the resampler refuses or a speed outside [0.25, 4.0]."""
+        if req.sample_rate is None and req.encoding is None and req.speed == 1.0:
             return None
         from .audio_out import AudioOutSpec
         enc = (req.encoding or "s16").lower()
         try:
-            return AudioOutSpec(req.sample_rate, "s16" if enc == "f32" else enc).validate(sample_rate)
+            return AudioOutSpec(req.sample_rate, "s16" if enc == "f32" else enc, req.speed).validate(sample_rate)
         except ValueError as exc:
             raise HTTPException(status_code=400, detail=str(exc))
 
@@ -284,7 +285,7 @@ def create_app(model, voices: Dict[str, dict], default_voice: Optional[str] = No
 
         def producer():
             try:
-                with lock, (contextlib.nullcontext() if spec is None else model.audio_output(spec.sample_rate, spec.encoding)):
+                with lock, (contextlib.nullcontext() if spec is None else model.audio_output(spec.sample_rate, spec.encoding, spec.speed)):
                     for chunk, _sr, _t in model.generate_voice_clone_streaming(chunk_size=cfg.get("chunk_size", 12),
                                                                                non_streaming_mode=False, **clone_kwargs(cfg, text)):
                         q.put(chunk)

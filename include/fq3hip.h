@@ -511,6 +511,43 @@ int fq3_audio_out_reset(fq3_audio_out* a, void* stream);
 int fq3_audio_out_push(fq3_audio_out* a, const float* pcm, int64_t n_in, int final, void* out, int64_t capacity_samples,
                        int64_t* n_out, void* stream);
 
+/* ---- time-scale modification: the `speed` of a stream, applied to the vocoder's PCM on the device ---------------------------
+ * WSOLA (waveform-similarity overlap-add with a plain cross-correlation search) in front of the audio output stage: the duration
+ * changes by 1 / speed, the pitch stays.  ONE launch of ONE workgroup per push (the segments form a chain); the result does not
+ * depend on how the stream was cut into pushes.
+ *
+ * Design (host only, no HIP call): P = speed_permille in [250, 4000], Hs = round(in_rate / 100) (a multiple of 16 in [16, 480], else
+ * FQ3_EINVAL), N = 2 Hs, delta = Hs; window (may be NULL; `capacity` floats, at least N) receives the periodic Hann window of length
+ * N, computed in double precision.  With x = 0 outside the stream, output segment s is samples [s Hs, (s + 1) Hs):
+ *     a(s) = floor(s Hs P / 1000)        pos(s) = a(s) + d(s)        pos(-1) = -Hs        d(0) = 0
+ *     s >= 1:  t[j] = x[pos(s-1) + Hs + j],   c(d) = sum_{j < N} x[a(s) + d + j] t[j],   d(s) = argmax over [-delta, delta],
+ *              ties to the smallest d
+ *     y[s Hs + j] = fmaf(w[j], x[pos(s) + j], w[j + Hs] * x[pos(s-1) + Hs + j])
+ * c(d) is accumulated in fp32 as eight partial sums, each an fmaf chain from 0.0f over one eighth of j in ascending order, added in
+ * ascending order: a fixed function of (d, j). */
+int fq3_tsm_design(int in_rate, int speed_permille, int* N, int* Hs, int* delta, float* window, int64_t capacity);
+/* Output samples that exist once the first n_in input samples of a stream have been pushed.  final != 0: the stream ended there and
+ * the count is T = ceil(1000 n_in / P) (the last segment is cut to it).  Otherwise whole segments only: segment s >= 1 exists once
+ * max(a(s), a(s-1) + Hs) + delta + N <= n_in (segment 0: Hs <= n_in), and never more than Hs floor(T / Hs) samples.  A function of the
+ * cumulative length alone, non-decreasing in it, never above T; the look-ahead is about N + delta input samples.  Negative: an
+ * FQ3_E* code. */
+int64_t fq3_tsm_count(int in_rate, int speed_permille, int64_t n_in, int final);
+
+typedef struct fq3_tsm fq3_tsm;
+typedef struct fq3_tsm_config { int in_rate, speed_permille; } fq3_tsm_config;
+/* One object per stream; it owns the window, the input history the next segment can still reach and d of the last emitted segment
+ * (chosen on the device; the host never learns it) on the current device.  NULL or range errors are answered before any HIP call. */
+int fq3_tsm_create(const fq3_tsm_config* cfg, fq3_tsm** out);
+int fq3_tsm_destroy(fq3_tsm* t);                              /* NULL -> 0 */
+/* a new utterance on the same object (nothing is enqueued) */
+int fq3_tsm_reset(fq3_tsm* t, void* stream);
+/* As fq3_audio_out_push, float32 in and out: *n_out = fq3_tsm_count(total so far, final) minus what earlier pushes wrote, known
+ * before the launch; above capacity_samples: FQ3_EINVAL and nothing is launched; after a final push: FQ3_ESTATE until fq3_tsm_reset.
+ * deltas (optional, device int32[deltas_capacity]) receives d(s) of every segment this push emitted (ceil(*n_out / Hs) of them;
+ * more than deltas_capacity: FQ3_EINVAL, nothing launched). */
+int fq3_tsm_push(fq3_tsm* t, const float* pcm, int64_t n_in, int final, float* out, int64_t capacity_samples,
+                 int64_t* n_out, int32_t* deltas, int64_t deltas_capacity, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

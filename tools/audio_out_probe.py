@@ -5,7 +5,10 @@ median of the timed runs after a warm-up -- each run its own event pair around o
 pair (the first includes what an event pair around a single short launch costs).  The yardstick, in the same run: the bf16x2
 vocoder's streaming-chunk decode (25 context + 8 new frames, the tail of 8 frames produced) at the real codec shapes.  Also the bytes
 copied to the host with and without the stage.  Writes profiles/audio_out.json.
-usage: audio_out_probe.py [runs=100] [out.json]"""
+With --speed: the time-scale stage (fq3_tsm_*, one launch of tsm_kernel per push, one workgroup walking the chunk's segments) ALONE at
+speeds 0.5, 1.25 and 2.0 on the streaming chunk, per push and per segment, next to the same vocoder yardstick from the same run and the
+same stream, and as a fraction of it.  Writes profiles/tsm_stage.json.
+usage: audio_out_probe.py [--speed] [runs=100] [out.json]"""
 import json
 import os
 import statistics
@@ -42,18 +45,66 @@ def timed(fn, runs, warmup=10):
     return single, e0.elapsed_time(e1) / runs
 
 
-def main():
-    runs = max(50, int(sys.argv[1])) if len(sys.argv) > 1 else 100
-    out_path = sys.argv[2] if len(sys.argv) > 2 else os.path.join(ROOT, "profiles", "audio_out.json")
-    g = torch.Generator().manual_seed(3)
-    res = {"device": torch.cuda.get_device_name(0), "runs": runs, "in_rate": 24000, "stage": [], "notes": []}
+SPEEDS = (500, 1250, 2000)
 
+
+def vocoder_chunk(g, runs):
+    """the yardstick: (median single call, back to back per call) ms of the bf16x2 vocoder's streaming-chunk decode"""
     cfg = qwen3_tts_0p6b()
     W = synth_weights(cfg, 0, torch.bfloat16, parts=("codec",), codec_normalized=True)
     tok = HipSpeechTokenizer(cfg.codec, W, "cuda", max_frames=400, precision="bf16x2")
     codes = torch.randint(0, cfg.codec.codebook_size, (33, 16), generator=g).cuda()
     first = tok.num_samples_total(33) - 8 * SAMPLES_PER_FRAME
-    voc_single, voc_stream = timed(lambda: tok.decode_tensor(codes, first), runs)
+    return timed(lambda: tok.decode_tensor(codes, first), runs)
+
+
+def main_speed(argv):
+    runs = max(50, int(argv[0])) if argv else 100
+    out_path = argv[1] if len(argv) > 1 else os.path.join(ROOT, "profiles", "tsm_stage.json")
+    g = torch.Generator().manual_seed(3)
+    res = {"device": torch.cuda.get_device_name(0), "runs": runs, "in_rate": 24000, "stage": [], "notes": []}
+    voc_single, voc_stream = vocoder_chunk(g, runs)
+    res["vocoder_bf16x2_streaming_chunk_ms"] = {"median_single_call": round(voc_single, 4), "back_to_back_per_call": round(voc_stream, 4)}
+    n = 8 * SAMPLES_PER_FRAME
+    pcm = (torch.rand(n, generator=g) * 2 - 1).cuda()
+    N, Hs, D, _ = ao.tsm_design(24000, SPEEDS[0], window=False)
+    for P in SPEEDS:
+        stage = ao.AudioOut(ao.AudioOutSpec(speed=P / 1000), 24000, "cuda")
+        n_out = ao.tsm_count(24000, P, n, True)
+        out = torch.empty(n_out, dtype=torch.float32, device="cuda")
+
+        def one():
+            # the launch alone: reset (host only) + one final push of the chunk into a buffer that exists
+            stage.reset()
+            return stage.push_into(pcm, True, out)
+        single, stream = timed(one, runs)
+        segs = -(-n_out // Hs)
+        res["stage"].append({
+            "speed_permille": P, "input": "streaming chunk, 8 frames", "n_in": n, "n_out": n_out, "segments": segs,
+            "candidates_per_segment": 2 * D + 1, "window": N,
+            "median_single_push_ms": round(single, 4), "back_to_back_per_push_ms": round(stream, 4),
+            "us_per_segment_back_to_back": round(1000 * stream / segs, 3),
+            "fraction_of_vocoder_chunk_back_to_back": round(stream / voc_stream, 4), "flop": 2 * N * (2 * D + 1) * (segs - 1)})
+    worst = max(r["fraction_of_vocoder_chunk_back_to_back"] for r in res["stage"])
+    res["notes"].append(f"the time-scale stage takes at most {worst:.3f} of the bf16x2 vocoder's chunk decode (back-to-back figures, same stream); "
+                        + ("ABOVE 1: with speed on, this stage and not the vocoder bounds the streamed real-time factor" if worst > 1 else
+                           "below 1: the vocoder still bounds the streamed chunk, the stage adds this fraction to it"))
+    os.makedirs(os.path.dirname(out_path) or ".", exist_ok=True)
+    with open(out_path, "w") as f:
+        json.dump(res, f, indent=1)
+        f.write("\n")
+    print(json.dumps(res, indent=1))
+
+
+def main():
+    if "--speed" in sys.argv[1:]:
+        return main_speed([a for a in sys.argv[1:] if a != "--speed"])
+    runs = max(50, int(sys.argv[1])) if len(sys.argv) > 1 else 100
+    out_path = sys.argv[2] if len(sys.argv) > 2 else os.path.join(ROOT, "profiles", "audio_out.json")
+    g = torch.Generator().manual_seed(3)
+    res = {"device": torch.cuda.get_device_name(0), "runs": runs, "in_rate": 24000, "stage": [], "notes": []}
+
+    voc_single, voc_stream = vocoder_chunk(g, runs)
     res["vocoder_bf16x2_streaming_chunk_ms"] = {"median_single_call": round(voc_single, 4), "back_to_back_per_call": round(voc_stream, 4)}
 
     for size_name, n in SIZES:

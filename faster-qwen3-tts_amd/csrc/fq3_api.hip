@@ -837,11 +837,6 @@ __global__ void build_seen_kernel(const int64_t* history, int n, unsigned char* 
     __syncthreads();
     for (int i = threadIdx.x; i < n; i += blockDim.x) { const int id = (int)history[i]; if (id >= 0 && id < V) seen[id] = 1; }
 }
-template <typename F>
-static void dispatch_nc(int V, F&& f) {
-    if (V <= 2048) f(std::integral_constant<int, 1>{});
-    else f(std::integral_constant<int, 2>{});
-}
 
 template <typename T>
 static void launch_sample_pred(const DecodeState* st, const T* lg, int V, int cb, const SampleCfg& cfg, const T* nz,

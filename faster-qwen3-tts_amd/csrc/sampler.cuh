@@ -12,8 +12,12 @@ namespace fq3 {
 
 constexpr int kMaxVocab = 4096;
 
-__device__ __forceinline__ uint32_t okey(float f) {           // order-preserving float -> uint
-    const uint32_t u = __float_as_uint(f);
+// order-preserving float -> uint.  -0.0 takes the key of +0.0: the reference compares FLOATS (`logits < kth`, a stable sort), for which
+// signed zeros are equal, so neither the top-k filters nor the nucleus order may tell them apart (ties: lowest index first).  No other
+// key changes (-inf keeps 0x007FFFFF).
+__device__ __forceinline__ uint32_t okey(float f) {
+    uint32_t u = __float_as_uint(f);
+    if (u == 0x80000000u) u = 0u;
     return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
 }
 

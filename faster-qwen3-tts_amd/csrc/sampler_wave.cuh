@@ -3,6 +3,7 @@
 // noise lands behind the k-th-value search; a handful of workgroup barriers in total.  Same arithmetic and rounding as sample_core (sampler.cuh) / sampling.py:32-66.
 #pragma once
 #include "sampler.cuh"
+#include <type_traits>
 
 namespace fq3 {
 
@@ -149,6 +150,14 @@ __device__ int sample_wave_core(Raw8<T> (&xraw)[NC], int V, const SampleCfg& c, 
         }
     }
     return blk_argmax4(a, sm);
+}
+
+// Chunks the register-resident kernels are instantiated with: V <= 2048 -> NC = 1, else 2 (kMaxVocab = 4096).  The one copy of the
+// rule: the launchers of fq3_api.hip and the conformance probe (tools/microbench/sampler_probe.hip) both go through it.
+template <typename F>
+inline void dispatch_nc(int V, F&& f) {
+    if (V <= 2048) f(std::integral_constant<int, 1>{});
+    else f(std::integral_constant<int, 2>{});
 }
 
 template <typename T, int NC>

@@ -79,6 +79,10 @@ class TsmConfig(C.Structure):
     _fields_ = [("in_rate", C.c_int), ("speed_permille", C.c_int)]
 
 
+class FlacConfig(C.Structure):
+    _fields_ = [("sample_rate", C.c_int), ("block_size", C.c_int)]
+
+
 class RefEncConfig(C.Structure):
     _fields_ = [("num_filters", i32), ("n_ratios", i32), ("ratios", i32 * 8), ("kernel_size", i32), ("last_kernel_size", i32),
                 ("residual_kernel_size", i32), ("n_residual_layers", i32), ("dilation_growth_rate", i32), ("compress", i32),
@@ -181,6 +185,13 @@ SIGNATURES = {
     "fq3_tsm_destroy": (C.c_int, [vp]),
     "fq3_tsm_reset": (C.c_int, [vp, vp]),
     "fq3_tsm_push": (C.c_int, [vp, vp, C.c_int64, C.c_int, vp, C.c_int64, C.POINTER(C.c_int64), vp, C.c_int64, vp]),
+    "fq3_flac_design": (C.c_int, [C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "fq3_flac_header": (C.c_int, [C.c_int, C.c_int, C.c_int64, vp, C.c_int64]),
+    "fq3_flac_count": (C.c_int64, [C.c_int, C.c_int, C.c_int64, C.c_int]),
+    "fq3_flac_create": (C.c_int, [C.POINTER(FlacConfig), C.POINTER(vp)]),
+    "fq3_flac_destroy": (C.c_int, [vp]),
+    "fq3_flac_reset": (C.c_int, [vp, vp]),
+    "fq3_flac_push": (C.c_int, [vp, vp, C.c_int64, C.c_int, vp, C.c_int64, C.POINTER(C.c_int64), vp, vp]),
 }
 
 _lib = None

@@ -39,6 +39,9 @@ def wav_header_for(sample_rate: int, encoding: str, data_len: int = 0xFFFFFFFF) 
     ``fmt`` chunk and a ``fact`` chunk with the sample count.  ``data_len = 0xFFFFFFFF``: a stream of unknown size."""
     if encoding == "s16":
         return wav_header(sample_rate, data_len)
+    if encoding == "flac":
+        raise ValueError("a FLAC stream is not WAV data: it starts with its own header (flac_header), and the output stage hands it out "
+                         "with that header in front")
     if encoding not in _G711_TAGS:
         raise ValueError(f"no WAV header for encoding {encoding!r}: one of s16, mulaw, alaw")
     unknown = data_len == 0xFFFFFFFF
@@ -46,6 +49,13 @@ def wav_header_for(sample_rate: int, encoding: str, data_len: int = 0xFFFFFFFF) 
     return (b"RIFF" + struct.pack("<I", riff) + b"WAVE" + b"fmt " +
             struct.pack("<IHHIIHHH", 18, _G711_TAGS[encoding], 1, sample_rate, sample_rate, 1, 8, 0) +
             b"fact" + struct.pack("<II", 4, data_len) + b"data" + struct.pack("<I", data_len))
+
+
+def flac_header(rate: int, block: int = 0, total: int = 0) -> bytes:
+    """The 42 bytes in front of the FLAC output stage's frames: ``fLaC`` and one STREAMINFO block (mono, 16 bits; ``block`` 0: the
+    stage's default for ``rate``; ``total`` samples, 0: unknown, what a stream in progress says).  Host only."""
+    from .audio_out import flac_header as _header
+    return _header(rate, block, total)
 
 
 def write_wav_encoded(path: str, data: np.ndarray, sample_rate: int, encoding: str) -> None:

@@ -2,7 +2,9 @@
 per chunk) before it is copied to the host, so that a client gets the rate and sample encoding it asked for -- 8 kHz mu-law for
 telephony, 16 kHz s16, 44.1 / 48 kHz -- and only those bytes cross the bus.  The result does not depend on how the stream was cut
 into chunks.  A ``speed`` other than 1 puts the time-scale stage in front (``fq3_tsm_*``: WSOLA, one more
-launch per chunk; duration changes, pitch does not), with the same contract.
+launch per chunk; duration changes, pitch does not), with the same contract.  The ``flac`` encoding puts the
+FLAC stage behind the s16 encoder (``fq3_flac_*``: lossless, a launch pair per chunk): what leaves the chain
+then is FLAC frames, and the 42-byte stream header comes from the host (``flac_header``).
 
 ``AudioOutSpec``  what a caller asks for (rate, encoding, speed); host only, validates without a GPU
 ``AudioOut``      one stream's time-scale + resampler + encoder state on a device
@@ -19,16 +21,20 @@ import torch
 
 from . import _lib
 
-ENCODINGS = {"f32": _lib.FQ3_PCM_F32, "s16": _lib.FQ3_PCM_S16, "mulaw": _lib.FQ3_PCM_MULAW, "alaw": _lib.FQ3_PCM_ALAW}
-_DTYPES = {"f32": torch.float32, "s16": torch.int16, "mulaw": torch.uint8, "alaw": torch.uint8}
-NUMPY_DTYPES = {"f32": np.float32, "s16": np.dtype("<i2"), "mulaw": np.uint8, "alaw": np.uint8}
+# ``flac`` is the s16 encoding followed by the FLAC stage: the output stage itself runs in FQ3_PCM_S16
+ENCODINGS = {"f32": _lib.FQ3_PCM_F32, "s16": _lib.FQ3_PCM_S16, "mulaw": _lib.FQ3_PCM_MULAW, "alaw": _lib.FQ3_PCM_ALAW,
+             "flac": _lib.FQ3_PCM_S16}
+_DTYPES = {"f32": torch.float32, "s16": torch.int16, "mulaw": torch.uint8, "alaw": torch.uint8, "flac": torch.uint8}
+NUMPY_DTYPES = {"f32": np.float32, "s16": np.dtype("<i2"), "mulaw": np.uint8, "alaw": np.uint8, "flac": np.uint8}
+FLAC_HEADER_BYTES = 42
 MIN_SPEED, MAX_SPEED = 0.25, 4.0
 
 
 @dataclass(frozen=True)
 class AudioOutSpec:
-    """``sample_rate`` None: the model's rate.  ``encoding``: ``f32`` | ``s16`` | ``mulaw`` | ``alaw``.  ``speed`` in [0.25, 4.0],
-    applied in per-mille steps; 1.0: no time-scale stage at all."""
+    """``sample_rate`` None: the model's rate.  ``encoding``: ``f32`` | ``s16`` | ``mulaw`` | ``alaw`` | ``flac`` (the s16 samples, losslessly
+    compressed; the output is bytes, not samples).  ``speed`` in [0.25, 4.0], applied in per-mille steps; 1.0: no time-scale stage at
+    all."""
     sample_rate: Optional[int] = None
     encoding: str = "f32"
     speed: float = 1.0
@@ -54,8 +60,10 @@ class AudioOutSpec:
 
     def validate(self, in_rate: int) -> "AudioOutSpec":
         """Raises ``ValueError`` with the library's reason when the resampler refuses ``in_rate -> sample_rate`` or the time-scale
-        stage refuses ``in_rate`` (host only)."""
+        stage refuses ``in_rate``, or the FLAC stage the output rate (host only)."""
         design(int(in_rate), self.out_rate(in_rate), bank=False)
+        if self.encoding == "flac":
+            flac_design(self.out_rate(in_rate))
         if self.permille != 1000:
             tsm_design(int(in_rate), self.permille, window=False)
         return self
@@ -106,6 +114,32 @@ def tsm_count(in_rate: int, permille: int, n_in: int, final: bool) -> int:
     return int(n)
 
 
+def flac_design(rate: int, block: int = 0):
+    """``(block size in force, frame bound 2 * block + 18 bytes)`` of the FLAC stage (``fq3_flac_design``; no GPU needed)."""
+    lib = _lib.load()
+    b, m = C.c_int(), C.c_int()
+    if lib.fq3_flac_design(int(rate), int(block), C.byref(b), C.byref(m)) != 0:
+        raise ValueError(lib.fq3_last_error().decode("utf-8", "replace"))
+    return b.value, m.value
+
+
+def flac_count(rate: int, block: int, n_in: int, final: bool) -> int:
+    """FLAC frames that exist once ``n_in`` samples of a stream were pushed (``fq3_flac_count``)."""
+    n = _lib.load().fq3_flac_count(int(rate), int(block), int(n_in), 1 if final else 0)
+    if n < 0:
+        _lib.check(int(n))
+    return int(n)
+
+
+def flac_header(rate: int, block: int = 0, total: int = 0) -> bytes:
+    """The 42 bytes in front of a FLAC stream's frames (``fq3_flac_header``; no GPU needed).  ``total`` 0: length unknown."""
+    lib = _lib.load()
+    buf = (C.c_uint8 * FLAC_HEADER_BYTES)()
+    if lib.fq3_flac_header(int(rate), int(block), int(total), buf, FLAC_HEADER_BYTES) != 0:
+        raise ValueError(lib.fq3_last_error().decode("utf-8", "replace"))
+    return bytes(buf)
+
+
 class AudioOut:
     """One stream through the stage.  ``push(pcm)`` takes the next float32 samples (a device tensor) and returns the output samples
     they complete as a device tensor (float32 / int16 / uint8); ``push(..., final=True)`` ends the stream and returns the rest.
@@ -113,9 +147,17 @@ class AudioOut:
 
     With a ``speed`` other than 1 the samples first go through the time-scale stage (one launch of its own, one intermediate device
     tensor per push), which holds back about 30 ms of input (N + delta = 3 hops of in_rate / 100 samples) until the final push.
-    ``n_in`` counts the vocoder's samples, ``n_out`` what has left the chain."""
+    ``n_in`` counts the vocoder's samples, ``n_out`` what has left the chain.
 
-    def __init__(self, spec: AudioOutSpec, in_rate: int, device, stream=None, zero_crossings: int = 0):
+    With the ``flac`` encoding the s16 samples go into an intermediate device tensor and through the FLAC stage (a launch pair per 64
+    frames), which holds back the samples behind the last whole block (up to 48 ms at 24 kHz) until the final push.  ``push`` then
+    returns the bytes of the frames this push completes -- without the stream header: ``header()`` -- and ``n_out`` counts bytes
+    (``n_samples``, with every encoding, the samples that left the resample + encode launch).  How many bytes that is only the device
+    knows: ``push`` reads the 8-byte length (one synchronisation of the stream) and slices; ``push_host`` copies the length and the
+    frame buffer to the host in ONE transfer and slices there, so that a caller who wants the bytes on the host pays the one
+    synchronisation its copy has anyway."""
+
+    def __init__(self, spec: AudioOutSpec, in_rate: int, device, stream=None, zero_crossings: int = 0, flac_block: int = 0):
         self.spec, self.in_rate, self.out_rate = spec, int(in_rate), spec.out_rate(in_rate)
         self.dev = torch.device(device) if not isinstance(device, torch.device) else device
         if self.dev.type != "cuda":
@@ -123,10 +165,11 @@ class AudioOut:
         if self.dev.index is None:
             self.dev = torch.device("cuda", torch.cuda.current_device())
         self.stream, self.zero = stream, int(zero_crossings)
-        self.dtype = _DTYPES[spec.encoding]
+        self.dtype = torch.int16 if spec.encoding == "flac" else _DTYPES[spec.encoding]      # what the resample + encode launch writes
         self.permille = spec.permille
         self._lib = _lib.load()
-        self._h = self._tsm = None
+        self._h = self._tsm = self._flac = None
+        self.flac = spec.encoding == "flac"
         # speed alone (the model's rate, float32): the time-scale stage writes the output itself, no second launch
         self._encode = self.permille == 1000 or self.out_rate != self.in_rate or spec.encoding != "f32"
         with torch.cuda.device(self.dev):
@@ -135,7 +178,10 @@ class AudioOut:
             if self._encode:
                 self._h = self._create(self._lib.fq3_audio_out_create,
                                        _lib.AudioOutConfig(self.in_rate, self.out_rate, ENCODINGS[spec.encoding], self.zero))
-        self.n_in = self.n_mid = self.n_out = 0
+            if self.flac:
+                self.flac_block, self.flac_bound = flac_design(self.out_rate, flac_block)
+                self._flac = self._create(self._lib.fq3_flac_create, _lib.FlacConfig(self.out_rate, self.flac_block))
+        self.n_in = self.n_mid = self.n_out = self.n_samples = 0
         self.finished = False
         self._empty = torch.empty(0, dtype=torch.float32, device=self.dev)
 
@@ -154,6 +200,9 @@ class AudioOut:
         t, self._tsm = getattr(self, "_tsm", None), None
         if t:
             self._lib.fq3_tsm_destroy(t)
+        f, self._flac = getattr(self, "_flac", None), None
+        if f:
+            self._lib.fq3_flac_destroy(f)
 
     def _stream(self):
         return self.stream if self.stream is not None else torch.cuda.current_stream(self.dev)
@@ -165,11 +214,56 @@ class AudioOut:
             _lib.check(self._lib.fq3_tsm_reset(self._tsm, s))
         if self._h:
             _lib.check(self._lib.fq3_audio_out_reset(self._h, s))
-        self.n_in = self.n_mid = self.n_out = 0
+        if self._flac:
+            _lib.check(self._lib.fq3_flac_reset(self._flac, s))
+        self.n_in = self.n_mid = self.n_out = self.n_samples = 0
         self.finished = False
 
     def push(self, pcm: Optional[torch.Tensor], final: bool = False) -> torch.Tensor:
+        if self.flac:
+            buf = self._push_flac(pcm, final)
+            with torch.cuda.stream(self._stream()):            # (the copy must queue behind the stage's launches, on ITS stream)
+                n = int(buf[:8].view(torch.int64).item())      # the one synchronisation: how many bytes the frames took
+            self.n_out += n
+            return buf[8: 8 + n]
         return self.push_into(pcm, final, None)
+
+    def push_host(self, pcm: Optional[torch.Tensor], final: bool = False) -> np.ndarray:
+        """``push`` with the result on the host.  ``flac``: the length and the frames cross in one copy (one synchronisation)."""
+        if not self.flac:
+            return self.push(pcm, final).cpu().numpy()
+        buf = self._push_flac(pcm, final)
+        with torch.cuda.stream(self._stream()):
+            host = buf.cpu().numpy()
+        n = int(host[:8].view(np.int64)[0])
+        self.n_out += n
+        return host[8: 8 + n]
+
+    def header(self, total: int = 0) -> bytes:
+        """``flac``: the stream header (``total`` samples; 0: unknown) that goes in front of everything ``push`` returns."""
+        if not self.flac:
+            raise ValueError("only the flac encoding has a stream header")
+        return flac_header(self.out_rate, self.flac_block, total)
+
+    def _push_flac(self, pcm: Optional[torch.Tensor], final: bool):
+        """-> device uint8 buffer: the total length of the frames this push completes as an int64, then the frames back to back"""
+        s = self._stream()
+        before = self.n_samples
+        pcm16 = self.push_into(pcm, final, None)               # the s16 half of the chain, through the code every encoding shares
+        n = int(pcm16.numel())
+        assert self.n_samples == before + n
+        frames = flac_count(self.out_rate, self.flac_block, self.n_samples, final) - flac_count(self.out_rate, self.flac_block, before, False)
+        with torch.cuda.device(self.dev), torch.cuda.stream(s):
+            cap = frames * self.flac_bound
+            buf = torch.empty(8 + cap, dtype=torch.uint8, device=self.dev)          # torch aligns allocations far beyond 8 bytes
+            got = C.c_int64()
+            _lib.check(self._lib.fq3_flac_push(self._flac, C.c_void_p(pcm16.data_ptr() if n else None), n, 1 if final else 0,
+                                               C.c_void_p(buf.data_ptr() + 8 if cap else None), cap, C.byref(got),
+                                               C.c_void_p(buf.data_ptr()), C.c_void_p(s.cuda_stream)))
+            assert got.value == frames
+            if n:
+                pcm16.record_stream(s)
+        return buf
 
     def _counts(self, n_in: int, final: bool):
         """(time-scaled samples, output samples) that exist once ``n_in`` samples of the stream were pushed"""
@@ -178,7 +272,7 @@ class AudioOut:
 
     def push_into(self, pcm: Optional[torch.Tensor], final: bool, out: Optional[torch.Tensor]) -> torch.Tensor:
         """``push`` into ``out`` (a device tensor of the stage's dtype with room for the samples this push completes; None: a new
-        tensor of exactly that size).  Returns the part of ``out`` that was written."""
+        tensor of exactly that size).  Returns the part of ``out`` that was written.  ``flac``: the s16 half of the chain alone."""
         if self.finished:
             # the library's own answer (FQ3_ESTATE, before any launch): the output count below has no meaning past the end
             if self._h:
@@ -192,7 +286,7 @@ class AudioOut:
                 x = x.to(device=self.dev, dtype=torch.float32).contiguous()
             n = n_pushed = int(x.numel())
             mid_total, out_total = self._counts(self.n_in + n, final)
-            n_mid, need = mid_total - self.n_mid, out_total - self.n_out
+            n_mid, need = mid_total - self.n_mid, out_total - self.n_samples
             if out is None:
                 out = torch.empty(need, dtype=self.dtype, device=self.dev)
             elif out.dtype != self.dtype or out.device != self.dev or not out.is_contiguous() or out.dim() != 1:
@@ -218,7 +312,9 @@ class AudioOut:
                 if n:
                     x.record_stream(s)
         self.n_in += n_pushed
-        self.n_mid, self.n_out = mid_total, out_total
+        self.n_mid, self.n_samples = mid_total, out_total
+        if not self.flac:
+            self.n_out = out_total
         self.finished = self.finished or bool(final)
         return out[:need]
 

@@ -122,10 +122,17 @@ def _output_stage(model, args):
 
 
 def _write_output(path, audio, sr, args):
-    """float32 audio as 16-bit PCM (as ever); what the output stage encoded (int16, G.711 bytes) as it is."""
+    """float32 audio as 16-bit PCM (as ever); what the output stage encoded (int16, G.711 bytes, a FLAC stream) as it is."""
+    import os
     from .audio_io import write_wav, write_wav_encoded
     enc = getattr(args, "encoding", None)
-    if enc in ("s16", "mulaw", "alaw"):
+    if enc == "flac":
+        if not path.lower().endswith(".flac"):
+            print(f"WARNING: {path} receives a FLAC stream; a .flac name would say so")
+        os.makedirs(os.path.dirname(path) or ".", exist_ok=True)
+        with open(path, "wb") as f:
+            f.write(np.ascontiguousarray(audio, dtype=np.uint8).tobytes())
+    elif enc in ("s16", "mulaw", "alaw"):
         write_wav_encoded(path, audio, sr, enc)
     else:
         write_wav(path, audio, sr)
@@ -155,6 +162,9 @@ def cmd_once(args, model=None, lines=None):
         audio, sr = synthesize_text_stream(model, args, _stdin_pieces(lines)) if text_stdin else synthesize(model, args, args.text)
     total = time.perf_counter() - start
     _write_output(args.output, audio, sr, args)
+    if getattr(args, "encoding", None) == "flac":              # bytes, not samples: the duration is inside the stream
+        print(f"Wrote {args.output} ({len(audio)} bytes of FLAC in {total:.2f}s)")
+        return
     dur = len(audio) / sr if sr else 0.0
     print(f"Wrote {args.output} (dur {dur:.2f}s, RTF {dur / total if total > 0 else 0.0:.2f})")
 
@@ -198,9 +208,13 @@ def cmd_serve(args, model=None, lines=None):
                 outs = [synthesize(model, args, t) for t in pending]
         total = time.perf_counter() - start
         for audio, sr in outs:
-            out_path = os.path.join(args.output_dir, f"out_{idx:04d}.wav")
+            flac = getattr(args, "encoding", None) == "flac"
+            out_path = os.path.join(args.output_dir, f"out_{idx:04d}.{'flac' if flac else 'wav'}")
             idx += 1
             _write_output(out_path, audio, sr, args)
+            if flac:
+                print(f"Wrote {out_path} ({len(audio)} bytes of FLAC)")
+                continue
             dur = len(audio) / sr if sr else 0.0
             print(f"Wrote {out_path} (dur {dur:.2f}s, RTF {dur * len(outs) / total if total > 0 else 0.0:.2f})")
 
@@ -226,8 +240,9 @@ def build_parser():
         sp.add_argument("--chunk-size", type=int, default=12)
         sp.add_argument("--out-rate", type=int, default=None, metavar="HZ",
                         help="output sample rate, resampled on the device (e.g. 8000, 16000, 44100, 48000; default: the model's)")
-        sp.add_argument("--encoding", default=None, choices=["f32", "s16", "mulaw", "alaw"],
-                        help="sample encoding done on the device; mulaw / alaw write a G.711 WAV (default: float32, written as 16-bit)")
+        sp.add_argument("--encoding", default=None, choices=["f32", "s16", "mulaw", "alaw", "flac"],
+                        help="sample encoding done on the device; mulaw / alaw write a G.711 WAV, flac a FLAC file of the s16 samples, "
+                             "compressed on the device (default: float32, written as 16-bit)")
         sp.add_argument("--speed", type=float, default=None, metavar="X",
                         help="speaking rate, 0.25 to 4.0, time-scaled on the device: duration changes, pitch does not (default: 1.0)")
         if output:

@@ -235,13 +235,15 @@ class StreamingVocoder:
     waveform goes through the device output stage (``fq3hip/audio_out.py``) on the vocoder's stream before it is copied to the host,
     and the rate handed back with a chunk is the output rate.  The stage holds back its look-ahead (about 16 * max(1, in / out) input
     samples; with a ``speed`` other than 1 the time-scale stage in front of it adds about 30 ms of input, three hops of 10 ms, and
-    hands out whole 10 ms segments) until ``push(..., final=True)`` or ``flush()``."""
+    hands out whole 10 ms segments) until ``push(..., final=True)`` or ``flush()``.  With the ``flac`` encoding the chunks are
+    ``uint8`` arrays that concatenate to a complete FLAC stream: the first begins with the 42-byte header, and the samples behind the
+    last whole FLAC block (up to 48 ms at 24 kHz) wait for the final push as well."""
 
     CONTEXT_FRAMES = 25
 
     def __init__(self, tok, ref_codes, chunk_size: int, device, side_stream=None, output=None):
         self.tok, self.ref_codes, self.side = tok, ref_codes, side_stream
-        self.output, self.stage = output, None
+        self.output, self.stage, self.header_sent = output, None, False
         self.dev = torch.device(device) if not isinstance(device, torch.device) else device
         self.min_cal = max(self.CONTEXT_FRAMES, int(chunk_size))
         self.all_codes: List[torch.Tensor] = []
@@ -262,10 +264,12 @@ class StreamingVocoder:
     def _encoded(self, wav, final: bool):
         """``wav`` (device tensor, or None for the tail alone) through the output stage -> (host array, output rate)"""
         st = self._stage()
-        if self.side is None:
-            return st.push(wav, final).cpu().numpy(), st.out_rate
-        with torch.cuda.stream(self.side):
-            return st.push(wav, final).cpu().numpy(), st.out_rate
+        with (contextlib.nullcontext() if self.side is None else torch.cuda.stream(self.side)):
+            out = st.push_host(wav, final)
+        if st.flac and not self.header_sent:
+            # a FLAC stream: the utterance's first chunk starts with the stream header (length unknown); the chunks are bytes
+            out, self.header_sent = np.concatenate([np.frombuffer(st.header(), dtype=np.uint8), out]), True
+        return out, st.out_rate
 
     def flush(self):
         """With an ``output``: ends the stage's stream and returns ``(tail, rate)`` -- the samples it held back as look-ahead -- for an
@@ -798,8 +802,10 @@ class FasterQwen3TTS:
     @contextlib.contextmanager
     def audio_output(self, sample_rate: Optional[int] = None, encoding: str = "f32", speed: float = 1.0):
         """Context manager: inside it the single-stream entry points (``generate_*``, ``generate_*_streaming``, ``stream_*``) hand out
-        audio at ``sample_rate`` (None: the model's) in ``encoding`` (``f32`` | ``s16`` | ``mulaw`` | ``alaw``), resampled and encoded
-        on the device before the copy to the host (``fq3hip/audio_out.py``); ``sr`` in what they yield or return is the output rate.
+        audio at ``sample_rate`` (None: the model's) in ``encoding`` (``f32`` | ``s16`` | ``mulaw`` | ``alaw`` | ``flac``), resampled and
+        encoded on the device before the copy to the host (``fq3hip/audio_out.py``); ``sr`` in what they yield or return is the output
+        rate.  ``flac``: the s16 samples compressed losslessly on the device; the streaming entry points yield ``uint8`` chunks that
+        concatenate to a FLAC stream (the first one starts with the header), the one-shot ones return one ``uint8`` array, a FLAC file.
         ``speed`` in [0.25, 4.0] (1.0: off) time-scales the audio on the device first: an utterance of n samples becomes
         ceil(n / speed) samples at the same pitch.  The ``*_batch`` entry points raise ``ValueError`` inside it.  Outside it nothing
         changes."""
@@ -822,7 +828,10 @@ class FasterQwen3TTS:
         dev = torch.device(self.device) if not isinstance(self.device, torch.device) else self.device
         stage = AudioOut(self._audio_spec, self.sample_rate, wav.device if hasattr(wav, "is_cuda") and wav.is_cuda else dev)
         x = wav.flatten().float() if hasattr(wav, "cpu") else torch.from_numpy(np.ascontiguousarray(wav, dtype=np.float32).reshape(-1))
-        return stage.push(x.to(stage.dev), final=True).cpu().numpy(), stage.out_rate
+        out = stage.push_host(x.to(stage.dev), final=True)
+        if stage.flac:                 # a whole FLAC file: its header carries the sample count
+            out = np.concatenate([np.frombuffer(stage.header(stage.n_samples), dtype=np.uint8), out])
+        return out, stage.out_rate
 
     @staticmethod
     def _tail_event(voc, timing: Optional[dict]):

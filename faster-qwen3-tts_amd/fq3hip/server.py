@@ -39,7 +39,7 @@ from pydantic import BaseModel
 from .audio_io import to_pcm16, to_wav_bytes, wav_header, wav_header_for
 
 logger = logging.getLogger(__name__)
-CONTENT_TYPES = {"wav": "audio/wav", "pcm": "audio/pcm", "mp3": "audio/mpeg"}
+CONTENT_TYPES = {"wav": "audio/wav", "pcm": "audio/pcm", "mp3": "audio/mpeg", "flac": "audio/flac"}
 
 
 class SpeechRequest(BaseModel):
@@ -47,7 +47,7 @@ class SpeechRequest(BaseModel):
     model: str = "tts-1"
     input: str
     voice: str = "alloy"
-    response_format: str = "wav"          # wav | pcm | mp3
+    response_format: str = "wav"          # wav | pcm | flac (compressed on the device: the s16 samples, losslessly) | mp3 (refused)
     speed: float = 1.0                     # 0.25 .. 4.0, applied on the device after the vocoder (duration changes, pitch does not)
     # extension: the device audio output stage (fq3hip/audio_out.py).  Both absent: 16-bit PCM at the model's rate, as ever
     sample_rate: Optional[int] = None      # Hz, e.g. 8000, 16000, 44100, 48000
@@ -56,7 +56,7 @@ class SpeechRequest(BaseModel):
 
 class SessionRequest(BaseModel):
     voice: str = "alloy"
-    response_format: str = "wav"          # wav | pcm
+    response_format: str = "wav"          # wav | pcm | flac
     speed: float = 1.0                     # as in SpeechRequest
     sample_rate: Optional[int] = None
     encoding: Optional[str] = None
@@ -263,13 +263,28 @@ def create_app(model, voices: Dict[str, dict], default_voice: Optional[str] = No
             return voices[default_voice]
         raise HTTPException(status_code=400, detail=f"Voice {name!r} is not configured. Available voices: {list(voices.keys())}")
 
-    def request_spec(req):
+    # FLAC is made by the device stage alone: a model without ``audio_output`` cannot answer it
+    flac_ok = hasattr(model, "audio_output")
+
+    def request_spec(req, fmt: str = "wav"):
         """The request's ``AudioOutSpec``, or None when it names neither a rate nor an encoding nor a speed other than 1 (today's
-        path).  400 for an unknown encoding, a rate the resampler refuses or a speed outside [0.25, 4.0]."""
+        path).  400 for an unknown encoding, a rate the resampler refuses or a speed outside [0.25, 4.0].  ``response_format="flac"``
+        is the ``flac`` encoding of the stage (with the request's rate and speed); it is the whole answer's format, so a request that
+        also names an ``encoding`` gets 400, and so does ``encoding="flac"`` under another format."""
+        from .audio_out import AudioOutSpec
+        if fmt == "flac":
+            if req.encoding is not None:
+                raise HTTPException(status_code=400, detail="response_format='flac' is an encoding of its own (the s16 samples, compressed "
+                                                            "losslessly): leave 'encoding' out")
+            try:
+                return AudioOutSpec(req.sample_rate, "flac", req.speed).validate(sample_rate)
+            except ValueError as exc:
+                raise HTTPException(status_code=400, detail=str(exc))
         if req.sample_rate is None and req.encoding is None and req.speed == 1.0:
             return None
-        from .audio_out import AudioOutSpec
         enc = (req.encoding or "s16").lower()
+        if enc == "flac":
+            raise HTTPException(status_code=400, detail="encoding 'flac' is asked for with response_format='flac'")
         try:
             return AudioOutSpec(req.sample_rate, "s16" if enc == "f32" else enc, req.speed).validate(sample_rate)
         except ValueError as exc:
@@ -370,9 +385,9 @@ def create_app(model, voices: Dict[str, dict], default_voice: Optional[str] = No
             raise HTTPException(status_code=400, detail="text sessions need --scheduler batch")
         cfg = resolve_voice(req.voice)
         fmt = req.response_format.lower()
-        if fmt not in ("wav", "pcm"):
+        if fmt not in ("wav", "pcm", "flac") or (fmt == "flac" and not flac_ok):
             raise HTTPException(status_code=400, detail=f"response_format {fmt!r} not supported for sessions. Use: wav, pcm")
-        spec = request_spec(req)
+        spec = request_spec(req, fmt)
         if spec is not None:
             cfg = dict(cfg, audio_output=spec)
         try:
@@ -425,11 +440,11 @@ def create_app(model, voices: Dict[str, dict], default_voice: Optional[str] = No
             raise HTTPException(status_code=400, detail="'input' text is empty")
         cfg = resolve_voice(req.voice)
         fmt = req.response_format.lower()
-        if fmt not in CONTENT_TYPES:
+        if fmt not in CONTENT_TYPES or (fmt == "flac" and not flac_ok):
             raise HTTPException(status_code=400, detail=f"response_format {fmt!r} not supported. Use: wav, pcm, mp3")
         if fmt == "mp3":
             raise HTTPException(status_code=400, detail="response_format='mp3' needs pydub + ffmpeg, which this image does not ship; use wav or pcm")
-        spec = request_spec(req)
+        spec = request_spec(req, fmt)
         if worker is not None:
             return await box_response(worker.submit(cfg if spec is None else dict(cfg, audio_output=spec), req.input), fmt, spec=spec)
 

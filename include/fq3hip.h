@@ -548,6 +548,44 @@ int fq3_tsm_reset(fq3_tsm* t, void* stream);
 int fq3_tsm_push(fq3_tsm* t, const float* pcm, int64_t n_in, int final, float* out, int64_t capacity_samples,
                  int64_t* n_out, int32_t* deltas, int64_t deltas_capacity, void* stream);
 
+/* ---- FLAC output: lossless compression of the s16 samples on the device ------------------------------------------------------
+ * Behind the s16 output stage: int16 device samples in, FLAC frames (device bytes) out; the 42-byte stream header is made on the
+ * host.  Decoding the stream gives the s16 samples bit for bit.  The result does not depend on how the stream was cut into pushes.
+ *
+ * The stream: `fLaC`, one STREAMINFO block (block size, rate, mono, 16 bits, total samples or 0 = unknown, no MD5), then frames of B
+ * samples -- only the last frame of a stream may be shorter -- with fixed-blocksize frame numbers, a CRC-8 over the header and a
+ * CRC-16 over the frame.  B = block_size, any value in [16, 4608]; 0: 1152 above 16 kHz, else 576.  The rate needs a frame-header
+ * code: 8, 16, 22.05, 24, 32, 44.1, 48, 88.2, 96 kHz, or any rate up to 65535 Hz (two more header bytes); else FQ3_EINVAL.
+ * A frame holds one subframe, chosen per block of n samples by this rule:
+ *   - all samples equal: CONSTANT;
+ *   - else for every FIXED order o in 0 .. min(4, n - 1) and every partition order p in 0 .. 6 with n % 2^p == 0 and (n >> p) > o:
+ *     per partition the Rice parameter k in 0 .. 14 that minimises count (1 + k) + sum(u >> k), u = (r << 1) ^ (r >> 31), lowest k
+ *     on ties; cost = 16 o + 6 + sum over partitions of (4 + that minimum); the cheapest (o, p), ties to the lower o, then the lower p;
+ *   - that cost >= 16 n: VERBATIM.
+ * A frame is therefore never longer than 2 n + 18 bytes. */
+typedef struct fq3_flac fq3_flac;
+typedef struct fq3_flac_config { int sample_rate, block_size; } fq3_flac_config;      /* block_size 0: the default */
+/* host only: the block size in force and the frame bound 2 * block + 18 */
+int fq3_flac_design(int sample_rate, int block_size, int* block, int* max_frame_bytes);
+/* host only: the 42 header bytes into out (capacity >= 42); total_samples in [0, 2^36), 0 = unknown (a stream in progress) */
+int fq3_flac_header(int sample_rate, int block_size, int64_t total_samples, uint8_t* out, int64_t capacity);
+/* frames that exist once n_in samples of a stream were pushed: floor(n_in / B); final != 0: ceil.  Negative: an FQ3_E* code */
+int64_t fq3_flac_count(int sample_rate, int block_size, int64_t n_in, int final);
+/* One object per stream; it owns the held-back tail (fewer than B samples), the frame counter and staging for 64 frames on the
+ * current device.  NULL or range errors are answered before any HIP call. */
+int fq3_flac_create(const fq3_flac_config* cfg, fq3_flac** out);
+int fq3_flac_destroy(fq3_flac* f);                           /* NULL -> 0 */
+/* a new utterance on the same object (nothing is enqueued) */
+int fq3_flac_reset(fq3_flac* f, void* stream);
+/* pcm: n_in device int16 (n_in may be 0), the next samples of the stream; final != 0: the stream ends with them.  out: device bytes
+ * at any alignment.  *n_frames (host) = the frames this push completes, known before the launch; capacity_bytes below
+ * *n_frames * max_frame_bytes: FQ3_EINVAL and nothing is launched.  The frames are written back to back from out[0];
+ * *n_bytes_dev (a DEVICE int64, required) receives their total length.  Per 64 frames one launch pair on `stream` -- the frames are
+ * encoded into the object's staging, one workgroup each, then gathered -- and no host synchronisation; pcm, out and n_bytes_dev must
+ * stay valid until the stream has run them.  After a final push: FQ3_ESTATE until fq3_flac_reset. */
+int fq3_flac_push(fq3_flac* f, const int16_t* pcm, int64_t n_in, int final, uint8_t* out, int64_t capacity_bytes,
+                  int64_t* n_frames, int64_t* n_bytes_dev, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

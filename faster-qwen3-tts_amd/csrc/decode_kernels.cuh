@@ -293,8 +293,35 @@ __device__ __forceinline__ void gemv_body(const GemvArgs& a) {
     }
 }
 
+// Kernel entry ("kernel entry"): gfx950 delivers the first 14 dwords of the kernarg segment in user SGPRs at
+// wave launch when the arguments are plain pointers / 32-bit scalars and the file is built with -amdgpu-kernarg-preload-count (the
+// Makefile's KERNARG_PRELOAD); a by-value struct is never preloaded and ends the preloaded run.  So every kernel of the frame takes
+// what it needs to ISSUE ITS FIRST LOADS as leading flat arguments -- pointers first (no padding holes), then scalars -- and the
+// rest, which is read behind those loads anyway, as one trailing struct.  The wrapper rebuilds the argument struct of the body; the
+// *_launch helper beside it does the split, so the callers keep filling GemvArgs / AttnArgs.  tests/test_kernarg_preload.py reads
+// the preload length of every one of these kernels from the built library.
+constexpr int kGemvLeadDwords = 12;      // W, x | part, norm_w; N, K, eps, up_off, n_part, rep: sections 1 and 2 of gemv_body
+struct GemvTail { void* y; const void* res; const void* bias; void* xn_out; const void* x2; void* y2; const void* res2; size_t part_stride2; };
+
 template <typename T, int NCH, int PRO, int EPI, bool NT, int M = 1, int R = 1>
-__global__ __launch_bounds__(256) void gemv_kernel(GemvArgs a) { gemv_body<T, NCH, PRO, EPI, NT, M, R>(a); }
+__global__ __launch_bounds__(256) void gemv_kernel(const void* W, const void* x, const void* norm_w, int N, int K, float eps, int up_off,
+                                                   int n_part, int rep, GemvTail t) {
+    GemvArgs a;
+    a.W = W; a.N = N; a.K = K;
+    a.x = PRO == PRO_COMBINE ? nullptr : x;                                  // (one slot: a launch has either an input vector or partial slots)
+    a.part = PRO == PRO_COMBINE ? reinterpret_cast<const float*>(x) : nullptr;
+    a.norm_w = norm_w; a.eps = eps; a.up_off = up_off; a.n_part = n_part; a.rep = rep;
+    a.bias = t.bias; a.y = t.y; a.res = t.res; a.xn_out = t.xn_out;
+    a.x2 = t.x2; a.y2 = t.y2; a.res2 = t.res2; a.part_stride2 = t.part_stride2;
+    gemv_body<T, NCH, PRO, EPI, NT, M, R>(a);
+}
+template <typename T, int NCH, int PRO, int EPI, bool NT, int M, int R>
+inline void gemv_launch(const GemvArgs& a, int grid, size_t shm, hipStream_t s) {
+    const GemvTail t{a.y, a.res, a.bias, a.xn_out, a.x2, a.y2, a.res2, a.part_stride2};
+    const void* x = PRO == PRO_COMBINE ? static_cast<const void*>(a.part) : a.x;
+    hipLaunchKernelGGL((gemv_kernel<T, NCH, PRO, EPI, NT, M, R>), dim3(grid), dim3(256), shm, s, a.W, x, a.norm_w, a.N, a.K, a.eps, a.up_off,
+                       a.n_part, a.rep, t);
+}
 
 // ================================================================================================
 // Attention for one new token over the talker's PAGED KV cache: fixed-size blocks of 64 keys (= one
@@ -495,8 +522,38 @@ __device__ __forceinline__ void attn_decode_body(const AttnArgs& a) {
     }
 }
 
+// what the attention kernels do not take as leading arguments (see gemv_kernel): each wrapper reads the fields its own leading list
+// leaves out (table / pos_ptr / blk_stride: attn_pred_kernel; q_norm_w / k_norm_w / rep: attn_decode_kernel)
+struct AttnTail {
+    const void* q_norm_w; const void* k_norm_w; const float* cos_row; const float* sin_row;
+    const int* table; const int* pos_ptr; const int* done_ptr; float* part; void* out;
+    float eps; float scale; int n_pad; int blk_stride; int rep;
+};
+inline AttnTail attn_tail(const AttnArgs& a) {
+    return AttnTail{a.q_norm_w, a.k_norm_w, a.cos_row, a.sin_row, a.table, a.pos_ptr, a.done_ptr, a.part, a.out, a.eps, a.scale, a.n_pad, a.blk_stride, a.rep};
+}
+__device__ __forceinline__ AttnArgs attn_args_of(const AttnTail& t) {
+    AttnArgs a;
+    a.q_norm_w = t.q_norm_w; a.k_norm_w = t.k_norm_w; a.cos_row = t.cos_row; a.sin_row = t.sin_row;
+    a.table = t.table; a.pos_ptr = t.pos_ptr; a.done_ptr = t.done_ptr; a.part = t.part; a.out = t.out;
+    a.eps = t.eps; a.scale = t.scale; a.n_pad = t.n_pad; a.blk_stride = t.blk_stride; a.rep = t.rep;
+    return a;
+}
+
+constexpr int kAttnDecodeLeadDwords = 14;    // table, qkv, kcache, vcache, pos_ptr; max_seq, n_kv, blk_stride, pos_imm
 template <typename T, int REP, bool PAGED>
-__global__ __launch_bounds__(256) void attn_decode_kernel(AttnArgs a) { attn_decode_body<T, REP, PAGED>(a); }
+__global__ __launch_bounds__(256) void attn_decode_kernel(const int* table, const void* qkv, void* kcache, void* vcache, const int* pos_ptr,
+                                                          int max_seq, int n_kv, int blk_stride, int pos_imm, AttnTail t) {
+    AttnArgs a = attn_args_of(t);
+    a.table = table; a.qkv = qkv; a.kcache = kcache; a.vcache = vcache; a.pos_ptr = pos_ptr;
+    a.max_seq = max_seq; a.n_kv = n_kv; a.blk_stride = blk_stride; a.pos_imm = pos_imm;
+    attn_decode_body<T, REP, PAGED>(a);
+}
+template <typename T, int REP, bool PAGED>
+inline void attn_decode_launch(const AttnArgs& a, int workers, hipStream_t s) {
+    hipLaunchKernelGGL((attn_decode_kernel<T, REP, PAGED>), dim3(a.n_kv, workers), dim3(256), 0, s, a.table, a.qkv, a.kcache, a.vcache, a.pos_ptr,
+                       a.max_seq, a.n_kv, a.blk_stride, a.pos_imm, attn_tail(a));
+}
 
 // ================================================================================================
 // Code-predictor attention (context <= 17 keys): ONE wave per q head, everything in registers, no LDS, no
@@ -729,8 +786,21 @@ __device__ __forceinline__ void attn_pred_group_body(const AttnArgs& a, int g) {
     }
 }
 
+constexpr int kAttnPredLeadDwords = 14;      // qkv, q_norm_w, k_norm_w, kcache, vcache; n_kv, rep, max_seq, pos_imm
 template <typename T>
-__global__ __launch_bounds__(64) void attn_pred_kernel(AttnArgs a) { attn_pred_body<T>(a); }
+__global__ __launch_bounds__(64) void attn_pred_kernel(const void* qkv, const void* q_norm_w, const void* k_norm_w, void* kcache, void* vcache,
+                                                       int n_kv, int rep, int max_seq, int pos_imm, AttnTail t) {
+    AttnArgs a = attn_args_of(t);
+    a.qkv = qkv; a.q_norm_w = q_norm_w; a.k_norm_w = k_norm_w; a.kcache = kcache; a.vcache = vcache;
+    a.n_kv = n_kv; a.rep = rep; a.max_seq = max_seq; a.pos_imm = pos_imm;
+    attn_pred_body<T>(a);
+}
+// heads: the grid, one wave per q head
+template <typename T>
+inline void attn_pred_launch(const AttnArgs& a, int heads, hipStream_t s) {
+    hipLaunchKernelGGL((attn_pred_kernel<T>), dim3(heads), dim3(64), 0, s, a.qkv, a.q_norm_w, a.k_norm_w, a.kcache, a.vcache,
+                       a.n_kv, a.rep, a.max_seq, a.pos_imm, attn_tail(a));
+}
 
 // ================================================================================================
 // Small glue kernels
@@ -817,10 +887,16 @@ __device__ __forceinline__ void frame_begin_body(DecodeState* st, const T* codec
         pred_in[H + e] = codec_emb[(size_t)tok * H + e];
     }
 }
+constexpr int kFrameBeginLeadDwords = 14;    // st, past_hidden, codec_emb, pred_in, codes, seen; H, G (ph_hold: the hold path only)
 template <typename T>
-__global__ __launch_bounds__(256) void frame_begin_kernel(DecodeState* st, const T* codec_emb, const T* past_hidden, T* ph_hold,
-                                                          T* pred_in, int* codes, unsigned char* seen, int H, int G) {
+__global__ __launch_bounds__(256) void frame_begin_kernel(DecodeState* st, const T* past_hidden, const T* codec_emb, T* pred_in, int* codes,
+                                                          unsigned char* seen, int H, int G, T* ph_hold) {
     frame_begin_body<T>(st, codec_emb, past_hidden, ph_hold, pred_in, codes, seen, H, G);
+}
+template <typename T>
+inline void frame_begin_launch(DecodeState* st, const T* codec_emb, const T* past_hidden, T* ph_hold, T* pred_in, int* codes,
+                               unsigned char* seen, int H, int G, hipStream_t s) {
+    hipLaunchKernelGGL((frame_begin_kernel<T>), dim3(1), dim3(256), 0, s, st, past_hidden, codec_emb, pred_in, codes, seen, H, G, ph_hold);
 }
 
 // 16-way embedding sum + text/pad embed -> talker input (generate.py:162-171); position limit test
@@ -872,11 +948,18 @@ __device__ __forceinline__ void embed_sum_body(DecodeState* st, const EmbTables&
         for (int i = 0; i < 8; ++i) DT<T>::st(x + e0 + i, DT<T>::rnd(sum[i]) + f[i]);
     }
 }
+constexpr int kEmbedSumLeadDwords = 14;      // st, codes, cos_tab, sin_tab, rope_now, x; rope_len, rope_delta (H and the tables follow)
+struct EmbedSumTail { int H; EmbTables tabs; };
 template <typename T, int G>
-__global__ __launch_bounds__(256) void embed_sum_kernel(DecodeState* st, EmbTables tabs, const int* codes, T* x, int H,
-                                                        const float* cos_tab, const float* sin_tab, int rope_len,
-                                                        int rope_delta, float* rope_now) {
-    embed_sum_body<T, G>(st, tabs, codes, x, H, cos_tab, sin_tab, rope_len, rope_delta, rope_now);
+__global__ __launch_bounds__(256) void embed_sum_kernel(DecodeState* st, const int* codes, const float* cos_tab, const float* sin_tab,
+                                                        float* rope_now, T* x, int rope_len, int rope_delta, EmbedSumTail t) {
+    embed_sum_body<T, G>(st, t.tabs, codes, x, t.H, cos_tab, sin_tab, rope_len, rope_delta, rope_now);
+}
+template <typename T, int G>
+inline void embed_sum_launch(DecodeState* st, const EmbTables& tabs, const int* codes, T* x, int H, const float* cos_tab,
+                             const float* sin_tab, int rope_len, int rope_delta, float* rope_now, hipStream_t s) {
+    const EmbedSumTail t{H, tabs};
+    hipLaunchKernelGGL((embed_sum_kernel<T, G>), dim3(1), dim3(256), 0, s, st, codes, cos_tab, sin_tab, rope_now, x, rope_len, rope_delta, t);
 }
 
 }  // namespace fq3

@@ -401,9 +401,9 @@ static void launch_gemv_n(const GemvArgs& a, int rmax, hipStream_t s) {
     const int grid = gemv_grid(a.N, R);
     const size_t shm = gemv_lds_bytes<PRO, M>(a.K);
     if constexpr (MaxRows<NCH, EPI>::v >= 2) {
-        if (R == 2) { hipLaunchKernelGGL((gemv_kernel<T, NCH, PRO, EPI, NT, M, 2>), dim3(grid), dim3(256), shm, s, a); return; }
+        if (R == 2) { gemv_launch<T, NCH, PRO, EPI, NT, M, 2>(a, grid, shm, s); return; }
     }
-    hipLaunchKernelGGL((gemv_kernel<T, NCH, PRO, EPI, NT, M, 1>), dim3(grid), dim3(256), shm, s, a);
+    gemv_launch<T, NCH, PRO, EPI, NT, M, 1>(a, grid, shm, s);
 }
 // two-token launches: code predictor only (default cache policy).  Inner dimensions: a normalising GEMV reads the hidden size
 // (<= 2048: four 512-element chunks per lane), the others q_dim / the intermediate size (<= 3072 for a two-token pass: the row
@@ -444,7 +444,7 @@ static int launch_gemv(const fq3_ctx* c, const GemvArgs& a, bool nt, hipStream_t
 template <typename T, bool PAGED>
 static void launch_attn_p(const AttnArgs& a, int rep, int workers, hipStream_t s) {
     with_value<1, 2, 4>(rep, [&](auto r) {
-        hipLaunchKernelGGL((attn_decode_kernel<T, decltype(r)::value, PAGED>), dim3(a.n_kv, workers), dim3(256), 0, s, a);
+        attn_decode_launch<T, decltype(r)::value, PAGED>(a, workers, s);
     });
 }
 template <typename T>
@@ -505,8 +505,8 @@ static int run_stack(fq3_ctx* c, bool talker, const StepSrc& src, hipStream_t s)
         const bool pred_attn = c->opt_pred_attn && !talker && !src.pos_ptr && src.pos_imm <= 16;
         if (pred_attn) {
             // short context: one wave per q head, final head output written directly -> plain o_proj, no merge
-            if (c->cfg.dtype == FQ3_BF16) hipLaunchKernelGGL((attn_pred_kernel<bf16_t>), dim3(d.n_heads), dim3(64), 0, s, a);
-            else hipLaunchKernelGGL((attn_pred_kernel<float>), dim3(d.n_heads), dim3(64), 0, s, a);
+            if (c->cfg.dtype == FQ3_BF16) attn_pred_launch<bf16_t>(a, d.n_heads, s);
+            else attn_pred_launch<float>(a, d.n_heads, s);
             if (tail_skip) break;
             o.x = c->attn_out;
             if (int r = launch_gemv<PRO_PLAIN, EPI_RESIDUAL>(c, o, nt, s)) return r;
@@ -555,8 +555,8 @@ static int run_predictor_pair(fq3_ctx* c, const void* x_a, const void* x_b, hipS
             a.part = c->part + (size_t)m * c->part_stride; a.scale = 1.0f / sqrtf((float)kHeadDim);
             a.rep = rep; a.out = m == 0 ? c->attn_out : c->attn_out2;
             if (c->opt_pred_attn) {
-                if (c->cfg.dtype == FQ3_BF16) hipLaunchKernelGGL((attn_pred_kernel<bf16_t>), dim3(d.n_heads), dim3(64), 0, s, a);
-                else hipLaunchKernelGGL((attn_pred_kernel<float>), dim3(d.n_heads), dim3(64), 0, s, a);
+                if (c->cfg.dtype == FQ3_BF16) attn_pred_launch<bf16_t>(a, d.n_heads, s);
+                else attn_pred_launch<float>(a, d.n_heads, s);
             } else if (c->cfg.dtype == FQ3_BF16) launch_attn_t<bf16_t>(a, rep, kv.workers, s);
             else launch_attn_t<float>(a, rep, kv.workers, s);
         }
@@ -844,8 +844,7 @@ static void launch_sample_pred(const DecodeState* st, const T* lg, int V, int cb
                                const TeacherForcing* tf, hipStream_t s) {
     if (wave) dispatch_nc(V, [&](auto nc) {
         constexpr int NC = decltype(nc)::value;
-        hipLaunchKernelGGL((sample_pred_wave_kernel<T, NC>), dim3(1), dim3(256), 0, s, st, lg, V, cb, cfg, nz, codes, G,
-                           out64, next_emb, next_in, H, tf);
+        sample_pred_wave_launch<T, NC>(st, lg, V, cb, cfg, nz, codes, G, out64, next_emb, next_in, H, tf, s);
     });
     else hipLaunchKernelGGL((sample_pred_kernel<T>), dim3(1), dim3(256), 0, s, st, lg, V, cb, cfg, nz, codes, G, out64,
                             next_emb, next_in, H, tf);
@@ -855,7 +854,7 @@ static void launch_sample_talker(DecodeState* st, const T* lg, int V, const unsi
                                  const TeacherForcing* tf, hipStream_t s) {
     if (wave) dispatch_nc(V, [&](auto nc) {
         constexpr int NC = decltype(nc)::value;
-        hipLaunchKernelGGL((sample_talker_wave_kernel<T, NC>), dim3(1), dim3(256), 0, s, st, lg, V, seen, G, tf);
+        sample_talker_wave_launch<T, NC>(st, lg, V, seen, G, tf, s);
     });
     else hipLaunchKernelGGL((sample_talker_kernel<T>), dim3(1), dim3(256), 0, s, st, lg, V, seen, G, tf);
 }
@@ -1081,15 +1080,15 @@ static int enqueue_frame_t(fq3_ctx* c, hipStream_t s) {
     const fq3_stack_dims& t = c->cfg.talker;
     const int G = c->cfg.num_code_groups, H = t.hidden;
     DecodeState* st = c->st;
-    hipLaunchKernelGGL((frame_begin_kernel<T>), dim3(1), dim3(256), 0, s, st, (const T*)c->wt.codec_embedding,
-                       (const T*)c->past_hidden, (T*)c->ph_hold, (T*)c->pred_in, c->codes, c->seen, H, G);
+    frame_begin_launch<T>(st, (const T*)c->wt.codec_embedding, (const T*)c->past_hidden, (T*)c->ph_hold, (T*)c->pred_in, c->codes, c->seen,
+                          H, G, s);
     if (int r = predictor_passes_t<T>(c, st, c->pred_in, nullptr, nullptr, nullptr, s)) return r;
     EmbTables tabs{};
     tabs.t[0] = c->wt.codec_embedding;
     for (int i = 1; i < G; ++i) tabs.t[i] = c->pemb[i - 1];
     if (G != 16) return fail(FQ3_EUNSUPPORTED, "the fused loop is built for 16 code groups");
-    hipLaunchKernelGGL((embed_sum_kernel<T, 16>), dim3(1), dim3(256), 0, s, st, tabs, c->codes, (T*)c->xin, H,
-                       c->wt.talker_cos, c->wt.talker_sin, c->wt.talker_rope_len, c->rope_delta, c->rope_now);
+    embed_sum_launch<T, 16>(st, tabs, c->codes, (T*)c->xin, H, c->wt.talker_cos, c->wt.talker_sin, c->wt.talker_rope_len, c->rope_delta,
+                            c->rope_now, s);
     StepSrc src{c->xin, &st->pos, 0};
     if (int r = run_stack(c, true, src, s)) return r;
     // final norm fused into the codec_head GEMV; block 0 also stores the normed hidden = next frame's past_hidden

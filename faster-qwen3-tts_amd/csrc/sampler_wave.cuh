@@ -243,11 +243,21 @@ __device__ __forceinline__ void sample_pred_wave_body(const DecodeState* st, con
     }
 }
 
+// Leading arguments (preloaded into SGPRs at wave launch, decode_kernels.cuh "kernel entry"): what the logits / state / noise loads
+// need; the immediate policy and the epilogue's fields follow in a struct.
+constexpr int kSamplePredLeadDwords = 14;    // st, logits, noise_imm, codes, out64, next_emb; V, cb
 template <typename T, int NC>
-__global__ __launch_bounds__(256) void sample_pred_wave_kernel(const DecodeState* st, const T* logits, int V, int cb,
-                                                              SampleCfg c_imm, const T* noise_imm, int* codes, int G,
-                                                              int64_t* out64, const T* next_emb, T* next_in, int H, const TeacherForcing* tf) {
+__global__ __launch_bounds__(256) void sample_pred_wave_kernel(const DecodeState* st, const T* logits, const T* noise_imm, int* codes,
+                                                              int64_t* out64, const T* next_emb, int V, int cb, int G, int H,
+                                                              T* next_in, const TeacherForcing* tf, SampleCfg c_imm) {
     sample_pred_wave_body<T, NC>(st, logits, V, cb, c_imm, noise_imm, codes, G, out64, next_emb, next_in, H, tf);
+}
+template <typename T, int NC>
+inline void sample_pred_wave_launch(const DecodeState* st, const T* logits, int V, int cb, const SampleCfg& c_imm, const T* noise_imm,
+                                    int* codes, int G, int64_t* out64, const T* next_emb, T* next_in, int H, const TeacherForcing* tf,
+                                    hipStream_t s) {
+    hipLaunchKernelGGL((sample_pred_wave_kernel<T, NC>), dim3(1), dim3(256), 0, s, st, logits, noise_imm, codes, out64, next_emb, V, cb, G, H,
+                       next_in, tf, c_imm);
 }
 
 template <typename T, int NC, bool NUCLEUS = false>
@@ -276,10 +286,16 @@ __device__ __forceinline__ void sample_talker_wave_body(DecodeState* st, const T
     tok = forced_or(tf, (frame + 1) * G, tok);
     if (threadIdx.x == 0) { st->token = tok; st->frame = frame + 1; st->pos += 1; st->gen_step += 1; }
 }
+constexpr int kSampleTalkerLeadDwords = 10;  // st, logits, seen, tf; V, G: the whole list
 template <typename T, int NC>
-__global__ __launch_bounds__(256) void sample_talker_wave_kernel(DecodeState* st, const T* logits, int V,
-                                                                const unsigned char* seen, int G, const TeacherForcing* tf) {
+__global__ __launch_bounds__(256) void sample_talker_wave_kernel(DecodeState* st, const T* logits, const unsigned char* seen,
+                                                                const TeacherForcing* tf, int V, int G) {
     sample_talker_wave_body<T, NC>(st, logits, V, seen, G, tf);
+}
+template <typename T, int NC>
+inline void sample_talker_wave_launch(DecodeState* st, const T* logits, int V, const unsigned char* seen, int G, const TeacherForcing* tf,
+                                      hipStream_t s) {
+    hipLaunchKernelGGL((sample_talker_wave_kernel<T, NC>), dim3(1), dim3(256), 0, s, st, logits, seen, tf, V, G);
 }
 
 }  // namespace fq3

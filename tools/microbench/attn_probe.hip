@@ -174,8 +174,8 @@ int run_t(int kind, const AttnProbeArgs& p, hipStream_t s) {
             if (p.flags & FL_DONE_PTR) a.done_ptr = &db->done0;
             with_value<1, 2, 4>(p.rep, [&](auto r) {
                 constexpr int REP = decltype(r)::value;
-                if (p.paged) hipLaunchKernelGGL((attn_decode_kernel<T, REP, true>), dim3(p.n_kv, p.workers), dim3(256), 0, s, a);
-                else hipLaunchKernelGGL((attn_decode_kernel<T, REP, false>), dim3(p.n_kv, p.workers), dim3(256), 0, s, a);
+                if (p.paged) attn_decode_launch<T, REP, true>(a, p.workers, s);
+                else attn_decode_launch<T, REP, false>(a, p.workers, s);
             });
             break;
         case K_MERGE:
@@ -188,12 +188,12 @@ int run_t(int kind, const AttnProbeArgs& p, hipStream_t s) {
             const int grid = (g.N + 3) / 4;
             const size_t shm = (size_t)g.K * sizeof(float);
             with_value<1, 2, 4>(gemv_chunks(q_dim, 4), [&](auto n) {
-                hipLaunchKernelGGL((gemv_kernel<T, decltype(n)::value, PRO_COMBINE, EPI_STORE, false, 1, 1>), dim3(grid), dim3(256), shm, s, g);
+                gemv_launch<T, decltype(n)::value, PRO_COMBINE, EPI_STORE, false, 1, 1>(g, grid, shm, s);
             });
             break;
         }
         case K_PRED:
-            hipLaunchKernelGGL((attn_pred_kernel<T>), dim3(p.n_kv * p.rep), dim3(64), 0, s, a);
+            attn_pred_launch<T>(a, p.n_kv * p.rep, s);
             break;
         case K_PRED_BATCH:
             hipLaunchKernelGGL((attn_pred_batch_kernel<T>), dim3(p.n_kv * p.rep, B), dim3(64), 0, s, a, &db->kv, p.qkv_stride, p.out_stride);

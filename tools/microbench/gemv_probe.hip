@@ -209,9 +209,9 @@ int launch_one_gemv(const GemvArgs& a, int rmax, int te, hipStream_t s) {
     const size_t shm = gemv_lds_bytes<PRO, M>(a.K);
     g_last_inst = gemv_id(te, PE, NCH, NT, M, R);
     if constexpr (MaxRows<NCH, EPI>::v >= 2) {
-        if (R == 2) { hipLaunchKernelGGL((gemv_kernel<T, NCH, PRO, EPI, NT, M, 2>), dim3(grid), dim3(256), shm, s, a); return 0; }
+        if (R == 2) { gemv_launch<T, NCH, PRO, EPI, NT, M, 2>(a, grid, shm, s); return 0; }
     }
-    hipLaunchKernelGGL((gemv_kernel<T, NCH, PRO, EPI, NT, M, 1>), dim3(grid), dim3(256), shm, s, a);
+    gemv_launch<T, NCH, PRO, EPI, NT, M, 1>(a, grid, shm, s);
     return 0;
 }
 

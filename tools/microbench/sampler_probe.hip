@@ -250,14 +250,14 @@ int run(int kind, int te, const SamplerProbeArgs& p, hipStream_t s) {
             with_nc(p, [&](auto nc) {
                 constexpr int NC = decltype(nc)::value;
                 g_last_inst = inst_id(kind, te, NC);
-                hipLaunchKernelGGL((sample_pred_wave_kernel<T, NC>), one, blk, 0, s, st, lg, p.V, p.cb, p.cfg, nz, p.codes, p.G, out64, emb, nin, p.H, tf);
+                sample_pred_wave_launch<T, NC>(st, lg, p.V, p.cb, p.cfg, nz, p.codes, p.G, out64, emb, nin, p.H, tf, s);
             });
             break;
         case K_TALKER_WAVE:
             with_nc(p, [&](auto nc) {
                 constexpr int NC = decltype(nc)::value;
                 g_last_inst = inst_id(kind, te, NC);
-                hipLaunchKernelGGL((sample_talker_wave_kernel<T, NC>), one, blk, 0, s, st, lg, p.V, p.seen, p.G, tf);
+                sample_talker_wave_launch<T, NC>(st, lg, p.V, p.seen, p.G, tf, s);
             });
             break;
         case K_PRED_BATCH:

@@ -697,6 +697,35 @@ extern "C" int fq3_kv_adopt(fq3_ctx* dst, fq3_ctx* src, int L, void* stream) {
     return FQ3_OK;
 }
 
+// A COPY of K/V rows [0, L) of every talker layer (the cross-pool branch of fq3_kv_adopt, taken whether or not the pools differ): whole
+// blocks [0, ceil(L / 64)), dead rows included, in one launch; src keeps its blocks.
+extern "C" int fq3_kv_copy(fq3_ctx* dst, fq3_ctx* src, int L, void* stream) {
+    if (!dst || !src) return fail(FQ3_EINVAL, "null ctx");
+    if (dst == src) return fail(FQ3_EINVAL, "fq3_kv_copy: source and destination are the same context");
+    const auto &a = dst->cfg, &b = src->cfg;
+    if (a.dtype != b.dtype || a.talker.n_layers != b.talker.n_layers || a.talker.n_kv_heads != b.talker.n_kv_heads)
+        return fail(FQ3_EINVAL, "fq3_kv_copy: contexts of different shape");
+    if (L < 0 || L > src->tk.max_seq || L > (int)src->tk.blocks.size() * kKeysPerTile) return fail(FQ3_EINVAL, "fq3_kv_copy: L outside the source cache");
+    if (L > dst->tk.max_seq) {
+        char m[256];
+        snprintf(m, sizeof m, "Input is too long: prefill has %d tokens but max_seq_len=%d. Use shorter text or shorter reference audio.", L, a.max_seq_len);
+        return fail(FQ3_ETOOLONG, m);
+    }
+    const int nl = a.talker.n_layers;
+    if (2 * nl > 128) return fail(FQ3_EUNSUPPORTED, "fq3_kv_copy: more than 64 layers");
+    if (L == 0) return FQ3_OK;
+    hipStream_t s = (hipStream_t)stream;
+    if (int r = fq3_kv_ensure_(dst, L, s)) return r;
+    KvAdoptTab t{};
+    for (int l = 0; l < nl; ++l) { t.dst[2 * l] = dst->tk.k[l]; t.src[2 * l] = src->tk.k[l]; t.dst[2 * l + 1] = dst->tk.v[l]; t.src[2 * l + 1] = src->tk.v[l]; }
+    const dim3 grid(2 * nl, (L + kKeysPerTile - 1) / kKeysPerTile);
+    const int be = (int)dst->tk.pool->blk_elems;
+    if (a.dtype == FQ3_BF16) hipLaunchKernelGGL((kv_adopt_kernel<bf16_t>), grid, dim3(256), 0, s, t, dst->tk.d_table, src->tk.d_table, be);
+    else hipLaunchKernelGGL((kv_adopt_kernel<float>), grid, dim3(256), 0, s, t, dst->tk.d_table, src->tk.d_table, be);
+    LAUNCH_CHECK();
+    return FQ3_OK;
+}
+
 static int final_norm(fq3_ctx* c, bool talker, const void* x, void* y, hipStream_t s) {
     const fq3_stack_dims& d = talker ? c->cfg.talker : c->cfg.predictor;
     const void* w = talker ? c->wt.talker_final_norm : c->wt.predictor_final_norm;
@@ -764,6 +793,42 @@ extern "C" int fq3_prefill(fq3_ctx* c, const void* embeds, int L, int n_pad, voi
         g.W = c->wt.codec_head; g.N = c->cfg.talker.vocab; g.K = c->cfg.talker.hidden; g.x = hid; g.y = out_logits;
         if (int r = launch_gemv<PRO_PLAIN, EPI_STORE>(c, g, true, s)) return r;
     }
+    LAUNCH_CHECK();
+    return FQ3_OK;
+}
+
+// Continuation of a prefill: rows [start, start + n) behind K/V rows [0, start) that are already in this context's cache (unpadded).
+// Matrix-core path by default (csrc/fq3_prefill.hip: prefill_continue_t); n < 4 or prefill_mode 1 walks the new rows token by token
+// through the decode-step kernels from position start.
+extern "C" int fq3_prefill_continue(fq3_ctx* c, const void* embeds, int start, int n, void* out_logits, void* out_hidden, void* stream) {
+    NEED_BOUND(c);
+    if (!embeds || n <= 0) return fail(FQ3_EINVAL, "bad prompt");
+    if (start < 0) return fail(FQ3_EINVAL, "fq3_prefill_continue: negative start");
+    if ((long)start + n > c->cfg.max_seq_len) {
+        char b[256];
+        snprintf(b, sizeof b, "Input is too long: prefill has %ld tokens but max_seq_len=%d. Use shorter text or shorter reference audio.",
+                 (long)start + n, c->cfg.max_seq_len);
+        return fail(FQ3_ETOOLONG, b);
+    }
+    if ((int)c->tk.blocks.size() < (start + kKeysPerTile - 1) / kKeysPerTile)
+        return fail(FQ3_ESTATE, "fq3_prefill_continue: the context does not own the blocks of rows [0, start)");
+    if (int r = fq3_set_generation_state(c, 0, 0)) return r;
+    hipStream_t s = (hipStream_t)stream;
+    if (int r = fq3_kv_ensure_(c, start + n, s)) return r;
+    void* hid = out_hidden ? out_hidden : c->tmp_hidden;
+    if (c->prefill_mode != 1 && n >= 4) {
+        if (int r = fq3_prefill_continue_mfma_(c, embeds, start, n, out_logits, hid, s)) return r;
+        LAUNCH_CHECK();
+        return FQ3_OK;
+    }
+    const size_t rowb = (size_t)c->cfg.talker.hidden * c->esz;
+    for (int i = 0; i < n; ++i) {
+        StepSrc src{(const char*)embeds + rowb * i, nullptr, start + i};
+        if (int r = run_stack(c, true, src, s)) return r;
+    }
+    final_norm(c, true, c->h, hid, s);
+    if (out_logits)
+        if (int r = fq3_codec_head_launch_(c, hid, out_logits, s)) return r;
     LAUNCH_CHECK();
     return FQ3_OK;
 }

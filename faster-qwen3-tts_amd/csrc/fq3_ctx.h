@@ -111,6 +111,7 @@ int fq3_fail_(int code, const std::string& m);                 // sets the threa
 int fq3_kv_ensure_(fq3_ctx* c, int n_pos, hipStream_t s);
 int fq3_prefill_reserve_(fq3_ctx* c);
 int fq3_prefill_mfma_(fq3_ctx* c, const void* embeds, int L, int n_pad, void* out_logits, void* out_hidden, hipStream_t s);
+int fq3_prefill_continue_mfma_(fq3_ctx* c, const void* embeds, int start, int n, void* out_logits, void* out_hidden, hipStream_t s);
 int fq3_prefill_batch_mfma_(fq3_ctx* const* cs, int n, const void* const* embeds, const int* L, const int* n_pad, void* const* out_logits,
                             void* const* out_hidden, hipStream_t s);
 int fq3_codec_head_launch_(fq3_ctx* c, const void* hidden, void* out_logits, hipStream_t s);

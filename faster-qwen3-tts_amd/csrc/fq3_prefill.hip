@@ -166,6 +166,65 @@ int prefill_t(fq3_ctx* c, const void* embeds, int L, int n_pad, void* out_logits
     return 0;
 }
 
+// CUs of the current device (the key-split rule of the continuation's flash attention); asked once
+static int device_cus() {
+    static int n = 0;
+    if (n == 0) {
+        int dev = 0, v = 0;
+        if (hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && v > 0) n = v;
+        else n = 256;
+    }
+    return n;
+}
+
+// causal attention of n new rows over keys [0, start + n): the flash kernel with key splits (+ the merge launch when S > 1)
+static void flash_cont_launch(const bf16_t* qkv, const PagedKV<bf16_t>& kv, bf16_t* out, float* ws, int start, int n, int NH, int NKV,
+                              float scale, int S, hipStream_t s) {
+    hipLaunchKernelGGL(flash_prefill_cont_kernel, dim3((n + kFaQ - 1) / kFaQ, NH, S), dim3(256), 0, s, qkv, kv, out, ws, start, n, NH, NKV, scale, S);
+    if (S > 1) hipLaunchKernelGGL(flash_cont_merge_kernel, dim3((n * NH + 1) / 2), dim3(256), 0, s, (const float*)ws, out, n, NH, S);
+}
+
+// Continuation of a prefill (fq3_prefill_continue): the n NEW rows behind K/V rows [0, start) that are already in the cache.  Shaped like
+// prefill_t: everything row-wise runs over the n rows through the same choosers; norm + RoPE + K/V write take the position base and the
+// attention reads keys 0 .. start + t of the paged cache.  The key-split records of the flash kernel live in the split-K workspace
+// (pf_ws): the GEMMs that lend it run before and after the attention in stream order.
+template <typename T>
+int prefill_continue_t(fq3_ctx* c, const void* embeds, int start, int n, void* out_logits, void* out_hidden, hipStream_t s) {
+    const fq3_stack_dims& d = c->cfg.talker;
+    const int H = d.hidden, I = d.inter, NH = d.n_heads, NKV = d.n_kv_heads;
+    const int QD = NH * kHeadDim, KVD = NKV * kHeadDim, per = QD + 2 * KVD;
+    if (H % 32 || I % 32) return fq3_fail_(FQ3_EUNSUPPORTED, "MFMA prefill needs hidden and intermediate sizes that are multiples of 32");
+    if (int r = fq3_prefill_reserve_(c)) return r;
+    T *X = (T*)c->pf_x, *XN = (T*)c->pf_xn, *QKV = (T*)c->pf_qkv, *ATT = (T*)c->pf_att, *GU = (T*)c->pf_gu, *ACT = (T*)c->pf_act;
+    if (hipMemcpyAsync(X, embeds, (size_t)n * H * c->esz, hipMemcpyDeviceToDevice, s) != hipSuccess)
+        return fq3_fail_(FQ3_EHIP, "prefill: copy of the prompt embeddings failed");
+    const float scale = 1.0f / sqrtf((float)kHeadDim);
+    const bool flash = sizeof(T) == 2 && c->opt_flash_prefill;
+    const int S = flash ? flash_cont_splits(start, n, NH, device_cus(), kPrefillWsFloats) : 1;
+    for (int i = 0; i < d.n_layers; ++i) {
+        const fq3_layer_weights& w = c->tl[i];
+        rmsnorm_rows<T>((const T*)X, (const T*)w.input_norm, XN, n, H, d.rms_eps, s);
+        gemm<T>(lin<T>(c, XN, n, H, w.qkv, per, QKV), s);
+        const PagedKV<T> kv = paged_kv<T>(c, i);
+        hipLaunchKernelGGL((qk_norm_rope_kv_cont_kernel<T>), dim3((n * (NH + 2 * NKV) + 3) / 4), dim3(256), 0, s, QKV, (const T*)w.q_norm,
+                           (const T*)w.k_norm, d.rms_eps, c->wt.talker_cos, c->wt.talker_sin, c->wt.talker_rope_len, c->rope_delta,
+                           kv, start, n, NH, NKV);
+        if constexpr (sizeof(T) == 2) {
+            if (flash) flash_cont_launch((const bf16_t*)QKV, kv, (bf16_t*)ATT, (float*)c->pf_ws, start, n, NH, NKV, scale, S, s);
+        }
+        if (!flash)
+            hipLaunchKernelGGL((prefill_attn_cont_kernel<T>), dim3((n * NH + 3) / 4), dim3(256), 0, s, (const T*)QKV, kv, ATT, start, n, NH, NKV, scale);
+        { GemmArgs a = lin<T>(c, ATT, n, QD, w.o, H, X); a.res = X; a.ldr = H; gemm<T>(a, s); }
+        rmsnorm_rows<T>((const T*)X, (const T*)w.post_norm, XN, n, H, d.rms_eps, s);
+        gemm_swiglu_halves<T>(lin<T>(c, XN, n, H, w.gate_up, 2 * I, GU, 1), ACT, s);
+        { GemmArgs a = lin<T>(c, ACT, n, I, w.down, H, X); a.res = X; a.ldr = H; gemm<T>(a, s); }
+    }
+    hipLaunchKernelGGL((rmsnorm_kernel<T>), dim3(1), dim3(256), 0, s, (const T*)X + (size_t)(n - 1) * H, (const T*)c->wt.talker_final_norm,
+                       (T*)out_hidden, H, d.rms_eps);
+    if (out_logits) return fq3_codec_head_launch_(c, out_hidden, out_logits, s);
+    return 0;
+}
+
 // The same prefill for n prompts at once: everything row-wise (norms, the four GEMMs, SwiGLU) runs over the PACKED rows of all
 // prompts -- one pass over the layer's weights instead of n -- and only the sequence-specific steps run per prompt on its
 // slice of the packed rows: q/k norm + RoPE + KV write into that context's own cache, and causal attention over it.
@@ -263,4 +322,9 @@ int fq3_prefill_batch_mfma_(fq3_ctx* const* cs, int n, const void* const* embeds
 int fq3_prefill_mfma_(fq3_ctx* c, const void* embeds, int L, int n_pad, void* out_logits, void* out_hidden, hipStream_t s) {
     return c->cfg.dtype == FQ3_BF16 ? prefill_t<bf16_t>(c, embeds, L, n_pad, out_logits, out_hidden, s)
                                     : prefill_t<float>(c, embeds, L, n_pad, out_logits, out_hidden, s);
+}
+
+int fq3_prefill_continue_mfma_(fq3_ctx* c, const void* embeds, int start, int n, void* out_logits, void* out_hidden, hipStream_t s) {
+    return c->cfg.dtype == FQ3_BF16 ? prefill_continue_t<bf16_t>(c, embeds, start, n, out_logits, out_hidden, s)
+                                    : prefill_continue_t<float>(c, embeds, start, n, out_logits, out_hidden, s);
 }

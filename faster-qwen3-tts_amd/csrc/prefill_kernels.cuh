@@ -427,4 +427,219 @@ __global__ __launch_bounds__(256) void qk_norm_rope_kv_pack_kernel(T* qkv, const
     DT<T>::st(dst + lane + 64, x1);
 }
 
+// ---------------------------------------------------------------------------------------------------------------------
+// Continuation prefill (fq3_prefill_continue): rows [start, start + n) of a prompt whose K/V rows [0, start) are already in the paged
+// cache.  qkv / out hold the n NEW rows only (local row t = position start + t); no left padding.
+// ---------------------------------------------------------------------------------------------------------------------
+
+// qk_norm_rope_kv_kernel with a position base: local row t is normalised and rotated at RoPE row clamp(start + t + rope_delta), q in
+// place at local row t, K / V to cache row start + t.  Cache rows below start are not touched.
+template <typename T>
+__global__ __launch_bounds__(256) void qk_norm_rope_kv_cont_kernel(T* qkv, const T* qw, const T* kw, float eps, const float* cos_tab,
+                                                                   const float* sin_tab, int rope_len, int rope_delta, PagedKV<T> kv,
+                                                                   int start, int n, int NH, int NKV) {
+    constexpr int HD = kHeadDim;
+    const int per = NH + 2 * NKV;
+    const int w = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+    if (w >= n * per) return;
+    const int t = w / per, v = w - t * per, pos = start + t;
+    T* src = qkv + (size_t)t * per * HD + (size_t)v * HD;
+    float x0 = DT<T>::ld(src + lane), x1 = DT<T>::ld(src + lane + 64);
+    if (v < NH + NKV) {
+        const T* gw = v < NH ? qw : kw;
+        const float ss = wave_sum(fmaf(x0, x0, x1 * x1));
+        const float rs = 1.0f / sqrtf(ss / (float)HD + eps);
+        const float n0 = DT<T>::rnd(DT<T>::ld(gw + lane) * DT<T>::rnd(x0 * rs));
+        const float n1 = DT<T>::rnd(DT<T>::ld(gw + lane + 64) * DT<T>::rnd(x1 * rs));
+        int rp = pos + rope_delta;
+        rp = rp < 0 ? 0 : (rp >= rope_len ? rope_len - 1 : rp);
+        const float cs = cos_tab[(size_t)rp * 64 + lane], sn = sin_tab[(size_t)rp * 64 + lane];
+        x0 = DT<T>::rnd(DT<T>::rnd(n0 * cs) + DT<T>::rnd(-n1 * sn));
+        x1 = DT<T>::rnd(DT<T>::rnd(n1 * cs) + DT<T>::rnd(n0 * sn));
+    }
+    T* dst = v < NH ? src : (v < NH + NKV ? kv.k + paged_row(kv, v - NH, pos) : kv.v + paged_row(kv, v - NH - NKV, pos));
+    DT<T>::st(dst + lane, x0);
+    DT<T>::st(dst + lane + 64, x1);
+}
+
+// prefill_attn_kernel with a query base: one wave per (new row, q head); local row t attends to keys 0 .. start + t with the loop of
+// prefill_attn_kernel (16 lanes per key, 16 keys per trip, fp32 online softmax, one rounding at the end).
+template <typename T>
+__global__ __launch_bounds__(256) void prefill_attn_cont_kernel(const T* qkv, PagedKV<T> kv, T* out, int start, int n, int NH, int NKV,
+                                                                float scale) {
+    constexpr int HD = kHeadDim;
+    const int w = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+    if (w >= n * NH) return;
+    const int t = w / NH, h = w - t * NH, last = start + t;               // last: the row's own key
+    const int per = NH + 2 * NKV, g = h / (NH / NKV);
+    const int sub = lane >> 4, c = lane & 15;
+    T* op = out + ((size_t)t * NH + h) * HD;
+    Raw8<T> qraw;
+    ldraw<false>(qraw, qkv + (size_t)t * per * HD + (size_t)h * HD + c * 8);
+    float q[8];
+    unpack(qraw, q);
+    float m = -1e30f, l = 0.f, o[8];
+#pragma unroll
+    for (int i = 0; i < 8; ++i) o[i] = 0.f;
+    for (int k0 = 0; k0 <= last; k0 += 16) {
+        Raw8<T> kr[4], vr[4];
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            int key = k0 + i * 4 + sub;
+            key = key <= last ? key : last;
+            const size_t off = paged_row(kv, g, key) + c * 8;
+            ldraw<false>(kr[i], kv.k + off);
+            ldraw<false>(vr[i], kv.v + off);
+        }
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const bool valid = k0 + i * 4 + sub <= last;
+            float kf[8], vf[8];
+            unpack(kr[i], kf); unpack(vr[i], vf);
+            float sc = 0.f;
+#pragma unroll
+            for (int d = 0; d < 8; ++d) sc = fmaf(q[d], kf[d], sc);
+            sc += __shfl_xor(sc, 1, 64); sc += __shfl_xor(sc, 2, 64);
+            sc += __shfl_xor(sc, 4, 64); sc += __shfl_xor(sc, 8, 64);
+            sc = valid ? sc * scale : -INFINITY;
+            const float mn = fmaxf(m, sc), al = __expf(m - mn), p = __expf(sc - mn);
+            l = fmaf(l, al, p);
+#pragma unroll
+            for (int d = 0; d < 8; ++d) o[d] = fmaf(o[d], al, valid ? p * vf[d] : 0.f);
+            m = mn;
+        }
+    }
+#pragma unroll
+    for (int off = 16; off <= 32; off <<= 1) {
+        const float mo = __shfl_xor(m, off, 64), lo = __shfl_xor(l, off, 64);
+        const float M = fmaxf(m, mo), wa = __expf(m - M), wb = __expf(mo - M);
+        l = l * wa + lo * wb;
+#pragma unroll
+        for (int d = 0; d < 8; ++d) { const float oo = __shfl_xor(o[d], off, 64); o[d] = o[d] * wa + oo * wb; }
+        m = M;
+    }
+    if (sub == 0)
+#pragma unroll
+        for (int i = 0; i < 8; ++i) DT<T>::st(op + c * 8 + i, o[i] / l);
+}
+
+// Continuation flash kernel (bf16).  One workgroup = one q head x 64 NEW queries (4 waves) x one KEY SPLIT: a continuation has few
+// query blocks and many key tiles (128 new rows behind 3968 cached keys: 2 blocks x 16 heads, 64 tiles each), so the key tiles
+// [0, nt) of a query block (nt = tiles up to its last query's own key) are cut into S contiguous ranges of ceil(nt / S) tiles, one per
+// blockIdx.z.  A tile is found by its ABSOLUTE index through the block table and streamed through the LDS stage of
+// flash_prefill_kernel; flash_tile gets the absolute query position, so a tile's arithmetic is that of the whole prefill.
+// S == 1: normalise, round once, write `out`.  S > 1: each split writes its un-normalised fp32 (m, l, o[128]) per (row, head) to
+// `ws` ([split][row][head][kFcRec]) with plain stores and flash_cont_merge_kernel -- a SECOND launch; no counters, flags or spins --
+// merges them in split order and rounds once.  A split with no tile (nt < S ranges) stores (m = -1e30, l = 0, o = 0): weight 0.
+// S is fixed by the launcher per (start, n): the same call gives the same bits.
+// CONTRACT (as flash_prefill_kernel): P = 0 is multiplied by whatever the dead rows of an OWNED block hold (rows past start + n in the
+// last tile): every block a context owns must be finite -- the pool is zeroed at creation, recycled blocks hold finite bf16, and
+// fq3_kv_copy copies WHOLE blocks, dead rows included.
+constexpr int kFcRec = 2 + kHeadDim;               // floats per (split, row, head) record: m, l, o[128]
+__global__ __launch_bounds__(256) void flash_prefill_cont_kernel(const bf16_t* qkv, PagedKV<bf16_t> kv, bf16_t* out, float* ws,
+                                                                 int start, int n, int NH, int NKV, float scale, int S) {
+    constexpr int HD = kHeadDim, NW = 4, Q = 16 * NW, CPT = 16 / NW;
+    __shared__ __attribute__((aligned(16))) bf16_t Ks[kFaK * kFaKLd];            // [key][dim]
+    __shared__ __attribute__((aligned(16))) bf16_t Vt[HD * kFaVLd];              // [dim][key]
+    __shared__ __attribute__((aligned(16))) bf16_t Ps[NW][2][16 * kFaPLd];       // per wave: P high / residual, [query][key]
+    const int tid = threadIdx.x, lane = tid & 63, fr = lane & 15, fq = lane >> 4;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int h = blockIdx.y, g = h / (NH / NKV), per = NH + 2 * NKV, z = blockIdx.z;
+    const bf16_t* kc = kv.k + (size_t)g * kFaK * HD;
+    const bf16_t* vc = kv.v + (size_t)g * kFaK * HD;
+    const float sl2 = scale * 1.4426950408889634f;
+    const int skey = tid & 63, sch = tid >> 6;
+    const int q0 = (int)blockIdx.x * Q;                                   // first LOCAL row of the block (grid.x covers n)
+    const int qrow = q0 + wave * 16 + fr;
+    const int qrc = qrow < n ? qrow : n - 1;
+    bf16x8_t qf[4];
+#pragma unroll
+    for (int ks = 0; ks < 4; ++ks)
+        qf[ks] = *reinterpret_cast<const bf16x8_t*>(qkv + (size_t)qrc * per * HD + (size_t)h * HD + ks * 32 + fq * 8);
+    f32x4_t o[8];
+#pragma unroll
+    for (int d = 0; d < 8; ++d) o[d] = f32x4_t{0.f, 0.f, 0.f, 0.f};
+    float m[4], l[4];
+#pragma unroll
+    for (int r = 0; r < 4; ++r) { m[r] = -1e30f; l[r] = 0.f; }
+    const int nt = (start + min(q0 + Q, n) - 1) / kFaK + 1;               // key tiles [0, nt): up to the block's last query's own key
+    const int tps = (nt + S - 1) / S;
+    const int t_lo = z * tps, t_end = min(nt, t_lo + tps);                // this split: tiles [t_lo, t_end), maybe none
+    u32x4 kst[CPT], vst[CPT];
+    auto issue = [&](int tile) {
+        const size_t off = (size_t)kv.table[tile] * kv.blk_stride + (size_t)skey * HD;       // tile < nt: a block this context owns
+#pragma unroll
+        for (int j = 0; j < CPT; ++j) {
+            kst[j] = *reinterpret_cast<const u32x4*>(kc + off + (sch + NW * j) * 8);
+            vst[j] = *reinterpret_cast<const u32x4*>(vc + off + (sch + NW * j) * 8);
+        }
+    };
+    if (t_lo < t_end) issue(t_lo);
+    for (int tile = t_lo; tile < t_end; ++tile) {
+        __syncthreads();                                                  // everyone is done reading the previous tile
+#pragma unroll
+        for (int j = 0; j < CPT; ++j) {
+            *reinterpret_cast<u32x4*>(&Ks[skey * kFaKLd + (sch + NW * j) * 8]) = kst[j];
+            // transposed store, two keys per 32-bit write (see flash_prefill_kernel)
+#pragma unroll
+            for (int w = 0; w < 4; ++w) {
+                const uint32_t mine = vst[j][w];
+                const uint32_t other = (uint32_t)__builtin_amdgcn_mov_dpp((int)mine, 0xB1, 0xF, 0xF, true);
+                const bool odd = skey & 1;
+                const uint32_t word = odd ? ((other >> 16) | (mine & 0xFFFF0000u)) : ((mine & 0xFFFFu) | (other << 16));
+                const int dim = (sch + NW * j) * 8 + 2 * w + (odd ? 1 : 0);
+                *reinterpret_cast<uint32_t*>(&Vt[dim * kFaVLd + (skey & ~1)]) = word;
+            }
+        }
+        __syncthreads();
+        if (tile + 1 < t_end) issue(tile + 1);                            // next tile's loads fly under the MFMAs
+        flash_tile(Ks, Vt, Ps[wave][0], Ps[wave][1], qf, o, m, l, tile, start + q0, wave, fr, fq, 0, sl2);
+    }
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+        const int qi = q0 + wave * 16 + fq * 4 + r;                       // local row
+        if (qi >= n) continue;
+        if (S == 1) {
+            const float inv = l[r] > 0.f ? 1.0f / l[r] : 0.f;
+#pragma unroll
+            for (int d = 0; d < 8; ++d) out[((size_t)qi * NH + h) * HD + d * 16 + fr] = f_to_bf16(o[d][r] * inv);
+        } else {
+            float* rec = ws + (((size_t)z * n + qi) * NH + h) * kFcRec;
+            if (fr == 0) { rec[0] = m[r]; rec[1] = l[r]; }
+#pragma unroll
+            for (int d = 0; d < 8; ++d) rec[2 + d * 16 + fr] = o[d][r];
+        }
+    }
+}
+
+// merge of the key splits of flash_prefill_cont_kernel: one thread per (row, head, dim); M = max of the splits' m (base-2 units),
+// then l and o accumulated in split order with weights 2^(m_s - M), one division, one rounding to bf16.
+__global__ __launch_bounds__(256) void flash_cont_merge_kernel(const float* ws, bf16_t* out, int n, int NH, int S) {
+    const int i = blockIdx.x * 2 + (threadIdx.x >> 7), d = threadIdx.x & 127;          // i = row * NH + head
+    if (i >= n * NH) return;
+    const size_t split = (size_t)n * NH * kFcRec;
+    const float* rec = ws + (size_t)i * kFcRec;
+    float M = -1e30f;
+    for (int s = 0; s < S; ++s) M = fmaxf(M, rec[s * split]);
+    float l = 0.f, o = 0.f;
+    for (int s = 0; s < S; ++s) {
+        const float w = exp2f(rec[s * split] - M);
+        l = fmaf(rec[s * split + 1], w, l);
+        o = fmaf(rec[s * split + 2 + d], w, o);
+    }
+    out[(size_t)i * kHeadDim + d] = f_to_bf16(l > 0.f ? o / l : 0.f);
+}
+
+// key splits of a continuation: blocks x heads x S about half to one times the CU count (whole multiples of the blocks x heads grid,
+// rounded down), at least kFcMinTiles key tiles per split, at most kFcMaxSplit, and the records must fit the workspace.
+constexpr int kFcMinTiles = 4, kFcMaxSplit = 16;
+inline int flash_cont_splits(int start, int n, int NH, int n_cu, long ws_floats) {
+    const int nqb = (n + kFaQ - 1) / kFaQ, nt = (start + n + kFaK - 1) / kFaK;
+    int S = n_cu / (nqb * NH);
+    S = S < nt / kFcMinTiles ? S : nt / kFcMinTiles;
+    S = S < kFcMaxSplit ? S : kFcMaxSplit;
+    while (S > 1 && (long)S * n * NH * kFcRec > ws_floats) --S;
+    return S < 1 ? 1 : S;
+}
+
 }  // namespace fq3

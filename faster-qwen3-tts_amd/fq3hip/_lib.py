@@ -112,9 +112,11 @@ SIGNATURES = {
     "fq3_kv_import": (C.c_int, [vp, C.c_int, vp, vp, C.c_int, vp]),
     "fq3_kv_export": (C.c_int, [vp, C.c_int, vp, vp, C.c_int, vp]),
     "fq3_kv_adopt": (C.c_int, [vp, vp, C.c_int, vp]),
+    "fq3_kv_copy": (C.c_int, [vp, vp, C.c_int, vp]),
     "fq3_set_generation_state": (C.c_int, [vp, C.c_int, C.c_int]),
     "fq3_talker_step": (C.c_int, [vp, vp, C.c_int, vp, vp]),
     "fq3_prefill": (C.c_int, [vp, vp, C.c_int, C.c_int, vp, vp, vp]),
+    "fq3_prefill_continue": (C.c_int, [vp, vp, C.c_int, C.c_int, vp, vp, vp]),
     "fq3_prefill_reserve": (C.c_int, [vp]),
     "fq3_prefill_batch": (C.c_int, [C.POINTER(vp), C.c_int, C.POINTER(vp), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(vp),
                                     C.POINTER(vp), vp]),

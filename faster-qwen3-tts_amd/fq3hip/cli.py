@@ -47,6 +47,8 @@ def load_model(args):
                                                max_seq_len=2048)
     if getattr(args, "voice_cache", None):
         model.set_voice_ref_cache(args.voice_cache)
+    if int(getattr(args, "prefix_cache_rows", 0) or 0) > 0:
+        model.enable_prefix_cache(int(args.prefix_cache_rows))
     return model
 
 
@@ -261,12 +263,19 @@ def build_parser():
         sp.add_argument("--xvec-only", action="store_true")
         sp.add_argument("--non-streaming-mode", action="store_true", default=None)
 
+    def prefix_cache_flag(sp):
+        sp.add_argument("--prefix-cache-rows", type=int, default=0, metavar="N",
+                        help="keep the talker K/V rows of instruct turns on the device, up to N rows, and prefill only the rest of a "
+                             "prompt whose instruct is cached (default 0: off)")
+
     c = sub.add_parser("clone", help="voice cloning from reference audio")
     common(c); clone_refs(c); c.set_defaults(mode="clone", func=cmd_once)
     c = sub.add_parser("custom", help="CustomVoice model: predefined speaker")
     common(c, text_stdin=True); c.add_argument("--speaker"); c.add_argument("--instruct"); c.set_defaults(mode="custom", func=cmd_once)
+    prefix_cache_flag(c)
     c = sub.add_parser("design", help="VoiceDesign model: voice from an instruction")
     common(c, text_stdin=True); c.add_argument("--instruct"); c.set_defaults(mode="design", func=cmd_once)
+    prefix_cache_flag(c)
     s = sub.add_parser("serve", help="read one text per stdin line, write out_NNNN.wav")
     common(s, output=False); clone_refs(s)
     s.add_argument("--mode", default="clone", choices=["clone", "custom", "design"])

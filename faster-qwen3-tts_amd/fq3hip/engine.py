@@ -125,6 +125,7 @@ class Fq3Engine:
                 self._bind(weights)
         self.weights = weights
         self._pred_sampling = dict(do_sample=True, top_k=50, top_p=1.0, temperature=0.9)
+        self.prefix_cache = None      # a fq3hip.prefix_cache.PrefixCache once FasterQwen3TTS.enable_prefix_cache has set one
 
     @classmethod
     def sampler_only(cls, device, dtype: torch.dtype) -> "Fq3Engine":
@@ -264,14 +265,38 @@ class Fq3Engine:
         L.check(self.lib.fq3_talker_step(self.ctx, embeds.data_ptr(), int(position), out.data_ptr(), self._stream()))
         return out
 
-    def prefill(self, embeds: torch.Tensor, n_pad: int = 0):
-        """embeds [L, H] -> (logits [V], hidden [H])."""
+    def prefill(self, embeds: torch.Tensor, n_pad: int = 0, want_logits: bool = True):
+        """embeds [L, H] -> (logits [V], hidden [H]); ``want_logits=False`` skips the codec head (logits is None)."""
         Lp, H = embeds.shape
         self._chk(embeds, Lp * H, "prefill embeds")
-        logits, hid = self.new(self.cfg.talker.vocab_size), self.new(H)
-        L.check(self.lib.fq3_prefill(self.ctx, embeds.data_ptr(), int(Lp), int(n_pad), logits.data_ptr(),
+        logits, hid = self.new(self.cfg.talker.vocab_size) if want_logits else None, self.new(H)
+        L.check(self.lib.fq3_prefill(self.ctx, embeds.data_ptr(), int(Lp), int(n_pad), _ptr(logits),
                                      hid.data_ptr(), self._stream()))
         return logits, hid
+
+    def prefill_continue(self, embeds: torch.Tensor, start: int):
+        """The new rows ``embeds`` [n, H] of a prompt whose rows ``[0, start)`` are already in this context's cache
+        (``fq3_prefill_continue``) -> (logits [V], hidden [H]) of the last new row."""
+        n, H = embeds.shape
+        self._chk(embeds, n * H, "prefill_continue embeds")
+        logits, hid = self.new(self.cfg.talker.vocab_size), self.new(H)
+        L.check(self.lib.fq3_prefill_continue(self.ctx, embeds.data_ptr(), int(start), int(n), logits.data_ptr(),
+                                              hid.data_ptr(), self._stream()))
+        return logits, hid
+
+    def kv_copy(self, src: "Fq3Engine", Lk: int):
+        """Receive a copy of the first ``Lk`` KV rows of every talker layer of ``src`` (``fq3_kv_copy``: whole 64-key blocks, one
+        launch); ``src`` keeps its blocks.  ``Fq3Error(FQ3_ENOMEM)`` when this context's pool is short (nothing is taken then)."""
+        L.check(self.lib.fq3_kv_copy(self.ctx, src.ctx, int(Lk), self._stream()))
+
+    def kv_pool(self, n_blocks: int) -> Fq3KvPool:
+        """A KV pool of ``n_blocks`` 64-key blocks of this engine's shape, device and dtype."""
+        return Fq3KvPool(self.cfg, int(n_blocks), device=str(self.device), dtype=self.dtype)
+
+    def spawn_pooled(self, pool: Fq3KvPool, max_frames: int = 8) -> "Fq3Engine":
+        """Another context on this engine's weights whose talker K/V blocks come from ``pool`` (it owns none until it is given some)."""
+        return Fq3Engine(self.cfg, self.weights, device=str(self.device), dtype=self.dtype, max_seq_len=self.max_seq_len,
+                         max_frames=max_frames, share=self, pool=pool)
 
     def prefill_reserve(self):
         """Allocate this context's prefill workspace now (``fq3_prefill_reserve``) instead of inside its first prefill."""

@@ -56,7 +56,13 @@ def _prefill_first_token(eng, talker_input_embeds, attention_mask, config, min_n
     V = config.vocab_size
     n_pad = _n_pad_of(attention_mask)
     x = talker_input_embeds[0].to(device=dev, dtype=dt).contiguous()
-    logits, hidden = eng.prefill(x, n_pad=n_pad)
+    cache = getattr(eng, "prefix_cache", None)
+    if cache is not None:
+        # prefix KV cache (fq3hip/prefix_cache.py): the instruct rows the prompt builder noted are reused or saved; it falls back to
+        # the plain prefill by itself (no note, padding, a prefix too short or too long)
+        logits, hidden = cache.prefill(eng, x, n_pad, getattr(talker_input_embeds, "fq3_prefix", None))
+    else:
+        logits, hidden = eng.prefill(x, n_pad=n_pad)
     first_noise = torch.empty(V, dtype=dt, device=dev).exponential_(1) if do_sample else None
     token = eng.sample(logits, temperature=temperature, top_k=top_k, top_p=top_p, do_sample=do_sample,
                        sup_lo=max(0, V - 1024), sup_hi=V, keep_id=eos_id, suppress_eos=min_new_tokens > 0,

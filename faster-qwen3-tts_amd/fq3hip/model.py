@@ -518,6 +518,26 @@ class FasterQwen3TTS:
     def _warmup(self, prefill_len: int) -> None:
         self.warmup(prefill_len=prefill_len)
 
+    # ---- prefix KV cache (opt-in) -----------------------------------------------------------------------------------
+    def enable_prefix_cache(self, capacity_rows: int, min_rows: Optional[int] = None):
+        """Keep the talker K/V rows of instruct turns (voice design, custom voice with an instruct) on the device, up to
+        ``capacity_rows`` rows, and prefill only the rest of a prompt whose instruct is cached (``fq3hip/prefix_cache.py``).  Applies
+        to the single-stream entry points (``generate_*``, ``generate_*_streaming``, ``stream_*``); the ``*_batch`` entry points and the
+        batch scheduler run on engines of their own, which never carry a cache.  Returns the :class:`PrefixCache`."""
+        from .prefix_cache import PrefixCache
+        self.disable_prefix_cache()
+        eng = self.talker_graph.engine
+        eng.prefix_cache = PrefixCache(eng, capacity_rows, min_rows)
+        return eng.prefix_cache
+
+    def disable_prefix_cache(self) -> None:
+        eng = self.talker_graph.engine
+        cache = getattr(eng, "prefix_cache", None)
+        eng.prefix_cache = None
+        if cache is not None:
+            torch.cuda.current_stream(eng.device).synchronize()      # the last request's copies out of the entries have run
+            cache.close()
+
     def generate(self, text: str, language: str = "English", max_new_tokens: int = 2048, temperature: float = 0.9,
                  top_k: int = 50, do_sample: bool = True, repetition_penalty: float = 1.05) -> Tuple[list, int]:
         raise NotImplementedError("Default voice generation not yet implemented. "
@@ -752,6 +772,12 @@ class FasterQwen3TTS:
         tth = pad.squeeze(0).expand(len(seqs), Tt, H).clone()
         for b, t in enumerate(trailing):
             tth[b, : t.shape[0]] = t
+        if len(seqs) == 1 and instruct_ids is not None and instruct_ids[0] is not None:
+            # a single prompt is not padded: its instruct rows come first and depend on the instruct ids alone (fq3hip/prefix_cache.py)
+            from .prompt import host_ids
+            key = tuple(host_ids(instruct_ids[0]))
+            if key:
+                embeds.fq3_prefix = (len(key), key)
         return embeds, mask, tth, pad
 
     def _after_prepare(self, m, tie):

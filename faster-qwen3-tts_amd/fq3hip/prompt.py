@@ -57,8 +57,18 @@ def build_talker_inputs_hip(m, input_id: torch.Tensor, ref_id: Optional[torch.Te
     trail: List[Tuple[int, int, int]] = []
 
     # optional instruct turn: text only (model.py:601-606)
+    # With a prefix cache on the engine (fq3hip/prefix_cache.py) the instruct ids are projected by a call of their own: the K/V rows a
+    # later request reuses then come from the same launches on the same ids, whatever else that request's prompt holds (the batched MLP
+    # below may pick another tile shape for another row count).
+    instruct_key, instruct_rows = None, None
     if instruct_id is not None:
-        rows += [(t, NONE, 0) for t in pool.add(host_ids(instruct_id))]
+        ins = host_ids(instruct_id)
+        instruct_key = tuple(ins)
+        if getattr(eng, "prefix_cache", None) is not None and ins:
+            instruct_rows = eng.text_project(torch.tensor(ins, dtype=torch.long, device=eng.device))
+            rows += [(-2 - j, NONE, 0) for j in range(len(ins))]          # resolved below: rows behind the pooled ones
+        else:
+            rows += [(t, NONE, 0) for t in pool.add(ins)]
 
     # speaker embedding of the codec prefix (model.py:615-631)
     spk_vec, spk_kind = None, None
@@ -126,6 +136,10 @@ def build_talker_inputs_hip(m, input_id: torch.Tensor, ref_id: Optional[torch.Te
 
     dev = eng.device
     text_rows = eng.text_project(torch.tensor(pool.ids, dtype=torch.long, device=dev))
+    if instruct_rows is not None:
+        base = len(pool.ids)
+        rows = [(base + (-2 - t), k, a) if t <= -2 else (t, k, a) for t, k, a in rows]
+        text_rows = torch.cat((text_rows, instruct_rows), 0)
     prog = torch.tensor(rows + trail + [(i_pad, NONE, 0)], dtype=torch.int32, device=dev)
     out = eng.prompt_rows(text_rows, prog, ref_codes=ref_codes, spk_embed=spk_vec)
     L, Tt = len(rows), len(trail)
@@ -137,4 +151,7 @@ def build_talker_inputs_hip(m, input_id: torch.Tensor, ref_id: Optional[torch.Te
     # carries the tensor's version counter: an in-place edit of the mask afterwards voids it (generate._n_pad_of counts again)
     # (a tensor created under torch.inference_mode() has no version counter: its note is taken as it is)
     tam.fq3_n_pad = (0, None if tam.is_inference() else tam._version)
+    # the instruct rows come first and depend on the instruct ids alone: noted for the prefix KV cache (rows, key)
+    if instruct_key:
+        tie.fq3_prefix = (len(instruct_key), instruct_key)
     return tie, tam, tth, tpe

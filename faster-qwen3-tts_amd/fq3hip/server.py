@@ -241,9 +241,10 @@ class BatchWorker:
 
 
 def create_app(model, voices: Dict[str, dict], default_voice: Optional[str] = None, scheduler: str = "lock", lanes: int = 8,
-               chunk_size: int = 12, worker=None):
+               chunk_size: int = 12, worker=None, prefix_cache_rows: int = 0):
     """``worker``: a ready ``BatchWorker`` (or a stand-in with ``submit`` / ``submit_text``) instead of the one ``scheduler="batch"``
-    would start."""
+    would start.  ``prefix_cache_rows`` > 0: the model's prefix KV cache (``FasterQwen3TTS.enable_prefix_cache``) with that many rows;
+    it serves the ``lock`` scheduler (the batch scheduler decodes on engines of its own, which carry no cache)."""
     from fastapi import FastAPI, HTTPException
     from fastapi.responses import Response, StreamingResponse
 
@@ -251,6 +252,12 @@ def create_app(model, voices: Dict[str, dict], default_voice: Optional[str] = No
     lock = threading.Lock()
     if worker is None and scheduler == "batch":
         worker = BatchWorker(model, lanes, chunk_size)
+    prefix_cache = None
+    if int(prefix_cache_rows or 0) > 0:
+        if worker is not None:
+            logger.info("--prefix-cache-rows does nothing with --scheduler batch (it serves --scheduler lock)")
+        else:
+            prefix_cache = model.enable_prefix_cache(int(prefix_cache_rows))
     sessions: Dict[str, dict] = {}
     sessions_lock = threading.Lock()
     sample_rate = int(getattr(model, "sample_rate", 24000))
@@ -298,11 +305,14 @@ def create_app(model, voices: Dict[str, dict], default_voice: Optional[str] = No
         q: "queue.Queue" = queue.Queue()
         done = object()
 
+        # a voice entry's optional "instruct" (an instruct turn ahead of the prompt: what the prefix cache reuses); lock scheduler only
+        instruct_kw = {"instruct": cfg["instruct"]} if cfg.get("instruct") else {}
+
         def producer():
             try:
                 with lock, (contextlib.nullcontext() if spec is None else model.audio_output(spec.sample_rate, spec.encoding, spec.speed)):
                     for chunk, _sr, _t in model.generate_voice_clone_streaming(chunk_size=cfg.get("chunk_size", 12),
-                                                                               non_streaming_mode=False, **clone_kwargs(cfg, text)):
+                                                                               non_streaming_mode=False, **clone_kwargs(cfg, text), **instruct_kw):
                         q.put(chunk)
             except Exception as exc:
                 q.put(exc)
@@ -430,7 +440,10 @@ def create_app(model, voices: Dict[str, dict], default_voice: Optional[str] = No
 
     @app.get("/health")
     async def health():
-        return {"status": "ok", "model_loaded": model is not None, "scheduler": scheduler, "lanes": lanes if worker else 1}
+        out = {"status": "ok", "model_loaded": model is not None, "scheduler": scheduler, "lanes": lanes if worker else 1}
+        if prefix_cache is not None:
+            out["prefix_cache"] = prefix_cache.stats()
+        return out
 
     @app.post("/v1/audio/speech")
     async def create_speech(req: SpeechRequest):
@@ -460,7 +473,7 @@ def create_app(model, voices: Dict[str, dict], default_voice: Optional[str] = No
     return app
 
 
-def main(argv=None):
+def build_parser():
     p = argparse.ArgumentParser(description="OpenAI-compatible TTS server over the MI355X HIP path")
     p.add_argument("--model", default=os.environ.get("QWEN_TTS_MODEL", "Qwen/Qwen3-TTS-12Hz-1.7B-Base"))
     p.add_argument("--voices", default=os.environ.get("QWEN_TTS_VOICES"), metavar="FILE")
@@ -475,7 +488,14 @@ def main(argv=None):
     p.add_argument("--chunk-size", type=int, default=12, help="frames per streamed chunk (batch scheduler: server-wide)")
     p.add_argument("--voice-cache", help="directory of precomputed voice prompts serving ref_audio entries")
     p.add_argument("--synthetic", choices=["0.6b", "1.7b"])
-    args = p.parse_args(argv)
+    p.add_argument("--prefix-cache-rows", type=int, default=0, metavar="N",
+                   help="keep the talker K/V rows of instruct turns on the device, up to N rows (default 0: off); takes effect with "
+                        "--scheduler lock")
+    return p
+
+
+def main(argv=None):
+    args = build_parser().parse_args(argv)
     if args.voices:
         with open(args.voices) as f:
             voices = json.load(f)
@@ -492,7 +512,8 @@ def main(argv=None):
                                        voice_cache=args.voice_cache))
     import uvicorn
     logging.basicConfig(level=logging.INFO)
-    uvicorn.run(create_app(model, voices, default_voice, args.scheduler, args.lanes, args.chunk_size), host=args.host, port=args.port)
+    uvicorn.run(create_app(model, voices, default_voice, args.scheduler, args.lanes, args.chunk_size,
+                           prefix_cache_rows=args.prefix_cache_rows), host=args.host, port=args.port)
 
 
 if __name__ == "__main__":

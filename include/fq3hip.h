@@ -162,6 +162,10 @@ int fq3_kv_export(fq3_ctx* ctx, int layer, void* k, void* v, int L, void* stream
  * keeps decoding, and hand the result to whichever lane frees up (fq3hip/batching.py).  FQ3_ETOOLONG if L > dst's max_seq_len. */
 int fq3_kv_adopt(fq3_ctx* dst, fq3_ctx* src, int L, void* stream);
 
+/* dst receives a COPY of K/V rows [0, L) of every talker layer (whole 64-key blocks, one launch); src keeps its blocks, whether
+ * or not the two contexts share a pool.  dst takes the blocks it needs (FQ3_ENOMEM and nothing taken when its pool is short). */
+int fq3_kv_copy(fq3_ctx* dst, fq3_ctx* src, int L, void* stream);
+
 /* TalkerGraph.set_generation_state (talker_graph.py:172-196): left-pad count of the prompt mask and
  * the rope delta; replaces the 2048-row additive mask table with two integers. */
 int fq3_set_generation_state(fq3_ctx* ctx, int n_pad, int rope_delta);
@@ -174,6 +178,14 @@ int fq3_talker_step(fq3_ctx* ctx, const void* embeds, int position, void* out_hi
  * [0,L); outputs last-position logits T[V] and post-norm hidden T[H].  n_pad = left padding. */
 int fq3_prefill(fq3_ctx* ctx, const void* embeds, int L, int n_pad, void* out_logits, void* out_hidden,
                 void* stream);
+/* Rows [start, start + n) of a prompt whose rows [0, start) are already in this context's cache (written by fq3_prefill,
+ * fq3_prefill_continue, fq3_kv_copy, fq3_kv_adopt or fq3_kv_import, without left padding): embeds T[n, H] are the NEW rows only;
+ * K/V of the new rows go to slots [start, start + n); row start + t attends to keys 0 .. start + t.  Outputs as fq3_prefill
+ * (last new row).  Sets the generation state to (n_pad 0, rope_delta 0) like fq3_prefill does for an unpadded prompt.
+ * start == 0 is a whole prefill through the continuation kernels.  FQ3_ESTATE when the context owns fewer than ceil(start / 64)
+ * blocks, FQ3_ETOOLONG when start + n > max_seq_len.  bf16: the attention splits the keys of a query block over several
+ * workgroups and merges them in a second launch, in a fixed order: the same call gives the same bits. */
+int fq3_prefill_continue(fq3_ctx* ctx, const void* embeds, int start, int n, void* out_logits, void* out_hidden, void* stream);
 /* The same prefill for n prompts with ONE pass over the weights: row-wise work (norms, GEMMs, SwiGLU) on the packed rows of
  * all prompts, q/k norm + RoPE + KV write and causal attention per prompt into ctxs[q]'s own cache.  ctxs must share one
  * weight table; workspaces are ctxs[0]'s (sum of L <= its max_seq_len) -- otherwise this is n fq3_prefill calls.  No

@@ -264,6 +264,7 @@ extern "C" int fq3_set_option(fq3_ctx* c, const char* key, int value) {
     else if (k == "prefill_mode") c->prefill_mode = value;     // 0 matrix-core prefill, 1 token walk
     else if (k == "flash_prefill") c->opt_flash_prefill = value;   // bf16 prefill attention on MFMA (default 1)
     else if (k == "flash_small") c->opt_flash_small = value;   // <= 256-row prompts: resident key tiles + packed sequences in one launch (default 1; bit-identical to 0)
+    else if (k == "cont_pack") c->opt_cont_pack = value;       // fq3_prefill_continue_batch: the pack's attention in one launch (default 1; 0 = per-prompt launches)
     else if (k == "swiglu_tile") c->opt_swiglu_tile = value;   // many-row prefills: SwiGLU in the ring tile's epilogue over the interleaved gate | up copy (default 1; bit-identical)
     else if (k == "packed_weights") c->opt_packed = value;     // weight-stationary GEMMs on the fragment-major weight copies (default 1; bit-identical)
     else if (k == "skinny_gemm") c->opt_no_skinny = !value;    // weight-stationary short-prompt prefill GEMMs (default 1)
@@ -881,6 +882,66 @@ extern "C" int fq3_prefill_batch(fq3_ctx* const* ctxs, int n, const void* const*
             }
     }
     if (int r = fq3_prefill_batch_mfma_(ctxs, n, embeds, L, n_pad, out_logits, out_hidden, (hipStream_t)stream)) return r;
+    LAUNCH_CHECK();
+    return FQ3_OK;
+}
+
+// fq3_prefill_continue for n prompts with one pass over the weights (csrc/fq3_prefill.hip: prefill_continue_batch_t).  Everything is
+// checked, and every block taken, before anything is queued: an error leaves every context with the blocks it had.
+extern "C" int fq3_prefill_continue_batch(fq3_ctx* const* ctxs, int n, const void* const* embeds, const int* start, const int* cnt,
+                                          void* const* out_logits, void* const* out_hidden, void* stream) {
+    if (!ctxs || !embeds || !start || !cnt || !out_hidden || n < 1 || n > 64) return fail(FQ3_EINVAL, "fq3_prefill_continue_batch: bad argument");
+    long total = 0;
+    bool walk = false;
+    for (int q = 0; q < n; ++q) {
+        fq3_ctx* c = ctxs[q];
+        NEED_BOUND(c);
+        if (!embeds[q] || !out_hidden[q] || cnt[q] < 1) return fail(FQ3_EINVAL, "fq3_prefill_continue_batch: bad prompt");
+        if (start[q] < 0) return fail(FQ3_EINVAL, "fq3_prefill_continue_batch: negative start");
+        const fq3_ctx* c0 = ctxs[0];
+        if (c->cfg.dtype != c0->cfg.dtype || c->wt.codec_head != c0->wt.codec_head || c->tl.size() != c0->tl.size() || c->tl.empty() ||
+            c->tl[0].qkv != c0->tl[0].qkv)
+            return fail(FQ3_EINVAL, "fq3_prefill_continue_batch: the contexts do not share one weight table and dtype");
+        for (int p = 0; p < q; ++p) if (ctxs[p] == c) return fail(FQ3_EINVAL, "fq3_prefill_continue_batch: a context appears twice");
+        walk = walk || c->prefill_mode == 1;
+        total += cnt[q];
+    }
+    for (int q = 0; q < n; ++q)
+        if ((long)start[q] + cnt[q] > ctxs[q]->cfg.max_seq_len) {
+            char b[256];
+            snprintf(b, sizeof b, "Input is too long: prefill has %ld tokens but max_seq_len=%d. Use shorter text or shorter reference audio.",
+                     (long)start[q] + cnt[q], ctxs[q]->cfg.max_seq_len);
+            return fail(FQ3_ETOOLONG, b);
+        }
+    if (total > ctxs[0]->cfg.max_seq_len) {
+        char b[256];
+        snprintf(b, sizeof b, "Input is too long: the pack has %ld new rows but max_seq_len=%d. Use shorter text or shorter reference audio.",
+                 total, ctxs[0]->cfg.max_seq_len);
+        return fail(FQ3_ETOOLONG, b);
+    }
+    for (int q = 0; q < n; ++q)
+        if ((int)ctxs[q]->tk.blocks.size() < (start[q] + kKeysPerTile - 1) / kKeysPerTile)
+            return fail(FQ3_ESTATE, "fq3_prefill_continue_batch: a context does not own the blocks of rows [0, start)");
+    hipStream_t s = (hipStream_t)stream;
+    {   // the blocks of every prompt, all or nothing: a short pool leaves every context as it was
+        std::vector<int> had(n);
+        for (int q = 0; q < n; ++q) had[q] = (int)ctxs[q]->tk.blocks.size();
+        for (int q = 0; q < n; ++q)
+            if (int r = fq3_kv_ensure_(ctxs[q], start[q] + cnt[q], s)) {
+                const std::string m = g_err;
+                for (int p = 0; p < q; ++p) (void)fq3_kv_release(ctxs[p], had[p] * kKeysPerTile);
+                g_err = m;
+                return r;
+            }
+    }
+    if (walk) {                                          // the token walk is a single-prompt path: the n single calls
+        for (int q = 0; q < n; ++q)
+            if (int r = fq3_prefill_continue(ctxs[q], embeds[q], start[q], cnt[q], out_logits ? out_logits[q] : nullptr, out_hidden[q], stream)) return r;
+        return FQ3_OK;
+    }
+    for (int q = 0; q < n; ++q)
+        if (int r = fq3_set_generation_state(ctxs[q], 0, 0)) return r;
+    if (int r = fq3_prefill_continue_batch_mfma_(ctxs, n, embeds, start, cnt, out_logits, out_hidden, s)) return r;
     LAUNCH_CHECK();
     return FQ3_OK;
 }

@@ -66,6 +66,7 @@ struct fq3_ctx {
     int opt_rmax = 2;             // GEMV rows-per-wave cap
     int opt_flash_prefill = 1;    // bf16 prefill attention on the matrix cores (0: the per-row wave kernel)
     int opt_flash_small = 1;      // prompts of <= 256 rows: every key tile resident in LDS, the sequences of a packed prefill in one launch (0: the streamed-tile kernel, per prompt)
+    int opt_cont_pack = 1;        // fq3_prefill_continue_batch: norm + RoPE + K/V write and flash attention of the whole pack in one launch each (0: per prompt)
     int opt_swiglu_tile = 1;      // many-row prefills: gate | up on the ring tile over the 16-row-interleaved copy with SwiGLU in the epilogue (round 6; bit-identical); 0: GEMM + silu_mul
     int opt_packed = 1;           // weight-stationary GEMMs read the fragment-major copies of the layer matrices (round 6; bit-identical); 0: the row-major matrices
     std::vector<std::pair<const void*, int>> packed_refs;      // (matrix, kind) references this context holds in the registry
@@ -112,6 +113,8 @@ int fq3_kv_ensure_(fq3_ctx* c, int n_pos, hipStream_t s);
 int fq3_prefill_reserve_(fq3_ctx* c);
 int fq3_prefill_mfma_(fq3_ctx* c, const void* embeds, int L, int n_pad, void* out_logits, void* out_hidden, hipStream_t s);
 int fq3_prefill_continue_mfma_(fq3_ctx* c, const void* embeds, int start, int n, void* out_logits, void* out_hidden, hipStream_t s);
+int fq3_prefill_continue_batch_mfma_(fq3_ctx* const* cs, int n, const void* const* embeds, const int* start, const int* cnt,
+                                     void* const* out_logits, void* const* out_hidden, hipStream_t s);
 int fq3_prefill_batch_mfma_(fq3_ctx* const* cs, int n, const void* const* embeds, const int* L, const int* n_pad, void* const* out_logits,
                             void* const* out_hidden, hipStream_t s);
 int fq3_codec_head_launch_(fq3_ctx* c, const void* hidden, void* out_logits, hipStream_t s);

@@ -290,6 +290,88 @@ int prefill_batch_t(fq3_ctx* const* cs, int n, const void* const* embeds, const 
     return 0;
 }
 
+// prefill_continue_t for n prompts at once (fq3_prefill_continue_batch): the packed NEW rows of all prompts go through the norms, the
+// four GEMMs and SwiGLU in one pass over the weights (workspaces of cs[0], as prefill_batch_t); norm + RoPE + K/V write take each
+// sequence's position base and table from a PackCont in one launch, and the attention of the whole pack is one flash launch over every
+// (sequence, query block, head, key split) plus one merge launch when some sequence splits.  fp32, flash_prefill 0 and contexts of
+// different pools run the single-prompt kernels on each prompt's slice instead.
+template <typename T>
+int prefill_continue_batch_t(fq3_ctx* const* cs, int n, const void* const* embeds, const int* start, const int* cnt, void* const* out_logits,
+                             void* const* out_hidden, hipStream_t s) {
+    fq3_ctx* c = cs[0];
+    const fq3_stack_dims& d = c->cfg.talker;
+    const int H = d.hidden, I = d.inter, NH = d.n_heads, NKV = d.n_kv_heads;
+    const int QD = NH * kHeadDim, KVD = NKV * kHeadDim, per = QD + 2 * KVD;
+    if (H % 32 || I % 32) return fq3_fail_(FQ3_EUNSUPPORTED, "MFMA prefill needs hidden and intermediate sizes that are multiples of 32");
+    if (int r = fq3_prefill_reserve_(c)) return r;
+    T *X = (T*)c->pf_x, *XN = (T*)c->pf_xn, *QKV = (T*)c->pf_qkv, *ATT = (T*)c->pf_att, *GU = (T*)c->pf_gu, *ACT = (T*)c->pf_act;
+    bool pack = sizeof(T) == 2 && c->opt_flash_prefill && c->opt_cont_pack;
+    for (int q = 0; q < n; ++q) pack = pack && cs[q]->tk.pool == c->tk.pool;
+    PackCont sq{};
+    int S[kMaxPack], nqb_max = 0;
+    flash_cont_pack_splits(start, cnt, n, NH, device_cus(), kPrefillWsFloats, S);
+    sq.n = n;
+    for (int q = 0; q < n; ++q) {
+        sq.table[q] = cs[q]->tk.d_table; sq.off[q + 1] = sq.off[q] + cnt[q]; sq.start[q] = start[q]; sq.rope_delta[q] = cs[q]->rope_delta;
+        sq.zoff[q + 1] = sq.zoff[q] + S[q];
+        sq.wsoff[q] = q == 0 ? 0 : sq.wsoff[q - 1] + (S[q - 1] > 1 ? S[q - 1] * cnt[q - 1] * NH * kFcRec : 0);
+        nqb_max = std::max(nqb_max, (cnt[q] + kFaQ - 1) / kFaQ);
+    }
+    const int Lt = sq.off[n];
+    const bool merge = sq.zoff[n] > n;
+    for (int q = 0; q < n; ++q)
+        if (hipMemcpyAsync(X + (size_t)sq.off[q] * H, embeds[q], (size_t)cnt[q] * H * c->esz, hipMemcpyDeviceToDevice, s) != hipSuccess)
+            return fq3_fail_(FQ3_EHIP, "prefill: copy of the prompt embeddings failed");
+    const float scale = 1.0f / sqrtf((float)kHeadDim);
+    for (int i = 0; i < d.n_layers; ++i) {
+        const fq3_layer_weights& w = c->tl[i];
+        rmsnorm_rows<T>((const T*)X, (const T*)w.input_norm, XN, Lt, H, d.rms_eps, s);
+        gemm<T>(lin<T>(c, XN, Lt, H, w.qkv, per, QKV), s);
+        if constexpr (sizeof(T) == 2) {
+            if (pack) {
+                const PagedKV<bf16_t> kv = paged_kv<bf16_t>(c, i);
+                hipLaunchKernelGGL((qk_norm_rope_kv_cont_pack_kernel<bf16_t>), dim3((Lt * (NH + 2 * NKV) + 3) / 4), dim3(256), 0, s, (bf16_t*)QKV,
+                                   (const bf16_t*)w.q_norm, (const bf16_t*)w.k_norm, d.rms_eps, c->wt.talker_cos, c->wt.talker_sin,
+                                   c->wt.talker_rope_len, kv, sq, NH, NKV);
+                hipLaunchKernelGGL(flash_prefill_cont_pack_kernel, dim3(nqb_max, NH, sq.zoff[n]), dim3(256), 0, s, (const bf16_t*)QKV, kv, (bf16_t*)ATT,
+                                   (float*)c->pf_ws, sq, NH, NKV, scale);
+                if (merge)
+                    hipLaunchKernelGGL(flash_cont_pack_merge_kernel, dim3((Lt * NH + 1) / 2), dim3(256), 0, s, (const float*)c->pf_ws, (bf16_t*)ATT, sq, NH);
+            }
+        }
+        for (int q = 0; q < n && !pack; ++q) {
+            fq3_ctx* cq = cs[q];
+            T* qkv = QKV + (size_t)sq.off[q] * per;
+            T* att = ATT + (size_t)sq.off[q] * QD;
+            const PagedKV<T> kv = paged_kv<T>(cq, i);
+            hipLaunchKernelGGL((qk_norm_rope_kv_cont_kernel<T>), dim3((cnt[q] * (NH + 2 * NKV) + 3) / 4), dim3(256), 0, s, qkv, (const T*)w.q_norm,
+                               (const T*)w.k_norm, d.rms_eps, c->wt.talker_cos, c->wt.talker_sin, c->wt.talker_rope_len, cq->rope_delta,
+                               kv, start[q], cnt[q], NH, NKV);
+            bool flash = false;
+            if constexpr (sizeof(T) == 2) {
+                flash = c->opt_flash_prefill != 0;
+                // the prompts take the records' workspace in turn: stream order
+                if (flash) flash_cont_launch((const bf16_t*)qkv, kv, (bf16_t*)att, (float*)c->pf_ws, start[q], cnt[q], NH, NKV, scale,
+                                             flash_cont_splits(start[q], cnt[q], NH, device_cus(), kPrefillWsFloats), s);
+            }
+            if (!flash)
+                hipLaunchKernelGGL((prefill_attn_cont_kernel<T>), dim3((cnt[q] * NH + 3) / 4), dim3(256), 0, s, (const T*)qkv, kv, att, start[q], cnt[q],
+                                   NH, NKV, scale);
+        }
+        { GemmArgs a = lin<T>(c, ATT, Lt, QD, w.o, H, X); a.res = X; a.ldr = H; gemm<T>(a, s); }
+        rmsnorm_rows<T>((const T*)X, (const T*)w.post_norm, XN, Lt, H, d.rms_eps, s);
+        gemm_swiglu_halves<T>(lin<T>(c, XN, Lt, H, w.gate_up, 2 * I, GU, 1), ACT, s);
+        { GemmArgs a = lin<T>(c, ACT, Lt, I, w.down, H, X); a.res = X; a.ldr = H; gemm<T>(a, s); }
+    }
+    for (int q = 0; q < n; ++q) {
+        hipLaunchKernelGGL((rmsnorm_kernel<T>), dim3(1), dim3(256), 0, s, (const T*)X + (size_t)(sq.off[q + 1] - 1) * H, (const T*)c->wt.talker_final_norm,
+                           (T*)out_hidden[q], H, d.rms_eps);
+        if (out_logits && out_logits[q])
+            if (int r = fq3_codec_head_launch_(cs[q], out_hidden[q], out_logits[q], s)) return r;
+    }
+    return 0;
+}
+
 }  // namespace
 
 // The matrix-core prefill's activation workspace (max_seq_len rows of x, norm(x), qkv, attention, gate|up, act + the split-K
@@ -322,6 +404,12 @@ int fq3_prefill_batch_mfma_(fq3_ctx* const* cs, int n, const void* const* embeds
 int fq3_prefill_mfma_(fq3_ctx* c, const void* embeds, int L, int n_pad, void* out_logits, void* out_hidden, hipStream_t s) {
     return c->cfg.dtype == FQ3_BF16 ? prefill_t<bf16_t>(c, embeds, L, n_pad, out_logits, out_hidden, s)
                                     : prefill_t<float>(c, embeds, L, n_pad, out_logits, out_hidden, s);
+}
+
+int fq3_prefill_continue_batch_mfma_(fq3_ctx* const* cs, int n, const void* const* embeds, const int* start, const int* cnt,
+                                     void* const* out_logits, void* const* out_hidden, hipStream_t s) {
+    return cs[0]->cfg.dtype == FQ3_BF16 ? prefill_continue_batch_t<bf16_t>(cs, n, embeds, start, cnt, out_logits, out_hidden, s)
+                                        : prefill_continue_batch_t<float>(cs, n, embeds, start, cnt, out_logits, out_hidden, s);
 }
 
 int fq3_prefill_continue_mfma_(fq3_ctx* c, const void* embeds, int start, int n, void* out_logits, void* out_hidden, hipStream_t s) {

@@ -642,4 +642,199 @@ inline int flash_cont_splits(int start, int n, int NH, int n_cu, long ws_floats)
     return S < 1 ? 1 : S;
 }
 
+// ---------------------------------------------------------------------------------------------------------------------
+// Packed continuation prefill (fq3_prefill_continue_batch): n sequences, each with cnt[q] NEW rows behind its own cached rows
+// [0, start[q]), share the launches of a layer the way the sequences of fq3_prefill_batch do (PackSeq).  qkv / out hold the packed new
+// rows: sequence q's local row t is packed row off[q] + t = position start[q] + t of that sequence.
+// ---------------------------------------------------------------------------------------------------------------------
+struct PackCont {
+    const int* table[kMaxPack];                     // block table of each sequence's context (all of ONE pool)
+    int off[kMaxPack + 1];                          // first packed row of each sequence
+    int start[kMaxPack];                            // cached rows in front of each sequence's new rows
+    int rope_delta[kMaxPack];
+    int zoff[kMaxPack + 1];                         // prefix sum of the key splits S[q]: the (sequence, split) axis of the flash grid
+    int wsoff[kMaxPack];                            // first float of each sequence's split records ([split][row][head][kFcRec]; S[q] > 1 only)
+    int n;
+};
+
+// qk_norm_rope_kv_cont_kernel for the pack: the sequence of a packed row by scalar compares (uniform per wave, as
+// qk_norm_rope_kv_pack_kernel), position start[q] + t, K / V through that sequence's table.  zoff / wsoff are not read.
+template <typename T>
+__global__ __launch_bounds__(256) void qk_norm_rope_kv_cont_pack_kernel(T* qkv, const T* qw, const T* kw, float eps, const float* cos_tab,
+                                                                        const float* sin_tab, int rope_len, PagedKV<T> kvp, PackCont sq,
+                                                                        int NH, int NKV) {
+    constexpr int HD = kHeadDim;
+    const int per = NH + 2 * NKV;
+    const int w = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+    const int Lt = sq.off[sq.n];
+    if (w >= Lt * per) return;
+    const int tg = w / per, v = w - tg * per;
+    int qi = 0;                                          // the sequence of packed row tg (uniform per wave: scalar compares)
+    for (int q = 1; q < sq.n; ++q) qi = tg >= sq.off[q] ? q : qi;
+    const int pos = sq.start[qi] + (tg - sq.off[qi]);
+    PagedKV<T> kv = kvp;
+    kv.table = sq.table[qi];
+    T* src = qkv + (size_t)tg * per * HD + (size_t)v * HD;
+    float x0 = DT<T>::ld(src + lane), x1 = DT<T>::ld(src + lane + 64);
+    if (v < NH + NKV) {
+        const T* gw = v < NH ? qw : kw;
+        const float ss = wave_sum(fmaf(x0, x0, x1 * x1));
+        const float rs = 1.0f / sqrtf(ss / (float)HD + eps);
+        const float n0 = DT<T>::rnd(DT<T>::ld(gw + lane) * DT<T>::rnd(x0 * rs));
+        const float n1 = DT<T>::rnd(DT<T>::ld(gw + lane + 64) * DT<T>::rnd(x1 * rs));
+        int rp = pos + sq.rope_delta[qi];
+        rp = rp < 0 ? 0 : (rp >= rope_len ? rope_len - 1 : rp);
+        const float cs = cos_tab[(size_t)rp * 64 + lane], sn = sin_tab[(size_t)rp * 64 + lane];
+        x0 = DT<T>::rnd(DT<T>::rnd(n0 * cs) + DT<T>::rnd(-n1 * sn));
+        x1 = DT<T>::rnd(DT<T>::rnd(n1 * cs) + DT<T>::rnd(n0 * sn));
+    }
+    T* dst = v < NH ? src : (v < NH + NKV ? kv.k + paged_row(kv, v - NH, pos) : kv.v + paged_row(kv, v - NH - NKV, pos));
+    DT<T>::st(dst + lane, x0);
+    DT<T>::st(dst + lane + 64, x1);
+}
+
+// flash_prefill_cont_kernel for the pack (bf16, one pool).  Grid (max query blocks of a sequence, NH, sum of S[q]): blockIdx.z is a
+// (sequence, split) pair found in the prefix sum zoff by scalar compares; a workgroup whose query block lies beyond its sequence
+// returns at once (as flash_prefill_small_kernel).  From there on it is flash_prefill_cont_kernel on that sequence's slice: the same
+// LDS stage, the same tile ranges, flash_tile with the absolute query position -- so a (sequence, split) does that kernel's
+// arithmetic in that kernel's order.  S[q] == 1 writes `out`; S[q] > 1 stores the fp32 records at ws + wsoff[q] with plain stores for
+// flash_cont_pack_merge_kernel.  No atomics, counters or spins.  The dead-rows CONTRACT of flash_prefill_cont_kernel holds.
+__global__ __launch_bounds__(256) void flash_prefill_cont_pack_kernel(const bf16_t* qkv_all, PagedKV<bf16_t> kv, bf16_t* out_all, float* ws_all,
+                                                                      PackCont sq, int NH, int NKV, float scale) {
+    constexpr int HD = kHeadDim, NW = 4, Q = 16 * NW, CPT = 16 / NW;
+    __shared__ __attribute__((aligned(16))) bf16_t Ks[kFaK * kFaKLd];            // [key][dim]
+    __shared__ __attribute__((aligned(16))) bf16_t Vt[HD * kFaVLd];              // [dim][key]
+    __shared__ __attribute__((aligned(16))) bf16_t Ps[NW][2][16 * kFaPLd];       // per wave: P high / residual, [query][key]
+    const int zz = blockIdx.z;
+    int sqi = 0;                                                          // uniform per workgroup: scalar compares
+    for (int q = 1; q < sq.n; ++q) sqi = zz >= sq.zoff[q] ? q : sqi;
+    const int off = sq.off[sqi], n = sq.off[sqi + 1] - off, start = sq.start[sqi];
+    const int z = zz - sq.zoff[sqi], S = sq.zoff[sqi + 1] - sq.zoff[sqi];
+    const int q0 = (int)blockIdx.x * Q;                                   // first LOCAL row of the block
+    if (q0 >= n) return;
+    const int* table = sq.table[sqi];
+    const int tid = threadIdx.x, lane = tid & 63, fr = lane & 15, fq = lane >> 4;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int h = blockIdx.y, g = h / (NH / NKV), per = NH + 2 * NKV;
+    const bf16_t* qkv = qkv_all + (size_t)off * per * HD;
+    bf16_t* out = out_all + (size_t)off * NH * HD;
+    float* ws = ws_all + sq.wsoff[sqi];
+    const bf16_t* kc = kv.k + (size_t)g * kFaK * HD;
+    const bf16_t* vc = kv.v + (size_t)g * kFaK * HD;
+    const float sl2 = scale * 1.4426950408889634f;
+    const int skey = tid & 63, sch = tid >> 6;
+    const int qrow = q0 + wave * 16 + fr;
+    const int qrc = qrow < n ? qrow : n - 1;
+    bf16x8_t qf[4];
+#pragma unroll
+    for (int ks = 0; ks < 4; ++ks)
+        qf[ks] = *reinterpret_cast<const bf16x8_t*>(qkv + (size_t)qrc * per * HD + (size_t)h * HD + ks * 32 + fq * 8);
+    f32x4_t o[8];
+#pragma unroll
+    for (int d = 0; d < 8; ++d) o[d] = f32x4_t{0.f, 0.f, 0.f, 0.f};
+    float m[4], l[4];
+#pragma unroll
+    for (int r = 0; r < 4; ++r) { m[r] = -1e30f; l[r] = 0.f; }
+    const int nt = (start + min(q0 + Q, n) - 1) / kFaK + 1;               // key tiles [0, nt): up to the block's last query's own key
+    const int tps = (nt + S - 1) / S;
+    const int t_lo = z * tps, t_end = min(nt, t_lo + tps);                // this split: tiles [t_lo, t_end), maybe none
+    u32x4 kst[CPT], vst[CPT];
+    auto issue = [&](int tile) {
+        const size_t o_ = (size_t)table[tile] * kv.blk_stride + (size_t)skey * HD;          // tile < nt: a block this sequence owns
+#pragma unroll
+        for (int j = 0; j < CPT; ++j) {
+            kst[j] = *reinterpret_cast<const u32x4*>(kc + o_ + (sch + NW * j) * 8);
+            vst[j] = *reinterpret_cast<const u32x4*>(vc + o_ + (sch + NW * j) * 8);
+        }
+    };
+    if (t_lo < t_end) issue(t_lo);
+    for (int tile = t_lo; tile < t_end; ++tile) {
+        __syncthreads();                                                  // everyone is done reading the previous tile
+#pragma unroll
+        for (int j = 0; j < CPT; ++j) {
+            *reinterpret_cast<u32x4*>(&Ks[skey * kFaKLd + (sch + NW * j) * 8]) = kst[j];
+            // transposed store, two keys per 32-bit write (see flash_prefill_kernel)
+#pragma unroll
+            for (int w = 0; w < 4; ++w) {
+                const uint32_t mine = vst[j][w];
+                const uint32_t other = (uint32_t)__builtin_amdgcn_mov_dpp((int)mine, 0xB1, 0xF, 0xF, true);
+                const bool odd = skey & 1;
+                const uint32_t word = odd ? ((other >> 16) | (mine & 0xFFFF0000u)) : ((mine & 0xFFFFu) | (other << 16));
+                const int dim = (sch + NW * j) * 8 + 2 * w + (odd ? 1 : 0);
+                *reinterpret_cast<uint32_t*>(&Vt[dim * kFaVLd + (skey & ~1)]) = word;
+            }
+        }
+        __syncthreads();
+        if (tile + 1 < t_end) issue(tile + 1);                            // next tile's loads fly under the MFMAs
+        flash_tile(Ks, Vt, Ps[wave][0], Ps[wave][1], qf, o, m, l, tile, start + q0, wave, fr, fq, 0, sl2);
+    }
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+        const int qi = q0 + wave * 16 + fq * 4 + r;                       // local row
+        if (qi >= n) continue;
+        if (S == 1) {
+            const float inv = l[r] > 0.f ? 1.0f / l[r] : 0.f;
+#pragma unroll
+            for (int d = 0; d < 8; ++d) out[((size_t)qi * NH + h) * HD + d * 16 + fr] = f_to_bf16(o[d][r] * inv);
+        } else {
+            float* rec = ws + (((size_t)z * n + qi) * NH + h) * kFcRec;
+            if (fr == 0) { rec[0] = m[r]; rec[1] = l[r]; }
+#pragma unroll
+            for (int d = 0; d < 8; ++d) rec[2 + d * 16 + fr] = o[d][r];
+        }
+    }
+}
+
+// flash_cont_merge_kernel for the pack: one thread per (packed row, head, dim); rows of a sequence with S[q] == 1 were written by the
+// flash kernel and are left alone; the others merge their S[q] records in split order with that kernel's arithmetic.
+__global__ __launch_bounds__(256) void flash_cont_pack_merge_kernel(const float* ws_all, bf16_t* out, PackCont sq, int NH) {
+    const int i = blockIdx.x * 2 + (threadIdx.x >> 7), d = threadIdx.x & 127;          // i = packed row * NH + head
+    const int Lt = sq.off[sq.n];
+    if (i >= Lt * NH) return;
+    const int tg = i / NH;
+    int qi = 0;                                                           // uniform per wave (a wave holds one i)
+    for (int q = 1; q < sq.n; ++q) qi = tg >= sq.off[q] ? q : qi;
+    const int S = sq.zoff[qi + 1] - sq.zoff[qi];
+    if (S == 1) return;
+    const int n = sq.off[qi + 1] - sq.off[qi];
+    const size_t split = (size_t)n * NH * kFcRec;
+    const float* rec = ws_all + sq.wsoff[qi] + (size_t)(i - sq.off[qi] * NH) * kFcRec;
+    float M = -1e30f;
+    for (int s = 0; s < S; ++s) M = fmaxf(M, rec[s * split]);
+    float l = 0.f, o = 0.f;
+    for (int s = 0; s < S; ++s) {
+        const float w = exp2f(rec[s * split] - M);
+        l = fmaf(rec[s * split + 1], w, l);
+        o = fmaf(rec[s * split + 2 + d], w, o);
+    }
+    out[(size_t)i * kHeadDim + d] = f_to_bf16(l > 0.f ? o / l : 0.f);
+}
+
+// floats of split records a pack with these S[] stores (sequences with S == 1 store none)
+inline long flash_cont_pack_ws_floats(const int* cnt, int n, int NH, const int* S) {
+    long t = 0;
+    for (int q = 0; q < n; ++q) t += S[q] > 1 ? (long)S[q] * cnt[q] * NH * kFcRec : 0;
+    return t;
+}
+
+// key splits of a packed continuation, a pure function of (start[], cnt[]) and the CU count: the CU budget is divided by the pack's
+// total query blocks x heads; per sequence at least kFcMinTiles key tiles per split and at most kFcMaxSplit; while the records of the
+// whole pack exceed the workspace the largest S (the first of equals) loses one.  A pack of one gives flash_cont_splits(start, n, ...).
+inline void flash_cont_pack_splits(const int* start, const int* cnt, int n, int NH, int n_cu, long ws_floats, int* S) {
+    long nqb = 0;
+    for (int q = 0; q < n; ++q) nqb += (cnt[q] + kFaQ - 1) / kFaQ;
+    const int budget = (int)(n_cu / (nqb * NH));
+    for (int q = 0; q < n; ++q) {
+        const int nt = (start[q] + cnt[q] + kFaK - 1) / kFaK;
+        int s = budget < nt / kFcMinTiles ? budget : nt / kFcMinTiles;
+        s = s < kFcMaxSplit ? s : kFcMaxSplit;
+        S[q] = s < 1 ? 1 : s;
+    }
+    while (flash_cont_pack_ws_floats(cnt, n, NH, S) > ws_floats) {
+        int big = 0;
+        for (int q = 1; q < n; ++q) big = S[q] > S[big] ? q : big;
+        --S[big];                                        // > 1 here: records exist only where S > 1
+    }
+}
+
 }  // namespace fq3

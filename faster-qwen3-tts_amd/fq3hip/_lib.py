@@ -118,6 +118,8 @@ SIGNATURES = {
     "fq3_prefill": (C.c_int, [vp, vp, C.c_int, C.c_int, vp, vp, vp]),
     "fq3_prefill_continue": (C.c_int, [vp, vp, C.c_int, C.c_int, vp, vp, vp]),
     "fq3_prefill_reserve": (C.c_int, [vp]),
+    "fq3_prefill_continue_batch": (C.c_int, [C.POINTER(vp), C.c_int, C.POINTER(vp), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(vp),
+                                             C.POINTER(vp), vp]),
     "fq3_prefill_batch": (C.c_int, [C.POINTER(vp), C.c_int, C.POINTER(vp), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(vp),
                                     C.POINTER(vp), vp]),
     "fq3_set_prefill_mode": (C.c_int, [vp, C.c_int]),

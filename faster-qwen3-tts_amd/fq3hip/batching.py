@@ -111,7 +111,8 @@ class BatchDecoder:
     (``Fq3Engine(..., share=engines[0])``)."""
 
     def __init__(self, engines: List[Any], predictor_policy: Optional[Dict[str, Any]] = None, poll_every: int = 8,
-                 use_graph: bool = True, batch_factory=None, staging: Optional[List[Any]] = None, packed_prefill: bool = True):
+                 use_graph: bool = True, batch_factory=None, staging: Optional[List[Any]] = None, packed_prefill: bool = True,
+                 prefix_cache=None):
         if batch_factory is None:
             from .engine import Fq3Batch as batch_factory
         policy = predictor_policy or dict(do_sample=True, top_k=50, top_p=1.0, temperature=0.9)
@@ -148,6 +149,11 @@ class BatchDecoder:
         # tests/test_gpu_decode.py).  Measured with the workspaces reserved up front (profiles/r03_packed_prefill.txt, 0.6B shapes,
         # 200-row prompts): first-wave TTFA 82.5 -> 63.6 ms at 8 lanes and 125 -> 89 ms at 16, aggregate 153.5 -> 156x / 229 -> 234x.
         self.packed_prefill = bool(packed_prefill)
+        # PREFIX KV CACHE (fq3hip/prefix_cache.py; None = off): every prefill this scheduler queues goes through it -- the packed
+        # groups through PrefixCache.prefill_pack, a single member through PrefixCache.prefill.  The cache serves THIS scheduler alone:
+        # all its work is queued on the stream the scheduler prefills on (the side stream with spare contexts, the decode stream
+        # without), which is what orders an evicted entry's blocks against their next tenant.
+        self.prefix_cache = prefix_cache
         # FIRST WAVE (round 5): how many requests are prepared, prefilled and armed before the first frame is queued (None = one per lane,
         # the behaviour up to round 4).  With many lanes and many simultaneous requests, preparing all of them first puts every prompt
         # build and every prefill in front of EVERYBODY's first chunk (128 lanes: first-wave TTFA 348 ms, of which ~250 ms is that
@@ -215,7 +221,8 @@ class BatchDecoder:
         _eng, tn, pn, max_frames = _prefill_and_arm(
             req.talker, req.talker_input_embeds, req.attention_mask, req.trailing_text_hiddens, req.tts_pad_embed,
             req.config, ln.predictor_graph, ln.talker_graph, kw["max_new_tokens"], kw["min_new_tokens"],
-            kw["temperature"], kw["top_k"], kw["top_p"], kw["do_sample"], kw["repetition_penalty"], use_graph=False)
+            kw["temperature"], kw["top_k"], kw["top_p"], kw["do_sample"], kw["repetition_penalty"], use_graph=False,
+            **({} if self.stages or self.prefix_cache is None else dict(cache=self.prefix_cache)))   # with spare contexts the cache lives on the side stream
         ln.req, ln.tn, ln.pn, ln.issued, ln.emitted, ln.max_frames = req, tn, pn, 0, 0, max_frames
         ln.t_arm, ln.prefill_ms = t0, (time.time() - t0) * 1000
         self._open_text(ln)
@@ -287,6 +294,7 @@ class BatchDecoder:
         engines = [st.engine for st, _req, _ev in group]
         taken = []
         host_toks = None
+        ck = {} if self.prefix_cache is None else dict(cache=self.prefix_cache)      # (nothing changes in the calls while it is off)
 
         def reserve_all():
             # the KV blocks of every member's whole utterance (prompt + max_new_tokens + 1 slots, capped at max_seq_len) are taken
@@ -319,29 +327,29 @@ class BatchDecoder:
             for i, it in enumerate(items):
                 n = int(it[0].shape[1])
                 if i > lo and rows + n > cap:
-                    out += _prefill_first_tokens_launch(engines[lo:i], items[lo:i], cnt[lo:i])
+                    out += _prefill_first_tokens_launch(engines[lo:i], items[lo:i], cnt[lo:i], **ck)
                     lo, rows = i, 0
                 rows += n
-            out += _prefill_first_tokens_launch(engines[lo:], items[lo:], cnt[lo:])
+            out += _prefill_first_tokens_launch(engines[lo:], items[lo:], cnt[lo:], **ck)
             return out
 
         def run():
             if defer:
                 return run_deferred()
             if len(group) == 1 or not self.packed_prefill:
-                return [_prefill_first_token(e, *it) for e, it in zip(engines, items)]
+                return [_prefill_first_token(e, *it, **ck) for e, it in zip(engines, items)]
             # packed prefills share the leading context's workspace (max_seq_len rows): split the group where the rows run out
             out, lo, rows = [], 0, 0
             cap = int(getattr(engines[0], "max_seq_len", 1 << 30))
             for i, it in enumerate(items):
                 n = int(it[0].shape[1])
                 if i > lo and rows + n > cap:
-                    out += (_prefill_first_tokens_packed(engines[lo:i], items[lo:i]) if i - lo > 1
-                            else [_prefill_first_token(engines[lo], *items[lo])])
+                    out += (_prefill_first_tokens_packed(engines[lo:i], items[lo:i], **ck) if i - lo > 1
+                            else [_prefill_first_token(engines[lo], *items[lo], **ck)])
                     lo, rows = i, 0
                 rows += n
-            out += (_prefill_first_tokens_packed(engines[lo:], items[lo:]) if len(items) - lo > 1
-                    else [_prefill_first_token(engines[lo], *items[lo])])
+            out += (_prefill_first_tokens_packed(engines[lo:], items[lo:], **ck) if len(items) - lo > 1
+                    else [_prefill_first_token(engines[lo], *items[lo], **ck)])
             return out
 
         try:

@@ -266,7 +266,7 @@ def build_parser():
     def prefix_cache_flag(sp):
         sp.add_argument("--prefix-cache-rows", type=int, default=0, metavar="N",
                         help="keep the talker K/V rows of instruct turns on the device, up to N rows, and prefill only the rest of a "
-                             "prompt whose instruct is cached (default 0: off)")
+                             "prompt whose instruct is cached (default 0: off; the server honours it under both schedulers)")
 
     c = sub.add_parser("clone", help="voice cloning from reference audio")
     common(c); clone_refs(c); c.set_defaults(mode="clone", func=cmd_once)

@@ -126,6 +126,7 @@ class Fq3Engine:
         self.weights = weights
         self._pred_sampling = dict(do_sample=True, top_k=50, top_p=1.0, temperature=0.9)
         self.prefix_cache = None      # a fq3hip.prefix_cache.PrefixCache once FasterQwen3TTS.enable_prefix_cache has set one
+        self.prefix_split = False     # the prompt builder projects instruct ids on their own although this engine carries no cache (a batch scheduler's does)
 
     @classmethod
     def sampler_only(cls, device, dtype: torch.dtype) -> "Fq3Engine":
@@ -304,9 +305,10 @@ class Fq3Engine:
             L.check(self.lib.fq3_prefill_reserve(self.ctx))
 
     @staticmethod
-    def prefill_batch(engines, embeds, n_pads=None):
+    def prefill_batch(engines, embeds, n_pads=None, want_logits: bool = True):
         """Several prompts in one pass over the weights (``fq3_prefill_batch``): ``embeds[i]`` [L_i, H] is prefilled into
-        ``engines[i]``'s cache.  Returns ``[(logits [V], hidden [H]), ...]``.  The engines must share one weight table."""
+        ``engines[i]``'s cache.  Returns ``[(logits [V], hidden [H]), ...]``; ``want_logits=False`` skips the codec heads (logits are
+        None).  The engines must share one weight table."""
         import ctypes as C
         e0 = engines[0]
         n = len(engines)
@@ -315,20 +317,43 @@ class Fq3Engine:
         outs = []
         for e, x in zip(engines, embeds):
             e._chk(x, x.shape[0] * H, "prefill embeds")
-            outs.append((e.new(V), e.new(H)))
+            outs.append((e.new(V) if want_logits else None, e.new(H)))
         vp = C.c_void_p
         ctxs = (vp * n)(*[e.ctx for e in engines])
         emb = (vp * n)(*[x.data_ptr() for x in embeds])
         Ls = (C.c_int * n)(*[int(x.shape[0]) for x in embeds])
         pads = (C.c_int * n)(*[int(p) for p in n_pads])
-        lg = (vp * n)(*[o[0].data_ptr() for o in outs])
+        lg = (vp * n)(*[_ptr(o[0]) for o in outs])
         hd = (vp * n)(*[o[1].data_ptr() for o in outs])
         L.check(e0.lib.fq3_prefill_batch(ctxs, n, emb, Ls, pads, lg, hd, e0._stream()))
         return outs
 
+    @staticmethod
+    def prefill_continue_batch(engines, embeds, starts):
+        """``prefill_continue`` for several prompts in one pass over the weights (``fq3_prefill_continue_batch``): ``embeds[i]``
+        [n_i, H] are the new rows of prompt i, whose rows ``[0, starts[i])`` are already in ``engines[i]``'s cache.  Returns
+        ``[(logits [V], hidden [H]), ...]`` of each prompt's last new row.  The engines must share one weight table."""
+        import ctypes as C
+        e0 = engines[0]
+        n = len(engines)
+        H, V = e0.cfg.talker.hidden_size, e0.cfg.talker.vocab_size
+        outs = []
+        for e, x in zip(engines, embeds):
+            e._chk(x, x.shape[0] * H, "prefill_continue embeds")
+            outs.append((e.new(V), e.new(H)))
+        vp = C.c_void_p
+        ctxs = (vp * n)(*[e.ctx for e in engines])
+        emb = (vp * n)(*[x.data_ptr() for x in embeds])
+        st = (C.c_int * n)(*[int(p) for p in starts])
+        cnt = (C.c_int * n)(*[int(x.shape[0]) for x in embeds])
+        lg = (vp * n)(*[o[0].data_ptr() for o in outs])
+        hd = (vp * n)(*[o[1].data_ptr() for o in outs])
+        L.check(e0.lib.fq3_prefill_continue_batch(ctxs, n, emb, st, cnt, lg, hd, e0._stream()))
+        return outs
+
     def set_option(self, key: str, value: int):
         """Kernel-variant switch (``fq3_set_option``): weight_nt, pred_m2, pred_attn, rows_per_wave_max, prefill_mode, flash_prefill,
-        flash_small, skinny_gemm."""
+        flash_small, skinny_gemm, cont_pack."""
         L.check(self.lib.fq3_set_option(self.ctx, key.encode(), int(value)))
 
     def decode_set_forced(self, forced: Optional[torch.Tensor], decisions: Optional[torch.Tensor]):

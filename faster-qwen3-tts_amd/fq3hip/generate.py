@@ -48,15 +48,15 @@ def noted_n_pad(attention_mask):
     return int(note[0])
 
 
-def _prefill_first_token(eng, talker_input_embeds, attention_mask, config, min_new_tokens, temperature, top_k, top_p, do_sample):
-    """=== PREFILL (generate.py:107-134) === on ``eng``: KV rows written, first codebook-0 token sampled.
-    Returns (token, past_hidden, prompt_rows, n_pad)."""
+def _prefill_first_token(eng, talker_input_embeds, attention_mask, config, min_new_tokens, temperature, top_k, top_p, do_sample, cache=None):
+    """=== PREFILL (generate.py:107-134) === on ``eng``: KV rows written, first codebook-0 token sampled.  ``cache``: a batch
+    scheduler's prefix cache (the engine's own ``prefix_cache`` otherwise).  Returns (token, past_hidden, prompt_rows, n_pad)."""
     dt, dev = eng.dtype, eng.device
     eos_id = config.codec_eos_token_id
     V = config.vocab_size
     n_pad = _n_pad_of(attention_mask)
     x = talker_input_embeds[0].to(device=dev, dtype=dt).contiguous()
-    cache = getattr(eng, "prefix_cache", None)
+    cache = cache if cache is not None else getattr(eng, "prefix_cache", None)
     if cache is not None:
         # prefix KV cache (fq3hip/prefix_cache.py): the instruct rows the prompt builder noted are reused or saved; it falls back to
         # the plain prefill by itself (no note, padding, a prefix too short or too long)
@@ -70,16 +70,24 @@ def _prefill_first_token(eng, talker_input_embeds, attention_mask, config, min_n
     return int(token), hidden, int(x.shape[0]), n_pad
 
 
-def _prefill_first_tokens_packed(engines, items):
+def _prefill_pack(engines, items, xs, pads, cache):
+    """The packed prefill of a group: through the scheduler's prefix cache when it has one (``PrefixCache.prefill_pack``)."""
+    from .engine import Fq3Engine
+    if cache is None:
+        return Fq3Engine.prefill_batch(engines, xs, pads)
+    return cache.prefill_pack(engines, xs, pads, [getattr(it[0], "fq3_prefix", None) for it in items])
+
+
+def _prefill_first_tokens_packed(engines, items, cache=None):
     """``_prefill_first_token`` for several requests at once: ONE packed prefill (``fq3_prefill_batch``: one pass over the
     weights), then the first tokens sampled per request.  ``items[i]`` = the argument tuple ``_prefill_first_token`` takes
-    after the engine.  Returns one ``(token, past_hidden, prompt_rows, n_pad)`` per request."""
-    from .engine import Fq3Engine
+    after the engine.  ``cache``: the scheduler's prefix cache or None.  Returns one ``(token, past_hidden, prompt_rows, n_pad)``
+    per request."""
     xs, pads = [], []
     for eng, (tie, tam, _config, *_rest) in zip(engines, items):
         pads.append(_n_pad_of(tam))
         xs.append(tie[0].to(device=eng.device, dtype=eng.dtype).contiguous())
-    outs = Fq3Engine.prefill_batch(engines, xs, pads)
+    outs = _prefill_pack(engines, items, xs, pads, cache)
     toks = []
     for eng, x, (logits, hidden), (tie, tam, config, min_new_tokens, temperature, top_k, top_p, do_sample) in zip(engines, xs, outs, items):
         V = config.vocab_size
@@ -90,14 +98,13 @@ def _prefill_first_tokens_packed(engines, items):
     return [(int(t), o[1], int(x.shape[0]), p) for t, o, x, p in zip(toks, outs, xs, pads)]      # the first int() waits for all
 
 
-def _prefill_first_tokens_launch(engines, items, pads):
+def _prefill_first_tokens_launch(engines, items, pads, cache=None):
     """The LAUNCH half of :func:`_prefill_first_tokens_packed` (the batch scheduler's pipelined first wave): the packed prefill and the
     first-token samplers are queued on the current stream and nothing is waited for.  ``pads[i]``: the prompt's left padding (the
     caller counted all of them with one device round trip).  Returns ``[(token TENSOR on the device, past_hidden, prompt_rows, n_pad)]``;
     the caller turns the tensors into ints when it needs them (one copy for all)."""
-    from .engine import Fq3Engine
     xs = [tie[0].to(device=eng.device, dtype=eng.dtype).contiguous() for eng, (tie, *_r) in zip(engines, items)]
-    outs = Fq3Engine.prefill_batch(engines, xs, pads)
+    outs = _prefill_pack(engines, items, xs, pads, cache)
     res = []
     for eng, x, (logits, hidden), p, (tie, tam, config, min_new_tokens, temperature, top_k, top_p, do_sample) in zip(engines, xs, outs, pads, items):
         V = config.vocab_size
@@ -144,9 +151,9 @@ def _arm_decode(talker, config, token, hidden, n_rows, attention_mask, trailing_
 
 def _prefill_and_arm(talker, talker_input_embeds, attention_mask, trailing_text_hiddens, tts_pad_embed, config,
                      predictor_graph, talker_graph, max_new_tokens, min_new_tokens, temperature, top_k, top_p,
-                     do_sample, repetition_penalty, use_graph):
+                     do_sample, repetition_penalty, use_graph, cache=None):
     token, hidden, n_rows, n_pad = _prefill_first_token(talker_graph.engine, talker_input_embeds, attention_mask, config,
-                                                        min_new_tokens, temperature, top_k, top_p, do_sample)
+                                                        min_new_tokens, temperature, top_k, top_p, do_sample, cache=cache)
     return _arm_decode(talker, config, token, hidden, n_rows, attention_mask, trailing_text_hiddens, tts_pad_embed, predictor_graph,
                        talker_graph, max_new_tokens, min_new_tokens, temperature, top_k, top_p, do_sample, repetition_penalty,
                        use_graph, n_pad=n_pad)

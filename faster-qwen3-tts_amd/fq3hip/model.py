@@ -519,19 +519,42 @@ class FasterQwen3TTS:
         self.warmup(prefill_len=prefill_len)
 
     # ---- prefix KV cache (opt-in) -----------------------------------------------------------------------------------
-    def enable_prefix_cache(self, capacity_rows: int, min_rows: Optional[int] = None):
+    def enable_prefix_cache(self, capacity_rows: int, min_rows: Optional[int] = None, batch: bool = False):
         """Keep the talker K/V rows of instruct turns (voice design, custom voice with an instruct) on the device, up to
-        ``capacity_rows`` rows, and prefill only the rest of a prompt whose instruct is cached (``fq3hip/prefix_cache.py``).  Applies
-        to the single-stream entry points (``generate_*``, ``generate_*_streaming``, ``stream_*``); the ``*_batch`` entry points and the
-        batch scheduler run on engines of their own, which never carry a cache.  Returns the :class:`PrefixCache`."""
-        from .prefix_cache import PrefixCache
-        self.disable_prefix_cache()
+        ``capacity_rows`` rows, and prefill only the rest of a prompt whose instruct is cached (``fq3hip/prefix_cache.py``).
+        ``batch=False``: the cache of the single-stream entry points (``generate_*``, ``generate_*_streaming``, ``stream_*``), carried by
+        the model's engine.  ``batch=True``: the cache of the ``*_batch`` entry points and the batch scheduler
+        (``BatchDecoder(prefix_cache=...)``: packed groups go through ``PrefixCache.prefill_pack``); it is a cache of its own, because
+        the scheduler prefills on a stream of its own, and the single-stream entry points never see it.  Both may be on.  Returns the
+        :class:`PrefixCache`."""
+        from .prefix_cache import DEFAULT_BATCH_MIN_ROWS, PrefixCache
         eng = self.talker_graph.engine
+        if batch:
+            self.disable_prefix_cache(batch=True)
+            self._batch_prefix_cache = PrefixCache(eng, capacity_rows, DEFAULT_BATCH_MIN_ROWS if min_rows is None else min_rows)
+            eng.prefix_split = True           # the prompt builder projects the instruct ids on their own (prompt.py)
+            cached = getattr(self, "_batch_cache", None)
+            if cached is not None:
+                cached[1].prefix_cache = self._batch_prefix_cache
+            return self._batch_prefix_cache
+        self.disable_prefix_cache()
         eng.prefix_cache = PrefixCache(eng, capacity_rows, min_rows)
         return eng.prefix_cache
 
-    def disable_prefix_cache(self) -> None:
+    def disable_prefix_cache(self, batch: bool = False) -> None:
         eng = self.talker_graph.engine
+        if batch:
+            cache = getattr(self, "_batch_prefix_cache", None)
+            self._batch_prefix_cache = None
+            eng.prefix_split = False
+            cached = getattr(self, "_batch_cache", None)
+            if cached is not None:
+                cached[1].prefix_cache = None
+            if cache is not None:
+                if torch.cuda.is_available():
+                    torch.cuda.synchronize(eng.device)                    # the scheduler's prefill stream has run the last copies
+                cache.close()
+            return
         cache = getattr(eng, "prefix_cache", None)
         eng.prefix_cache = None
         if cache is not None:
@@ -1029,6 +1052,7 @@ class FasterQwen3TTS:
             # the lanes follow this model's CURRENT predictor policy (it is copied into the loop state when a lane is armed)
             pg = self.predictor_graph
             cached[1].set_predictor_policy(do_sample=pg.do_sample, top_k=pg.top_k, top_p=pg.top_p, temperature=pg.temperature)
+            cached[1].prefix_cache = getattr(self, "_batch_prefix_cache", None)
             return cached[1]
         self._batch_cache = None                    # a differently shaped scheduler: its contexts and pool go first
         pool = Fq3KvPool(first.cfg, blocks, device=str(first.device), dtype=first.dtype)
@@ -1038,7 +1062,7 @@ class FasterQwen3TTS:
         pg = self.predictor_graph
         dec = BatchDecoder(engines, predictor_policy=dict(do_sample=pg.do_sample, top_k=pg.top_k, top_p=pg.top_p,
                                                           temperature=pg.temperature),
-                           staging=[mk() for _ in range(staging)])
+                           staging=[mk() for _ in range(staging)], prefix_cache=getattr(self, "_batch_prefix_cache", None))
         dec.kv_pool = pool
         # batch_lookahead (attribute, default None = the scheduler's default, 1: the next batch of frames is queued before the previous
         # batch's poll is read; 0 = wait for every batch right after queuing it) -- see BatchDecoder.lookahead

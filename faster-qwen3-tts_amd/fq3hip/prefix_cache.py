@@ -12,10 +12,15 @@ Both run the same continuation on the same prefix bits -- the copy is exact -- s
 voice was cached.  An entry is a pooled context that never prefills (so it never allocates a prefill workspace): it shares the
 engine's weights and holds ``ceil(P / 64)`` blocks of the cache's own KV pool of ``capacity_rows / 64`` blocks.
 
+A lock-step batch scheduler hands a whole admitted group to :meth:`PrefixCache.prefill_pack`: the members without a usable prefix go
+through the plain packed prefill, each distinct missing prefix is prefilled once, and every member behind a prefix continues in ONE
+packed continuation (``fq3_prefill_continue_batch``).
+
 **One stream.**  All cache work is enqueued on the engine's current stream.  Eviction hands an entry's blocks back to the pool on
 the host at once, and the next save overwrites them: that is safe only because every copy out of and into those blocks is ordered
 on that one stream.  Do not share a cache between engines that run on different streams; the object is not re-entrant either (the
-server uses it under its one-request-at-a-time lock).
+server uses it under its one-request-at-a-time lock).  A cache handed to a ``BatchDecoder`` serves that scheduler alone: all its work
+is queued on the stream the scheduler prefills on.
 """
 from __future__ import annotations
 
@@ -28,6 +33,8 @@ from .engine import KV_BLOCK
 # The smallest probed prefix at which a hit beats the plain prefill on both model sizes (tools/prefix_cache_probe.py ->
 # profiles/prefix_cache.json): 64 rows, one KV block -- a hit won at every probed prefix.
 DEFAULT_MIN_ROWS = 64
+# The same for a batch scheduler's packed admission (profiles/prefix_cache_batch.json).
+DEFAULT_BATCH_MIN_ROWS = 64
 
 
 def _blocks(rows: int) -> int:
@@ -105,6 +112,79 @@ class PrefixCache:
             self._save(engine, key, P)
             self._n["misses"] += 1
         return engine.prefill_continue(x[P:], P)
+
+    @staticmethod
+    def _runs(idx, rows, cap):
+        """``idx`` cut into runs whose ``rows`` sum to at most ``cap`` (a packed pass runs on one context's workspace)."""
+        out, cur, tot = [], [], 0
+        for i, r in zip(idx, rows):
+            if cur and tot + r > cap:
+                out.append(cur)
+                cur, tot = [], 0
+            cur.append(i)
+            tot += r
+        if cur:
+            out.append(cur)
+        return out
+
+    def prefill_pack(self, engines, xs, pads, notes):
+        """:meth:`prefill` for a group a batch scheduler admits together: ``xs[i]`` [L_i, H] into ``engines[i]`` (contexts of one
+        weight table), ``pads[i]`` its left padding, ``notes[i]`` its ``fq3_prefix`` note or None.  Returns ``[(logits, hidden), ...]``
+        in request order; everything is queued on the current stream and nothing is waited for.
+
+        Members without a usable prefix go through one plain ``Fq3Engine.prefill_batch``.  Of the others, a hit receives the entry's
+        rows; each DISTINCT missing key is prefilled once, into the first member that names it (several of them in one packed pass
+        without logits), saved, and copied to the other members of that key -- those count as hits.  Then all of them continue in one
+        ``Fq3Engine.prefill_continue_batch``.  The members' contexts may already own the blocks of their whole utterance: a copy
+        into them takes none."""
+        from .engine import Fq3Engine
+        n = len(engines)
+        res = [None] * n
+        cap = int(getattr(engines[0], "max_seq_len", 1 << 30))
+        Ps = [self._usable(x, int(p), nt) for x, p, nt in zip(xs, pads, notes)]
+        rest = [i for i in range(n) if Ps[i] == 0]
+        use = [i for i in range(n) if Ps[i] > 0]
+        self._n["bypasses"] += len(rest)
+        for run in self._runs(rest, [int(xs[i].shape[0]) for i in rest], cap):
+            outs = Fq3Engine.prefill_batch([engines[i] for i in run], [xs[i] for i in run], [int(pads[i]) for i in run])
+            for i, o in zip(run, outs):
+                res[i] = o
+        if not use:
+            return res
+        first = {}                        # missing key -> the member that prefills it
+        followers = []                    # (member, key): named a key that missed earlier in this group
+        for i in use:
+            key = self._key(engines[i], notes[i][1])
+            if key in first:
+                followers.append((i, key))
+                self._n["hits"] += 1
+                self._n["rows_reused"] += Ps[i]
+                continue
+            hit = self._entries.get(key)
+            if hit is not None:
+                self._entries.move_to_end(key)
+                engines[i].kv_copy(hit[0], Ps[i])
+                self._n["hits"] += 1
+                self._n["rows_reused"] += Ps[i]
+            else:
+                first[key] = i
+                self._n["misses"] += 1
+        miss = list(first.values())
+        for run in self._runs(miss, [Ps[i] for i in miss], cap):
+            if len(run) == 1:
+                i = run[0]
+                engines[i].prefill(xs[i][:Ps[i]], n_pad=0, want_logits=False)
+            else:
+                Fq3Engine.prefill_batch([engines[i] for i in run], [xs[i][:Ps[i]] for i in run], [0] * len(run), want_logits=False)
+        for key, i in first.items():
+            self._save(engines[i], key, Ps[i])
+        for j, key in followers:          # from the member that holds the rows: the entry may already have been evicted again
+            engines[j].kv_copy(engines[first[key]], Ps[j])
+        for run in self._runs(use, [int(xs[i].shape[0]) - Ps[i] for i in use], cap):
+            outs = Fq3Engine.prefill_continue_batch([engines[i] for i in run], [xs[i][Ps[i]:] for i in run], [Ps[i] for i in run])
+            for i, o in zip(run, outs):
+                res[i] = o
+        return res
 
     def stats(self) -> Dict[str, int]:
         held = sum(_blocks(P) for _ctx, P in self._entries.values())

@@ -64,7 +64,8 @@ def build_talker_inputs_hip(m, input_id: torch.Tensor, ref_id: Optional[torch.Te
     if instruct_id is not None:
         ins = host_ids(instruct_id)
         instruct_key = tuple(ins)
-        if getattr(eng, "prefix_cache", None) is not None and ins:
+        # (prefix_split: a batch scheduler's cache asks for the same without being this engine's cache, model.enable_prefix_cache)
+        if (getattr(eng, "prefix_cache", None) is not None or getattr(eng, "prefix_split", False)) and ins:
             instruct_rows = eng.text_project(torch.tensor(ins, dtype=torch.long, device=eng.device))
             rows += [(-2 - j, NONE, 0) for j in range(len(ins))]          # resolved below: rows behind the pooled ones
         else:

@@ -73,9 +73,11 @@ class BatchWorker:
 
     DONE = object()
 
-    def __init__(self, model, lanes: int = 8, chunk_size: int = 12):
+    def __init__(self, model, lanes: int = 8, chunk_size: int = 12, prefix_cache_rows: int = 0):
         from .batching import MAX_LANES
         self.model, self.lanes = model, max(1, min(int(lanes), MAX_LANES))
+        # the batch scheduler's prefix KV cache (FasterQwen3TTS.enable_prefix_cache(rows, batch=True)): off by default
+        self.prefix_cache = model.enable_prefix_cache(int(prefix_cache_rows), batch=True) if int(prefix_cache_rows or 0) > 0 else None
         # ONE chunk size for the whole server: the lock-step decoder hands out chunks of this many frames and every request's
         # StreamingVocoder is built for the same number (a voice entry's own "chunk_size" only applies to the lock scheduler)
         self.chunk_size = max(1, int(chunk_size))
@@ -243,21 +245,20 @@ class BatchWorker:
 def create_app(model, voices: Dict[str, dict], default_voice: Optional[str] = None, scheduler: str = "lock", lanes: int = 8,
                chunk_size: int = 12, worker=None, prefix_cache_rows: int = 0):
     """``worker``: a ready ``BatchWorker`` (or a stand-in with ``submit`` / ``submit_text``) instead of the one ``scheduler="batch"``
-    would start.  ``prefix_cache_rows`` > 0: the model's prefix KV cache (``FasterQwen3TTS.enable_prefix_cache``) with that many rows;
-    it serves the ``lock`` scheduler (the batch scheduler decodes on engines of its own, which carry no cache)."""
+    would start.  ``prefix_cache_rows`` > 0: the model's prefix KV cache (``FasterQwen3TTS.enable_prefix_cache``) with that many rows:
+    the engine's cache under the ``lock`` scheduler; under ``batch`` the ``BatchWorker`` started here creates the scheduler's own
+    (``batch=True``: packed admission through ``PrefixCache.prefill_pack``).  A ``worker`` handed in brings its own (its
+    ``prefix_cache`` attribute, if any, is what ``/health`` reports)."""
     from fastapi import FastAPI, HTTPException
     from fastapi.responses import Response, StreamingResponse
 
     app = FastAPI(title="faster-qwen3-tts (MI355X) OpenAI-compatible API")
     lock = threading.Lock()
     if worker is None and scheduler == "batch":
-        worker = BatchWorker(model, lanes, chunk_size)
-    prefix_cache = None
-    if int(prefix_cache_rows or 0) > 0:
-        if worker is not None:
-            logger.info("--prefix-cache-rows does nothing with --scheduler batch (it serves --scheduler lock)")
-        else:
-            prefix_cache = model.enable_prefix_cache(int(prefix_cache_rows))
+        worker = BatchWorker(model, lanes, chunk_size, prefix_cache_rows=int(prefix_cache_rows or 0))
+    prefix_cache = getattr(worker, "prefix_cache", None)
+    if worker is None and int(prefix_cache_rows or 0) > 0:
+        prefix_cache = model.enable_prefix_cache(int(prefix_cache_rows))
     sessions: Dict[str, dict] = {}
     sessions_lock = threading.Lock()
     sample_rate = int(getattr(model, "sample_rate", 24000))
@@ -489,8 +490,8 @@ def build_parser():
     p.add_argument("--voice-cache", help="directory of precomputed voice prompts serving ref_audio entries")
     p.add_argument("--synthetic", choices=["0.6b", "1.7b"])
     p.add_argument("--prefix-cache-rows", type=int, default=0, metavar="N",
-                   help="keep the talker K/V rows of instruct turns on the device, up to N rows (default 0: off); takes effect with "
-                        "--scheduler lock")
+                   help="keep the talker K/V rows of instruct turns on the device, up to N rows (default 0: off); under --scheduler batch "
+                        "the packed admission reuses them, under --scheduler lock each request does")
     return p
 
 

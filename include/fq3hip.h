@@ -134,7 +134,8 @@ int fq3_kv_blocks(const fq3_ctx* ctx);
  *   fq3_prefill_batch over ONE pool share two attention launches per layer; 0 = the streamed-tile kernel, per prompt; bit-identical),
  *   "packed_weights" 0|1 (round 6; the weight-stationary GEMMs read the fragment-major copies of the layer matrices; bit-identical),
  *   "swiglu_tile" 0|1 (round 6; prefills of more than 416 rows run gate | up on the ring tile over a 16-row-interleaved copy of the
- *   weight with SwiGLU in the epilogue instead of GEMM + elementwise pass; bit-identical).
+ *   weight with SwiGLU in the epilogue instead of GEMM + elementwise pass; bit-identical),
+ *   "cont_pack" 0|1 (fq3_prefill_continue_batch: the attention of the whole pack in one launch per layer; 0 = per prompt).
  * Resets a captured graph. */
 int fq3_set_option(fq3_ctx* ctx, const char* key, int value);
 
@@ -193,6 +194,18 @@ int fq3_prefill_continue(fq3_ctx* ctx, const void* embeds, int start, int n, voi
  * admits several requests at once.  out_logits may be null, or hold nulls. */
 int fq3_prefill_batch(fq3_ctx* const* ctxs, int n, const void* const* embeds, const int* L, const int* n_pad,
                       void* const* out_logits, void* const* out_hidden, void* stream);
+
+/* fq3_prefill_continue for n prompts with ONE pass over the weights: embeds[q] T[cnt[q], H] are the NEW rows of prompt q, whose rows
+ * [0, start[q]) are already in ctxs[q]'s cache; K/V go to slots [start[q], start[q] + cnt[q]), row start[q] + t attends to keys
+ * 0 .. start[q] + t, outputs come from each prompt's last new row.  Packing as fq3_prefill_batch: row-wise work on the packed new rows
+ * on ctxs[0]'s workspace (sum of cnt <= its max_seq_len), one weight table, n <= 64.  bf16 with contexts of one pool: one norm + RoPE +
+ * K/V launch and one flash attention launch per layer for the whole pack (+ one merge launch when a sequence splits its keys; fixed
+ * order, the same call gives the same bits); otherwise per-prompt launches of the fq3_prefill_continue kernels ("cont_pack" 0 forces
+ * them).  All-or-nothing, checked before anything is queued: FQ3_EINVAL (n < 1, n > 64, cnt < 1, start < 0, mixed weight tables or
+ * dtypes), FQ3_ESTATE (a context owns fewer than ceil(start / 64) blocks), FQ3_ETOOLONG (start + cnt > max_seq_len, or the packed rows
+ * exceed the workspace), FQ3_ENOMEM (pool short: nothing taken).  Sets each context's generation state to (n_pad 0, rope_delta 0). */
+int fq3_prefill_continue_batch(fq3_ctx* const* ctxs, int n, const void* const* embeds, const int* start, const int* cnt,
+                               void* const* out_logits, void* const* out_hidden, void* stream);
 
 /* Allocate the matrix-core prefill's activation workspace of this context now (max_seq_len rows; otherwise it is allocated by
  * the first fq3_prefill / fq3_prefill_batch that leads with this context).  A scheduler that prefills into spare contexts on a

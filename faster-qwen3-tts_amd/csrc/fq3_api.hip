@@ -799,7 +799,7 @@ extern "C" int fq3_prefill(fq3_ctx* c, const void* embeds, int L, int n_pad, voi
 }
 
 // Continuation of a prefill: rows [start, start + n) behind K/V rows [0, start) that are already in this context's cache (unpadded).
-// Matrix-core path by default (csrc/fq3_prefill.hip: prefill_continue_t); n < 4 or prefill_mode 1 walks the new rows token by token
+// Matrix-core path by default (csrc/fq3_prefill.hip: prefill_continue_batch_t for one prompt); n < 4 or prefill_mode 1 walks the new rows token by token
 // through the decode-step kernels from position start.
 extern "C" int fq3_prefill_continue(fq3_ctx* c, const void* embeds, int start, int n, void* out_logits, void* out_hidden, void* stream) {
     NEED_BOUND(c);

@@ -1,6 +1,13 @@
 // Kernels of the matrix-core prefill of the talker (fq3_prefill.hip holds the host side: paged_kv, pack_seq and the launch choosers):
 // head RMSNorm + RoPE + K/V write into the paged cache, the per-row wave attention kernel and the flash-style MFMA attention kernels.
 // A header of their own so that a conformance probe (tools/microbench/prefill_attn_probe.hip) can launch each of them alone.
+// Shared bodies: flash_tile (one key tile of every flash kernel) and flash_acc_init.  The remaining arithmetic -- norm + RoPE + store,
+// the wave-attention loop, the K/V staging with the transposed V store, the epilogues, the merge loop -- is written out in each
+// kernel of its family ON PURPOSE: moved into __forceinline__ functions it compiles to other instruction streams and register counts
+// than the text in place (even the two-line sequence lookup does), and these kernels are kept at their measured code.  The copies must
+// stay the same instructions on the same values in the same order: the bit-equality tests between the families
+// (tests/test_gpu_prefill_*_reference.py, tests/test_gpu_prefix_cache*.py) hold them to it, so a fix to one copy goes into all of them.
+// Host side: flash_cont_splits is flash_cont_pack_splits for a pack of one.
 #pragma once
 #include "decode_kernels.cuh"
 #include "codec_kernels.cuh"
@@ -199,6 +206,14 @@ __device__ __forceinline__ void flash_tile(const bf16_t* Ks, const bf16_t* Vt, b
         }
 }
 
+// fresh accumulators of a wave's 16 queries: O = 0, running row maximum m = -1e30 (base-2 units), running row sum l = 0
+__device__ __forceinline__ void flash_acc_init(f32x4_t (&o)[8], float (&m)[4], float (&l)[4]) {
+#pragma unroll
+    for (int d = 0; d < 8; ++d) o[d] = f32x4_t{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int r = 0; r < 4; ++r) { m[r] = -1e30f; l[r] = 0.f; }
+}
+
 // NW waves = 16 * NW queries per block (4: 64 queries, the short-prompt shape; 8: 128 queries -- a staged K/V tile feeds twice the
 // MFMA work).  PAIRED: the workgroup handles query block bx and then block nqb - 1 - bx, so that under the causal mask every
 // workgroup walks the same number of key tiles (nqb + 1) instead of 1 .. nqb of them: a 4096-token prompt at 128 queries per block
@@ -232,11 +247,8 @@ __global__ __launch_bounds__(64 * NW) void flash_prefill_kernel(const bf16_t* qk
     for (int ks = 0; ks < 4; ++ks)
         qf[ks] = *reinterpret_cast<const bf16x8_t*>(qkv + (size_t)qrc * per * HD + (size_t)h * HD + ks * 32 + fq * 8);
     f32x4_t o[8];
-#pragma unroll
-    for (int d = 0; d < 8; ++d) o[d] = f32x4_t{0.f, 0.f, 0.f, 0.f};
     float m[4], l[4];
-#pragma unroll
-    for (int r = 0; r < 4; ++r) { m[r] = -1e30f; l[r] = 0.f; }
+    flash_acc_init(o, m, l);
     const int q_hi = min(q0 + Q, L) - 1;                                  // last query of the block
     const int t_lo = n_pad / kFaK, t_hi = q_hi / kFaK;                    // key tiles [t_lo, t_hi]
     u32x4 kst[CPT], vst[CPT];
@@ -371,11 +383,8 @@ __global__ __launch_bounds__(256) void flash_prefill_small_kernel(const bf16_t* 
     stage(kst[1], vst[1], 3);
     __syncthreads();
     f32x4_t o[8];
-#pragma unroll
-    for (int d = 0; d < 8; ++d) o[d] = f32x4_t{0.f, 0.f, 0.f, 0.f};
     float m[4], l[4];
-#pragma unroll
-    for (int r = 0; r < 4; ++r) { m[r] = -1e30f; l[r] = 0.f; }
+    flash_acc_init(o, m, l);
     bf16_t* ph = PsAll + (size_t)(wave * 2 + 0) * 16 * kFaPLd;
     bf16_t* pl = PsAll + (size_t)(wave * 2 + 1) * 16 * kFaPLd;
     for (int tile = t_lo; tile <= t_hi; ++tile) {
@@ -557,11 +566,8 @@ __global__ __launch_bounds__(256) void flash_prefill_cont_kernel(const bf16_t* q
     for (int ks = 0; ks < 4; ++ks)
         qf[ks] = *reinterpret_cast<const bf16x8_t*>(qkv + (size_t)qrc * per * HD + (size_t)h * HD + ks * 32 + fq * 8);
     f32x4_t o[8];
-#pragma unroll
-    for (int d = 0; d < 8; ++d) o[d] = f32x4_t{0.f, 0.f, 0.f, 0.f};
     float m[4], l[4];
-#pragma unroll
-    for (int r = 0; r < 4; ++r) { m[r] = -1e30f; l[r] = 0.f; }
+    flash_acc_init(o, m, l);
     const int nt = (start + min(q0 + Q, n) - 1) / kFaK + 1;               // key tiles [0, nt): up to the block's last query's own key
     const int tps = (nt + S - 1) / S;
     const int t_lo = z * tps, t_end = min(nt, t_lo + tps);                // this split: tiles [t_lo, t_end), maybe none
@@ -630,17 +636,7 @@ __global__ __launch_bounds__(256) void flash_cont_merge_kernel(const float* ws, 
     out[(size_t)i * kHeadDim + d] = f_to_bf16(l > 0.f ? o / l : 0.f);
 }
 
-// key splits of a continuation: blocks x heads x S about half to one times the CU count (whole multiples of the blocks x heads grid,
-// rounded down), at least kFcMinTiles key tiles per split, at most kFcMaxSplit, and the records must fit the workspace.
-constexpr int kFcMinTiles = 4, kFcMaxSplit = 16;
-inline int flash_cont_splits(int start, int n, int NH, int n_cu, long ws_floats) {
-    const int nqb = (n + kFaQ - 1) / kFaQ, nt = (start + n + kFaK - 1) / kFaK;
-    int S = n_cu / (nqb * NH);
-    S = S < nt / kFcMinTiles ? S : nt / kFcMinTiles;
-    S = S < kFcMaxSplit ? S : kFcMaxSplit;
-    while (S > 1 && (long)S * n * NH * kFcRec > ws_floats) --S;
-    return S < 1 ? 1 : S;
-}
+constexpr int kFcMinTiles = 4, kFcMaxSplit = 16;       // key-split rule (flash_cont_pack_splits below): tiles per split at least, splits at most
 
 // ---------------------------------------------------------------------------------------------------------------------
 // Packed continuation prefill (fq3_prefill_continue_batch): n sequences, each with cnt[q] NEW rows behind its own cached rows
@@ -730,11 +726,8 @@ __global__ __launch_bounds__(256) void flash_prefill_cont_pack_kernel(const bf16
     for (int ks = 0; ks < 4; ++ks)
         qf[ks] = *reinterpret_cast<const bf16x8_t*>(qkv + (size_t)qrc * per * HD + (size_t)h * HD + ks * 32 + fq * 8);
     f32x4_t o[8];
-#pragma unroll
-    for (int d = 0; d < 8; ++d) o[d] = f32x4_t{0.f, 0.f, 0.f, 0.f};
     float m[4], l[4];
-#pragma unroll
-    for (int r = 0; r < 4; ++r) { m[r] = -1e30f; l[r] = 0.f; }
+    flash_acc_init(o, m, l);
     const int nt = (start + min(q0 + Q, n) - 1) / kFaK + 1;               // key tiles [0, nt): up to the block's last query's own key
     const int tps = (nt + S - 1) / S;
     const int t_lo = z * tps, t_end = min(nt, t_lo + tps);                // this split: tiles [t_lo, t_end), maybe none
@@ -817,9 +810,10 @@ inline long flash_cont_pack_ws_floats(const int* cnt, int n, int NH, const int* 
     return t;
 }
 
-// key splits of a packed continuation, a pure function of (start[], cnt[]) and the CU count: the CU budget is divided by the pack's
-// total query blocks x heads; per sequence at least kFcMinTiles key tiles per split and at most kFcMaxSplit; while the records of the
-// whole pack exceed the workspace the largest S (the first of equals) loses one.  A pack of one gives flash_cont_splits(start, n, ...).
+// key splits of a packed continuation, a pure function of (start[], cnt[]) and the CU count: blocks x heads x S about half to one times
+// the CU count -- the CU budget is divided by the pack's total query blocks x heads (whole multiples, rounded down); per sequence at
+// least kFcMinTiles key tiles per split and at most kFcMaxSplit; while the records of the whole pack exceed the workspace the largest S
+// (the first of equals) loses one.
 inline void flash_cont_pack_splits(const int* start, const int* cnt, int n, int NH, int n_cu, long ws_floats, int* S) {
     long nqb = 0;
     for (int q = 0; q < n; ++q) nqb += (cnt[q] + kFaQ - 1) / kFaQ;
@@ -835,6 +829,13 @@ inline void flash_cont_pack_splits(const int* start, const int* cnt, int n, int 
         for (int q = 1; q < n; ++q) big = S[q] > S[big] ? q : big;
         --S[big];                                        // > 1 here: records exist only where S > 1
     }
+}
+
+// the key splits of one prompt's continuation: the pack of one
+inline int flash_cont_splits(int start, int n, int NH, int n_cu, long ws_floats) {
+    int S;
+    flash_cont_pack_splits(&start, &n, 1, NH, n_cu, ws_floats, &S);
+    return S;
 }
 
 }  // namespace fq3

@@ -83,6 +83,10 @@ class FlacConfig(C.Structure):
     _fields_ = [("sample_rate", C.c_int), ("block_size", C.c_int)]
 
 
+class NoiseRing(C.Structure):
+    _fields_ = [("talker", vp), ("pred", vp), ("seed", C.c_uint64), ("first_frame", C.c_uint32), ("n_frames", i32)]
+
+
 class RefEncConfig(C.Structure):
     _fields_ = [("num_filters", i32), ("n_ratios", i32), ("ratios", i32 * 8), ("kernel_size", i32), ("last_kernel_size", i32),
                 ("residual_kernel_size", i32), ("n_residual_layers", i32), ("dilation_growth_rate", i32), ("compress", i32),
@@ -196,6 +200,9 @@ SIGNATURES = {
     "fq3_flac_destroy": (C.c_int, [vp]),
     "fq3_flac_reset": (C.c_int, [vp, vp]),
     "fq3_flac_push": (C.c_int, [vp, vp, C.c_int64, C.c_int, vp, C.c_int64, C.POINTER(C.c_int64), vp, vp]),
+    "fq3_noise_fill": (C.c_int, [vp, C.POINTER(NoiseRing), C.c_int, C.c_int, vp]),
+    "fq3_noise_first": (C.c_int, [vp, C.c_uint64, vp, vp]),
+    "fq3_noise_words": (C.c_int, [C.c_uint64, C.c_uint32, C.c_uint32, C.c_int, vp, vp]),
 }
 
 _lib = None

@@ -33,7 +33,7 @@ import torch
 
 from ._lib import FQ3_ENOMEM
 from .generate import (NOISE_RING, _arm_decode, _prefill_and_arm, _prefill_first_token, _prefill_first_tokens_launch,
-                       _prefill_first_tokens_packed, _refill)
+                       _prefill_first_tokens_packed, _refill, validate_seed)
 from .predictor_graph import PredictorGraph
 from .talker_graph import TalkerGraph
 
@@ -57,6 +57,9 @@ class BatchRequest:
     # the row the scheduler appends when the feeder is closed
     text_feeder: Any = None
     tts_eos_id: Optional[int] = None
+    # sampling seed (None: torch's global generator, as ever): the lane's noise is a pure function of (seed, emitted frame), so the codes
+    # do not depend on the lane, its neighbours or the order of admission
+    seed: Optional[int] = None
 
 
 @dataclass
@@ -88,6 +91,7 @@ class _Lane:
     first_batch: int = 0         # index of the first batch of frames queued after this tenant was armed (polls of earlier batches show its predecessor)
     copied: Any = None           # event: the last side-stream read of this lane's code buffer (a new tenant is armed after it)
     text: Optional[_TextLane] = None     # incremental text: `issued` then counts EMITTED frames (the host's model of the hold rule)
+    seed: Optional[int] = None   # the tenant's sampling seed (BatchRequest.seed); a new tenant starts again at frame 0
 
 
 @dataclass
@@ -222,10 +226,22 @@ class BatchDecoder:
             req.talker, req.talker_input_embeds, req.attention_mask, req.trailing_text_hiddens, req.tts_pad_embed,
             req.config, ln.predictor_graph, ln.talker_graph, kw["max_new_tokens"], kw["min_new_tokens"],
             kw["temperature"], kw["top_k"], kw["top_p"], kw["do_sample"], kw["repetition_penalty"], use_graph=False,
-            **({} if self.stages or self.prefix_cache is None else dict(cache=self.prefix_cache)))   # with spare contexts the cache lives on the side stream
+            **({} if self.stages or self.prefix_cache is None else dict(cache=self.prefix_cache)),   # with spare contexts the cache lives on the side stream
+            **self._seed_kw(req))
         ln.req, ln.tn, ln.pn, ln.issued, ln.emitted, ln.max_frames = req, tn, pn, 0, 0, max_frames
+        ln.seed = self._seed_of(req)
         ln.t_arm, ln.prefill_ms = t0, (time.time() - t0) * 1000
         self._open_text(ln)
+
+    @staticmethod
+    def _seed_of(req):
+        return validate_seed(getattr(req, "seed", None))
+
+    @classmethod
+    def _seed_kw(cls, req) -> Dict[str, Any]:
+        """``seed=`` for the generate.py helpers -- nothing at all for an unseeded request (the calls stay what they were)."""
+        seed = cls._seed_of(req)
+        return {} if seed is None else dict(seed=seed)
 
     def _open_text(self, ln: _Lane):
         """Right after ``decode_begin``: a text-fed request's lane gets an open table of ``max_frames + 1`` rows (frame g reads row
@@ -295,6 +311,13 @@ class BatchDecoder:
         taken = []
         host_toks = None
         ck = {} if self.prefix_cache is None else dict(cache=self.prefix_cache)      # (nothing changes in the calls while it is off)
+        seeds = [self._seed_of(req) for _st, req, _ev in group]
+
+        def sk(lo, hi=None):
+            """``seed=`` of members [lo, hi) for the packed helpers (a list), of member lo for the single one; nothing when none is seeded."""
+            if hi is None:
+                return {} if seeds[lo] is None else dict(seed=seeds[lo])
+            return {} if all(s is None for s in seeds[lo:hi]) else dict(seed=seeds[lo:hi])
 
         def reserve_all():
             # the KV blocks of every member's whole utterance (prompt + max_new_tokens + 1 slots, capped at max_seq_len) are taken
@@ -327,29 +350,29 @@ class BatchDecoder:
             for i, it in enumerate(items):
                 n = int(it[0].shape[1])
                 if i > lo and rows + n > cap:
-                    out += _prefill_first_tokens_launch(engines[lo:i], items[lo:i], cnt[lo:i], **ck)
+                    out += _prefill_first_tokens_launch(engines[lo:i], items[lo:i], cnt[lo:i], **ck, **sk(lo, i))
                     lo, rows = i, 0
                 rows += n
-            out += _prefill_first_tokens_launch(engines[lo:], items[lo:], cnt[lo:], **ck)
+            out += _prefill_first_tokens_launch(engines[lo:], items[lo:], cnt[lo:], **ck, **sk(lo, len(items)))
             return out
 
         def run():
             if defer:
                 return run_deferred()
             if len(group) == 1 or not self.packed_prefill:
-                return [_prefill_first_token(e, *it, **ck) for e, it in zip(engines, items)]
+                return [_prefill_first_token(e, *it, **ck, **sk(i)) for i, (e, it) in enumerate(zip(engines, items))]
             # packed prefills share the leading context's workspace (max_seq_len rows): split the group where the rows run out
             out, lo, rows = [], 0, 0
             cap = int(getattr(engines[0], "max_seq_len", 1 << 30))
             for i, it in enumerate(items):
                 n = int(it[0].shape[1])
                 if i > lo and rows + n > cap:
-                    out += (_prefill_first_tokens_packed(engines[lo:i], items[lo:i], **ck) if i - lo > 1
-                            else [_prefill_first_token(engines[lo], *items[lo], **ck)])
+                    out += (_prefill_first_tokens_packed(engines[lo:i], items[lo:i], **ck, **sk(lo, i)) if i - lo > 1
+                            else [_prefill_first_token(engines[lo], *items[lo], **ck, **sk(lo))])
                     lo, rows = i, 0
                 rows += n
-            out += (_prefill_first_tokens_packed(engines[lo:], items[lo:], **ck) if len(items) - lo > 1
-                    else [_prefill_first_token(engines[lo], *items[lo], **ck)])
+            out += (_prefill_first_tokens_packed(engines[lo:], items[lo:], **ck, **sk(lo, len(items))) if len(items) - lo > 1
+                    else [_prefill_first_token(engines[lo], *items[lo], **ck, **sk(lo))])
             return out
 
         try:
@@ -411,8 +434,9 @@ class BatchDecoder:
         _eng, tn, pn, max_frames = _arm_decode(
             req.talker, req.config, st.token, st.hidden, st.n_rows, req.attention_mask, req.trailing_text_hiddens, req.tts_pad_embed,
             ln.predictor_graph, ln.talker_graph, kw["max_new_tokens"], kw["min_new_tokens"], kw["temperature"], kw["top_k"],
-            kw["top_p"], kw["do_sample"], kw["repetition_penalty"], use_graph=False, n_pad=st.n_pad)
+            kw["top_p"], kw["do_sample"], kw["repetition_penalty"], use_graph=False, n_pad=st.n_pad, **self._seed_kw(req))
         ln.req, ln.tn, ln.pn, ln.issued, ln.emitted, ln.max_frames = req, tn, pn, 0, 0, max_frames
+        ln.seed = self._seed_of(req)
         ln.t_arm, ln.prefill_ms = st.t0, st.prefill_ms
         st.req, st.kw, st.hidden = None, None, None
         self._open_text(ln)
@@ -567,7 +591,7 @@ class BatchDecoder:
         self._polls.clear()
         self._unsynced = []                               # (first tokens an abandoned run left on the device: their stages are reset below)
         for ln in self.lanes:
-            ln.req, ln.tn, ln.pn, ln.issued, ln.emitted, ln.text = None, None, None, 0, 0, None
+            ln.req, ln.tn, ln.pn, ln.issued, ln.emitted, ln.text, ln.seed = None, None, None, 0, 0, None, None
         stats = self.text_stats = dict(iterations=0, frames_calls=0, appends=0, idle_waits=0, polls_held=0, polls_mixed=0, idle_closed=0,
                                        append_wait_n=0, append_wait_ms_sum=0.0, append_wait_ms_max=0.0)
         self._wake.clear()
@@ -859,16 +883,23 @@ class BatchDecoder:
                 need = [ln for ln in need if self._avail(ln) > ln.issued]
             if need:
                 step = self.poll_every
+                seeded = []                                           # seeded lanes at a ring boundary: ONE fill for all of them below
                 for ln in need:
                     if ln.text is None:
-                        if ln.issued % NOISE_RING == 0:
-                            _refill(ln.engine, ln.tn, ln.pn)
-                    elif ln.issued % NOISE_RING == 0 and ln.text.refilled_at != ln.issued:
+                        at_boundary = ln.issued % NOISE_RING == 0
+                    else:
                         # once per 64 EMITTED frames: every frame before the boundary is in front of this in the stream, and a lane
                         # that sat held on the boundary comes here once, when it can go on
+                        at_boundary = ln.issued % NOISE_RING == 0 and ln.text.refilled_at != ln.issued
+                        if at_boundary:
+                            ln.text.refilled_at = ln.issued
+                    if at_boundary and ln.seed is None:
                         _refill(ln.engine, ln.tn, ln.pn)
-                        ln.text.refilled_at = ln.issued
+                    elif at_boundary and (ln.tn is not None or ln.pn is not None):
+                        seeded.append((ln.engine, ln.tn, ln.pn, ln.seed, ln.issued, None))
                     step = min(step, NOISE_RING - ln.issued % NOISE_RING, max(ln.max_frames - ln.issued, 1))
+                if seeded:
+                    type(seeded[0][0]).noise_fill_many(seeded, NOISE_RING)
                 pull()                                                # stamp new arrivals before the frames are queued
                 self.batch.frames(step)
                 stats["frames_calls"] += 1

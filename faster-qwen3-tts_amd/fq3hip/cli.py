@@ -123,6 +123,13 @@ def _output_stage(model, args):
     return model.audio_output(rate, enc or "f32", 1.0 if speed is None else speed)
 
 
+def _seeded(model, args):
+    """``--seed``: the model's ``seeded`` context, or a no-op."""
+    import contextlib
+    seed = getattr(args, "seed", None)
+    return contextlib.nullcontext() if seed is None else model.seeded(seed)
+
+
 def _write_output(path, audio, sr, args):
     """float32 audio as 16-bit PCM (as ever); what the output stage encoded (int16, G.711 bytes, a FLAC stream) as it is."""
     import os
@@ -160,7 +167,7 @@ def cmd_once(args, model=None, lines=None):
         sys.exit(2)
     model = model or load_model(args)
     start = time.perf_counter()
-    with _output_stage(model, args):
+    with _output_stage(model, args), _seeded(model, args):
         audio, sr = synthesize_text_stream(model, args, _stdin_pieces(lines)) if text_stdin else synthesize(model, args, args.text)
     total = time.perf_counter() - start
     _write_output(args.output, audio, sr, args)
@@ -248,6 +255,8 @@ def build_parser():
         sp.add_argument("--speed", type=float, default=None, metavar="X",
                         help="speaking rate, 0.25 to 4.0, time-scaled on the device: duration changes, pitch does not (default: 1.0)")
         if output:
+            sp.add_argument("--seed", type=int, default=None, metavar="N",
+                            help="sampling seed in [0, 2^64): the same command gives the same audio (default: unseeded)")
             sp.add_argument("--text", required=not text_stdin)
             if text_stdin:
                 sp.add_argument("--text-stdin", action="store_true",

@@ -451,6 +451,50 @@ class Fq3Engine:
                                     self._stream()))
         return out
 
+    # ---- seeded sampling noise (csrc/noise_kernels.cuh: a row is a pure function of (seed, frame, slot)) ----
+    def _chk_ring(self, t: Optional[torch.Tensor], row: int, ring_frames: int, what: str):
+        if t is not None:
+            self._chk(t, ring_frames * row, what)
+
+    def noise_fill(self, talker_noise: Optional[torch.Tensor], pred_noise: Optional[torch.Tensor], seed: int, first_frame: int = 0,
+                   n_frames: Optional[int] = None, ring_frames: Optional[int] = None):
+        """Write rows ``(first_frame + j) % ring_frames``, ``j < n_frames``, of this context's noise rings with the seeded noise of
+        frames ``first_frame + j`` (``fq3_noise_fill``).  ``ring_frames`` defaults to the rings' first dimension, ``n_frames`` to the
+        whole ring."""
+        Fq3Engine.noise_fill_many([(self, talker_noise, pred_noise, seed, first_frame, n_frames)], ring_frames)
+
+    @staticmethod
+    def noise_fill_many(items, ring_frames: Optional[int] = None):
+        """``noise_fill`` for many lanes in one call (one launch per 32 lanes): ``items[i]`` = ``(engine, talker ring or None,
+        predictor ring or None, seed, first_frame, n_frames or None)``.  The engines share one shape, dtype and device; the rings one
+        ``ring_frames``."""
+        items = list(items)
+        if not items:
+            return
+        e0 = items[0][0]
+        if ring_frames is None:
+            ring_frames = next((int(t.shape[0]) for it in items for t in it[1:3] if t is not None), 1)
+        V, G1, Vp = e0.cfg.talker.vocab_size, e0.cfg.num_code_groups - 1, e0.cfg.predictor.vocab_size
+        arr = (L.NoiseRing * len(items))()
+        for r, (e, tn, pn, seed, first_frame, n_frames) in zip(arr, items):
+            if e.dtype != e0.dtype or e.device != e0.device or e.cfg is not e0.cfg and (
+                    e.cfg.talker.vocab_size, e.cfg.num_code_groups - 1, e.cfg.predictor.vocab_size) != (V, G1, Vp):
+                raise ValueError("noise_fill_many: the engines must share shape, dtype and device")
+            e._chk_ring(tn, V, ring_frames, "noise_fill talker ring")
+            e._chk_ring(pn, G1 * Vp, ring_frames, "noise_fill predictor ring")
+            r.talker, r.pred, r.seed = _ptr(tn), _ptr(pn), int(seed)
+            r.first_frame = int(first_frame) & 0xFFFFFFFF
+            r.n_frames = int(ring_frames if n_frames is None else n_frames)
+        L.check(e0.lib.fq3_noise_fill(e0.ctx, arr, len(items), int(ring_frames), e0._stream()))
+
+    def noise_first(self, seed: int, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """The seeded noise row of the first token after the prefill (``fq3_noise_first``): [V] in the context dtype."""
+        V = self.cfg.talker.vocab_size
+        out = out if out is not None else self.new(V)
+        self._chk(out, V, "noise_first out")
+        L.check(self.lib.fq3_noise_first(self.ctx, int(seed), out.data_ptr(), self._stream()))
+        return out
+
     # ---- fused on-device loop ----
     def decode_begin(self, *, first_token: int, prefill_len: int, gen_step: int, past_hidden: torch.Tensor,
                      trailing_text: torch.Tensor, tts_pad_embed: torch.Tensor, temperature: float, top_k: int,

@@ -23,6 +23,12 @@ logger = logging.getLogger(__name__)
 _GGML_ONLY = ("ref_spk", "ref_rvq", "ref_spk_emb", "ref_codes")
 
 
+def expand_seeds(seeds, n: int) -> list:
+    """``generate.expand_seeds`` (the ``seeds=`` keyword of the batch entry points), imported when first needed like the decode loops."""
+    from .generate import expand_seeds as expand
+    return expand(seeds, n)
+
+
 def _to_numpy(a) -> np.ndarray:
     if hasattr(a, "cpu"):
         return a.flatten().float().cpu().numpy()
@@ -407,6 +413,7 @@ class FasterQwen3TTS:
         self._warmed_up = False
         self._voice_prompt_cache: Dict[Any, Any] = {}
         self._audio_spec = None          # the AudioOutSpec of an open ``audio_output`` context
+        self._seed = None                # the sampling seed of an open ``seeded`` context
 
     # ---- small helpers pinned by the reference's unit tests ------------------------------------------------
     @staticmethod
@@ -866,6 +873,28 @@ class FasterQwen3TTS:
         finally:
             self._audio_spec = prev
 
+    # ---- reproducible sampling (opt-in) ------------------------------------------------------------------------------
+    @contextlib.contextmanager
+    def seeded(self, seed: Optional[int]):
+        """Context manager: inside it the single-stream entry points (``generate_*``, ``generate_*_streaming``, ``stream_*``) sample
+        with ``seed`` (an integer in [0, 2^64); ``ValueError`` otherwise): the sampling noise is a pure function of (seed, frame)
+        generated on the device, so the same request gives the same codes -- streaming or not, at any chunk size, whole or incremental
+        text.  Iterate a streaming generator inside the context.  With ``do_sample=False`` the talker's greedy choice ignores the seed; a
+        code predictor that still samples (``predictor_graph.do_sample``) draws its codebooks from it.  The ``*_batch`` entry points
+        take ``seeds=`` instead.  Not re-entrant across threads, like the rest of the model.  Outside it nothing changes."""
+        from .generate import validate_seed
+        seed = validate_seed(seed)
+        prev, self._seed = getattr(self, "_seed", None), seed
+        try:
+            yield seed
+        finally:
+            self._seed = prev
+
+    def _seed_kw(self) -> dict:
+        """``seed=`` for the decode loops inside ``seeded`` -- nothing at all outside it (the calls stay what they were)."""
+        seed = getattr(self, "_seed", None)
+        return {} if seed is None else dict(seed=seed)
+
     def _refuse_batch_audio_output(self) -> None:
         if getattr(self, "_audio_spec", None) is not None:
             raise ValueError("the batch entry points decode their audio in groups and do not run the audio output stage: call them outside "
@@ -902,7 +931,7 @@ class FasterQwen3TTS:
         codec_ids, timing = fast_generate(talker=talker, talker_input_embeds=tie, attention_mask=tam,
                                           trailing_text_hiddens=tth, tts_pad_embed=tpe, config=config,
                                           predictor_graph=self.predictor_graph, talker_graph=self.talker_graph,
-                                          **gen_kwargs)
+                                          **gen_kwargs, **self._seed_kw())
         if codec_ids is None:
             logger.warning("Generation returned no tokens")
             if self._audio_spec is not None:
@@ -983,7 +1012,7 @@ class FasterQwen3TTS:
         fn = parity_generate_streaming if parity_mode else fast_generate_streaming
         stream = fn(talker=talker, talker_input_embeds=tie, attention_mask=tam, trailing_text_hiddens=tth,
                     tts_pad_embed=tpe, config=config, predictor_graph=self.predictor_graph,
-                    talker_graph=self.talker_graph, chunk_size=chunk_size, **gen_kwargs)
+                    talker_graph=self.talker_graph, chunk_size=chunk_size, **gen_kwargs, **self._seed_kw())
         timing = None
         for chunk, timing in stream:
             ev = timing.pop("codes_ready_event", None)
@@ -1089,11 +1118,12 @@ class FasterQwen3TTS:
             self._side_voc_stream = self._vocoder_stream(tok) or concurrent_stream(self.device)
         return _SideVocoder(tok, self.device, getattr(self, "_side_voc_stream", None))
 
-    def _batch_feed(self, prepared, gen_kwargs, lanes: int, meta: dict, first_wave: Optional[int] = None):
+    def _batch_feed(self, prepared, gen_kwargs, lanes: int, meta: dict, first_wave: Optional[int] = None, seeds=None):
         """``prepared``: an iterable (usually a generator: the prompt of utterance i is built when the scheduler asks for it) of
         ``(talker, config, tie, tam, tth, tpe, ref_codes | None)``.  Returns ``(head, source)`` for ``BatchDecoder.run``: the first
         ``lanes`` requests up front -- the first wave starts decoding before the later prompts exist -- and a ``source`` callback
-        that prepares the rest one at a time at frame boundaries.  ``meta[i]`` receives the entry's ``ref_codes``."""
+        that prepares the rest one at a time at frame boundaries.  ``meta[i]`` receives the entry's ``ref_codes``.  ``seeds``: one
+        sampling seed or None per entry (``generate.expand_seeds``)."""
         from .batching import BatchRequest
         it = enumerate(prepared)
 
@@ -1103,7 +1133,7 @@ class FasterQwen3TTS:
                 return None
             i, (talker, config, tie, tam, tth, tpe, rc) = nxt
             meta[i] = rc
-            return BatchRequest(i, talker, tie, tam, tth, tpe, config, dict(gen_kwargs))
+            return BatchRequest(i, talker, tie, tam, tth, tpe, config, dict(gen_kwargs), seed=None if seeds is None else seeds[i])
 
         # (only the first SLICE of the first wave is built here: the scheduler pulls the rest from `source` in slices and queues every
         # slice's packed prefill behind the one before, so prompt builds and prefills overlap -- BatchDecoder.run, "first wave, pipelined")
@@ -1116,17 +1146,18 @@ class FasterQwen3TTS:
             head.append(r)
         return head, pull
 
-    def _run_batch_full(self, prepared, gen_kwargs, lanes: int, count: int) -> List[Tuple[list, int]]:
+    def _run_batch_full(self, prepared, gen_kwargs, lanes: int, count: int, seeds=None) -> List[Tuple[list, int]]:
         """The lock-step decode of ``count`` prepared utterances (see :meth:`_batch_feed`) through ``lanes`` lanes, every finished
         utterance vocoded on the side stream (the reference's share of an ICL waveform is cut by not producing it,
         model.py:927-930).  One ``([waveform], sample_rate)`` per entry, in input order."""
         self._refuse_batch_audio_output()
+        seeds = expand_seeds(seeds, count)
         meta: dict = {}
         dec = self._batch_decoder(lanes)
         # batch_first_wave (attribute): requests prepared + prefilled + armed before the first frame is queued (BatchDecoder.first_wave);
         # None = one per lane
         dec.first_wave = getattr(self, "batch_first_wave", None)
-        head, source = self._batch_feed(prepared, gen_kwargs, len(dec.lanes), meta, dec.first_wave)
+        head, source = self._batch_feed(prepared, gen_kwargs, len(dec.lanes), meta, dec.first_wave, seeds)
         out: List[Optional[Tuple[list, int]]] = [None] * count
         voc = self._side_vocoder()
         # batch_vocode_every (attribute; default 0 = vocode an utterance when it has ended; N > 0 = produce the waveform in slices every N
@@ -1160,7 +1191,8 @@ class FasterQwen3TTS:
             out[rid] = ([a], voc.sample_rate)
         return out
 
-    def _run_batch_streaming(self, prepared, gen_kwargs, chunk_size: int, lanes: int, rounds=None, stamp=None):
+    def _run_batch_streaming(self, prepared, gen_kwargs, chunk_size: int, lanes: int, rounds=None, stamp=None, seeds=None,
+                             count: Optional[int] = None):
         """Streaming form of :meth:`_run_batch_full`: yields ``(index, audio_chunk, sample_rate, timing)`` for every
         ``chunk_size`` frames of any utterance -- per utterance exactly the chunks the single-utterance streaming entry point
         would produce (same windowing state machine).  ``timing``: ``chunk_index``, ``total_steps_so_far``, ``is_final``.
@@ -1168,6 +1200,12 @@ class FasterQwen3TTS:
         successive scheduler runs instead of the one pair :meth:`_batch_feed` makes of ``prepared``; ``stamp(index, timing)`` may add
         keys to a chunk's timing before it goes out."""
         self._refuse_batch_audio_output()
+        if seeds is not None:
+            # the ``seeds=`` keyword of the public entry points is expanded HERE and in _run_batch_full, nowhere else; a caller that
+            # builds its own requests (``rounds``) seeds them itself
+            if rounds is not None or count is None:
+                raise ValueError("seeds= goes with `prepared` and its `count`; requests made by `rounds` carry their own seed")
+            seeds = expand_seeds(seeds, count)
         meta: dict = {}
         vocs, n_chunks = {}, {}
         dec = self._batch_decoder(lanes)
@@ -1176,7 +1214,7 @@ class FasterQwen3TTS:
         # first wave does not buy its members a lower latency -- the prefills of the followers run beside their first frames and
         # stretch them (128 lanes: p25 305 ms / p50 395 ms at a wave of 32 against 340 ms for everybody at once) -- so the default stays.
         dec.first_wave = getattr(self, "batch_first_wave_streaming", None)
-        pairs = rounds(dec, meta) if rounds is not None else [self._batch_feed(prepared, gen_kwargs, len(dec.lanes), meta, dec.first_wave)]
+        pairs = rounds(dec, meta) if rounds is not None else [self._batch_feed(prepared, gen_kwargs, len(dec.lanes), meta, dec.first_wave, seeds)]
         tok = self.model.model.speech_tokenizer
         side = self._vocoder_stream(tok)
         batched = side is not None and hasattr(tok, "decode_tensor_batch")
@@ -1302,7 +1340,7 @@ class FasterQwen3TTS:
                                    non_streaming_mode: Optional[bool] = None, append_silence: bool = True,
                                    instruct: Optional[str] = None,
                                    voice_clone_prompt: Optional[Union[Dict[str, Any], List[Any]]] = None,
-                                   lanes: int = 8) -> List[Tuple[list, int]]:
+                                   lanes: int = 8, seeds=None) -> List[Tuple[list, int]]:
         """Voice cloning of several texts with one voice: up to ``lanes`` (<= 128) utterances decode in lock-step over
         one pass of the weights per frame (``fq3_batch_*``), finished lanes are refilled from the queue.  Returns one
         ``([np.float32 waveform], sample_rate)`` per text, in input order; each utterance follows exactly the
@@ -1311,7 +1349,7 @@ class FasterQwen3TTS:
         prepared = self._prepare_clone_batch(texts, language, ref_audio, ref_text, xvec_only, nsm, append_silence, instruct,
                                              voice_clone_prompt)
         return self._run_batch_full(prepared, self._gen_kwargs(max_new_tokens, min_new_tokens, temperature, top_k, top_p, do_sample,
-                                                               repetition_penalty), lanes, len(texts))
+                                                               repetition_penalty), lanes, len(texts), seeds=seeds)
 
     @torch.inference_mode()
     def generate_voice_clone_batch_streaming(self, texts: List[str], language: Union[str, List[str]] = "English",
@@ -1322,7 +1360,7 @@ class FasterQwen3TTS:
                                              non_streaming_mode: Optional[bool] = None, append_silence: bool = True,
                                              instruct: Optional[str] = None,
                                              voice_clone_prompt: Optional[Union[Dict[str, Any], List[Any]]] = None,
-                                             lanes: int = 8) -> Generator[Tuple[int, np.ndarray, int, dict], None, None]:
+                                             lanes: int = 8, seeds=None) -> Generator[Tuple[int, np.ndarray, int, dict], None, None]:
         """Streaming AND batched: the texts decode in lock-step lanes (as :meth:`generate_voice_clone_batch`) and every
         ``chunk_size`` frames of any utterance yield ``(text_index, audio_chunk, sample_rate, timing)`` -- per utterance
         exactly the chunks :meth:`generate_voice_clone_streaming` would produce for it (same windowing state machine).
@@ -1331,7 +1369,8 @@ class FasterQwen3TTS:
         prepared = self._prepare_clone_batch(texts, language, ref_audio, ref_text, xvec_only, nsm, append_silence, instruct,
                                              voice_clone_prompt)
         yield from self._run_batch_streaming(prepared, self._gen_kwargs(max_new_tokens, min_new_tokens, temperature, top_k, top_p,
-                                                                         do_sample, repetition_penalty), chunk_size, lanes)
+                                                                         do_sample, repetition_penalty), chunk_size, lanes,
+                                             seeds=seeds, count=len(texts))
 
     def _prepare_custom_batch(self, texts, speaker, language, instruct, non_streaming_mode):
         n = len(texts)
@@ -1352,14 +1391,14 @@ class FasterQwen3TTS:
                                     instruct: Optional[Union[str, List[Optional[str]]]] = None,
                                     non_streaming_mode: Optional[bool] = None, max_new_tokens: int = 2048, min_new_tokens: int = 2,
                                     temperature: float = 0.9, top_k: int = 50, top_p: float = 1.0, do_sample: bool = True,
-                                    repetition_penalty: float = 1.05, lanes: int = 16) -> List[Tuple[list, int]]:
+                                    repetition_penalty: float = 1.05, lanes: int = 16, seeds=None) -> List[Tuple[list, int]]:
         """CustomVoice for several texts (BASELINE configs[3]: many concurrent utterances of a CustomVoice model): every
         utterance is prepared exactly like :meth:`generate_custom_voice` (speaker-id prompt, model.py:1139-1326; ``speaker`` /
         ``language`` / ``instruct`` may be one value or one per text) and up to ``lanes`` of them decode in lock-step over one pass of
         the weights per frame.  Returns one ``([waveform], sample_rate)`` per text, in input order."""
         prepared = self._prepare_custom_batch(texts, speaker, language, instruct, non_streaming_mode)
         return self._run_batch_full(prepared, self._gen_kwargs(max_new_tokens, min_new_tokens, temperature, top_k, top_p, do_sample,
-                                                               repetition_penalty), lanes, len(texts))
+                                                               repetition_penalty), lanes, len(texts), seeds=seeds)
 
     @torch.inference_mode()
     def generate_custom_voice_batch_streaming(self, texts: List[str], speaker: Union[str, List[str]],
@@ -1368,21 +1407,22 @@ class FasterQwen3TTS:
                                               non_streaming_mode: Optional[bool] = None, max_new_tokens: int = 2048,
                                               min_new_tokens: int = 2, temperature: float = 0.9, top_k: int = 50, top_p: float = 1.0,
                                               do_sample: bool = True, repetition_penalty: float = 1.05, chunk_size: int = 12,
-                                              lanes: int = 16) -> Generator[Tuple[int, np.ndarray, int, dict], None, None]:
+                                              lanes: int = 16, seeds=None) -> Generator[Tuple[int, np.ndarray, int, dict], None, None]:
         """Streaming form of :meth:`generate_custom_voice_batch`: ``(text_index, audio_chunk, sample_rate, timing)`` per chunk."""
         prepared = self._prepare_custom_batch(texts, speaker, language, instruct, non_streaming_mode)
         yield from self._run_batch_streaming(prepared, self._gen_kwargs(max_new_tokens, min_new_tokens, temperature, top_k, top_p,
-                                                                         do_sample, repetition_penalty), chunk_size, lanes)
+                                                                         do_sample, repetition_penalty), chunk_size, lanes,
+                                             seeds=seeds, count=len(texts))
 
     @torch.inference_mode()
     def generate_voice_design_batch(self, texts: List[str], instruct: Union[str, List[str]], language: Union[str, List[str]] = "English",
                                     non_streaming_mode: Optional[bool] = None, max_new_tokens: int = 2048, min_new_tokens: int = 2,
                                     temperature: float = 0.9, top_k: int = 50, top_p: float = 1.0, do_sample: bool = True,
-                                    repetition_penalty: float = 1.05, lanes: int = 16) -> List[Tuple[list, int]]:
+                                    repetition_penalty: float = 1.05, lanes: int = 16, seeds=None) -> List[Tuple[list, int]]:
         """VoiceDesign for several texts in lock-step lanes; every utterance prepared like :meth:`generate_voice_design`."""
         return self._run_batch_full(self._prepare_design_batch(texts, instruct, language, non_streaming_mode),
                                     self._gen_kwargs(max_new_tokens, min_new_tokens, temperature, top_k, top_p, do_sample, repetition_penalty),
-                                    lanes, len(texts))
+                                    lanes, len(texts), seeds=seeds)
 
     def _prepare_design_batch(self, texts, instruct, language, non_streaming_mode):
         n = len(texts)
@@ -1402,11 +1442,12 @@ class FasterQwen3TTS:
                                               language: Union[str, List[str]] = "English", non_streaming_mode: Optional[bool] = None,
                                               max_new_tokens: int = 2048, min_new_tokens: int = 2, temperature: float = 0.9,
                                               top_k: int = 50, top_p: float = 1.0, do_sample: bool = True, repetition_penalty: float = 1.05,
-                                              chunk_size: int = 12, lanes: int = 16) -> Generator[Tuple[int, np.ndarray, int, dict], None, None]:
+                                              chunk_size: int = 12, lanes: int = 16, seeds=None) -> Generator[Tuple[int, np.ndarray, int, dict], None, None]:
         """Streaming form of :meth:`generate_voice_design_batch`: ``(text_index, audio_chunk, sample_rate, timing)`` per chunk."""
         prepared = self._prepare_design_batch(texts, instruct, language, non_streaming_mode)
         yield from self._run_batch_streaming(prepared, self._gen_kwargs(max_new_tokens, min_new_tokens, temperature, top_k, top_p,
-                                                                         do_sample, repetition_penalty), chunk_size, lanes)
+                                                                         do_sample, repetition_penalty), chunk_size, lanes,
+                                             seeds=seeds, count=len(texts))
 
     @torch.inference_mode()
     def generate_voice_clone_streaming(self, text: str, language: str, ref_audio: Optional[Union[str, Path]] = None,
@@ -1555,7 +1596,7 @@ class FasterQwen3TTS:
             stream = fast_generate_text_streaming(
                 talker=talker, talker_input_embeds=tie, attention_mask=tam, tts_pad_embed=tpe, config=config,
                 predictor_graph=self.predictor_graph, talker_graph=self.talker_graph, feeder=feeder,
-                tts_eos_id=int(m.config.tts_eos_token_id), chunk_size=chunk_size, **gen_kwargs)
+                tts_eos_id=int(m.config.tts_eos_token_id), chunk_size=chunk_size, **gen_kwargs, **self._seed_kw())
             timing = None
             for chunk, timing in stream:
                 ev = timing.pop("codes_ready_event", None)
@@ -1647,19 +1688,20 @@ class FasterQwen3TTS:
             if getattr(ln.engine, "_prompt_keep", None) is None:
                 ln.engine.bind_prompt_weights(*keep)
 
-    def text_batch_request(self, rid, feeder, prepare, gen_kwargs):
+    def text_batch_request(self, rid, feeder, prepare, gen_kwargs, seed=None):
         """The scheduler's request for a text stream whose first token exists: the step-by-step prompt around that token, an empty
         trailing table, the feeder for every later token.  ``prepare(input_ids)`` is the voice's prompt builder."""
         from .batching import BatchRequest
         m, talker, config, tie, tam, _tth, tpe = prepare(self._text_session_ids(feeder))
         return BatchRequest(rid, talker, tie, tam, tie.new_zeros(1, 0, tie.shape[-1]), tpe, config, dict(gen_kwargs),
-                            text_feeder=feeder, tts_eos_id=int(m.config.tts_eos_token_id))
+                            text_feeder=feeder, tts_eos_id=int(m.config.tts_eos_token_id), seed=seed)
 
-    def _run_text_batch_streaming(self, text_iters, prepares, gen_kwargs, chunk_size: int, lanes: int):
+    def _run_text_batch_streaming(self, text_iters, prepares, gen_kwargs, chunk_size: int, lanes: int, seeds=None):
         """Shared back half of the ``stream_*_batch`` entry points.  A request enters the scheduler when its first token exists;
         streams whose first token has not arrived wait beside it and do not block the others."""
         import threading
         from collections import deque
+        seeds = expand_seeds(seeds, len(text_iters))
         feeders = self._text_feeders(text_iters)
         arrived = threading.Event()
         for f in feeders:
@@ -1675,7 +1717,7 @@ class FasterQwen3TTS:
                     n, closed = feeders[i].pending()
                     if n or closed:                             # (closed and empty: _text_session_ids raises, as the single stream does)
                         meta[i] = None
-                        return self.text_batch_request(i, feeders[i], prepares[i], gen_kwargs)
+                        return self.text_batch_request(i, feeders[i], prepares[i], gen_kwargs, seed=seeds[i])
                     waiting.append(i)
                 return None
 
@@ -1697,7 +1739,7 @@ class FasterQwen3TTS:
                                   instruct: Optional[Union[str, List[Optional[str]]]] = None, chunk_size: int = 12,
                                   max_new_tokens: int = 2048, min_new_tokens: int = 2, temperature: float = 0.9, top_k: int = 50,
                                   top_p: float = 1.0, do_sample: bool = True, repetition_penalty: float = 1.05,
-                                  lanes: int = 16) -> Generator[Tuple[int, np.ndarray, int, dict], None, None]:
+                                  lanes: int = 16, seeds=None) -> Generator[Tuple[int, np.ndarray, int, dict], None, None]:
         """``generate_custom_voice_batch_streaming(..., non_streaming_mode=False)`` for texts that are still arriving: every element of
         ``text_iters`` is an iterable of ``str`` pieces or a ``TextFeeder`` (an LLM's token stream per utterance), and up to ``lanes``
         of them decode in lock-step while their text comes in.  Yields ``(index, audio_chunk, sample_rate, timing)``; per utterance the
@@ -1713,13 +1755,13 @@ class FasterQwen3TTS:
             return lambda input_ids: self._custom_prepare(None, spk, lang, ins, False, input_ids=input_ids)
         yield from self._run_text_batch_streaming(text_iters, [prep(*a) for a in zip(spks, langs, inss)],
                                                   self._gen_kwargs(max_new_tokens, min_new_tokens, temperature, top_k, top_p, do_sample,
-                                                                   repetition_penalty), chunk_size, lanes)
+                                                                   repetition_penalty), chunk_size, lanes, seeds=seeds)
 
     @torch.inference_mode()
     def stream_voice_design_batch(self, text_iters, instruct: Union[str, List[str]], language: Union[str, List[str]] = "English",
                                   chunk_size: int = 12, max_new_tokens: int = 2048, min_new_tokens: int = 2, temperature: float = 0.9,
                                   top_k: int = 50, top_p: float = 1.0, do_sample: bool = True, repetition_penalty: float = 1.05,
-                                  lanes: int = 16) -> Generator[Tuple[int, np.ndarray, int, dict], None, None]:
+                                  lanes: int = 16, seeds=None) -> Generator[Tuple[int, np.ndarray, int, dict], None, None]:
         """``generate_voice_design_batch_streaming(..., non_streaming_mode=False)`` for texts that are still arriving (see
         :meth:`stream_custom_voice_batch`)."""
         n = len(text_iters)
@@ -1732,7 +1774,7 @@ class FasterQwen3TTS:
             return lambda input_ids: self._design_prepare(None, ins, lang, False, input_ids=input_ids)
         yield from self._run_text_batch_streaming(text_iters, [prep(*a) for a in zip(inss, langs)],
                                                   self._gen_kwargs(max_new_tokens, min_new_tokens, temperature, top_k, top_p, do_sample,
-                                                                   repetition_penalty), chunk_size, lanes)
+                                                                   repetition_penalty), chunk_size, lanes, seeds=seeds)
 
     @torch.inference_mode()
     def stream_voice_clone_batch(self, text_iters, language: Union[str, List[str]] = "English",
@@ -1741,7 +1783,7 @@ class FasterQwen3TTS:
                                  do_sample: bool = True, repetition_penalty: float = 1.05, xvec_only: bool = True,
                                  append_silence: bool = True, instruct: Optional[str] = None,
                                  voice_clone_prompt: Optional[Union[Dict[str, Any], List[Any]]] = None,
-                                 lanes: int = 16) -> Generator[Tuple[int, np.ndarray, int, dict], None, None]:
+                                 lanes: int = 16, seeds=None) -> Generator[Tuple[int, np.ndarray, int, dict], None, None]:
         """``generate_voice_clone_batch_streaming(..., non_streaming_mode=False)`` for texts that are still arriving, one x-vector-only
         voice for all of them.  An ICL voice is refused with the message of :meth:`stream_voice_clone`."""
         why = self._refuse_icl_text_stream(xvec_only, voice_clone_prompt)
@@ -1758,4 +1800,4 @@ class FasterQwen3TTS:
             return prepare
         yield from self._run_text_batch_streaming(text_iters, [prep(l) for l in langs],
                                                   self._gen_kwargs(max_new_tokens, min_new_tokens, temperature, top_k, top_p, do_sample,
-                                                                   repetition_penalty), chunk_size, lanes)
+                                                                   repetition_penalty), chunk_size, lanes, seeds=seeds)

@@ -52,6 +52,10 @@ class SpeechRequest(BaseModel):
     # extension: the device audio output stage (fq3hip/audio_out.py).  Both absent: 16-bit PCM at the model's rate, as ever
     sample_rate: Optional[int] = None      # Hz, e.g. 8000, 16000, 44100, 48000
     encoding: Optional[str] = None         # s16 | mulaw | alaw (f32 is answered as s16)
+    # extension: reproducible sampling.  An integer in [0, 2^64): the same request with the same seed gives the same audio, whatever
+    # else the server is doing (the noise is a pure function of (seed, frame)); the reply carries X-Seed.
+    # Absent: unseeded, as ever
+    seed: Optional[int] = None
 
 
 class SessionRequest(BaseModel):
@@ -60,6 +64,7 @@ class SessionRequest(BaseModel):
     speed: float = 1.0                     # as in SpeechRequest
     sample_rate: Optional[int] = None
     encoding: Optional[str] = None
+    seed: Optional[int] = None             # as in SpeechRequest
 
 
 class SessionText(BaseModel):
@@ -152,7 +157,8 @@ class BatchWorker:
                         waiting[i] = (out, m.streaming_vocoder(rc, self.chunk_size) if spec is None else
                                       m.streaming_vocoder(rc, self.chunk_size, output=spec))
                         kw = m._gen_kwargs(int(cfg.get("max_new_tokens", 2048)), 2, 0.9, 50, 1.0, True, 1.05)
-                        return BatchRequest(i, talker, tie, tam, tth, tpe, config, kw)
+                        seed_kw = {} if cfg.get("seed") is None else dict(seed=cfg["seed"])     # (unseeded: the call stays what it was)
+                        return BatchRequest(i, talker, tie, tam, tth, tpe, config, kw, **seed_kw)
 
                     def prepare_text(item):
                         """A text session: parked until its first token exists, then a request built around that token."""
@@ -177,7 +183,8 @@ class BatchWorker:
                         try:
                             m._bind_lane_prompt_weights(m._batch_decoder(self.lanes))
                             kw = m._gen_kwargs(int(cfg.get("max_new_tokens", 2048)), 2, 0.9, 50, 1.0, True, 1.05)
-                            req = m.text_batch_request(i, feeder, build, kw)
+                            seed_kw = {} if cfg.get("seed") is None else dict(seed=cfg["seed"])
+                            req = m.text_batch_request(i, feeder, build, kw, **seed_kw)
                         except Exception as exc:
                             out.put(exc)
                             out.put(self.DONE)
@@ -298,6 +305,19 @@ def create_app(model, voices: Dict[str, dict], default_voice: Optional[str] = No
         except ValueError as exc:
             raise HTTPException(status_code=400, detail=str(exc))
 
+    def request_seed(req) -> Optional[int]:
+        """The request's seed, or None; 400 outside [0, 2^64)."""
+        if req.seed is None:
+            return None
+        from .generate import validate_seed
+        try:
+            return validate_seed(req.seed)
+        except ValueError as exc:
+            raise HTTPException(status_code=400, detail=str(exc))
+
+    def seed_headers(seed: Optional[int]) -> Optional[dict]:
+        return None if seed is None else {"X-Seed": str(seed)}
+
     def clone_kwargs(cfg: dict, text: str) -> dict:
         return dict(text=text, language=cfg.get("language", "Auto"), ref_audio=cfg.get("ref_audio"), ref_text=cfg.get("ref_text", ""),
                     voice_clone_prompt=cfg.get("voice_clone_prompt"))
@@ -311,7 +331,8 @@ def create_app(model, voices: Dict[str, dict], default_voice: Optional[str] = No
 
         def producer():
             try:
-                with lock, (contextlib.nullcontext() if spec is None else model.audio_output(spec.sample_rate, spec.encoding, spec.speed)):
+                with lock, (contextlib.nullcontext() if spec is None else model.audio_output(spec.sample_rate, spec.encoding, spec.speed)), \
+                        (contextlib.nullcontext() if cfg.get("seed") is None else model.seeded(cfg["seed"])):
                     for chunk, _sr, _t in model.generate_voice_clone_streaming(chunk_size=cfg.get("chunk_size", 12),
                                                                                non_streaming_mode=False, **clone_kwargs(cfg, text), **instruct_kw):
                         q.put(chunk)
@@ -330,7 +351,7 @@ def create_app(model, voices: Dict[str, dict], default_voice: Optional[str] = No
                 raise item
             yield to_pcm16(item) if spec is None else np.ascontiguousarray(item).tobytes()
 
-    async def box_response(box, fmt: str, on_end=None, spec=None):
+    async def box_response(box, fmt: str, on_end=None, spec=None, seed=None):
         """The streaming body of a batch-scheduler reply queue (``BatchWorker.submit`` / ``submit_text``)."""
         loop = asyncio.get_event_loop()
 
@@ -372,7 +393,7 @@ def create_app(model, voices: Dict[str, dict], default_voice: Optional[str] = No
                 if on_end is not None:
                     on_end()
 
-        return StreamingResponse(replay(), media_type=CONTENT_TYPES[fmt])
+        return StreamingResponse(replay(), media_type=CONTENT_TYPES[fmt], headers=seed_headers(seed))
 
     # ---- text sessions: the text arrives in pieces while the audio is already streaming (batch scheduler) -----------------------
     def drop_session(sid: str):
@@ -401,6 +422,9 @@ def create_app(model, voices: Dict[str, dict], default_voice: Optional[str] = No
         spec = request_spec(req, fmt)
         if spec is not None:
             cfg = dict(cfg, audio_output=spec)
+        seed = request_seed(req)
+        if seed is not None:
+            cfg = dict(cfg, seed=seed)
         try:
             from .model import FasterQwen3TTS
             FasterQwen3TTS._refuse_icl_text_stream(True, cfg.get("voice_clone_prompt"))
@@ -414,8 +438,9 @@ def create_app(model, voices: Dict[str, dict], default_voice: Optional[str] = No
             # sessions nobody ever read: their text ended (the client's `final`, or the scheduler's idle rule) long ago
             for old in [k for k, s in sessions.items() if not s["reading"] and s["feeder"].closed and now - s["t_closed"] > 60.0]:
                 sessions.pop(old, None)
-            sessions[sid] = dict(feeder=feeder, box=worker.submit_text(cfg, feeder), fmt=fmt, reading=False, t_closed=now, spec=spec)
-        return {"id": sid}
+            sessions[sid] = dict(feeder=feeder, box=worker.submit_text(cfg, feeder), fmt=fmt, reading=False, t_closed=now, spec=spec,
+                                 seed=seed)
+        return {"id": sid} if seed is None else {"id": sid, "seed": seed}
 
     @app.post("/v1/audio/speech/sessions/{sid}/text")
     async def session_text(sid: str, req: SessionText):
@@ -437,7 +462,7 @@ def create_app(model, voices: Dict[str, dict], default_voice: Optional[str] = No
             if s["reading"]:
                 raise HTTPException(status_code=409, detail="this session's audio is being read already")
             s["reading"] = True
-        return await box_response(s["box"], s["fmt"], on_end=lambda: drop_session(sid), spec=s["spec"])
+        return await box_response(s["box"], s["fmt"], on_end=lambda: drop_session(sid), spec=s["spec"], seed=s.get("seed"))
 
     @app.get("/health")
     async def health():
@@ -459,8 +484,12 @@ def create_app(model, voices: Dict[str, dict], default_voice: Optional[str] = No
         if fmt == "mp3":
             raise HTTPException(status_code=400, detail="response_format='mp3' needs pydub + ffmpeg, which this image does not ship; use wav or pcm")
         spec = request_spec(req, fmt)
+        seed = request_seed(req)
+        if seed is not None:
+            cfg = dict(cfg, seed=seed)
         if worker is not None:
-            return await box_response(worker.submit(cfg if spec is None else dict(cfg, audio_output=spec), req.input), fmt, spec=spec)
+            return await box_response(worker.submit(cfg if spec is None else dict(cfg, audio_output=spec), req.input), fmt, spec=spec,
+                                      seed=seed)
 
         async def audio_stream():
             if fmt == "wav":
@@ -469,7 +498,7 @@ def create_app(model, voices: Dict[str, dict], default_voice: Optional[str] = No
             async for raw in stream_chunks(cfg, req.input, spec):
                 yield raw
 
-        return StreamingResponse(audio_stream(), media_type=CONTENT_TYPES[fmt])
+        return StreamingResponse(audio_stream(), media_type=CONTENT_TYPES[fmt], headers=seed_headers(seed))
 
     return app
 

@@ -27,7 +27,7 @@ from typing import Callable, Generator, Iterable, List, Optional, Tuple
 
 import torch
 
-from .generate import NOISE_RING, _prefill_and_arm, _refill
+from .generate import NOISE_RING, _prefill_and_arm, _refill, validate_seed
 
 
 class TextFeeder:
@@ -146,8 +146,9 @@ class TextSession:
     the table is closed: ``capacity = max_frames + 1`` rows are more than the loop can read (frame ``g`` reads row ``g < max_frames``).
     """
 
-    def __init__(self, eng, feeder: TextFeeder, eos_id: int, capacity: int, talker_noise=None, pred_noise=None, refill=_refill):
+    def __init__(self, eng, feeder: TextFeeder, eos_id: int, capacity: int, talker_noise=None, pred_noise=None, refill=_refill, seed=None):
         self.eng, self.feeder, self.eos_id, self.capacity = eng, feeder, int(eos_id), int(capacity)
+        self.seed = seed                         # a seeded session refills with the emitted-frame count (= issued: the gate below)
         self.tn, self.pn, self._refill = talker_noise, pred_noise, refill
         self.rows, self.closed, self.issued, self.refills = 0, False, 0, 0
 
@@ -173,7 +174,10 @@ class TextSession:
     def _launch(self, count: int):
         while count > 0:
             if self.issued % NOISE_RING == 0:
-                self._refill(self.eng, self.tn, self.pn)
+                if self.seed is None:
+                    self._refill(self.eng, self.tn, self.pn)
+                else:
+                    self._refill(self.eng, self.tn, self.pn, self.seed, self.issued)
                 self.refills += 1
             k = min(count, NOISE_RING - self.issued % NOISE_RING)
             self.eng.decode_frames(k)
@@ -200,20 +204,21 @@ def fast_generate_text_streaming(talker, talker_input_embeds, attention_mask, tt
                                  feeder: TextFeeder, tts_eos_id: int, max_new_tokens: int = 2048, min_new_tokens: int = 2,
                                  temperature: float = 0.9, top_k: int = 50, top_p: float = 1.0, do_sample: bool = True,
                                  repetition_penalty: float = 1.05, chunk_size: int = 12,
-                                 use_graph: bool = True) -> Generator[Tuple[torch.Tensor, dict], None, None]:
+                                 use_graph: bool = True, seed=None) -> Generator[Tuple[torch.Tensor, dict], None, None]:
     """``fast_generate_streaming`` for a text that is still arriving.  ``talker_input_embeds`` is the step-by-step prompt (it ends
     with the first text token against ``codec_bos``); ``feeder`` yields the ids of every LATER text token; the session appends
     ``tts_eos_id`` itself when the feeder is closed, as ``prompt.py`` ends the trailing table.  Yields ``(codes, timing)`` with the
     same keys, the same ``is_final`` rule and the same look-ahead of one chunk; the first chunk's timing also has ``first_text_ms``
     (first piece received -> first chunk's codes) when the feeder noted a first piece."""
+    seed = validate_seed(seed)
     t_start = time.time()
     H = talker_input_embeds.shape[-1]
     empty = talker_input_embeds.new_zeros(1, 0, H)
     eng, tn, pn, max_frames = _prefill_and_arm(
         talker, talker_input_embeds, attention_mask, empty, tts_pad_embed, config, predictor_graph, talker_graph, max_new_tokens,
-        min_new_tokens, temperature, top_k, top_p, do_sample, repetition_penalty, use_graph=use_graph)
+        min_new_tokens, temperature, top_k, top_p, do_sample, repetition_penalty, use_graph=use_graph, seed=seed)
     eng.decode_text_open(max_frames + 1)
-    sess = TextSession(eng, feeder, tts_eos_id, max_frames + 1, tn, pn)
+    sess = TextSession(eng, feeder, tts_eos_id, max_frames + 1, tn, pn, seed=seed)
     torch.cuda.current_stream(eng.device).synchronize()
     t_prefill = time.time() - t_start
     emitted, chunk_count = 0, 0

@@ -611,6 +611,44 @@ int fq3_flac_reset(fq3_flac* f, void* stream);
 int fq3_flac_push(fq3_flac* f, const int16_t* pcm, int64_t n_in, int final, uint8_t* out, int64_t capacity_bytes,
                   int64_t* n_frames, int64_t* n_bytes_dev, void* stream);
 
+/* ---- Seeded sampling noise: the samplers' Exp(1) variates from a counter-based generator on the device -------------------------
+ * The samplers divide by host-provided noise (fq3_sample's noise vector, the rings of fq3_decode_begin).  These calls fill such
+ * buffers as a PURE FUNCTION of (seed, emitted-frame index, slot, vocabulary index): no state, no dependence on lane, batch
+ * composition, ring size or how the calls are cut.  The contract -- a seed printed today gives the same noise after any later change:
+ *   generator   Philox4x32-10: multipliers 0xD2511F53 / 0xCD9E8D57, key increments 0x9E3779B9 / 0xBB67AE85
+ *   key         (seed & 0xffffffff, seed >> 32)
+ *   counter     (v >> 2, frame, slot, 0); vocabulary index v takes output word v & 3
+ *   frame       the emitted-frame index (the loop state's `frame`): talker and predictor samplers of a frame read ring row
+ *               frame % noise_frames
+ *   slot        0: the talker's row; 1 + cb: predictor codebook cb in 0 .. G-2; 0xFFFFFFFF with frame 0: the first token after the prefill
+ *   variate     k = word >> 9; u = (2 k + 1) 2^-24; e = -ln(u) in fp64, rounded once to fp32 (nearest even) and, in a bf16 context,
+ *               once more to bf16.  Range [5.96e-8, 16.64]: strictly positive and finite in both storage types.
+ * Known answers:
+ *   Philox   counter 0,0,0,0 key 0,0 -> 6627e8d5 e169c58d bc57ac4c 9b00dbd8;  counter and key all ffffffff -> 408f276d 41c83b0e
+ *            a20bc7c6 6d5451fd;  counter 243f6a88 85a308d3 13198a2e 03707344, key a4093822 299f31d0 -> d16cfe09 94fdcceb 5001e420 24126ea1
+ *   seed 1234, frame 0, slot 0, v = 0..7:  words 2090b348 da7cf0ab 4401906f cbca470e 9eeede35 1cbe137c fa277093 147edd50;  fp32 variates
+ *            2.0619323 0.15844612 1.3255798 0.22808668 0.47669414 2.1868014 0.02310045 2.524969 = bits 4003f6b3 3e223fb3 3fa9ac99
+ *            3e698f8e 3ef41141 400bf48e 3cbd3d25 40219918
+ *   seed 1234, first token (slot 0xFFFFFFFF, frame 0), v = 0..3:  words ab2cfba4 d35d7331 f3a5f4c3 79a03acc;  fp32 variates 0.4024869
+ *            0.19159077 0.04945178 0.7442275 = bits 3ece12c3 3e44305f 3d4a8df2 3f3e85b2 */
+typedef struct fq3_noise_ring {
+    void* talker;               /* T[ring_frames][V] or NULL */
+    void* pred;                 /* T[ring_frames][G-1][Vp] or NULL */
+    uint64_t seed;
+    uint32_t first_frame;       /* emitted-frame index of the first row written */
+    int32_t n_frames;           /* rows written: 0 .. ring_frames */
+} fq3_noise_ring;
+/* Writes, for every i < n and j < rings[i].n_frames, ring row (first_frame + j) % ring_frames of rings[i] with the noise of frame
+ * first_frame + j; no other row is touched.  T, V, G and Vp come from ctx's config (ctx is not otherwise used: the rings may belong
+ * to any contexts of that shape).  One launch per 32 rings.  All or nothing, checked before anything is queued: FQ3_EINVAL for a NULL
+ * ctx or one without a config, NULL rings with n > 0, n < 0, ring_frames < 1, n_frames outside [0, ring_frames], a misaligned ring. */
+int fq3_noise_fill(fq3_ctx* ctx, const fq3_noise_ring* rings, int n, int ring_frames, void* stream);
+/* out: T[V], the first-token row (slot 0xFFFFFFFF, frame 0) */
+int fq3_noise_first(fq3_ctx* ctx, uint64_t seed, void* out, void* stream);
+/* Conformance hook: the raw Philox words of one row, out[v] = word v & 3 of counter (v >> 2, frame, slot, 0), for any V >= 1
+ * (device uint32[V]).  Needs no context. */
+int fq3_noise_words(uint64_t seed, uint32_t frame, uint32_t slot, int V, uint32_t* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -83,6 +83,10 @@ class FlacConfig(C.Structure):
     _fields_ = [("sample_rate", C.c_int), ("block_size", C.c_int)]
 
 
+class JoinConfig(C.Structure):
+    _fields_ = [("in_rate", C.c_int), ("threshold", C.c_float), ("lead_hops", C.c_int), ("tail_hops", C.c_int), ("hold_hops", C.c_int)]
+
+
 class NoiseRing(C.Structure):
     _fields_ = [("talker", vp), ("pred", vp), ("seed", C.c_uint64), ("first_frame", C.c_uint32), ("n_frames", i32)]
 
@@ -200,6 +204,11 @@ SIGNATURES = {
     "fq3_flac_destroy": (C.c_int, [vp]),
     "fq3_flac_reset": (C.c_int, [vp, vp]),
     "fq3_flac_push": (C.c_int, [vp, vp, C.c_int64, C.c_int, vp, C.c_int64, C.POINTER(C.c_int64), vp, vp]),
+    "fq3_join_bound": (C.c_int64, [C.POINTER(JoinConfig), C.c_int64, C.c_int64]),
+    "fq3_join_create": (C.c_int, [C.POINTER(JoinConfig), C.POINTER(vp)]),
+    "fq3_join_destroy": (C.c_int, [vp]),
+    "fq3_join_reset": (C.c_int, [vp, vp]),
+    "fq3_join_push": (C.c_int, [vp, vp, C.c_int64, C.c_int, C.c_int64, vp, C.c_int64, vp, vp]),
     "fq3_noise_fill": (C.c_int, [vp, C.POINTER(NoiseRing), C.c_int, C.c_int, vp]),
     "fq3_noise_first": (C.c_int, [vp, C.c_uint64, vp, vp]),
     "fq3_noise_words": (C.c_int, [C.c_uint64, C.c_uint32, C.c_uint32, C.c_int, vp, vp]),

@@ -93,6 +93,20 @@ def synthesize_text_stream(model, args, pieces):
 def synthesize(model, args, text: str):
     """One text -> (waveform, sample_rate) in the selected mode (``cli.py:81-225``)."""
     kw = _gen_kwargs(args)
+    if getattr(args, "long", False) and args.mode in ("clone", "custom"):
+        from .long_form import LongFormSpec
+        lkw = dict(lanes=args.lanes, long_form=LongFormSpec(max_chars=args.max_chars), **kw)
+        if args.mode == "clone":
+            lkw.update(text=text, language=args.language, ref_audio=args.ref_audio, ref_text=args.ref_text, xvec_only=args.xvec_only,
+                       non_streaming_mode=args.non_streaming_mode)
+            name = "generate_long_voice_clone"
+        else:
+            lkw.update(text=text, speaker=args.speaker, language=args.language, instruct=args.instruct)
+            name = "generate_long_custom_voice"
+        if args.streaming:
+            return _stream_to_audio(getattr(model, name + "_streaming")(chunk_size=args.chunk_size, **lkw))
+        audio_list, sr = getattr(model, name)(**lkw)
+        return audio_list[0], sr
     if args.mode == "clone":
         ckw = dict(text=text, language=args.language, ref_audio=args.ref_audio, ref_text=args.ref_text, xvec_only=args.xvec_only,
                    non_streaming_mode=args.non_streaming_mode, **kw)
@@ -277,11 +291,17 @@ def build_parser():
                         help="keep the talker K/V rows of instruct turns on the device, up to N rows, and prefill only the rest of a "
                              "prompt whose instruct is cached (default 0: off; the server honours it under both schedulers)")
 
+    def long_form_flags(sp):
+        sp.add_argument("--long", action="store_true",
+                        help="long form: cut the text into segments, decode them side by side and join them on the device into one stream")
+        sp.add_argument("--max-chars", type=int, default=240, metavar="N", help="--long: the splitter's budget per segment")
+        sp.add_argument("--lanes", type=int, default=16, metavar="N", help="--long: segments decoded side by side")
+
     c = sub.add_parser("clone", help="voice cloning from reference audio")
-    common(c); clone_refs(c); c.set_defaults(mode="clone", func=cmd_once)
+    common(c); clone_refs(c); long_form_flags(c); c.set_defaults(mode="clone", func=cmd_once)
     c = sub.add_parser("custom", help="CustomVoice model: predefined speaker")
     common(c, text_stdin=True); c.add_argument("--speaker"); c.add_argument("--instruct"); c.set_defaults(mode="custom", func=cmd_once)
-    prefix_cache_flag(c)
+    prefix_cache_flag(c); long_form_flags(c)
     c = sub.add_parser("design", help="VoiceDesign model: voice from an instruction")
     common(c, text_stdin=True); c.add_argument("--instruct"); c.set_defaults(mode="design", func=cmd_once)
     prefix_cache_flag(c)

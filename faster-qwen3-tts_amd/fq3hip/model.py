@@ -51,6 +51,7 @@ class _SideVocoder:
             stream = concurrent_stream(self.dev)               # verified to run beside the decode stream (fq3hip/streams.py)
         self.stream = stream if self.async_ok else None
         self.items: list = []
+        self.device_only = False          # long form: the waveforms stay on the device (``collect_device``), no pinned-host copies
 
     def _prefix(self, ref):
         """the tokenizer's cached front-end state of an ICL reference (built on the vocoder stream), or None"""
@@ -73,8 +74,10 @@ class _SideVocoder:
         pf = self._prefix(ref) if ref_len > 0 else None
         with torch.cuda.stream(self.stream):
             pcm = self.tok.decode_tensor(codes, cut, prefix=pf) if pf is not None else self.tok.decode_tensor(codes, cut)
-            host = torch.empty(pcm.shape, dtype=torch.float32, pin_memory=True)
-            host.copy_(pcm, non_blocking=True)
+            host = None
+            if not self.device_only:
+                host = torch.empty(pcm.shape, dtype=torch.float32, pin_memory=True)
+                host.copy_(pcm, non_blocking=True)
             ev = torch.cuda.Event()
             ev.record(self.stream)
         self.items.append((key, host, ev, pcm))          # pcm kept alive until its copy has completed
@@ -122,12 +125,14 @@ class _SideVocoder:
                 with torch.cuda.stream(self.stream):
                     stacked = torch.stack([c for _k, c, _r in part])
                     pcm = self.tok.decode_tensor_batch(stacked, cut, prefixes=pfs) if pfs is not None else self.tok.decode_tensor_batch(stacked, cut)
-                    host = torch.empty(pcm.shape, dtype=torch.float32, pin_memory=True)
-                    host.copy_(pcm, non_blocking=True)
+                    host = None
+                    if not self.device_only:
+                        host = torch.empty(pcm.shape, dtype=torch.float32, pin_memory=True)
+                        host.copy_(pcm, non_blocking=True)
                     ev = torch.cuda.Event()
                     ev.record(self.stream)
                 for j, (key, _c, _r) in enumerate(part):
-                    self.items.append((key, host[j], ev, pcm))
+                    self.items.append((key, host[j] if host is not None else None, ev, pcm[j]))
 
     # ---- incremental (exact) vocoding of utterances that are still decoding ------------------------------------------------
     # The codec decoder is causal: decode(codes[:p]) is bit for bit the prefix of decode(codes), and a tail decode from sample s is
@@ -227,6 +232,13 @@ class _SideVocoder:
             else:
                 ev.synchronize()
                 yield key, host.numpy().copy()
+        self.items = []
+
+    def collect_device(self):
+        """``device_only``: -> (key, waveform) in submission order, the waveform a float32 tensor still on the device, valid on
+        ``self.stream`` without a wait (a host array for a tokenizer that is decoded synchronously)."""
+        for key, host, ev, pcm in self.items:
+            yield key, (host if ev is None else pcm.flatten().float())
         self.items = []
 
 
@@ -1146,11 +1158,14 @@ class FasterQwen3TTS:
             head.append(r)
         return head, pull
 
-    def _run_batch_full(self, prepared, gen_kwargs, lanes: int, count: int, seeds=None) -> List[Tuple[list, int]]:
+    def _run_batch_full(self, prepared, gen_kwargs, lanes: int, count: int, seeds=None, device_audio: bool = False) -> List[Tuple[list, int]]:
         """The lock-step decode of ``count`` prepared utterances (see :meth:`_batch_feed`) through ``lanes`` lanes, every finished
         utterance vocoded on the side stream (the reference's share of an ICL waveform is cut by not producing it,
-        model.py:927-930).  One ``([waveform], sample_rate)`` per entry, in input order."""
-        self._refuse_batch_audio_output()
+        model.py:927-930).  One ``([waveform], sample_rate)`` per entry, in input order.  ``device_audio`` (internal, long form): the
+        waveforms are handed out as device tensors valid on the side vocoder's stream -- ``(out, voc)`` is returned -- and the caller
+        runs the output chain itself."""
+        if not device_audio:
+            self._refuse_batch_audio_output()
         seeds = expand_seeds(seeds, count)
         meta: dict = {}
         dec = self._batch_decoder(lanes)
@@ -1160,13 +1175,14 @@ class FasterQwen3TTS:
         head, source = self._batch_feed(prepared, gen_kwargs, len(dec.lanes), meta, dec.first_wave, seeds)
         out: List[Optional[Tuple[list, int]]] = [None] * count
         voc = self._side_vocoder()
+        voc.device_only = bool(device_audio)
         # batch_vocode_every (attribute; default 0 = vocode an utterance when it has ended; N > 0 = produce the waveform in slices every N
         # frames while the utterance still decodes -- exact, see _SideVocoder.inc_add -- so that what is left at the end is the last slice
         # only).  Measured on MI355X (profiles/r04_batch_e2e_vocode_every_*.txt): the slices contend with the latency-bound lock-step
         # frames for more than they save at the end -- 64 lanes x 128 utterances, 0.6B: 561x at 0, 537x at 64, 552x at 100; 1.7B: 458x vs
         # 443x -- so it is OFF by default; a server whose lanes finish at different times has nothing to gain from it either.
         inc = int(getattr(self, "batch_vocode_every", 0) or 0)
-        if inc > 0 and voc.async_ok and hasattr(voc.tok, "decode_tensor_batch") and hasattr(voc.tok, "num_samples_total"):
+        if inc > 0 and not device_audio and voc.async_ok and hasattr(voc.tok, "decode_tensor_batch") and hasattr(voc.tok, "num_samples_total"):
             max_new = min(int(gen_kwargs.get("max_new_tokens", 2048)), int(self.talker_graph.engine.max_frames))
             for rid, codes, info in dec.run(head, source=source, chunk_frames=inc):
                 more = int(getattr(dec, "more_in_poll", 0))
@@ -1187,19 +1203,26 @@ class FasterQwen3TTS:
             # together (equal lengths: one batched launch set)
             voc.add(rid, codes, ref_len=rc.shape[0] if rc is not None else 0, more=more, ref=rc)
         voc.add_flush()
+        if device_audio:
+            for rid, a in voc.collect_device():
+                out[rid] = ([a], voc.sample_rate)
+            return out, voc
         for rid, a in voc.collect():
             out[rid] = ([a], voc.sample_rate)
         return out
 
     def _run_batch_streaming(self, prepared, gen_kwargs, chunk_size: int, lanes: int, rounds=None, stamp=None, seeds=None,
-                             count: Optional[int] = None):
+                             count: Optional[int] = None, device_audio: bool = False):
         """Streaming form of :meth:`_run_batch_full`: yields ``(index, audio_chunk, sample_rate, timing)`` for every
         ``chunk_size`` frames of any utterance -- per utterance exactly the chunks the single-utterance streaming entry point
         would produce (same windowing state machine).  ``timing``: ``chunk_index``, ``total_steps_so_far``, ``is_final``.
         ``rounds`` (incremental text, :meth:`_run_text_batch_streaming`): ``rounds(dec, meta)`` yields the ``(head, source)`` pairs of
         successive scheduler runs instead of the one pair :meth:`_batch_feed` makes of ``prepared``; ``stamp(index, timing)`` may add
-        keys to a chunk's timing before it goes out."""
-        self._refuse_batch_audio_output()
+        keys to a chunk's timing before it goes out.  ``device_audio`` (internal, long form; what is yielded by default does not
+        change): a chunk vocoded on the vocoder stream is handed out as the group's device waveform row -- a float32 tensor valid on
+        that stream, no copy to the host, no wait -- and the utterances' vocoders carry no output stage of their own."""
+        if not device_audio:
+            self._refuse_batch_audio_output()
         if seeds is not None:
             # the ``seeds=`` keyword of the public entry points is expanded HERE and in _run_batch_full, nowhere else; a caller that
             # builds its own requests (``rounds``) seeds them itself
@@ -1245,10 +1268,12 @@ class FasterQwen3TTS:
                     stacked = torch.stack([j[3][0] for j in part])
                     wav = tok.decode_tensor_batch(stacked, first, prefixes=pfs) if pfs else tok.decode_tensor_batch(stacked, first)
                 wav = wav.float()
-                host = torch.empty(wav.shape, dtype=wav.dtype, pin_memory=True)
-                host.copy_(wav, non_blocking=True)
-                landed = torch.cuda.Event()
-                landed.record(side)
+                host = landed = None
+                if not device_audio:
+                    host = torch.empty(wav.shape, dtype=wav.dtype, pin_memory=True)
+                    host.copy_(wav, non_blocking=True)
+                    landed = torch.cuda.Event()
+                    landed.record(side)
             queued.append((part, host, landed, wav))
 
         def launch_open():
@@ -1271,9 +1296,12 @@ class FasterQwen3TTS:
             plain = [j for j in jobs if j[3] is None]
             jobs[:] = []
             groups, queued[:] = list(queued), []
-            for part, host, landed, _wav in groups:
-                landed.synchronize()
-                arr = host.numpy()
+            for part, host, landed, wav in groups:
+                if landed is None:
+                    arr = wav                                      # device rows: whoever takes them works on the vocoder stream
+                else:
+                    landed.synchronize()
+                    arr = host.numpy()
                 for k, j in enumerate(part):
                     j[2] = arr[k]
                 yield from part
@@ -1287,7 +1315,9 @@ class FasterQwen3TTS:
         for head, source in pairs:
           for rid, codes, info in dec.run(head, source=source, chunk_frames=chunk_size):
             if rid not in vocs:
-                vocs[rid], n_chunks[rid] = self.streaming_vocoder(meta[rid], chunk_size), 0
+                vocs[rid] = (StreamingVocoder(tok, meta[rid], chunk_size, self.device, side) if device_audio
+                             else self.streaming_vocoder(meta[rid], chunk_size))
+                n_chunks[rid] = 0
             ev = info.pop("codes_ready_event", None)
             final = bool(info.get("is_final"))
             more = int(getattr(dec, "more_in_poll", 0))
@@ -1533,6 +1563,150 @@ class FasterQwen3TTS:
         yield from self._run_streaming(m, talker, config, tie, tam, tth, tpe, None,
                                        self._gen_kwargs(max_new_tokens, min_new_tokens, temperature, top_k, top_p,
                                                         do_sample, repetition_penalty), chunk_size)
+
+    # ---- long form (extension: a text of any length; fq3hip/long_form.py) --------------------------------
+    def _long_setup(self, text, long_form):
+        """-> (LongFormSpec, segments): every argument error before anything is prepared or decoded"""
+        from .long_form import LongFormSpec
+        spec = LongFormSpec() if long_form is None else long_form
+        if not isinstance(spec, LongFormSpec):
+            raise ValueError(f"long_form must be a LongFormSpec or None, not {type(long_form).__name__}")
+        if getattr(self.model.model, "tts_model_type", None) == "voice_design":
+            raise ValueError("long form is not offered for voice-design models: every segment would sample its own voice from the "
+                             "description, so the voice would change between segments (use a clone or a custom voice)")
+        if not isinstance(text, str) or not text.strip():
+            raise ValueError("long form needs a text that is not empty")
+        segs = spec.split(text)
+        # the join stage's own range checks (host only), so that they too surface before the decode
+        from .long_form import join_bound
+        join_bound(self.sample_rate, spec.threshold, spec.lead_hops, spec.tail_hops, spec.hold_hops, 0, 0)
+        return spec, segs
+
+    def _long_chain(self, spec, segs, stream):
+        """The request's ONE output stream: the join stage and, inside ``audio_output``, the chain behind it, all on ``stream``."""
+        from .long_form import OrderedJoin, SegmentJoin
+        dev = torch.device(self.device) if not isinstance(self.device, torch.device) else self.device
+        join = SegmentJoin.from_spec(spec, self.sample_rate, dev, stream=stream)
+        chain = None
+        if self._audio_spec is not None:
+            from .audio_out import AudioOut
+            chain = AudioOut(self._audio_spec, self.sample_rate, join.dev, stream)
+        pauses = [spec.pause_samples(s.pause, self.sample_rate) for s in segs]
+        return OrderedJoin(join, pauses, chain), chain
+
+    def _run_long_full(self, prepared, segs, spec, gen_kwargs, lanes: int) -> Tuple[list, int]:
+        """The segments as the requests of one lock-step run, whole waveforms kept on the device, joined in text order on the side
+        vocoder's stream, then (inside ``audio_output``) through the one-shot output stage as ONE utterance."""
+        n = len(segs)
+        outs, voc = self._run_batch_full(prepared, gen_kwargs, lanes, n, seeds=getattr(self, "_seed", None), device_audio=True)
+        oj, _chain = self._long_chain(spec, segs, voc.stream)
+        oj.audio_out = None                                         # the whole stream goes through _one_shot_output below
+        parts = []
+        with (torch.cuda.stream(voc.stream) if voc.stream is not None else contextlib.nullcontext()):
+            for k, (wavs, _sr) in enumerate(outs):
+                w = wavs[0]
+                w = w if torch.is_tensor(w) else torch.from_numpy(np.ascontiguousarray(w, dtype=np.float32)).to(oj.join.dev)
+                parts.extend(y for _k, y, _e in oj.feed(k, w, True))
+            pcm = torch.cat(parts) if parts else torch.zeros(0, dtype=torch.float32, device=oj.join.dev)
+            if self._audio_spec is not None:
+                a, sr = self._one_shot_output(pcm)
+                return [a], sr
+            return [pcm.cpu().numpy()], self.sample_rate
+
+    def _run_long_streaming(self, prepared, segs, spec, gen_kwargs, chunk_size: int, lanes: int):
+        """Streaming form: the chunks of the lanes' utterances stay device tensors on the vocoder stream; the chunks of segment k + 1
+        wait until segment k has ended; what leaves is one stream in text order.  Segment 0 streams as it decodes."""
+        n = len(segs)
+        tok = self.model.model.speech_tokenizer
+        side = self._vocoder_stream(tok)
+        oj, chain = self._long_chain(spec, segs, side)
+        sr = chain.out_rate if chain is not None else self.sample_rate
+        header = chain is not None and chain.flac
+        index = 0
+        ctx = (lambda: torch.cuda.stream(side)) if side is not None else contextlib.nullcontext
+        for rid, audio, _sr, tm in self._run_batch_streaming(prepared, gen_kwargs, chunk_size, lanes,
+                                                             seeds=getattr(self, "_seed", None), count=n, device_audio=True):
+            with ctx():
+                pcm = audio if torch.is_tensor(audio) else torch.from_numpy(np.ascontiguousarray(audio, dtype=np.float32)).to(oj.join.dev)
+                pieces = [(k, y.cpu().numpy(), ended) for k, y, ended in oj.feed(rid, pcm, bool(tm.get("is_final")))]
+            for k, host, ended in pieces:
+                if host.size == 0 and not ended:
+                    continue                                       # a chunk the join stage removed whole (or holds back)
+                if header:
+                    host, header = np.concatenate([np.frombuffer(chain.header(), dtype=np.uint8), host]), False
+                yield host, sr, dict(segment_index=k, n_segments=n, chunk_index=index, is_final=ended,
+                                     total_steps_so_far=int(tm.get("total_steps_so_far", 0)))
+                index += 1
+
+    @torch.inference_mode()
+    def generate_long_voice_clone(self, text: str, language: str, ref_audio: Optional[Union[str, Path]] = None,
+                                  ref_text: str = "", max_new_tokens: int = 2048, min_new_tokens: int = 2,
+                                  temperature: float = 0.9, top_k: int = 50, top_p: float = 1.0, do_sample: bool = True,
+                                  repetition_penalty: float = 1.05, xvec_only: bool = False,
+                                  non_streaming_mode: Optional[bool] = None, append_silence: bool = True,
+                                  instruct: Optional[str] = None, ref_spk: Optional[Union[str, Path]] = None,
+                                  ref_rvq: Optional[Union[str, Path]] = None, ref_spk_emb: Optional[np.ndarray] = None,
+                                  ref_codes: Optional[np.ndarray] = None,
+                                  voice_clone_prompt: Optional[Union[Dict[str, Any], List[Any]]] = None,
+                                  lanes: int = 16, long_form=None) -> Tuple[list, int]:
+        """Voice cloning of a text of any length: ``long_form`` (a ``LongFormSpec``; None: the defaults) cuts it into segments, up to
+        ``lanes`` of them decode side by side (``max_new_tokens`` is per segment), and their waveforms are joined on the device --
+        leading and trailing silence removed, a pause per boundary -- into one ``([waveform], sample_rate)``.  Works inside
+        ``audio_output`` (one stream: join -> time-scale -> resample / encode -> FLAC; pauses scale with ``speed``) and ``seeded``
+        (segment i samples with seed + i)."""
+        self._reject_ggml_cached_reference_args(ref_spk=ref_spk, ref_rvq=ref_rvq, ref_spk_emb=ref_spk_emb, ref_codes=ref_codes)
+        spec, segs = self._long_setup(text, long_form)
+        nsm = self._resolve_non_streaming_mode(non_streaming_mode, default=False)
+        prepared = self._prepare_clone_batch([s.text for s in segs], language, ref_audio, ref_text, xvec_only, nsm, append_silence,
+                                             instruct, voice_clone_prompt)
+        return self._run_long_full(prepared, segs, spec, self._gen_kwargs(max_new_tokens, min_new_tokens, temperature, top_k, top_p,
+                                                                          do_sample, repetition_penalty), lanes)
+
+    @torch.inference_mode()
+    def generate_long_voice_clone_streaming(self, text: str, language: str, ref_audio: Optional[Union[str, Path]] = None,
+                                            ref_text: str = "", max_new_tokens: int = 2048, min_new_tokens: int = 2,
+                                            temperature: float = 0.9, top_k: int = 50, top_p: float = 1.0, do_sample: bool = True,
+                                            repetition_penalty: float = 1.05, chunk_size: int = 12, xvec_only: bool = False,
+                                            non_streaming_mode: Optional[bool] = None, append_silence: bool = True,
+                                            instruct: Optional[str] = None, ref_spk: Optional[Union[str, Path]] = None,
+                                            ref_rvq: Optional[Union[str, Path]] = None, ref_spk_emb: Optional[np.ndarray] = None,
+                                            ref_codes: Optional[np.ndarray] = None,
+                                            voice_clone_prompt: Optional[Union[Dict[str, Any], List[Any]]] = None,
+                                            lanes: int = 16, long_form=None) -> Generator[Tuple[np.ndarray, int, dict], None, None]:
+        """Streaming form of :meth:`generate_long_voice_clone`: yields ``(audio_chunk, sample_rate, timing)`` strictly in text order;
+        ``timing``: ``segment_index``, ``n_segments``, ``chunk_index``, ``is_final``."""
+        self._reject_ggml_cached_reference_args(ref_spk=ref_spk, ref_rvq=ref_rvq, ref_spk_emb=ref_spk_emb, ref_codes=ref_codes)
+        spec, segs = self._long_setup(text, long_form)
+        nsm = self._resolve_non_streaming_mode(non_streaming_mode, default=False)
+        prepared = self._prepare_clone_batch([s.text for s in segs], language, ref_audio, ref_text, xvec_only, nsm, append_silence,
+                                             instruct, voice_clone_prompt)
+        yield from self._run_long_streaming(prepared, segs, spec, self._gen_kwargs(max_new_tokens, min_new_tokens, temperature, top_k,
+                                                                                   top_p, do_sample, repetition_penalty), chunk_size, lanes)
+
+    @torch.inference_mode()
+    def generate_long_custom_voice(self, text: str, speaker: str, language: str, instruct: Optional[str] = None,
+                                   non_streaming_mode: Optional[bool] = None, max_new_tokens: int = 2048,
+                                   min_new_tokens: int = 2, temperature: float = 0.9, top_k: int = 50, top_p: float = 1.0,
+                                   do_sample: bool = True, repetition_penalty: float = 1.05, lanes: int = 16,
+                                   long_form=None) -> Tuple[list, int]:
+        """CustomVoice for a text of any length; see :meth:`generate_long_voice_clone`."""
+        spec, segs = self._long_setup(text, long_form)
+        prepared = self._prepare_custom_batch([s.text for s in segs], speaker, language, instruct, non_streaming_mode)
+        return self._run_long_full(prepared, segs, spec, self._gen_kwargs(max_new_tokens, min_new_tokens, temperature, top_k, top_p,
+                                                                          do_sample, repetition_penalty), lanes)
+
+    @torch.inference_mode()
+    def generate_long_custom_voice_streaming(self, text: str, speaker: str, language: str, instruct: Optional[str] = None,
+                                             non_streaming_mode: Optional[bool] = None, max_new_tokens: int = 2048,
+                                             min_new_tokens: int = 2, temperature: float = 0.9, top_k: int = 50,
+                                             top_p: float = 1.0, do_sample: bool = True, repetition_penalty: float = 1.05,
+                                             chunk_size: int = 12, lanes: int = 16,
+                                             long_form=None) -> Generator[Tuple[np.ndarray, int, dict], None, None]:
+        """Streaming form of :meth:`generate_long_custom_voice`."""
+        spec, segs = self._long_setup(text, long_form)
+        prepared = self._prepare_custom_batch([s.text for s in segs], speaker, language, instruct, non_streaming_mode)
+        yield from self._run_long_streaming(prepared, segs, spec, self._gen_kwargs(max_new_tokens, min_new_tokens, temperature, top_k,
+                                                                                   top_p, do_sample, repetition_penalty), chunk_size, lanes)
 
     # ---- incremental text (extension: the reference takes the whole text before it starts; fq3hip/text_stream.py) ---------
     @staticmethod

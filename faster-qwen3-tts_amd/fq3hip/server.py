@@ -56,6 +56,10 @@ class SpeechRequest(BaseModel):
     # else the server is doing (the noise is a pure function of (seed, frame)); the reply carries X-Seed.
     # Absent: unseeded, as ever
     seed: Optional[int] = None
+    # extension: long-form synthesis (fq3hip/long_form.py; lock scheduler).  true: the text is cut into segments
+    # that decode side by side and are joined on the device into ONE stream; absent: taken when the text is longer than the
+    # splitter's budget (max_chars); false: never.  The reply carries X-Segments
+    long_form: Optional[bool] = None
 
 
 class SessionRequest(BaseModel):
@@ -250,13 +254,16 @@ class BatchWorker:
 
 
 def create_app(model, voices: Dict[str, dict], default_voice: Optional[str] = None, scheduler: str = "lock", lanes: int = 8,
-               chunk_size: int = 12, worker=None, prefix_cache_rows: int = 0):
+               chunk_size: int = 12, worker=None, prefix_cache_rows: int = 0, long_form=None):
     """``worker``: a ready ``BatchWorker`` (or a stand-in with ``submit`` / ``submit_text``) instead of the one ``scheduler="batch"``
     would start.  ``prefix_cache_rows`` > 0: the model's prefix KV cache (``FasterQwen3TTS.enable_prefix_cache``) with that many rows:
     the engine's cache under the ``lock`` scheduler; under ``batch`` the ``BatchWorker`` started here creates the scheduler's own
     (``batch=True``: packed admission through ``PrefixCache.prefill_pack``).  A ``worker`` handed in brings its own (its
-    ``prefix_cache`` attribute, if any, is what ``/health`` reports)."""
+    ``prefix_cache`` attribute, if any, is what ``/health`` reports).  ``long_form``: the ``LongFormSpec`` of the long-form path
+    (None: the defaults); under the ``lock`` scheduler ``lanes`` is the number of segments it decodes side by side."""
     from fastapi import FastAPI, HTTPException
+    from .long_form import LongFormSpec
+    long_spec = long_form if long_form is not None else LongFormSpec()
     from fastapi.responses import Response, StreamingResponse
 
     app = FastAPI(title="faster-qwen3-tts (MI355X) OpenAI-compatible API")
@@ -322,7 +329,23 @@ def create_app(model, voices: Dict[str, dict], default_voice: Optional[str] = No
         return dict(text=text, language=cfg.get("language", "Auto"), ref_audio=cfg.get("ref_audio"), ref_text=cfg.get("ref_text", ""),
                     voice_clone_prompt=cfg.get("voice_clone_prompt"))
 
-    async def stream_chunks(cfg: dict, text: str, spec=None) -> AsyncGenerator[bytes, None]:
+    def long_segments(req) -> int:
+        """How many segments the request's long-form path has, or 0 when it takes today's path.  400 when ``long_form: true`` cannot
+        be served."""
+        design = getattr(getattr(getattr(model, "model", None), "model", None), "tts_model_type", None) == "voice_design"
+        able = hasattr(model, "generate_long_voice_clone_streaming") and not design
+        if req.long_form:
+            if worker is not None:
+                raise HTTPException(status_code=400, detail="long_form is served by the lock scheduler (--scheduler lock); the batch "
+                                                            "scheduler does not take segments yet")
+            if not able:
+                raise HTTPException(status_code=400, detail="long_form needs a clone or custom voice (a voice-design model would "
+                                                            "change its voice between segments)")
+        elif req.long_form is False or worker is not None or not able or len(req.input) <= long_spec.max_chars:
+            return 0
+        return len(long_spec.split(req.input))
+
+    async def stream_chunks(cfg: dict, text: str, spec=None, long: bool = False) -> AsyncGenerator[bytes, None]:
         q: "queue.Queue" = queue.Queue()
         done = object()
 
@@ -333,8 +356,12 @@ def create_app(model, voices: Dict[str, dict], default_voice: Optional[str] = No
             try:
                 with lock, (contextlib.nullcontext() if spec is None else model.audio_output(spec.sample_rate, spec.encoding, spec.speed)), \
                         (contextlib.nullcontext() if cfg.get("seed") is None else model.seeded(cfg["seed"])):
-                    for chunk, _sr, _t in model.generate_voice_clone_streaming(chunk_size=cfg.get("chunk_size", 12),
-                                                                               non_streaming_mode=False, **clone_kwargs(cfg, text), **instruct_kw):
+                    gen = (model.generate_long_voice_clone_streaming(chunk_size=cfg.get("chunk_size", 12), non_streaming_mode=False,
+                                                                     lanes=lanes, long_form=long_spec, **clone_kwargs(cfg, text), **instruct_kw)
+                           if long else
+                           model.generate_voice_clone_streaming(chunk_size=cfg.get("chunk_size", 12), non_streaming_mode=False,
+                                                                **clone_kwargs(cfg, text), **instruct_kw))
+                    for chunk, _sr, _t in gen:
                         q.put(chunk)
             except Exception as exc:
                 q.put(exc)
@@ -487,6 +514,7 @@ def create_app(model, voices: Dict[str, dict], default_voice: Optional[str] = No
         seed = request_seed(req)
         if seed is not None:
             cfg = dict(cfg, seed=seed)
+        n_segments = long_segments(req)
         if worker is not None:
             return await box_response(worker.submit(cfg if spec is None else dict(cfg, audio_output=spec), req.input), fmt, spec=spec,
                                       seed=seed)
@@ -495,10 +523,13 @@ def create_app(model, voices: Dict[str, dict], default_voice: Optional[str] = No
             if fmt == "wav":
                 # unknown data length: streaming
                 yield wav_header(sample_rate) if spec is None else wav_header_for(spec.out_rate(sample_rate), spec.encoding)
-            async for raw in stream_chunks(cfg, req.input, spec):
+            async for raw in stream_chunks(cfg, req.input, spec, long=n_segments > 0):
                 yield raw
 
-        return StreamingResponse(audio_stream(), media_type=CONTENT_TYPES[fmt], headers=seed_headers(seed))
+        headers = dict(seed_headers(seed) or {})
+        if n_segments > 0:
+            headers["X-Segments"] = str(n_segments)
+        return StreamingResponse(audio_stream(), media_type=CONTENT_TYPES[fmt], headers=headers or None)
 
     return app
 

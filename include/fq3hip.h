@@ -611,6 +611,43 @@ int fq3_flac_reset(fq3_flac* f, void* stream);
 int fq3_flac_push(fq3_flac* f, const int16_t* pcm, int64_t n_in, int final, uint8_t* out, int64_t capacity_bytes,
                   int64_t* n_frames, int64_t* n_bytes_dev, void* stream);
 
+/* ---- Segment join: the sentences of a long text become one PCM stream on the device ---------------------------------------------
+ * In FRONT of the time-scale stage: the stream is a sequence of SEGMENTS (float32 at in_rate, the vocoder's waveforms of the pieces
+ * of a long text).  Of every segment the leading and trailing silence is removed, and a pause of zeros is put behind it.  The result
+ * is a pure function of the segments' samples and pauses; it does not depend on how they were cut into pushes.
+ *
+ * H = in_rate / 100 (in_rate a multiple of 100 in [8000, 48000]); 0 < threshold < 1; 0 <= lead_hops <= 16;
+ * 0 <= tail_hops <= hold_hops <= 400.  A segment of n samples has hops h = 0 .. last = ceil(n / H) - 1 (only the last may be short).
+ * active(h): some sample of hop h has fabsf(x) >= threshold (a NaN compares false; order-free, so cut independence is exact).
+ *   - no active hop: the segment contributes nothing, and its pause is dropped as well;
+ *   - else with a the first and b the last active hop and L = last - b the segment contributes its samples from
+ *     max(0, a - lead_hops) H up to the end of hop last - R, R = min(max(0, L - tail_hops), hold_hops), copied bit for bit, and then
+ *     pause_samples zeros (0.0f).  Internal silences are never touched.  There are no fades: every cut lies in a hop below the threshold.
+ * hold_hops bounds the state: an inactive hop after an active one waits in a hold queue; when the queue exceeds hold_hops its oldest
+ * hop is released (emitted); at the segment's end max(0, tail_hops - released of this run) hops of the queue go out and the rest is
+ * dropped -- which gives R above.  The object owns at most (hold_hops + lead_hops + 1) H floats of history on the device (two
+ * buffers of that size, used in turn), plus the phase, the queue length and the released count, written by ordinary stores. */
+typedef struct fq3_join fq3_join;
+typedef struct fq3_join_config { int in_rate; float threshold; int lead_hops, tail_hops, hold_hops; } fq3_join_config;
+/* host only: the room a push of n_in samples followed by pause_samples zeros needs: n_in + (hold_hops + lead_hops + 1) H +
+ * pause_samples; n_in in [0, 2^40], pause_samples in [0, 5 in_rate].  Negative: an FQ3_E* code. */
+int64_t fq3_join_bound(const fq3_join_config* cfg, int64_t n_in, int64_t pause_samples);
+/* One object per output stream.  NULL or range errors are answered before any HIP call. */
+int fq3_join_create(const fq3_join_config* cfg, fq3_join** out);
+int fq3_join_destroy(fq3_join* j);                           /* NULL -> 0 */
+/* a new stream on the same object (nothing is enqueued) */
+int fq3_join_reset(fq3_join* j, void* stream);
+/* pcm: n_in device floats (n_in may be 0 with any `end`), the next samples of the current segment.  end: 0 the segment goes on, 1 it
+ * ends with them and pause_samples zeros in [0, 5 in_rate] follow (unless the segment had no active hop), 2 the segment and the
+ * stream end, no pause (pause_samples is read with end == 1 only).  out: device floats at any float alignment; capacity must be at
+ * least fq3_join_bound(cfg, n_in, the pause in force), else FQ3_EINVAL.  *n_out_dev (a DEVICE int64, required) receives the number of
+ * samples written from out[0]: it depends on the data, so only the device knows it.  ONE launch of one workgroup on `stream` (a
+ * long push loops inside it), no host synchronisation; pcm, out and n_out_dev must stay valid until the stream has run it.  Every
+ * error is answered before anything is launched or changed: the stream goes on as if the call had not been made.  After end == 2:
+ * FQ3_ESTATE until fq3_join_reset. */
+int fq3_join_push(fq3_join* j, const float* pcm, int64_t n_in, int end, int64_t pause_samples, float* out, int64_t capacity,
+                  int64_t* n_out_dev, void* stream);
+
 /* ---- Seeded sampling noise: the samplers' Exp(1) variates from a counter-based generator on the device -------------------------
  * The samplers divide by host-provided noise (fq3_sample's noise vector, the rings of fq3_decode_begin).  These calls fill such
  * buffers as a PURE FUNCTION of (seed, emitted-frame index, slot, vocabulary index): no state, no dependence on lane, batch

@@ -1498,6 +1498,68 @@ __global__ void rope_rows_kernel(T* qkv, const float* cos_tab, const float* sin_
     DT<T>::st(p + j + half, DT<T>::rnd(x1 * cs) + DT<T>::rnd(x0 * sn));
 }
 
+// ---- codec stream states (fq3_codec.hip: fq3_codec_stream): a push runs in LOCAL rows -- [0, row_lo) the cached rows, [row_lo, rows)
+// the new frames -- while every utterance of the launch stands at its own absolute position.  Variants of the three kernels above
+// whose arithmetic per element is that of the original (the tests hold the cross-form bit equality).
+struct StreamPos { int p[128]; };                    // per utterance: absolute position of local row row_lo (= frames absorbed so far)
+struct StreamDst { void* p[128]; };
+
+// rvq_gather_kernel for codes that hold the NEW frames only: codes [utterance][rows - row_lo][nq] -> local rows [row_lo, rows)
+template <typename T>
+__global__ void rvq_gather_new_kernel(RvqArgs a, const int64_t* codes, T* first, T* rest, int Tn, int row_lo) {
+    const int t = row_lo + blockIdx.x;
+    {
+        const size_t g = blockIdx.y;
+        codes += g * (size_t)(Tn - row_lo) * a.nq; first += g * Tn * a.dim; rest += g * Tn * a.dim;
+    }
+    const int64_t* cr = codes + (size_t)blockIdx.x * a.nq;
+    for (int d = threadIdx.x; d < a.dim; d += blockDim.x) {
+        float f = 0.f, r = 0.f;
+        bool hf = false, hr = false;
+        for (int j = 0; j < a.nq; ++j) {
+            const float e = DT<T>::ld(reinterpret_cast<const T*>(a.books[j]) + (size_t)cr[j] * a.dim + d);
+            if (j < a.n_first) { f = hf ? DT<T>::rnd(f + e) : e; hf = true; }
+            else { r = hr ? DT<T>::rnd(r + e) : e; hr = true; }
+        }
+        DT<T>::st(first + (size_t)t * a.dim + d, f);
+        DT<T>::st(rest + (size_t)t * a.dim + d, r);
+    }
+}
+
+// rope_rows_kernel with a per-utterance position base: local row t of utterance u stands at position base.p[u] + t - row_lo (the
+// host checks that the last one lies inside the table)
+template <typename T>
+__global__ void rope_rows_pos_kernel(T* qkv, const float* cos_tab, const float* sin_tab, int rows, int QD, int HD, int row_lo, StreamPos base) {
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const int half = HD / 2, per_row = 2 * (QD / HD) * half;
+    if (i >= (size_t)(rows - row_lo) * per_row) return;
+    qkv += (size_t)blockIdx.y * rows * 3 * QD;
+    const int dt = (int)(i / per_row), r = (int)(i % per_row);
+    const int t = row_lo + dt, pos = base.p[blockIdx.y] + dt;
+    const int head = r / half, j = r % half;              // heads 0..QD/HD-1 = q, then k
+    T* p = qkv + (size_t)t * 3 * QD + (size_t)head * HD;
+    const float cs = cos_tab[(size_t)pos * half + j], sn = sin_tab[(size_t)pos * half + j];
+    const float x0 = DT<T>::ld(p + j), x1 = DT<T>::ld(p + j + half);
+    DT<T>::st(p + j, DT<T>::rnd(x0 * cs) + DT<T>::rnd(-x1 * sn));
+    DT<T>::st(p + j + half, DT<T>::rnd(x1 * cs) + DT<T>::rnd(x0 * sn));
+}
+
+// the reverse of prefix_rows_kernel with per-utterance destinations: rows src_row0 .. src_row0 + n_rows of utterance u's
+// [rows_per_utt][src_ld] workspace tensor (columns src_col0 ..) -> rows 0 .. of dst.p[u] (+ dst_off, leading dimension dst_ld); 16-byte
+// pieces.  The source is a workspace, so a state is updated in place safely in stream order.
+template <typename T>
+__global__ __launch_bounds__(256) void keep_rows_kernel(const T* src, size_t src_seg, int src_ld, int src_row0, int src_col0, StreamDst dst,
+                                                        size_t dst_off, int dst_ld, int n_rows, int n_cols) {
+    constexpr int EPC = 16 / sizeof(T);
+    const int cpr = n_cols / EPC;
+    const int e = blockIdx.x * 256 + threadIdx.x;
+    if (e >= n_rows * cpr) return;
+    const int r = e / cpr, c = (e - r * cpr) * EPC;
+    const T* sp = src + (size_t)blockIdx.y * src_seg + (size_t)(src_row0 + r) * src_ld + src_col0 + c;
+    T* dp = reinterpret_cast<T*>(dst.p[blockIdx.y]) + dst_off + (size_t)r * dst_ld + c;
+    *reinterpret_cast<u32x4*>(dp) = *reinterpret_cast<const u32x4*>(sp);
+}
+
 // Causal sliding-window attention, one wave per (query, head), head_dim in {32, 64, 128}, window <= 128; fp32 math, one
 // rounding.  Scores: one KEY per lane (the lane reads its key row with 16-byte loads, q is broadcast from LDS);
 // softmax across lanes; P.V: one (or two) head dims per lane, looping over the window with the probability broadcast by

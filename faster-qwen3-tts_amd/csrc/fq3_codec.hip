@@ -13,6 +13,8 @@
 //   q/k/v        "<p>.self_attn.qkv.weight" [3*QD][hidden]
 //   gate/up      "<p>.mlp.gate_up.weight" [2*I][hidden], rows interleaved in groups of 16: gate[16b..16b+16), up[16b..16b+16)
 //   rope tables  "rope.cos" / "rope.sin"  fp32 [max_frames][head_dim/2]
+//                "rope.stream_cos" / "rope.stream_sin"  fp32 [rows][head_dim/2], the same values row for row: what the stream
+//                states index by absolute position (optional; without them fq3_codec_stream_push returns FQ3_ESTATE)
 //
 // A decode is planned as a list of row-range ops (see Plan below): the transformer runs over all T frames (its
 // receptive field is the whole prefix), everything after it only over the rows the requested samples depend on.
@@ -68,6 +70,19 @@ struct fq3_codec_prefix {
     int ref_len = 0, n_pre = 0, n_kv = 0, n_out = 0;
     void *pre = nullptr, *kv = nullptr, *out = nullptr;       // [n_pre][codebook_dim], [n_layers][n_kv][2 QD], [n_out][latent_dim] in the codec's element type
 };
+
+// Rolling form of that state ("streaming with persistent left-context state"): one per utterance, moved forward
+// by every fq3_codec_stream_push.  Same three parts at their FULL capacity -- 2 pre rows, (sliding_window - 1) k | v rows per layer (layer
+// stride = the capacity), kPrefixOutRows output rows -- of which the first min(frames, capacity) rows are valid: the last rows absorbed,
+// oldest first.
+struct fq3_codec_stream {
+    fq3_codec* owner = nullptr;
+    int frames = 0;                                           // F: frames absorbed so far, the prefix it began behind included
+    bool broken = false;                                      // a push failed after its first launch: FQ3_ESTATE until reset
+    void *pre = nullptr, *kv = nullptr, *out = nullptr;
+};
+// one push as decode_t sees it: local rows [0, ctx) are cached, [ctx, Tn) new; st[u]->frames is the position of local row ctx
+struct StreamPush { fq3_codec_stream* const* st; int ctx; const float* cos_tab; const float* sin_tab; };
 
 static int64_t samples_for(const fq3_codec_config& c, int64_t T) {
     int64_t n = T;
@@ -245,15 +260,37 @@ static GemmArgs segmented(GemmArgs a, int NS) {
 // pfx (or null): NS prefix states of one ref_len -- the front end runs over rows [ref_len, Tn) only; when the requested samples reach
 // further back than the cached output rows the call returns kPrefixTooShort and the caller takes the full path.
 // cap (or null; NS = 1, front end only): the call fills this prefix state from a decode of the Tn = ref_len reference rows.
+// sp (or null): a push of NS stream states in LOCAL rows -- Tn = sp->ctx + n_new, rows [0, ctx) are the states' cached rows, codes hold the
+// new frames only ([NS][n_new][nq]), RoPE positions come from each state; every state is written back, moved forward by the new rows.
+// A row offset of `off` frames is an offset of exactly off x total_upsample samples at every stage (the transposed convs' trim is a
+// constant), so the samples wanted are the local tail; kPrefixTooShort when one of them reads a row older than the cached ones.
 constexpr int kPrefixTooShort = -1000;
 template <typename T>
 static int decode_t(fq3_codec* c, const int64_t* codes, int NS, int Tn, int64_t first_sample, float* pcm, hipStream_t s,
-                    const fq3_codec_prefix* const* pfx = nullptr, fq3_codec_prefix* cap = nullptr) {
+                    const fq3_codec_prefix* const* pfx = nullptr, fq3_codec_prefix* cap = nullptr, const StreamPush* sp = nullptr) {
     const auto& g = c->cfg;
     int err = 0;
-    const int f0 = pfx ? pfx[0]->ref_len : 0;          // first row the front end computes
+    const int f0 = pfx ? pfx[0]->ref_len : (sp ? sp->ctx : 0);          // first row the front end computes
     PrefixSrc src_pre{}, src_kv{}, src_out{};
     if (pfx) for (int u = 0; u < NS; ++u) { src_pre.p[u] = pfx[u]->pre; src_kv.p[u] = pfx[u]->kv; src_out.p[u] = pfx[u]->out; }
+    // cached rows in front of the new ones, and the rows between two layers of the cached k | v: a prefix state is compact, a stream
+    // state has its capacity; a push (sp) reads the streams' states and writes them back, moved forward by the new rows
+    const int kv_cap = g.sliding_window - 1;
+    int c_pre = pfx ? pfx[0]->n_pre : 0, c_kv = pfx ? pfx[0]->n_kv : 0, c_out = pfx ? pfx[0]->n_out : 0, c_kvs = c_kv;
+    int k_pre = 0, k_kv = 0, k_out = 0;                // rows a push keeps: min(F + n_new, capacity), the same for every lane of a class
+    StreamDst dst_pre{}, dst_kv{}, dst_out{};
+    StreamPos pos{};
+    if (sp) {
+        c_pre = std::min(f0, 2); c_kv = std::min(f0, kv_cap); c_out = std::min(f0, kPrefixOutRows); c_kvs = kv_cap;
+        k_pre = std::min(Tn, 2); k_kv = std::min(Tn, kv_cap); k_out = std::min(Tn, kPrefixOutRows);
+        for (int u = 0; u < NS; ++u) {
+            src_pre.p[u] = dst_pre.p[u] = sp->st[u]->pre; src_kv.p[u] = dst_kv.p[u] = sp->st[u]->kv; src_out.p[u] = dst_out.p[u] = sp->st[u]->out;
+            pos.p[u] = sp->st[u]->frames;
+        }
+    }
+    const bool behind = pfx || sp;
+    bool deep = false;                                 // some lane's local row 0 lies behind its frame 0
+    if (sp) for (int u = 0; u < NS; ++u) deep = deep || sp->st[u]->frames > f0;
     auto W = [&](const std::string& n) -> const void* { const void* p = nullptr; if (!err) err = need(c, n, 0, &p); return p; };
     auto SN = [&](const std::string& prefix) -> std::pair<const void*, const void*> {
         auto it = c->snake.find(prefix);
@@ -279,6 +316,13 @@ static int decode_t(fq3_codec* c, const int64_t* codes, int NS, int Tn, int64_t 
         constexpr int EPC = 16 / (int)sizeof(T);
         hipLaunchKernelGGL((prefix_rows_kernel<T>), dim3((n_rows * (n_cols / EPC) + 255) / 256, NS), dim3(256), 0, s, src, src_off, src_ld, dst,
                            (size_t)Tn * dst_ld, dst_ld, f0 - n_rows, dst_col0, n_rows, n_cols);
+    };
+    // (a push) the last n_rows local rows -> every stream's state, rows 0 ..
+    auto keep_rows_b = [&](const StreamDst& dst, size_t dst_off, int dst_ld, const T* src, int src_ld, int src_col0, int n_rows, int n_cols) {
+        if (n_rows <= 0) return;
+        constexpr int EPC = 16 / (int)sizeof(T);
+        hipLaunchKernelGGL((keep_rows_kernel<T>), dim3((n_rows * (n_cols / EPC) + 255) / 256, NS), dim3(256), 0, s, src, (size_t)Tn * src_ld, src_ld,
+                           Tn - n_rows, src_col0, dst, dst_off, dst_ld, n_rows, n_cols);
     };
     auto keep_rows = [&](void* dst, size_t dst_off, int dst_ld, const T* src, int src_ld, int src_col0, int n_rows, int n_cols) {
         if (n_rows <= 0) return;
@@ -317,10 +361,12 @@ static int decode_t(fq3_codec* c, const int64_t* codes, int NS, int Tn, int64_t 
         if (err) return err;
         o.run = [=](int) {
             T* qf = B1; T* qr = B1 + (size_t)NS * Tn * g.rvq_dim;
-            hipLaunchKernelGGL((rvq_gather_kernel<T>), dim3(Tn - f0, NS), dim3(256), 0, s, ra, codes, qf, qr, Tn, f0);
+            if (sp) hipLaunchKernelGGL((rvq_gather_new_kernel<T>), dim3(Tn - f0, NS), dim3(256), 0, s, ra, codes, qf, qr, Tn, f0);
+            else hipLaunchKernelGGL((rvq_gather_kernel<T>), dim3(Tn - f0, NS), dim3(256), 0, s, ra, codes, qf, qr, Tn, f0);
             G(lin<T>(qf, Tn, g.rvq_dim, w_first, g.codebook_dim, nullptr, B0));
             { GemmArgs a = lin<T>(qr, Tn, g.rvq_dim, w_rest, g.codebook_dim, nullptr, B0); a.res = B0; a.ldr = g.codebook_dim; G(a); }
-            if (pfx) put_rows(src_pre, 0, g.codebook_dim, B0, g.codebook_dim, 0, pfx[0]->n_pre, g.codebook_dim);      // the k = 3 pre_conv's left context
+            if (behind) put_rows(src_pre, 0, g.codebook_dim, B0, g.codebook_dim, 0, c_pre, g.codebook_dim);      // the k = 3 pre_conv's left context
+            if (sp) keep_rows_b(dst_pre, 0, g.codebook_dim, B0, g.codebook_dim, 0, k_pre, g.codebook_dim);
             if (cap) keep_rows(cap->pre, 0, g.codebook_dim, B0, g.codebook_dim, 0, cap->n_pre, g.codebook_dim);
             G(conv(B0, Tn, g.codebook_dim, w_pre, g.latent_dim, b_pre, B1, 3, 1));
             G(lin<T>(B1, Tn, g.latent_dim, w_in, g.hidden, b_in, B0));                     // x = B0
@@ -328,9 +374,11 @@ static int decode_t(fq3_codec* c, const int64_t* codes, int NS, int Tn, int64_t 
                 const LayerW& w = LW[i];
                 hipLaunchKernelGGL((rmsnorm_rows_kernel<T>), rows4, dim3(256), 0, s, (const T*)B0, (const T*)w.ln1, B1, f0, Tn, g.hidden, g.rms_eps);
                 G(lin<T>(B1, Tn, g.hidden, w.qkv, 3 * QD, nullptr, B2));
-                hipLaunchKernelGGL((rope_rows_kernel<T>), el((size_t)(Tn - f0) * 2 * g.n_heads * (g.head_dim / 2)), dim3(256), 0, s, B2, cosT, sinT, Tn, QD, g.head_dim, f0);
+                if (sp) hipLaunchKernelGGL((rope_rows_pos_kernel<T>), el((size_t)(Tn - f0) * 2 * g.n_heads * (g.head_dim / 2)), dim3(256), 0, s, B2, sp->cos_tab, sp->sin_tab, Tn, QD, g.head_dim, f0, pos);
+                else hipLaunchKernelGGL((rope_rows_kernel<T>), el((size_t)(Tn - f0) * 2 * g.n_heads * (g.head_dim / 2)), dim3(256), 0, s, B2, cosT, sinT, Tn, QD, g.head_dim, f0);
                 // the layer's cached post-RoPE k | v of the last window - 1 prefix rows, in front of the new rows
-                if (pfx) put_rows(src_kv, (size_t)i * pfx[0]->n_kv * 2 * QD, 2 * QD, B2, 3 * QD, QD, pfx[0]->n_kv, 2 * QD);
+                if (behind) put_rows(src_kv, (size_t)i * c_kvs * 2 * QD, 2 * QD, B2, 3 * QD, QD, c_kv, 2 * QD);
+                if (sp) keep_rows_b(dst_kv, (size_t)i * c_kvs * 2 * QD, 2 * QD, B2, 3 * QD, QD, k_kv, 2 * QD);    // (before a later layer reuses B2)
                 if (cap) keep_rows(cap->kv, (size_t)i * cap->n_kv * 2 * QD, 2 * QD, B2, 3 * QD, QD, cap->n_kv, 2 * QD);
                 const dim3 ag((Tn - f0 + 3) / 4, g.n_heads, NS);
                 const float sc = 1.0f / sqrtf((float)g.head_dim);
@@ -344,7 +392,8 @@ static int decode_t(fq3_codec* c, const int64_t* codes, int NS, int Tn, int64_t 
             }
             hipLaunchKernelGGL((rmsnorm_rows_kernel<T>), rows4, dim3(256), 0, s, (const T*)B0, (const T*)w_norm, B1, f0, Tn, g.hidden, g.rms_eps);
             G(lin<T>(B1, Tn, g.hidden, w_out, g.latent_dim, b_out, B0));                    // h = B0 [T, latent]
-            if (pfx) put_rows(src_out, 0, g.latent_dim, B0, g.latent_dim, 0, pfx[0]->n_out, g.latent_dim);           // the conv stack's halo rows
+            if (behind) put_rows(src_out, 0, g.latent_dim, B0, g.latent_dim, 0, c_out, g.latent_dim);           // the conv stack's halo rows
+            if (sp) keep_rows_b(dst_out, 0, g.latent_dim, B0, g.latent_dim, 0, k_out, g.latent_dim);
             if (cap) keep_rows(cap->out, 0, g.latent_dim, B0, g.latent_dim, 0, cap->n_out, g.latent_dim);
         };
         if (cap) { o.run(0); return err; }                     // (fq3_codec_prefix_create: the front end over the reference rows, nothing else)
@@ -352,7 +401,7 @@ static int decode_t(fq3_codec* c, const int64_t* codes, int NS, int Tn, int64_t 
     }
     // consumers of the front end's output: all of its rows exist in a full decode; behind a prefix state only rows >= ref_len - n_out do,
     // so there the true first row needed is propagated (and checked below)
-    const int kFrontSame = pfx ? DEP_SAME : DEP_ALL, kFrontBack = pfx ? DEP_BACK : DEP_ALL;
+    const int kFrontSame = behind ? DEP_SAME : DEP_ALL, kFrontBack = behind ? DEP_BACK : DEP_ALL;
     // ---- upsample: transposed conv (k = stride) + ConvNeXt ------------------------------------------------------------
     int rows = Tn;
     const int Lc = g.latent_dim;
@@ -473,18 +522,21 @@ static int decode_t(fq3_codec* c, const int64_t* codes, int NS, int Tn, int64_t 
         if (lo == LONG_MAX) continue;                          // nothing downstream reads this op
         const long lrow = std::max(0L, lo / o.unit);           // launch row (input row for transposed convs)
         lo_of[i] = (int)lrow;
+        // a push whose local row 0 is not the utterance's frame 0: a row below 0 is NOT causal padding there, so the reach is carried
+        // unclipped down to the front end and refused below
+        const long dep_row = deep ? (lo >= 0 ? lo / o.unit : -((-lo + o.unit - 1) / o.unit)) : lrow;
         for (const Dep& d : o.in) {
             long v = 0;
             switch (d.kind) {
-                case DEP_SAME: v = lrow; break;
-                case DEP_BACK: v = lrow - d.p; break;
+                case DEP_SAME: v = dep_row; break;
+                case DEP_BACK: v = dep_row - d.p; break;
                 case DEP_ALL: v = 0; break;
-                default: v = lrow; break;
+                default: v = dep_row; break;
             }
-            need_from[d.t] = std::min(need_from[d.t], std::max(0L, v));
+            need_from[d.t] = std::min(need_from[d.t], deep ? v : std::max(0L, v));
         }
     }
-    if (pfx && need_from[t_front] < (long)(f0 - pfx[0]->n_out)) return kPrefixTooShort;       // nothing was launched: the caller decodes in full
+    if (behind && need_from[t_front] < (long)(f0 - c_out)) return kPrefixTooShort;       // nothing was launched: the caller decodes in full
     for (size_t i = 0; i < P.ops.size(); ++i)
         if (lo_of[i] >= 0) P.ops[i].run(lo_of[i]);
     return 0;
@@ -601,4 +653,119 @@ extern "C" int fq3_codec_decode_batch_prefix(fq3_codec* c, const fq3_codec_prefi
                                              int64_t first_sample, float* pcm, void* stream) {
     if (!prefixes) return cfail(FQ3_EINVAL, "null argument");
     return decode_any(c, codes, B, T, first_sample, pcm, stream, prefixes);
+}
+
+// ---- rolling stream state (see fq3_codec_stream above) -------------------------------------------------------------------------------
+// The RoPE rows a push reads are a function of the position alone; positions run past max_frames, so the host binds a longer table under
+// names of its own ("rope.stream_cos" / "rope.stream_sin", fp32 [rows][head_dim / 2], any number of rows >= 1).
+static int stream_table(fq3_codec* c, const float** cs, const float** sn) {
+    auto a = c->w.find("rope.stream_cos"), b = c->w.find("rope.stream_sin");
+    if (a == c->w.end() || b == c->w.end()) return cfail(FQ3_ESTATE, "codec stream: rope.stream_cos / rope.stream_sin are not bound");
+    const int64_t half = c->cfg.head_dim / 2, na = c->wn["rope.stream_cos"], nb = c->wn["rope.stream_sin"];
+    if (na != nb || na < half || na % half) return cfail(FQ3_EINVAL, "codec stream: the stream RoPE tables must be two [rows][head_dim / 2] tensors of one size");
+    *cs = (const float*)a->second; *sn = (const float*)b->second;
+    return (int)std::min<int64_t>(na / half, INT_MAX);
+}
+
+static int stream_ctx_max(const fq3_codec_config& g) { return std::max(g.sliding_window - 1, kPrefixOutRows); }
+
+extern "C" int fq3_codec_stream_destroy(fq3_codec_stream* s) {
+    if (!s) return FQ3_OK;
+    (void)hipDeviceSynchronize();
+    if (s->pre) (void)hipFree(s->pre);
+    if (s->kv) (void)hipFree(s->kv);
+    if (s->out) (void)hipFree(s->out);
+    delete s;
+    return FQ3_OK;
+}
+
+extern "C" int fq3_codec_stream_reset(fq3_codec_stream* s, const fq3_codec_prefix* start, void* stream) {
+    if (!s) return cfail(FQ3_EINVAL, "null argument");
+    fq3_codec* c = s->owner;
+    if (start && start->owner != c) return cfail(FQ3_EINVAL, "prefix state belongs to another codec");
+    const auto& g = c->cfg;
+    const size_t esz = c->esz, QD2 = (size_t)2 * g.n_heads * g.head_dim;
+    const int kv_cap = g.sliding_window - 1;
+    hipStream_t st = (hipStream_t)stream;
+    s->frames = 0;
+    s->broken = true;                                          // (a copy that fails half way leaves no usable state)
+    if (start) {
+        // the prefix stays shared by the voice's other streams: copy its rows (its k | v is compact per layer, the stream's has its capacity)
+        if (start->n_pre) CHIP(hipMemcpyAsync(s->pre, start->pre, (size_t)start->n_pre * g.codebook_dim * esz, hipMemcpyDeviceToDevice, st));
+        for (int i = 0; i < g.n_layers && start->n_kv; ++i)
+            CHIP(hipMemcpyAsync((char*)s->kv + (size_t)i * kv_cap * QD2 * esz, (const char*)start->kv + (size_t)i * start->n_kv * QD2 * esz,
+                                (size_t)start->n_kv * QD2 * esz, hipMemcpyDeviceToDevice, st));
+        if (start->n_out) CHIP(hipMemcpyAsync(s->out, start->out, (size_t)start->n_out * g.latent_dim * esz, hipMemcpyDeviceToDevice, st));
+        s->frames = start->ref_len;
+    }
+    s->broken = false;
+    return FQ3_OK;
+}
+
+extern "C" int fq3_codec_stream_create(fq3_codec* c, const fq3_codec_prefix* start, fq3_codec_stream** out, void* stream) {
+    if (!c || !out) return cfail(FQ3_EINVAL, "null argument");
+    if (!c->ready) return cfail(FQ3_ESTATE, "codec weights not finalized");
+    if (start && start->owner != c) return cfail(FQ3_EINVAL, "prefix state belongs to another codec");
+    const auto& g = c->cfg;
+    const size_t esz = c->esz, QD2 = (size_t)2 * g.n_heads * g.head_dim;
+    fq3_codec_stream* s = new fq3_codec_stream();
+    s->owner = c;
+    if (hipMalloc(&s->pre, (size_t)2 * g.codebook_dim * esz) != hipSuccess ||
+        hipMalloc(&s->kv, std::max<size_t>(16, (size_t)g.n_layers * (g.sliding_window - 1) * QD2 * esz)) != hipSuccess ||
+        hipMalloc(&s->out, (size_t)kPrefixOutRows * g.latent_dim * esz) != hipSuccess) {
+        (void)hipGetLastError(); fq3_codec_stream_destroy(s); return cfail(FQ3_ENOMEM, "codec stream state: out of device memory");
+    }
+    if (int r = fq3_codec_stream_reset(s, start, stream)) { fq3_codec_stream_destroy(s); return r; }
+    *out = s;
+    return FQ3_OK;
+}
+
+extern "C" int fq3_codec_stream_frames(const fq3_codec_stream* s) { return s ? s->frames : -1; }
+
+extern "C" int fq3_codec_stream_push(fq3_codec* c, fq3_codec_stream* const* streams, int B, const int64_t* codes, int n_new,
+                                     float* pcm, void* stream) {
+    if (!c || !streams || !codes || !pcm) return cfail(FQ3_EINVAL, "null argument");
+    if (!c->ready) return cfail(FQ3_ESTATE, "codec weights not finalized");
+    if (B < 1 || B > 128) return cfail(FQ3_EINVAL, "codec stream push: 1..128 streams per call");
+    if (n_new < 1) return cfail(FQ3_EINVAL, "codec stream push: need at least 1 new frame");
+    const int ctx_max = stream_ctx_max(c->cfg);
+    for (int u = 0; u < B; ++u) {
+        if (!streams[u] || streams[u]->owner != c) return cfail(FQ3_EINVAL, "stream state is null or belongs to another codec");
+        for (int v = 0; v < u; ++v) if (streams[v] == streams[u]) return cfail(FQ3_EINVAL, "codec stream push: the same state twice in one call");
+    }
+    for (int u = 0; u < B; ++u) if (streams[u]->broken) return cfail(FQ3_ESTATE, "codec stream: an earlier push failed; reset the state");
+    const int ctx = std::min(streams[0]->frames, ctx_max);
+    int f_max = 0;
+    for (int u = 0; u < B; ++u) {
+        if (std::min(streams[u]->frames, ctx_max) != ctx)
+            return cfail(FQ3_EINVAL, "codec stream push: the streams of one call must share min(frames, " + std::to_string(ctx_max) + ")");
+        f_max = std::max(f_max, streams[u]->frames);
+    }
+    StreamPush sp{streams, ctx, nullptr, nullptr};
+    const int table_rows = stream_table(c, &sp.cos_tab, &sp.sin_tab);
+    if (table_rows < 0) return table_rows;
+    if ((int64_t)f_max + n_new > table_rows)
+        return cfail(FQ3_ETOOLONG, "codec stream push: position " + std::to_string((int64_t)f_max + n_new) + " passes the RoPE table of " +
+                                   std::to_string(table_rows) + " rows");
+    const int Tn = ctx + n_new;                                // local rows: the cached ones, then the new ones
+    if (int r = reserve_batch(c, B, Tn)) return r;
+    const int64_t first = ctx > 0 ? samples_for(c->cfg, ctx) : 0;    // an offset of `off` frames is exactly off x total_upsample samples at every stage
+    hipStream_t s = (hipStream_t)stream;
+    for (int u = 0; u < B; ++u) streams[u]->broken = true;     // (until every launch of the push is queued)
+    int r;
+    switch (c->cfg.dtype) {
+        case FQ3_BF16: r = decode_t<bf16_t>(c, codes, B, Tn, first, pcm, s, nullptr, nullptr, &sp); break;
+        case FQ3_BF16X2: r = decode_t<bfs_t>(c, codes, B, Tn, first, pcm, s, nullptr, nullptr, &sp); break;
+        default: r = decode_t<float>(c, codes, B, Tn, first, pcm, s, nullptr, nullptr, &sp); break;
+    }
+    if (r == kPrefixTooShort) {
+        // nothing was launched.  There is no full path to fall back to: a requested sample that reads a row older than the cached ones
+        // means the state keeps too few rows for this decoder
+        for (int u = 0; u < B; ++u) streams[u]->broken = false;
+        return cfail(FQ3_EUNSUPPORTED, "codec stream push: the conv stack reaches further back than the " + std::to_string(kPrefixOutRows) + " cached rows");
+    }
+    if (r) return r;
+    CHIP(hipGetLastError());
+    for (int u = 0; u < B; ++u) { streams[u]->frames += n_new; streams[u]->broken = false; }
+    return FQ3_OK;
 }

@@ -176,6 +176,11 @@ SIGNATURES = {
     "fq3_codec_prefix_destroy": (C.c_int, [vp]),
     "fq3_codec_prefix_frames": (C.c_int, [vp]),
     "fq3_codec_decode_batch_prefix": (C.c_int, [vp, C.POINTER(vp), vp, C.c_int, C.c_int, C.c_int64, vp, vp]),
+    "fq3_codec_stream_create": (C.c_int, [vp, vp, C.POINTER(vp), vp]),
+    "fq3_codec_stream_reset": (C.c_int, [vp, vp, vp]),
+    "fq3_codec_stream_destroy": (C.c_int, [vp]),
+    "fq3_codec_stream_frames": (C.c_int, [vp]),
+    "fq3_codec_stream_push": (C.c_int, [vp, C.POINTER(vp), C.c_int, vp, C.c_int, vp, vp]),
     "fq3_refenc_create": (C.c_int, [C.POINTER(RefEncConfig), C.POINTER(vp)]),
     "fq3_refenc_destroy": (C.c_int, [vp]),
     "fq3_refenc_bind": (C.c_int, [vp, C.c_char_p, vp, C.c_int64]),

@@ -144,6 +144,12 @@ def _seeded(model, args):
     return contextlib.nullcontext() if seed is None else model.seeded(seed)
 
 
+def _exact(model, args):
+    """``--exact-streaming``: the model's ``exact_streaming`` context, or a no-op."""
+    import contextlib
+    return model.exact_streaming() if getattr(args, "exact_streaming", False) else contextlib.nullcontext()
+
+
 def _write_output(path, audio, sr, args):
     """float32 audio as 16-bit PCM (as ever); what the output stage encoded (int16, G.711 bytes, a FLAC stream) as it is."""
     import os
@@ -181,7 +187,7 @@ def cmd_once(args, model=None, lines=None):
         sys.exit(2)
     model = model or load_model(args)
     start = time.perf_counter()
-    with _output_stage(model, args), _seeded(model, args):
+    with _output_stage(model, args), _seeded(model, args), _exact(model, args):
         audio, sr = synthesize_text_stream(model, args, _stdin_pieces(lines)) if text_stdin else synthesize(model, args, args.text)
     total = time.perf_counter() - start
     _write_output(args.output, audio, sr, args)
@@ -227,7 +233,7 @@ def cmd_serve(args, model=None, lines=None):
                                                        lanes=args.lanes, **_gen_kwargs(args))
             outs = [(r[0][0], r[1]) for r in results]
         else:
-            with _output_stage(model, args):
+            with _output_stage(model, args), _exact(model, args):
                 outs = [synthesize(model, args, t) for t in pending]
         total = time.perf_counter() - start
         for audio, sr in outs:
@@ -261,6 +267,9 @@ def build_parser():
         sp.add_argument("--greedy", action="store_true")
         sp.add_argument("--streaming", action="store_true")
         sp.add_argument("--chunk-size", type=int, default=12)
+        sp.add_argument("--exact-streaming", action="store_true",
+                        help="with --streaming: the streamed audio is the one-pass decode of the codes, whatever --chunk-size "
+                             "(default: the reference's 25-frame windowing)")
         sp.add_argument("--out-rate", type=int, default=None, metavar="HZ",
                         help="output sample rate, resampled on the device (e.g. 8000, 16000, 44100, 48000; default: the model's)")
         sp.add_argument("--encoding", default=None, choices=["f32", "s16", "mulaw", "alaw", "flac"],

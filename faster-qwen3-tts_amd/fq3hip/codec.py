@@ -100,8 +100,9 @@ class HipSpeechTokenizer:
     within the north star's 1e-3 PCM RMS of an fp32 evaluation at about twice the bf16 decode time."""
 
     def __init__(self, cfg: CodecConfig, weights: Weights, device: str = "cuda", dtype: torch.dtype = torch.bfloat16,
-                 max_frames: int = 1024, share: "HipSpeechTokenizer" = None, precision: str = None):
+                 max_frames: int = 1024, share: "HipSpeechTokenizer" = None, precision: str = None, stream_positions: int = 4096):
         self.lib = L.load()
+        self.stream_positions = max(int(max_frames), int(stream_positions))     # rows of the RoPE table the stream states index
         if precision is None:
             precision = "bf16" if dtype == torch.bfloat16 else "fp32"
         if precision not in ("bf16", "fp32", "bf16x2"):
@@ -150,6 +151,14 @@ class HipSpeechTokenizer:
             self._bound["rope.cos"] = cs.to(self.device).contiguous()
             self._bound["rope.sin"] = sn.to(self.device).contiguous()
             self._numel["rope.cos"], self._numel["rope.sin"] = cs.numel(), sn.numel()
+        # a stream state's positions run past max_frames (the talker emits up to 2048 frames behind a reference): a longer table under
+        # names of its own -- "rope.cos" / "rope.sin" are length-checked.  A row is a function of its position alone, so both hold the
+        # same values where they overlap.
+        if "rope.stream_cos" not in self._bound or self._numel["rope.stream_cos"] != self.stream_positions * (cfg.head_dim // 2):
+            cs, sn = rope_tables(cfg.head_dim, cfg.rope_theta, self.stream_positions, dtype)
+            self._bound["rope.stream_cos"] = cs.to(self.device).contiguous()
+            self._bound["rope.stream_sin"] = sn.to(self.device).contiguous()
+            self._numel["rope.stream_cos"], self._numel["rope.stream_sin"] = cs.numel(), sn.numel()
         for name, t in self._bound.items():
             L.check(self.lib.fq3_codec_bind(self.h, name.encode(), t.data_ptr(), self._numel[name]))
         with torch.cuda.device(self.device):
@@ -358,6 +367,103 @@ class HipSpeechTokenizer:
         up = self.cfg.total_upsample
         return sum(self.num_samples(e - s + c) - c * up for s, e, c in self._pieces(Tn))
 
+    # ---- rolling stream states (``fq3_codec_stream_*``) ------------------------------------------------------------------------
+    # One state per utterance, moved forward by every ``stream_push``: the samples a stream has produced are, bit for bit,
+    # ``decode_tensor(ref + all codes)[num_samples(ref_len):]`` as ONE pass computes them, however the frames were cut into pushes and
+    # whichever other streams shared the launches (tests/test_gpu_codec_stream.py).
+    class CodecStream:
+        """Owner of one ``fq3_codec_stream`` handle.  ``close`` (or the end of the object) hands the state back to the tokenizer, which
+        gives it to a later ``stream_open`` on the same HIP stream -- destroying one waits for the device, and an utterance of a running
+        batch must not -- and destroys what is left in ``HipSpeechTokenizer.close``."""
+
+        def __init__(self, tok, handle, keep=None):
+            self.tok, self.h, self._keep, self._sid = tok, handle, keep, None      # _sid: the HIP stream its last reset / push was queued on
+
+        @property
+        def frames(self) -> int:
+            """frames absorbed so far, the reference it began behind included"""
+            return int(self.tok.lib.fq3_codec_stream_frames(self.h))
+
+        def reset(self, ref_codes=None, stream=None) -> None:
+            """back to the state ``stream_open(ref_codes, stream)`` returns"""
+            self.tok._stream_start(self, ref_codes, stream)
+
+        def close(self):
+            if getattr(self, "h", None) is not None and self.h.value:
+                h, self.h, self._keep = self.h, L.vp(), None
+                pool = self.tok.__dict__.setdefault("_stream_pool", {}).setdefault(self._sid, [])
+                if self.tok.h.value and len(pool) < self.tok.STREAM_POOL:
+                    pool.append(h)
+                else:
+                    self.tok.lib.fq3_codec_stream_destroy(h)
+
+        def __del__(self):
+            try:
+                self.close()
+            except Exception:
+                pass
+
+    STREAM_POOL = 128           # closed stream states kept per HIP stream for the next ``stream_open`` (4.6 MB each at the real shapes in bf16x2)
+
+    @property
+    def stream_ctx_max(self) -> int:
+        """cached rows a push runs behind (csrc/fq3_codec.hip): the lanes of one ``stream_push`` share ``min(frames, stream_ctx_max)``"""
+        return max(int(self.cfg.sliding_window) - 1, 48)
+
+    def _stream_start(self, cs, ref_codes, stream) -> None:
+        st = stream if stream is not None else torch.cuda.current_stream(self.device)
+        pf = self.prefix_for(ref_codes, stream) if ref_codes is not None else None
+        with torch.cuda.stream(st):
+            if cs.h.value:
+                L.check(self.lib.fq3_codec_stream_reset(cs.h, pf.h if pf is not None else None, st.cuda_stream))
+            else:
+                L.check(self.lib.fq3_codec_stream_create(self.h, pf.h if pf is not None else None, C.byref(cs.h), st.cuda_stream))
+            cs._keep, cs._sid = pf, int(st.cuda_stream)
+            if pf is None and ref_codes is not None and hasattr(ref_codes, "shape") and ref_codes.dim() == 2 and ref_codes.shape[0] > 0:
+                # no prefix state for this reference (switched off, or too long for one): the stream absorbs the reference itself
+                ref = ref_codes.to(device=self.device, dtype=torch.long).contiguous()
+                if stream is not None:
+                    stream.wait_stream(torch.cuda.current_stream(self.device))
+                    ref.record_stream(stream)
+                for i in range(0, int(ref.shape[0]), 64):
+                    self.stream_push([cs], ref[i:i + 64].unsqueeze(0))
+
+    def stream_open(self, ref_codes=None, stream=None) -> "HipSpeechTokenizer.CodecStream":
+        """A fresh stream state: at frame 0, or behind ``ref_codes`` LongTensor[ref_len, 16] (a copy of ``prefix_for(ref_codes)``: the
+        prefix state stays shared by the voice's other streams).  ``stream`` (a ``torch.cuda.Stream``; default: the current one): the
+        stream the state is set up on -- use the one its pushes run on."""
+        st = stream if stream is not None else torch.cuda.current_stream(self.device)
+        pool = self.__dict__.get("_stream_pool", {}).get(int(st.cuda_stream))
+        # (a recycled state is reset in stream order behind its last push: same HIP stream)
+        cs = HipSpeechTokenizer.CodecStream(self, pool.pop() if pool else L.vp())
+        with torch.cuda.device(self.device):
+            self._stream_start(cs, ref_codes, stream)
+        import weakref
+        self.__dict__.setdefault("_streams", weakref.WeakSet()).add(cs)
+        return cs
+
+    def stream_samples(self, frames: int, n_new: int) -> int:
+        """samples a push of ``n_new`` frames onto a stream at ``frames`` returns (no launch)"""
+        frames, n_new = int(frames), int(n_new)
+        return self.num_samples(frames + n_new) - (self.num_samples(frames) if frames > 0 else 0)
+
+    def stream_push(self, streams, codes: torch.Tensor) -> torch.Tensor:
+        """``codes`` LongTensor[B, n, 16]: the NEW frames of ``streams`` (B ``CodecStream`` objects that share ``min(frames,
+        stream_ctx_max)``; each at most once) -> float32 [B, n_out] on the device, ``n_out = stream_samples(frames, n)``, on the current
+        stream.  Row b continues stream b's one-pass waveform, bit for bit."""
+        codes = codes.to(device=self.device, dtype=torch.long).contiguous()
+        if codes.dim() != 3 or codes.shape[0] != len(streams):
+            raise ValueError("codes must be [len(streams), n, num_quantizers]")
+        B, n = int(codes.shape[0]), int(codes.shape[1])
+        n_out = self.stream_samples(streams[0].frames, n) if B > 0 and n > 0 else 0
+        pcm = torch.empty(B, n_out, dtype=torch.float32, device=self.device)
+        arr = (L.vp * max(B, 1))(*[s.h for s in streams])
+        sid = int(torch.cuda.current_stream(self.device).cuda_stream)
+        L.check(self.lib.fq3_codec_stream_push(self.h, arr, B, codes.data_ptr(), n, pcm.data_ptr(), sid))
+        for s in streams:
+            s._sid = sid
+        return pcm
+
     def decode(self, payload):
         codes = payload["audio_codes"]
         if codes.dim() != 3:
@@ -368,6 +474,11 @@ class HipSpeechTokenizer:
         return [wav[b] for b in range(wav.shape[0])], self.sample_rate
 
     def close(self):
+        for cs in list(self.__dict__.get("_streams", ())):
+            cs.close()                                            # open stream states go first, like the prefix states
+        for pool in self.__dict__.pop("_stream_pool", {}).values():
+            for h in pool:
+                self.lib.fq3_codec_stream_destroy(h)
         for pf in list(self.__dict__.get("_prefixes", {}).values()):
             pf.close()                                            # a prefix state must not outlive its codec
         self.__dict__["_prefixes"] = {}

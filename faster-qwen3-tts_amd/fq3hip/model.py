@@ -255,14 +255,22 @@ class StreamingVocoder:
     samples; with a ``speed`` other than 1 the time-scale stage in front of it adds about 30 ms of input, three hops of 10 ms, and
     hands out whole 10 ms segments) until ``push(..., final=True)`` or ``flush()``.  With the ``flac`` encoding the chunks are
     ``uint8`` arrays that concatenate to a complete FLAC stream: the first begins with the 42-byte header, and the samples behind the
-    last whole FLAC block (up to 48 ms at 24 kHz) wait for the final push as well."""
+    last whole FLAC block (up to 48 ms at 24 kHz) wait for the final push as well.
+
+    ``exact=True`` (opt-in; the default stays the reference's windowing): no windowing at all -- the utterance owns a codec stream
+    state and a chunk's audio is that push's samples, so the chunks concatenate to the one-pass decode of all the codes at any chunk
+    size (see ``_init_exact``).  ``push`` / ``prepare`` / ``flush`` keep their signatures; the output stage sits behind it unchanged."""
 
     CONTEXT_FRAMES = 25
 
-    def __init__(self, tok, ref_codes, chunk_size: int, device, side_stream=None, output=None):
+    def __init__(self, tok, ref_codes, chunk_size: int, device, side_stream=None, output=None, exact=False):
         self.tok, self.ref_codes, self.side = tok, ref_codes, side_stream
         self.output, self.stage, self.header_sent = output, None, False
         self.dev = torch.device(device) if not isinstance(device, torch.device) else device
+        self.exact = bool(exact)
+        if self.exact:
+            self._init_exact()
+            return
         self.min_cal = max(self.CONTEXT_FRAMES, int(chunk_size))
         self.all_codes: List[torch.Tensor] = []
         self.prev_len, self.spf = 0, None
@@ -271,6 +279,60 @@ class StreamingVocoder:
         self.prefix = (tok.prefix_for(ref_codes, side_stream) if side_stream is not None and ref_codes is not None and hasattr(tok, "prefix_for")
                        else None)
         self.last_prefix = None          # the prefix the decode returned by the last ``prepare`` may use (None in phase 2)
+
+    # ---- exact mode (``exact=True``) ------------------------------------------------------------------------------
+    # The utterance owns one codec stream state (``tok.stream_open``) that moves forward with every chunk: a chunk's audio is that
+    # push's samples, so the chunks concatenate, sample for sample, to the ONE-PASS decode of all the codes -- at any chunk size.  No
+    # phase 1 / phase 2, no calibrated samples-per-frame, no concatenation of the codes so far.
+    # ICL: the non-streaming cut ``int(ref_len / T * n)`` depends on the final length T, so the stream begins at ``c0``, its lower bound
+    # over every total length of a one-pass decode (T <= CHUNK_FRAMES; beyond that the non-streaming output is piecewise anyway), and
+    # drops the ``c0 - num_samples(ref_len)`` samples in front of it from its first push: the non-streaming waveform is the stream from
+    # sample ``cut - c0`` on.
+    def _init_exact(self):
+        tok, rc = self.tok, self.ref_codes
+        if not hasattr(tok, "stream_open") or not hasattr(tok, "stream_push"):
+            raise ValueError("exact streaming needs a speech tokenizer with codec stream states (stream_open / stream_push)")
+        self.prefix = self.last_prefix = None
+        ref_len = int(rc.shape[0]) if rc is not None else 0
+        self.c0 = 0
+        if ref_len > 0:
+            cache = tok.__dict__.setdefault("_exact_c0", {})
+            if ref_len not in cache:
+                cache[ref_len] = _SideVocoder._cut_floor(self, ref_len, int(getattr(tok, "CHUNK_FRAMES", 300)))
+            self.c0 = cache[ref_len]
+        self.cstream = tok.stream_open(rc if ref_len > 0 else None, self.side)
+        self.frames = ref_len                                     # frames handed to the stream so far (prepared pushes included)
+        self.drop = max(0, self.c0 - self._samples_upto(ref_len)) if ref_len > 0 else 0
+
+    def _samples_upto(self, frames: int) -> int:
+        """samples of the one-pass decode that belong to the first ``frames`` frames"""
+        if hasattr(self.tok, "stream_samples"):
+            return self.tok.stream_samples(0, frames)
+        return self.tok.num_samples_total(frames)
+
+    def _prepare_exact(self, chunk):
+        """-> (the new frames, samples to drop from the front of their push); the push itself is the caller's (``tok.stream_push`` on
+        ``self.cstream``, alone or with other utterances of the same class ``(min(frames_before, ctx_max), n_new)``)"""
+        if self.side is not None:
+            chunk.record_stream(self.side)
+        drop, self.drop = self.drop, 0
+        self.frames_before, self.frames = self.frames, self.frames + int(chunk.shape[0])
+        return chunk, drop
+
+    def _push_exact(self, chunk, ev, final):
+        codes, drop = self._prepare_exact(chunk)
+        if self.side is not None:
+            if ev is not None:
+                self.side.wait_event(ev)
+            else:
+                self.side.wait_stream(torch.cuda.current_stream(self.dev))
+        with (contextlib.nullcontext() if self.side is None else torch.cuda.stream(self.side)):
+            wav = self.tok.stream_push([self.cstream], codes.unsqueeze(0))[0]
+            wav = wav[drop:]              # (the drop is below one frame's samples: the trims of the transposed convs add up to less)
+            if self.output is not None:
+                return self._encoded(wav.flatten().float(), final)
+            out = _to_numpy(wav)
+        return out, int(getattr(self.tok, "sample_rate", 24000))
 
     def _stage(self):
         """the output stage of this utterance, made at its first chunk (on the vocoder's stream; without one, on the current stream)"""
@@ -347,6 +409,8 @@ class StreamingVocoder:
         first_sample)`` -- the decode whose ``waveform[first_sample:]`` is this chunk's audio -- so that a caller with several
         utterances at the same point (the first chunks of lock-step lanes) can run those decodes as ONE batched launch set."""
         assert self.side is not None
+        if self.exact:
+            return self._prepare_exact(chunk)
         chunk.record_stream(self.side)
         self.all_codes.append(chunk)
         n_new = chunk.shape[0]
@@ -373,6 +437,8 @@ class StreamingVocoder:
     def push(self, chunk: torch.Tensor, ready_event=None, final=False):
         """``chunk`` LongTensor[n_new, 16] (device) -> (new audio as a host array, sample_rate).  ``final`` (only read with an
         ``output``): this is the utterance's last chunk, the output stage's tail comes with it."""
+        if self.exact:
+            return self._push_exact(chunk, ready_event, final)
         if self.side is not None:
             inp, first = self.prepare(chunk, ready_event)
             return self._vocode(inp, first, ready_event, self.last_prefix, final)
@@ -902,6 +968,25 @@ class FasterQwen3TTS:
         finally:
             self._seed = prev
 
+    # ---- exact streaming (opt-in) --------------------------------------------------------------------------------------
+    @contextlib.contextmanager
+    def exact_streaming(self):
+        """Context manager: inside it every streaming vocoder this model hands out (``streaming_vocoder``: the ``generate_*_streaming``,
+        ``stream_*``, ``generate_long_*_streaming``, ``*_batch_streaming`` / ``stream_*_batch`` entry points and the server's workers)
+        is exact: the streamed audio is, sample for sample, the one-pass decode of the utterance's codes, whatever the chunk size and
+        whichever lanes share a launch.  Behind an ICL reference the stream begins at ``StreamingVocoder.c0``, a few samples before
+        the non-streaming cut, and up to ``CHUNK_FRAMES`` total frames ``generate_voice_clone``'s waveform is the stream from sample
+        ``cut - c0`` on.  Iterate a streaming generator inside the context.  Outside it nothing changes: the reference's windowing."""
+        prev, self._exact_stream = getattr(self, "_exact_stream", False), True
+        try:
+            yield
+        finally:
+            self._exact_stream = prev
+
+    def _exact_kw(self) -> dict:
+        """``exact=True`` for the vocoders built inside ``exact_streaming`` -- nothing at all outside it (the calls stay what they were)."""
+        return dict(exact=True) if getattr(self, "_exact_stream", False) else {}
+
     def _seed_kw(self) -> dict:
         """``seed=`` for the decode loops inside ``seeded`` -- nothing at all outside it (the calls stay what they were)."""
         seed = getattr(self, "_seed", None)
@@ -1012,7 +1097,7 @@ class FasterQwen3TTS:
         ``AudioOutSpec`` for this utterance's audio (default: that of the open ``audio_output`` context, if any)."""
         tok = self.model.model.speech_tokenizer
         return StreamingVocoder(tok, ref_codes, chunk_size, self.device, self._vocoder_stream(tok),
-                                output=output if output is not None else getattr(self, "_audio_spec", None))
+                                output=output if output is not None else getattr(self, "_audio_spec", None), **self._exact_kw())
 
     def _run_streaming(self, m, talker, config, tie, tam, tth, tpe, ref_codes, gen_kwargs, chunk_size: int,
                        parity_mode: bool = False):
@@ -1020,7 +1105,7 @@ class FasterQwen3TTS:
         reference's windowing would emit for it."""
         from .streaming import fast_generate_streaming, parity_generate_streaming
         tok = m.speech_tokenizer
-        voc = StreamingVocoder(tok, ref_codes, chunk_size, self.device, self._vocoder_stream(tok), output=self._audio_spec)
+        voc = StreamingVocoder(tok, ref_codes, chunk_size, self.device, self._vocoder_stream(tok), output=self._audio_spec, **self._exact_kw())
         fn = parity_generate_streaming if parity_mode else fast_generate_streaming
         stream = fn(talker=talker, talker_input_embeds=tie, attention_mask=tam, trailing_text_hiddens=tth,
                     tts_pad_embed=tpe, config=config, predictor_graph=self.predictor_graph,
@@ -1252,6 +1337,8 @@ class FasterQwen3TTS:
         # handed out in launch order, a launch takes every open class in order of first appearance, markers without audio come last.
         open_classes: Dict[Any, list] = {}
         queued: list = []                               # (jobs of the group, pinned waveforms, event, device waveforms kept alive)
+        exact_pending: dict = {}                        # (exact mode) utterance -> (its chunks waiting in open classes, order of the last one's class)
+        class_seq: dict = {}                            # (exact mode) open class -> order of first appearance = launch order
 
         def launch(key, part):
             _T, first, pf_len = key
@@ -1261,8 +1348,12 @@ class FasterQwen3TTS:
                 else:
                     side.wait_stream(torch.cuda.current_stream(torch.device(self.device)))
             with torch.cuda.stream(side):
-                pfs = [j[3][3] for j in part] if pf_len > 0 else None      # (phase 1 behind ICL references: the voices' cached front-end states)
-                if len(part) == 1:
+                exact = pf_len == "exact"
+                pfs = [j[3][3] for j in part] if not exact and pf_len > 0 else None      # (phase 1 behind ICL references: the voices' cached front-end states)
+                if exact:
+                    # exact mode: the group's stream states take their new frames in one push; `first` = samples in front of an ICL cut's floor
+                    wav = tok.stream_push([j[3][4] for j in part], torch.stack([j[3][0] for j in part]))[:, first:]
+                elif len(part) == 1:
                     wav = (tok.decode_tensor(part[0][3][0], first, prefix=pfs[0]) if pfs else tok.decode_tensor(part[0][3][0], first)).reshape(1, -1)
                 else:
                     stacked = torch.stack([j[3][0] for j in part])
@@ -1277,6 +1368,8 @@ class FasterQwen3TTS:
             queued.append((part, host, landed, wav))
 
         def launch_open():
+            exact_pending.clear()
+            class_seq.clear()
             for key in list(open_classes):
                 members = open_classes.pop(key)
                 for i in range(0, len(members), _SideVocoder.STREAM_GROUP):
@@ -1284,7 +1377,23 @@ class FasterQwen3TTS:
 
         def add_job(j):
             jobs.append(j)
-            if j[3] is not None:
+            if j[3] is not None and len(j[3]) > 4:
+                # exact mode: (new codes, drop, ev, None, stream state, frames before the push) -- the class is (min(F, ctx_max), n_new) and the
+                # drop, so every steady-state chunk of every lane falls into one class.  A state is pushed once per call and in order: a
+                # poll that completes several chunks of an utterance puts its k-th waiting chunk into the k-th generation of the class,
+                # and a class that would launch in front of an earlier chunk of the same utterance is not joined -- everything open
+                # is launched first.
+                cnt, last = exact_pending.get(j[0], (0, -1))
+                shape = (min(int(j[3][5]), tok.stream_ctx_max), int(j[3][0].shape[0]))
+                key = ((cnt,) + shape, int(j[3][1]), "exact")
+                if class_seq.get(key, len(class_seq)) <= last:
+                    launch_open()
+                    cnt, key = 0, ((0,) + shape, int(j[3][1]), "exact")
+                exact_pending[j[0]] = (cnt + 1, class_seq.setdefault(key, len(class_seq)))
+                open_classes.setdefault(key, []).append(j)
+                if len(open_classes[key]) >= _SideVocoder.STREAM_GROUP:
+                    launch_open()
+            elif j[3] is not None:
                 pf = j[3][3] if len(j[3]) > 3 else None
                 key = (int(j[3][0].shape[0]), int(j[3][1]), pf.ref_len if pf is not None else 0)
                 open_classes.setdefault(key, []).append(j)
@@ -1315,7 +1424,7 @@ class FasterQwen3TTS:
         for head, source in pairs:
           for rid, codes, info in dec.run(head, source=source, chunk_frames=chunk_size):
             if rid not in vocs:
-                vocs[rid] = (StreamingVocoder(tok, meta[rid], chunk_size, self.device, side) if device_audio
+                vocs[rid] = (StreamingVocoder(tok, meta[rid], chunk_size, self.device, side, **self._exact_kw()) if device_audio
                              else self.streaming_vocoder(meta[rid], chunk_size))
                 n_chunks[rid] = 0
             ev = info.pop("codes_ready_event", None)
@@ -1326,7 +1435,10 @@ class FasterQwen3TTS:
             if codes is not None and codes.shape[0] > 0:
                 if batched:
                     inp, first = vocs[rid].prepare(codes, ev)
-                    add_job([rid, out_meta, None, (inp, first, ev, vocs[rid].last_prefix)])
+                    if vocs[rid].exact:
+                        add_job([rid, out_meta, None, (inp, first, ev, None, vocs[rid].cstream, vocs[rid].frames_before)])
+                    else:
+                        add_job([rid, out_meta, None, (inp, first, ev, vocs[rid].last_prefix)])
                 else:
                     audio, _sr = vocs[rid].push(codes, ev)
                     add_job([rid, out_meta, audio, None])
@@ -1766,7 +1878,7 @@ class FasterQwen3TTS:
         try:
             m, talker, config, tie, tam, _tth, tpe = prepare(self._text_session_ids(feeder))
             tok = m.speech_tokenizer
-            voc = StreamingVocoder(tok, None, chunk_size, self.device, self._vocoder_stream(tok), output=self._audio_spec)
+            voc = StreamingVocoder(tok, None, chunk_size, self.device, self._vocoder_stream(tok), output=self._audio_spec, **self._exact_kw())
             stream = fast_generate_text_streaming(
                 talker=talker, talker_input_embeds=tie, attention_mask=tam, tts_pad_embed=tpe, config=config,
                 predictor_graph=self.predictor_graph, talker_graph=self.talker_graph, feeder=feeder,

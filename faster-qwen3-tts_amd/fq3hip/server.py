@@ -254,13 +254,16 @@ class BatchWorker:
 
 
 def create_app(model, voices: Dict[str, dict], default_voice: Optional[str] = None, scheduler: str = "lock", lanes: int = 8,
-               chunk_size: int = 12, worker=None, prefix_cache_rows: int = 0, long_form=None):
+               chunk_size: int = 12, worker=None, prefix_cache_rows: int = 0, long_form=None, exact_streaming: bool = False):
     """``worker``: a ready ``BatchWorker`` (or a stand-in with ``submit`` / ``submit_text``) instead of the one ``scheduler="batch"``
     would start.  ``prefix_cache_rows`` > 0: the model's prefix KV cache (``FasterQwen3TTS.enable_prefix_cache``) with that many rows:
     the engine's cache under the ``lock`` scheduler; under ``batch`` the ``BatchWorker`` started here creates the scheduler's own
     (``batch=True``: packed admission through ``PrefixCache.prefill_pack``).  A ``worker`` handed in brings its own (its
     ``prefix_cache`` attribute, if any, is what ``/health`` reports).  ``long_form``: the ``LongFormSpec`` of the long-form path
-    (None: the defaults); under the ``lock`` scheduler ``lanes`` is the number of segments it decodes side by side."""
+    (None: the defaults); under the ``lock`` scheduler ``lanes`` is the number of segments it decodes side by side.
+    ``exact_streaming``: the model's ``exact_streaming()`` context is entered for the life of the app -- both schedulers and the text
+    sessions then stream the one-pass decode of every utterance instead of the reference's windowing (the vocoders come from
+    ``model.streaming_vocoder``, on whichever thread)."""
     from fastapi import FastAPI, HTTPException
     from .long_form import LongFormSpec
     long_spec = long_form if long_form is not None else LongFormSpec()
@@ -268,6 +271,11 @@ def create_app(model, voices: Dict[str, dict], default_voice: Optional[str] = No
 
     app = FastAPI(title="faster-qwen3-tts (MI355X) OpenAI-compatible API")
     lock = threading.Lock()
+    if exact_streaming:
+        if not hasattr(model, "exact_streaming"):
+            raise ValueError("exact_streaming: this model has no exact_streaming() context")
+        app.state.exact_streaming = contextlib.ExitStack()
+        app.state.exact_streaming.enter_context(model.exact_streaming())
     if worker is None and scheduler == "batch":
         worker = BatchWorker(model, lanes, chunk_size, prefix_cache_rows=int(prefix_cache_rows or 0))
     prefix_cache = getattr(worker, "prefix_cache", None)
@@ -496,6 +504,8 @@ def create_app(model, voices: Dict[str, dict], default_voice: Optional[str] = No
         out = {"status": "ok", "model_loaded": model is not None, "scheduler": scheduler, "lanes": lanes if worker else 1}
         if prefix_cache is not None:
             out["prefix_cache"] = prefix_cache.stats()
+        if exact_streaming:
+            out["exact_streaming"] = True
         return out
 
     @app.post("/v1/audio/speech")
@@ -552,6 +562,9 @@ def build_parser():
     p.add_argument("--prefix-cache-rows", type=int, default=0, metavar="N",
                    help="keep the talker K/V rows of instruct turns on the device, up to N rows (default 0: off); under --scheduler batch "
                         "the packed admission reuses them, under --scheduler lock each request does")
+    p.add_argument("--exact-streaming", action="store_true",
+                   help="stream the one-pass decode of every utterance (codec stream states) instead of the reference's 25-frame windowing: "
+                        "the audio no longer depends on the chunk size (default: off)")
     return p
 
 
@@ -574,7 +587,7 @@ def main(argv=None):
     import uvicorn
     logging.basicConfig(level=logging.INFO)
     uvicorn.run(create_app(model, voices, default_voice, args.scheduler, args.lanes, args.chunk_size,
-                           prefix_cache_rows=args.prefix_cache_rows), host=args.host, port=args.port)
+                           prefix_cache_rows=args.prefix_cache_rows, exact_streaming=args.exact_streaming), host=args.host, port=args.port)
 
 
 if __name__ == "__main__":

@@ -460,6 +460,30 @@ int fq3_codec_prefix_destroy(fq3_codec_prefix* prefix);
 int fq3_codec_prefix_frames(const fq3_codec_prefix* prefix);
 int fq3_codec_decode_batch_prefix(fq3_codec* c, const fq3_codec_prefix* const* prefixes, const int64_t* codes, int B, int T,
                                   int64_t first_sample, float* pcm, void* stream);
+/* Rolling stream state: the prefix state moved forward with every chunk.  One state per utterance keeps what
+ * later rows read of earlier ones -- the pre_conv's 2 context rows, every layer's post-RoPE K / V of the last sliding_window - 1 rows,
+ * the last 48 front-end output rows.  The samples a stream has produced after ANY sequence of pushes are, bit for bit,
+ * fq3_codec_decode(all codes, F)[num_samples(F0):] (F0 = the prefix it began behind, whose codes go in front): for every split of the
+ * frames into pushes, for B = 1 or many, in all three precisions.  A push is the decode behind a prefix in LOCAL rows -- [0, ctx) the
+ * cached rows, ctx = min(F, ctx_max), ctx_max = max(sliding_window - 1, 48), then the n_new new ones -- so its workspaces are those of
+ * ctx_max + n_new frames however long the stream is.
+ *   start  NULL = an utterance that begins at frame 0; else the stream begins BEHIND that prefix (ICL reference): the state is a copy,
+ *          the prefix stays shared by the voice's other streams
+ *   push   B <= 128 streams (HOST array) take n_new frames each: codes int64[B][n_new][16] (device) hold the NEW frames only; pcm
+ *          float32[B][n_out], n_out = num_samples(F + n_new) - num_samples(F) (num_samples(0) = 0).  The lanes of one call may stand at
+ *          different positions F but must share n_new and min(F, ctx_max), and a state may appear once: else FQ3_EINVAL.  Positions index
+ *          the RoPE tables bound as "rope.stream_cos" / "rope.stream_sin" (fp32 [rows][head_dim / 2], rows of their own choosing; FQ3_ESTATE
+ *          when not bound): a push that would pass them returns FQ3_ETOOLONG.  There is no full path to fall back to: a decoder whose
+ *          conv stack reaches further back than the cached rows gets FQ3_EUNSUPPORTED.  Every such refusal leaves the states untouched.  A push
+ *          that fails after its first launch leaves its streams unusable: FQ3_ESTATE until fq3_codec_stream_reset.
+ * A state belongs to the codec that made it and must be destroyed before it. */
+typedef struct fq3_codec_stream fq3_codec_stream;
+int fq3_codec_stream_create(fq3_codec* c, const fq3_codec_prefix* start, fq3_codec_stream** out, void* stream);
+int fq3_codec_stream_reset(fq3_codec_stream* s, const fq3_codec_prefix* start, void* stream);
+int fq3_codec_stream_destroy(fq3_codec_stream* s);                 /* NULL -> 0 */
+int fq3_codec_stream_frames(const fq3_codec_stream* s);            /* F: frames absorbed so far, the prefix included */
+int fq3_codec_stream_push(fq3_codec* c, fq3_codec_stream* const* streams, int B, const int64_t* codes, int n_new,
+                          float* pcm, void* stream);
 
 /* ---- reference-audio analysis (create_voice_clone_prompt, model.py:415-463 -> upstream qwen_tts) -----------------------
  * What the reference runs once per new (ref_audio, ref_text) pair and then caches (model.py:424-463):

@@ -111,6 +111,7 @@ __device__ __forceinline__ float snake_apply(float v, float a, float ib) {
     const float s = DT<T>::rnd(snake_sin<T>(DT<T>::rnd(v * a)));
     return v + DT<T>::rnd(ib * DT<T>::rnd(s * s));
 }
+// a = rnd(exp(alpha)); ib = rnd(1 / rnd(rnd(exp(beta)) + 1e-9f)): one rounding to T per operation, as the oracle's T-typed tensor ops
 template <typename T>
 __global__ void snake_consts_kernel(const T* alpha, const T* beta, T* a_out, T* ib_out, int C) {
     const int c = blockIdx.x * blockDim.x + threadIdx.x;
@@ -1388,6 +1389,8 @@ inline void gemm_swiglu_halves(const GemmArgs& a, void* y, hipStream_t s) {
 }
 
 // ---- RVQ: sequential (rounded) sum of codebook rows; one block per frame ------------------------------
+// levels [0, n_first) -> first, [n_first, nq) -> rest; the first term of a half is taken as it is, every later addition is rounded
+// to T; an empty half stores 0
 struct RvqArgs { const void* books[32]; int nq; int n_first; int dim; };
 template <typename T>
 __global__ void rvq_gather_kernel(RvqArgs a, const int64_t* codes, T* first, T* rest, int Tn, int row_lo) {
@@ -1427,6 +1430,8 @@ __global__ __launch_bounds__(256) void prefix_rows_kernel(PrefixSrc src, size_t 
 }
 
 // ---- row norms: one wave per row, rows [row_lo, rows) ---------------------------------------------------
+// RMSNorm: y = rnd(w * rnd(x * rs)), rs = 1 / sqrt(mean(x^2) + eps) in fp32 (two roundings to T: before the gain and on store).
+// LayerNorm: y = rnd((x - mean) * rstd * w + b), biased variance about the fp32 mean, everything in fp32 and ONE rounding on store.
 template <typename T>
 __global__ __launch_bounds__(256) void rmsnorm_rows_kernel(const T* x, const T* w, T* y, int row_lo, int rows, int C, float eps) {
     const int row = row_lo + blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
@@ -1457,7 +1462,8 @@ __global__ __launch_bounds__(256) void layernorm_rows_kernel(const T* x, const T
         DT<T>::st(y + (size_t)row * C + c, (DT<T>::ld(xr + c) - mean) * rstd * DT<T>::ld(w + c) + DT<T>::ld(b + c));
 }
 
-// causal depthwise conv k=7 over time, channels-last, rows [row_lo, rows)
+// causal depthwise conv k=7 over time, channels-last, rows [row_lo, rows): y[t][c] = rnd(sum_k w[c][k] x[t - 6 + k][c] + b[c]), rows
+// before the utterance's first read as zero; fp32 fma chain in tap order, bias added last, one rounding on store
 template <typename T>
 __global__ void dwconv7_kernel(const T* x, const T* w /*[C][7]*/, const T* b, T* y, int row_lo, int rows, int C) {
     const size_t i = (size_t)row_lo * C + (size_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -1473,6 +1479,7 @@ __global__ void dwconv7_kernel(const T* x, const T* w /*[C][7]*/, const T* b, T*
     DT<T>::st(y + i, acc + DT<T>::ld(b + c));
 }
 
+// y = rnd(rnd(silu(g)) * u): silu in fp32 (g / (1 + expf(-g)): 0 once expf overflows, g < -88.7), rounded to T before the product
 template <typename T>
 __global__ void silu_mul_kernel(const T* gu, T* y, int rows, int I) {     // gu [rows][2I] = gate | up (not interleaved)
     const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -1482,7 +1489,8 @@ __global__ void silu_mul_kernel(const T* gu, T* y, int rows, int I) {     // gu 
     DT<T>::st(y + i, DT<T>::rnd(g / (1.0f + expf(-g))) * u);
 }
 
-// RoPE on the q and k thirds of qkv [rows][3*QD], head_dim HD (rotate_half convention), position = row
+// RoPE on the q and k thirds of qkv [rows][3*QD], head_dim HD (rotate_half convention), position = row; the v third is left alone.
+// Each of the four products is rounded to T, then each sum on store: y0 = rnd(rnd(x0 cs) + rnd(-x1 sn)), y1 = rnd(rnd(x1 cs) + rnd(x0 sn))
 template <typename T>
 __global__ void rope_rows_kernel(T* qkv, const float* cos_tab, const float* sin_tab, int rows, int QD, int HD, int row_lo) {
     const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -1615,6 +1623,7 @@ __global__ __launch_bounds__(256) void swa_attn_kernel(const T* qkv, T* out, int
 }
 
 // Output conv k=7, C -> 1, + clamp to [-1, 1]; fp32 PCM out for samples [t_lo, rows), written to pcm[t - t_lo].
+// pcm = clamp(rnd(acc + b)): the bias is added to the fp32 sum, the result rounded to T (the value a T-typed conv would store), then clamped.
 // One workgroup per `spw` consecutive samples (a multiple of 64, <= 256; one thread per sample): the (spw + 6) x C input window is
 // copied to LDS as it is (16-byte chunks, no conversion; rows padded by 16 bytes so that consecutive samples' 16-byte reads fall
 // into distinct bank quads), the 7 x C weights as fp32.  A thread walks its 7 rows with 16-byte LDS reads (the weights are

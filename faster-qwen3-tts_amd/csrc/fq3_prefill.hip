@@ -94,46 +94,6 @@ static void flash_prefill_launch(const bf16_t* qkv, const PagedKV<bf16_t>& kv, b
     }
 }
 
-// RMSNorm of prompt rows, one wave per row, the whole row in registers: 16-byte loads, one reduction, 16-byte stores (the row-loop
-// kernel the codec uses takes 10 us on 200 rows of 1024: 32 dependent 2-byte accesses per lane).  Per element the arithmetic is
-// the same -- w * rnd(x * rs), rounded on store; only the order of the sum of squares differs.  C = NCH * 512.
-template <typename T, int NCH>
-__global__ __launch_bounds__(256) void rmsnorm_rows_vec_kernel(const T* x, const T* w, T* y, int rows, float eps) {
-    constexpr int C = NCH * 512;
-    const int row = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
-    if (row >= rows) return;
-    Raw8<T> xr[NCH], wr[NCH];
-#pragma unroll
-    for (int j = 0; j < NCH; ++j) {
-        ldraw<false>(xr[j], x + (size_t)row * C + j * 512 + lane * 8);
-        ldraw<false>(wr[j], w + j * 512 + lane * 8);
-    }
-    float xv[NCH][8], ss = 0.f;
-#pragma unroll
-    for (int j = 0; j < NCH; ++j) {
-        unpack(xr[j], xv[j]);
-#pragma unroll
-        for (int i = 0; i < 8; ++i) ss = fmaf(xv[j][i], xv[j][i], ss);
-    }
-    ss = wave_sum(ss);
-    const float rs = 1.0f / sqrtf(ss / (float)C + eps);
-#pragma unroll
-    for (int j = 0; j < NCH; ++j) {
-        float wv[8];
-        unpack(wr[j], wv);
-#pragma unroll
-        for (int i = 0; i < 8; ++i) xv[j][i] = wv[i] * DT<T>::rnd(xv[j][i] * rs);
-        DT<T>::st8(y + (size_t)row * C + j * 512 + lane * 8, xv[j]);
-    }
-}
-template <typename T>
-void rmsnorm_rows(const T* x, const T* w, T* y, int rows, int C, float eps, hipStream_t s) {
-    const dim3 grid((rows + 3) / 4), block(256);
-    if (C == 1024) hipLaunchKernelGGL((rmsnorm_rows_vec_kernel<T, 2>), grid, block, 0, s, x, w, y, rows, eps);
-    else if (C == 2048) hipLaunchKernelGGL((rmsnorm_rows_vec_kernel<T, 4>), grid, block, 0, s, x, w, y, rows, eps);
-    else hipLaunchKernelGGL((rmsnorm_rows_kernel<T>), grid, block, 0, s, x, w, y, 0, rows, C, eps);
-}
-
 constexpr long kPrefillWsFloats = 8L << 20;       // split-K partials of the short-prompt GEMMs (32 MB)
 // every prefill GEMM lends the split-K workspace: that also marks it free to take the weight-stationary kernel (skinny_gemm.cuh)
 // (kind: 0 = a plain matrix, 1 = [gate | up] halves -- which fragment-major copy the weight-stationary kernel would read, fq3_ctx.h)

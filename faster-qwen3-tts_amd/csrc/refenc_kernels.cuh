@@ -185,7 +185,8 @@ __global__ void dft_mag_kernel(const float* __restrict__ spec, float* __restrict
 // Per-channel statistics over time of x [T][ldx] (channels [0, C)), 64 channels x 16 time slices per workgroup.
 //   logits == nullptr: uniform weights 1/T (SE mean; the pooling layer's global context)
 //   logits != nullptr: weights = softmax over time of logits[:, c] (attentive statistics pooling)
-// mean[c] = sum w x, std[c] = sqrt(max(sum w (x - mean)^2, eps)); either output may be null.
+// mean[c] = sum w x, std[c] = sqrt(max(sum w (x - mean)^2, eps)); either output may be null.  The softmax subtracts the column's
+// maximum logit before expf (logits beyond +88 would overflow fp32 otherwise); the variance is the biased one, about the fp32 mean.
 constexpr int kStatSlices = 16;
 __global__ __launch_bounds__(64 * kStatSlices) void col_stats_kernel(const float* __restrict__ x, int ldx, const float* __restrict__ logits, int ldl,
                                                         float* __restrict__ mean, float* __restrict__ stdv, int T, int C, float eps) {

@@ -87,6 +87,16 @@ class JoinConfig(C.Structure):
     _fields_ = [("in_rate", C.c_int), ("threshold", C.c_float), ("lead_hops", C.c_int), ("tail_hops", C.c_int), ("hold_hops", C.c_int)]
 
 
+class LoudConfig(C.Structure):
+    _fields_ = [("in_rate", C.c_int), ("target_lufs", C.c_double), ("ceiling_db", C.c_double), ("max_gain_db", C.c_double),
+                ("capacity_hops", C.c_int)]
+
+
+class LoudStats(C.Structure):
+    _fields_ = [("mean_power", C.c_double), ("peak", C.c_float), ("gain", C.c_float), ("n_hops", i32), ("n_abs", i32), ("n_rel", i32),
+                ("n_bad", i32), ("valid", i32), ("reserved", i32)]
+
+
 class NoiseRing(C.Structure):
     _fields_ = [("talker", vp), ("pred", vp), ("seed", C.c_uint64), ("first_frame", C.c_uint32), ("n_frames", i32)]
 
@@ -214,6 +224,15 @@ SIGNATURES = {
     "fq3_join_destroy": (C.c_int, [vp]),
     "fq3_join_reset": (C.c_int, [vp, vp]),
     "fq3_join_push": (C.c_int, [vp, vp, C.c_int64, C.c_int, C.c_int64, vp, C.c_int64, vp, vp]),
+    "fq3_loud_design": (C.c_int, [C.c_int, C.c_double, C.c_double, C.c_double, C.POINTER(C.c_int), C.POINTER(C.c_double), C.POINTER(C.c_float),
+                                  C.POINTER(C.c_uint64), C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double)]),
+    "fq3_loud_create": (C.c_int, [C.POINTER(LoudConfig), C.POINTER(vp)]),
+    "fq3_loud_destroy": (C.c_int, [vp]),
+    "fq3_loud_reset": (C.c_int, [vp, vp]),
+    "fq3_loud_push": (C.c_int, [vp, vp, C.c_int64, C.c_int, vp]),
+    "fq3_loud_finish": (C.c_int, [vp, vp, vp]),
+    "fq3_loud_hops": (C.c_int, [vp, vp, C.c_int64, C.POINTER(C.c_int64), vp]),
+    "fq3_loud_apply": (C.c_int, [vp, vp, C.c_int64, vp, vp]),
     "fq3_noise_fill": (C.c_int, [vp, C.POINTER(NoiseRing), C.c_int, C.c_int, vp]),
     "fq3_noise_first": (C.c_int, [vp, C.c_uint64, vp, vp]),
     "fq3_noise_words": (C.c_int, [C.c_uint64, C.c_uint32, C.c_uint32, C.c_int, vp, vp]),

@@ -150,6 +150,35 @@ def _exact(model, args):
     return model.exact_streaming() if getattr(args, "exact_streaming", False) else contextlib.nullcontext()
 
 
+def _levelled(model, args):
+    """``--loudness`` / ``--gain-db``: the model's ``loudness`` or ``fixed_gain`` context (the level set on the device), or a no-op."""
+    import contextlib
+    lufs, gain = getattr(args, "loudness", None), getattr(args, "gain_db", None)
+    if lufs is not None:
+        return model.loudness(target_lufs=lufs)
+    return contextlib.nullcontext() if gain is None else model.fixed_gain(gain)
+
+
+def check_level_args(parser, args):
+    """``--loudness`` needs the whole utterance: an argparse error together with a streaming mode or with ``--gain-db``; so is a
+    ``--loudness`` or ``--gain-db`` outside its range (said before the model is loaded)."""
+    from .loudness import LoudnessSpec, gain_factor
+    try:
+        if getattr(args, "loudness", None) is not None:
+            LoudnessSpec(target_lufs=args.loudness)
+        if getattr(args, "gain_db", None) is not None:
+            gain_factor(args.gain_db)
+    except ValueError as exc:
+        parser.error(str(exc))
+    if getattr(args, "loudness", None) is None:
+        return
+    if getattr(args, "streaming", False) or getattr(args, "text_stdin", False):
+        parser.error("--loudness measures the whole utterance, so it does not go with --streaming / --text-stdin: a stream's gain cannot "
+                     "be known before it ends (use --gain-db X)")
+    if getattr(args, "gain_db", None) is not None:
+        parser.error("--loudness and --gain-db both set the level: give one")
+
+
 def _write_output(path, audio, sr, args):
     """float32 audio as 16-bit PCM (as ever); what the output stage encoded (int16, G.711 bytes, a FLAC stream) as it is."""
     import os
@@ -187,7 +216,7 @@ def cmd_once(args, model=None, lines=None):
         sys.exit(2)
     model = model or load_model(args)
     start = time.perf_counter()
-    with _output_stage(model, args), _seeded(model, args), _exact(model, args):
+    with _levelled(model, args), _output_stage(model, args), _seeded(model, args), _exact(model, args):
         audio, sr = synthesize_text_stream(model, args, _stdin_pieces(lines)) if text_stdin else synthesize(model, args, args.text)
     total = time.perf_counter() - start
     _write_output(args.output, audio, sr, args)
@@ -226,14 +255,14 @@ def cmd_serve(args, model=None, lines=None):
         if not pending:
             continue
         start = time.perf_counter()
-        staged = any(getattr(args, k, None) is not None for k in ("out_rate", "encoding", "speed"))
+        staged = any(getattr(args, k, None) is not None for k in ("out_rate", "encoding", "speed", "gain_db"))
         if len(pending) > 1 and args.mode == "clone" and not staged:      # (the output stage runs per stream: line by line)
             results = model.generate_voice_clone_batch(pending, language=args.language, ref_audio=args.ref_audio, ref_text=args.ref_text,
                                                        xvec_only=args.xvec_only, non_streaming_mode=args.non_streaming_mode,
                                                        lanes=args.lanes, **_gen_kwargs(args))
             outs = [(r[0][0], r[1]) for r in results]
         else:
-            with _output_stage(model, args), _exact(model, args):
+            with _levelled(model, args), _output_stage(model, args), _exact(model, args):
                 outs = [synthesize(model, args, t) for t in pending]
         total = time.perf_counter() - start
         for audio, sr in outs:
@@ -277,7 +306,13 @@ def build_parser():
                              "compressed on the device (default: float32, written as 16-bit)")
         sp.add_argument("--speed", type=float, default=None, metavar="X",
                         help="speaking rate, 0.25 to 4.0, time-scaled on the device: duration changes, pitch does not (default: 1.0)")
+        sp.add_argument("--gain-db", type=float, default=None, metavar="X",
+                        help="multiply the audio by 10^(X/20) on the device, in front of --speed / --out-rate / --encoding; no limiter "
+                             "(default: off)")
         if output:
+            sp.add_argument("--loudness", type=float, default=None, metavar="LUFS",
+                            help="measure the utterance on the device (ITU-R BS.1770-4, integrated) and scale it to LUFS, at most +20 dB and "
+                                 "a sample peak of -1 dBFS; with --long every segment is levelled on its own; not with a streaming mode")
             sp.add_argument("--seed", type=int, default=None, metavar="N",
                             help="sampling seed in [0, 2^64): the same command gives the same audio (default: unseeded)")
             sp.add_argument("--text", required=not text_stdin)
@@ -325,7 +360,9 @@ def build_parser():
 
 
 def main(argv=None):
-    args = build_parser().parse_args(argv)
+    parser = build_parser()
+    args = parser.parse_args(argv)
+    check_level_args(parser, args)
     args.func(args)
 
 

@@ -292,10 +292,13 @@ class OrderedJoin:
     segment ``k`` (``last``: the segment ends with it); segments may be fed in any interleaving.  Chunks of segment ``k + 1`` wait as
     device tensors until segment ``k`` has ended; what ``feed`` returns is the list of ``(segment_index, joined device tensor, stream
     ended)`` pieces that became ready, strictly in text order.  With ``audio_out`` (an ``AudioOut``) the joined samples go through that
-    chain (join -> time-scale -> resample / encode -> FLAC, one stream) and the pieces are its output."""
+    chain (join -> time-scale -> resample / encode -> FLAC, one stream) and the pieces are its output.  ``gains`` (None; a 1-element
+    float32 device tensor; or a list of them, one per segment): what segment ``k`` contributes -- its samples and the pause behind
+    them -- leaves the join multiplied by ``gains`` / ``gains[k]`` (``fq3_loud_apply``)."""
 
     def __init__(self, join: SegmentJoin, pauses: List[int], audio_out=None):
         self.join, self.pauses, self.audio_out = join, [int(p) for p in pauses], audio_out
+        self.gains = None                                          # a 1-element device tensor, or one per segment: see ``_emit``
         self.n = len(self.pauses)
         self.cur = 0
         self._wait: List[List] = [[] for _ in range(self.n)]        # per segment: [(device tensor or None, last)]
@@ -304,6 +307,11 @@ class OrderedJoin:
     def _emit(self, k, pcm, last):
         end = 0 if not last else (2 if k == self.n - 1 else 1)
         y = self.join.push(pcm, end, self.pauses[k] if end == 1 else 0)
+        g = self.gains[k] if isinstance(self.gains, (list, tuple)) else self.gains
+        if g is not None:
+            # level behind the join, in front of the chain: the join's silence decisions saw the raw samples, pause zeros stay zeros
+            from .loudness import apply_gain
+            y = apply_gain(y.contiguous(), g, self.join.stream)
         if self.audio_out is not None:
             y = self.audio_out.push(y, final=end == 2)
         return (k, y, end == 2)

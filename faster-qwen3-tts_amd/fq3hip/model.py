@@ -18,6 +18,8 @@ from typing import Any, Dict, Generator, List, Optional, Tuple, Union
 import numpy as np
 import torch
 
+from .loudness import LoudnessSession
+
 logger = logging.getLogger(__name__)
 
 _GGML_ONLY = ("ref_spk", "ref_rvq", "ref_spk_emb", "ref_codes")
@@ -52,6 +54,7 @@ class _SideVocoder:
         self.stream = stream if self.async_ok else None
         self.items: list = []
         self.device_only = False          # long form: the waveforms stay on the device (``collect_device``), no pinned-host copies
+        self.level = None                 # ``level(key, waveform)``: the model's loudness / fixed-gain step, run between the decode and the copy
 
     def _prefix(self, ref):
         """the tokenizer's cached front-end state of an ICL reference (built on the vocoder stream), or None"""
@@ -66,7 +69,10 @@ class _SideVocoder:
         if not self.async_ok or not hasattr(self.tok, "num_samples_total"):
             lst, _rate = self.tok.decode({"audio_codes": codes.unsqueeze(0)})
             a = _to_numpy(lst[0])
-            self.items.append((key, a[int(ref_len / max(codes.shape[0], 1) * len(a)):] if ref_len > 0 else a, None, None))
+            a = a[int(ref_len / max(codes.shape[0], 1) * len(a)):] if ref_len > 0 else a
+            if self.level is not None:
+                a = _to_numpy(self.level(key, a))
+            self.items.append((key, a, None, None))
             return
         cut = int(ref_len / max(codes.shape[0], 1) * self.tok.num_samples_total(codes.shape[0])) if ref_len > 0 else 0
         self.stream.wait_stream(torch.cuda.current_stream(self.dev))
@@ -74,6 +80,8 @@ class _SideVocoder:
         pf = self._prefix(ref) if ref_len > 0 else None
         with torch.cuda.stream(self.stream):
             pcm = self.tok.decode_tensor(codes, cut, prefix=pf) if pf is not None else self.tok.decode_tensor(codes, cut)
+            if self.level is not None:
+                pcm = self.level(key, pcm)
             host = None
             if not self.device_only:
                 host = torch.empty(pcm.shape, dtype=torch.float32, pin_memory=True)
@@ -125,6 +133,10 @@ class _SideVocoder:
                 with torch.cuda.stream(self.stream):
                     stacked = torch.stack([c for _k, c, _r in part])
                     pcm = self.tok.decode_tensor_batch(stacked, cut, prefixes=pfs) if pfs is not None else self.tok.decode_tensor_batch(stacked, cut)
+                    if self.level is not None:
+                        pcm = pcm.float().contiguous()
+                        for j, (key, _c, _r) in enumerate(part):
+                            self.level(key, pcm[j])                 # row by row, in place: every utterance has its own gain
                     host = None
                     if not self.device_only:
                         host = torch.empty(pcm.shape, dtype=torch.float32, pin_memory=True)
@@ -263,9 +275,10 @@ class StreamingVocoder:
 
     CONTEXT_FRAMES = 25
 
-    def __init__(self, tok, ref_codes, chunk_size: int, device, side_stream=None, output=None, exact=False):
+    def __init__(self, tok, ref_codes, chunk_size: int, device, side_stream=None, output=None, exact=False, gain=None):
         self.tok, self.ref_codes, self.side = tok, ref_codes, side_stream
         self.output, self.stage, self.header_sent = output, None, False
+        self.gain = gain                  # a 1-element float32 device tensor (``FasterQwen3TTS.fixed_gain``) or None
         self.dev = torch.device(device) if not isinstance(device, torch.device) else device
         self.exact = bool(exact)
         if self.exact:
@@ -329,10 +342,18 @@ class StreamingVocoder:
         with (contextlib.nullcontext() if self.side is None else torch.cuda.stream(self.side)):
             wav = self.tok.stream_push([self.cstream], codes.unsqueeze(0))[0]
             wav = wav[drop:]              # (the drop is below one frame's samples: the trims of the transposed convs add up to less)
+            wav = self._gained(wav)
             if self.output is not None:
                 return self._encoded(wav.flatten().float(), final)
             out = _to_numpy(wav)
         return out, int(getattr(self.tok, "sample_rate", 24000))
+
+    def _gained(self, wav):
+        """``wav`` (device tensor, on the vocoder's stream) times the fixed gain, in front of the output stage; without one: ``wav``"""
+        if self.gain is None:
+            return wav
+        from .loudness import apply_gain
+        return apply_gain(wav.flatten().float().contiguous(), self.gain, self.side)
 
     def _stage(self):
         """the output stage of this utterance, made at its first chunk (on the vocoder's stream; without one, on the current stream)"""
@@ -374,6 +395,7 @@ class StreamingVocoder:
         with torch.cuda.stream(self.side):
             # (.cpu() synchronises the side stream only)
             wav = self.tok.decode_tensor(codes_in, first_sample, prefix=prefix) if prefix is not None else self.tok.decode_tensor(codes_in, first_sample)
+            wav = self._gained(wav)
             if self.output is not None:
                 return self._encoded(wav.flatten().float(), final)
             out = _to_numpy(wav)
@@ -470,6 +492,10 @@ class StreamingVocoder:
             window = flat[start:]
             n_ctx = window.shape[0] - n_new
             new_audio, sr = self._vocode(window, int(round(n_ctx * self.spf)) if n_ctx > 0 else 0, ready_event)
+        if self.gain is not None:
+            # synchronous tokenizer: its audio is on the host; the chunk is uploaded for the multiply (and the stage behind it)
+            wav = self._gained(torch.from_numpy(np.ascontiguousarray(new_audio, dtype=np.float32)).to(self.dev))
+            return self._encoded(wav, final) if self.output is not None else (wav.cpu().numpy(), sr)
         if self.output is not None:
             # synchronous tokenizer: its audio is on the host; the chunk is uploaded for the stage
             return self._encoded(torch.from_numpy(np.ascontiguousarray(new_audio, dtype=np.float32)).to(self.dev), final)
@@ -491,6 +517,8 @@ class FasterQwen3TTS:
         self._warmed_up = False
         self._voice_prompt_cache: Dict[Any, Any] = {}
         self._audio_spec = None          # the AudioOutSpec of an open ``audio_output`` context
+        self._loud = None                # the LoudnessSession of an open ``loudness`` context
+        self._gain = None                # the factor of an open ``fixed_gain`` context
         self._seed = None                # the sampling seed of an open ``seeded`` context
 
     # ---- small helpers pinned by the reference's unit tests ------------------------------------------------
@@ -983,9 +1011,132 @@ class FasterQwen3TTS:
         finally:
             self._exact_stream = prev
 
+    # ---- loudness (opt-in; fq3hip/loudness.py) ------------------------------------------------------
+    @contextlib.contextmanager
+    def loudness(self, target_lufs: float = -16.0, ceiling_db: float = -1.0, max_gain_db: float = 20.0):
+        """Context manager: inside it the one-shot entry points (``generate``, ``generate_voice_clone``, ``generate_custom_voice``,
+        ``generate_voice_design``), the non-streaming ``*_batch`` ones and the non-streaming ``generate_long_*`` return every utterance
+        measured (ITU-R BS.1770-4, integrated, gated) and scaled to ``target_lufs`` on the device, on the vocoder's stream and in front
+        of the copy to the host and of an open ``audio_output`` stage.  The gain is bounded by ``max_gain_db`` and by what keeps the
+        sample peak at or below ``ceiling_db`` dBFS -- a bound on the gain, there is no limiter -- and an utterance that cannot be
+        measured (shorter than 0.4 s, silent, not finite) is left as it is.  Long form: each segment is measured on its raw waveform
+        and its gain applied to what the join stage emits for it, so the segments leave at one level; the join's silence decisions
+        see the unscaled samples.  Yields a ``LoudnessSession``: ``.stats`` holds the ``LoudnessStats`` of the last call, one per
+        utterance (per segment for long form).  Every STREAMING entry point raises ``ValueError`` inside it: a stream's gain cannot be
+        known before it ends -- measure the voice once (``measure_loudness``) and stream inside ``fixed_gain``.  The defaults are not
+        tuned on real voices.  Outside it nothing changes."""
+        from .loudness import LoudnessSpec, design
+        spec = LoudnessSpec(target_lufs, ceiling_db, max_gain_db)
+        design(self.sample_rate, spec)                       # the library's own range checks (host only)
+        if getattr(self, "_gain", None) is not None:
+            raise ValueError("loudness() inside fixed_gain(): one of the two sets the level")
+        prev, self._loud = getattr(self, "_loud", None), LoudnessSession(spec)
+        try:
+            yield self._loud
+        finally:
+            self._loud = prev
+
+    @contextlib.contextmanager
+    def fixed_gain(self, gain_db: float):
+        """Context manager: inside it every vocoder this model hands out (``streaming_vocoder``, hence every streaming entry point and
+        the server's workers) and every one-shot, batch and long-form path multiplies its audio by ``10^(gain_db / 20)`` on the device
+        (``fq3_loud_apply``, the factor read from a 1-element device tensor), in front of the time-scale and output stages.
+        ``gain_db`` in [-60, 40].  There is no limiter: float32 output may exceed 1.0, the s16 / G.711 encoders clamp.  Iterate a
+        streaming generator inside the context.  Outside it nothing changes."""
+        from .loudness import gain_factor
+        factor = gain_factor(gain_db)
+        if getattr(self, "_loud", None) is not None:
+            raise ValueError("fixed_gain() inside loudness(): one of the two sets the level")
+        prev, self._gain = getattr(self, "_gain", None), dict(gain_db=float(gain_db), factor=factor, tensors={})
+        try:
+            yield float(np.float32(factor))
+        finally:
+            self._gain = prev
+
+    def _gain_tensor(self, device=None):
+        """the open ``fixed_gain`` context's factor as a 1-element float32 tensor on ``device`` (made once per device), or None"""
+        g = getattr(self, "_gain", None)
+        if g is None:
+            return None
+        dev = torch.device(self.device if device is None else device)
+        if dev.index is None and dev.type == "cuda":
+            dev = torch.device("cuda", torch.cuda.current_device())
+        if dev not in g["tensors"]:
+            g["tensors"][dev] = torch.tensor([g["factor"]], dtype=torch.float32, device=dev)
+        return g["tensors"][dev]
+
+    def _levelling(self) -> bool:
+        return getattr(self, "_loud", None) is not None or getattr(self, "_gain", None) is not None
+
+    def _refuse_streaming_loudness(self) -> None:
+        if getattr(self, "_loud", None) is not None:
+            raise ValueError("a stream's gain cannot be known before the stream ends, so the streaming entry points do not run inside "
+                             "loudness(): measure the voice once (measure_loudness) and stream inside fixed_gain(stats.gain_db)")
+
+    def _meter(self, spec, device, stream):
+        """One ``LoudnessMeter`` per (device, stream), kept: its buffers are reused by the utterances that follow on that stream.  A
+        meter is made for one spec (the gain constants live in it): another spec on the same stream replaces it, so the cache does not
+        grow with the targets a caller asks for."""
+        from .loudness import LoudnessMeter
+        meters = self.__dict__.setdefault("_meters", {})
+        key = (str(device), None if stream is None else stream.cuda_stream)
+        if key not in meters or meters[key].spec != spec:
+            meters[key] = LoudnessMeter(spec, self.sample_rate, device, stream)
+        return meters[key]
+
+    def _measure(self, x, key=None, stream=None):
+        """``x`` (contiguous float32 device vector) through the open ``loudness`` context's meter on ``stream`` (None: the current
+        one) -> the device stats buffer, also noted in the session under ``key``"""
+        sess = self._loud
+        s = stream if stream is not None else torch.cuda.current_stream(x.device)
+        meter = self._meter(sess.spec, x.device, s)
+        meter.reset()
+        meter.push(x, final=True)
+        buf = meter.finish()
+        sess.put(key, buf)
+        return buf
+
+    def _level(self, wav, key=None, stream=None, inplace: bool = False):
+        """A whole utterance's waveform (device tensor or host array) as the open ``loudness`` / ``fixed_gain`` context wants it: a
+        float32 device vector, measured and scaled, or multiplied by the fixed factor.  Outside both: ``wav`` itself."""
+        if not self._levelling():
+            return wav
+        from .loudness import apply_gain, gain_of
+        dev = torch.device(self.device) if not isinstance(self.device, torch.device) else self.device
+        if torch.is_tensor(wav) and wav.is_cuda:
+            x = wav.reshape(-1)
+            if x.dtype != torch.float32 or not x.is_contiguous():
+                x, inplace = x.float().contiguous(), False
+        else:
+            x, inplace = torch.from_numpy(np.ascontiguousarray(_to_numpy(wav), dtype=np.float32).reshape(-1)).to(dev), True
+        gain = self._gain_tensor(x.device) if self._gain is not None else gain_of(self._measure(x, key, stream))
+        return apply_gain(x, gain, stream, out=x if inplace else None)
+
+    def measure_loudness(self, audio, spec=None):
+        """``audio`` (a device tensor or a host array, mono, at the model's rate) -> ``LoudnessStats``: its integrated loudness, sample
+        peak and the gain ``spec`` (a ``LoudnessSpec``; None: the defaults) would give it, measured on the device.  How a caller
+        calibrates a voice once -- synthesise a sentence, measure it -- and then streams inside ``fixed_gain(stats.gain_db)``."""
+        from .loudness import LoudnessSpec
+        spec = LoudnessSpec() if spec is None else spec
+        if not isinstance(spec, LoudnessSpec):
+            raise ValueError(f"spec must be a LoudnessSpec or None, not {type(spec).__name__}")
+        dev = torch.device(self.device) if not isinstance(self.device, torch.device) else self.device
+        if torch.is_tensor(audio) and audio.is_cuda:
+            x = audio.reshape(-1).float().contiguous()
+        else:
+            x = torch.from_numpy(np.ascontiguousarray(_to_numpy(audio), dtype=np.float32).reshape(-1)).to(dev)
+        meter = self._meter(spec, x.device, torch.cuda.current_stream(x.device))
+        meter.reset()
+        meter.push(x, final=True)
+        return meter.stats()
+
     def _exact_kw(self) -> dict:
         """``exact=True`` for the vocoders built inside ``exact_streaming`` -- nothing at all outside it (the calls stay what they were)."""
         return dict(exact=True) if getattr(self, "_exact_stream", False) else {}
+
+    def _gain_kw(self) -> dict:
+        """``gain=`` for the vocoders built inside ``fixed_gain`` -- nothing at all outside it (the calls stay what they were)."""
+        return dict(gain=self._gain_tensor()) if getattr(self, "_gain", None) is not None else {}
 
     def _seed_kw(self) -> dict:
         """``seed=`` for the decode loops inside ``seeded`` -- nothing at all outside it (the calls stay what they were)."""
@@ -1029,6 +1180,8 @@ class FasterQwen3TTS:
                                           trailing_text_hiddens=tth, tts_pad_embed=tpe, config=config,
                                           predictor_graph=self.predictor_graph, talker_graph=self.talker_graph,
                                           **gen_kwargs, **self._seed_kw())
+        if self._loud is not None:
+            self._loud.begin()
         if codec_ids is None:
             logger.warning("Generation returned no tokens")
             if self._audio_spec is not None:
@@ -1044,15 +1197,18 @@ class FasterQwen3TTS:
             # decoder produces only that tail (bit-identical to the slice, fq3_codec_decode_tail)
             cut = int(ref_len / max(codes.shape[0], 1) * tok.num_samples_total(codes.shape[0]))
             pf = tok.prefix_for(ref_codes) if hasattr(tok, "prefix_for") else None          # the voice's cached front-end state
-            wav = tok.decode_tensor(codes, cut, prefix=pf) if pf is not None else tok.decode_tensor(codes, cut)
+            wav = self._level(tok.decode_tensor(codes, cut, prefix=pf) if pf is not None else tok.decode_tensor(codes, cut))
             if self._audio_spec is not None:
                 a, sr = self._one_shot_output(wav)
                 out = [a]
             else:
                 out, sr = [_to_numpy(wav)], tok.sample_rate
         elif self._audio_spec is not None and ref_len == 0 and hasattr(tok, "decode_tensor"):
-            a, sr = self._one_shot_output(tok.decode_tensor(codes, 0))
+            a, sr = self._one_shot_output(self._level(tok.decode_tensor(codes, 0)))
             out = [a]
+        elif self._levelling() and ref_len == 0 and hasattr(tok, "decode_tensor"):
+            # (``tok.decode`` of one utterance IS decode_tensor: the waveform stays on the device for the meter and the multiply)
+            out, sr = [_to_numpy(self._level(tok.decode_tensor(codes, 0)))], tok.sample_rate
         else:
             audio_list, sr = tok.decode({"audio_codes": codes.unsqueeze(0)})
             out = []
@@ -1060,6 +1216,9 @@ class FasterQwen3TTS:
                 a = _to_numpy(a)
                 if ref_len > 0:
                     a = a[int(ref_len / max(codes.shape[0], 1) * len(a)):]
+                if self._levelling():
+                    a = self._level(a)                             # a foreign tokenizer's host waveform: uploaded for the stage
+                    a = a if self._audio_spec is not None else _to_numpy(a)
                 if self._audio_spec is not None:
                     a, sr = self._one_shot_output(a)
                 out.append(a)
@@ -1095,17 +1254,21 @@ class FasterQwen3TTS:
     def streaming_vocoder(self, ref_codes, chunk_size: int, output=None) -> "StreamingVocoder":
         """A fresh windowing state for one utterance (used by the streaming entry points and by the batch server).  ``output``: an
         ``AudioOutSpec`` for this utterance's audio (default: that of the open ``audio_output`` context, if any)."""
+        self._refuse_streaming_loudness()
         tok = self.model.model.speech_tokenizer
         return StreamingVocoder(tok, ref_codes, chunk_size, self.device, self._vocoder_stream(tok),
-                                output=output if output is not None else getattr(self, "_audio_spec", None), **self._exact_kw())
+                                output=output if output is not None else getattr(self, "_audio_spec", None), **self._exact_kw(),
+                                **self._gain_kw())
 
     def _run_streaming(self, m, talker, config, tie, tam, tth, tpe, ref_codes, gen_kwargs, chunk_size: int,
                        parity_mode: bool = False):
         """model.py:1048-1137: the decode loop yields code chunks, ``StreamingVocoder`` turns each into the audio the
         reference's windowing would emit for it."""
         from .streaming import fast_generate_streaming, parity_generate_streaming
+        self._refuse_streaming_loudness()
         tok = m.speech_tokenizer
-        voc = StreamingVocoder(tok, ref_codes, chunk_size, self.device, self._vocoder_stream(tok), output=self._audio_spec, **self._exact_kw())
+        voc = StreamingVocoder(tok, ref_codes, chunk_size, self.device, self._vocoder_stream(tok), output=self._audio_spec, **self._exact_kw(),
+                               **self._gain_kw())
         fn = parity_generate_streaming if parity_mode else fast_generate_streaming
         stream = fn(talker=talker, talker_input_embeds=tie, attention_mask=tam, trailing_text_hiddens=tth,
                     tts_pad_embed=tpe, config=config, predictor_graph=self.predictor_graph,
@@ -1261,13 +1424,18 @@ class FasterQwen3TTS:
         out: List[Optional[Tuple[list, int]]] = [None] * count
         voc = self._side_vocoder()
         voc.device_only = bool(device_audio)
+        if self._loud is not None:
+            self._loud.begin(count)
+        if self._levelling() and not device_audio:
+            # between the decode and the pinned copy, on the vocoder's stream (long form levels behind the join instead)
+            voc.level = lambda key, wav: self._level(wav, key, voc.stream, inplace=True)
         # batch_vocode_every (attribute; default 0 = vocode an utterance when it has ended; N > 0 = produce the waveform in slices every N
         # frames while the utterance still decodes -- exact, see _SideVocoder.inc_add -- so that what is left at the end is the last slice
         # only).  Measured on MI355X (profiles/r04_batch_e2e_vocode_every_*.txt): the slices contend with the latency-bound lock-step
         # frames for more than they save at the end -- 64 lanes x 128 utterances, 0.6B: 561x at 0, 537x at 64, 552x at 100; 1.7B: 458x vs
         # 443x -- so it is OFF by default; a server whose lanes finish at different times has nothing to gain from it either.
         inc = int(getattr(self, "batch_vocode_every", 0) or 0)
-        if inc > 0 and not device_audio and voc.async_ok and hasattr(voc.tok, "decode_tensor_batch") and hasattr(voc.tok, "num_samples_total"):
+        if inc > 0 and not device_audio and not self._levelling() and voc.async_ok and hasattr(voc.tok, "decode_tensor_batch") and hasattr(voc.tok, "num_samples_total"):
             max_new = min(int(gen_kwargs.get("max_new_tokens", 2048)), int(self.talker_graph.engine.max_frames))
             for rid, codes, info in dec.run(head, source=source, chunk_frames=inc):
                 more = int(getattr(dec, "more_in_poll", 0))
@@ -1306,8 +1474,10 @@ class FasterQwen3TTS:
         keys to a chunk's timing before it goes out.  ``device_audio`` (internal, long form; what is yielded by default does not
         change): a chunk vocoded on the vocoder stream is handed out as the group's device waveform row -- a float32 tensor valid on
         that stream, no copy to the host, no wait -- and the utterances' vocoders carry no output stage of their own."""
+        self._refuse_streaming_loudness()
         if not device_audio:
             self._refuse_batch_audio_output()
+        gain = None if device_audio else self._gain_tensor()       # (long form multiplies behind the join)
         if seeds is not None:
             # the ``seeds=`` keyword of the public entry points is expanded HERE and in _run_batch_full, nowhere else; a caller that
             # builds its own requests (``rounds``) seeds them itself
@@ -1359,6 +1529,9 @@ class FasterQwen3TTS:
                     stacked = torch.stack([j[3][0] for j in part])
                     wav = tok.decode_tensor_batch(stacked, first, prefixes=pfs) if pfs else tok.decode_tensor_batch(stacked, first)
                 wav = wav.float()
+                if gain is not None:
+                    from .loudness import apply_gain
+                    wav = apply_gain(wav.contiguous(), gain, side)
                 host = landed = None
                 if not device_audio:
                     host = torch.empty(wav.shape, dtype=wav.dtype, pin_memory=True)
@@ -1704,7 +1877,9 @@ class FasterQwen3TTS:
             from .audio_out import AudioOut
             chain = AudioOut(self._audio_spec, self.sample_rate, join.dev, stream)
         pauses = [spec.pause_samples(s.pause, self.sample_rate) for s in segs]
-        return OrderedJoin(join, pauses, chain), chain
+        oj = OrderedJoin(join, pauses, chain)
+        oj.gains = self._gain_tensor(join.dev)                     # fixed_gain: every joined piece times the one factor
+        return oj, chain
 
     def _run_long_full(self, prepared, segs, spec, gen_kwargs, lanes: int) -> Tuple[list, int]:
         """The segments as the requests of one lock-step run, whole waveforms kept on the device, joined in text order on the side
@@ -1715,9 +1890,15 @@ class FasterQwen3TTS:
         oj.audio_out = None                                         # the whole stream goes through _one_shot_output below
         parts = []
         with (torch.cuda.stream(voc.stream) if voc.stream is not None else contextlib.nullcontext()):
+            if self._loud is not None:
+                oj.gains = [None] * n
             for k, (wavs, _sr) in enumerate(outs):
                 w = wavs[0]
                 w = w if torch.is_tensor(w) else torch.from_numpy(np.ascontiguousarray(w, dtype=np.float32)).to(oj.join.dev)
+                if self._loud is not None:
+                    # the segment's RAW waveform is measured; its gain scales what the join emits for it (the join sees raw samples)
+                    from .loudness import gain_of
+                    oj.gains[k] = gain_of(self._measure(w.reshape(-1).contiguous(), k, voc.stream))
                 parts.extend(y for _k, y, _e in oj.feed(k, w, True))
             pcm = torch.cat(parts) if parts else torch.zeros(0, dtype=torch.float32, device=oj.join.dev)
             if self._audio_spec is not None:
@@ -1729,6 +1910,7 @@ class FasterQwen3TTS:
         """Streaming form: the chunks of the lanes' utterances stay device tensors on the vocoder stream; the chunks of segment k + 1
         wait until segment k has ended; what leaves is one stream in text order.  Segment 0 streams as it decodes."""
         n = len(segs)
+        self._refuse_streaming_loudness()
         tok = self.model.model.speech_tokenizer
         side = self._vocoder_stream(tok)
         oj, chain = self._long_chain(spec, segs, side)
@@ -1868,6 +2050,7 @@ class FasterQwen3TTS:
         """Shared back half of the ``stream_*`` entry points: ``prepare(input_ids)`` builds the step-by-step prompt from the first
         token; the decode loop runs behind the text as it arrives and ``StreamingVocoder`` turns each code chunk into audio."""
         from .text_stream import TextFeeder, fast_generate_text_streaming, pump_text
+        self._refuse_streaming_loudness()
         if isinstance(text_iter, TextFeeder):
             feeder = text_iter
         else:
@@ -1878,7 +2061,8 @@ class FasterQwen3TTS:
         try:
             m, talker, config, tie, tam, _tth, tpe = prepare(self._text_session_ids(feeder))
             tok = m.speech_tokenizer
-            voc = StreamingVocoder(tok, None, chunk_size, self.device, self._vocoder_stream(tok), output=self._audio_spec, **self._exact_kw())
+            voc = StreamingVocoder(tok, None, chunk_size, self.device, self._vocoder_stream(tok), output=self._audio_spec, **self._exact_kw(),
+                                   **self._gain_kw())
             stream = fast_generate_text_streaming(
                 talker=talker, talker_input_embeds=tie, attention_mask=tam, tts_pad_embed=tpe, config=config,
                 predictor_graph=self.predictor_graph, talker_graph=self.talker_graph, feeder=feeder,

@@ -253,8 +253,12 @@ class BatchWorker:
                 waiting.clear()
 
 
+DEFAULT_LOUDNESS_TEXT = "The quick brown fox jumps over the lazy dog, and then it rests beside the quiet river for a while."
+
+
 def create_app(model, voices: Dict[str, dict], default_voice: Optional[str] = None, scheduler: str = "lock", lanes: int = 8,
-               chunk_size: int = 12, worker=None, prefix_cache_rows: int = 0, long_form=None, exact_streaming: bool = False):
+               chunk_size: int = 12, worker=None, prefix_cache_rows: int = 0, long_form=None, exact_streaming: bool = False,
+               loudness: Optional[float] = None, loudness_text: str = DEFAULT_LOUDNESS_TEXT):
     """``worker``: a ready ``BatchWorker`` (or a stand-in with ``submit`` / ``submit_text``) instead of the one ``scheduler="batch"``
     would start.  ``prefix_cache_rows`` > 0: the model's prefix KV cache (``FasterQwen3TTS.enable_prefix_cache``) with that many rows:
     the engine's cache under the ``lock`` scheduler; under ``batch`` the ``BatchWorker`` started here creates the scheduler's own
@@ -263,7 +267,11 @@ def create_app(model, voices: Dict[str, dict], default_voice: Optional[str] = No
     (None: the defaults); under the ``lock`` scheduler ``lanes`` is the number of segments it decodes side by side.
     ``exact_streaming``: the model's ``exact_streaming()`` context is entered for the life of the app -- both schedulers and the text
     sessions then stream the one-pass decode of every utterance instead of the reference's windowing (the vocoders come from
-    ``model.streaming_vocoder``, on whichever thread)."""
+    ``model.streaming_vocoder``, on whichever thread).  ``loudness`` (a target in LUFS; None: off; ``lock`` scheduler only): every
+    configured voice is synthesised once with ``loudness_text`` under ``seeded(0)`` and measured on the device
+    (``model.measure_loudness``); the streamed replies of that voice then run inside ``model.fixed_gain`` with the gain that brings the
+    calibration sentence to the target, and carry ``X-Gain-Db``.  A voice whose measurement is invalid gets 0 dB; ``/health`` lists
+    the gains and says which voices are calibrated."""
     from fastapi import FastAPI, HTTPException
     from .long_form import LongFormSpec
     long_spec = long_form if long_form is not None else LongFormSpec()
@@ -284,6 +292,26 @@ def create_app(model, voices: Dict[str, dict], default_voice: Optional[str] = No
     sessions: Dict[str, dict] = {}
     sessions_lock = threading.Lock()
     sample_rate = int(getattr(model, "sample_rate", 24000))
+    gains: Dict[int, dict] = {}                  # id(voice entry) -> its calibration (``loudness``)
+    if loudness is not None:
+        if worker is not None or scheduler == "batch":
+            raise ValueError("--loudness is served by the lock scheduler (--scheduler lock): the batch worker decodes the voices of many "
+                             "requests in one launch set and has no per-request gain yet")
+        from .loudness import LoudnessSpec
+        loud_spec = LoudnessSpec(target_lufs=float(loudness))
+        if not isinstance(loudness_text, str) or not loudness_text.strip():
+            raise ValueError("--loudness-text must not be empty")
+        for name, vcfg in voices.items():
+            with model.seeded(0):
+                wavs, _sr = model.generate_voice_clone(non_streaming_mode=False, language=vcfg.get("language", "Auto"), text=loudness_text,
+                                                       ref_audio=vcfg.get("ref_audio"), ref_text=vcfg.get("ref_text", ""),
+                                                       voice_clone_prompt=vcfg.get("voice_clone_prompt"),
+                                                       **({"instruct": vcfg["instruct"]} if vcfg.get("instruct") else {}))
+            st = model.measure_loudness(wavs[0], loud_spec)
+            gains[id(vcfg)] = dict(voice=name, calibrated=bool(st.valid), gain_db=round(float(st.gain_db), 3) if st.valid else 0.0,
+                                   lufs=round(float(st.lufs), 3) if st.valid else None)
+            logger.info("loudness: voice %r reads %s LUFS, gain %+.2f dB%s", name, gains[id(vcfg)]["lufs"], gains[id(vcfg)]["gain_db"],
+                        "" if st.valid else " (could not be calibrated)")
 
     def resolve_voice(name: str) -> dict:
         if name in voices:
@@ -363,7 +391,8 @@ def create_app(model, voices: Dict[str, dict], default_voice: Optional[str] = No
         def producer():
             try:
                 with lock, (contextlib.nullcontext() if spec is None else model.audio_output(spec.sample_rate, spec.encoding, spec.speed)), \
-                        (contextlib.nullcontext() if cfg.get("seed") is None else model.seeded(cfg["seed"])):
+                        (contextlib.nullcontext() if cfg.get("seed") is None else model.seeded(cfg["seed"])), \
+                        (contextlib.nullcontext() if cfg.get("gain_db") is None else model.fixed_gain(cfg["gain_db"])):
                     gen = (model.generate_long_voice_clone_streaming(chunk_size=cfg.get("chunk_size", 12), non_streaming_mode=False,
                                                                      lanes=lanes, long_form=long_spec, **clone_kwargs(cfg, text), **instruct_kw)
                            if long else
@@ -506,6 +535,9 @@ def create_app(model, voices: Dict[str, dict], default_voice: Optional[str] = No
             out["prefix_cache"] = prefix_cache.stats()
         if exact_streaming:
             out["exact_streaming"] = True
+        if loudness is not None:
+            out["loudness"] = {"target_lufs": float(loudness),
+                               "voices": {g["voice"]: {k: g[k] for k in ("gain_db", "lufs", "calibrated")} for g in gains.values()}}
         return out
 
     @app.post("/v1/audio/speech")
@@ -522,6 +554,9 @@ def create_app(model, voices: Dict[str, dict], default_voice: Optional[str] = No
             raise HTTPException(status_code=400, detail="response_format='mp3' needs pydub + ffmpeg, which this image does not ship; use wav or pcm")
         spec = request_spec(req, fmt)
         seed = request_seed(req)
+        gain = gains.get(id(cfg))
+        if gain is not None:
+            cfg = dict(cfg, gain_db=gain["gain_db"])
         if seed is not None:
             cfg = dict(cfg, seed=seed)
         n_segments = long_segments(req)
@@ -537,6 +572,8 @@ def create_app(model, voices: Dict[str, dict], default_voice: Optional[str] = No
                 yield raw
 
         headers = dict(seed_headers(seed) or {})
+        if gain is not None:
+            headers["X-Gain-Db"] = f"{gain['gain_db']:.3f}"
         if n_segments > 0:
             headers["X-Segments"] = str(n_segments)
         return StreamingResponse(audio_stream(), media_type=CONTENT_TYPES[fmt], headers=headers or None)
@@ -565,11 +602,18 @@ def build_parser():
     p.add_argument("--exact-streaming", action="store_true",
                    help="stream the one-pass decode of every utterance (codec stream states) instead of the reference's 25-frame windowing: "
                         "the audio no longer depends on the chunk size (default: off)")
+    p.add_argument("--loudness", type=float, default=None, metavar="LUFS",
+                   help="calibrate every voice at start-up (one seeded synthesis of --loudness-text, measured on the device by BS.1770) and "
+                        "stream its replies with the fixed gain that brings that sentence to LUFS; --scheduler lock only (default: off)")
+    p.add_argument("--loudness-text", default=DEFAULT_LOUDNESS_TEXT, metavar="TEXT", help="the calibration sentence of --loudness")
     return p
 
 
 def main(argv=None):
-    args = build_parser().parse_args(argv)
+    parser = build_parser()
+    args = parser.parse_args(argv)
+    if args.loudness is not None and args.scheduler == "batch":
+        parser.error("--loudness is served by the lock scheduler: add --scheduler lock (the batch worker has no per-request gain yet)")
     if args.voices:
         with open(args.voices) as f:
             voices = json.load(f)
@@ -587,7 +631,8 @@ def main(argv=None):
     import uvicorn
     logging.basicConfig(level=logging.INFO)
     uvicorn.run(create_app(model, voices, default_voice, args.scheduler, args.lanes, args.chunk_size,
-                           prefix_cache_rows=args.prefix_cache_rows, exact_streaming=args.exact_streaming), host=args.host, port=args.port)
+                           prefix_cache_rows=args.prefix_cache_rows, exact_streaming=args.exact_streaming, loudness=args.loudness,
+                           loudness_text=args.loudness_text), host=args.host, port=args.port)
 
 
 if __name__ == "__main__":

@@ -672,6 +672,64 @@ int fq3_join_reset(fq3_join* j, void* stream);
 int fq3_join_push(fq3_join* j, const float* pcm, int64_t n_in, int end, int64_t pause_samples, float* out, int64_t capacity,
                   int64_t* n_out_dev, void* stream);
 
+/* ---- Loudness: an ITU-R BS.1770-4 meter (mono, integrated, gated), the gain to a target level, and a gain multiply ----------------
+ * On the vocoder's float32 PCM: the MEASURE is taken in front of the join, time-scale and output stages; the gain is applied in front
+ * of the time-scale and output stages -- in long form behind the join, whose silence decisions see unscaled samples.  Sample peak only (no true peak), no loudness
+ * range, no momentary or short-term meter, no limiter.  The measure does not depend on how the stream was cut into pushes: it is
+ * built from integers.
+ *
+ * Design (host only, no HIP call): in_rate a multiple of 100 in [8000, 48000], target_lufs in [-40, -5], ceiling_db in [-20, 0],
+ * max_gain_db in [0, 40], else FQ3_EINVAL.  H = in_rate / 10 (a hop of 100 ms).  K-weighting = two biquads designed in double by the
+ * bilinear transform (the libebur128 construction; at 48 kHz it reproduces the standard's table):
+ *   shelf      f0 = 1681.974450955533, G = 3.999843853973347 dB, Q = 0.7071752369554196; K = tan(pi f0 / in_rate), Vh = 10^(G / 20),
+ *              Vb = Vh^0.4996667741545416, a0 = 1 + K / Q + K^2;  b = [Vh + Vb K / Q + K^2, 2 (K^2 - Vh), Vh - Vb K / Q + K^2] / a0,
+ *              a1 = 2 (K^2 - 1) / a0, a2 = (1 - K / Q + K^2) / a0
+ *   high-pass  f0 = 38.13547087602444, Q = 0.5003270373238773; b = [1, -2, 1] (not divided by a0), a1 and a2 as above
+ * coef64 / coef32 (each may be NULL; 10 values: shelf b0 b1 b2 a1 a2, high-pass b0 b1 b2 a1 a2) receive the design in double and
+ * rounded to float32 -- the latter is what the device uses.  *abs_gate = floor(10^((-70 + 0.691) / 10) * 4 H * 2^40),
+ * *target_power = 10^((target_lufs + 0.691) / 10), *ceiling = 10^(ceiling_db / 20), *max_gain = 10^(max_gain_db / 20) (any may be NULL).
+ *
+ * Filter: hop h is samples [h H, (h + 1) H).  Its outputs y come from running both biquads FROM ZERO STATE starting at sample
+ * max(0, (h - 1) H); the outputs of that warm-up hop are discarded.  So a hop is a fixed function of at most 2 H samples.  A biquad is
+ * transposed direct form II in fp32:  u = fmaf(b0, x, s1);  s1 = fmaf(-a1, u, fmaf(b1, x, s2));  s2 = fmaf(-a2, u, b2 * x);  the shelf
+ * feeds the high-pass.
+ * Hop energy: E_h = sum over the hop of (uint64) rint((double) min(y * y, 64.0f) * 2^40), y * y in fp32: integers, so the sum is exact
+ * in any order.  Only whole hops count; a tail shorter than a hop is left out of the energies and still counts toward the peak.
+ * Peak: max of fabsf(x) over the finite samples.  n_bad: the samples that are not finite; with n_bad > 0 the energies are unspecified.
+ * Gating and gain (fq3_loud_finish, one launch of one workgroup):
+ *   B_b = E_b + E_b+1 + E_b+2 + E_b+3, b = 0 .. n_hops - 4;   G1 = {b : B_b > abs_gate}, n1 members, S1 their exact integer sum
+ *   S1d = (double) hi * 4294967296.0 + (double) lo with S1 = hi 2^32 + lo (one rounding: the correctly rounded double of S1)
+ *   G2 = {b in G1 : (double) B_b * (double) (10 n1) > S1d}, n2 members, S2d formed likewise
+ *   mean_power = S2d / ((double) n2 * (double) (4 H) * 2^40)
+ *   g = sqrt(target_power / mean_power);  g = min(g, max_gain);  peak > 0: g = min(g, ceiling / (double) peak);  gain = (float) g
+ * in IEEE double multiply, divide, sqrt, compare and convert only.  Fewer than 4 hops, an empty G1 or n_bad > 0: gain = 1.0f, valid = 0.
+ * The host turns mean_power into LUFS: -0.691 + 10 log10(mean_power). */
+typedef struct fq3_loud fq3_loud;
+typedef struct fq3_loud_config { int in_rate; double target_lufs, ceiling_db, max_gain_db; int capacity_hops; } fq3_loud_config;
+typedef struct fq3_loud_stats { double mean_power; float peak, gain; int32_t n_hops, n_abs, n_rel, n_bad, valid, reserved; } fq3_loud_stats;
+int fq3_loud_design(int in_rate, double target_lufs, double ceiling_db, double max_gain_db, int* H, double* coef64, float* coef32,
+                    uint64_t* abs_gate, double* target_power, double* ceiling, double* max_gain);
+/* One object per stream; capacity_hops in [0, 2^20], 0: 4096 hops (about 410 s).  It owns at most 2 H - 1 samples of history (two
+ * buffers, used in turn) and per hop the energy, the peak and the non-finite count, on the current device.  NULL or range errors are
+ * answered before any HIP call. */
+int fq3_loud_create(const fq3_loud_config* cfg, fq3_loud** out);
+int fq3_loud_destroy(fq3_loud* l);                           /* NULL -> 0 */
+/* a new stream on the same object (nothing is enqueued) */
+int fq3_loud_reset(fq3_loud* l, void* stream);
+/* pcm: n_in device floats at any float alignment (n_in may be 0), the next samples of the stream; final != 0: the stream ends with
+ * them.  ONE launch on `stream` (none for an empty push that is not final), no host synchronisation; the hops this push completes are
+ * written by ordinary stores.  More hops than the capacity: FQ3_ETOOLONG.  Every error is answered before anything is launched or
+ * changed.  After a final push: FQ3_ESTATE until fq3_loud_reset. */
+int fq3_loud_push(fq3_loud* l, const float* pcm, int64_t n_in, int final, void* stream);
+/* Only after a final push (else FQ3_ESTATE): gating and gain into *stats_dev (DEVICE memory, 8-byte aligned).  May be repeated. */
+int fq3_loud_finish(fq3_loud* l, fq3_loud_stats* stats_dev, void* stream);
+/* for tests and probes: the energies of the hops completed so far to out_dev_u64 (device, room for `capacity` values; fewer than the
+ * hops: FQ3_EINVAL), their number to *n_hops (host) */
+int fq3_loud_hops(fq3_loud* l, uint64_t* out_dev_u64, int64_t capacity, int64_t* n_hops, void* stream);
+/* out[i] = pcm[i] * *gain_dev, one fp32 multiply, i < n; out may equal pcm; any float alignment; n = 0 launches nothing.  gain_dev: a
+ * DEVICE float, e.g. &stats_dev->gain. */
+int fq3_loud_apply(const float* gain_dev, const float* pcm, int64_t n, float* out, void* stream);
+
 /* ---- Seeded sampling noise: the samplers' Exp(1) variates from a counter-based generator on the device -------------------------
  * The samplers divide by host-provided noise (fq3_sample's noise vector, the rings of fq3_decode_begin).  These calls fill such
  * buffers as a PURE FUNCTION of (seed, emitted-frame index, slot, vocabulary index): no state, no dependence on lane, batch

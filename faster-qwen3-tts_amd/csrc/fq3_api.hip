@@ -5,6 +5,7 @@
 #include "sampler.cuh"
 #include "sampler_wave.cuh"
 #include "skinny_gemm.cuh"
+#include "state_kernels.cuh"
 
 #include <cstdio>
 #include <cstdlib>
@@ -108,11 +109,6 @@ extern "C" int fq3_kv_pool_stats(const fq3_kv_pool* p, int* n_blocks, int* n_fre
     return FQ3_OK;
 }
 
-struct KvTableVals { int v[128]; };
-__global__ void kv_table_write_kernel(int* table, KvTableVals vals, int first, int count) {
-    const int i = threadIdx.x;
-    if (i < count) table[first + i] = vals.v[i];
-}
 // entries [first, first + count) of the device table <- ids (by value in the launch: nothing on the host is read later)
 static void table_write(fq3_ctx* c, const int* ids, int first, int count, hipStream_t s) {
     for (int o = 0; o < count; o += 128) {
@@ -593,18 +589,6 @@ extern "C" int fq3_set_generation_state(fq3_ctx* c, int n_pad, int rope_delta) {
     return FQ3_OK;
 }
 
-// rows [0, L) of one layer between the paged cache and a dense [n_kv][L][128] tensor (the HF layout), 16 bytes per thread
-template <typename T, bool TO_CACHE>
-__global__ __launch_bounds__(256) void kv_paged_copy_kernel(T* cache, const int* table, int blk_stride, T* dense, int n_kv, int L) {
-    constexpr int EPC = 16 / (int)sizeof(T), CPR = kHeadDim / EPC;          // 16-byte chunks per row
-    const int i = blockIdx.x * 256 + threadIdx.x;
-    if (i >= n_kv * L * CPR) return;
-    const int ch = i % CPR, row = i / CPR, key = row % L, h = row / L;
-    T* cp = cache + (size_t)table[key / kKeysPerTile] * blk_stride + ((size_t)h * kKeysPerTile + key % kKeysPerTile) * kHeadDim + ch * EPC;
-    T* dp = dense + ((size_t)h * L + key) * kHeadDim + ch * EPC;
-    if (TO_CACHE) *reinterpret_cast<u32x4*>(cp) = *reinterpret_cast<const u32x4*>(dp);
-    else *reinterpret_cast<u32x4*>(dp) = *reinterpret_cast<const u32x4*>(cp);
-}
 template <typename T, bool TO_CACHE>
 static void kv_paged_copy(fq3_ctx* c, int layer, void* k, void* v, int L, hipStream_t s) {
     const int nk = c->cfg.talker.n_kv_heads, n = nk * L * (kHeadDim * (int)sizeof(T) / 16);
@@ -640,18 +624,6 @@ extern "C" int fq3_kv_export(fq3_ctx* c, int layer, void* k, void* v, int L, voi
     else kv_paged_copy<float, false>(c, layer, k, v, L, s);
     LAUNCH_CHECK();
     return FQ3_OK;
-}
-
-// fq3_kv_adopt between contexts of DIFFERENT pools: whole blocks [0, ceil(L / 64)) of every talker layer, block to block, in one
-// launch: grid (2 * layers, blocks)
-struct KvAdoptTab { void* dst[128]; const void* src[128]; };
-template <typename T>
-__global__ __launch_bounds__(256) void kv_adopt_kernel(KvAdoptTab t, const int* dst_table, const int* src_table, int blk_elems) {
-    const int which = blockIdx.x, b = blockIdx.y;
-    const u32x4* s = reinterpret_cast<const u32x4*>(reinterpret_cast<const T*>(t.src[which]) + (size_t)src_table[b] * blk_elems);
-    u32x4* d = reinterpret_cast<u32x4*>(reinterpret_cast<T*>(t.dst[which]) + (size_t)dst_table[b] * blk_elems);
-    const int n16 = blk_elems * (int)sizeof(T) / 16;
-    for (int i = threadIdx.x; i < n16; i += 256) d[i] = s[i];
 }
 
 extern "C" int fq3_kv_adopt(fq3_ctx* dst, fq3_ctx* src, int L, void* stream) {
@@ -1131,16 +1103,6 @@ extern "C" int fq3_predictor_loop(fq3_ctx* c, const void* pred_input, const void
 // -------------------------------------------------------------------------------------------------
 // Fused on-device decode loop
 // -------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void decode_arm_kernel(DecodeState* st, DecodeState init, unsigned char* seen, int seen_bytes,
-                                                         uint32_t* past_hidden, const uint32_t* ph_src, int ph_words) {
-    for (int i = threadIdx.x; i < seen_bytes / 4; i += 256) reinterpret_cast<uint32_t*>(seen)[i] = 0u;
-    for (int i = threadIdx.x; i < ph_words; i += 256) past_hidden[i] = ph_src[i];
-    if (threadIdx.x == 0) *st = init;
-}
-__global__ void decode_set_forced_kernel(TeacherForcing* tf, const int* forced, int* decisions) {
-    tf->forced = forced; tf->decisions = decisions;
-}
-
 extern "C" int fq3_decode_begin(fq3_ctx* c, const fq3_decode_params* p, void* stream) {
     NEED_BOUND(c);
     if (!p || !p->past_hidden || !p->tts_pad_embed) return fail(FQ3_EINVAL, "null argument");
@@ -1179,7 +1141,6 @@ extern "C" int fq3_decode_begin(fq3_ctx* c, const fq3_decode_params* p, void* st
     return FQ3_OK;
 }
 
-__global__ void decode_cancel_kernel(DecodeState* st) { st->done = 1; }
 extern "C" int fq3_decode_cancel(fq3_ctx* c, void* stream) {
     if (!c) return fail(FQ3_EINVAL, "null ctx");
     hipLaunchKernelGGL(decode_cancel_kernel, dim3(1), dim3(1), 0, (hipStream_t)stream, c->st);
@@ -1266,11 +1227,6 @@ extern "C" int fq3_decode_poll(fq3_ctx* c, int* n_frames_total, int* done, void*
     if (n_frames_total) *n_frames_total = h.frame;
     if (done) *done = h.done == 2 ? 2 : (h.done || h.token == h.eos_id);      // 2: held on an open text table (fq3_decode_text_open)
     return FQ3_OK;
-}
-
-__global__ void codes_to_i64_kernel(const int* src, int64_t* dst, int n) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) dst[i] = src[i];
 }
 
 extern "C" int fq3_decode_codes(fq3_ctx* c, int from, int count, int64_t* out, void* stream) {

@@ -3,6 +3,7 @@
 #define FQ3_SKINNY_EXTERN           // skinny_gemm.cuh: the weight-stationary GEMM kernels are instantiated in fq3_prefill.hip only
 #include "fq3_ctx.h"
 #include "batch_kernels.cuh"
+#include "state_kernels.cuh"
 #include "skinny_gemm.cuh"
 
 #include <algorithm>
@@ -763,16 +764,6 @@ static int batch_frames_one(fq3_batch* b, int n_frames, hipStream_t s) {
 
 extern "C" int fq3_batch_size(const fq3_batch* b) { return b ? b->B : 0; }
 
-namespace {
-__global__ void poll_gather_kernel(LaneSt t, int B, int* out) {
-    const int l = threadIdx.x;
-    if (l < B) {
-        const DecodeState* st = t.st[l];
-        out[2 * l] = st->frame;
-        out[2 * l + 1] = st->done == 2 ? 2 : ((st->done || st->token == st->eos_id) ? 1 : 0);      // fq3_decode_poll's `done`
-    }
-}
-}
 static int poll_prepare(fq3_batch* b) {
     if (b->poll_host) return 0;
     const size_t bytes = (size_t)kPollSlots * 2 * kMaxLanes * sizeof(int);
@@ -812,31 +803,6 @@ extern "C" int fq3_batch_poll_wait(fq3_batch* b, int slot, int* n_frames_total, 
 // The single-lane append (fq3_prompt.hip) costs four launches per lane and streams text_projection's matrices once per lane.  Here the
 // ids of every lane are projected by ONE gather + ONE fc1 + ONE fc2 into a packed [N][H] buffer; one launch scatters row r to its
 // lane's table and one publishes the new lengths.  Rows before lengths, stream order the only synchronisation -- as in the single lane.
-namespace {
-struct AppendDst { void* dst[kMaxLanes]; int first[kMaxLanes + 1]; };        // item i: packed rows [first[i], first[i + 1]) -> dst[i]
-struct AppendPub { DecodeState* st[kMaxLanes]; int rows[kMaxLanes]; int closes[kMaxLanes]; };
-// one workgroup per packed row, 16-byte pieces (a row is H elements, H a multiple of 32: fq3_bind_prompt_weights)
-__global__ __launch_bounds__(256) void text_scatter_kernel(AppendDst a, int n_items, const u32x4* y, int row_vec) {
-    const int r = blockIdx.x;
-    int lo = 0, hi = n_items - 1;                          // the last item whose first row is <= r (items without rows never match)
-    while (lo < hi) {
-        const int mid = (lo + hi + 1) >> 1;
-        if (a.first[mid] <= r) lo = mid; else hi = mid - 1;
-    }
-    u32x4* d = gptr(reinterpret_cast<u32x4*>(a.dst[lo])) + (size_t)(r - a.first[lo]) * row_vec;
-    const u32x4* src = y + (size_t)r * row_vec;
-    for (int e = threadIdx.x; e < row_vec; e += 256) d[e] = src[e];
-}
-__global__ __launch_bounds__(kMaxLanes) void text_publish_lanes_kernel(AppendPub p, int n_items) {
-    const int i = threadIdx.x;
-    if (i < n_items) {
-        DecodeState* st = gptr(p.st[i]);
-        st->trailing_len = p.rows[i];
-        if (p.closes[i]) st->text_open = 0;
-    }
-}
-}  // namespace
-
 extern "C" int fq3_batch_text_append(fq3_batch* b, int n_items, const int32_t* lane, const int32_t* count, const int32_t* final_,
                                      const int64_t* ids, void* stream) {
     if (!b) return fq3_fail_(FQ3_EINVAL, "null batch");

@@ -6,71 +6,11 @@
 #define FQ3_SKINNY_EXTERN           // skinny_gemm.cuh: the weight-stationary GEMM kernels are instantiated in fq3_prefill.hip only
 #include "fq3_ctx.h"
 #include "codec_kernels.cuh"
+#include "prompt_kernels.cuh"
 
 using namespace fq3;
 
 namespace {
-
-template <typename T>
-__global__ __launch_bounds__(256) void text_gather_kernel(const int64_t* ids, const T* table, T* out, int n, int Ht, int vocab) {
-    const int r = blockIdx.x;
-    int64_t id = ids[r];
-    id = id < 0 ? 0 : (id >= vocab ? vocab - 1 : id);            // F.embedding would fault; clamp keeps the launch safe
-    const T* src = table + (size_t)id * Ht;
-    for (int e = threadIdx.x * 8; e < Ht; e += 256 * 8) {
-        Raw8<T> v; ldraw<false>(v, src + e);
-        float f[8]; unpack(v, f);
-        DT<T>::st8(out + (size_t)r * Ht + e, f);
-    }
-}
-
-struct RowTables { const void* t[16]; };
-
-// one workgroup per prompt row
-template <typename T>
-__global__ __launch_bounds__(256) void prompt_rows_kernel(const T* text_rows, int n_text, const int* prog, const int64_t* ref_codes,
-                                                          int n_ref, const T* spk, RowTables tabs, int vocab0, int vocab_rest,
-                                                          T* out, int H) {
-    const int r = blockIdx.x;
-    const int trow = prog[r * 3 + 0], kind = prog[r * 3 + 1], arg = prog[r * 3 + 2];
-    const bool has_text = trow >= 0 && trow < n_text;
-    for (int e = threadIdx.x * 8; e < H; e += 256 * 8) {
-        float c[8], t[8];
-#pragma unroll
-        for (int i = 0; i < 8; ++i) { c[i] = 0.f; t[i] = 0.f; }
-        bool has_codec = true;
-        if (kind == 1) {
-            const int id = arg < 0 ? 0 : (arg >= vocab0 ? vocab0 - 1 : arg);
-            Raw8<T> v; ldraw<false>(v, reinterpret_cast<const T*>(tabs.t[0]) + (size_t)id * H + e);
-            unpack(v, c);
-        } else if (kind == 2) {
-            Raw8<T> v; ldraw<false>(v, spk + e);
-            unpack(v, c);
-        } else if (kind == 3) {
-            const int fr = arg < 0 ? 0 : (arg >= n_ref ? n_ref - 1 : arg);
-#pragma unroll
-            for (int g = 0; g < 16; ++g) {
-                const int vmax = g == 0 ? vocab0 : vocab_rest;
-                int64_t id = ref_codes[(size_t)fr * 16 + g];
-                id = id < 0 ? 0 : (id >= vmax ? vmax - 1 : id);
-                Raw8<T> v; ldraw<false>(v, reinterpret_cast<const T*>(tabs.t[g]) + (size_t)id * H + e);
-                float f[8]; unpack(v, f);
-#pragma unroll
-                for (int i = 0; i < 8; ++i) c[i] += f[i];
-            }
-#pragma unroll
-            for (int i = 0; i < 8; i += 2) DT<T>::rnd2(c[i], c[i + 1]);          // torch: cat(...).sum(1), one rounding
-        } else has_codec = false;
-        if (has_text) {
-            Raw8<T> v; ldraw<false>(v, text_rows + (size_t)trow * H + e);
-            unpack(v, t);
-        }
-        float o[8];
-#pragma unroll
-        for (int i = 0; i < 8; ++i) o[i] = (has_text && has_codec) ? t[i] + c[i] : (has_text ? t[i] : c[i]);
-        DT<T>::st8(out + (size_t)r * H + e, o);
-    }
-}
 
 // the three launches of text_projection(text_embedding(ids)) over workspaces x, h of at least n rows of text_hidden
 template <typename T>
@@ -102,20 +42,6 @@ int text_project_t(fq3_ctx* c, const int64_t* ids, int n, void* out, hipStream_t
     }
     text_project_launch<T>(c, ids, n, c->pw_x, c->pw_h, out, s);
     return 0;
-}
-
-// ---- open text table of the decode loop ----------------------------------------------------------------------------------------
-// The loop state lives in device memory and every replay of the frame graph reads it afresh, so the table may grow between replays:
-// the rows are written first, then ONE thread publishes the new length on the same stream.  Frames queued before see the old length,
-// frames queued after the new one; stream order is the only synchronisation.
-__global__ __launch_bounds__(256) void text_open_kernel(DecodeState* st, uint32_t* table, const uint32_t* rows, int words) {
-    for (int i = threadIdx.x; i < words; i += 256) table[i] = rows[i];
-    __syncthreads();
-    if (threadIdx.x == 0) { st->trailing_text = table; st->text_open = 1; }
-}
-__global__ void text_publish_kernel(DecodeState* st, int rows, int final) {
-    st->trailing_len = rows;
-    if (final) st->text_open = 0;
 }
 
 }  // namespace

@@ -305,7 +305,9 @@ int fq3_text_project(fq3_ctx* ctx, const int64_t* ids, int n, void* out, void* s
 /* Assemble n_rows prompt rows.  prog int32[n_rows][3] = {text_row, kind, arg}: text_row indexes text_rows T[n_text, H]
  * (-1: no text part); kind 0 no codec part, 1 codec_embedding[arg], 2 the speaker embedding spk_embed T[H],
  * 3 the sum over the 16 codebook embeddings of reference frame arg (ref_codes int64[n_ref, 16], model.py:699-712).
- * out[r] = text part + codec part (one rounding), or the single part that is present. */
+ * out[r] = text part + codec part (one rounding), or the single part that is present, or zeros where neither is.
+ * prog is read on the device, so a row cannot be refused: a row of kind 3 when ref_codes is null or n_ref <= 0, a row of
+ * kind 2 when spk_embed is null, and a row of any other kind have no codec part (nothing is read for it). */
 int fq3_prompt_rows(fq3_ctx* ctx, const void* text_rows, int n_text, const int32_t* prog, int n_rows,
                     const int64_t* ref_codes, int n_ref, const void* spk_embed, void* out, void* stream);
 

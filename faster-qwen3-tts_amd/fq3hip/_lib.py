@@ -92,6 +92,14 @@ class LoudConfig(C.Structure):
                 ("capacity_hops", C.c_int)]
 
 
+class LimitConfig(C.Structure):
+    _fields_ = [("in_rate", C.c_int), ("ceiling_db", C.c_double), ("lookahead_ms", C.c_double), ("hold_ms", C.c_double), ("tile", C.c_int)]
+
+
+class LimitStats(C.Structure):
+    _fields_ = [("true_peak", C.c_float), ("min_gain_q23", C.c_uint32), ("n_limited", C.c_int64), ("n_bad", C.c_int64)]
+
+
 class LoudStats(C.Structure):
     _fields_ = [("mean_power", C.c_double), ("peak", C.c_float), ("gain", C.c_float), ("n_hops", i32), ("n_abs", i32), ("n_rel", i32),
                 ("n_bad", i32), ("valid", i32), ("reserved", i32)]
@@ -224,6 +232,14 @@ SIGNATURES = {
     "fq3_join_destroy": (C.c_int, [vp]),
     "fq3_join_reset": (C.c_int, [vp, vp]),
     "fq3_join_push": (C.c_int, [vp, vp, C.c_int64, C.c_int, C.c_int64, vp, C.c_int64, vp, vp]),
+    "fq3_limit_design": (C.c_int, [C.c_int, C.c_double, C.c_double, C.c_double, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_float),
+                                   C.POINTER(C.c_float), C.POINTER(C.c_int)]),
+    "fq3_limit_count": (C.c_int64, [C.c_int, C.c_double, C.c_int64, C.c_int]),
+    "fq3_limit_create": (C.c_int, [C.POINTER(LimitConfig), C.POINTER(vp)]),
+    "fq3_limit_destroy": (C.c_int, [vp]),
+    "fq3_limit_reset": (C.c_int, [vp, vp]),
+    "fq3_limit_push": (C.c_int, [vp, vp, C.c_int64, C.c_int, vp, C.c_int64, C.POINTER(C.c_int64), vp]),
+    "fq3_limit_stats": (C.c_int, [vp, vp, vp]),
     "fq3_loud_design": (C.c_int, [C.c_int, C.c_double, C.c_double, C.c_double, C.POINTER(C.c_int), C.POINTER(C.c_double), C.POINTER(C.c_float),
                                   C.POINTER(C.c_uint64), C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     "fq3_loud_create": (C.c_int, [C.POINTER(LoudConfig), C.POINTER(vp)]),

@@ -151,12 +151,18 @@ def _exact(model, args):
 
 
 def _levelled(model, args):
-    """``--loudness`` / ``--gain-db``: the model's ``loudness`` or ``fixed_gain`` context (the level set on the device), or a no-op."""
+    """``--loudness`` / ``--gain-db``: the model's ``loudness`` or ``fixed_gain`` context (the level set on the device), or a no-op;
+    ``--limiter-db``: the model's ``limiter`` context around it (the limiter runs behind the gain)."""
     import contextlib
-    lufs, gain = getattr(args, "loudness", None), getattr(args, "gain_db", None)
+    lufs, gain, ceiling = getattr(args, "loudness", None), getattr(args, "gain_db", None), getattr(args, "limiter_db", None)
+    stack = contextlib.ExitStack()
     if lufs is not None:
-        return model.loudness(target_lufs=lufs)
-    return contextlib.nullcontext() if gain is None else model.fixed_gain(gain)
+        stack.enter_context(model.loudness(target_lufs=lufs))
+    elif gain is not None:
+        stack.enter_context(model.fixed_gain(gain))
+    if ceiling is not None:
+        stack.enter_context(model.limiter(ceiling_db=ceiling))
+    return stack
 
 
 def check_level_args(parser, args):
@@ -168,6 +174,9 @@ def check_level_args(parser, args):
             LoudnessSpec(target_lufs=args.loudness)
         if getattr(args, "gain_db", None) is not None:
             gain_factor(args.gain_db)
+        if getattr(args, "limiter_db", None) is not None:
+            from .limiter import LimiterSpec
+            LimiterSpec(ceiling_db=args.limiter_db)
     except ValueError as exc:
         parser.error(str(exc))
     if getattr(args, "loudness", None) is None:
@@ -255,7 +264,7 @@ def cmd_serve(args, model=None, lines=None):
         if not pending:
             continue
         start = time.perf_counter()
-        staged = any(getattr(args, k, None) is not None for k in ("out_rate", "encoding", "speed", "gain_db"))
+        staged = any(getattr(args, k, None) is not None for k in ("out_rate", "encoding", "speed", "gain_db", "limiter_db"))
         if len(pending) > 1 and args.mode == "clone" and not staged:      # (the output stage runs per stream: line by line)
             results = model.generate_voice_clone_batch(pending, language=args.language, ref_audio=args.ref_audio, ref_text=args.ref_text,
                                                        xvec_only=args.xvec_only, non_streaming_mode=args.non_streaming_mode,
@@ -309,6 +318,9 @@ def build_parser():
         sp.add_argument("--gain-db", type=float, default=None, metavar="X",
                         help="multiply the audio by 10^(X/20) on the device, in front of --speed / --out-rate / --encoding; no limiter "
                              "(default: off)")
+        sp.add_argument("--limiter-db", type=float, default=None, metavar="DB",
+                        help="true-peak look-ahead limiter on the device behind the gain: no sample leaves above DB dBFS (-20 to 0; 5 ms "
+                             "look-ahead, 20 ms hold); works in every mode, streaming included (default: off)")
         if output:
             sp.add_argument("--loudness", type=float, default=None, metavar="LUFS",
                             help="measure the utterance on the device (ITU-R BS.1770-4, integrated) and scale it to LUFS, at most +20 dB and "

@@ -271,14 +271,22 @@ class StreamingVocoder:
 
     ``exact=True`` (opt-in; the default stays the reference's windowing): no windowing at all -- the utterance owns a codec stream
     state and a chunk's audio is that push's samples, so the chunks concatenate to the one-pass decode of all the codes at any chunk
-    size (see ``_init_exact``).  ``push`` / ``prepare`` / ``flush`` keep their signatures; the output stage sits behind it unchanged."""
+    size (see ``_init_exact``).  ``push`` / ``prepare`` / ``flush`` keep their signatures; the output stage sits behind it unchanged.
+
+    ``gain`` / ``limiter`` (``FasterQwen3TTS.fixed_gain`` / ``limiter``): the chunk is multiplied and then limited on the vocoder's
+    stream, in front of the output stage.  The limiter holds back ``A + 6`` samples of the stream; ``push(..., final=True)`` or
+    ``flush()`` hands them out, with or without an ``output``."""
 
     CONTEXT_FRAMES = 25
 
-    def __init__(self, tok, ref_codes, chunk_size: int, device, side_stream=None, output=None, exact=False, gain=None):
+    def __init__(self, tok, ref_codes, chunk_size: int, device, side_stream=None, output=None, exact=False, gain=None, limiter=None,
+                 limiter_pool=None):
         self.tok, self.ref_codes, self.side = tok, ref_codes, side_stream
         self.output, self.stage, self.header_sent = output, None, False
         self.gain = gain                  # a 1-element float32 device tensor (``FasterQwen3TTS.fixed_gain``) or None
+        # a ``LimiterSpec`` (``FasterQwen3TTS.limiter``) or None; the stage, taken at the first chunk and given back at the last;
+        # ``limiter_pool``: a list the model keeps per (device, stream, spec) -- idle ``Limiter`` objects of finished utterances
+        self.limit_spec, self.limit, self.limit_pool = limiter, None, limiter_pool
         self.dev = torch.device(device) if not isinstance(device, torch.device) else device
         self.exact = bool(exact)
         if self.exact:
@@ -342,18 +350,46 @@ class StreamingVocoder:
         with (contextlib.nullcontext() if self.side is None else torch.cuda.stream(self.side)):
             wav = self.tok.stream_push([self.cstream], codes.unsqueeze(0))[0]
             wav = wav[drop:]              # (the drop is below one frame's samples: the trims of the transposed convs add up to less)
-            wav = self._gained(wav)
+            wav = self._gained(wav, final)
             if self.output is not None:
                 return self._encoded(wav.flatten().float(), final)
             out = _to_numpy(wav)
         return out, int(getattr(self.tok, "sample_rate", 24000))
 
-    def _gained(self, wav):
-        """``wav`` (device tensor, on the vocoder's stream) times the fixed gain, in front of the output stage; without one: ``wav``"""
-        if self.gain is None:
-            return wav
-        from .loudness import apply_gain
-        return apply_gain(wav.flatten().float().contiguous(), self.gain, self.side)
+    def _gained(self, wav, final: bool = False):
+        """``wav`` (device tensor, on the vocoder's stream) times the fixed gain and then through the limiter, in front of the output
+        stage; without either: ``wav``.  The limiter holds back its look-ahead (``A + 6`` samples) until ``final`` or ``flush()``."""
+        if self.gain is not None:
+            from .loudness import apply_gain
+            wav = apply_gain(wav.flatten().float().contiguous(), self.gain, self.side)
+        if self.limit_spec is not None:
+            wav = self.limit_push(wav.flatten().float().contiguous(), final)
+        return wav
+
+    LIMITER_POOL_MAX = 256
+
+    def limit_push(self, wav, final: bool):
+        """``wav`` (contiguous float32 device vector, or None) through this utterance's limiter on the vocoder's stream (without one,
+        the current stream).  The object is taken at the first chunk -- an idle one from the model's pool, reset, or a new one -- and
+        goes back to the pool with the final push: its device buffers are then reused by a later utterance on the same stream
+        instead of being allocated and freed per reply (a free synchronises the device while other lanes run)."""
+        if self.limit is None:
+            try:
+                lim = self.limit_pool.pop() if self.limit_pool else None        # (another thread may take the last one first)
+            except IndexError:
+                lim = None
+            if lim is not None and lim.stream is self.side and lim.dev == (self.dev if self.dev.index is not None else torch.device("cuda", torch.cuda.current_device())) and lim.spec == self.limit_spec:
+                lim.reset()
+                self.limit = lim
+            else:
+                from .limiter import Limiter
+                self.limit = Limiter(self.limit_spec, int(getattr(self.tok, "sample_rate", 24000)), self.dev, self.side)
+        out = self.limit.push(wav, final)
+        if final:
+            lim, self.limit = self.limit, None
+            if self.limit_pool is not None and len(self.limit_pool) < self.LIMITER_POOL_MAX:
+                self.limit_pool.append(lim)
+        return out
 
     def _stage(self):
         """the output stage of this utterance, made at its first chunk (on the vocoder's stream; without one, on the current stream)"""
@@ -374,7 +410,15 @@ class StreamingVocoder:
 
     def flush(self):
         """With an ``output``: ends the stage's stream and returns ``(tail, rate)`` -- the samples it held back as look-ahead -- for an
-        utterance whose last event carried no codes.  Empty after a ``push(..., final=True)``, and without an ``output``."""
+        utterance whose last event carried no codes.  Empty after a ``push(..., final=True)``, and without an ``output``.  With a
+        ``limiter``: ends its stream as well; the ``A + 6`` samples it held back come out (through the ``output`` stage, if any)."""
+        if self.limit is not None:
+            # the limiter's held-back samples: they go out through the output stage, or as they are
+            with (contextlib.nullcontext() if self.side is None else torch.cuda.stream(self.side)):
+                tail = self.limit_push(None, True)
+                if self.output is None:
+                    return tail.cpu().numpy(), int(getattr(self.tok, "sample_rate", 24000))
+            return self._encoded(tail, True)
         if self.output is None:
             return np.zeros(0, dtype=np.float32), int(getattr(self.tok, "sample_rate", 24000))
         st = self._stage()
@@ -395,7 +439,7 @@ class StreamingVocoder:
         with torch.cuda.stream(self.side):
             # (.cpu() synchronises the side stream only)
             wav = self.tok.decode_tensor(codes_in, first_sample, prefix=prefix) if prefix is not None else self.tok.decode_tensor(codes_in, first_sample)
-            wav = self._gained(wav)
+            wav = self._gained(wav, final)
             if self.output is not None:
                 return self._encoded(wav.flatten().float(), final)
             out = _to_numpy(wav)
@@ -458,7 +502,7 @@ class StreamingVocoder:
 
     def push(self, chunk: torch.Tensor, ready_event=None, final=False):
         """``chunk`` LongTensor[n_new, 16] (device) -> (new audio as a host array, sample_rate).  ``final`` (only read with an
-        ``output``): this is the utterance's last chunk, the output stage's tail comes with it."""
+        ``output`` or a ``limiter``): this is the utterance's last chunk, the tail those stages held back comes with it."""
         if self.exact:
             return self._push_exact(chunk, ready_event, final)
         if self.side is not None:
@@ -492,9 +536,9 @@ class StreamingVocoder:
             window = flat[start:]
             n_ctx = window.shape[0] - n_new
             new_audio, sr = self._vocode(window, int(round(n_ctx * self.spf)) if n_ctx > 0 else 0, ready_event)
-        if self.gain is not None:
-            # synchronous tokenizer: its audio is on the host; the chunk is uploaded for the multiply (and the stage behind it)
-            wav = self._gained(torch.from_numpy(np.ascontiguousarray(new_audio, dtype=np.float32)).to(self.dev))
+        if self.gain is not None or self.limit_spec is not None:
+            # synchronous tokenizer: its audio is on the host; the chunk is uploaded for the multiply (and the stages behind it)
+            wav = self._gained(torch.from_numpy(np.ascontiguousarray(new_audio, dtype=np.float32)).to(self.dev), final)
             return self._encoded(wav, final) if self.output is not None else (wav.cpu().numpy(), sr)
         if self.output is not None:
             # synchronous tokenizer: its audio is on the host; the chunk is uploaded for the stage
@@ -519,6 +563,7 @@ class FasterQwen3TTS:
         self._audio_spec = None          # the AudioOutSpec of an open ``audio_output`` context
         self._loud = None                # the LoudnessSession of an open ``loudness`` context
         self._gain = None                # the factor of an open ``fixed_gain`` context
+        self._limit = None               # the LimiterSpec of an open ``limiter`` context
         self._seed = None                # the sampling seed of an open ``seeded`` context
 
     # ---- small helpers pinned by the reference's unit tests ------------------------------------------------
@@ -1041,7 +1086,8 @@ class FasterQwen3TTS:
         """Context manager: inside it every vocoder this model hands out (``streaming_vocoder``, hence every streaming entry point and
         the server's workers) and every one-shot, batch and long-form path multiplies its audio by ``10^(gain_db / 20)`` on the device
         (``fq3_loud_apply``, the factor read from a 1-element device tensor), in front of the time-scale and output stages.
-        ``gain_db`` in [-60, 40].  There is no limiter: float32 output may exceed 1.0, the s16 / G.711 encoders clamp.  Iterate a
+        ``gain_db`` in [-60, 40].  The gain itself does not limit -- float32 output may exceed 1.0, the s16 / G.711 encoders clamp --
+        so stream inside ``limiter()`` as well when the level of what comes is not known.  Iterate a
         streaming generator inside the context.  Outside it nothing changes."""
         from .loudness import gain_factor
         factor = gain_factor(gain_db)
@@ -1052,6 +1098,39 @@ class FasterQwen3TTS:
             yield float(np.float32(factor))
         finally:
             self._gain = prev
+
+    @contextlib.contextmanager
+    def limiter(self, ceiling_db: float = -1.0, lookahead_ms: float = 5.0, hold_ms: float = 20.0):
+        """Context manager: inside it every vocoder this model hands out (``streaming_vocoder``, hence the single-stream streaming
+        entry points and the server's workers) and every one-shot, ``*_batch`` and long-form path runs a true-peak look-ahead
+        limiter on the device (``fq3hip/limiter.py``) directly behind the gain of ``fixed_gain`` / ``loudness``
+        and in front of the time-scale and output stages: no sample leaves above ``ceiling_db`` dBFS (by more than one part in 2^22),
+        whatever the stream does later.  The audio keeps its length and is delayed by ``lookahead_ms`` plus 6 samples inside a stream:
+        a chunk comes out that much shorter, and the samples held back come with the final chunk (or one more, final, chunk).  A
+        stream's output does not depend on the chunk size beyond what the vocoder's windowing does (``exact_streaming``: not at all).
+        The ``*_batch_streaming`` / ``stream_*_batch`` entry points give every utterance its own limiter; long form limits the ONE
+        joined stream, behind the join and the per-segment gains.  Yields the ``LimiterSpec``.  The defaults are not tuned on real
+        voices.  Iterate a streaming generator inside the context.  Outside it nothing changes."""
+        from .limiter import LimiterSpec, design
+        spec = LimiterSpec(ceiling_db, lookahead_ms, hold_ms)
+        design(self.sample_rate, spec)                       # the library's own range checks (host only)
+        prev, self._limit = getattr(self, "_limit", None), spec
+        try:
+            yield spec
+        finally:
+            self._limit = prev
+
+    def _limited(self, x, stream=None):
+        """A whole utterance (contiguous float32 device vector) through the open ``limiter`` context's stage on ``stream`` (None: the
+        current one): one object per (device, stream), kept, reset for every utterance."""
+        from .limiter import Limiter
+        s = stream if stream is not None else torch.cuda.current_stream(x.device)
+        lims = self.__dict__.setdefault("_limiters", {})
+        key = (str(x.device), s.cuda_stream)
+        if key not in lims or lims[key].spec != self._limit:
+            lims[key] = Limiter(self._limit, self.sample_rate, x.device, s)
+        lims[key].reset()
+        return lims[key].push(x, final=True)
 
     def _gain_tensor(self, device=None):
         """the open ``fixed_gain`` context's factor as a 1-element float32 tensor on ``device`` (made once per device), or None"""
@@ -1066,7 +1145,7 @@ class FasterQwen3TTS:
         return g["tensors"][dev]
 
     def _levelling(self) -> bool:
-        return getattr(self, "_loud", None) is not None or getattr(self, "_gain", None) is not None
+        return getattr(self, "_loud", None) is not None or getattr(self, "_gain", None) is not None or getattr(self, "_limit", None) is not None
 
     def _refuse_streaming_loudness(self) -> None:
         if getattr(self, "_loud", None) is not None:
@@ -1097,8 +1176,9 @@ class FasterQwen3TTS:
         return buf
 
     def _level(self, wav, key=None, stream=None, inplace: bool = False):
-        """A whole utterance's waveform (device tensor or host array) as the open ``loudness`` / ``fixed_gain`` context wants it: a
-        float32 device vector, measured and scaled, or multiplied by the fixed factor.  Outside both: ``wav`` itself."""
+        """A whole utterance's waveform (device tensor or host array) as the open ``loudness`` / ``fixed_gain`` / ``limiter`` contexts
+        want it: a float32 device vector, measured and scaled, or multiplied by the fixed factor, and then limited.  Outside all of
+        them: ``wav`` itself."""
         if not self._levelling():
             return wav
         from .loudness import apply_gain, gain_of
@@ -1109,8 +1189,18 @@ class FasterQwen3TTS:
                 x, inplace = x.float().contiguous(), False
         else:
             x, inplace = torch.from_numpy(np.ascontiguousarray(_to_numpy(wav), dtype=np.float32).reshape(-1)).to(dev), True
-        gain = self._gain_tensor(x.device) if self._gain is not None else gain_of(self._measure(x, key, stream))
-        return apply_gain(x, gain, stream, out=x if inplace else None)
+        if self._gain is not None or self._loud is not None:
+            gain = self._gain_tensor(x.device) if self._gain is not None else gain_of(self._measure(x, key, stream))
+            x = apply_gain(x, gain, stream, out=x if inplace else None)
+        if getattr(self, "_limit", None) is None:
+            return x
+        y = self._limited(x, stream)
+        if not inplace:
+            return y
+        # (the limiter reads its tiles' halos while other tiles write: it cannot run in place, so a row levelled in place is copied back)
+        with torch.cuda.stream(stream if stream is not None else torch.cuda.current_stream(x.device)):
+            x.copy_(y)
+        return x
 
     def measure_loudness(self, audio, spec=None):
         """``audio`` (a device tensor or a host array, mono, at the model's rate) -> ``LoudnessStats``: its integrated loudness, sample
@@ -1136,7 +1226,12 @@ class FasterQwen3TTS:
 
     def _gain_kw(self) -> dict:
         """``gain=`` for the vocoders built inside ``fixed_gain`` -- nothing at all outside it (the calls stay what they were)."""
-        return dict(gain=self._gain_tensor()) if getattr(self, "_gain", None) is not None else {}
+        kw = dict(gain=self._gain_tensor()) if getattr(self, "_gain", None) is not None else {}
+        if getattr(self, "_limit", None) is not None:
+            # (the vocoders of one model share the vocoder stream; the pool is per spec, so a change of context starts another)
+            kw["limiter"] = self._limit
+            kw["limiter_pool"] = self.__dict__.setdefault("_limiter_pools", {}).setdefault(self._limit, [])
+        return kw
 
     def _seed_kw(self) -> dict:
         """``seed=`` for the decode loops inside ``seeded`` -- nothing at all outside it (the calls stay what they were)."""
@@ -1163,7 +1258,7 @@ class FasterQwen3TTS:
     def _tail_event(voc, timing: Optional[dict]):
         """After a streaming loop with an output stage: the stage's tail as one more chunk, when the last chunk was not marked final
         (an utterance that ends on a full chunk) -- with that event's timing, no codes, ``is_final``."""
-        if voc.output is None:
+        if voc.output is None and getattr(voc, "limit_spec", None) is None:
             return None
         tail, sr = voc.flush()
         if len(tail) == 0:
@@ -1478,6 +1573,7 @@ class FasterQwen3TTS:
         if not device_audio:
             self._refuse_batch_audio_output()
         gain = None if device_audio else self._gain_tensor()       # (long form multiplies behind the join)
+        limit = None if device_audio else getattr(self, "_limit", None)      # (and limits there, as one stream)
         if seeds is not None:
             # the ``seeds=`` keyword of the public entry points is expanded HERE and in _run_batch_full, nowhere else; a caller that
             # builds its own requests (``rounds``) seeds them itself
@@ -1533,7 +1629,16 @@ class FasterQwen3TTS:
                     from .loudness import apply_gain
                     wav = apply_gain(wav.contiguous(), gain, side)
                 host = landed = None
-                if not device_audio:
+                if limit is not None:
+                    # every utterance's own limiter takes its row: the rows come back shorter by what it holds back, or longer at the end
+                    wav = [vocs[j[0]].limit_push(wav[k].contiguous(), bool(j[1].get("is_final"))) for k, j in enumerate(part)]
+                    host = []
+                    for row in wav:
+                        host.append(torch.empty(row.shape, dtype=row.dtype, pin_memory=True))
+                        host[-1].copy_(row, non_blocking=True)
+                    landed = torch.cuda.Event()
+                    landed.record(side)
+                elif not device_audio:
                     host = torch.empty(wav.shape, dtype=wav.dtype, pin_memory=True)
                     host.copy_(wav, non_blocking=True)
                     landed = torch.cuda.Event()
@@ -1583,7 +1688,7 @@ class FasterQwen3TTS:
                     arr = wav                                      # device rows: whoever takes them works on the vocoder stream
                 else:
                     landed.synchronize()
-                    arr = host.numpy()
+                    arr = [h.numpy() for h in host] if isinstance(host, list) else host.numpy()
                 for k, j in enumerate(part):
                     j[2] = arr[k]
                 yield from part
@@ -1613,11 +1718,16 @@ class FasterQwen3TTS:
                     else:
                         add_job([rid, out_meta, None, (inp, first, ev, vocs[rid].last_prefix)])
                 else:
-                    audio, _sr = vocs[rid].push(codes, ev)
+                    audio, _sr = vocs[rid].push(codes, ev, final=final) if limit is not None else vocs[rid].push(codes, ev)
                     add_job([rid, out_meta, audio, None])
                 n_chunks[rid] += 1
             elif final:
-                add_job([rid, out_meta, np.zeros(1 if codes is None else 0, dtype=np.float32), None])
+                tail = np.zeros(1 if codes is None else 0, dtype=np.float32)
+                if limit is not None and vocs[rid].limit is not None:
+                    launch_open()                                  # the utterance's chunks that still wait go in front of its tail
+                    held, _sr = vocs[rid].flush()
+                    tail = held if len(held) else tail
+                add_job([rid, out_meta, tail, None])
                 n_chunks[rid] += 1
             if more <= 0:
                 for r, m, audio, _job in flush():
@@ -1879,6 +1989,9 @@ class FasterQwen3TTS:
         pauses = [spec.pause_samples(s.pause, self.sample_rate) for s in segs]
         oj = OrderedJoin(join, pauses, chain)
         oj.gains = self._gain_tensor(join.dev)                     # fixed_gain: every joined piece times the one factor
+        if getattr(self, "_limit", None) is not None:
+            from .limiter import Limiter
+            oj.limiter = Limiter(self._limit, self.sample_rate, join.dev, stream)      # behind the join and the gains, one stream
         return oj, chain
 
     def _run_long_full(self, prepared, segs, spec, gen_kwargs, lanes: int) -> Tuple[list, int]:

@@ -226,8 +226,9 @@ class BatchWorker:
                         final = bool(info.get("is_final")) or "error" in info
                         if "error" in info or (codes is None and final and info.get("steps", 0) == 0):
                             out.put(RuntimeError(info.get("error", "generation returned no tokens")))
-                        elif getattr(voc, "output", None) is not None:
-                            # the request asked for a rate / encoding: the chunk comes back encoded; the last one brings the stage's tail
+                        elif getattr(voc, "output", None) is not None or getattr(voc, "limit_spec", None) is not None:
+                            # the request asked for a rate / encoding, or the server limits: the chunk comes back encoded (or float32); the
+                            # last one brings the tail that the output stage / the limiter held back
                             if codes is not None and codes.shape[0] > 0:
                                 audio, _sr = voc.push(codes, info.get("codes_ready_event"), final=final)
                             else:
@@ -258,7 +259,7 @@ DEFAULT_LOUDNESS_TEXT = "The quick brown fox jumps over the lazy dog, and then i
 
 def create_app(model, voices: Dict[str, dict], default_voice: Optional[str] = None, scheduler: str = "lock", lanes: int = 8,
                chunk_size: int = 12, worker=None, prefix_cache_rows: int = 0, long_form=None, exact_streaming: bool = False,
-               loudness: Optional[float] = None, loudness_text: str = DEFAULT_LOUDNESS_TEXT):
+               loudness: Optional[float] = None, loudness_text: str = DEFAULT_LOUDNESS_TEXT, limiter_db: Optional[float] = None):
     """``worker``: a ready ``BatchWorker`` (or a stand-in with ``submit`` / ``submit_text``) instead of the one ``scheduler="batch"``
     would start.  ``prefix_cache_rows`` > 0: the model's prefix KV cache (``FasterQwen3TTS.enable_prefix_cache``) with that many rows:
     the engine's cache under the ``lock`` scheduler; under ``batch`` the ``BatchWorker`` started here creates the scheduler's own
@@ -271,7 +272,10 @@ def create_app(model, voices: Dict[str, dict], default_voice: Optional[str] = No
     configured voice is synthesised once with ``loudness_text`` under ``seeded(0)`` and measured on the device
     (``model.measure_loudness``); the streamed replies of that voice then run inside ``model.fixed_gain`` with the gain that brings the
     calibration sentence to the target, and carry ``X-Gain-Db``.  A voice whose measurement is invalid gets 0 dB; ``/health`` lists
-    the gains and says which voices are calibrated."""
+    the gains and says which voices are calibrated.  ``limiter_db`` (a ceiling in dBFS; None: off; server-wide, both schedulers and
+    the text sessions): the model's ``limiter()`` context is entered for the life of the app, behind the calibration, so every reply
+    leaves through a true-peak look-ahead limiter on the device.  ``loudness`` and ``limiter_db`` together are the safe way to serve a
+    levelled stream: the gain comes from one calibration sentence, and the limiter catches the reply that comes out hotter."""
     from fastapi import FastAPI, HTTPException
     from .long_form import LongFormSpec
     long_spec = long_form if long_form is not None else LongFormSpec()
@@ -312,6 +316,12 @@ def create_app(model, voices: Dict[str, dict], default_voice: Optional[str] = No
                                    lufs=round(float(st.lufs), 3) if st.valid else None)
             logger.info("loudness: voice %r reads %s LUFS, gain %+.2f dB%s", name, gains[id(vcfg)]["lufs"], gains[id(vcfg)]["gain_db"],
                         "" if st.valid else " (could not be calibrated)")
+
+    if limiter_db is not None:
+        if not hasattr(model, "limiter"):
+            raise ValueError("limiter_db: this model has no limiter() context")
+        app.state.limiter = contextlib.ExitStack()
+        app.state.limiter_spec = app.state.limiter.enter_context(model.limiter(ceiling_db=float(limiter_db)))      # (ValueError outside [-20, 0])
 
     def resolve_voice(name: str) -> dict:
         if name in voices:
@@ -538,6 +548,9 @@ def create_app(model, voices: Dict[str, dict], default_voice: Optional[str] = No
         if loudness is not None:
             out["loudness"] = {"target_lufs": float(loudness),
                                "voices": {g["voice"]: {k: g[k] for k in ("gain_db", "lufs", "calibrated")} for g in gains.values()}}
+        if limiter_db is not None:
+            spec = app.state.limiter_spec                   # the LimiterSpec in force, as the model's context yielded it
+            out["limiter"] = {k: float(getattr(spec, k)) for k in ("ceiling_db", "lookahead_ms", "hold_ms")}
         return out
 
     @app.post("/v1/audio/speech")
@@ -606,6 +619,10 @@ def build_parser():
                    help="calibrate every voice at start-up (one seeded synthesis of --loudness-text, measured on the device by BS.1770) and "
                         "stream its replies with the fixed gain that brings that sentence to LUFS; --scheduler lock only (default: off)")
     p.add_argument("--loudness-text", default=DEFAULT_LOUDNESS_TEXT, metavar="TEXT", help="the calibration sentence of --loudness")
+    p.add_argument("--limiter-db", type=float, default=None, metavar="DB",
+                   help="server-wide true-peak look-ahead limiter on the device: no sample of any reply leaves above DB dBFS (-20 to 0); both "
+                        "schedulers and the text sessions.  With --loudness the two together are the safe way to serve a levelled stream: a "
+                        "reply hotter than the calibration sentence is limited instead of clipped (default: off)")
     return p
 
 
@@ -614,6 +631,8 @@ def main(argv=None):
     args = parser.parse_args(argv)
     if args.loudness is not None and args.scheduler == "batch":
         parser.error("--loudness is served by the lock scheduler: add --scheduler lock (the batch worker has no per-request gain yet)")
+    if args.limiter_db is not None and not -20.0 <= args.limiter_db <= 0.0:
+        parser.error("--limiter-db is a ceiling in dBFS, -20 to 0")
     if args.voices:
         with open(args.voices) as f:
             voices = json.load(f)
@@ -632,7 +651,7 @@ def main(argv=None):
     logging.basicConfig(level=logging.INFO)
     uvicorn.run(create_app(model, voices, default_voice, args.scheduler, args.lanes, args.chunk_size,
                            prefix_cache_rows=args.prefix_cache_rows, exact_streaming=args.exact_streaming, loudness=args.loudness,
-                           loudness_text=args.loudness_text), host=args.host, port=args.port)
+                           loudness_text=args.loudness_text, limiter_db=args.limiter_db), host=args.host, port=args.port)
 
 
 if __name__ == "__main__":

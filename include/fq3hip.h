@@ -677,7 +677,7 @@ int fq3_join_push(fq3_join* j, const float* pcm, int64_t n_in, int end, int64_t 
 /* ---- Loudness: an ITU-R BS.1770-4 meter (mono, integrated, gated), the gain to a target level, and a gain multiply ----------------
  * On the vocoder's float32 PCM: the MEASURE is taken in front of the join, time-scale and output stages; the gain is applied in front
  * of the time-scale and output stages -- in long form behind the join, whose silence decisions see unscaled samples.  Sample peak only (no true peak), no loudness
- * range, no momentary or short-term meter, no limiter.  The measure does not depend on how the stream was cut into pushes: it is
+ * range, no momentary or short-term meter; the limiter is a stage of its own (below).  The measure does not depend on how the stream was cut into pushes: it is
  * built from integers.
  *
  * Design (host only, no HIP call): in_rate a multiple of 100 in [8000, 48000], target_lufs in [-40, -5], ceiling_db in [-20, 0],
@@ -731,6 +731,60 @@ int fq3_loud_hops(fq3_loud* l, uint64_t* out_dev_u64, int64_t capacity, int64_t*
 /* out[i] = pcm[i] * *gain_dev, one fp32 multiply, i < n; out may equal pcm; any float alignment; n = 0 launches nothing.  gain_dev: a
  * DEVICE float, e.g. &stats_dev->gain. */
 int fq3_loud_apply(const float* gain_dev, const float* pcm, int64_t n, float* out, void* stream);
+
+/* ---- Limiter: a true-peak look-ahead limiter over the float32 PCM, for streams and one-shot -----------------------------------------
+ * Float32 mono in, float32 out at the same rate, length-preserving, with a fixed latency of A + 6 samples.  Directly behind the gain
+ * (fq3_loud_apply), in front of the time-scale and output stages.  Built from FIR and integer operations only: there is no serial
+ * recursion, and the result does not depend on how the stream was cut into pushes, bit for bit.
+ *
+ * Design (host only, no HIP call; double precision, results rounded once to float32): in_rate in [8000, 48000], ceiling_db in
+ * [-20, 0], c = (float) 10^(ceiling_db / 20); attack A = round(in_rate lookahead_ms / 1000) in [8, 480], hold
+ * H = round(in_rate hold_ms / 1000) in [0, 1920] (round: halves away from zero, so 5 ms at 44 100 Hz is 221); else FQ3_EINVAL.
+ * The detector is a 4x oversampler kept as three fractional-phase rows h_f[0 .. 11], f = 1, 2, 3: with d = (t - 5) - f / 4,
+ * h_f[t] = sinc(d) I0(8 sqrt(1 - (d / 6)^2)) / I0(8) (a Kaiser window, beta 8, six taps each side), each row divided by its sum.
+ * *ceiling receives c, rows (36 floats: h_1, h_2, h_3) the rows, *tile the default tile of the push kernel; any may be NULL.
+ * The defaults callers use (5 ms, 20 ms, -1 dB) are common figures; they have NOT been tuned on real voices.
+ *
+ * With x = 0 outside the stream, and a non-finite sample taken as 0, emitted as 0 and counted in n_bad:
+ *   u_f[n] = sum_t h_f[t] x[n - 5 + t]   from 0.0f over ascending t, every multiply and every add rounded on its own (no fma)
+ *   p[n]   = max(|x[n]|, |u_1[n]|, |u_2[n]|, |u_3[n]|)
+ *   q[n]   = 2^23 if p[n] <= c, else (uint32) floor((c / p[n]) * 2^23), the division correctly rounded in fp32;  outside the
+ *            stream q = 2^23
+ *   m[n]   = min of q[j], j in [n - A - H, n]
+ *   s[n]   = sum of m[n - k], k in [0, A]      ((A + 1) 2^23 < 2^32)
+ *   g[n]   = s[n] / (A + 1), integer division
+ *   y[i]   = x[i] * ((float) g[i + A] * 2^-23)      one fp32 multiply; the conversion and the scaling are exact
+ * Every window that enters g[i + A] contains i, so g[i + A] <= q[i] and |y[i]| <= c (1 + 2^-22) for every sample (the slack is the
+ * division's rounding plus the product's).  The gain starts to fall A samples before a peak, stays down for H samples behind it and
+ * comes back linearly over A + 1 samples.  Minimum, sum and division are exact integer operations: no order needs pinning. */
+typedef struct fq3_limit fq3_limit;
+/* tile: output samples per workgroup, 0 = the default, else a multiple of 256 in [256, 4096]; the result does not depend on it */
+typedef struct fq3_limit_config { int in_rate; double ceiling_db, lookahead_ms, hold_ms; int tile; } fq3_limit_config;
+/* true_peak: the largest p of the stream so far;  min_gain_q23: the smallest g applied (2^23: none below 1);  n_limited: output
+ * samples with g < 2^23;  n_bad: non-finite samples among those emitted.  Accumulated with integer atomic max / add (the bit pattern
+ * of a non-negative float orders as an integer), so they do not depend on any order either. */
+typedef struct fq3_limit_report { float true_peak; uint32_t min_gain_q23; int64_t n_limited, n_bad; } fq3_limit_report;
+int fq3_limit_design(int in_rate, double ceiling_db, double lookahead_ms, double hold_ms, int* A, int* H, float* ceiling, float* rows,
+                     int* tile);
+/* Output samples that exist once the first n_in samples of a stream were pushed: final ? n_in : max(0, n_in - A - 6) -- y[i] reaches
+ * x[i + A + 6].  n_in in [0, 2^31].  A function of the cumulative length alone.  Negative: an FQ3_E* code. */
+int64_t fq3_limit_count(int in_rate, double lookahead_ms, int64_t n_in, int final);
+/* One object per stream; it owns the last 2 A + H + 11 input samples (two buffers, used in turn) and the accumulators behind
+ * fq3_limit_stats on the current device.  NULL or range errors are answered before any HIP call. */
+int fq3_limit_create(const fq3_limit_config* cfg, fq3_limit** out);
+int fq3_limit_destroy(fq3_limit* l);                         /* NULL -> 0 */
+/* a new stream on the same object: the accumulators are cleared on `stream` */
+int fq3_limit_reset(fq3_limit* l, void* stream);
+/* pcm: n_in device floats at any float alignment (n_in may be 0, at most 2^31), the next samples of the stream; final != 0: the
+ * stream ends with them and the held-back samples come out (a final push with n_in = 0 emits the tail; a stream shorter than the
+ * latency is legal).  *n_out (host) = fq3_limit_count(in_rate, lookahead_ms, total so far, final) minus what earlier pushes wrote, known before the launch;
+ * above capacity_samples: FQ3_EINVAL and nothing is launched or changed.  out: device floats at any float alignment, not overlapping
+ * pcm.  ONE launch on `stream` (none for an empty push that is not final), no host synchronisation; pcm and out must stay valid until
+ * the stream has run it.  After a final push: FQ3_ESTATE until fq3_limit_reset. */
+int fq3_limit_push(fq3_limit* l, const float* pcm, int64_t n_in, int final, float* out, int64_t capacity_samples, int64_t* n_out,
+                   void* stream);
+/* the accumulators of the pushes enqueued so far into *stats_dev (DEVICE memory, 8-byte aligned); one launch of one thread */
+int fq3_limit_stats(fq3_limit* l, fq3_limit_report* stats_dev, void* stream);
 
 /* ---- Seeded sampling noise: the samplers' Exp(1) variates from a counter-based generator on the device -------------------------
  * The samplers divide by host-provided noise (fq3_sample's noise vector, the rings of fq3_decode_begin).  These calls fill such

@@ -80,8 +80,9 @@ template <int FMT> __device__ __forceinline__ unsigned audio_encode(float y) {
 // One workgroup: tile_groups consecutive 4-byte words of the output (AudioFmt::per samples each; the words are aligned whatever the
 // alignment of `out`, so the first and the last word of a push may be partial and are then written element by element).
 // LDS: [span_cap floats: the inputs the tile reads][BANK_LDS: L rows of bank_stride floats].
+// `bx` is the tile's index within its push: the single kernel and the group kernel (one push per blockIdx.y) both run this body.
 template <int FMT, bool BANK_LDS>
-__global__ void __launch_bounds__(kAudioThreads) audio_out_kernel(const AudioOutArgs a) {
+__device__ __forceinline__ void audio_out_body(const AudioOutArgs& a, const int bx) {
     extern __shared__ float audio_lds[];
     constexpr int per = AudioFmt<FMT>::per;
     float* xs = audio_lds;
@@ -90,11 +91,11 @@ __global__ void __launch_bounds__(kAudioThreads) audio_out_kernel(const AudioOut
     const int L = a.L, M = a.M, K = a.K;
 
     // the history of the NEXT push: the last HL samples of (history ++ chunk), into the other buffer -- no workgroup of this launch reads it
-    if (blockIdx.x == 0)
+    if (bx == 0)
         for (int j = tid; j < a.HL; j += kAudioThreads) a.hist_next[j] = audio_fetch(a, a.n_in - a.HL + j);
 
     // outputs [d_a, d_b) of this tile
-    const int64_t g0 = (int64_t)blockIdx.x * a.tile_groups;
+    const int64_t g0 = (int64_t)bx * a.tile_groups;
     int64_t d_a = g0 * per - a.shift, d_b = (g0 + a.tile_groups) * per - a.shift;
     if (d_a < 0) d_a = 0;
     if (d_b > a.n_out) d_b = a.n_out;
@@ -152,6 +153,46 @@ __global__ void __launch_bounds__(kAudioThreads) audio_out_kernel(const AudioOut
             }
         }
     }
+}
+
+template <int FMT, bool BANK_LDS>
+__global__ void __launch_bounds__(kAudioThreads) audio_out_kernel(const AudioOutArgs a) {
+    audio_out_body<FMT, BANK_LDS>(a, (int)blockIdx.x);
+}
+
+// ---- a group of pushes in one launch (fq3_audio_out_push_group) ----
+// Grid (the largest tile count over the rows, B): blockIdx.y picks the row, blockIdx.x the tile of that row's push.  The rows share one
+// design -- the bank and the launch plan -- and differ in everything a push derives from its object's state.  The descriptors travel
+// BY VALUE in the kernel's argument block: blockIdx.y is uniform, so a row's fields are scalar loads from the argument segment at a
+// scalar offset, no table in device memory has to be filled (and kept alive) per call, and nothing is copied.  Workgroups past a row's
+// last tile leave before the barrier; workgroup x = 0 of every row writes that row's next history, outputs or not.
+constexpr int kAudioGroupMax = 32;              // FQ3_STAGE_GROUP_MAX
+
+struct AudioRow {
+    const float* pcm;
+    const float* hist;
+    float* hist_next;
+    void* out;
+    int64_t n_in, n_out, e0;
+    int r0, p0, hist_valid, shift;
+};
+
+struct AudioGroupArgs {
+    const float* bank;
+    int L, M, K, HL, tile_groups, span_cap, bank_stride;
+    AudioRow rows[kAudioGroupMax];
+};
+static_assert(sizeof(AudioRow) == 72 && sizeof(AudioGroupArgs) <= 4096, "the descriptors must fit the 4 KB of arguments a launch may carry");
+
+template <int FMT, bool BANK_LDS>
+__global__ void __launch_bounds__(kAudioThreads) audio_out_group_kernel(const AudioGroupArgs g) {
+    const AudioRow& r = g.rows[blockIdx.y];
+    AudioOutArgs a;
+    a.pcm = r.pcm; a.hist = r.hist; a.hist_next = r.hist_next; a.bank = g.bank; a.out = r.out;
+    a.n_in = r.n_in; a.n_out = r.n_out; a.e0 = r.e0; a.r0 = r.r0; a.p0 = r.p0;
+    a.L = g.L; a.M = g.M; a.K = g.K; a.HL = g.HL; a.hist_valid = r.hist_valid; a.shift = r.shift;
+    a.tile_groups = g.tile_groups; a.span_cap = g.span_cap; a.bank_stride = g.bank_stride;
+    audio_out_body<FMT, BANK_LDS>(a, (int)blockIdx.x);
 }
 
 }  // namespace fq3

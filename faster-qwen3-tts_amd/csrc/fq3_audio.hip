@@ -1,6 +1,7 @@
 // Audio output stage behind the C ABI: what happens to the vocoder's float32 PCM before it leaves the device.
 //   fq3_audio_out_design / _count   host only (no HIP call): the polyphase bank of a rate pair and the stream's output count
 //   fq3_audio_out_create / _push    streaming resampler + sample encoder (f32, s16, G.711 mu-law / A-law), ONE launch per push
+//   fq3_audio_out_push_group        the pushes of up to 32 objects of one design in ONE launch, each row bit for bit its single push
 //
 // The rate pair in_rate -> out_rate reduces to L / M (L = out / g, M = in / g, g = gcd).  The prototype is a Kaiser-windowed sinc of
 // half length half = Z m (m = max(L, M), Z zero crossings a side), cutoff rho / m of the up-sampled Nyquist, scaled to sum L; phase
@@ -189,51 +190,145 @@ extern "C" int fq3_audio_out_reset(fq3_audio_out* a, void* stream) {
     return 0;
 }
 
+namespace {
+
+// One push, in the three steps the single and the group entry share, so that a row of a group IS a single push:
+//   check_push_   every refusal, and the number of outputs; the object does not change
+//   plan_push_    what the launch reads of the object's state (AudioOutArgs; a group copies the per-row part into its descriptor)
+//   commit_push_  the object after the launch was enqueued
+int check_push_(const std::string& who, const fq3_audio_out* a, const float* pcm, int64_t n_in, int final, const void* out,
+                int64_t capacity_samples, int64_t* cnt_out) {
+    if (n_in < 0 || capacity_samples < 0 || (n_in > 0 && !pcm)) return fq3_fail_(FQ3_EINVAL, who + ": bad input");
+    if (a->finished) return fq3_fail_(FQ3_ESTATE, who + ": the stream has ended; fq3_audio_out_reset starts the next one");
+    const int64_t cnt = count_(a->r, a->n_in + n_in, final) - a->n_out;
+    if (cnt > capacity_samples)
+        return fq3_fail_(FQ3_EINVAL, who + ": " + std::to_string(cnt) + " output samples, capacity " + std::to_string(capacity_samples));
+    if (cnt > 0 && !out) return fq3_fail_(FQ3_EINVAL, who + ": null output");
+    *cnt_out = cnt;
+    return 0;
+}
+
+inline int per_word_(int fmt) { return fmt == FQ3_PCM_F32 ? 1 : fmt == FQ3_PCM_S16 ? 2 : 4; }
+inline bool has_work_(const fq3_audio_out* a, int64_t n_in, int64_t cnt) { return cnt > 0 || (n_in > 0 && a->HL > 0); }
+inline size_t lds_bytes_(const fq3_audio_out* a) {
+    return ((size_t)a->span_cap + (a->bank_lds ? (size_t)a->r.L * a->bank_stride : 0)) * sizeof(float);
+}
+
+// -> workgroups of the push (at least one: x = 0 writes the next history)
+int64_t plan_push_(const fq3_audio_out* a, const float* pcm, int64_t n_in, void* out, int64_t cnt, AudioOutArgs* kp) {
+    const Ratio& r = a->r;
+    const int per = per_word_(a->cfg.format);
+    AudioOutArgs& k = *kp;
+    k.pcm = pcm; k.hist = a->hist[a->cur]; k.hist_next = a->hist[a->cur ^ 1]; k.bank = a->bank; k.out = out;
+    k.n_in = n_in; k.n_out = cnt;
+    const int64_t u0 = a->n_out * r.M;                    // 64-bit: hours of audio pass 2^31
+    k.e0 = (u0 + r.half) / r.L - a->n_in;
+    k.r0 = (int)((u0 + r.half) % r.L);
+    k.p0 = (int)(u0 % r.L);
+    k.L = r.L; k.M = r.M; k.K = r.K; k.HL = a->HL; k.hist_valid = a->hist_valid;
+    k.shift = (int)(((uintptr_t)out / (uintptr_t)(4 / per)) % (uintptr_t)per);
+    k.tile_groups = a->tile_outputs / per;
+    k.span_cap = a->span_cap; k.bank_stride = a->bank_stride;
+    const int64_t groups = (cnt + k.shift + per - 1) / per;
+    return groups > 0 ? (groups + k.tile_groups - 1) / k.tile_groups : 1;
+}
+
+void commit_push_(fq3_audio_out* a, int64_t n_in, int64_t cnt, int final, bool launched) {
+    const int64_t total = a->n_in + n_in;
+    if (launched && a->HL > 0 && n_in > 0) {
+        a->cur ^= 1;
+        a->hist_valid = (int)(total < a->HL ? total : a->HL);
+    }
+    a->n_in = total;
+    a->n_out += cnt;
+    if (final) a->finished = true;
+}
+
+template <int FMT> void launch_group_(bool bank_lds, dim3 grid, size_t shm, hipStream_t s, const AudioGroupArgs& g) {
+    if (bank_lds) hipLaunchKernelGGL((audio_out_group_kernel<FMT, true>), grid, dim3(kAudioThreads), shm, s, g);
+    else hipLaunchKernelGGL((audio_out_group_kernel<FMT, false>), grid, dim3(kAudioThreads), shm, s, g);
+}
+
+}  // namespace
+
 extern "C" int fq3_audio_out_push(fq3_audio_out* a, const float* pcm, int64_t n_in, int final, void* out, int64_t capacity_samples,
                                   int64_t* n_out, void* stream) {
     if (!a || !n_out) return fq3_fail_(FQ3_EINVAL, "fq3_audio_out_push: null argument");
-    if (n_in < 0 || capacity_samples < 0 || (n_in > 0 && !pcm)) return fq3_fail_(FQ3_EINVAL, "fq3_audio_out_push: bad input");
-    if (a->finished) return fq3_fail_(FQ3_ESTATE, "fq3_audio_out_push: the stream has ended; fq3_audio_out_reset starts the next one");
-    const Ratio& r = a->r;
-    const int64_t total = a->n_in + n_in;
-    const int64_t cnt = count_(r, total, final) - a->n_out;
-    if (cnt > capacity_samples)
-        return fq3_fail_(FQ3_EINVAL, "fq3_audio_out_push: " + std::to_string(cnt) + " output samples, capacity " + std::to_string(capacity_samples));
-    if (cnt > 0 && !out) return fq3_fail_(FQ3_EINVAL, "fq3_audio_out_push: null output");
+    int64_t cnt = 0;
+    if (int rc = check_push_("fq3_audio_out_push", a, pcm, n_in, final, out, capacity_samples, &cnt)) return rc;
     *n_out = cnt;
-    if (cnt > 0 || (n_in > 0 && a->HL > 0)) {
-        const int fmt = a->cfg.format;
-        const int per = fmt == FQ3_PCM_F32 ? 1 : fmt == FQ3_PCM_S16 ? 2 : 4;
+    const bool work = has_work_(a, n_in, cnt);
+    if (work) {
         AudioOutArgs k{};
-        k.pcm = pcm; k.hist = a->hist[a->cur]; k.hist_next = a->hist[a->cur ^ 1]; k.bank = a->bank; k.out = out;
-        k.n_in = n_in; k.n_out = cnt;
-        const int64_t u0 = a->n_out * r.M;                    // 64-bit: hours of audio pass 2^31
-        k.e0 = (u0 + r.half) / r.L - a->n_in;
-        k.r0 = (int)((u0 + r.half) % r.L);
-        k.p0 = (int)(u0 % r.L);
-        k.L = r.L; k.M = r.M; k.K = r.K; k.HL = a->HL; k.hist_valid = a->hist_valid;
-        k.shift = (int)(((uintptr_t)out / (uintptr_t)(4 / per)) % (uintptr_t)per);
-        k.tile_groups = a->tile_outputs / per;
-        k.span_cap = a->span_cap; k.bank_stride = a->bank_stride;
-        const int64_t groups = (cnt + k.shift + per - 1) / per;
-        const int64_t blocks = groups > 0 ? (groups + k.tile_groups - 1) / k.tile_groups : 1;
+        const int64_t blocks = plan_push_(a, pcm, n_in, out, cnt, &k);
         if (blocks > 0x7FFFFFFF) return fq3_fail_(FQ3_EINVAL, "fq3_audio_out_push: chunk too long for one launch");
-        const size_t shm = ((size_t)a->span_cap + (a->bank_lds ? (size_t)r.L * a->bank_stride : 0)) * sizeof(float);
+        const size_t shm = lds_bytes_(a);
         hipStream_t s = (hipStream_t)stream;
-        switch (fmt) {
+        switch (a->cfg.format) {
             case FQ3_PCM_F32: launch_<kPcmF32>(a->bank_lds, (int)blocks, shm, s, k); break;
             case FQ3_PCM_S16: launch_<kPcmS16>(a->bank_lds, (int)blocks, shm, s, k); break;
             case FQ3_PCM_MULAW: launch_<kPcmMulaw>(a->bank_lds, (int)blocks, shm, s, k); break;
             default: launch_<kPcmAlaw>(a->bank_lds, (int)blocks, shm, s, k); break;
         }
         AHIP(hipGetLastError());
-        if (a->HL > 0 && n_in > 0) {
-            a->cur ^= 1;
-            a->hist_valid = (int)(total < a->HL ? total : a->HL);
+    }
+    commit_push_(a, n_in, cnt, final, work);
+    return 0;
+}
+
+extern "C" int fq3_audio_out_push_group(fq3_audio_out* const* objs, int B, const float* const* pcm, const int64_t* n_in, const int* final,
+                                        void* const* out, const int64_t* capacity_samples, int64_t* n_out, void* stream) {
+    if (B < 0 || B > FQ3_STAGE_GROUP_MAX)
+        return fq3_fail_(FQ3_EINVAL, "fq3_audio_out_push_group: B = " + std::to_string(B) + "; a group has 0 to " + std::to_string(FQ3_STAGE_GROUP_MAX) + " rows");
+    if (B == 0) return 0;
+    if (!objs || !pcm || !n_in || !final || !out || !capacity_samples || !n_out) return fq3_fail_(FQ3_EINVAL, "fq3_audio_out_push_group: null array");
+    for (int b = 0; b < B; ++b) {
+        if (!objs[b]) return fq3_fail_(FQ3_EINVAL, "fq3_audio_out_push_group: row " + std::to_string(b) + ": null object");
+        for (int c = 0; c < b; ++c)
+            if (objs[c] == objs[b]) return fq3_fail_(FQ3_EINVAL, "fq3_audio_out_push_group: rows " + std::to_string(c) + " and " + std::to_string(b) + " are the same object");
+        const fq3_audio_out_config &x = objs[0]->cfg, &y = objs[b]->cfg;
+        if (x.in_rate != y.in_rate || x.out_rate != y.out_rate || x.format != y.format || x.zero_crossings != y.zero_crossings)
+            return fq3_fail_(FQ3_EINVAL, "fq3_audio_out_push_group: row " + std::to_string(b) + " has another design (rates, format, zero crossings) than row 0");
+    }
+    // every row is checked and planned before any object moves
+    static_assert(FQ3_STAGE_GROUP_MAX == kAudioGroupMax, "the header's limit is the descriptor table's size");
+    const fq3_audio_out* a0 = objs[0];
+    AudioGroupArgs g{};
+    int64_t cnt[FQ3_STAGE_GROUP_MAX], blocks_max = 1;
+    bool any = false;
+    for (int b = 0; b < B; ++b) {
+        const fq3_audio_out* a = objs[b];
+        if (int rc = check_push_("fq3_audio_out_push_group: row " + std::to_string(b), a, pcm[b], n_in[b], final[b], out[b], capacity_samples[b], &cnt[b]))
+            return rc;
+        AudioOutArgs k{};
+        const int64_t blocks = plan_push_(a, pcm[b], n_in[b], out[b], cnt[b], &k);
+        if (blocks > 0x7FFFFFFF) return fq3_fail_(FQ3_EINVAL, "fq3_audio_out_push_group: row " + std::to_string(b) + ": chunk too long for one launch");
+        if (blocks > blocks_max) blocks_max = blocks;
+        any = any || has_work_(a, n_in[b], cnt[b]);
+        AudioRow& r = g.rows[b];
+        r.pcm = k.pcm; r.hist = k.hist; r.hist_next = k.hist_next; r.out = k.out;
+        r.n_in = k.n_in; r.n_out = k.n_out; r.e0 = k.e0; r.r0 = k.r0; r.p0 = k.p0; r.hist_valid = k.hist_valid; r.shift = k.shift;
+        if (b == 0) {
+            g.bank = k.bank; g.L = k.L; g.M = k.M; g.K = k.K; g.HL = k.HL;
+            g.tile_groups = k.tile_groups; g.span_cap = k.span_cap; g.bank_stride = k.bank_stride;
         }
     }
-    a->n_in = total;
-    a->n_out += cnt;
-    if (final) a->finished = true;
+    if (any) {
+        const dim3 grid((unsigned)blocks_max, (unsigned)B);
+        const size_t shm = lds_bytes_(a0);
+        hipStream_t s = (hipStream_t)stream;
+        switch (a0->cfg.format) {
+            case FQ3_PCM_F32: launch_group_<kPcmF32>(a0->bank_lds, grid, shm, s, g); break;
+            case FQ3_PCM_S16: launch_group_<kPcmS16>(a0->bank_lds, grid, shm, s, g); break;
+            case FQ3_PCM_MULAW: launch_group_<kPcmMulaw>(a0->bank_lds, grid, shm, s, g); break;
+            default: launch_group_<kPcmAlaw>(a0->bank_lds, grid, shm, s, g); break;
+        }
+        AHIP(hipGetLastError());
+    }
+    for (int b = 0; b < B; ++b) {
+        n_out[b] = cnt[b];
+        // a row without work was not worth a launch of its own and moves as its single push would: the history stays where it is
+        commit_push_(objs[b], n_in[b], cnt[b], final[b], has_work_(objs[b], n_in[b], cnt[b]));
+    }
     return 0;
 }

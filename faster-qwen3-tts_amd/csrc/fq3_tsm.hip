@@ -2,6 +2,7 @@
 // output stage (fq3_audio.hip).  Duration changes, pitch does not.
 //   fq3_tsm_design / _count   host only (no HIP call): the parameters and window of a rate, and the stream's output count
 //   fq3_tsm_create / _push    streaming WSOLA (waveform-similarity overlap-add, plain cross-correlation search), ONE launch per push
+//   fq3_tsm_push_group        the pushes of up to 32 objects of one in_rate in ONE launch (a workgroup per row), each row its single push
 //
 // P = speed in per-mille, Hs = round(in_rate / 100), N = 2 Hs, D = Hs, w = periodic Hann of length N.  With x = 0 outside the stream:
 //     a(s) = floor(s Hs P / 1000)          pos(s) = a(s) + delta(s)          pos(-1) = -Hs          delta(0) = 0
@@ -145,49 +146,116 @@ extern "C" int fq3_tsm_reset(fq3_tsm* t, void* stream) {
     return 0;
 }
 
-extern "C" int fq3_tsm_push(fq3_tsm* t, const float* pcm, int64_t n_in, int final, float* out, int64_t capacity_samples,
-                            int64_t* n_out, int32_t* deltas, int64_t deltas_capacity, void* stream) {
-    if (!t || !n_out) return fq3_fail_(FQ3_EINVAL, "fq3_tsm_push: null argument");
-    if (n_in < 0 || capacity_samples < 0 || deltas_capacity < 0 || (n_in > 0 && !pcm)) return fq3_fail_(FQ3_EINVAL, "fq3_tsm_push: bad input");
-    if (t->finished) return fq3_fail_(FQ3_ESTATE, "fq3_tsm_push: the stream has ended; fq3_tsm_reset starts the next one");
+namespace {
+
+// One push, in the steps the single and the group entry share (as in fq3_audio.hip): check_push_ refuses or counts and leaves the
+// object alone, plan_push_ reads the object's state into the kernel's arguments, commit_push_ moves the object.
+int check_push_(const std::string& who, const fq3_tsm* t, const float* pcm, int64_t n_in, int final, const float* out,
+                int64_t capacity_samples, const int32_t* deltas, int64_t deltas_capacity, int64_t* cnt_out) {
+    if (n_in < 0 || capacity_samples < 0 || deltas_capacity < 0 || (n_in > 0 && !pcm)) return fq3_fail_(FQ3_EINVAL, who + ": bad input");
+    if (t->finished) return fq3_fail_(FQ3_ESTATE, who + ": the stream has ended; fq3_tsm_reset starts the next one");
     const Plan& p = t->p;
-    if (n_in > kMaxLength - t->n_in) return fq3_fail_(FQ3_EINVAL, "fq3_tsm_push: stream above 2^50 samples");
+    if (n_in > kMaxLength - t->n_in) return fq3_fail_(FQ3_EINVAL, who + ": stream above 2^50 samples");
     const int64_t total = t->n_in + n_in;
     const int64_t cnt = count_(p, total, final) - t->n_out;
     if (cnt > capacity_samples)
-        return fq3_fail_(FQ3_EINVAL, "fq3_tsm_push: " + std::to_string(cnt) + " output samples, capacity " + std::to_string(capacity_samples));
-    if (cnt > 0 && !out) return fq3_fail_(FQ3_EINVAL, "fq3_tsm_push: null output");
+        return fq3_fail_(FQ3_EINVAL, who + ": " + std::to_string(cnt) + " output samples, capacity " + std::to_string(capacity_samples));
+    if (cnt > 0 && !out) return fq3_fail_(FQ3_EINVAL, who + ": null output");
     const int64_t s0 = t->n_out / p.Hs, n_seg = (cnt + p.Hs - 1) / p.Hs;      // an unfinished stream holds whole segments only
     if (deltas && n_seg > deltas_capacity)
-        return fq3_fail_(FQ3_EINVAL, "fq3_tsm_push: " + std::to_string(n_seg) + " segments, delta capacity " + std::to_string(deltas_capacity));
+        return fq3_fail_(FQ3_EINVAL, who + ": " + std::to_string(n_seg) + " segments, delta capacity " + std::to_string(deltas_capacity));
     if (!final) {
         // what the next segment may reach back to must be inside the history this push leaves (plan_ sizes it; never expected)
         const int64_t S = s0 + n_seg;
         const int64_t reach = S == 0 ? 0 : std::min(a_(p, S), a_(p, S - 1) + p.Hs) - p.Hs;
-        if (total - reach > p.HL) return fq3_fail_(FQ3_ESTATE, "fq3_tsm_push: history too short for the next segment");
+        if (total - reach > p.HL) return fq3_fail_(FQ3_ESTATE, who + ": history too short for the next segment");
     }
-    *n_out = cnt;
-    if (cnt > 0 || n_in > 0) {
-        TsmArgs k{};
-        k.pcm = pcm; k.hist = t->hist[t->cur]; k.hist_next = t->hist[t->cur ^ 1]; k.window = t->window; k.out = out;
-        k.delta_out = deltas; k.state = t->state;
-        k.n_in = n_in; k.n_out = cnt; k.n_seg = n_seg;
-        const int64_t u0 = s0 * p.Hs * p.P;                    // 64-bit: hours of audio pass 2^31
-        k.a0 = u0 / 1000 - t->n_in;
-        k.r0 = (int)(u0 % 1000);
-        k.prev_a = (s0 == 0 ? -(int64_t)p.Hs : a_(p, s0 - 1)) - t->n_in;
-        k.step = (int64_t)p.Hs * p.P;
-        k.Hs = p.Hs; k.HL = p.HL; k.hist_valid = t->hist_valid;
-        k.first_is_zero = s0 == 0;
-        hipLaunchKernelGGL(tsm_kernel, dim3(1), dim3(kTsmThreads), (size_t)tsm_lds_floats(p.Hs) * sizeof(float), (hipStream_t)stream, k);
-        THIP(hipGetLastError());
-        if (n_in > 0) {
-            t->cur ^= 1;
-            t->hist_valid = (int)(total < p.HL ? total : p.HL);
-        }
+    *cnt_out = cnt;
+    return 0;
+}
+
+void plan_push_(const fq3_tsm* t, const float* pcm, int64_t n_in, float* out, int64_t cnt, int32_t* deltas, TsmArgs* kp) {
+    const Plan& p = t->p;
+    const int64_t s0 = t->n_out / p.Hs, n_seg = (cnt + p.Hs - 1) / p.Hs;
+    TsmArgs& k = *kp;
+    k.pcm = pcm; k.hist = t->hist[t->cur]; k.hist_next = t->hist[t->cur ^ 1]; k.window = t->window; k.out = out;
+    k.delta_out = deltas; k.state = t->state;
+    k.n_in = n_in; k.n_out = cnt; k.n_seg = n_seg;
+    const int64_t u0 = s0 * p.Hs * p.P;                    // 64-bit: hours of audio pass 2^31
+    k.a0 = u0 / 1000 - t->n_in;
+    k.r0 = (int)(u0 % 1000);
+    k.prev_a = (s0 == 0 ? -(int64_t)p.Hs : a_(p, s0 - 1)) - t->n_in;
+    k.step = (int64_t)p.Hs * p.P;
+    k.Hs = p.Hs; k.HL = p.HL; k.hist_valid = t->hist_valid;
+    k.first_is_zero = s0 == 0;
+}
+
+void commit_push_(fq3_tsm* t, int64_t n_in, int64_t cnt, int final) {
+    const int64_t total = t->n_in + n_in;
+    if (n_in > 0) {                                        // (a push with input is always launched)
+        t->cur ^= 1;
+        t->hist_valid = (int)(total < t->p.HL ? total : t->p.HL);
     }
     t->n_in = total;
     t->n_out += cnt;
     if (final) t->finished = true;
+}
+
+}  // namespace
+
+extern "C" int fq3_tsm_push(fq3_tsm* t, const float* pcm, int64_t n_in, int final, float* out, int64_t capacity_samples,
+                            int64_t* n_out, int32_t* deltas, int64_t deltas_capacity, void* stream) {
+    if (!t || !n_out) return fq3_fail_(FQ3_EINVAL, "fq3_tsm_push: null argument");
+    int64_t cnt = 0;
+    if (int rc = check_push_("fq3_tsm_push", t, pcm, n_in, final, out, capacity_samples, deltas, deltas_capacity, &cnt)) return rc;
+    *n_out = cnt;
+    if (cnt > 0 || n_in > 0) {
+        TsmArgs k{};
+        plan_push_(t, pcm, n_in, out, cnt, deltas, &k);
+        hipLaunchKernelGGL(tsm_kernel, dim3(1), dim3(kTsmThreads), (size_t)tsm_lds_floats(t->p.Hs) * sizeof(float), (hipStream_t)stream, k);
+        THIP(hipGetLastError());
+    }
+    commit_push_(t, n_in, cnt, final);
+    return 0;
+}
+
+extern "C" int fq3_tsm_push_group(fq3_tsm* const* objs, int B, const float* const* pcm, const int64_t* n_in, const int* final,
+                                  float* const* out, const int64_t* capacity_samples, int64_t* n_out, void* stream) {
+    if (B < 0 || B > FQ3_STAGE_GROUP_MAX)
+        return fq3_fail_(FQ3_EINVAL, "fq3_tsm_push_group: B = " + std::to_string(B) + "; a group has 0 to " + std::to_string(FQ3_STAGE_GROUP_MAX) + " rows");
+    if (B == 0) return 0;
+    if (!objs || !pcm || !n_in || !final || !out || !capacity_samples || !n_out) return fq3_fail_(FQ3_EINVAL, "fq3_tsm_push_group: null array");
+    for (int b = 0; b < B; ++b) {
+        if (!objs[b]) return fq3_fail_(FQ3_EINVAL, "fq3_tsm_push_group: row " + std::to_string(b) + ": null object");
+        for (int c = 0; c < b; ++c)
+            if (objs[c] == objs[b]) return fq3_fail_(FQ3_EINVAL, "fq3_tsm_push_group: rows " + std::to_string(c) + " and " + std::to_string(b) + " are the same object");
+        if (objs[b]->p.Hs != objs[0]->p.Hs)
+            return fq3_fail_(FQ3_EINVAL, "fq3_tsm_push_group: row " + std::to_string(b) + " has another in_rate (hop) than row 0");
+    }
+    // every row is checked and planned before any object moves
+    static_assert(FQ3_STAGE_GROUP_MAX == kTsmGroupMax, "the header's limit is the descriptor table's size");
+    TsmGroupArgs g{};
+    g.window = objs[0]->window; g.Hs = objs[0]->p.Hs;
+    int64_t cnt[FQ3_STAGE_GROUP_MAX];
+    bool any = false;
+    for (int b = 0; b < B; ++b) {
+        if (int rc = check_push_("fq3_tsm_push_group: row " + std::to_string(b), objs[b], pcm[b], n_in[b], final[b], out[b], capacity_samples[b], nullptr, 0, &cnt[b]))
+            return rc;
+        TsmArgs k{};
+        plan_push_(objs[b], pcm[b], n_in[b], out[b], cnt[b], nullptr, &k);
+        any = any || cnt[b] > 0 || n_in[b] > 0;
+        TsmRow& r = g.rows[b];
+        r.pcm = k.pcm; r.hist = k.hist; r.hist_next = k.hist_next; r.out = k.out; r.state = k.state;
+        r.n_in = k.n_in; r.n_out = k.n_out; r.n_seg = k.n_seg; r.a0 = k.a0; r.prev_a = k.prev_a; r.step = k.step;
+        r.r0 = k.r0; r.HL = k.HL; r.hist_valid = k.hist_valid; r.first_is_zero = k.first_is_zero;
+    }
+    if (any) {
+        hipLaunchKernelGGL(tsm_group_kernel, dim3((unsigned)B), dim3(kTsmThreads), (size_t)tsm_lds_floats(g.Hs) * sizeof(float), (hipStream_t)stream, g);
+        THIP(hipGetLastError());
+    }
+    for (int b = 0; b < B; ++b) {
+        n_out[b] = cnt[b];
+        commit_push_(objs[b], n_in[b], cnt[b], final[b]);
+    }
     return 0;
 }

@@ -56,7 +56,8 @@ __device__ __forceinline__ bool tsm_better(float v2, int i2, float v1, int i1) {
 // LDS (floats): [4 Hs + 4 candidate samples][2 Hs template][2 Hs window][8 x (2 Hs + 4) partial sums][16 wave values][16 wave indices]
 __host__ __device__ inline int tsm_lds_floats(int Hs) { return 24 * Hs + 4 + 8 * 4 + 32; }
 
-__global__ void __launch_bounds__(kTsmThreads) tsm_kernel(const TsmArgs a) {
+// One workgroup, one push: the single kernel and the group kernel (one push per workgroup) both run this body.
+__device__ __forceinline__ void tsm_body(const TsmArgs& a) {
     extern __shared__ float tsm_lds[];
     const int Hs = a.Hs, N = 2 * Hs, D = Hs, n_cand = 2 * D + 1;
     const int n_grp = (n_cand + 3) / 4, p_stride = 4 * n_grp, J = N / kTsmSlices;      // Hs is a multiple of 16: J of 4
@@ -133,6 +134,42 @@ __global__ void __launch_bounds__(kTsmThreads) tsm_kernel(const TsmArgs a) {
         prev_pos = a_i + delta;
     }
     if (tid == 0 && a.n_seg > 0) a.state[0] = delta;
+}
+
+__global__ void __launch_bounds__(kTsmThreads) tsm_kernel(const TsmArgs a) { tsm_body(a); }
+
+// ---- a group of pushes in one launch (fq3_tsm_push_group) ----
+// Grid B, one workgroup per row: each row's segment chain is serial, the rows' chains run side by side.  The rows share the hop (one
+// in_rate, so one window and one LDS layout); the speed enters only the host-computed fields (a0, prev_a, step, r0, HL) and may differ
+// per row.  The descriptors travel BY VALUE in the kernel's argument block, as in audio_kernels.cuh: blockIdx.x is uniform, so a row's
+// fields are scalar loads from the argument segment.  A row with nothing to do (n_in = 0, n_seg = 0) stages the window and leaves.
+constexpr int kTsmGroupMax = 32;                // FQ3_STAGE_GROUP_MAX
+
+struct TsmRow {
+    const float* pcm;
+    const float* hist;
+    float* hist_next;
+    float* out;
+    int* state;
+    int64_t n_in, n_out, n_seg, a0, prev_a, step;
+    int r0, HL, hist_valid, first_is_zero;
+};
+
+struct TsmGroupArgs {
+    const float* window;
+    int Hs;
+    TsmRow rows[kTsmGroupMax];
+};
+static_assert(sizeof(TsmRow) == 104 && sizeof(TsmGroupArgs) <= 4096, "the descriptors must fit the 4 KB of arguments a launch may carry");
+
+__global__ void __launch_bounds__(kTsmThreads) tsm_group_kernel(const TsmGroupArgs g) {
+    const TsmRow& r = g.rows[blockIdx.x];
+    TsmArgs a;
+    a.pcm = r.pcm; a.hist = r.hist; a.hist_next = r.hist_next; a.window = g.window; a.out = r.out;
+    a.delta_out = nullptr; a.state = r.state;
+    a.n_in = r.n_in; a.n_out = r.n_out; a.n_seg = r.n_seg; a.a0 = r.a0; a.prev_a = r.prev_a; a.step = r.step;
+    a.r0 = r.r0; a.Hs = g.Hs; a.HL = r.HL; a.hist_valid = r.hist_valid; a.first_is_zero = r.first_is_zero;
+    tsm_body(a);
 }
 
 }  // namespace fq3

@@ -17,6 +17,7 @@ LIB_PATH = os.path.join(os.path.dirname(_HERE), "lib", "libfq3hip.so")
 
 FQ3_BF16, FQ3_F32, FQ3_BF16X2 = 0, 1, 2
 FQ3_PCM_F32, FQ3_PCM_S16, FQ3_PCM_MULAW, FQ3_PCM_ALAW = 0, 1, 2, 3
+FQ3_STAGE_GROUP_MAX = 32          # rows of one fq3_audio_out_push_group / fq3_tsm_push_group
 FQ3_OK, FQ3_EINVAL, FQ3_EHIP, FQ3_ESTATE, FQ3_ETOOLONG, FQ3_EUNSUPPORTED, FQ3_ENOMEM = 0, -1, -2, -3, -4, -5, -6
 
 vp = C.c_void_p
@@ -220,6 +221,11 @@ SIGNATURES = {
     "fq3_tsm_destroy": (C.c_int, [vp]),
     "fq3_tsm_reset": (C.c_int, [vp, vp]),
     "fq3_tsm_push": (C.c_int, [vp, vp, C.c_int64, C.c_int, vp, C.c_int64, C.POINTER(C.c_int64), vp, C.c_int64, vp]),
+    # host arrays of B entries: objects, pcm pointers, lengths, final flags, output pointers, capacities, counts (out); then the stream
+    "fq3_audio_out_push_group": (C.c_int, [C.POINTER(vp), C.c_int, C.POINTER(vp), C.POINTER(C.c_int64), C.POINTER(C.c_int),
+                                           C.POINTER(vp), C.POINTER(C.c_int64), C.POINTER(C.c_int64), vp]),
+    "fq3_tsm_push_group": (C.c_int, [C.POINTER(vp), C.c_int, C.POINTER(vp), C.POINTER(C.c_int64), C.POINTER(C.c_int),
+                                     C.POINTER(vp), C.POINTER(C.c_int64), C.POINTER(C.c_int64), vp]),
     "fq3_flac_design": (C.c_int, [C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "fq3_flac_header": (C.c_int, [C.c_int, C.c_int, C.c_int64, vp, C.c_int64]),
     "fq3_flac_count": (C.c_int64, [C.c_int, C.c_int, C.c_int64, C.c_int]),

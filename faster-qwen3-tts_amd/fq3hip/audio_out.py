@@ -8,6 +8,7 @@ then is FLAC frames, and the 42-byte stream header comes from the host (``flac_h
 
 ``AudioOutSpec``  what a caller asks for (rate, encoding, speed); host only, validates without a GPU
 ``AudioOut``      one stream's time-scale + resampler + encoder state on a device
+``push_group`` / ``push_group_host`` / ``GroupCopy``  many streams' pushes in one launch per stage (the lock-step batch; section 4.17)
 ``resample_device``  one-shot form, host array in, host array out"""
 from __future__ import annotations
 
@@ -317,6 +318,183 @@ class AudioOut:
             self.n_out = out_total
         self.finished = self.finished or bool(final)
         return out[:need]
+
+
+# ---- a group of streams in one launch set (the lock-step batch) -----------------------------------------
+GROUP_MAX = _lib.FQ3_STAGE_GROUP_MAX
+
+
+class _Row:
+    """one stage's share of a group push: its input, the counts its ``push`` would reach, and where its output lies in the buffer"""
+    __slots__ = ("st", "x", "n", "final", "n_mid", "need", "mid_total", "out_total", "off", "mid_off", "flac_off", "flac_cap", "frames")
+
+
+def _align(n: int, a: int) -> int:
+    return (n + a - 1) // a * a
+
+
+def _call_group(fn, handles, ptrs, lens, finals, outs, caps, sp) -> list:
+    """``fn`` = fq3_audio_out_push_group / fq3_tsm_push_group over up to GROUP_MAX rows per call -> the rows' counts"""
+    got = []
+    for i in range(0, len(handles), GROUP_MAX):
+        j = min(len(handles), i + GROUP_MAX)
+        B = j - i
+        n_out = (C.c_int64 * B)()
+        _lib.check(fn((C.c_void_p * B)(*handles[i:j]), B, (C.c_void_p * B)(*ptrs[i:j]), (C.c_int64 * B)(*lens[i:j]),
+                      (C.c_int * B)(*finals[i:j]), (C.c_void_p * B)(*outs[i:j]), (C.c_int64 * B)(*caps[i:j]), n_out, sp))
+        got.extend(int(v) for v in n_out)
+    return got
+
+
+def _push_group(stages, pcms, finals):
+    """The launches of ``push_group``: -> (the uint8 device buffer every row's output lies in, the rows, the stream)."""
+    if not (len(stages) == len(pcms) == len(finals)):
+        raise ValueError("push_group: one pcm and one final flag per stage")
+    if len(set(map(id, stages))) != len(stages):
+        raise ValueError("push_group: the same stage twice in one call")
+    if not stages:
+        return None, [], None
+    lib, dev, s = stages[0]._lib, stages[0].dev, stages[0]._stream()
+    rows = []
+    for st, pcm, final in zip(stages, pcms, finals):
+        if st.dev != dev or st._stream().cuda_stream != s.cuda_stream:
+            raise ValueError("push_group: the stages of one call share a device and a stream")
+        if st.finished:
+            st.push_into(None, False, None)                    # the library's own answer (FQ3_ESTATE), as ``push`` gives it
+        r = _Row()
+        r.st, r.final, r.x = st, bool(final), (st._empty if pcm is None else pcm.reshape(-1))
+        rows.append(r)
+    with torch.cuda.device(dev), torch.cuda.stream(s):
+        # buckets in order of first appearance: the rows of one resample + encode design, and the rows the time-scale stage writes itself
+        buckets: dict = {}
+        cursor = mid_cursor = 0
+        for r in rows:
+            st = r.st
+            if r.x.dtype != torch.float32 or r.x.device != dev or not r.x.is_contiguous():
+                r.x = r.x.to(device=dev, dtype=torch.float32).contiguous()
+            r.n = int(r.x.numel())
+            r.mid_total, r.out_total = st._counts(st.n_in + r.n, r.final)
+            r.n_mid, r.need = r.mid_total - st.n_mid, r.out_total - st.n_samples
+            key = (st.in_rate, st.out_rate, ENCODINGS[st.spec.encoding], st.zero) if st._encode else (st.in_rate,)
+            buckets.setdefault(key, []).append(r)
+            r.mid_off = None
+            if st._tsm and st._encode:
+                r.mid_off, mid_cursor = mid_cursor, mid_cursor + r.n_mid
+        for members in buckets.values():
+            cursor = _align(cursor, 16)
+            for r in members:                                  # back to back: a row starts at whatever element offset it falls on
+                r.off, cursor = cursor, cursor + r.need * r.st.dtype.itemsize
+        for r in rows:
+            r.flac_off = None
+            if r.st.flac:
+                st, before = r.st, r.st.n_samples
+                r.frames = flac_count(st.out_rate, st.flac_block, r.out_total, r.final) - flac_count(st.out_rate, st.flac_block, before, False)
+                r.flac_cap = r.frames * st.flac_bound
+                cursor = _align(cursor, 8)
+                r.flac_off, cursor = cursor, cursor + 8 + r.flac_cap
+        buf = torch.empty(cursor, dtype=torch.uint8, device=dev)
+        mid = torch.empty(mid_cursor, dtype=torch.float32, device=dev)
+        base, mid_base, sp = buf.data_ptr(), mid.data_ptr(), C.c_void_p(s.cuda_stream)
+        # one time-scale launch per in_rate over the rows with a speed ...
+        by_rate: dict = {}
+        for r in rows:
+            if r.st._tsm:
+                by_rate.setdefault(r.st.in_rate, []).append(r)
+        for members in by_rate.values():
+            outs = [(mid_base + 4 * r.mid_off if r.mid_off is not None else base + r.off) if r.n_mid else None for r in members]
+            got = _call_group(lib.fq3_tsm_push_group, [r.st._tsm.value for r in members], [r.x.data_ptr() if r.n else None for r in members],
+                              [r.n for r in members], [int(r.final) for r in members], outs, [r.n_mid for r in members], sp)
+            assert got == [r.n_mid for r in members]
+        # ... then one resample + encode launch per design
+        for key, members in buckets.items():
+            if len(key) == 1:
+                continue
+            ins = [((mid_base + 4 * r.mid_off, r.n_mid) if r.mid_off is not None else (r.x.data_ptr(), r.n)) for r in members]
+            got = _call_group(lib.fq3_audio_out_push_group, [r.st._h.value for r in members], [p if n else None for p, n in ins],
+                              [n for _p, n in ins], [int(r.final) for r in members], [base + r.off if r.need else None for r in members],
+                              [r.need for r in members], sp)
+            assert got == [r.need for r in members]
+        # FLAC: frame sizes depend on the data, so every flac row's s16 samples go through its own launch pair, into this buffer as well
+        for r in rows:
+            if r.flac_off is not None:
+                got = C.c_int64()
+                _lib.check(lib.fq3_flac_push(r.st._flac, C.c_void_p(base + r.off if r.need else None), r.need, int(r.final),
+                                             C.c_void_p(base + r.flac_off + 8 if r.flac_cap else None), r.flac_cap, C.byref(got),
+                                             C.c_void_p(base + r.flac_off), sp))
+                assert got.value == r.frames
+        for r in rows:
+            if r.n:
+                r.x.record_stream(s)
+            st = r.st
+            st.n_in += r.n
+            st.n_mid, st.n_samples = r.mid_total, r.out_total
+            if not st.flac:
+                st.n_out = r.out_total
+            st.finished = st.finished or r.final
+    return buf, rows, s
+
+
+def push_group(stages, pcms, finals) -> list:
+    """``[stages[i].push(pcms[i], finals[i]) for i]`` -- the same device tensors, bit for bit, and the same counters on every stage --
+    with ONE time-scale launch for the rows that have a speed and ONE resample + encode launch per distinct (rates, encoding) instead
+    of one or two launches per row (``fq3_tsm_push_group`` / ``fq3_audio_out_push_group``, up to 32 rows a call).  The stages share a
+    device and a stream; ``pcms[i]`` is a float32 device vector or None.  All outputs lie in one device buffer, the rows of a design
+    back to back.  A ``flac`` row takes its s16 half in the group launch and then its own ``fq3_flac_push``; as in ``push``, reading
+    how many bytes its frames took synchronises the stream (once for the call)."""
+    buf, rows, s = _push_group(stages, pcms, finals)
+    out = []
+    lens = None
+    if any(r.flac_off is not None for r in rows):
+        with torch.cuda.stream(s):
+            heads = torch.cat([buf[r.flac_off: r.flac_off + 8] for r in rows if r.flac_off is not None])
+            lens = iter(heads.cpu().view(torch.int64).tolist())                                  # the one synchronisation
+    for r in rows:
+        if r.flac_off is not None:
+            n = int(next(lens))
+            r.st.n_out += n
+            out.append(buf[r.flac_off + 8: r.flac_off + 8 + n])
+        else:
+            out.append(buf[r.off: r.off + r.need * r.st.dtype.itemsize].view(r.st.dtype))
+    return out
+
+
+class GroupCopy:
+    """``push_group`` on its way to the host: every row of the call in ONE pinned buffer behind ONE copy.  ``rows()`` waits for the
+    copy (the call's only synchronisation) and returns the rows as host arrays; the stages' byte counts of ``flac`` rows move then."""
+
+    def __init__(self, stages, pcms, finals):
+        buf, self._rows, s = _push_group(stages, pcms, finals)
+        self.host = self.event = None
+        if self._rows:
+            with torch.cuda.stream(s):
+                self.host = torch.empty(buf.shape, dtype=torch.uint8, pin_memory=True)
+                self.host.copy_(buf, non_blocking=True)
+                self.event = torch.cuda.Event()
+                self.event.record(s)
+            self._buf = buf                                    # alive until the copy has run
+
+    def rows(self) -> list:
+        if self.event is not None:
+            self.event.synchronize()
+            self.event = self._buf = None
+        out = []
+        h = self.host.numpy() if self.host is not None else None
+        for r in self._rows:
+            if r.flac_off is not None:
+                n = int(h[r.flac_off: r.flac_off + 8].view(np.int64)[0])
+                if r.frames is not None:
+                    r.st.n_out += n
+                    r.frames = None                            # counted once, however often the rows are read
+                out.append(h[r.flac_off + 8: r.flac_off + 8 + n])
+            else:
+                out.append(h[r.off: r.off + r.need * r.st.dtype.itemsize].view(NUMPY_DTYPES[r.st.spec.encoding]))
+        return out
+
+
+def push_group_host(stages, pcms, finals) -> list:
+    """``push_group`` with the results on the host -- ``[stages[i].push_host(pcms[i], finals[i]) for i]`` -- all rows in one pinned
+    copy and one synchronisation (``GroupCopy`` is the form that does not wait)."""
+    return GroupCopy(stages, pcms, finals).rows()
 
 
 def resample_device(audio: np.ndarray, sr: int, target_sr: int, device) -> np.ndarray:

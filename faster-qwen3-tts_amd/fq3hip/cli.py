@@ -137,6 +137,15 @@ def _output_stage(model, args):
     return model.audio_output(rate, enc or "f32", 1.0 if speed is None else speed)
 
 
+def _output_spec(args):
+    """``--out-rate`` / ``--encoding`` / ``--speed`` as the ``output=`` of the batch entry points: an ``AudioOutSpec``, or None."""
+    rate, enc, speed = getattr(args, "out_rate", None), getattr(args, "encoding", None), getattr(args, "speed", None)
+    if rate is None and enc is None and speed is None:
+        return None
+    from .audio_out import AudioOutSpec
+    return AudioOutSpec(rate, enc or "f32", 1.0 if speed is None else speed)
+
+
 def _seeded(model, args):
     """``--seed``: the model's ``seeded`` context, or a no-op."""
     import contextlib
@@ -264,11 +273,13 @@ def cmd_serve(args, model=None, lines=None):
         if not pending:
             continue
         start = time.perf_counter()
-        staged = any(getattr(args, k, None) is not None for k in ("out_rate", "encoding", "speed", "gain_db", "limiter_db"))
-        if len(pending) > 1 and args.mode == "clone" and not staged:      # (the output stage runs per stream: line by line)
+        levelled = any(getattr(args, k, None) is not None for k in ("gain_db", "limiter_db"))
+        if len(pending) > 1 and args.mode == "clone" and not levelled:    # (--gain-db / --limiter-db: line by line, as before)
+            # --out-rate / --encoding / --speed: the lines decoded together go through the output stage together (``output=``)
+            spec = _output_spec(args)
             results = model.generate_voice_clone_batch(pending, language=args.language, ref_audio=args.ref_audio, ref_text=args.ref_text,
                                                        xvec_only=args.xvec_only, non_streaming_mode=args.non_streaming_mode,
-                                                       lanes=args.lanes, **_gen_kwargs(args))
+                                                       lanes=args.lanes, **_gen_kwargs(args), **({} if spec is None else dict(output=spec)))
             outs = [(r[0][0], r[1]) for r in results]
         else:
             with _levelled(model, args), _output_stage(model, args), _exact(model, args):

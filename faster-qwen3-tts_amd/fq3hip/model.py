@@ -37,6 +37,23 @@ def _to_numpy(a) -> np.ndarray:
     return a.flatten() if hasattr(a, "flatten") else a
 
 
+class _Encoded:
+    """One utterance of a ``_SideVocoder`` group that went through the output stage: row ``index`` of the group's one pinned copy."""
+
+    def __init__(self, copy, index: int, stage, give):
+        self.copy, self.index, self.stage, self.give = copy, index, stage, give
+
+    def array(self) -> np.ndarray:
+        """the encoded utterance (waits for the copy); ``flac``: the whole file, its header carries the sample count"""
+        a, st = self.copy.rows()[self.index], self.stage
+        if st.flac:
+            a = np.concatenate([np.frombuffer(st.header(st.n_samples), dtype=np.uint8), a])
+        else:
+            a = a.copy()
+        self.give(st)
+        return a
+
+
 class _SideVocoder:
     """Non-streaming vocoding of whole utterances off the decode stream (batched generation): ``submit`` enqueues the codec
     decode + the device-to-pinned-host copy on a side stream after the codes are ready, ``collect`` waits and returns the
@@ -55,6 +72,22 @@ class _SideVocoder:
         self.items: list = []
         self.device_only = False          # long form: the waveforms stay on the device (``collect_device``), no pinned-host copies
         self.level = None                 # ``level(key, waveform)``: the model's loudness / fixed-gain step, run between the decode and the copy
+        # ``output=`` of the batch entry points: {key: AudioOutSpec} of the utterances whose waveform goes through the output stage
+        # behind ``level`` -- the utterances vocoded together in ONE ``audio_out.push_group`` -- and the model's ``(take, give)`` of
+        # pooled stages
+        self.outputs, self.stages = None, None
+
+    def _spec(self, key):
+        return self.outputs.get(key) if self.outputs else None
+
+    def _encode_group(self, keys, pcms) -> list:
+        """whole utterances (float32 device vectors) through pooled output stages, one ``push_group`` with ``final`` for all of them
+        -> one ``_Encoded`` per key: its host array exists once the group's one pinned copy has landed"""
+        from .audio_out import GroupCopy
+        take, give = self.stages
+        stages = [take(self.outputs[k], self.stream) for k in keys]
+        copy = GroupCopy(stages, [p.flatten() for p in pcms], [True] * len(keys))
+        return [_Encoded(copy, i, st, give) for i, st in enumerate(stages)]
 
     def _prefix(self, ref):
         """the tokenizer's cached front-end state of an ICL reference (built on the vocoder stream), or None"""
@@ -72,6 +105,9 @@ class _SideVocoder:
             a = a[int(ref_len / max(codes.shape[0], 1) * len(a)):] if ref_len > 0 else a
             if self.level is not None:
                 a = _to_numpy(self.level(key, a))
+            if self._spec(key) is not None:
+                # synchronous tokenizer: its audio is on the host; the utterance is uploaded for the stage
+                a = self._encode_group([key], [torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32)).to(self.dev)])[0]
             self.items.append((key, a, None, None))
             return
         cut = int(ref_len / max(codes.shape[0], 1) * self.tok.num_samples_total(codes.shape[0])) if ref_len > 0 else 0
@@ -83,7 +119,9 @@ class _SideVocoder:
             if self.level is not None:
                 pcm = self.level(key, pcm)
             host = None
-            if not self.device_only:
+            if self._spec(key) is not None:
+                host = self._encode_group([key], [pcm])[0]
+            elif not self.device_only:
                 host = torch.empty(pcm.shape, dtype=torch.float32, pin_memory=True)
                 host.copy_(pcm, non_blocking=True)
             ev = torch.cuda.Event()
@@ -138,13 +176,15 @@ class _SideVocoder:
                         for j, (key, _c, _r) in enumerate(part):
                             self.level(key, pcm[j])                 # row by row, in place: every utterance has its own gain
                     host = None
-                    if not self.device_only:
+                    staged = [j for j, (key, _c, _r) in enumerate(part) if self._spec(key) is not None]
+                    enc = dict(zip(staged, self._encode_group([part[j][0] for j in staged], [pcm[j] for j in staged]))) if staged else {}
+                    if not self.device_only and len(staged) < len(part):
                         host = torch.empty(pcm.shape, dtype=torch.float32, pin_memory=True)
                         host.copy_(pcm, non_blocking=True)
                     ev = torch.cuda.Event()
                     ev.record(self.stream)
                 for j, (key, _c, _r) in enumerate(part):
-                    self.items.append((key, host[j] if host is not None else None, ev, pcm[j]))
+                    self.items.append((key, enc[j] if j in enc else host[j] if host is not None else None, ev, pcm[j]))
 
     # ---- incremental (exact) vocoding of utterances that are still decoding ------------------------------------------------
     # The codec decoder is causal: decode(codes[:p]) is bit for bit the prefix of decode(codes), and a tail decode from sample s is
@@ -239,7 +279,9 @@ class _SideVocoder:
 
     def collect(self):
         for key, host, ev, _pcm in self.items:
-            if ev is None:
+            if isinstance(host, _Encoded):
+                yield key, host.array()
+            elif ev is None:
                 yield key, host
             else:
                 ev.synchronize()
@@ -1243,6 +1285,43 @@ class FasterQwen3TTS:
             raise ValueError("the batch entry points decode their audio in groups and do not run the audio output stage: call them outside "
                              "audio_output(), or use the single-stream entry points (the server builds one vocoder per request instead)")
 
+    def _batch_outputs(self, output, n: int) -> Optional[list]:
+        """``output=`` of the batch entry points -> None, or one validated ``AudioOutSpec`` or None per text.  Every argument error
+        surfaces here, before anything is prepared or decoded."""
+        if output is None:
+            return None
+        from .audio_out import AudioOutSpec
+        if getattr(self, "_audio_spec", None) is not None:
+            raise ValueError("output= inside audio_output(): the batch entry points take their output specs as output= alone; call them "
+                             "outside the context")
+        specs = self._per_text(output, n, "output")
+        for sp in specs:
+            if sp is not None and not isinstance(sp, AudioOutSpec):
+                raise ValueError(f"output must be an AudioOutSpec, or a list with one AudioOutSpec or None per text, not {type(sp).__name__}")
+        specs = [None if sp is None else sp.validate(self.sample_rate) for sp in specs]
+        return specs if any(sp is not None for sp in specs) else None
+
+    STAGE_POOL_MAX = 256
+
+    def _take_stage(self, spec, stream):
+        """An output stage for one utterance of a batched run: an idle one of the same spec and stream from the model's pool, reset,
+        or a new one -- its device buffers are not allocated and freed per reply (a free synchronises the device while other lanes run)."""
+        from .audio_out import AudioOut
+        pool = self.__dict__.setdefault("_stage_pools", {}).setdefault((spec, str(self.device), stream), [])
+        try:
+            st = pool.pop()
+        except IndexError:
+            st = AudioOut(spec, self.sample_rate, self.device, stream)
+            st.pool = pool
+            return st
+        st.reset()
+        return st
+
+    def _give_stage(self, st) -> None:
+        pool = getattr(st, "pool", None)
+        if pool is not None and len(pool) < self.STAGE_POOL_MAX and not any(st is other for other in pool):
+            pool.append(st)
+
     def _one_shot_output(self, wav) -> Tuple[np.ndarray, int]:
         """A whole utterance's waveform (device tensor or host array) through the output stage of the open context."""
         from .audio_out import AudioOut
@@ -1501,12 +1580,15 @@ class FasterQwen3TTS:
             head.append(r)
         return head, pull
 
-    def _run_batch_full(self, prepared, gen_kwargs, lanes: int, count: int, seeds=None, device_audio: bool = False) -> List[Tuple[list, int]]:
+    def _run_batch_full(self, prepared, gen_kwargs, lanes: int, count: int, seeds=None, device_audio: bool = False,
+                        outputs=None) -> List[Tuple[list, int]]:
         """The lock-step decode of ``count`` prepared utterances (see :meth:`_batch_feed`) through ``lanes`` lanes, every finished
         utterance vocoded on the side stream (the reference's share of an ICL waveform is cut by not producing it,
         model.py:927-930).  One ``([waveform], sample_rate)`` per entry, in input order.  ``device_audio`` (internal, long form): the
         waveforms are handed out as device tensors valid on the side vocoder's stream -- ``(out, voc)`` is returned -- and the caller
-        runs the output chain itself."""
+        runs the output chain itself.  ``outputs`` (:meth:`_batch_outputs`): utterance i with a spec comes back as
+        ``([encoded array], output rate)`` -- the utterances vocoded together go through the output stage together, behind the levelling
+        step (``_SideVocoder._encode_group``)."""
         if not device_audio:
             self._refuse_batch_audio_output()
         seeds = expand_seeds(seeds, count)
@@ -1519,6 +1601,19 @@ class FasterQwen3TTS:
         out: List[Optional[Tuple[list, int]]] = [None] * count
         voc = self._side_vocoder()
         voc.device_only = bool(device_audio)
+        if outputs is not None:
+            voc.outputs, voc.stages = {i: sp for i, sp in enumerate(outputs) if sp is not None}, (self._take_stage, self._give_stage)
+        rate_of = lambda rid: self.sample_rate if outputs is None or outputs[rid] is None else outputs[rid].out_rate(self.sample_rate)  # noqa: E731
+
+        def nothing(rid):
+            """an utterance without a single frame: one zero sample, through its stage if it has one"""
+            if outputs is None or outputs[rid] is None:
+                return [np.zeros(1, dtype=np.float32)], self.sample_rate
+            z = torch.zeros(1, dtype=torch.float32, device=voc.dev)
+            if voc.stream is not None:
+                voc.stream.wait_stream(torch.cuda.current_stream(voc.dev))
+            a = voc._encode_group([rid], [z])[0].array()
+            return [a], rate_of(rid)
         if self._loud is not None:
             self._loud.begin(count)
         if self._levelling() and not device_audio:
@@ -1530,7 +1625,7 @@ class FasterQwen3TTS:
         # frames for more than they save at the end -- 64 lanes x 128 utterances, 0.6B: 561x at 0, 537x at 64, 552x at 100; 1.7B: 458x vs
         # 443x -- so it is OFF by default; a server whose lanes finish at different times has nothing to gain from it either.
         inc = int(getattr(self, "batch_vocode_every", 0) or 0)
-        if inc > 0 and not device_audio and not self._levelling() and voc.async_ok and hasattr(voc.tok, "decode_tensor_batch") and hasattr(voc.tok, "num_samples_total"):
+        if inc > 0 and not device_audio and outputs is None and not self._levelling() and voc.async_ok and hasattr(voc.tok, "decode_tensor_batch") and hasattr(voc.tok, "num_samples_total"):
             max_new = min(int(gen_kwargs.get("max_new_tokens", 2048)), int(self.talker_graph.engine.max_frames))
             for rid, codes, info in dec.run(head, source=source, chunk_frames=inc):
                 more = int(getattr(dec, "more_in_poll", 0))
@@ -1541,7 +1636,7 @@ class FasterQwen3TTS:
         for rid, codec_ids, timing in dec.run(head, source=source):
             more = int(getattr(dec, "more_in_poll", 0))
             if codec_ids is None:
-                out[rid] = ([np.zeros(1, dtype=np.float32)], self.sample_rate)
+                out[rid] = nothing(rid)
                 if more <= 0:
                     voc.add_flush()
                 continue
@@ -1556,11 +1651,11 @@ class FasterQwen3TTS:
                 out[rid] = ([a], voc.sample_rate)
             return out, voc
         for rid, a in voc.collect():
-            out[rid] = ([a], voc.sample_rate)
+            out[rid] = ([a], voc.sample_rate if outputs is None else rate_of(rid))
         return out
 
     def _run_batch_streaming(self, prepared, gen_kwargs, chunk_size: int, lanes: int, rounds=None, stamp=None, seeds=None,
-                             count: Optional[int] = None, device_audio: bool = False):
+                             count: Optional[int] = None, device_audio: bool = False, outputs=None):
         """Streaming form of :meth:`_run_batch_full`: yields ``(index, audio_chunk, sample_rate, timing)`` for every
         ``chunk_size`` frames of any utterance -- per utterance exactly the chunks the single-utterance streaming entry point
         would produce (same windowing state machine).  ``timing``: ``chunk_index``, ``total_steps_so_far``, ``is_final``.
@@ -1568,7 +1663,11 @@ class FasterQwen3TTS:
         successive scheduler runs instead of the one pair :meth:`_batch_feed` makes of ``prepared``; ``stamp(index, timing)`` may add
         keys to a chunk's timing before it goes out.  ``device_audio`` (internal, long form; what is yielded by default does not
         change): a chunk vocoded on the vocoder stream is handed out as the group's device waveform row -- a float32 tensor valid on
-        that stream, no copy to the host, no wait -- and the utterances' vocoders carry no output stage of their own."""
+        that stream, no copy to the host, no wait -- and the utterances' vocoders carry no output stage of their own.
+        ``outputs`` (:meth:`_batch_outputs`): utterance i with a spec owns a pooled output stage; behind the gain and the limiter the
+        rows of a launch group that have one go through ONE ``audio_out.push_group`` on the vocoder stream and reach pinned memory in
+        one copy, and what is yielded for them is the encoded array and the output rate (``flac``: bytes, the stream header in the
+        utterance's first chunk).  What the stage held back leaves with the utterance's final event (``StreamingVocoder.flush``)."""
         self._refuse_streaming_loudness()
         if not device_audio:
             self._refuse_batch_audio_output()
@@ -1628,22 +1727,32 @@ class FasterQwen3TTS:
                 if gain is not None:
                     from .loudness import apply_gain
                     wav = apply_gain(wav.contiguous(), gain, side)
-                host = landed = None
+                host = landed = encoded = None
+                staged = [k for k, j in enumerate(part) if vocs[j[0]].output is not None]
                 if limit is not None:
                     # every utterance's own limiter takes its row: the rows come back shorter by what it holds back, or longer at the end
                     wav = [vocs[j[0]].limit_push(wav[k].contiguous(), bool(j[1].get("is_final"))) for k, j in enumerate(part)]
+                if staged:
+                    # the rows with an output spec: one time-scale launch, one resample + encode launch per design, one pinned copy
+                    from .audio_out import GroupCopy
+                    encoded = (staged, GroupCopy([vocs[part[k][0]]._stage() for k in staged], [wav[k] for k in staged],
+                                                 [bool(part[k][1].get("is_final")) for k in staged]))
+                if limit is not None:
                     host = []
-                    for row in wav:
-                        host.append(torch.empty(row.shape, dtype=row.dtype, pin_memory=True))
-                        host[-1].copy_(row, non_blocking=True)
+                    for k, row in enumerate(wav):
+                        host.append(None if k in staged else torch.empty(row.shape, dtype=row.dtype, pin_memory=True))
+                        if host[-1] is not None:
+                            host[-1].copy_(row, non_blocking=True)
                     landed = torch.cuda.Event()
                     landed.record(side)
-                elif not device_audio:
+                elif not device_audio and len(staged) < len(part):
                     host = torch.empty(wav.shape, dtype=wav.dtype, pin_memory=True)
                     host.copy_(wav, non_blocking=True)
                     landed = torch.cuda.Event()
                     landed.record(side)
-            queued.append((part, host, landed, wav))
+                elif staged:
+                    landed = encoded[1].event
+            queued.append((part, host, landed, wav, encoded))
 
         def launch_open():
             exact_pending.clear()
@@ -1683,14 +1792,24 @@ class FasterQwen3TTS:
             plain = [j for j in jobs if j[3] is None]
             jobs[:] = []
             groups, queued[:] = list(queued), []
-            for part, host, landed, wav in groups:
+            for part, host, landed, wav, encoded in groups:
                 if landed is None:
                     arr = wav                                      # device rows: whoever takes them works on the vocoder stream
                 else:
                     landed.synchronize()
-                    arr = [h.numpy() for h in host] if isinstance(host, list) else host.numpy()
+                    arr = ([None if h is None else h.numpy() for h in host] if isinstance(host, list) else
+                           host.numpy() if host is not None else [None] * len(part))
                 for k, j in enumerate(part):
                     j[2] = arr[k]
+                if encoded is not None:
+                    for k, a in zip(encoded[0], encoded[1].rows()):
+                        v = vocs[part[k][0]]
+                        if v.stage.flac and not v.header_sent:
+                            # a FLAC stream: the utterance's first chunk starts with the stream header (length unknown)
+                            a, v.header_sent = np.concatenate([np.frombuffer(v.stage.header(), dtype=np.uint8), a]), True
+                        part[k][2] = a
+                        if part[k][1].get("is_final"):
+                            self._give_stage(v.stage)
                 yield from part
             yield from plain
 
@@ -1699,11 +1818,15 @@ class FasterQwen3TTS:
                 stamp(r, m)
             return m
 
+        rate_of = lambda r: self.sample_rate if outputs is None or outputs[r] is None else outputs[r].out_rate(self.sample_rate)  # noqa: E731
+
         for head, source in pairs:
           for rid, codes, info in dec.run(head, source=source, chunk_frames=chunk_size):
             if rid not in vocs:
                 vocs[rid] = (StreamingVocoder(tok, meta[rid], chunk_size, self.device, side, **self._exact_kw()) if device_audio
                              else self.streaming_vocoder(meta[rid], chunk_size))
+                if outputs is not None and outputs[rid] is not None:
+                    vocs[rid].output, vocs[rid].stage = outputs[rid], self._take_stage(outputs[rid], side)
                 n_chunks[rid] = 0
             ev = info.pop("codes_ready_event", None)
             final = bool(info.get("is_final"))
@@ -1718,12 +1841,22 @@ class FasterQwen3TTS:
                     else:
                         add_job([rid, out_meta, None, (inp, first, ev, vocs[rid].last_prefix)])
                 else:
-                    audio, _sr = vocs[rid].push(codes, ev, final=final) if limit is not None else vocs[rid].push(codes, ev)
+                    staged = limit is not None or vocs[rid].output is not None
+                    audio, _sr = vocs[rid].push(codes, ev, final=final) if staged else vocs[rid].push(codes, ev)
+                    if final and vocs[rid].output is not None:
+                        self._give_stage(vocs[rid].stage)
                     add_job([rid, out_meta, audio, None])
                 n_chunks[rid] += 1
             elif final:
                 tail = np.zeros(1 if codes is None else 0, dtype=np.float32)
-                if limit is not None and vocs[rid].limit is not None:
+                if vocs[rid].output is not None:
+                    # what the output stage (and a limiter in front of it) held back leaves as this event's audio
+                    launch_open()
+                    tail, _sr = vocs[rid].flush()
+                    if vocs[rid].stage.flac and not vocs[rid].header_sent:
+                        tail, vocs[rid].header_sent = np.concatenate([np.frombuffer(vocs[rid].stage.header(), dtype=np.uint8), tail]), True
+                    self._give_stage(vocs[rid].stage)
+                elif limit is not None and vocs[rid].limit is not None:
                     launch_open()                                  # the utterance's chunks that still wait go in front of its tail
                     held, _sr = vocs[rid].flush()
                     tail = held if len(held) else tail
@@ -1731,9 +1864,9 @@ class FasterQwen3TTS:
                 n_chunks[rid] += 1
             if more <= 0:
                 for r, m, audio, _job in flush():
-                    yield r, audio, self.sample_rate, out(r, m)
+                    yield r, audio, rate_of(r), out(r, m)
           for r, m, audio, _job in flush():
-            yield r, audio, self.sample_rate, out(r, m)
+            yield r, audio, rate_of(r), out(r, m)
 
     @staticmethod
     def _per_text(value, n: int, what: str) -> list:
@@ -1765,7 +1898,7 @@ class FasterQwen3TTS:
                                    non_streaming_mode: Optional[bool] = None, append_silence: bool = True,
                                    instruct: Optional[str] = None,
                                    voice_clone_prompt: Optional[Union[Dict[str, Any], List[Any]]] = None,
-                                   lanes: int = 8, seeds=None) -> List[Tuple[list, int]]:
+                                   lanes: int = 8, seeds=None, output=None) -> List[Tuple[list, int]]:
         """Voice cloning of several texts with one voice: up to ``lanes`` (<= 128) utterances decode in lock-step over
         one pass of the weights per frame (``fq3_batch_*``), finished lanes are refilled from the queue.  Returns one
         ``([np.float32 waveform], sample_rate)`` per text, in input order; each utterance follows exactly the
@@ -1774,7 +1907,8 @@ class FasterQwen3TTS:
         prepared = self._prepare_clone_batch(texts, language, ref_audio, ref_text, xvec_only, nsm, append_silence, instruct,
                                              voice_clone_prompt)
         return self._run_batch_full(prepared, self._gen_kwargs(max_new_tokens, min_new_tokens, temperature, top_k, top_p, do_sample,
-                                                               repetition_penalty), lanes, len(texts), seeds=seeds)
+                                                               repetition_penalty), lanes, len(texts), seeds=seeds,
+                                    outputs=self._batch_outputs(output, len(texts)))
 
     @torch.inference_mode()
     def generate_voice_clone_batch_streaming(self, texts: List[str], language: Union[str, List[str]] = "English",
@@ -1785,7 +1919,7 @@ class FasterQwen3TTS:
                                              non_streaming_mode: Optional[bool] = None, append_silence: bool = True,
                                              instruct: Optional[str] = None,
                                              voice_clone_prompt: Optional[Union[Dict[str, Any], List[Any]]] = None,
-                                             lanes: int = 8, seeds=None) -> Generator[Tuple[int, np.ndarray, int, dict], None, None]:
+                                             lanes: int = 8, seeds=None, output=None) -> Generator[Tuple[int, np.ndarray, int, dict], None, None]:
         """Streaming AND batched: the texts decode in lock-step lanes (as :meth:`generate_voice_clone_batch`) and every
         ``chunk_size`` frames of any utterance yield ``(text_index, audio_chunk, sample_rate, timing)`` -- per utterance
         exactly the chunks :meth:`generate_voice_clone_streaming` would produce for it (same windowing state machine).
@@ -1795,7 +1929,7 @@ class FasterQwen3TTS:
                                              voice_clone_prompt)
         yield from self._run_batch_streaming(prepared, self._gen_kwargs(max_new_tokens, min_new_tokens, temperature, top_k, top_p,
                                                                          do_sample, repetition_penalty), chunk_size, lanes,
-                                             seeds=seeds, count=len(texts))
+                                             seeds=seeds, count=len(texts), outputs=self._batch_outputs(output, len(texts)))
 
     def _prepare_custom_batch(self, texts, speaker, language, instruct, non_streaming_mode):
         n = len(texts)
@@ -1816,14 +1950,15 @@ class FasterQwen3TTS:
                                     instruct: Optional[Union[str, List[Optional[str]]]] = None,
                                     non_streaming_mode: Optional[bool] = None, max_new_tokens: int = 2048, min_new_tokens: int = 2,
                                     temperature: float = 0.9, top_k: int = 50, top_p: float = 1.0, do_sample: bool = True,
-                                    repetition_penalty: float = 1.05, lanes: int = 16, seeds=None) -> List[Tuple[list, int]]:
+                                    repetition_penalty: float = 1.05, lanes: int = 16, seeds=None, output=None) -> List[Tuple[list, int]]:
         """CustomVoice for several texts (BASELINE configs[3]: many concurrent utterances of a CustomVoice model): every
         utterance is prepared exactly like :meth:`generate_custom_voice` (speaker-id prompt, model.py:1139-1326; ``speaker`` /
         ``language`` / ``instruct`` may be one value or one per text) and up to ``lanes`` of them decode in lock-step over one pass of
         the weights per frame.  Returns one ``([waveform], sample_rate)`` per text, in input order."""
         prepared = self._prepare_custom_batch(texts, speaker, language, instruct, non_streaming_mode)
         return self._run_batch_full(prepared, self._gen_kwargs(max_new_tokens, min_new_tokens, temperature, top_k, top_p, do_sample,
-                                                               repetition_penalty), lanes, len(texts), seeds=seeds)
+                                                               repetition_penalty), lanes, len(texts), seeds=seeds,
+                                    outputs=self._batch_outputs(output, len(texts)))
 
     @torch.inference_mode()
     def generate_custom_voice_batch_streaming(self, texts: List[str], speaker: Union[str, List[str]],
@@ -1832,22 +1967,23 @@ class FasterQwen3TTS:
                                               non_streaming_mode: Optional[bool] = None, max_new_tokens: int = 2048,
                                               min_new_tokens: int = 2, temperature: float = 0.9, top_k: int = 50, top_p: float = 1.0,
                                               do_sample: bool = True, repetition_penalty: float = 1.05, chunk_size: int = 12,
-                                              lanes: int = 16, seeds=None) -> Generator[Tuple[int, np.ndarray, int, dict], None, None]:
+                                              lanes: int = 16, seeds=None, output=None) -> Generator[Tuple[int, np.ndarray, int, dict], None, None]:
         """Streaming form of :meth:`generate_custom_voice_batch`: ``(text_index, audio_chunk, sample_rate, timing)`` per chunk."""
         prepared = self._prepare_custom_batch(texts, speaker, language, instruct, non_streaming_mode)
         yield from self._run_batch_streaming(prepared, self._gen_kwargs(max_new_tokens, min_new_tokens, temperature, top_k, top_p,
                                                                          do_sample, repetition_penalty), chunk_size, lanes,
-                                             seeds=seeds, count=len(texts))
+                                             seeds=seeds, count=len(texts), outputs=self._batch_outputs(output, len(texts)))
 
     @torch.inference_mode()
     def generate_voice_design_batch(self, texts: List[str], instruct: Union[str, List[str]], language: Union[str, List[str]] = "English",
                                     non_streaming_mode: Optional[bool] = None, max_new_tokens: int = 2048, min_new_tokens: int = 2,
                                     temperature: float = 0.9, top_k: int = 50, top_p: float = 1.0, do_sample: bool = True,
-                                    repetition_penalty: float = 1.05, lanes: int = 16, seeds=None) -> List[Tuple[list, int]]:
+                                    repetition_penalty: float = 1.05, lanes: int = 16, seeds=None, output=None) -> List[Tuple[list, int]]:
         """VoiceDesign for several texts in lock-step lanes; every utterance prepared like :meth:`generate_voice_design`."""
         return self._run_batch_full(self._prepare_design_batch(texts, instruct, language, non_streaming_mode),
                                     self._gen_kwargs(max_new_tokens, min_new_tokens, temperature, top_k, top_p, do_sample, repetition_penalty),
-                                    lanes, len(texts), seeds=seeds)
+                                    lanes, len(texts), seeds=seeds,
+                                    outputs=self._batch_outputs(output, len(texts)))
 
     def _prepare_design_batch(self, texts, instruct, language, non_streaming_mode):
         n = len(texts)
@@ -1867,12 +2003,12 @@ class FasterQwen3TTS:
                                               language: Union[str, List[str]] = "English", non_streaming_mode: Optional[bool] = None,
                                               max_new_tokens: int = 2048, min_new_tokens: int = 2, temperature: float = 0.9,
                                               top_k: int = 50, top_p: float = 1.0, do_sample: bool = True, repetition_penalty: float = 1.05,
-                                              chunk_size: int = 12, lanes: int = 16, seeds=None) -> Generator[Tuple[int, np.ndarray, int, dict], None, None]:
+                                              chunk_size: int = 12, lanes: int = 16, seeds=None, output=None) -> Generator[Tuple[int, np.ndarray, int, dict], None, None]:
         """Streaming form of :meth:`generate_voice_design_batch`: ``(text_index, audio_chunk, sample_rate, timing)`` per chunk."""
         prepared = self._prepare_design_batch(texts, instruct, language, non_streaming_mode)
         yield from self._run_batch_streaming(prepared, self._gen_kwargs(max_new_tokens, min_new_tokens, temperature, top_k, top_p,
                                                                          do_sample, repetition_penalty), chunk_size, lanes,
-                                             seeds=seeds, count=len(texts))
+                                             seeds=seeds, count=len(texts), outputs=self._batch_outputs(output, len(texts)))
 
     @torch.inference_mode()
     def generate_voice_clone_streaming(self, text: str, language: str, ref_audio: Optional[Union[str, Path]] = None,
@@ -2279,7 +2415,7 @@ class FasterQwen3TTS:
         return BatchRequest(rid, talker, tie, tam, tie.new_zeros(1, 0, tie.shape[-1]), tpe, config, dict(gen_kwargs),
                             text_feeder=feeder, tts_eos_id=int(m.config.tts_eos_token_id), seed=seed)
 
-    def _run_text_batch_streaming(self, text_iters, prepares, gen_kwargs, chunk_size: int, lanes: int, seeds=None):
+    def _run_text_batch_streaming(self, text_iters, prepares, gen_kwargs, chunk_size: int, lanes: int, seeds=None, outputs=None):
         """Shared back half of the ``stream_*_batch`` entry points.  A request enters the scheduler when its first token exists;
         streams whose first token has not arrived wait beside it and do not block the others."""
         import threading
@@ -2315,14 +2451,14 @@ class FasterQwen3TTS:
             if timing.get("chunk_index") == 0 and feeders[i].t_first is not None:
                 timing["first_text_ms"] = (time.time() - feeders[i].t_first) * 1000      # first piece received -> first audio
 
-        yield from self._run_batch_streaming(None, gen_kwargs, chunk_size, lanes, rounds=rounds, stamp=stamp)
+        yield from self._run_batch_streaming(None, gen_kwargs, chunk_size, lanes, rounds=rounds, stamp=stamp, outputs=outputs)
 
     @torch.inference_mode()
     def stream_custom_voice_batch(self, text_iters, speaker: Union[str, List[str]], language: Union[str, List[str]] = "English",
                                   instruct: Optional[Union[str, List[Optional[str]]]] = None, chunk_size: int = 12,
                                   max_new_tokens: int = 2048, min_new_tokens: int = 2, temperature: float = 0.9, top_k: int = 50,
                                   top_p: float = 1.0, do_sample: bool = True, repetition_penalty: float = 1.05,
-                                  lanes: int = 16, seeds=None) -> Generator[Tuple[int, np.ndarray, int, dict], None, None]:
+                                  lanes: int = 16, seeds=None, output=None) -> Generator[Tuple[int, np.ndarray, int, dict], None, None]:
         """``generate_custom_voice_batch_streaming(..., non_streaming_mode=False)`` for texts that are still arriving: every element of
         ``text_iters`` is an iterable of ``str`` pieces or a ``TextFeeder`` (an LLM's token stream per utterance), and up to ``lanes``
         of them decode in lock-step while their text comes in.  Yields ``(index, audio_chunk, sample_rate, timing)``; per utterance the
@@ -2338,13 +2474,14 @@ class FasterQwen3TTS:
             return lambda input_ids: self._custom_prepare(None, spk, lang, ins, False, input_ids=input_ids)
         yield from self._run_text_batch_streaming(text_iters, [prep(*a) for a in zip(spks, langs, inss)],
                                                   self._gen_kwargs(max_new_tokens, min_new_tokens, temperature, top_k, top_p, do_sample,
-                                                                   repetition_penalty), chunk_size, lanes, seeds=seeds)
+                                                                   repetition_penalty), chunk_size, lanes, seeds=seeds,
+                                                  outputs=self._batch_outputs(output, len(text_iters)))
 
     @torch.inference_mode()
     def stream_voice_design_batch(self, text_iters, instruct: Union[str, List[str]], language: Union[str, List[str]] = "English",
                                   chunk_size: int = 12, max_new_tokens: int = 2048, min_new_tokens: int = 2, temperature: float = 0.9,
                                   top_k: int = 50, top_p: float = 1.0, do_sample: bool = True, repetition_penalty: float = 1.05,
-                                  lanes: int = 16, seeds=None) -> Generator[Tuple[int, np.ndarray, int, dict], None, None]:
+                                  lanes: int = 16, seeds=None, output=None) -> Generator[Tuple[int, np.ndarray, int, dict], None, None]:
         """``generate_voice_design_batch_streaming(..., non_streaming_mode=False)`` for texts that are still arriving (see
         :meth:`stream_custom_voice_batch`)."""
         n = len(text_iters)
@@ -2357,7 +2494,8 @@ class FasterQwen3TTS:
             return lambda input_ids: self._design_prepare(None, ins, lang, False, input_ids=input_ids)
         yield from self._run_text_batch_streaming(text_iters, [prep(*a) for a in zip(inss, langs)],
                                                   self._gen_kwargs(max_new_tokens, min_new_tokens, temperature, top_k, top_p, do_sample,
-                                                                   repetition_penalty), chunk_size, lanes, seeds=seeds)
+                                                                   repetition_penalty), chunk_size, lanes, seeds=seeds,
+                                                  outputs=self._batch_outputs(output, len(text_iters)))
 
     @torch.inference_mode()
     def stream_voice_clone_batch(self, text_iters, language: Union[str, List[str]] = "English",
@@ -2366,7 +2504,7 @@ class FasterQwen3TTS:
                                  do_sample: bool = True, repetition_penalty: float = 1.05, xvec_only: bool = True,
                                  append_silence: bool = True, instruct: Optional[str] = None,
                                  voice_clone_prompt: Optional[Union[Dict[str, Any], List[Any]]] = None,
-                                 lanes: int = 16, seeds=None) -> Generator[Tuple[int, np.ndarray, int, dict], None, None]:
+                                 lanes: int = 16, seeds=None, output=None) -> Generator[Tuple[int, np.ndarray, int, dict], None, None]:
         """``generate_voice_clone_batch_streaming(..., non_streaming_mode=False)`` for texts that are still arriving, one x-vector-only
         voice for all of them.  An ICL voice is refused with the message of :meth:`stream_voice_clone`."""
         why = self._refuse_icl_text_stream(xvec_only, voice_clone_prompt)
@@ -2383,4 +2521,5 @@ class FasterQwen3TTS:
             return prepare
         yield from self._run_text_batch_streaming(text_iters, [prep(l) for l in langs],
                                                   self._gen_kwargs(max_new_tokens, min_new_tokens, temperature, top_k, top_p, do_sample,
-                                                                   repetition_penalty), chunk_size, lanes, seeds=seeds)
+                                                                   repetition_penalty), chunk_size, lanes, seeds=seeds,
+                                                  outputs=self._batch_outputs(output, len(text_iters)))

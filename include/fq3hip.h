@@ -599,6 +599,29 @@ int fq3_tsm_reset(fq3_tsm* t, void* stream);
 int fq3_tsm_push(fq3_tsm* t, const float* pcm, int64_t n_in, int final, float* out, int64_t capacity_samples,
                  int64_t* n_out, int32_t* deltas, int64_t deltas_capacity, void* stream);
 
+/* ---- the two stages above for a GROUP of streams: all rows in ONE launch ------------------------------------------------------
+ * For the lock-step batch, whose chunks leave the vocoder in groups.  Every array is a HOST array of B entries; row b is exactly
+ *     fq3_audio_out_push(objs[b], pcm[b], n_in[b], final[b], out[b], capacity_samples[b], &n_out[b], stream)
+ * (fq3_tsm_push_group: fq3_tsm_push with deltas = NULL), and all rows run in one launch on `stream`.
+ *   Equality.        What row b writes, n_out[b] and the state objs[b] is left in are bit for bit those of the single push: the sample
+ *                    is computed by the same device code.  Group and single pushes mix freely on one object; membership and order of a
+ *                    group may change from push to push.
+ *   All or nothing.  Every row is checked before any object changes (null pointers, negative lengths, capacity, FQ3_ESTATE after a
+ *                    final push): on an error that row's code is returned, nothing is launched and no object has moved.
+ *   Limits.          B == 0: returns 0, does nothing.  B < 0, B > FQ3_STAGE_GROUP_MAX, a null array, a null object or the same object
+ *                    twice in one call: FQ3_EINVAL.  These are answered before any HIP call.
+ *   Shared design.   fq3_audio_out_push_group: all objects have the same (in_rate, out_rate, format, zero_crossings) -- one bank, one
+ *                    launch plan -- else FQ3_EINVAL.  fq3_tsm_push_group: the same in_rate (one window); speed_permille may differ per
+ *                    row, it enters host-computed arguments only.
+ *   Empty rows.      A row with nothing to do (n_in == 0, no outputs) is legal and costs a workgroup that exits.
+ *   Asynchrony.      No host synchronisation and no copy: the rows' descriptors travel in the launch's argument block, and the counts
+ *                    are known on the host before the launch.  pcm[b] and out[b] must stay valid until the stream has run it. */
+#define FQ3_STAGE_GROUP_MAX 32
+int fq3_audio_out_push_group(fq3_audio_out* const* objs, int B, const float* const* pcm, const int64_t* n_in, const int* final,
+                             void* const* out, const int64_t* capacity_samples, int64_t* n_out, void* stream);
+int fq3_tsm_push_group(fq3_tsm* const* objs, int B, const float* const* pcm, const int64_t* n_in, const int* final,
+                       float* const* out, const int64_t* capacity_samples, int64_t* n_out, void* stream);
+
 /* ---- FLAC output: lossless compression of the s16 samples on the device ------------------------------------------------------
  * Behind the s16 output stage: int16 device samples in, FLAC frames (device bytes) out; the 42-byte stream header is made on the
  * host.  Decoding the stream gives the s16 samples bit for bit.  The result does not depend on how the stream was cut into pushes.

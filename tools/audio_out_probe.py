@@ -14,7 +14,14 @@ which ends VERBATIM -- next to the s16 output stage (the code of the parent comm
 the same run, and bytes out over s16 bytes.  With --recordings DIR (CPU only, no GPU touched): bytes out over s16 bytes of the numpy
 reference encoder (tests/_flac_ref.py, the same bytes as the device's) over every integer-PCM WAV under DIR, one ratio per file.  Both
 halves keep what the other wrote.  Writes profiles/flac_stage.json.
-usage: audio_out_probe.py [--speed | --encoding flac [--recordings DIR]] [runs=100] [out.json]"""
+With --group B: the output chain of a lock-step GROUP -- B rows (at most 32 a library call), one streaming chunk each, 8 kHz mu-law at
+speed 1.25 -- through ``audio_out.push_group`` (ONE fq3_tsm_push_group launch + ONE fq3_audio_out_push_group launch) and through B single
+``AudioOut.push`` calls (2 B launches: the parent commit's code path), alternating in the same run, each repeat between its own event
+pair, plus both forms with the rows landing on the host (one pinned copy against B copies; host clock around the call, which ends in a
+synchronise), next to the bf16x2 vocoder's windowed chunk decode for the same group (``decode_tensor_batch`` over B x [25 + 8] frames,
+the protocol of profiles/codec_stream.json).  The two forms' bytes are compared before anything is timed.  Writes
+profiles/stage_group.json.
+usage: audio_out_probe.py [--speed | --encoding flac [--recordings DIR] | --group B] [runs=100] [out.json]"""
 import json
 import os
 import statistics
@@ -212,8 +219,113 @@ def main_flac(argv):
     _merge(out_path, res)
 
 
+def main_group(B, argv):
+    import time
+    runs = max(20, int(argv[0])) if argv else 40
+    out_path = argv[1] if len(argv) > 1 else os.path.join(ROOT, "profiles", "stage_group.json")
+    g = torch.Generator().manual_seed(3)
+    n = 8 * SAMPLES_PER_FRAME
+    spec = ao.AudioOutSpec(8000, "mulaw", 1.25)
+    t = torch.arange(n, dtype=torch.float64) / 24000.0
+    voiced = sum(0.25 / h * torch.sin(2 * torch.pi * 140.0 * h * t) for h in range(1, 9)) * torch.exp(-3.0 * (t % 0.16))
+    rows = [(voiced * (0.5 + 0.5 * b / B) + 0.003 * torch.randn(n, generator=g)).float().cuda() for b in range(B)]
+    stages = [ao.AudioOut(spec, 24000, "cuda") for _ in range(B)]
+    finals = [True] * B
+
+    def reset():
+        for st in stages:
+            st.reset()                                            # host only
+
+    def group():
+        reset()
+        return ao.push_group(stages, rows, finals)
+
+    def singles():
+        reset()
+        return [st.push(x, True) for st, x in zip(stages, rows)]
+
+    def group_host():
+        reset()
+        return ao.push_group_host(stages, rows, finals)
+
+    def singles_host():
+        reset()
+        return [st.push_host(x, True) for st, x in zip(stages, rows)]
+
+    a, b = group(), singles()
+    torch.cuda.synchronize()
+    assert all(torch.equal(u, v) for u, v in zip(a, b)), "the group form and the single pushes must write the same bytes"
+    n_out = int(a[0].numel())
+
+    def events(fn):
+        pairs = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(runs)]
+        for e0, e1 in pairs:
+            e0.record(); fn(); e1.record()
+        torch.cuda.synchronize()
+        return [e0.elapsed_time(e1) for e0, e1 in pairs]
+
+    def clock(fn):
+        out = []
+        for _ in range(runs):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter(); fn(); out.append((time.perf_counter() - t0) * 1000)
+        return out
+
+    res = {"device": torch.cuda.get_device_name(0), "rows": B, "runs_per_round": runs, "rounds": 3, "warmup": 10, "in_rate": 24000,
+           "spec": "8 kHz mu-law, speed 1.25", "n_in_per_row": n, "n_out_per_row": n_out,
+           "unit": "ms per group of rows: median over all repeats; per_round: the median of each alternating round",
+           "launches": {"push_group": 2 * -(-B // ao.GROUP_MAX), "single pushes": 2 * B}}
+    voc_single, voc_stream = vocoder_group(g, B, runs)
+    res["vocoder_bf16x2_windowed_chunk_group_ms"] = {"median_single_call": round(voc_single, 4), "back_to_back_per_call": round(voc_stream, 4)}
+    cases = {"push_group (device rows)": (group, events), "single pushes (device rows)": (singles, events),
+             "push_group_host (one pinned copy)": (group_host, clock), "single push_host calls": (singles_host, clock)}
+    for fn, _how in cases.values():
+        for _ in range(10):
+            fn()
+    torch.cuda.synchronize()
+    samples = {k: [] for k in cases}
+    for _round in range(3):                                       # alternating: the forms see the same machine
+        for k, (fn, how) in cases.items():
+            samples[k].append(how(fn))
+    res["stage"] = {k: {"how": "device events around the call" if cases[k][1] is events else "host clock around the call (it ends in a synchronise)",
+                        "median_ms": round(statistics.median(v for r in rs for v in r), 4),
+                        "per_round_ms": [round(statistics.median(r), 4) for r in rs],
+                        "min_ms": round(min(v for r in rs for v in r), 4)} for k, rs in samples.items()}
+    gd, sd = res["stage"]["push_group (device rows)"]["median_ms"], res["stage"]["single pushes (device rows)"]["median_ms"]
+    gh, sh = res["stage"]["push_group_host (one pinned copy)"]["median_ms"], res["stage"]["single push_host calls"]["median_ms"]
+    res["notes"] = [
+        f"device rows: the group form takes {gd:.3f} ms, the {B} single pushes {sd:.3f} ms: " +
+        (f"{sd / gd:.2f}x faster" if gd < sd else f"NOT faster ({gd / sd:.2f}x the singles' time)"),
+        f"rows on the host: {gh:.3f} ms against {sh:.3f} ms: " + (f"{sh / gh:.2f}x faster" if gh < sh else f"NOT faster ({gh / sh:.2f}x the singles' time)"),
+        f"the vocoder's chunk decode for the same group takes {voc_stream:.3f} ms back to back: the group form is {gd / voc_stream:.3f} of it, "
+        f"the single pushes {sd / voc_stream:.3f}",
+        "every figure includes the host side of the call (Python, ctypes, the output allocations); the pushes are final pushes from a reset "
+        "stage, as in the other modes of this probe"]
+    os.makedirs(os.path.dirname(out_path) or ".", exist_ok=True)
+    with open(out_path, "w") as f:
+        json.dump(res, f, indent=1)
+        f.write("\n")
+    print(json.dumps(res, indent=1))
+
+
+def vocoder_group(g, B, runs):
+    """the yardstick for a group: (median single call, back to back per call) ms of the bf16x2 vocoder's windowed chunk decode of B rows"""
+    from fq3hip.codec import HipSpeechTokenizer
+    from fq3hip.config import qwen3_tts_0p6b
+    from fq3hip.weights import synth_weights
+    cfg = qwen3_tts_0p6b()
+    W = synth_weights(cfg, 0, torch.bfloat16, parts=("codec",), codec_normalized=True)
+    tok = HipSpeechTokenizer(cfg.codec, W, "cuda", max_frames=400, precision="bf16x2")
+    codes = torch.randint(0, cfg.codec.codebook_size, (B, 33, 16), generator=g).cuda()
+    first = tok.num_samples_total(33) - 8 * SAMPLES_PER_FRAME
+    return timed(lambda: tok.decode_tensor_batch(codes, first), runs)
+
+
 def main():
     args = sys.argv[1:]
+    if "--group" in args:
+        i = args.index("--group")
+        return main_group(int(args[i + 1]), args[:i] + args[i + 2:])
     if "--encoding" in args:
         i = args.index("--encoding")
         assert args[i + 1] == "flac", "--encoding flac is the only encoding with a probe of its own"

@@ -135,6 +135,11 @@ extern "C" int fq3_loud_destroy(fq3_loud* l) {
     return 0;
 }
 
+// fq3_level.hip: the per-hop arrays of a meter the leveller owns (capacity + 1 entries each), read by its target kernel
+void fq3_loud_buffers_(fq3_loud* l, const uint64_t** energy, const float** peak, const int** bad) {
+    *energy = l->energy; *peak = l->peak; *bad = l->bad;
+}
+
 extern "C" int fq3_loud_reset(fq3_loud* l, void* stream) {
     if (!l) return fq3_fail_(FQ3_EINVAL, "fq3_loud_reset: null object");
     (void)stream;                     // nothing to enqueue: every entry a finish reads is written by the pushes in front of it

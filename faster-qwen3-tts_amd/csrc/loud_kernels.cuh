@@ -108,6 +108,10 @@ __device__ __forceinline__ void loud_steps(const LoudPushArgs& a, const float* r
     if (kMeasure) z.e += ((uint64_t)hi << 23) + lo;
 }
 
+// FQ3_LOUD_NO_KERNELS (defined by a .hip file in front of its includes, never by a header): a second translation unit that wants the
+// __device__ helpers and constants above and below (fq3_level.hip) leaves the three __global__ definitions to fq3_loud.hip -- they
+// have external linkage and may exist once in the library.
+#ifndef FQ3_LOUD_NO_KERNELS
 __global__ void __launch_bounds__(kLoudLanes) loud_push_kernel(const LoudPushArgs a) {
     __shared__ float tile[kLoudLanes * kLoudPitch];
     __shared__ float r_pk[kLoudLanes];
@@ -204,6 +208,8 @@ __global__ void __launch_bounds__(kLoudLanes) loud_push_kernel(const LoudPushArg
     }
 }
 
+#endif  // FQ3_LOUD_NO_KERNELS
+
 struct LoudFinishArgs {
     const uint64_t* energy;
     const float* peak;
@@ -226,55 +232,82 @@ __device__ __forceinline__ void loud_reduce3(int tid, int& n, uint64_t& lo, uint
     n = r_n[0]; lo = r_lo[0]; hi = r_hi[0];
 }
 
-__global__ void __launch_bounds__(kLoudFinishThreads) loud_finish_kernel(const LoudFinishArgs a) {
-    __shared__ int r_n[kLoudFinishThreads];
-    __shared__ uint64_t r_lo[kLoudFinishThreads], r_hi[kLoudFinishThreads];
-    __shared__ float r_pk[kLoudFinishThreads];
+// The gating and the gain of the contract over the hops [0, n_hops), ONE copy: loud_finish_kernel runs it over a finished stream
+// (n_peaks = n_hops + 1: the partial hop behind the hops counts toward peak and non-finite count), the leveller's target kernel
+// (level_kernels.cuh) over every prefix of a running one (n_peaks = n_hops).  Called by all kLoudFinishThreads threads of a workgroup;
+// pk, nb, n1, n2 are valid on every thread, the doubles are formed where the caller asks for them (thread 0).
+struct LoudGateLds {
+    int r_n[kLoudFinishThreads];
+    uint64_t r_lo[kLoudFinishThreads], r_hi[kLoudFinishThreads];
+    float r_pk[kLoudFinishThreads];
+};
+
+struct LoudGate { float pk; int nb, n1, n2; uint64_t lo2, hi2; };
+
+__device__ __forceinline__ LoudGate loud_gate(const uint64_t* energy, const float* peak, const int* bad, int n_hops, int n_peaks,
+                                              uint64_t abs_gate, LoudGateLds& s) {
     const int tid = threadIdx.x;
-    // peak and non-finite count: the hops and the partial hop behind them
     float pk = 0.0f;
     int nb = 0;
-    for (int h = tid; h <= a.n_hops; h += kLoudFinishThreads) { pk = fmaxf(pk, a.peak[h]); nb += a.bad[h]; }
-    r_pk[tid] = pk;
+    for (int h = tid; h < n_peaks; h += kLoudFinishThreads) { pk = fmaxf(pk, peak[h]); nb += bad[h]; }
+    s.r_pk[tid] = pk;
     uint64_t z0 = 0, z1 = 0;
-    loud_reduce3(tid, nb, z0, z1, r_n, r_lo, r_hi);
-    for (int s = kLoudFinishThreads / 2; s > 0; s >>= 1) {
-        if (tid < s) r_pk[tid] = fmaxf(r_pk[tid], r_pk[tid + s]);
+    loud_reduce3(tid, nb, z0, z1, s.r_n, s.r_lo, s.r_hi);
+    for (int w = kLoudFinishThreads / 2; w > 0; w >>= 1) {
+        if (tid < w) s.r_pk[tid] = fmaxf(s.r_pk[tid], s.r_pk[tid + w]);
         __syncthreads();
     }
-    pk = r_pk[0];
-    const int n_blocks = a.n_hops >= 4 ? a.n_hops - 3 : 0;
+    pk = s.r_pk[0];
+    const int n_blocks = n_hops >= 4 ? n_hops - 3 : 0;
     int n1 = 0;
     uint64_t lo1 = 0, hi1 = 0;
     for (int b = tid; b < n_blocks; b += kLoudFinishThreads) {
-        const uint64_t B = a.energy[b] + a.energy[b + 1] + a.energy[b + 2] + a.energy[b + 3];
-        if (B > a.abs_gate) { ++n1; lo1 += B & 0xffffffffull; hi1 += B >> 32; }
+        const uint64_t B = energy[b] + energy[b + 1] + energy[b + 2] + energy[b + 3];
+        if (B > abs_gate) { ++n1; lo1 += B & 0xffffffffull; hi1 += B >> 32; }
     }
-    loud_reduce3(tid, n1, lo1, hi1, r_n, r_lo, r_hi);
+    loud_reduce3(tid, n1, lo1, hi1, s.r_n, s.r_lo, s.r_hi);
     const double s1d = (double)hi1 * 4294967296.0 + (double)lo1;
     const double tenfold = (double)(10 * (int64_t)n1);
     int n2 = 0;
     uint64_t lo2 = 0, hi2 = 0;
     for (int b = tid; b < n_blocks; b += kLoudFinishThreads) {
-        const uint64_t B = a.energy[b] + a.energy[b + 1] + a.energy[b + 2] + a.energy[b + 3];
-        if (B > a.abs_gate && (double)B * tenfold > s1d) { ++n2; lo2 += B & 0xffffffffull; hi2 += B >> 32; }
+        const uint64_t B = energy[b] + energy[b + 1] + energy[b + 2] + energy[b + 3];
+        if (B > abs_gate && (double)B * tenfold > s1d) { ++n2; lo2 += B & 0xffffffffull; hi2 += B >> 32; }
     }
-    loud_reduce3(tid, n2, lo2, hi2, r_n, r_lo, r_hi);
-    if (tid != 0) return;
+    loud_reduce3(tid, n2, lo2, hi2, s.r_n, s.r_lo, s.r_hi);
+    return LoudGate{pk, nb, n1, n2, lo2, hi2};
+}
+
+// mean power of the blocks that passed both gates (n2 > 0)
+__device__ __forceinline__ double loud_mean_power(const LoudGate& g, double four_h) {
+    const double s2d = (double)g.hi2 * 4294967296.0 + (double)g.lo2;
+    return s2d / ((double)g.n2 * four_h * kLoudScale);
+}
+
+// min(sqrt(target_power / mean_power), max_gain, ceiling / peak) in double, rounded once
+__device__ __forceinline__ float loud_gain(double mean_power, float pk, double target_power, double ceiling, double max_gain) {
+    double g = __dsqrt_rn(target_power / mean_power);
+    if (max_gain < g) g = max_gain;
+    if (pk > 0.0f) {
+        const double c = ceiling / (double)pk;
+        if (c < g) g = c;
+    }
+    return (float)g;
+}
+
+#ifndef FQ3_LOUD_NO_KERNELS
+__global__ void __launch_bounds__(kLoudFinishThreads) loud_finish_kernel(const LoudFinishArgs a) {
+    __shared__ LoudGateLds s;
+    // peak and non-finite count: the hops and the partial hop behind them
+    const LoudGate g = loud_gate(a.energy, a.peak, a.bad, a.n_hops, a.n_hops + 1, a.abs_gate, s);
+    if (threadIdx.x != 0) return;
     fq3_loud_stats st;
-    st.mean_power = 0.0; st.peak = pk; st.gain = 1.0f;
-    st.n_hops = a.n_hops; st.n_abs = n1; st.n_rel = n2; st.n_bad = nb; st.valid = 0; st.reserved = 0;
-    if (n2 > 0) {
-        const double s2d = (double)hi2 * 4294967296.0 + (double)lo2;
-        st.mean_power = s2d / ((double)n2 * a.four_h * kLoudScale);
-        if (nb == 0) {
-            double g = __dsqrt_rn(a.target_power / st.mean_power);
-            if (a.max_gain < g) g = a.max_gain;
-            if (pk > 0.0f) {
-                const double c = a.ceiling / (double)pk;
-                if (c < g) g = c;
-            }
-            st.gain = (float)g;
+    st.mean_power = 0.0; st.peak = g.pk; st.gain = 1.0f;
+    st.n_hops = a.n_hops; st.n_abs = g.n1; st.n_rel = g.n2; st.n_bad = g.nb; st.valid = 0; st.reserved = 0;
+    if (g.n2 > 0) {
+        st.mean_power = loud_mean_power(g, a.four_h);
+        if (g.nb == 0) {
+            st.gain = loud_gain(st.mean_power, g.pk, a.target_power, a.ceiling, a.max_gain);
             st.valid = 1;
         }
     }
@@ -302,5 +335,7 @@ __global__ void __launch_bounds__(kLoudApplyThreads) loud_apply_kernel(const flo
     const int64_t done = head + 4 * nv;
     if (done + tid < n) out[done + tid] = pcm[done + tid] * g;
 }
+
+#endif  // FQ3_LOUD_NO_KERNELS
 
 }  // namespace fq3

@@ -106,6 +106,16 @@ class LoudStats(C.Structure):
                 ("n_bad", i32), ("valid", i32), ("reserved", i32)]
 
 
+class LevelConfig(C.Structure):
+    _fields_ = [("in_rate", C.c_int), ("target_lufs", C.c_double), ("ceiling_db", C.c_double), ("max_gain_db", C.c_double),
+                ("initial_gain_db", C.c_double), ("smooth_hops", C.c_int), ("min_blocks", C.c_int), ("capacity_hops", C.c_int)]
+
+
+class LevelReport(C.Structure):
+    _fields_ = [("mean_power", C.c_double), ("target_gain", C.c_float), ("smooth_gain", C.c_float), ("n_hops", i32), ("n_abs", i32),
+                ("n_rel", i32), ("n_bad", i32), ("valid", i32), ("reserved", i32)]
+
+
 class NoiseRing(C.Structure):
     _fields_ = [("talker", vp), ("pred", vp), ("seed", C.c_uint64), ("first_frame", C.c_uint32), ("n_frames", i32)]
 
@@ -255,6 +265,13 @@ SIGNATURES = {
     "fq3_loud_finish": (C.c_int, [vp, vp, vp]),
     "fq3_loud_hops": (C.c_int, [vp, vp, C.c_int64, C.POINTER(C.c_int64), vp]),
     "fq3_loud_apply": (C.c_int, [vp, vp, C.c_int64, vp, vp]),
+    "fq3_level_create": (C.c_int, [C.POINTER(LevelConfig), C.POINTER(vp)]),
+    "fq3_level_destroy": (C.c_int, [vp]),
+    "fq3_level_reset": (C.c_int, [vp, vp]),
+    "fq3_level_set_initial_gain": (C.c_int, [vp, C.c_double]),
+    "fq3_level_push": (C.c_int, [vp, vp, C.c_int64, C.c_int, vp, vp]),
+    "fq3_level_stats": (C.c_int, [vp, vp, vp]),
+    "fq3_level_trace": (C.c_int, [vp, vp, vp, vp, vp, C.c_int64, C.POINTER(C.c_int64), vp]),
     "fq3_noise_fill": (C.c_int, [vp, C.POINTER(NoiseRing), C.c_int, C.c_int, vp]),
     "fq3_noise_first": (C.c_int, [vp, C.c_uint64, vp, vp]),
     "fq3_noise_words": (C.c_int, [C.c_uint64, C.c_uint32, C.c_uint32, C.c_int, vp, vp]),

@@ -161,7 +161,8 @@ def _exact(model, args):
 
 def _levelled(model, args):
     """``--loudness`` / ``--gain-db``: the model's ``loudness`` or ``fixed_gain`` context (the level set on the device), or a no-op;
-    ``--limiter-db``: the model's ``limiter`` context around it (the limiter runs behind the gain)."""
+    ``--level``: the model's ``leveller`` context (the streaming loudness leveller, behind the gain);
+    ``--limiter-db``: the model's ``limiter`` context around it (the limiter runs behind the gain and the leveller)."""
     import contextlib
     lufs, gain, ceiling = getattr(args, "loudness", None), getattr(args, "gain_db", None), getattr(args, "limiter_db", None)
     stack = contextlib.ExitStack()
@@ -169,6 +170,8 @@ def _levelled(model, args):
         stack.enter_context(model.loudness(target_lufs=lufs))
     elif gain is not None:
         stack.enter_context(model.fixed_gain(gain))
+    if getattr(args, "level", None) is not None:
+        stack.enter_context(model.leveller(target_lufs=args.level))
     if ceiling is not None:
         stack.enter_context(model.limiter(ceiling_db=ceiling))
     return stack
@@ -186,10 +189,15 @@ def check_level_args(parser, args):
         if getattr(args, "limiter_db", None) is not None:
             from .limiter import LimiterSpec
             LimiterSpec(ceiling_db=args.limiter_db)
+        if getattr(args, "level", None) is not None:
+            from .leveller import LevelSpec
+            LevelSpec(target_lufs=args.level)
     except ValueError as exc:
         parser.error(str(exc))
     if getattr(args, "loudness", None) is None:
         return
+    if getattr(args, "level", None) is not None:
+        parser.error("--loudness and --level answer the same question: give one (--level also works on a stream)")
     if getattr(args, "streaming", False) or getattr(args, "text_stdin", False):
         parser.error("--loudness measures the whole utterance, so it does not go with --streaming / --text-stdin: a stream's gain cannot "
                      "be known before it ends (use --gain-db X)")
@@ -273,7 +281,7 @@ def cmd_serve(args, model=None, lines=None):
         if not pending:
             continue
         start = time.perf_counter()
-        levelled = any(getattr(args, k, None) is not None for k in ("gain_db", "limiter_db"))
+        levelled = any(getattr(args, k, None) is not None for k in ("gain_db", "limiter_db", "level"))
         if len(pending) > 1 and args.mode == "clone" and not levelled:    # (--gain-db / --limiter-db: line by line, as before)
             # --out-rate / --encoding / --speed: the lines decoded together go through the output stage together (``output=``)
             spec = _output_spec(args)
@@ -332,6 +340,10 @@ def build_parser():
         sp.add_argument("--limiter-db", type=float, default=None, metavar="DB",
                         help="true-peak look-ahead limiter on the device behind the gain: no sample leaves above DB dBFS (-20 to 0; 5 ms "
                              "look-ahead, 20 ms hold); works in every mode, streaming included (default: off)")
+        sp.add_argument("--level", type=float, default=None, metavar="LUFS",
+                        help="streaming loudness leveller on the device: a causal BS.1770 gain that brings the stream to LUFS while it "
+                             "runs (zero latency, at most +20 dB); works in every mode, streaming included; it does not limit, so add "
+                             "--limiter-db; the defaults behind it are not tuned on real voices (default: off)")
         if output:
             sp.add_argument("--loudness", type=float, default=None, metavar="LUFS",
                             help="measure the utterance on the device (ITU-R BS.1770-4, integrated) and scale it to LUFS, at most +20 dB and "

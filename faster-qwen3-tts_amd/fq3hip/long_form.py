@@ -295,12 +295,13 @@ class OrderedJoin:
     chain (join -> time-scale -> resample / encode -> FLAC, one stream) and the pieces are its output.  ``gains`` (None; a 1-element
     float32 device tensor; or a list of them, one per segment): what segment ``k`` contributes -- its samples and the pause behind
     them -- leaves the join multiplied by ``gains`` / ``gains[k]`` (``fq3_loud_apply``).  ``limiter`` (None, or a ``Limiter``): the
-    joined and scaled stream goes through it in front of the chain."""
+    joined and scaled stream goes through it in front of the chain.  ``leveller`` (None, or a ``Leveller``): in front of the limiter."""
 
     def __init__(self, join: SegmentJoin, pauses: List[int], audio_out=None):
         self.join, self.pauses, self.audio_out = join, [int(p) for p in pauses], audio_out
         self.gains = None                                          # a 1-element device tensor, or one per segment: see ``_emit``
         self.limiter = None                                        # a ``Limiter`` on the join's stream: the joined stream goes through it
+        self.leveller = None                                       # a ``Leveller`` likewise, in front of the limiter
         self.n = len(self.pauses)
         self.cur = 0
         self._wait: List[List] = [[] for _ in range(self.n)]        # per segment: [(device tensor or None, last)]
@@ -314,6 +315,9 @@ class OrderedJoin:
             # level behind the join, in front of the chain: the join's silence decisions saw the raw samples, pause zeros stay zeros
             from .loudness import apply_gain
             y = apply_gain(y.contiguous(), g, self.join.stream)
+        if self.leveller is not None:
+            # the streaming loudness leveller: behind the gains, in front of the limiter; it holds nothing back
+            y = self.leveller.push(y.contiguous(), final=end == 2)
         if self.limiter is not None:
             # behind the gains, in front of the chain: one stream, so the look-ahead is held back once and comes out at the end
             y = self.limiter.push(y.contiguous(), final=end == 2)

@@ -317,18 +317,25 @@ class StreamingVocoder:
 
     ``gain`` / ``limiter`` (``FasterQwen3TTS.fixed_gain`` / ``limiter``): the chunk is multiplied and then limited on the vocoder's
     stream, in front of the output stage.  The limiter holds back ``A + 6`` samples of the stream; ``push(..., final=True)`` or
-    ``flush()`` hands them out, with or without an ``output``."""
+    ``flush()`` hands them out, with or without an ``output``.  ``leveller`` (``FasterQwen3TTS.leveller``): the streaming loudness
+    leveller (``fq3hip/leveller.py``) between the two; it holds nothing back and does not limit."""
 
     CONTEXT_FRAMES = 25
 
     def __init__(self, tok, ref_codes, chunk_size: int, device, side_stream=None, output=None, exact=False, gain=None, limiter=None,
-                 limiter_pool=None):
+                 limiter_pool=None, leveller=None, leveller_pool=None, leveller_hops: int = 0):
         self.tok, self.ref_codes, self.side = tok, ref_codes, side_stream
         self.output, self.stage, self.header_sent = output, None, False
         self.gain = gain                  # a 1-element float32 device tensor (``FasterQwen3TTS.fixed_gain``) or None
         # a ``LimiterSpec`` (``FasterQwen3TTS.limiter``) or None; the stage, taken at the first chunk and given back at the last;
         # ``limiter_pool``: a list the model keeps per (device, stream, spec) -- idle ``Limiter`` objects of finished utterances
         self.limit_spec, self.limit, self.limit_pool = limiter, None, limiter_pool
+        # a ``LevelSpec`` (``FasterQwen3TTS.leveller``) or None; its stage and pool likewise, between the gain and the limiter
+        # (the pool holds objects of ``leveller.pooled``: the initial gain is set per stream); ``leveller_hops``: the capacity a new
+        # object gets (0: 4096 hops); ``level_stats``: the device report of the utterance's leveller once its stream has ended;
+        # ``on_level``: a caller's hook (the server's worker keeps the voice-memory callback of its request here)
+        self.level_spec, self.level, self.level_pool, self.level_hops = leveller, None, leveller_pool, int(leveller_hops)
+        self.level_stats, self.on_level = None, None
         self.dev = torch.device(device) if not isinstance(device, torch.device) else device
         self.exact = bool(exact)
         if self.exact:
@@ -399,11 +406,14 @@ class StreamingVocoder:
         return out, int(getattr(self.tok, "sample_rate", 24000))
 
     def _gained(self, wav, final: bool = False):
-        """``wav`` (device tensor, on the vocoder's stream) times the fixed gain and then through the limiter, in front of the output
-        stage; without either: ``wav``.  The limiter holds back its look-ahead (``A + 6`` samples) until ``final`` or ``flush()``."""
+        """``wav`` (device tensor, on the vocoder's stream) times the fixed gain, through the leveller and then through the limiter,
+        in front of the output stage; without any: ``wav``.  The limiter holds back its look-ahead (``A + 6`` samples) until ``final``
+        or ``flush()``."""
         if self.gain is not None:
             from .loudness import apply_gain
             wav = apply_gain(wav.flatten().float().contiguous(), self.gain, self.side)
+        if self.level_spec is not None:
+            wav = self.level_push(wav.flatten().float().contiguous(), final)
         if self.limit_spec is not None:
             wav = self.limit_push(wav.flatten().float().contiguous(), final)
         return wav
@@ -433,6 +443,67 @@ class StreamingVocoder:
                 self.limit_pool.append(lim)
         return out
 
+    def level_push(self, wav, final: bool, out=None):
+        """``wav`` (contiguous float32 device vector) through this utterance's leveller on the vocoder's stream: as many samples come
+        back (into ``out``, if given).  The object is taken and given back as the limiter's is (``limit_push``)."""
+        if self.level is None:
+            try:
+                lev = self.level_pool.pop() if self.level_pool else None        # (another thread may take the last one first)
+            except IndexError:
+                lev = None
+            dev = self.dev if self.dev.index is not None else torch.device("cuda", torch.cuda.current_device())
+            if (lev is not None and lev.stream is self.side and lev.dev == dev and lev.spec.pooled == self.level_spec.pooled
+                    and lev.capacity_hops >= self.level_hops):
+                lev.reset(self.level_spec.initial_gain_db)          # one kept object, whatever gain the stream starts from
+                self.level = lev
+            else:
+                from .leveller import Leveller
+                self.level = Leveller(self.level_spec, int(getattr(self.tok, "sample_rate", 24000)), self.dev, self.side,
+                                      capacity_hops=self.level_hops)
+        y = self.level.push(wav, final, out=out)
+        if final:
+            self.level_release()
+        return y
+
+    def level_release(self) -> None:
+        """the utterance's leveller (if it has one) goes back to the pool: its stream has ended, with or without a final push"""
+        lev, self.level = self.level, None
+        if lev is not None:
+            self.level_stats = lev.stats_buffer()                  # the newest gains stay readable (``level_gain_db``), on the device
+            if self.level_pool is not None and len(self.level_pool) < self.LIMITER_POOL_MAX:
+                self.level_pool.append(lev)
+
+    @property
+    def level_gain_db(self):
+        """After the utterance: the leveller's last target in dB, None when it never measured one (or there was no leveller); waits
+        for the vocoder's stream."""
+        if self.level_stats is None:
+            return None
+        from .leveller import LevelStats
+        with (contextlib.nullcontext() if self.side is None else torch.cuda.stream(self.side)):
+            st = LevelStats.from_bytes(self.level_stats.cpu().numpy().tobytes())
+        return st.target_gain_db if st.valid else None
+
+    def level_report_async(self):
+        """After the utterance: ``(pinned host bytes, event)`` of the leveller's report -- the copy is queued on the vocoder's stream
+        and the event marks it, so a caller that may not wait (the server's scheduler thread) reads it once ``event.query()`` says so
+        (``level_gain_of``); None without a report."""
+        if self.level_stats is None:
+            return None
+        with (contextlib.nullcontext() if self.side is None else torch.cuda.stream(self.side)):
+            host = torch.empty(self.level_stats.shape, dtype=torch.uint8, pin_memory=True)
+            host.copy_(self.level_stats, non_blocking=True)
+            ev = torch.cuda.Event()
+            ev.record(self.side if self.side is not None else torch.cuda.current_stream(self.dev))
+        return host, ev
+
+    @staticmethod
+    def level_gain_of(host) -> Optional[float]:
+        """the last target in dB of a landed ``level_report_async`` copy, None when it never measured one"""
+        from .leveller import LevelStats
+        st = LevelStats.from_bytes(host.numpy().tobytes())
+        return st.target_gain_db if st.valid else None
+
     def _stage(self):
         """the output stage of this utterance, made at its first chunk (on the vocoder's stream; without one, on the current stream)"""
         if self.stage is None:
@@ -454,6 +525,9 @@ class StreamingVocoder:
         """With an ``output``: ends the stage's stream and returns ``(tail, rate)`` -- the samples it held back as look-ahead -- for an
         utterance whose last event carried no codes.  Empty after a ``push(..., final=True)``, and without an ``output``.  With a
         ``limiter``: ends its stream as well; the ``A + 6`` samples it held back come out (through the ``output`` stage, if any)."""
+        if self.level is not None:
+            with (contextlib.nullcontext() if self.side is None else torch.cuda.stream(self.side)):
+                self.level_release()                                # (it held nothing back)
         if self.limit is not None:
             # the limiter's held-back samples: they go out through the output stage, or as they are
             with (contextlib.nullcontext() if self.side is None else torch.cuda.stream(self.side)):
@@ -578,7 +652,7 @@ class StreamingVocoder:
             window = flat[start:]
             n_ctx = window.shape[0] - n_new
             new_audio, sr = self._vocode(window, int(round(n_ctx * self.spf)) if n_ctx > 0 else 0, ready_event)
-        if self.gain is not None or self.limit_spec is not None:
+        if self.gain is not None or self.limit_spec is not None or self.level_spec is not None:
             # synchronous tokenizer: its audio is on the host; the chunk is uploaded for the multiply (and the stages behind it)
             wav = self._gained(torch.from_numpy(np.ascontiguousarray(new_audio, dtype=np.float32)).to(self.dev), final)
             return self._encoded(wav, final) if self.output is not None else (wav.cpu().numpy(), sr)
@@ -606,6 +680,8 @@ class FasterQwen3TTS:
         self._loud = None                # the LoudnessSession of an open ``loudness`` context
         self._gain = None                # the factor of an open ``fixed_gain`` context
         self._limit = None               # the LimiterSpec of an open ``limiter`` context
+        self._lvl = None                 # the LevelSpec of an open ``leveller`` context
+        self._last_levelled = None       # the vocoder / leveller of the last levelled stream (``last_level_gain_db``)
         self._seed = None                # the sampling seed of an open ``seeded`` context
 
     # ---- small helpers pinned by the reference's unit tests ------------------------------------------------
@@ -1117,6 +1193,8 @@ class FasterQwen3TTS:
         design(self.sample_rate, spec)                       # the library's own range checks (host only)
         if getattr(self, "_gain", None) is not None:
             raise ValueError("loudness() inside fixed_gain(): one of the two sets the level")
+        if getattr(self, "_lvl", None) is not None:
+            raise ValueError("loudness() inside leveller(): the two answer the same question")
         prev, self._loud = getattr(self, "_loud", None), LoudnessSession(spec)
         try:
             yield self._loud
@@ -1162,6 +1240,56 @@ class FasterQwen3TTS:
         finally:
             self._limit = prev
 
+    @contextlib.contextmanager
+    def leveller(self, target_lufs: float = -16.0, ceiling_db: float = -1.0, max_gain_db: float = 20.0, initial_gain_db: float = 0.0,
+                 smooth_hops: int = 10, min_blocks: int = 8):
+        """Context manager: inside it every vocoder this model hands out (``streaming_vocoder``, hence every streaming entry point and
+        the server's workers) and every one-shot, ``*_batch`` and long-form path runs the streaming loudness leveller on the device
+        (``fq3hip/leveller.py``) behind the gain of ``fixed_gain`` and in front of the limiter, the time-scale
+        and the output stages.  It is causal and holds nothing back: a chunk keeps its length, and a sample's gain comes from the
+        BS.1770 measure of the 100 ms hops that ended before its own began -- ``initial_gain_db`` until ``min_blocks`` blocks of 400 ms
+        passed the absolute gate, then the mean of the last ``smooth_hops`` targets -- so the stream converges to the level
+        ``loudness()`` would have given the whole utterance.  It does NOT limit: a hop louder than everything before it can pass
+        ``ceiling_db``, so stream inside ``limiter()`` as well.  A stream's output does not depend on the chunk size beyond what the
+        vocoder's windowing does (``exact_streaming``: not at all).  The batch entry points give every utterance its own leveller;
+        long form levels the ONE joined stream, behind the join and the gains.  Together with ``loudness()`` it raises ``ValueError``:
+        the two answer the same question.  Yields the ``LevelSpec``.  The defaults are NOT tuned on real voices.  Iterate a streaming
+        generator inside the context.  Outside it nothing changes."""
+        from .leveller import LevelSpec
+        from .loudness import design
+        spec = LevelSpec(target_lufs, ceiling_db, max_gain_db, initial_gain_db, smooth_hops, min_blocks)
+        design(self.sample_rate, spec.loudness)              # the library's own range checks (host only)
+        if getattr(self, "_loud", None) is not None:
+            raise ValueError("leveller() inside loudness(): the two answer the same question")
+        prev, self._lvl = getattr(self, "_lvl", None), spec
+        try:
+            yield spec
+        finally:
+            self._lvl = prev
+
+    def _stream_level_hops(self) -> int:
+        """The capacity of an utterance's leveller: the hops of the longest stream the model can decode -- ``max_seq_len`` frames, the
+        bound of every frame limit (``max_new_tokens``, a text session) -- and at least the default 4096."""
+        from .leveller import MAX_HOPS
+        tok = getattr(getattr(getattr(self, "model", None), "model", None), "speech_tokenizer", None)
+        frames = int(getattr(self, "max_seq_len", 2048) or 2048)
+        per_frame = int(getattr(getattr(tok, "cfg", None), "total_upsample", 0) or (self.sample_rate * 2 // 25))
+        return min(MAX_HOPS, max(4096, frames * per_frame // (self.sample_rate // 10) + 2))
+
+    def _levelled(self, x, stream=None, inplace: bool = False):
+        """A whole utterance (contiguous float32 device vector) through the open ``leveller`` context's stage on ``stream`` (None: the
+        current one): one object per (device, stream), kept, reset for every utterance, replaced by a larger one when an utterance
+        needs more hops."""
+        from .leveller import Leveller, capacity_for
+        s = stream if stream is not None else torch.cuda.current_stream(x.device)
+        levs = self.__dict__.setdefault("_levellers", {})
+        key = (str(x.device), s.cuda_stream)
+        need = capacity_for(int(x.numel()), self.sample_rate)
+        if key not in levs or levs[key].spec.pooled != self._lvl.pooled or levs[key].capacity_hops < need:
+            levs[key] = Leveller(self._lvl, self.sample_rate, x.device, s, capacity_hops=max(need, 4096))
+        levs[key].reset(self._lvl.initial_gain_db)
+        return levs[key].push(x, final=True, out=x if inplace else None)
+
     def _limited(self, x, stream=None):
         """A whole utterance (contiguous float32 device vector) through the open ``limiter`` context's stage on ``stream`` (None: the
         current one): one object per (device, stream), kept, reset for every utterance."""
@@ -1187,7 +1315,8 @@ class FasterQwen3TTS:
         return g["tensors"][dev]
 
     def _levelling(self) -> bool:
-        return getattr(self, "_loud", None) is not None or getattr(self, "_gain", None) is not None or getattr(self, "_limit", None) is not None
+        return (getattr(self, "_loud", None) is not None or getattr(self, "_gain", None) is not None or getattr(self, "_limit", None) is not None
+                or getattr(self, "_lvl", None) is not None)
 
     def _refuse_streaming_loudness(self) -> None:
         if getattr(self, "_loud", None) is not None:
@@ -1234,6 +1363,8 @@ class FasterQwen3TTS:
         if self._gain is not None or self._loud is not None:
             gain = self._gain_tensor(x.device) if self._gain is not None else gain_of(self._measure(x, key, stream))
             x = apply_gain(x, gain, stream, out=x if inplace else None)
+        if getattr(self, "_lvl", None) is not None:
+            x = self._levelled(x, stream, inplace)
         if getattr(self, "_limit", None) is None:
             return x
         y = self._limited(x, stream)
@@ -1273,6 +1404,11 @@ class FasterQwen3TTS:
             # (the vocoders of one model share the vocoder stream; the pool is per spec, so a change of context starts another)
             kw["limiter"] = self._limit
             kw["limiter_pool"] = self.__dict__.setdefault("_limiter_pools", {}).setdefault(self._limit, [])
+        if getattr(self, "_lvl", None) is not None:
+            # (the pool is keyed WITHOUT the initial gain, which is set per stream: contexts that differ in it alone share objects)
+            kw["leveller"] = self._lvl
+            kw["leveller_pool"] = self.__dict__.setdefault("_leveller_pools", {}).setdefault(self._lvl.pooled, [])
+            kw["leveller_hops"] = self._stream_level_hops()
         return kw
 
     def _seed_kw(self) -> dict:
@@ -1440,6 +1576,7 @@ class FasterQwen3TTS:
         reference's windowing would emit for it."""
         from .streaming import fast_generate_streaming, parity_generate_streaming
         self._refuse_streaming_loudness()
+        self._last_levelled = None       # (``last_level_gain_db`` speaks of THIS stream once it has ended, never of an earlier one)
         tok = m.speech_tokenizer
         voc = StreamingVocoder(tok, ref_codes, chunk_size, self.device, self._vocoder_stream(tok), output=self._audio_spec, **self._exact_kw(),
                                **self._gain_kw())
@@ -1453,8 +1590,22 @@ class FasterQwen3TTS:
             new_audio, sr = voc.push(chunk, ev, final=bool(timing.get("is_final")))
             yield new_audio, sr, timing
         tail = self._tail_event(voc, timing)
+        if voc.level_spec is not None:
+            with (contextlib.nullcontext() if voc.side is None else torch.cuda.stream(voc.side)):
+                voc.level_release()                                 # (a stream that ended without a final chunk)
+            self._last_levelled = voc
         if tail is not None:
             yield tail
+
+    @property
+    def last_level_gain_db(self) -> Optional[float]:
+        """Inside or after ``leveller()``: the last target gain in dB of the single-stream or long-form stream that ended last -- what
+        the same voice's next stream may start from as ``initial_gain_db`` -- or None when it never reached a valid measure (or nothing
+        was levelled yet).  Waits for the vocoder's stream."""
+        last = getattr(self, "_last_levelled", None)
+        if last is None:
+            return None
+        return last.level_gain_db if hasattr(last, "level_gain_db") else last.final_gain_db
 
     @staticmethod
     def _gen_kwargs(max_new_tokens, min_new_tokens, temperature, top_k, top_p, do_sample, repetition_penalty):
@@ -1673,6 +1824,7 @@ class FasterQwen3TTS:
             self._refuse_batch_audio_output()
         gain = None if device_audio else self._gain_tensor()       # (long form multiplies behind the join)
         limit = None if device_audio else getattr(self, "_limit", None)      # (and limits there, as one stream)
+        lvl = None if device_audio else getattr(self, "_lvl", None)         # (and levels there, likewise)
         if seeds is not None:
             # the ``seeds=`` keyword of the public entry points is expanded HERE and in _run_batch_full, nowhere else; a caller that
             # builds its own requests (``rounds``) seeds them itself
@@ -1727,6 +1879,11 @@ class FasterQwen3TTS:
                 if gain is not None:
                     from .loudness import apply_gain
                     wav = apply_gain(wav.contiguous(), gain, side)
+                if lvl is not None:
+                    # every utterance's own leveller takes its row and writes a row of the same length: the group stays one tensor
+                    rows, wav = wav, torch.empty(wav.shape, dtype=torch.float32, device=wav.device)
+                    for k, j in enumerate(part):
+                        vocs[j[0]].level_push(rows[k].contiguous(), bool(j[1].get("is_final")), out=wav[k])
                 host = landed = encoded = None
                 staged = [k for k, j in enumerate(part) if vocs[j[0]].output is not None]
                 if limit is not None:
@@ -1841,7 +1998,7 @@ class FasterQwen3TTS:
                     else:
                         add_job([rid, out_meta, None, (inp, first, ev, vocs[rid].last_prefix)])
                 else:
-                    staged = limit is not None or vocs[rid].output is not None
+                    staged = limit is not None or lvl is not None or vocs[rid].output is not None
                     audio, _sr = vocs[rid].push(codes, ev, final=final) if staged else vocs[rid].push(codes, ev)
                     if final and vocs[rid].output is not None:
                         self._give_stage(vocs[rid].stage)
@@ -1849,6 +2006,10 @@ class FasterQwen3TTS:
                 n_chunks[rid] += 1
             elif final:
                 tail = np.zeros(1 if codes is None else 0, dtype=np.float32)
+                if lvl is not None and vocs[rid].level is not None:
+                    launch_open()                                  # the utterance's chunks that still wait end its leveller's stream
+                    with (contextlib.nullcontext() if side is None else torch.cuda.stream(side)):
+                        vocs[rid].level_release()
                 if vocs[rid].output is not None:
                     # what the output stage (and a limiter in front of it) held back leaves as this event's audio
                     launch_open()
@@ -2113,7 +2274,7 @@ class FasterQwen3TTS:
         join_bound(self.sample_rate, spec.threshold, spec.lead_hops, spec.tail_hops, spec.hold_hops, 0, 0)
         return spec, segs
 
-    def _long_chain(self, spec, segs, stream):
+    def _long_chain(self, spec, segs, stream, level_hops: Optional[int] = None):
         """The request's ONE output stream: the join stage and, inside ``audio_output``, the chain behind it, all on ``stream``."""
         from .long_form import OrderedJoin, SegmentJoin
         dev = torch.device(self.device) if not isinstance(self.device, torch.device) else self.device
@@ -2128,14 +2289,32 @@ class FasterQwen3TTS:
         if getattr(self, "_limit", None) is not None:
             from .limiter import Limiter
             oj.limiter = Limiter(self._limit, self.sample_rate, join.dev, stream)      # behind the join and the gains, one stream
+        if getattr(self, "_lvl", None) is not None:
+            from .leveller import Leveller
+            # behind the join and the gains, in front of the limiter: ONE leveller for the joined stream
+            oj.leveller = Leveller(self._lvl, self.sample_rate, join.dev, stream, capacity_hops=max(level_hops or 0, 4096))
+        self._last_levelled = oj.leveller
         return oj, chain
+
+    def _long_level_hops(self, spec, segs, gen_kwargs) -> Optional[int]:
+        """Inside ``leveller()``: the hops the joined stream of a long-form request can have -- every segment at its frame limit plus
+        its pause -- so that the one leveller is made large enough; ``ValueError`` beyond 2^20 hops, before anything decodes."""
+        if getattr(self, "_lvl", None) is None:
+            return None
+        from .leveller import capacity_for
+        tok = self.model.model.speech_tokenizer
+        frames = int(gen_kwargs.get("max_new_tokens", 2048))
+        per_seg = int(tok.num_samples_total(frames)) if hasattr(tok, "num_samples_total") else frames * (self.sample_rate * 2 // 25)
+        total = sum(per_seg + spec.pause_samples(s.pause, self.sample_rate) for s in segs)
+        return capacity_for(total, self.sample_rate)
 
     def _run_long_full(self, prepared, segs, spec, gen_kwargs, lanes: int) -> Tuple[list, int]:
         """The segments as the requests of one lock-step run, whole waveforms kept on the device, joined in text order on the side
         vocoder's stream, then (inside ``audio_output``) through the one-shot output stage as ONE utterance."""
         n = len(segs)
+        level_hops = self._long_level_hops(spec, segs, gen_kwargs)
         outs, voc = self._run_batch_full(prepared, gen_kwargs, lanes, n, seeds=getattr(self, "_seed", None), device_audio=True)
-        oj, _chain = self._long_chain(spec, segs, voc.stream)
+        oj, _chain = self._long_chain(spec, segs, voc.stream, level_hops)
         oj.audio_out = None                                         # the whole stream goes through _one_shot_output below
         parts = []
         with (torch.cuda.stream(voc.stream) if voc.stream is not None else contextlib.nullcontext()):
@@ -2162,7 +2341,7 @@ class FasterQwen3TTS:
         self._refuse_streaming_loudness()
         tok = self.model.model.speech_tokenizer
         side = self._vocoder_stream(tok)
-        oj, chain = self._long_chain(spec, segs, side)
+        oj, chain = self._long_chain(spec, segs, side, self._long_level_hops(spec, segs, gen_kwargs))
         sr = chain.out_rate if chain is not None else self.sample_rate
         header = chain is not None and chain.flac
         index = 0

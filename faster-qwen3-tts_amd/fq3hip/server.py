@@ -25,6 +25,7 @@ import asyncio
 import contextlib
 import json
 import logging
+import math
 import os
 import queue
 import sys
@@ -116,6 +117,7 @@ class BatchWorker:
     def _run(self):
         import torch
         from .batching import BatchRequest
+        from .model import StreamingVocoder
         m = self.model
         while True:
             first = None
@@ -139,6 +141,7 @@ class BatchWorker:
                 except queue.Empty:
                     continue
             waiting: Dict[int, Any] = {}
+            levels: list = []                   # (``--level``) reports of finished utterances on their way to the host: (bytes, event, hook)
             counter = [0]
             try:
                 with torch.inference_mode():
@@ -160,9 +163,38 @@ class BatchWorker:
                         spec = cfg.get("audio_output")            # the request's AudioOutSpec (create_app puts it there), or None
                         waiting[i] = (out, m.streaming_vocoder(rc, self.chunk_size) if spec is None else
                                       m.streaming_vocoder(rc, self.chunk_size, output=spec))
+                        level_start(waiting[i][1], cfg)
                         kw = m._gen_kwargs(int(cfg.get("max_new_tokens", 2048)), 2, 0.9, 50, 1.0, True, 1.05)
                         seed_kw = {} if cfg.get("seed") is None else dict(seed=cfg["seed"])     # (unseeded: the call stays what it was)
                         return BatchRequest(i, talker, tie, tam, tth, tpe, config, kw, **seed_kw)
+
+                    def level_start(voc, cfg):
+                        """``--level``: the request's leveller starts from what its voice's last stream learned, and reports back"""
+                        if getattr(voc, "level_spec", None) is not None and cfg.get("initial_gain_db") is not None:
+                            import dataclasses
+                            voc.level_spec = dataclasses.replace(voc.level_spec, initial_gain_db=float(cfg["initial_gain_db"]))
+                        voc.on_level = cfg.get("on_level")
+
+                    def level_end(voc):
+                        """the finished utterance's report is copied behind its last chunk; this thread, which feeds every lane, does
+                        not wait for it: ``level_poll`` hands it to the request's hook once the copy has landed"""
+                        if getattr(voc, "level_spec", None) is None or getattr(voc, "on_level", None) is None:
+                            return
+                        if voc.level is not None:                      # (an utterance that ended without a final chunk)
+                            with (contextlib.nullcontext() if voc.side is None else torch.cuda.stream(voc.side)):
+                                voc.level_release()
+                        rep = voc.level_report_async()
+                        if rep is not None:
+                            levels.append((rep[0], rep[1], voc.on_level))
+
+                    def level_poll(wait=False):
+                        for item in list(levels):
+                            host, ev, hook = item
+                            if wait:
+                                ev.synchronize()
+                            if wait or ev.query():
+                                levels.remove(item)
+                                hook(StreamingVocoder.level_gain_of(host))
 
                     def prepare_text(item):
                         """A text session: parked until its first token exists, then a request built around that token."""
@@ -197,6 +229,7 @@ class BatchWorker:
                         spec = cfg.get("audio_output")
                         waiting[i] = (out, m.streaming_vocoder(None, self.chunk_size) if spec is None else
                                       m.streaming_vocoder(None, self.chunk_size, output=spec))
+                        level_start(waiting[i][1], cfg)
                         return req
 
                     def source():
@@ -223,10 +256,12 @@ class BatchWorker:
                     for rid, codes, info in m._batch_decoder(self.lanes).run([head] if head is not None else [], on_error="yield",
                                                                              source=source, chunk_frames=chunk_frames):
                         out, voc = waiting[rid]
+                        level_poll()
                         final = bool(info.get("is_final")) or "error" in info
                         if "error" in info or (codes is None and final and info.get("steps", 0) == 0):
                             out.put(RuntimeError(info.get("error", "generation returned no tokens")))
-                        elif getattr(voc, "output", None) is not None or getattr(voc, "limit_spec", None) is not None:
+                        elif (getattr(voc, "output", None) is not None or getattr(voc, "limit_spec", None) is not None
+                              or getattr(voc, "level_spec", None) is not None):
                             # the request asked for a rate / encoding, or the server limits: the chunk comes back encoded (or float32); the
                             # last one brings the tail that the output stage / the limiter held back
                             if codes is not None and codes.shape[0] > 0:
@@ -239,8 +274,10 @@ class BatchWorker:
                             audio, _sr = voc.push(codes, info.get("codes_ready_event"))
                             out.put(np.asarray(audio, dtype=np.float32))
                         if final:
+                            level_end(voc)
                             out.put(self.DONE)
                             waiting.pop(rid, None)
+                    level_poll(wait=True)                              # the scheduler is idle: the last reports may be waited for
                 # the scheduler is done: nobody may be left without an answer (a request it never reported would otherwise
                 # block its HTTP handler and an executor thread forever)
                 for out, _ in waiting.values():
@@ -254,12 +291,24 @@ class BatchWorker:
                 waiting.clear()
 
 
+LEVEL_FIELDS = ("target_lufs", "ceiling_db", "max_gain_db", "smooth_hops", "min_blocks")
+
+
+def voice_key(cfg: dict, name: str):
+    """What the learned gains of ``--level`` are kept under: for a voice with a reference clip the leading fields of the model's voice
+    prompt cache key -- ``(str(ref_audio), ref_text)``, so two names for one clip share a gain -- else the speaker's or the voice's name."""
+    if cfg.get("ref_audio") is not None:
+        return (str(cfg["ref_audio"]), cfg.get("ref_text", ""))
+    return ("speaker", str(cfg["speaker"])) if cfg.get("speaker") else ("voice", str(name))
+
+
 DEFAULT_LOUDNESS_TEXT = "The quick brown fox jumps over the lazy dog, and then it rests beside the quiet river for a while."
 
 
 def create_app(model, voices: Dict[str, dict], default_voice: Optional[str] = None, scheduler: str = "lock", lanes: int = 8,
                chunk_size: int = 12, worker=None, prefix_cache_rows: int = 0, long_form=None, exact_streaming: bool = False,
-               loudness: Optional[float] = None, loudness_text: str = DEFAULT_LOUDNESS_TEXT, limiter_db: Optional[float] = None):
+               loudness: Optional[float] = None, loudness_text: str = DEFAULT_LOUDNESS_TEXT, limiter_db: Optional[float] = None,
+               level: Optional[float] = None):
     """``worker``: a ready ``BatchWorker`` (or a stand-in with ``submit`` / ``submit_text``) instead of the one ``scheduler="batch"``
     would start.  ``prefix_cache_rows`` > 0: the model's prefix KV cache (``FasterQwen3TTS.enable_prefix_cache``) with that many rows:
     the engine's cache under the ``lock`` scheduler; under ``batch`` the ``BatchWorker`` started here creates the scheduler's own
@@ -275,7 +324,13 @@ def create_app(model, voices: Dict[str, dict], default_voice: Optional[str] = No
     the gains and says which voices are calibrated.  ``limiter_db`` (a ceiling in dBFS; None: off; server-wide, both schedulers and
     the text sessions): the model's ``limiter()`` context is entered for the life of the app, behind the calibration, so every reply
     leaves through a true-peak look-ahead limiter on the device.  ``loudness`` and ``limiter_db`` together are the safe way to serve a
-    levelled stream: the gain comes from one calibration sentence, and the limiter catches the reply that comes out hotter."""
+    levelled stream: the gain comes from one calibration sentence, and the limiter catches the reply that comes out hotter.
+    ``level`` (a target in LUFS; None: off; server-wide, BOTH schedulers and the text sessions): the model's ``leveller()`` context is
+    entered for the life of the app, so every stream is levelled while it runs (``fq3hip/leveller.py``: causal, zero latency; it does
+    not limit -- without ``limiter_db`` one warning says so).  Per-voice memory: when a stream ends with a valid measure, its last
+    target gain is remembered under the voice's key (``voice_key``) and the voice's next request starts from it as
+    ``initial_gain_db``; that reply carries ``X-Initial-Gain-Db`` and ``/health`` lists what was learned.  The memory is a dict in
+    this process, nothing is written to disk.  Not together with ``loudness``.  The leveller's defaults are not tuned on real voices."""
     from fastapi import FastAPI, HTTPException
     from .long_form import LongFormSpec
     long_spec = long_form if long_form is not None else LongFormSpec()
@@ -294,7 +349,7 @@ def create_app(model, voices: Dict[str, dict], default_voice: Optional[str] = No
     if worker is None and int(prefix_cache_rows or 0) > 0:
         prefix_cache = model.enable_prefix_cache(int(prefix_cache_rows))
     sessions: Dict[str, dict] = {}
-    sessions_lock = threading.Lock()
+    sessions_lock = threading.Lock()             # (the gains ``level`` learns live under it too)
     sample_rate = int(getattr(model, "sample_rate", 24000))
     gains: Dict[int, dict] = {}                  # id(voice entry) -> its calibration (``loudness``)
     if loudness is not None:
@@ -316,6 +371,33 @@ def create_app(model, voices: Dict[str, dict], default_voice: Optional[str] = No
                                    lufs=round(float(st.lufs), 3) if st.valid else None)
             logger.info("loudness: voice %r reads %s LUFS, gain %+.2f dB%s", name, gains[id(vcfg)]["lufs"], gains[id(vcfg)]["gain_db"],
                         "" if st.valid else " (could not be calibrated)")
+
+    learned: Dict[Any, float] = {}               # voice key -> the last valid target gain (dB) of that voice's streams (``level``)
+    if level is not None:
+        if loudness is not None:
+            raise ValueError("--level and --loudness answer the same question: give one")
+        if not hasattr(model, "leveller"):
+            raise ValueError("level: this model has no leveller() context")
+        app.state.leveller = contextlib.ExitStack()
+        app.state.level_spec = app.state.leveller.enter_context(model.leveller(target_lufs=float(level)))      # (ValueError outside [-40, -5])
+        if limiter_db is None:
+            logger.warning("--level without --limiter-db: the leveller does not limit, a passage louder than everything before it can "
+                           "pass the ceiling (add --limiter-db)")
+
+    def level_cfg(cfg: dict, name: str):
+        """``level``: the request's voice entry with the gain its voice learned and the hook that learns the next -> (cfg, headers)"""
+        if level is None:
+            return cfg, {}
+        key = voice_key(cfg, name)
+        with sessions_lock:
+            start = learned.get(key)
+
+        def on_level(gain_db):
+            if gain_db is not None and math.isfinite(gain_db):
+                with sessions_lock:
+                    learned[key] = round(float(gain_db), 3)
+        cfg = dict(cfg, on_level=on_level, **({} if start is None else dict(initial_gain_db=start)))
+        return cfg, ({} if start is None else {"X-Initial-Gain-Db": f"{start:.3f}"})
 
     if limiter_db is not None:
         if not hasattr(model, "limiter"):
@@ -402,7 +484,9 @@ def create_app(model, voices: Dict[str, dict], default_voice: Optional[str] = No
             try:
                 with lock, (contextlib.nullcontext() if spec is None else model.audio_output(spec.sample_rate, spec.encoding, spec.speed)), \
                         (contextlib.nullcontext() if cfg.get("seed") is None else model.seeded(cfg["seed"])), \
-                        (contextlib.nullcontext() if cfg.get("gain_db") is None else model.fixed_gain(cfg["gain_db"])):
+                        (contextlib.nullcontext() if cfg.get("gain_db") is None else model.fixed_gain(cfg["gain_db"])), \
+                        (contextlib.nullcontext() if cfg.get("initial_gain_db") is None else
+                         model.leveller(**dict({k: getattr(app.state.level_spec, k) for k in LEVEL_FIELDS}, initial_gain_db=cfg["initial_gain_db"]))):
                     gen = (model.generate_long_voice_clone_streaming(chunk_size=cfg.get("chunk_size", 12), non_streaming_mode=False,
                                                                      lanes=lanes, long_form=long_spec, **clone_kwargs(cfg, text), **instruct_kw)
                            if long else
@@ -410,6 +494,8 @@ def create_app(model, voices: Dict[str, dict], default_voice: Optional[str] = No
                                                                 **clone_kwargs(cfg, text), **instruct_kw))
                     for chunk, _sr, _t in gen:
                         q.put(chunk)
+                    if cfg.get("on_level") is not None:
+                        cfg["on_level"](getattr(model, "last_level_gain_db", None))
             except Exception as exc:
                 q.put(exc)
             finally:
@@ -425,7 +511,7 @@ def create_app(model, voices: Dict[str, dict], default_voice: Optional[str] = No
                 raise item
             yield to_pcm16(item) if spec is None else np.ascontiguousarray(item).tobytes()
 
-    async def box_response(box, fmt: str, on_end=None, spec=None, seed=None):
+    async def box_response(box, fmt: str, on_end=None, spec=None, seed=None, headers=None):
         """The streaming body of a batch-scheduler reply queue (``BatchWorker.submit`` / ``submit_text``)."""
         loop = asyncio.get_event_loop()
 
@@ -467,7 +553,7 @@ def create_app(model, voices: Dict[str, dict], default_voice: Optional[str] = No
                 if on_end is not None:
                     on_end()
 
-        return StreamingResponse(replay(), media_type=CONTENT_TYPES[fmt], headers=seed_headers(seed))
+        return StreamingResponse(replay(), media_type=CONTENT_TYPES[fmt], headers=dict(seed_headers(seed) or {}, **(headers or {})) or None)
 
     # ---- text sessions: the text arrives in pieces while the audio is already streaming (batch scheduler) -----------------------
     def drop_session(sid: str):
@@ -499,6 +585,7 @@ def create_app(model, voices: Dict[str, dict], default_voice: Optional[str] = No
         seed = request_seed(req)
         if seed is not None:
             cfg = dict(cfg, seed=seed)
+        cfg, level_headers = level_cfg(cfg, req.voice)
         try:
             from .model import FasterQwen3TTS
             FasterQwen3TTS._refuse_icl_text_stream(True, cfg.get("voice_clone_prompt"))
@@ -513,7 +600,7 @@ def create_app(model, voices: Dict[str, dict], default_voice: Optional[str] = No
             for old in [k for k, s in sessions.items() if not s["reading"] and s["feeder"].closed and now - s["t_closed"] > 60.0]:
                 sessions.pop(old, None)
             sessions[sid] = dict(feeder=feeder, box=worker.submit_text(cfg, feeder), fmt=fmt, reading=False, t_closed=now, spec=spec,
-                                 seed=seed)
+                                 seed=seed, headers=level_headers)
         return {"id": sid} if seed is None else {"id": sid, "seed": seed}
 
     @app.post("/v1/audio/speech/sessions/{sid}/text")
@@ -536,7 +623,8 @@ def create_app(model, voices: Dict[str, dict], default_voice: Optional[str] = No
             if s["reading"]:
                 raise HTTPException(status_code=409, detail="this session's audio is being read already")
             s["reading"] = True
-        return await box_response(s["box"], s["fmt"], on_end=lambda: drop_session(sid), spec=s["spec"], seed=s.get("seed"))
+        return await box_response(s["box"], s["fmt"], on_end=lambda: drop_session(sid), spec=s["spec"], seed=s.get("seed"),
+                                  headers=s.get("headers"))
 
     @app.get("/health")
     async def health():
@@ -551,6 +639,11 @@ def create_app(model, voices: Dict[str, dict], default_voice: Optional[str] = No
         if limiter_db is not None:
             spec = app.state.limiter_spec                   # the LimiterSpec in force, as the model's context yielded it
             out["limiter"] = {k: float(getattr(spec, k)) for k in ("ceiling_db", "lookahead_ms", "hold_ms")}
+        if level is not None:
+            spec = app.state.level_spec                     # the LevelSpec in force, as the model's context yielded it
+            with sessions_lock:
+                known = {str(k): v for k, v in learned.items()}
+            out["level"] = dict({k: getattr(spec, k) for k in LEVEL_FIELDS}, learned_gains_db=known)
         return out
 
     @app.post("/v1/audio/speech")
@@ -572,10 +665,11 @@ def create_app(model, voices: Dict[str, dict], default_voice: Optional[str] = No
             cfg = dict(cfg, gain_db=gain["gain_db"])
         if seed is not None:
             cfg = dict(cfg, seed=seed)
+        cfg, level_headers = level_cfg(cfg, req.voice)
         n_segments = long_segments(req)
         if worker is not None:
             return await box_response(worker.submit(cfg if spec is None else dict(cfg, audio_output=spec), req.input), fmt, spec=spec,
-                                      seed=seed)
+                                      seed=seed, headers=level_headers)
 
         async def audio_stream():
             if fmt == "wav":
@@ -584,7 +678,7 @@ def create_app(model, voices: Dict[str, dict], default_voice: Optional[str] = No
             async for raw in stream_chunks(cfg, req.input, spec, long=n_segments > 0):
                 yield raw
 
-        headers = dict(seed_headers(seed) or {})
+        headers = dict(seed_headers(seed) or {}, **level_headers)
         if gain is not None:
             headers["X-Gain-Db"] = f"{gain['gain_db']:.3f}"
         if n_segments > 0:
@@ -623,12 +717,21 @@ def build_parser():
                    help="server-wide true-peak look-ahead limiter on the device: no sample of any reply leaves above DB dBFS (-20 to 0); both "
                         "schedulers and the text sessions.  With --loudness the two together are the safe way to serve a levelled stream: a "
                         "reply hotter than the calibration sentence is limited instead of clipped (default: off)")
+    p.add_argument("--level", type=float, default=None, metavar="LUFS",
+                   help="server-wide streaming loudness leveller on the device: every stream is brought to LUFS while it runs (causal BS.1770 "
+                        "gain, zero latency); both schedulers and the text sessions.  A voice's next request starts from the gain its last "
+                        "stream ended with (X-Initial-Gain-Db; kept in memory only).  It does not limit: add --limiter-db.  Its defaults are "
+                        "not tuned on real voices (default: off)")
     return p
 
 
 def main(argv=None):
     parser = build_parser()
     args = parser.parse_args(argv)
+    if args.level is not None and args.loudness is not None:
+        parser.error("--level and --loudness answer the same question: give one")
+    if args.level is not None and not -40.0 <= args.level <= -5.0:
+        parser.error("--level is a target in LUFS, -40 to -5")
     if args.loudness is not None and args.scheduler == "batch":
         parser.error("--loudness is served by the lock scheduler: add --scheduler lock (the batch worker has no per-request gain yet)")
     if args.limiter_db is not None and not -20.0 <= args.limiter_db <= 0.0:
@@ -651,7 +754,7 @@ def main(argv=None):
     logging.basicConfig(level=logging.INFO)
     uvicorn.run(create_app(model, voices, default_voice, args.scheduler, args.lanes, args.chunk_size,
                            prefix_cache_rows=args.prefix_cache_rows, exact_streaming=args.exact_streaming, loudness=args.loudness,
-                           loudness_text=args.loudness_text, limiter_db=args.limiter_db), host=args.host, port=args.port)
+                           loudness_text=args.loudness_text, limiter_db=args.limiter_db, level=args.level), host=args.host, port=args.port)
 
 
 if __name__ == "__main__":

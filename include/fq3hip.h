@@ -809,6 +809,66 @@ int fq3_limit_push(fq3_limit* l, const float* pcm, int64_t n_in, int final, floa
 /* the accumulators of the pushes enqueued so far into *stats_dev (DEVICE memory, 8-byte aligned); one launch of one thread */
 int fq3_limit_stats(fq3_limit* l, fq3_limit_report* stats_dev, void* stream);
 
+/* ---- Leveller: a causal BS.1770 gain for a stream that has not ended ------------------------------------------------------------------
+ * Float32 mono in, float32 out at the same rate: length-preserving, ZERO latency, and independent of how the stream was cut into
+ * pushes, of the alignment and of the launch geometry, bit for bit.  Behind the fixed gain (fq3_loud_apply), in front of the limiter.
+ * The gain of a sample is built from the loudness meter's hop integers of the hops that ENDED before the sample's own hop began, so it
+ * converges to the gain one-shot normalisation (fq3_loud_finish) would have applied to the whole stream.  The stage does NOT limit: a
+ * hop louder than everything before it can pass the ceiling -- the limiter is the stage behind it for that.
+ *
+ * Design constants: in_rate a multiple of 100 in [8000, 48000], H = in_rate / 10;  d = fq3_loud_design(in_rate, target_lufs,
+ * ceiling_db, max_gain_db) (the same call, the same ranges);  g0 = (float) 10^(initial_gain_db / 20), computed once on the host in
+ * double and rounded once, initial_gain_db in [-60, 40];  k = smooth_hops in [1, 64];  m = min_blocks in [1, 64];  else FQ3_EINVAL.
+ * The defaults callers use (-16 LUFS, -1 dBFS, +20 dB, 0 dB, k = 10, m = 8) have NOT been tuned on real voices.
+ *
+ * Per-hop measures: for every whole hop h of the stream, E_h, peak_h and bad_h are what fq3_loud_push produces for the same samples
+ * (the per-hop restart from zero state, the 2^40 quantum and the clip at 64 included): the same integers, bit for bit.
+ * Target: T(h), h >= 0, is the gain of the fq3_loud_finish computation run over the PREFIX E[0 .. h) with peak = max(peak_j, j < h)
+ * and n_bad = sum(bad_j, j < h) -- the same split sums, doubles, relative gate and min(sqrt(T / mean_power), Gmax, C / peak) -- when
+ * that prefix is valid (at least one block passes both gates, no non-finite sample) AND its n_abs >= m; otherwise T(h) = g0.
+ * T(h) = g0 for h < 0.  (m keeps the first blocks behind leading silence, which hold more silence than sound and read low, from
+ * setting the gain.)
+ * Smoothing: S(h) = (float) ((sum over i = h - k + 1 .. h, ascending, of (double) T(i)) / (double) k), so S(-1) = g0.
+ * Output: sample n lies in hop h = floor(n / H) at offset j = n - h H:
+ *   y[n] = x[n] * fmaf(S(h) - S(h - 1), (float) j / (float) H, S(h - 1))
+ * in IEEE float32 (the division correctly rounded), nothing contracted except where written.  A sample of hop h needs only hops < h,
+ * which are complete when it arrives.  A non-finite sample passes through (NaN in, NaN out); from the next hop on T = g0.
+ * Cost: the target of hop h walks its prefix twice, so a push that enters N hops behind h0 costs about N (h0 + N / 2) block sums:
+ * nothing for a stream fed chunk by chunk, but quadratic in ONE push -- about 5 * 10^11 for a single push of 2^20 hops.  Feed audio
+ * of more than a few thousand hops in pieces. */
+typedef struct fq3_level fq3_level;
+/* capacity_hops in [0, 2^20], 0: 4096 hops (about 410 s) */
+typedef struct fq3_level_config {
+    int in_rate; double target_lufs, ceiling_db, max_gain_db, initial_gain_db; int smooth_hops, min_blocks, capacity_hops;
+} fq3_level_config;
+/* of the newest hop h = n_hops the stream has entered: target_gain = T(h), smooth_gain = S(h); n_abs / n_rel / n_bad / mean_power:
+ * of the prefix E[0 .. h); valid: T(h) is the prefix's measured gain (0: it is g0) */
+typedef struct fq3_level_report { double mean_power; float target_gain, smooth_gain; int32_t n_hops, n_abs, n_rel, n_bad, valid, reserved; } fq3_level_report;
+/* One object per stream: a loudness meter (fq3_loud_create) plus T per hop, on the current device.  NULL or range errors are answered
+ * before any HIP call. */
+int fq3_level_create(const fq3_level_config* cfg, fq3_level** out);
+int fq3_level_destroy(fq3_level* l);                         /* NULL -> 0 */
+/* a new stream on the same object (nothing is enqueued) */
+int fq3_level_reset(fq3_level* l, void* stream);
+/* g0 = (float) 10^(initial_gain_db / 20) for the stream that begins: legal between create / reset and the first sample (afterwards
+ * FQ3_ESTATE), initial_gain_db in [-60, 40] (else FQ3_EINVAL); host only, nothing is enqueued.  It is how ONE kept object serves
+ * streams that start from different gains (a voice's last measured one): reset, set, push.  A reset alone keeps the last g0. */
+int fq3_level_set_initial_gain(fq3_level* l, double initial_gain_db);
+/* pcm: n_in device floats at any float alignment (n_in may be 0), the next samples of the stream; final != 0: the stream ends with
+ * them.  out receives exactly n_in samples and may equal pcm (it may not overlap it otherwise).  At most THREE launches on `stream`
+ * (the meter's, the targets of the hops the push enters, the multiply; none for an empty push), no host synchronisation.  More hops
+ * than the capacity: FQ3_ETOOLONG.  Every error is answered before anything is launched or changed.  After a final push: FQ3_ESTATE
+ * until fq3_level_reset. */
+int fq3_level_push(fq3_level* l, const float* pcm, int64_t n_in, int final, float* out, void* stream);
+/* the state behind the pushes enqueued so far into *stats_dev (DEVICE memory, 8-byte aligned); one launch of one thread.  Before the
+ * first sample: T = S = g0, everything else 0. */
+int fq3_level_stats(fq3_level* l, fq3_level_report* stats_dev, void* stream);
+/* for tests and probes: the hop integers of the n whole hops so far (energy: uint64, peak: float, bad: int32; n values each) and
+ * T(0 .. n) (n + 1 floats) to device buffers with room for `capacity` hops (capacity + 1 floats of T; fewer than the hops:
+ * FQ3_EINVAL; a NULL buffer is skipped), n to *n_hops (host) */
+int fq3_level_trace(fq3_level* l, uint64_t* energy_dev, float* peak_dev, int32_t* bad_dev, float* target_dev, int64_t capacity,
+                    int64_t* n_hops, void* stream);
+
 /* ---- Seeded sampling noise: the samplers' Exp(1) variates from a counter-based generator on the device -------------------------
  * The samplers divide by host-provided noise (fq3_sample's noise vector, the rings of fq3_decode_begin).  These calls fill such
  * buffers as a PURE FUNCTION of (seed, emitted-frame index, slot, vocabulary index): no state, no dependence on lane, batch

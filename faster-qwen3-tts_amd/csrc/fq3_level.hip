@@ -1,6 +1,8 @@
 // Leveller behind the C ABI: a causal, zero-latency BS.1770 gain for a stream that has not ended (include/fq3hip.h, "Leveller").
 //   fq3_level_create / _push   the meter's launch (fq3_loud_push on a meter the object owns: the hop integers ARE the meter's), the
 //                              targets T of the hops the push enters (one workgroup per hop), the ramped multiply: three launches
+//   fq3_leveller_push_group       the pushes of up to 32 objects of one design in at most three launches (the meters', the targets',
+//                              the multiplies'), each row bit for bit its single push
 //   fq3_level_set_initial_gain g0 of the next stream on a kept object (host only)
 //   fq3_level_stats            the newest T and S and the prefix's measure into device memory, one launch of one thread
 //   fq3_level_trace            hop integers and T so far, for tests and probes
@@ -16,6 +18,7 @@ using namespace fq3;
 
 int fq3_fail_(int code, const std::string& m);                 // fq3_api.hip: sets the thread-local error string
 void fq3_loud_buffers_(fq3_loud* l, const uint64_t** energy, const float** peak, const int** bad);      // fq3_loud.hip
+int fq3_loud_push_group_(fq3_loud* const* objs, int B, const float* const* pcm, const int64_t* n_in, const int* final, void* stream);      // fq3_loud.hip
 #define VHIP(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) return fq3_fail_(FQ3_EHIP, std::string(#x) + ": " + hipGetErrorString(e_)); } while (0)
 
 namespace {
@@ -99,37 +102,136 @@ extern "C" int fq3_level_set_initial_gain(fq3_level* l, double initial_gain_db) 
     return 0;
 }
 
+namespace {
+
+// One push, in the steps the single and the group entry share (as in fq3_audio.hip): check_push_ refuses and leaves the object alone,
+// plan_push_ reads the object's state into the two kernels' arguments, commit_push_ moves the object.  The meter's launch lies between
+// check and plan: fq3_loud_push (or its group form) checks the meter itself and moves nothing when it refuses.
+int check_push_(const std::string& who, const fq3_level* l, const float* pcm, int64_t n_in, const float* out) {
+    if (n_in < 0 || n_in > kMaxPush || (n_in > 0 && (!pcm || !out))) return fq3_fail_(FQ3_EINVAL, who + ": bad input");
+    if (l->finished) return fq3_fail_(FQ3_ESTATE, who + ": the stream has ended; fq3_level_reset starts the next one");
+    const int64_t h1 = (l->total + n_in) / l->H;
+    if (h1 > l->capacity)
+        return fq3_fail_(FQ3_ETOOLONG, who + ": " + std::to_string(h1) + " hops exceed the capacity of " + std::to_string(l->capacity));
+    return 0;
+}
+
+// n_in > 0.  -> whether the push enters a hop: T[t_done .. h1], hop h1 being the last one a sample of this push lies in (or the one behind it)
+bool plan_push_(const fq3_level* l, const float* pcm, int64_t n_in, float* out, LevelTargetArgs* tp, LevelApplyArgs* ap) {
+    const int64_t h1 = (l->total + n_in) / l->H;
+    LevelTargetArgs& k = *tp;
+    k.energy = l->energy; k.peak = l->peak; k.bad = l->bad; k.T = l->T; k.slot = l->slot;
+    k.h_first = l->t_done; k.h_last = (int)h1; k.min_blocks = l->m; k.g0 = l->g0;
+    k.abs_gate = l->abs_gate; k.four_h = (double)(4 * l->H); k.target_power = l->target_power; k.ceiling = l->ceiling; k.max_gain = l->max_gain;
+    LevelApplyArgs& a = *ap;
+    a.pcm = pcm; a.out = out; a.T = l->T; a.n0 = l->total; a.n_in = n_in; a.H = l->H; a.k = l->k; a.g0 = l->g0;
+    return (int)h1 >= l->t_done;
+}
+
+void commit_push_(fq3_level* l, int64_t n_in, int final) {
+    if (n_in > 0) {
+        const int64_t total = l->total + n_in, h1 = total / l->H;
+        if ((int)h1 >= l->t_done) l->t_done = (int)h1 + 1;
+        l->total = total;
+    }
+    if (final) l->finished = true;
+}
+
+// rows share every config field but initial_gain_db and capacity_hops
+bool same_design_(const fq3_level* a, const fq3_level* b) {
+    return a->H == b->H && a->k == b->k && a->m == b->m && a->abs_gate == b->abs_gate && a->target_power == b->target_power &&
+           a->ceiling == b->ceiling && a->max_gain == b->max_gain;
+}
+
+}  // namespace
+
 extern "C" int fq3_level_push(fq3_level* l, const float* pcm, int64_t n_in, int final, float* out, void* stream) {
     if (!l) return fq3_fail_(FQ3_EINVAL, "fq3_level_push: null object");
-    if (n_in < 0 || n_in > kMaxPush || (n_in > 0 && (!pcm || !out))) return fq3_fail_(FQ3_EINVAL, "fq3_level_push: bad input");
-    if (l->finished) return fq3_fail_(FQ3_ESTATE, "fq3_level_push: the stream has ended; fq3_level_reset starts the next one");
-    const int64_t total = l->total + n_in, h1 = total / l->H;
-    if (h1 > l->capacity)
-        return fq3_fail_(FQ3_ETOOLONG, "fq3_level_push: " + std::to_string(h1) + " hops exceed the capacity of " + std::to_string(l->capacity));
-    if (n_in == 0) {                                                // nothing completes and nothing is emitted
-        if (final) l->finished = true;
-        return 0;
-    }
-    // 1: the hops this push completes (its own arguments were checked above: it can only fail in the launch)
-    if (int rc = fq3_loud_push(l->meter, pcm, n_in, final, stream)) return rc;
-    // 2: T of the hops it enters, T[t_done .. h1]: hop h1 is the last one a sample of this push lies in (or the one behind it)
-    if ((int)h1 >= l->t_done) {
+    if (int rc = check_push_("fq3_level_push", l, pcm, n_in, out)) return rc;
+    if (n_in > 0) {                                                 // (an empty push completes and emits nothing)
+        // 1: the hops this push completes (its own arguments were checked above: it can only fail in the launch)
+        if (int rc = fq3_loud_push(l->meter, pcm, n_in, final, stream)) return rc;
         LevelTargetArgs k{};
-        k.energy = l->energy; k.peak = l->peak; k.bad = l->bad; k.T = l->T; k.slot = l->slot;
-        k.h_first = l->t_done; k.h_last = (int)h1; k.min_blocks = l->m; k.g0 = l->g0;
-        k.abs_gate = l->abs_gate; k.four_h = (double)(4 * l->H); k.target_power = l->target_power; k.ceiling = l->ceiling; k.max_gain = l->max_gain;
-        hipLaunchKernelGGL(level_target_kernel, dim3((unsigned)(k.h_last - k.h_first + 1)), dim3(kLevelTargetThreads), 0, (hipStream_t)stream, k);
+        LevelApplyArgs a{};
+        // 2: T of the hops it enters
+        if (plan_push_(l, pcm, n_in, out, &k, &a)) {
+            hipLaunchKernelGGL(level_target_kernel, dim3((unsigned)(k.h_last - k.h_first + 1)), dim3(kLevelTargetThreads), 0, (hipStream_t)stream, k);
+            VHIP(hipGetLastError());
+        }
+        // 3: the ramped gain
+        const int64_t tiles = (n_in + kLevelTile - 1) / kLevelTile;
+        hipLaunchKernelGGL(level_apply_kernel, dim3((unsigned)tiles), dim3(kLevelApplyThreads), 0, (hipStream_t)stream, a);
         VHIP(hipGetLastError());
-        l->t_done = (int)h1 + 1;
     }
-    // 3: the ramped gain
-    LevelApplyArgs a{};
-    a.pcm = pcm; a.out = out; a.T = l->T; a.n0 = l->total; a.n_in = n_in; a.H = l->H; a.k = l->k; a.g0 = l->g0;
-    const int64_t tiles = (n_in + kLevelTile - 1) / kLevelTile;
-    hipLaunchKernelGGL(level_apply_kernel, dim3((unsigned)tiles), dim3(kLevelApplyThreads), 0, (hipStream_t)stream, a);
-    VHIP(hipGetLastError());
-    l->total = total;
-    if (final) l->finished = true;
+    commit_push_(l, n_in, final);
+    return 0;
+}
+
+extern "C" int fq3_leveller_push_group(fq3_level* const* objs, int B, const float* const* pcm, const int64_t* n_in, const int* final,
+                                    float* const* out, void* stream) {
+    if (B < 0 || B > FQ3_STAGE_GROUP_MAX)
+        return fq3_fail_(FQ3_EINVAL, "fq3_leveller_push_group: B = " + std::to_string(B) + "; a group has 0 to " + std::to_string(FQ3_STAGE_GROUP_MAX) + " rows");
+    if (B == 0) return 0;
+    if (!objs || !pcm || !n_in || !final || !out) return fq3_fail_(FQ3_EINVAL, "fq3_leveller_push_group: null array");
+    for (int b = 0; b < B; ++b) {
+        if (!objs[b]) return fq3_fail_(FQ3_EINVAL, "fq3_leveller_push_group: row " + std::to_string(b) + ": null object");
+        for (int c = 0; c < b; ++c)
+            if (objs[c] == objs[b]) return fq3_fail_(FQ3_EINVAL, "fq3_leveller_push_group: rows " + std::to_string(c) + " and " + std::to_string(b) + " are the same object");
+        if (!same_design_(objs[b], objs[0]))
+            return fq3_fail_(FQ3_EINVAL, "fq3_leveller_push_group: row " + std::to_string(b) + " has another design (rate, target, ceiling, largest gain, smoothing, gate) than row 0");
+    }
+    static_assert(FQ3_STAGE_GROUP_MAX == kLevelGroupMax, "the header's limit is the descriptor table's size");
+    // every row is checked before any object moves; the meters of the rows with samples are checked once more by their group push
+    for (int b = 0; b < B; ++b)
+        if (int rc = check_push_("fq3_leveller_push_group: row " + std::to_string(b), objs[b], pcm[b], n_in[b], out[b])) return rc;
+    fq3_loud* meters[FQ3_STAGE_GROUP_MAX];
+    const float* m_pcm[FQ3_STAGE_GROUP_MAX];
+    int64_t m_n[FQ3_STAGE_GROUP_MAX];
+    int m_final[FQ3_STAGE_GROUP_MAX];
+    int n_m = 0;
+    for (int b = 0; b < B; ++b) {
+        if (n_in[b] == 0) continue;                                 // (an empty push never reaches the meter, final or not)
+        meters[n_m] = objs[b]->meter; m_pcm[n_m] = pcm[b]; m_n[n_m] = n_in[b]; m_final[n_m] = final[b];
+        ++n_m;
+    }
+    // 1: the hops the rows complete
+    if (int rc = fq3_loud_push_group_(meters, n_m, m_pcm, m_n, m_final, stream)) return rc;
+    if (n_m > 0) {
+        LevelTargetGroupArgs tg{};
+        LevelApplyGroupArgs ag{};
+        const fq3_level* l0 = objs[0];
+        tg.min_blocks = l0->m; tg.abs_gate = l0->abs_gate; tg.four_h = (double)(4 * l0->H);
+        tg.target_power = l0->target_power; tg.ceiling = l0->ceiling; tg.max_gain = l0->max_gain;
+        ag.H = l0->H; ag.k = l0->k;
+        int hops_max = 0;
+        int64_t tiles_max = 0;
+        for (int b = 0; b < B; ++b) {
+            LevelTargetRow& tr = tg.rows[b];
+            LevelApplyRow& ar = ag.rows[b];
+            tr.h_first = 0; tr.h_last = -1;                         // (a row that enters no hop; an empty row has n_in = 0 in ar)
+            if (n_in[b] == 0) continue;
+            LevelTargetArgs k{};
+            LevelApplyArgs a{};
+            if (plan_push_(objs[b], pcm[b], n_in[b], out[b], &k, &a)) {
+                tr.energy = k.energy; tr.peak = k.peak; tr.bad = k.bad; tr.T = k.T; tr.slot = k.slot;
+                tr.h_first = k.h_first; tr.h_last = k.h_last; tr.g0 = k.g0;
+                const int hops = k.h_last - k.h_first + 1;
+                hops_max = hops > hops_max ? hops : hops_max;
+            }
+            ar.pcm = a.pcm; ar.out = a.out; ar.T = a.T; ar.n0 = a.n0; ar.n_in = a.n_in; ar.g0 = a.g0;
+            const int64_t tiles = (a.n_in + kLevelTile - 1) / kLevelTile;
+            tiles_max = tiles > tiles_max ? tiles : tiles_max;
+        }
+        // 2: T of the hops they enter
+        if (hops_max > 0) {
+            hipLaunchKernelGGL(level_target_group_kernel, dim3((unsigned)hops_max, (unsigned)B), dim3(kLevelTargetThreads), 0, (hipStream_t)stream, tg);
+            VHIP(hipGetLastError());
+        }
+        // 3: the ramped gains
+        hipLaunchKernelGGL(level_apply_group_kernel, dim3((unsigned)tiles_max, (unsigned)B), dim3(kLevelApplyThreads), 0, (hipStream_t)stream, ag);
+        VHIP(hipGetLastError());
+    }
+    for (int b = 0; b < B; ++b) commit_push_(objs[b], n_in[b], final[b]);
     return 0;
 }
 

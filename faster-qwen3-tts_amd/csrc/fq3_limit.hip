@@ -2,6 +2,7 @@
 // latency of A + 6 samples -- behind the gain and in front of the time-scale and output stages (fq3_tsm.hip, fq3_audio.hip).
 //   fq3_limit_design / _count   host only (no HIP call): attack, hold, ceiling, the detector's three rows, the default tile
 //   fq3_limit_create / _push    ONE launch per push: a workgroup per tile of output samples plus one that keeps the history
+//   fq3_limit_push_group        the pushes of up to 32 objects of one design in ONE launch, each row bit for bit its single push
 //   fq3_limit_stats             the accumulators (true-peak estimate, smallest gain, limited and non-finite counts) into a device struct
 // The host tracks what follows from the lengths alone: samples pushed, samples emitted, which history buffer is current, whether the
 // stream has ended.  What depends on the data stays on the device.
@@ -78,6 +79,7 @@ size_t lds_bytes_(const Plan& p) {
 
 struct fq3_limit {
     Plan p{};
+    int rate = 0;
     int n_keep = 0;                           // 2 A + H + 11
     float* hist[2] = {nullptr, nullptr};      // n_keep floats each
     LimitAcc* acc = nullptr;
@@ -113,6 +115,7 @@ extern "C" int fq3_limit_create(const fq3_limit_config* cfg, fq3_limit** out) {
     if (int rc = plan_(cfg->in_rate, cfg->ceiling_db, cfg->lookahead_ms, cfg->hold_ms, cfg->tile, &p)) return rc;
     fq3_limit* l = new fq3_limit();
     l->p = p;
+    l->rate = cfg->in_rate;
     l->n_keep = 2 * p.A + p.H + kLimitBefore + kLimitAfter;
     hipError_t e = hipMalloc((void**)&l->hist[0], (size_t)(2 * l->n_keep) * sizeof(float));
     if (e == hipSuccess) e = hipMalloc((void**)&l->acc, sizeof(LimitAcc));
@@ -145,36 +148,118 @@ extern "C" int fq3_limit_reset(fq3_limit* l, void* stream) {
     return 0;
 }
 
-extern "C" int fq3_limit_push(fq3_limit* l, const float* pcm, int64_t n_in, int final, float* out, int64_t capacity_samples,
-                              int64_t* n_out, void* stream) {
-    if (!l || !n_out) return fq3_fail_(FQ3_EINVAL, "fq3_limit_push: null argument");
-    if (n_in < 0 || n_in > kMaxPush || (n_in > 0 && !pcm)) return fq3_fail_(FQ3_EINVAL, "fq3_limit_push: bad input");
-    if (l->finished) return fq3_fail_(FQ3_ESTATE, "fq3_limit_push: the stream has ended; fq3_limit_reset starts the next one");
+namespace {
+
+// One push, in the steps the single and the group entry share (as in fq3_audio.hip): check_push_ refuses or counts and leaves the
+// object alone, plan_push_ reads the object's state into the kernel's arguments, commit_push_ moves the object.
+int check_push_(const std::string& who, const fq3_limit* l, const float* pcm, int64_t n_in, int final, const float* out,
+                int64_t capacity_samples, int64_t* cnt_out) {
+    if (n_in < 0 || n_in > kMaxPush || (n_in > 0 && !pcm)) return fq3_fail_(FQ3_EINVAL, who + ": bad input");
+    if (l->finished) return fq3_fail_(FQ3_ESTATE, who + ": the stream has ended; fq3_limit_reset starts the next one");
     const int64_t total = l->total + n_in;
     const int64_t reach = total - l->p.A - kLimitAfter;
     const int64_t upto = final ? total : (reach > 0 ? reach : 0);
     const int64_t n = upto - l->emitted;
     if (n > capacity_samples || (n > 0 && !out))
-        return fq3_fail_(FQ3_EINVAL, "fq3_limit_push: " + std::to_string(n) + " output samples exceed the capacity of " + std::to_string(capacity_samples));
-    *n_out = n;
-    if (n_in == 0 && !final) return 0;                              // nothing completes and nothing changes
-    LimitPushArgs k{};
+        return fq3_fail_(FQ3_EINVAL, who + ": " + std::to_string(n) + " output samples exceed the capacity of " + std::to_string(capacity_samples));
+    *cnt_out = n;
+    return 0;
+}
+
+// a push with nothing to complete and nothing to end is not launched and changes nothing
+bool has_work_(int64_t n_in, int final) { return n_in > 0 || final; }
+
+void plan_push_(const fq3_limit* l, const float* pcm, int64_t n_in, int final, float* out, int64_t cnt, LimitPushArgs* kp) {
+    const int64_t total = l->total + n_in;
+    LimitPushArgs& k = *kp;
     k.n_hist = l->total < l->n_keep ? l->total : l->n_keep;
     k.pcm = pcm; k.hist = l->hist[l->cur]; k.hist_next = l->hist[l->cur ^ 1]; k.out = out; k.acc = l->acc;
-    k.n_in = n_in; k.v0 = l->total - k.n_hist; k.total = total; k.o0 = l->emitted; k.n_out = n;
+    k.n_in = n_in; k.v0 = l->total - k.n_hist; k.total = total; k.o0 = l->emitted; k.n_out = cnt;
     k.A = l->p.A; k.H = l->p.H; k.tile = l->p.tile;
     k.keep = final ? 0 : (int)(total < l->n_keep ? total : l->n_keep);
     k.c = l->p.c;
     for (int i = 0; i < 3 * kLimitTaps; ++i) k.h[i] = l->p.rows[i];
+}
+
+void commit_push_(fq3_limit* l, int64_t n_in, int64_t cnt, int final) {
+    if (!has_work_(n_in, final)) return;
+    l->cur ^= 1;
+    l->total += n_in;
+    l->emitted += cnt;
+    if (final) l->finished = true;
+}
+
+// in_rate, ceiling_db, lookahead_ms, hold_ms and tile, as the device sees them (the taps depend on nothing: plan_ builds the same 36)
+bool same_design_(const fq3_limit* a, const fq3_limit* b) {
+    return a->rate == b->rate && a->p.A == b->p.A && a->p.H == b->p.H && a->p.tile == b->p.tile && a->p.c == b->p.c;
+}
+
+}  // namespace
+
+extern "C" int fq3_limit_push(fq3_limit* l, const float* pcm, int64_t n_in, int final, float* out, int64_t capacity_samples,
+                              int64_t* n_out, void* stream) {
+    if (!l || !n_out) return fq3_fail_(FQ3_EINVAL, "fq3_limit_push: null argument");
+    int64_t n = 0;
+    if (int rc = check_push_("fq3_limit_push", l, pcm, n_in, final, out, capacity_samples, &n)) return rc;
+    *n_out = n;
+    if (!has_work_(n_in, final)) return 0;                          // nothing completes and nothing changes
+    LimitPushArgs k{};
+    plan_push_(l, pcm, n_in, final, out, n, &k);
     const size_t shm = lds_bytes_(l->p);
     if (!lds_limit_at_least<limit_push_kernel>(shm)) return fq3_fail_(FQ3_EHIP, "fq3_limit_push: could not raise the kernel's LDS limit");
     const int64_t n_tiles = (n + k.tile - 1) / k.tile;
     hipLaunchKernelGGL(limit_push_kernel, dim3((unsigned)(n_tiles + 1)), dim3(kLimitThreads), shm, (hipStream_t)stream, k);
     MHIP(hipGetLastError());
-    l->cur ^= 1;
-    l->total = total;
-    l->emitted = upto;
-    if (final) l->finished = true;
+    commit_push_(l, n_in, n, final);
+    return 0;
+}
+
+extern "C" int fq3_limit_push_group(fq3_limit* const* objs, int B, const float* const* pcm, const int64_t* n_in, const int* final,
+                                    float* const* out, const int64_t* capacity_samples, int64_t* n_out, void* stream) {
+    if (B < 0 || B > FQ3_STAGE_GROUP_MAX)
+        return fq3_fail_(FQ3_EINVAL, "fq3_limit_push_group: B = " + std::to_string(B) + "; a group has 0 to " + std::to_string(FQ3_STAGE_GROUP_MAX) + " rows");
+    if (B == 0) return 0;
+    if (!objs || !pcm || !n_in || !final || !out || !capacity_samples || !n_out) return fq3_fail_(FQ3_EINVAL, "fq3_limit_push_group: null array");
+    for (int b = 0; b < B; ++b) {
+        if (!objs[b]) return fq3_fail_(FQ3_EINVAL, "fq3_limit_push_group: row " + std::to_string(b) + ": null object");
+        for (int c = 0; c < b; ++c)
+            if (objs[c] == objs[b]) return fq3_fail_(FQ3_EINVAL, "fq3_limit_push_group: rows " + std::to_string(c) + " and " + std::to_string(b) + " are the same object");
+        if (!same_design_(objs[b], objs[0]))
+            return fq3_fail_(FQ3_EINVAL, "fq3_limit_push_group: row " + std::to_string(b) + " has another design (rate, ceiling, look-ahead, hold, tile) than row 0");
+    }
+    // every row is checked and planned before any object moves
+    static_assert(FQ3_STAGE_GROUP_MAX == kLimitGroupMax, "the header's limit is the descriptor table's size");
+    LimitGroupArgs g{};
+    const Plan& p0 = objs[0]->p;
+    g.A = p0.A; g.H = p0.H; g.tile = p0.tile; g.c = p0.c;
+    for (int i = 0; i < 3 * kLimitTaps; ++i) g.h[i] = p0.rows[i];
+    int64_t cnt[FQ3_STAGE_GROUP_MAX], tiles_max = 0;
+    bool any = false;
+    for (int b = 0; b < B; ++b) {
+        if (int rc = check_push_("fq3_limit_push_group: row " + std::to_string(b), objs[b], pcm[b], n_in[b], final[b], out[b], capacity_samples[b], &cnt[b]))
+            return rc;
+        LimitRow& r = g.rows[b];
+        r.active = has_work_(n_in[b], final[b]) ? 1 : 0;
+        if (!r.active) continue;
+        LimitPushArgs k{};
+        plan_push_(objs[b], pcm[b], n_in[b], final[b], out[b], cnt[b], &k);
+        r.pcm = k.pcm; r.hist = k.hist; r.hist_next = k.hist_next; r.out = k.out; r.acc = k.acc;
+        r.n_hist = k.n_hist; r.n_in = k.n_in; r.v0 = k.v0; r.total = k.total; r.o0 = k.o0; r.n_out = k.n_out;
+        r.keep = k.keep;
+        const int64_t n_tiles = (cnt[b] + g.tile - 1) / g.tile;
+        tiles_max = n_tiles > tiles_max ? n_tiles : tiles_max;
+        any = true;
+    }
+    if (any) {
+        const size_t shm = lds_bytes_(p0);
+        if (!lds_limit_at_least<limit_push_group_kernel>(shm)) return fq3_fail_(FQ3_EHIP, "fq3_limit_push_group: could not raise the kernel's LDS limit");
+        hipLaunchKernelGGL(limit_push_group_kernel, dim3((unsigned)(tiles_max + 1), (unsigned)B), dim3(kLimitThreads), shm, (hipStream_t)stream, g);
+        MHIP(hipGetLastError());
+    }
+    for (int b = 0; b < B; ++b) {
+        n_out[b] = cnt[b];
+        commit_push_(objs[b], n_in[b], cnt[b], final[b]);
+    }
     return 0;
 }
 

@@ -3,6 +3,7 @@
 // stages (fq3_tsm.hip, fq3_audio.hip), where the PCM already is.
 //   fq3_loud_design           host only (no HIP call): hop, K-weighting coefficients, the absolute gate as an integer, the gain constants
 //   fq3_loud_create / _push   hop energies, peaks and non-finite counts of the hops a push completes; ONE launch per push
+//   fq3_loud_push_group_      (internal, for fq3_leveller_push_group) the pushes of up to 32 meters of one rate in ONE launch
 //   fq3_loud_finish           gating and gain, one launch of one workgroup, into a device fq3_loud_stats
 //   fq3_loud_apply            out = pcm * *gain_dev
 // The host tracks what follows from the lengths alone: samples pushed, hops completed, which history buffer is current, whether the
@@ -148,16 +149,26 @@ extern "C" int fq3_loud_reset(fq3_loud* l, void* stream) {
     return 0;
 }
 
-extern "C" int fq3_loud_push(fq3_loud* l, const float* pcm, int64_t n_in, int final, void* stream) {
-    if (!l) return fq3_fail_(FQ3_EINVAL, "fq3_loud_push: null object");
-    if (n_in < 0 || n_in > kMaxPush || (n_in > 0 && !pcm)) return fq3_fail_(FQ3_EINVAL, "fq3_loud_push: bad input");
-    if (l->finished) return fq3_fail_(FQ3_ESTATE, "fq3_loud_push: the stream has ended; fq3_loud_reset starts the next one");
+namespace {
+
+// One push, in the steps the single and the group entry share (as in fq3_audio.hip): check_push_ refuses and leaves the object alone,
+// plan_push_ reads the object's state into the kernel's arguments, commit_push_ moves the object.
+int check_push_(const std::string& who, const fq3_loud* l, const float* pcm, int64_t n_in) {
+    if (n_in < 0 || n_in > kMaxPush || (n_in > 0 && !pcm)) return fq3_fail_(FQ3_EINVAL, who + ": bad input");
+    if (l->finished) return fq3_fail_(FQ3_ESTATE, who + ": the stream has ended; fq3_loud_reset starts the next one");
+    const int64_t h1 = (l->total + n_in) / l->p.H;
+    if (h1 > l->capacity)
+        return fq3_fail_(FQ3_ETOOLONG, who + ": " + std::to_string(h1) + " hops exceed the capacity of " + std::to_string(l->capacity));
+    return 0;
+}
+
+// a push with nothing to complete and nothing to end is not launched and changes nothing
+bool has_work_(int64_t n_in, int final) { return n_in > 0 || final; }
+
+void plan_push_(const fq3_loud* l, const float* pcm, int64_t n_in, int final, LoudPushArgs* kp) {
     const int H = l->p.H;
     const int64_t h0 = l->total / H, total = l->total + n_in, h1 = total / H;
-    if (h1 > l->capacity)
-        return fq3_fail_(FQ3_ETOOLONG, "fq3_loud_push: " + std::to_string(h1) + " hops exceed the capacity of " + std::to_string(l->capacity));
-    if (n_in == 0 && !final) return 0;                              // nothing completes and nothing changes
-    LoudPushArgs k{};
+    LoudPushArgs& k = *kp;
     k.v0 = h0 > 0 ? (h0 - 1) * H : 0;
     k.pcm = pcm; k.hist = l->hist[l->cur]; k.hist_next = l->hist[l->cur ^ 1];
     k.energy = l->energy; k.peak = l->peak; k.bad = l->bad;
@@ -165,12 +176,62 @@ extern "C" int fq3_loud_push(fq3_loud* l, const float* pcm, int64_t n_in, int fi
     k.h0 = h0; k.n_new = (int)(h1 - h0); k.H = H; k.final = final ? 1 : 0;
     k.keep = final ? 0 : (int)(total - (h1 > 0 ? (h1 - 1) * H : 0));
     k.shelf = coef_(l->p.c32); k.hp = coef_(l->p.c32 + 5);
+}
+
+void commit_push_(fq3_loud* l, int64_t n_in, int final) {
+    if (!has_work_(n_in, final)) return;
+    l->cur ^= 1;
+    l->total += n_in;
+    if (final) l->finished = true;
+}
+
+}  // namespace
+
+extern "C" int fq3_loud_push(fq3_loud* l, const float* pcm, int64_t n_in, int final, void* stream) {
+    if (!l) return fq3_fail_(FQ3_EINVAL, "fq3_loud_push: null object");
+    if (int rc = check_push_("fq3_loud_push", l, pcm, n_in)) return rc;
+    if (!has_work_(n_in, final)) return 0;                          // nothing completes and nothing changes
+    LoudPushArgs k{};
+    plan_push_(l, pcm, n_in, final, &k);
     const int n_wg = (k.n_new + kLoudLanes - 1) / kLoudLanes;
     hipLaunchKernelGGL(loud_push_kernel, dim3(n_wg + 1), dim3(kLoudLanes), 0, (hipStream_t)stream, k);
     LHIP(hipGetLastError());
-    l->cur ^= 1;
-    l->total = total;
-    if (final) l->finished = true;
+    commit_push_(l, n_in, final);
+    return 0;
+}
+
+// fq3_level.hip (fq3_leveller_push_group): the pushes of up to FQ3_STAGE_GROUP_MAX meters of one rate in ONE launch, each row bit for bit
+// its fq3_loud_push.  Every row is checked before any meter moves; on a refusal the first failing row's code comes back, nothing is
+// launched and no meter has changed.  The caller has checked B and the arrays and hands over distinct meters; another rate is FQ3_EINVAL.
+int fq3_loud_push_group_(fq3_loud* const* objs, int B, const float* const* pcm, const int64_t* n_in, const int* final, void* stream) {
+    static_assert(FQ3_STAGE_GROUP_MAX == kLoudGroupMax, "the header's limit is the descriptor table's size");
+    if (B < 0 || B > FQ3_STAGE_GROUP_MAX) return fq3_fail_(FQ3_EINVAL, "fq3_loud_push_group_: a group has 0 to " + std::to_string(FQ3_STAGE_GROUP_MAX) + " rows");
+    if (B == 0) return 0;
+    LoudGroupArgs g{};
+    g.H = objs[0]->p.H; g.shelf = coef_(objs[0]->p.c32); g.hp = coef_(objs[0]->p.c32 + 5);
+    int wg_max = 0;
+    bool any = false;
+    for (int b = 0; b < B; ++b) {
+        const fq3_loud* l = objs[b];
+        if (l->p.H != g.H) return fq3_fail_(FQ3_EINVAL, "fq3_loud_push_group_: row " + std::to_string(b) + " has another rate than row 0");
+        if (int rc = check_push_("fq3_loud_push_group_: row " + std::to_string(b), l, pcm[b], n_in[b])) return rc;
+        LoudRow& r = g.rows[b];
+        r.active = has_work_(n_in[b], final[b]) ? 1 : 0;
+        if (!r.active) continue;
+        LoudPushArgs k{};
+        plan_push_(l, pcm[b], n_in[b], final[b], &k);
+        r.pcm = k.pcm; r.hist = k.hist; r.hist_next = k.hist_next; r.energy = k.energy; r.peak = k.peak; r.bad = k.bad;
+        r.n_hist = k.n_hist; r.n_in = k.n_in; r.v0 = k.v0; r.h0 = k.h0;
+        r.n_new = k.n_new; r.final = k.final; r.keep = k.keep;
+        const int n_wg = (k.n_new + kLoudLanes - 1) / kLoudLanes;
+        wg_max = n_wg > wg_max ? n_wg : wg_max;
+        any = true;
+    }
+    if (any) {
+        hipLaunchKernelGGL(loud_push_group_kernel, dim3((unsigned)(wg_max + 1), (unsigned)B), dim3(kLoudLanes), 0, (hipStream_t)stream, g);
+        LHIP(hipGetLastError());
+    }
+    for (int b = 0; b < B; ++b) commit_push_(objs[b], n_in[b], final[b]);
     return 0;
 }
 

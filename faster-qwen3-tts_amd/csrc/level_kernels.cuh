@@ -16,7 +16,8 @@
 //         16 bytes, element-wise otherwise.  A sample's gain depends on its absolute position alone.
 // stats   one thread: the slot plus S of the newest hop into the caller's device memory.
 // No atomics, no private arrays in memory; everything is written by ordinary vector stores.  The __device__ bodies take their row's
-// arguments and LDS, the __global__ shells only hand them over: a launch over a group of rows can call the same bodies.
+// arguments and LDS, the __global__ shells only hand them over: level_target_group_kernel and level_apply_group_kernel (the launches of
+// fq3_leveller_push_group, at the end of this file) call the same bodies for the row blockIdx.y picks.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -156,6 +157,67 @@ __device__ __forceinline__ void level_apply_body(const LevelApplyArgs& a, int64_
 
 __global__ void __launch_bounds__(kLevelApplyThreads) level_apply_kernel(const LevelApplyArgs a) {
     __shared__ LevelApplyLds s;
+    level_apply_body(a, (int64_t)blockIdx.x, s);
+}
+
+// ---- a group of pushes in one launch each (fq3_leveller_push_group) ----
+// target: grid (most newly entered hops over the rows, B); apply: grid (most tiles, B).  blockIdx.y picks the row.  The rows share the
+// design but for the initial gain (H, k, min_blocks, the gate and gain constants); the pointers, the stream positions, the counts and
+// g0 travel per row, BY VALUE in the kernel's argument block as in audio_kernels.cuh and tsm_kernels.cuh.  A workgroup behind its row's
+// last hop or tile leaves before any barrier; a row that enters no hop (h_last < h_first) or has no samples costs workgroups that leave.
+constexpr int kLevelGroupMax = 32;                         // FQ3_STAGE_GROUP_MAX
+
+struct LevelTargetRow {
+    const uint64_t* energy;
+    const float* peak;
+    const int* bad;
+    float* T;
+    fq3_level_report* slot;
+    int h_first, h_last;
+    float g0;
+    int reserved;
+};
+
+struct LevelTargetGroupArgs {
+    int min_blocks;
+    uint64_t abs_gate;
+    double four_h, target_power, ceiling, max_gain;
+    LevelTargetRow rows[kLevelGroupMax];
+};
+
+struct LevelApplyRow {
+    const float* pcm;
+    float* out;
+    const float* T;
+    int64_t n0, n_in;
+    float g0;
+    int reserved;
+};
+
+struct LevelApplyGroupArgs {
+    int H, k;
+    LevelApplyRow rows[kLevelGroupMax];
+};
+static_assert(sizeof(LevelTargetRow) == 56 && sizeof(LevelTargetGroupArgs) <= 4096 && sizeof(LevelApplyRow) == 48 &&
+              sizeof(LevelApplyGroupArgs) <= 4096, "the descriptors must fit the 4 KB of arguments a launch may carry");
+
+__global__ void __launch_bounds__(kLevelTargetThreads) level_target_group_kernel(const LevelTargetGroupArgs g) {
+    __shared__ LoudGateLds s;
+    const LevelTargetRow& r = g.rows[blockIdx.y];
+    if ((int)blockIdx.x > r.h_last - r.h_first) return;
+    LevelTargetArgs a;
+    a.energy = r.energy; a.peak = r.peak; a.bad = r.bad; a.T = r.T; a.slot = r.slot;
+    a.h_first = r.h_first; a.h_last = r.h_last; a.min_blocks = g.min_blocks; a.g0 = r.g0;
+    a.abs_gate = g.abs_gate; a.four_h = g.four_h; a.target_power = g.target_power; a.ceiling = g.ceiling; a.max_gain = g.max_gain;
+    level_target_body(a, a.h_first + (int)blockIdx.x, s);
+}
+
+__global__ void __launch_bounds__(kLevelApplyThreads) level_apply_group_kernel(const LevelApplyGroupArgs g) {
+    __shared__ LevelApplyLds s;
+    const LevelApplyRow& r = g.rows[blockIdx.y];
+    if ((int64_t)blockIdx.x * kLevelTile >= r.n_in) return;
+    LevelApplyArgs a;
+    a.pcm = r.pcm; a.out = r.out; a.T = r.T; a.n0 = r.n0; a.n_in = r.n_in; a.H = g.H; a.k = g.k; a.g0 = r.g0;
     level_apply_body(a, (int64_t)blockIdx.x, s);
 }
 

@@ -17,7 +17,9 @@
 //         other history buffer.  Peak, largest gain drop, limited and non-finite counts are reduced per wave and added to the
 //         object's accumulators by integer atomics (max, max, add, add): order-free.
 // stats   one thread turns the accumulators into an fq3_limit_report.
-// No private arrays in memory, no inline assembly; results are written by ordinary vector stores.
+// No private arrays in memory, no inline assembly; results are written by ordinary vector stores.  The push is ONE __device__ body
+// (limit_push_body) behind two __global__ shells: limit_push_kernel for one stream and limit_push_group_kernel for a group of streams
+// of one design (fq3_limit_push_group), whose blockIdx.y picks the row.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -60,13 +62,16 @@ __device__ __forceinline__ float limit_clean(float x, bool& bad) {
     return bad ? 0.0f : x;
 }
 
-__global__ void __launch_bounds__(kLimitThreads) limit_push_kernel(const LimitPushArgs a) {
-    extern __shared__ __align__(16) unsigned char limit_lds[];
-    __shared__ uint32_t wave_sum[2][kLimitThreads / 64];
+struct LimitWaveSums { uint32_t v[2][kLimitThreads / 64]; };
+
+// workgroup `tile_index` of a push, tile_index <= ceil(n_out / tile) (the last one keeps the history): the ONE body of the single and
+// the group launch.  `limit_lds`: the launch's dynamic LDS, 3 * round_up(tile + 2 A + H + 11, 4) words; all kLimitThreads threads call it.
+__device__ __forceinline__ void limit_push_body(const LimitPushArgs& a, int tile_index, unsigned char* limit_lds, LimitWaveSums& sums) {
+    uint32_t (&wave_sum)[2][kLimitThreads / 64] = sums.v;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int n_tiles = (int)((a.n_out + a.tile - 1) / a.tile);
     const int64_t m = a.n_hist + a.n_in;
-    if ((int)blockIdx.x == n_tiles) {
+    if (tile_index == n_tiles) {
         // the workgroup behind the tiles: the history of the next push
         for (int j = tid; j < a.keep; j += kLimitThreads) {
             const int64_t cidx = m - a.keep + j;
@@ -75,7 +80,7 @@ __global__ void __launch_bounds__(kLimitThreads) limit_push_kernel(const LimitPu
         return;
     }
     const int A = a.A, H = a.H, W = A + H + 1;
-    const int64_t t0 = a.o0 + (int64_t)blockIdx.x * a.tile;                       // the tile's first output, a stream index
+    const int64_t t0 = a.o0 + (int64_t)tile_index * a.tile;                      // the tile's first output, a stream index
     const int Tn = (int)(a.o0 + a.n_out - t0 < a.tile ? a.o0 + a.n_out - t0 : a.tile);
     const int Lx = Tn + 2 * A + H + kLimitBefore + kLimitAfter;                    // samples staged
     const int Lq = Tn + 2 * A + H;                                                 // requests
@@ -216,6 +221,51 @@ __global__ void __launch_bounds__(kLimitThreads) limit_push_kernel(const LimitPu
         if (nlim) atomicAdd(&a.acc->n_limited, (unsigned long long)nlim);
         if (nbad) atomicAdd(&a.acc->n_bad, (unsigned long long)nbad);
     }
+}
+
+__global__ void __launch_bounds__(kLimitThreads) limit_push_kernel(const LimitPushArgs a) {
+    extern __shared__ __align__(16) unsigned char limit_lds[];
+    __shared__ LimitWaveSums sums;
+    limit_push_body(a, (int)blockIdx.x, limit_lds, sums);
+}
+
+// ---- a group of pushes in one launch (fq3_limit_push_group) ----
+// Grid (most tiles + 1 over the rows, B): blockIdx.y picks the row, blockIdx.x its tile.  The rows share the design (A, H, tile, the
+// ceiling, the detector's 36 taps -- so one LDS layout); the pointers, the stream positions and the counts travel per row, BY VALUE in
+// the kernel's argument block as in audio_kernels.cuh and tsm_kernels.cuh.  A workgroup behind its row's history workgroup leaves
+// before any barrier; a row with nothing to do (active == 0: no input, not final) costs workgroups that leave.
+constexpr int kLimitGroupMax = 32;                  // FQ3_STAGE_GROUP_MAX
+
+struct LimitRow {
+    const float* pcm;
+    const float* hist;
+    float* hist_next;
+    float* out;
+    LimitAcc* acc;
+    int64_t n_hist, n_in, v0, total, o0, n_out;
+    int keep, active;
+};
+
+struct LimitGroupArgs {
+    int A, H, tile;
+    float c;
+    float h[3 * kLimitTaps];
+    LimitRow rows[kLimitGroupMax];
+};
+static_assert(sizeof(LimitRow) == 96 && sizeof(LimitGroupArgs) <= 4096, "the descriptors must fit the 4 KB of arguments a launch may carry");
+
+__global__ void __launch_bounds__(kLimitThreads) limit_push_group_kernel(const LimitGroupArgs g) {
+    extern __shared__ __align__(16) unsigned char limit_lds[];
+    __shared__ LimitWaveSums sums;
+    const LimitRow& r = g.rows[blockIdx.y];
+    if (!r.active || (int64_t)blockIdx.x > (r.n_out + g.tile - 1) / g.tile) return;
+    LimitPushArgs a;
+    a.pcm = r.pcm; a.hist = r.hist; a.hist_next = r.hist_next; a.out = r.out; a.acc = r.acc;
+    a.n_hist = r.n_hist; a.n_in = r.n_in; a.v0 = r.v0; a.total = r.total; a.o0 = r.o0; a.n_out = r.n_out;
+    a.A = g.A; a.H = g.H; a.tile = g.tile; a.keep = r.keep; a.c = g.c;
+#pragma unroll
+    for (int i = 0; i < 3 * kLimitTaps; ++i) a.h[i] = g.h[i];
+    limit_push_body(a, (int)blockIdx.x, limit_lds, sums);
 }
 
 __global__ void limit_stats_kernel(const LimitAcc* acc, fq3_limit_report* out) {

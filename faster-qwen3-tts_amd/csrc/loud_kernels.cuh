@@ -15,7 +15,9 @@
 // finish  ONE workgroup: blocks of four hops, the two gates as exact integer sums (32-bit halves in two uint64, reduced through the
 //         LDS), and on thread 0 the mean power and the gain in IEEE double (multiply, divide, sqrt, compare, convert -- nothing else).
 // apply   out[i] = pcm[i] * *gain: 16 bytes per lane where source and destination agree modulo 16 bytes, element-wise otherwise.
-// No atomics, no private arrays in memory; everything is written by ordinary vector stores.
+// No atomics, no private arrays in memory; everything is written by ordinary vector stores.  The push is ONE __device__ body
+// (loud_push_body) behind two __global__ shells: loud_push_kernel for one stream and loud_push_group_kernel for the meters of a group
+// of levellers (fq3_leveller_push_group), whose blockIdx.y picks the row -- the rows' serial walks then run side by side.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -108,18 +110,21 @@ __device__ __forceinline__ void loud_steps(const LoudPushArgs& a, const float* r
     if (kMeasure) z.e += ((uint64_t)hi << 23) + lo;
 }
 
-// FQ3_LOUD_NO_KERNELS (defined by a .hip file in front of its includes, never by a header): a second translation unit that wants the
-// __device__ helpers and constants above and below (fq3_level.hip) leaves the three __global__ definitions to fq3_loud.hip -- they
-// have external linkage and may exist once in the library.
-#ifndef FQ3_LOUD_NO_KERNELS
-__global__ void __launch_bounds__(kLoudLanes) loud_push_kernel(const LoudPushArgs a) {
-    __shared__ float tile[kLoudLanes * kLoudPitch];
-    __shared__ float r_pk[kLoudLanes];
-    __shared__ int r_nb[kLoudLanes];
+struct LoudPushLds {
+    float tile[kLoudLanes * kLoudPitch];
+    float r_pk[kLoudLanes];
+    int r_nb[kLoudLanes];
+};
+
+// workgroup `wg` of a push, wg <= (n_new + 63) / 64: the ONE body of the single and the group launch (all kLoudLanes threads call it)
+__device__ __forceinline__ void loud_push_body(const LoudPushArgs& a, int wg, LoudPushLds& s) {
+    float* const tile = s.tile;
+    float* const r_pk = s.r_pk;
+    int* const r_nb = s.r_nb;
     const int lane = threadIdx.x;
     const int64_t m = a.n_hist + a.n_in;
     const int n_wg = (a.n_new + kLoudLanes - 1) / kLoudLanes;
-    if ((int)blockIdx.x == n_wg) {
+    if (wg == n_wg) {
         // the workgroup behind the hops: the history of the next push, or the partial hop that ends the stream
         if (!a.final) {
             for (int j = lane; j < a.keep; j += kLoudLanes) a.hist_next[j] = loud_fetch(a, m - a.keep + j);
@@ -139,7 +144,7 @@ __global__ void __launch_bounds__(kLoudLanes) loud_push_kernel(const LoudPushArg
         return;
     }
     const int H = a.H;
-    const int row0 = (int)blockIdx.x * kLoudLanes;                 // first hop of this workgroup, counted from h0
+    const int row0 = wg * kLoudLanes;                 // first hop of this workgroup, counted from h0
     const int rows = a.n_new - row0 < kLoudLanes ? a.n_new - row0 : kLoudLanes;
     // row r starts at V index (h0 + row0 + r - 1) H - v0: below zero only for hop 0, whose warm-up lies in front of the stream
     const int64_t base = (a.h0 + row0 - 1) * H - a.v0;
@@ -206,6 +211,52 @@ __global__ void __launch_bounds__(kLoudLanes) loud_push_kernel(const LoudPushArg
         const int64_t h = a.h0 + row0 + lane;
         a.energy[h] = z.e; a.peak[h] = z.pk; a.bad[h] = z.nb;
     }
+}
+
+// ---- a group of pushes in one launch (fq3_loud_push_group_, for fq3_leveller_push_group) ----
+// Grid (largest n_wg + 1 over the rows, B): blockIdx.y picks the row, blockIdx.x its workgroup.  The rows share the rate (H and the
+// K-weighting coefficients); everything else travels per row, BY VALUE in the kernel's argument block as in audio_kernels.cuh and
+// tsm_kernels.cuh: blockIdx.y is uniform, so a row's fields are scalar loads from the argument segment.  A workgroup behind its row's
+// last one (the history workgroup) leaves before any barrier; a row with nothing to do (active == 0) costs workgroups that leave.
+constexpr int kLoudGroupMax = 32;                   // FQ3_STAGE_GROUP_MAX
+
+struct LoudRow {
+    const float* pcm;
+    const float* hist;
+    float* hist_next;
+    uint64_t* energy;
+    float* peak;
+    int* bad;
+    int64_t n_hist, n_in, v0, h0;
+    int n_new, final, keep, active;
+};
+
+struct LoudGroupArgs {
+    int H;
+    LoudCoef shelf, hp;
+    LoudRow rows[kLoudGroupMax];
+};
+static_assert(sizeof(LoudRow) == 96 && sizeof(LoudGroupArgs) <= 4096, "the descriptors must fit the 4 KB of arguments a launch may carry");
+
+// FQ3_LOUD_NO_KERNELS (defined by a .hip file in front of its includes, never by a header): a second translation unit that wants the
+// __device__ helpers and constants above and below (fq3_level.hip) leaves the __global__ definitions to fq3_loud.hip -- they
+// have external linkage and may exist once in the library.
+#ifndef FQ3_LOUD_NO_KERNELS
+__global__ void __launch_bounds__(kLoudLanes) loud_push_kernel(const LoudPushArgs a) {
+    __shared__ LoudPushLds s;
+    loud_push_body(a, (int)blockIdx.x, s);
+}
+
+__global__ void __launch_bounds__(kLoudLanes) loud_push_group_kernel(const LoudGroupArgs g) {
+    __shared__ LoudPushLds s;
+    const LoudRow& r = g.rows[blockIdx.y];
+    if (!r.active || (int)blockIdx.x > (r.n_new + kLoudLanes - 1) / kLoudLanes) return;
+    LoudPushArgs a;
+    a.pcm = r.pcm; a.hist = r.hist; a.hist_next = r.hist_next; a.energy = r.energy; a.peak = r.peak; a.bad = r.bad;
+    a.n_hist = r.n_hist; a.n_in = r.n_in; a.v0 = r.v0; a.h0 = r.h0;
+    a.n_new = r.n_new; a.H = g.H; a.final = r.final; a.keep = r.keep;
+    a.shelf = g.shelf; a.hp = g.hp;
+    loud_push_body(a, (int)blockIdx.x, s);
 }
 
 #endif  // FQ3_LOUD_NO_KERNELS

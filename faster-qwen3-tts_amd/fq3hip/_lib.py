@@ -17,7 +17,7 @@ LIB_PATH = os.path.join(os.path.dirname(_HERE), "lib", "libfq3hip.so")
 
 FQ3_BF16, FQ3_F32, FQ3_BF16X2 = 0, 1, 2
 FQ3_PCM_F32, FQ3_PCM_S16, FQ3_PCM_MULAW, FQ3_PCM_ALAW = 0, 1, 2, 3
-FQ3_STAGE_GROUP_MAX = 32          # rows of one fq3_audio_out_push_group / fq3_tsm_push_group
+FQ3_STAGE_GROUP_MAX = 32          # rows of one fq3_audio_out_push_group / fq3_tsm_push_group / fq3_leveller_push_group / fq3_limit_push_group
 FQ3_OK, FQ3_EINVAL, FQ3_EHIP, FQ3_ESTATE, FQ3_ETOOLONG, FQ3_EUNSUPPORTED, FQ3_ENOMEM = 0, -1, -2, -3, -4, -5, -6
 
 vp = C.c_void_p
@@ -255,6 +255,8 @@ SIGNATURES = {
     "fq3_limit_destroy": (C.c_int, [vp]),
     "fq3_limit_reset": (C.c_int, [vp, vp]),
     "fq3_limit_push": (C.c_int, [vp, vp, C.c_int64, C.c_int, vp, C.c_int64, C.POINTER(C.c_int64), vp]),
+    "fq3_limit_push_group": (C.c_int, [C.POINTER(vp), C.c_int, C.POINTER(vp), C.POINTER(C.c_int64), C.POINTER(C.c_int),
+                                       C.POINTER(vp), C.POINTER(C.c_int64), C.POINTER(C.c_int64), vp]),
     "fq3_limit_stats": (C.c_int, [vp, vp, vp]),
     "fq3_loud_design": (C.c_int, [C.c_int, C.c_double, C.c_double, C.c_double, C.POINTER(C.c_int), C.POINTER(C.c_double), C.POINTER(C.c_float),
                                   C.POINTER(C.c_uint64), C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double)]),
@@ -270,6 +272,8 @@ SIGNATURES = {
     "fq3_level_reset": (C.c_int, [vp, vp]),
     "fq3_level_set_initial_gain": (C.c_int, [vp, C.c_double]),
     "fq3_level_push": (C.c_int, [vp, vp, C.c_int64, C.c_int, vp, vp]),
+    # host arrays of B entries: objects, pcm pointers, lengths, final flags, output pointers; then the stream
+    "fq3_leveller_push_group": (C.c_int, [C.POINTER(vp), C.c_int, C.POINTER(vp), C.POINTER(C.c_int64), C.POINTER(C.c_int), C.POINTER(vp), vp]),
     "fq3_level_stats": (C.c_int, [vp, vp, vp]),
     "fq3_level_trace": (C.c_int, [vp, vp, vp, vp, vp, C.c_int64, C.POINTER(C.c_int64), vp]),
     "fq3_noise_fill": (C.c_int, [vp, C.POINTER(NoiseRing), C.c_int, C.c_int, vp]),

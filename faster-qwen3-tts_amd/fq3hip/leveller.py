@@ -211,3 +211,88 @@ class Leveller:
             n = int(got.value)
             return dict(energy=e[:n].cpu().numpy().view(np.uint64), peak=p[:n].cpu().numpy(), bad=b[:n].cpu().numpy(),
                         target=t[:n + 1].cpu().numpy())
+
+
+# ---- a group of streams in one launch set (the lock-step batch) -----------------------------------------
+GROUP_MAX = _lib.FQ3_STAGE_GROUP_MAX
+
+
+def _group_members(what: str, stages, pcms, finals):
+    """the checks every group function makes on the host: one pcm and flag per stage, no stage twice, one device and one stream"""
+    if not (len(stages) == len(pcms) == len(finals)):
+        raise ValueError(f"{what}: one pcm and one final flag per stage")
+    if len(set(map(id, stages))) != len(stages):
+        raise ValueError(f"{what}: the same stage twice in one call")
+    if not stages:
+        return None, None
+    dev, s = stages[0].dev, stages[0]._stream()
+    for st in stages:
+        if st.dev != dev or st._stream().cuda_stream != s.cuda_stream:
+            raise ValueError(f"{what}: the stages of one call share a device and a stream")
+    return dev, s
+
+
+def _float_rows(pcms, dev):
+    """every pcm as a contiguous float32 vector on ``dev`` (None: no samples) -> [(tensor | None, length)]"""
+    rows = []
+    for pcm in pcms:
+        x = None if pcm is None else pcm.reshape(-1)
+        if x is not None and (x.dtype != torch.float32 or x.device != dev or not x.is_contiguous()):
+            x = x.to(device=dev, dtype=torch.float32).contiguous()
+        rows.append((x, 0 if x is None else int(x.numel())))
+    return rows
+
+
+def push_group(levellers, pcms, finals, outs=None) -> list:
+    """``[levellers[i].push(pcms[i], finals[i], out=outs[i]) for i]`` -- the same device tensors, bit for bit, and the same counters
+    on every object -- with at most THREE launches per design (the meters', the targets', the multiplies') instead of three per row
+    (``fq3_leveller_push_group``, up to 32 rows a call).  The levellers share a device and a stream and appear once; rows are bucketed
+    by design (rate and ``spec.pooled``: the initial gain may differ per row).  ``outs`` (None, or per row a tensor or None): where
+    a row's samples go, ``pcms[i]`` itself included; rows without one lie in one new device buffer.  A row the library would refuse
+    is refused before any object moves, with its single push's own error."""
+    levellers, pcms, finals = list(levellers), list(pcms), [bool(f) for f in finals]
+    outs = [None] * len(levellers) if outs is None else list(outs)
+    if len(outs) != len(levellers):
+        raise ValueError("leveller.push_group: one out (or None) per leveller")
+    dev, s = _group_members("leveller.push_group", levellers, pcms, finals)
+    if dev is None:
+        return []
+    lib = levellers[0]._lib
+    with torch.cuda.device(dev), torch.cuda.stream(s):
+        rows = _float_rows(pcms, dev)
+        cursor, offs = 0, []
+        for lev, (x, n), final, out in zip(levellers, rows, finals, outs):
+            if out is not None and (out.dtype != torch.float32 or out.device != dev or not out.is_contiguous() or int(out.numel()) != n):
+                raise ValueError("out must be a contiguous float32 tensor of the input's length on the leveller's device")
+            if lev.finished or (lev.n_in + n) // lev.design.H > lev.capacity_hops:
+                lev.push(x, final, out=out)                        # the library's own answer (FQ3_ESTATE, FQ3_ETOOLONG), as ``push`` gives it
+            if out is None and n:
+                # a new row begins where its source does modulo 16 bytes: the multiply then moves 16 bytes per lane
+                cursor = (cursor + 3) // 4 * 4 + ((x.data_ptr() >> 2) & 3)
+                offs.append(cursor)
+                cursor += n
+            else:
+                offs.append(None)
+        buf = torch.empty(cursor, dtype=torch.float32, device=dev)
+        result = [out if out is not None else (buf[off:off + n] if n else buf[:0]) for out, off, (_x, n) in zip(outs, offs, rows)]
+        buckets: dict = {}
+        for i, lev in enumerate(levellers):
+            buckets.setdefault((lev.in_rate, lev.spec.pooled), []).append(i)
+        sp = C.c_void_p(s.cuda_stream)
+        for members in buckets.values():
+            for a in range(0, len(members), GROUP_MAX):
+                part = members[a:a + GROUP_MAX]
+                B = len(part)
+                _lib.check(lib.fq3_leveller_push_group(
+                    (C.c_void_p * B)(*[levellers[i]._h.value for i in part]), B,
+                    (C.c_void_p * B)(*[rows[i][0].data_ptr() if rows[i][1] else None for i in part]),
+                    (C.c_int64 * B)(*[rows[i][1] for i in part]), (C.c_int * B)(*[int(finals[i]) for i in part]),
+                    (C.c_void_p * B)(*[result[i].data_ptr() if rows[i][1] else None for i in part]), sp))
+                for i in part:
+                    levellers[i].n_in += rows[i][1]
+                    levellers[i].finished = levellers[i].finished or finals[i]
+        for (x, n), y in zip(rows, result):
+            if n:
+                x.record_stream(s)
+            y.record_stream(s)
+    return [y.reshape(-1) for y in result]

@@ -141,6 +141,7 @@ class Limiter:
         if rc == _lib.FQ3_EINVAL:
             raise ValueError(self._lib.fq3_last_error().decode("utf-8", "replace"))
         _lib.check(rc)
+        self.tile = int(tile) if tile else self.design.tile
         self.n_in, self.n_out, self.finished = 0, 0, False
 
     def __del__(self):
@@ -197,3 +198,63 @@ class Limiter:
             buf = torch.empty(STATS_BYTES, dtype=torch.uint8, device=self.dev)          # torch aligns allocations far beyond 8 bytes
             _lib.check(self._lib.fq3_limit_stats(self._h, C.c_void_p(buf.data_ptr()), C.c_void_p(s.cuda_stream)))
             return LimiterStats.from_bytes(buf.cpu().numpy().tobytes())
+
+
+# ---- a group of streams in one launch (the lock-step batch) ----------------------------------------------
+GROUP_MAX = _lib.FQ3_STAGE_GROUP_MAX
+
+
+def _push_group(limiters, pcms, finals):
+    """The launches of ``push_group``: -> (the float32 device buffer every row's output lies in, [(offset, count)] per row, the stream)."""
+    from .leveller import _float_rows, _group_members
+    limiters, pcms, finals = list(limiters), list(pcms), [bool(f) for f in finals]
+    dev, s = _group_members("limiter.push_group", limiters, pcms, finals)
+    if dev is None:
+        return None, [], None
+    lib = limiters[0]._lib
+    with torch.cuda.device(dev), torch.cuda.stream(s):
+        rows = _float_rows(pcms, dev)
+        cursor, spans = 0, []
+        for lim, (x, n), final in zip(limiters, rows, finals):
+            if lim.finished:
+                lim.push(x, final)                                 # the library's own answer (FQ3_ESTATE), as ``push`` gives it
+            total = lim.n_in + n
+            room = max((total if final else max(0, total - lim.design.latency)) - lim.n_out, 0)
+            spans.append((cursor, room))                           # back to back: a row starts at whatever float offset it falls on
+            cursor += room
+        buf = torch.empty(cursor, dtype=torch.float32, device=dev)
+        base, sp = buf.data_ptr(), C.c_void_p(s.cuda_stream)
+        buckets: dict = {}
+        for i, lim in enumerate(limiters):
+            buckets.setdefault((lim.in_rate, lim.spec, lim.tile), []).append(i)
+        for members in buckets.values():
+            for a in range(0, len(members), GROUP_MAX):
+                part = members[a:a + GROUP_MAX]
+                B = len(part)
+                n_out = (C.c_int64 * B)()
+                _lib.check(lib.fq3_limit_push_group(
+                    (C.c_void_p * B)(*[limiters[i]._h.value for i in part]), B,
+                    (C.c_void_p * B)(*[rows[i][0].data_ptr() if rows[i][1] else None for i in part]),
+                    (C.c_int64 * B)(*[rows[i][1] for i in part]), (C.c_int * B)(*[int(finals[i]) for i in part]),
+                    (C.c_void_p * B)(*[base + 4 * spans[i][0] if spans[i][1] else None for i in part]),
+                    (C.c_int64 * B)(*[spans[i][1] for i in part]), n_out, sp))
+                for i, got in zip(part, n_out):
+                    assert int(got) == spans[i][1]
+                    limiters[i].n_in += rows[i][1]
+                    limiters[i].n_out += int(got)
+                    limiters[i].finished = limiters[i].finished or finals[i]
+        for x, n in rows:
+            if n:
+                x.record_stream(s)
+        buf.record_stream(s)
+    return buf, spans, s
+
+
+def push_group(limiters, pcms, finals) -> list:
+    """``[limiters[i].push(pcms[i], finals[i]) for i]`` -- the same device tensors, bit for bit, and the same counters on every
+    object -- with ONE launch per design instead of one per row (``fq3_limit_push_group``, up to 32 rows a call).  The limiters share
+    a device and a stream and appear once; rows are bucketed by design (rate, spec, tile).  All rows' outputs lie back to back, in
+    row order, in ONE float32 device buffer, and the results are views of it (``_push_group`` hands out the buffer and the rows'
+    places in it, for a caller that lands them in one pinned copy)."""
+    buf, spans, _s = _push_group(limiters, pcms, finals)
+    return [buf[off:off + cnt] for off, cnt in spans]

@@ -420,11 +420,9 @@ class StreamingVocoder:
 
     LIMITER_POOL_MAX = 256
 
-    def limit_push(self, wav, final: bool):
-        """``wav`` (contiguous float32 device vector, or None) through this utterance's limiter on the vocoder's stream (without one,
-        the current stream).  The object is taken at the first chunk -- an idle one from the model's pool, reset, or a new one -- and
-        goes back to the pool with the final push: its device buffers are then reused by a later utterance on the same stream
-        instead of being allocated and freed per reply (a free synchronises the device while other lanes run)."""
+    def limit_take(self):
+        """This utterance's limiter, taken at the first chunk: an idle one from the model's pool, reset, or a new one -- on the
+        vocoder's stream (without one, the current stream).  ``limit_release`` is the other half."""
         if self.limit is None:
             try:
                 lim = self.limit_pool.pop() if self.limit_pool else None        # (another thread may take the last one first)
@@ -436,16 +434,27 @@ class StreamingVocoder:
             else:
                 from .limiter import Limiter
                 self.limit = Limiter(self.limit_spec, int(getattr(self.tok, "sample_rate", 24000)), self.dev, self.side)
-        out = self.limit.push(wav, final)
+        return self.limit
+
+    def limit_release(self) -> None:
+        """the utterance's limiter (if it has one) goes back to the pool behind its final push: its device buffers are then reused by
+        a later utterance on the same stream instead of being allocated and freed per reply (a free synchronises the device while
+        other lanes run)"""
+        lim, self.limit = self.limit, None
+        if lim is not None and self.limit_pool is not None and len(self.limit_pool) < self.LIMITER_POOL_MAX:
+            self.limit_pool.append(lim)
+
+    def limit_push(self, wav, final: bool):
+        """``wav`` (contiguous float32 device vector, or None) through this utterance's limiter (``limit_take``); with the final push
+        the object goes back (``limit_release``)."""
+        out = self.limit_take().push(wav, final)
         if final:
-            lim, self.limit = self.limit, None
-            if self.limit_pool is not None and len(self.limit_pool) < self.LIMITER_POOL_MAX:
-                self.limit_pool.append(lim)
+            self.limit_release()
         return out
 
-    def level_push(self, wav, final: bool, out=None):
-        """``wav`` (contiguous float32 device vector) through this utterance's leveller on the vocoder's stream: as many samples come
-        back (into ``out``, if given).  The object is taken and given back as the limiter's is (``limit_push``)."""
+    def level_take(self):
+        """This utterance's leveller, taken at the first chunk as the limiter is (``limit_take``): a pooled object is reset to this
+        stream's initial gain.  ``level_release`` is the other half."""
         if self.level is None:
             try:
                 lev = self.level_pool.pop() if self.level_pool else None        # (another thread may take the last one first)
@@ -460,7 +469,12 @@ class StreamingVocoder:
                 from .leveller import Leveller
                 self.level = Leveller(self.level_spec, int(getattr(self.tok, "sample_rate", 24000)), self.dev, self.side,
                                       capacity_hops=self.level_hops)
-        y = self.level.push(wav, final, out=out)
+        return self.level
+
+    def level_push(self, wav, final: bool, out=None):
+        """``wav`` (contiguous float32 device vector) through this utterance's leveller on the vocoder's stream: as many samples come
+        back (into ``out``, if given).  The object is taken and given back as the limiter's is (``limit_push``)."""
+        y = self.level_take().push(wav, final, out=out)
         if final:
             self.level_release()
         return y
@@ -1879,27 +1893,56 @@ class FasterQwen3TTS:
                 if gain is not None:
                     from .loudness import apply_gain
                     wav = apply_gain(wav.contiguous(), gain, side)
+                finals = [bool(j[1].get("is_final")) for j in part]
+                # a poll that completes two chunks of one shape puts an utterance into a part twice; a stage is pushed once per group
+                # call, so such a part is cut into consecutive runs in which every utterance appears once (nearly always: one run)
+                runs, seen = [[]], set()
+                for k, j in enumerate(part):
+                    if j[0] in seen:
+                        runs.append([])
+                        seen = set()
+                    seen.add(j[0])
+                    runs[-1].append(k)
                 if lvl is not None:
-                    # every utterance's own leveller takes its row and writes a row of the same length: the group stays one tensor
+                    # every utterance's own leveller takes its row and writes a row of the same length: the group stays one tensor,
+                    # and the rows of a run go through ONE meter launch, ONE target launch and ONE multiply
+                    from .leveller import push_group as level_group
                     rows, wav = wav, torch.empty(wav.shape, dtype=torch.float32, device=wav.device)
-                    for k, j in enumerate(part):
-                        vocs[j[0]].level_push(rows[k].contiguous(), bool(j[1].get("is_final")), out=wav[k])
+                    for run in runs:
+                        level_group([vocs[part[k][0]].level_take() for k in run], [rows[k] for k in run], [finals[k] for k in run],
+                                    outs=[wav[k] for k in run])
+                        for k in run:
+                            if finals[k]:
+                                vocs[part[k][0]].level_release()
                 host = landed = encoded = None
                 staged = [k for k, j in enumerate(part) if vocs[j[0]].output is not None]
                 if limit is not None:
-                    # every utterance's own limiter takes its row: the rows come back shorter by what it holds back, or longer at the end
-                    wav = [vocs[j[0]].limit_push(wav[k].contiguous(), bool(j[1].get("is_final"))) for k, j in enumerate(part)]
+                    # every utterance's own limiter takes its row: the rows come back shorter by what it holds back, or longer at the
+                    # end.  ONE launch per run; the rows lie back to back in the run's device buffer
+                    from .limiter import _push_group as limit_group
+                    src, wav, bufs, place = wav, [None] * len(part), [], [None] * len(part)
+                    for run in runs:
+                        buf, spans, _s = limit_group([vocs[part[k][0]].limit_take() for k in run], [src[k] for k in run],
+                                                     [finals[k] for k in run])
+                        for k, (off, cnt) in zip(run, spans):
+                            wav[k], place[k] = buf[off:off + cnt], (sum(int(b.numel()) for b in bufs) + off, cnt)
+                            if finals[k]:
+                                vocs[part[k][0]].limit_release()
+                        bufs.append(buf)
                 if staged:
                     # the rows with an output spec: one time-scale launch, one resample + encode launch per design, one pinned copy
                     from .audio_out import GroupCopy
                     encoded = (staged, GroupCopy([vocs[part[k][0]]._stage() for k in staged], [wav[k] for k in staged],
                                                  [bool(part[k][1].get("is_final")) for k in staged]))
                 if limit is not None:
-                    host = []
-                    for k, row in enumerate(wav):
-                        host.append(None if k in staged else torch.empty(row.shape, dtype=row.dtype, pin_memory=True))
-                        if host[-1] is not None:
-                            host[-1].copy_(row, non_blocking=True)
+                    # the rows without an output spec: ONE pinned buffer behind one copy per run, and ONE event
+                    host = [None] * len(part)
+                    if len(staged) < len(part):
+                        pinned, at = torch.empty(sum(int(b.numel()) for b in bufs), dtype=torch.float32, pin_memory=True), 0
+                        for buf in bufs:
+                            pinned[at:at + int(buf.numel())].copy_(buf, non_blocking=True)
+                            at += int(buf.numel())
+                        host = [None if k in staged else pinned[place[k][0]:place[k][0] + place[k][1]] for k in range(len(part))]
                     landed = torch.cuda.Event()
                     landed.record(side)
                 elif not device_audio and len(staged) < len(part):

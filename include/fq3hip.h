@@ -869,6 +869,35 @@ int fq3_level_stats(fq3_level* l, fq3_level_report* stats_dev, void* stream);
 int fq3_level_trace(fq3_level* l, uint64_t* energy_dev, float* peak_dev, int32_t* bad_dev, float* target_dev, int64_t capacity,
                     int64_t* n_hops, void* stream);
 
+/* ---- the leveller and the limiter for a GROUP of streams: one launch per stage step, whatever the number of rows ------------------
+ * For the lock-step batch, as fq3_audio_out_push_group / fq3_tsm_push_group above and with their conventions.  Every array is a HOST
+ * array of B entries; row b is exactly
+ *     fq3_level_push(objs[b], pcm[b], n_in[b], final[b], out[b], stream)
+ *     fq3_limit_push(objs[b], pcm[b], n_in[b], final[b], out[b], capacity_samples[b], &n_out[b], stream)
+ *   Equality.        What row b writes, n_out[b] and the state objs[b] is left in -- the meter's hop integers and history, T, the
+ *                    stats slot, the limiter's accumulators -- are bit for bit those of the single push: the same device code computes
+ *                    them.  Group and single pushes mix freely on one object; membership and order may change from call to call.
+ *   Launches.        fq3_leveller_push_group: at most THREE for the whole call (the meters', the targets', the multiplies');
+ *                    fq3_limit_push_group: at most ONE.  A launch no row needs is not made.  No host synchronisation and no copy: the
+ *                    rows' descriptors travel in the launch's argument block.  pcm[b] and out[b] must stay valid until the stream
+ *                    has run the call.
+ *   All or nothing.  Every row is checked before any object changes, a leveller's meter included; the checks are the single push's
+ *                    own (FQ3_ESTATE after a final push, FQ3_ETOOLONG beyond the hop capacity, FQ3_EINVAL for bad input or capacity).
+ *                    On an error the first failing row's code is returned, nothing is launched and no object has moved.
+ *   Limits.          B == 0: returns 0, does nothing.  B < 0, B > FQ3_STAGE_GROUP_MAX, a null array, a null object or the same object
+ *                    twice in one call: FQ3_EINVAL.  These are answered before any HIP call.
+ *   Shared design.   fq3_leveller_push_group: every config field but initial_gain_db and capacity_hops is the same (g0 travels per row);
+ *                    fq3_limit_push_group: the same in_rate, ceiling_db, lookahead_ms, hold_ms and tile.  Else FQ3_EINVAL.
+ *   Empty rows.      Legal, and they cost workgroups that exit.  A leveller row with n_in == 0 only ends its stream when final; a
+ *                    limiter row with n_in == 0 does nothing unless final, and then emits its held-back A + 6 samples (fewer when the
+ *                    stream was shorter).  out[b] == pcm[b] stays legal for the leveller; the limiter stays out of place.
+ *   Name.            The leveller's entry is fq3_leveller_push_group: the fq3_level_* family above is one stream's interface and stays
+ *                    the seven calls it was. */
+int fq3_leveller_push_group(fq3_level* const* objs, int B, const float* const* pcm, const int64_t* n_in, const int* final,
+                         float* const* out, void* stream);
+int fq3_limit_push_group(fq3_limit* const* objs, int B, const float* const* pcm, const int64_t* n_in, const int* final,
+                         float* const* out, const int64_t* capacity_samples, int64_t* n_out, void* stream);
+
 /* ---- Seeded sampling noise: the samplers' Exp(1) variates from a counter-based generator on the device -------------------------
  * The samplers divide by host-provided noise (fq3_sample's noise vector, the rings of fq3_decode_begin).  These calls fill such
  * buffers as a PURE FUNCTION of (seed, emitted-frame index, slot, vocabulary index): no state, no dependence on lane, batch

@@ -9,7 +9,13 @@ over the repeats after a warm-up.  The two new launches have no entry point of t
 minus the meter's push.  Also p50 time to first audio of one streaming entry point (``generate_custom_voice_streaming`` on the
 synthetic 0.6B model, chunks of 8 frames) with and without the ``leveller()`` context, in alternating runs.  Writes
 profiles/leveller_stage.json; a ``bench`` section already in that file (written by the benchmark comparison) is kept.
-usage: leveller_probe.py [runs=100] [out.json]"""
+With --group N: the stage of a lock-step GROUP -- N rows, one streaming chunk each (8 frames, 15 360 samples at 24 kHz), pushed into N
+streams that are already running -- through ``leveller.push_group`` (at most THREE launches: the meters', the targets', the multiplies')
+and through N single pushes (three launches a row: the path of the batch before the group form) IN THE SAME PROCESS, alternating, three
+rounds of 40 repeats after a warm-up, HIP events around each call (the host side of the call included), medians; beside them the
+bf16x2 vocoder's windowed chunk decode of the same N rows (``decode_tensor_batch``).  ``limiter_probe.py --group N`` does the same for
+the limiter through ``group_probe`` below.  Both write their section of profiles/level_group.json and keep the others.
+usage: leveller_probe.py [--group N] [runs=100] [out.json]"""
 import json
 import os
 import statistics
@@ -125,5 +131,76 @@ def main():
     print(json.dumps(res, indent=1))
 
 
+def group_probe(kind, N, argv):
+    """``kind`` = "leveller" | "limiter": N rows of one chunk as a group call and as N single pushes -> the section of level_group.json"""
+    from fq3hip import limiter as LM
+    runs = max(20, int(argv[0])) if argv else 40
+    out_path = argv[1] if len(argv) > 1 else os.path.join(ROOT, "profiles", "level_group.json")
+    g = torch.Generator().manual_seed(3)
+    n = 8 * SAMPLES_PER_FRAME
+    rows = torch.stack([speech_like(n, g) * (0.5 + 1.5 * b / N) for b in range(N)]).contiguous()       # (the louder rows pass the limiter's ceiling)
+    outs = torch.empty_like(rows)
+    if kind == "leveller":
+        stages = [M.Leveller(M.LevelSpec(), 24000, "cuda", capacity_hops=1 << 15) for _ in range(N)]
+        group = lambda: M.push_group(stages, list(rows), [False] * N, outs=list(outs))                  # noqa: E731
+        singles = lambda: [st.push(rows[b], False, out=outs[b]) for b, st in enumerate(stages)]         # noqa: E731
+        launches = {"push_group": 3 * -(-N // M.GROUP_MAX), "single pushes": 3 * N}
+    else:
+        stages = [LM.Limiter(LM.LimiterSpec(), 24000, "cuda") for _ in range(N)]
+        group = lambda: LM.push_group(stages, list(rows), [False] * N)                                  # noqa: E731
+        singles = lambda: [st.push(rows[b], False) for b, st in enumerate(stages)]                      # noqa: E731
+        launches = {"push_group": -(-N // LM.GROUP_MAX), "single pushes": N}
+    for st in stages:
+        st.push(speech_like(40 * SAMPLES_PER_FRAME, g))               # streams that are running: 32 hops measured, the limiter's history full
+    from fq3hip.codec import HipSpeechTokenizer
+    from fq3hip.config import qwen3_tts_0p6b
+    from fq3hip.weights import synth_weights
+    cfg = qwen3_tts_0p6b()
+    W = synth_weights(cfg, 0, torch.bfloat16, parts=("codec",), codec_normalized=True)
+    tok = HipSpeechTokenizer(cfg.codec, W, "cuda", max_frames=400, precision="bf16x2")
+    codes = torch.randint(0, cfg.codec.codebook_size, (N, 33, 16), generator=g).cuda()
+    first = tok.num_samples_total(33) - 8 * SAMPLES_PER_FRAME
+    cases = {"push_group": group, f"{N} single pushes": singles, "vocoder decode_tensor_batch": lambda: tok.decode_tensor_batch(codes, first)}
+
+    def events(fn):
+        pairs = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(runs)]
+        for e0, e1 in pairs:
+            e0.record(); fn(); e1.record()
+        torch.cuda.synchronize()
+        return [e0.elapsed_time(e1) for e0, e1 in pairs]
+    for fn in cases.values():
+        for _ in range(10):
+            fn()
+    torch.cuda.synchronize()
+    samples = {k: [] for k in cases}
+    for _round in range(3):                                           # alternating: the forms see the same machine
+        for k, fn in cases.items():
+            samples[k].append(events(fn))
+    res = {"device": torch.cuda.get_device_name(0), "stage": kind, "rows": N, "runs_per_round": runs, "rounds": 3, "warmup": 10, "in_rate": 24000,
+           "n_in_per_row": n, "launches": launches,
+           "unit": "ms per group of rows, device events around the call (host side included): median over all repeats; per_round: each alternating round's median",
+           "ms": {k: {"median": round(statistics.median(v for r in rs for v in r), 4), "per_round": [round(statistics.median(r), 4) for r in rs],
+                      "min": round(min(v for r in rs for v in r), 4)} for k, rs in samples.items()}}
+    gd, sd, vd = (res["ms"][k]["median"] for k in cases)
+    res["notes"] = [f"the group call takes {gd:.3f} ms, the {N} single pushes {sd:.3f} ms: " +
+                    (f"{sd / gd:.2f}x faster" if gd < sd else f"NOT faster ({gd / sd:.2f}x the singles' time)"),
+                    f"the vocoder's chunk decode of the same {N} rows takes {vd:.3f} ms: the group call is {gd / vd:.3f} of it, the single pushes {sd / vd:.3f}"]
+    try:
+        with open(out_path) as f:
+            whole = json.load(f)
+    except (OSError, ValueError):
+        whole = {}
+    whole[f"{kind}_rows_{N}"] = res
+    os.makedirs(os.path.dirname(out_path) or ".", exist_ok=True)
+    with open(out_path, "w") as f:
+        json.dump(whole, f, indent=1)
+        f.write("\n")
+    print(json.dumps(res, indent=1))
+
+
 if __name__ == "__main__":
-    main()
+    if "--group" in sys.argv[1:]:
+        _i = sys.argv.index("--group")
+        group_probe("leveller", int(sys.argv[_i + 1]), sys.argv[1:_i] + sys.argv[_i + 2:])
+    else:
+        main()

@@ -9,7 +9,10 @@ running (its history full), as a streaming vocoder issues it.  The input is driv
 limiter works; its time does not depend on the data.  Also the detector's figures on the GPU tests' signals (tests/_limit_ref.py):
 the under-read against the 32x float64 yardstick and the true-peak overshoot of the limited output -- CPU measurements, taken here so
 that one file holds them.  Writes profiles/limiter_stage.json.
-usage: limiter_probe.py [runs=60] [out.json]"""
+With --group N: N rows of one streaming chunk into N running streams through ``limiter.push_group`` (ONE launch) and through N single
+pushes, alternating in the same process, beside the bf16x2 vocoder's chunk decode of the same rows (``leveller_probe.group_probe``
+holds the method); writes its section of profiles/level_group.json.
+usage: limiter_probe.py [--group N] [runs=60] [out.json]"""
 import json
 import os
 import sys
@@ -91,4 +94,9 @@ def main():
 
 
 if __name__ == "__main__":
-    main()
+    if "--group" in sys.argv[1:]:
+        from leveller_probe import group_probe
+        _i = sys.argv.index("--group")
+        group_probe("limiter", int(sys.argv[_i + 1]), sys.argv[1:_i] + sys.argv[_i + 2:])
+    else:
+        main()

@@ -19,6 +19,7 @@ import numpy as np
 import torch
 
 from .loudness import LoudnessSession
+from .stream_groups import StreamGroups, runs_of, window_plan
 
 logger = logging.getLogger(__name__)
 
@@ -612,23 +613,18 @@ class StreamingVocoder:
         n_new = chunk.shape[0]
         flat = self._cat(self.all_codes, ready_event)
         n_total = flat.shape[0]
-        if self.spf is None:
-            rc = self.ref_codes
+        rc = self.ref_codes
+        ref_len = rc.shape[0] if rc is not None else 0
+        start, n_in, first, self.prev_len, self.spf = window_plan(n_total, n_new, ref_len, self.prev_len, self.spf, self.min_cal,
+                                                                  self.CONTEXT_FRAMES, self.tok.num_samples_total)
+        if start is None:
             inp = self._cat([self._ref_on(flat.device), flat], ready_event) if rc is not None else flat
-            ref_len = rc.shape[0] if rc is not None else 0
-            n_audio = self.tok.num_samples_total(inp.shape[0])
-            cut = int(ref_len / max(inp.shape[0], 1) * n_audio) if ref_len else 0
-            first = cut + self.prev_len
-            self.prev_len = n_audio - cut
-            if n_total >= self.min_cal:
-                self.spf = self.prev_len / n_total
             self.last_prefix = self.prefix if ref_len else None
-            return inp, first
-        start = max(0, n_total - n_new - self.CONTEXT_FRAMES)
-        window = flat[start:]
-        n_ctx = window.shape[0] - n_new
-        self.last_prefix = None
-        return window, (int(round(n_ctx * self.spf)) if n_ctx > 0 else 0)
+        else:
+            inp = flat[start:]
+            self.last_prefix = None
+        assert inp.shape[0] == n_in
+        return inp, first
 
     def push(self, chunk: torch.Tensor, ready_event=None, final=False):
         """``chunk`` LongTensor[n_new, 16] (device) -> (new audio as a host array, sample_rate).  ``final`` (only read with an
@@ -1626,6 +1622,12 @@ class FasterQwen3TTS:
         return dict(max_new_tokens=max_new_tokens, min_new_tokens=min_new_tokens, temperature=temperature,
                     top_k=top_k, top_p=top_p, do_sample=do_sample, repetition_penalty=repetition_penalty)
 
+    @staticmethod
+    def _frame_limit(gen_kwargs) -> int:
+        """the largest ``max_new_tokens`` of a batch's entries (one value, or one per text: ``_batch_feed``)"""
+        n = gen_kwargs.get("max_new_tokens", 2048)
+        return max(int(v) for v in n) if isinstance(n, (list, tuple)) else int(n)
+
     # ---- public generation entry points ----------------------------------------------------------------------------
     @torch.inference_mode()
     def generate_voice_clone(self, text: str, language: str, ref_audio: Optional[Union[str, Path]] = None,
@@ -1722,7 +1724,8 @@ class FasterQwen3TTS:
         ``(talker, config, tie, tam, tth, tpe, ref_codes | None)``.  Returns ``(head, source)`` for ``BatchDecoder.run``: the first
         ``lanes`` requests up front -- the first wave starts decoding before the later prompts exist -- and a ``source`` callback
         that prepares the rest one at a time at frame boundaries.  ``meta[i]`` receives the entry's ``ref_codes``.  ``seeds``: one
-        sampling seed or None per entry (``generate.expand_seeds``)."""
+        sampling seed or None per entry (``generate.expand_seeds``).  ``gen_kwargs["max_new_tokens"]`` may be a list: entry i's own
+        frame limit (the ``max_new_tokens`` of the batch entry points: one value, or one per text)."""
         from .batching import BatchRequest
         it = enumerate(prepared)
 
@@ -1732,7 +1735,13 @@ class FasterQwen3TTS:
                 return None
             i, (talker, config, tie, tam, tth, tpe, rc) = nxt
             meta[i] = rc
-            return BatchRequest(i, talker, tie, tam, tth, tpe, config, dict(gen_kwargs), seed=None if seeds is None else seeds[i])
+            kw = dict(gen_kwargs)
+            if isinstance(kw.get("max_new_tokens"), (list, tuple)):
+                # one frame limit per entry (lanes then finish, and are re-used, at staggered frames)
+                if i >= len(kw["max_new_tokens"]):
+                    raise ValueError("max_new_tokens must be one value or one per text")
+                kw["max_new_tokens"] = int(kw["max_new_tokens"][i])
+            return BatchRequest(i, talker, tie, tam, tth, tpe, config, kw, seed=None if seeds is None else seeds[i])
 
         # (only the first SLICE of the first wave is built here: the scheduler pulls the rest from `source` in slices and queues every
         # slice's packed prefill behind the one before, so prompt builds and prefills overlap -- BatchDecoder.run, "first wave, pipelined")
@@ -1791,7 +1800,7 @@ class FasterQwen3TTS:
         # 443x -- so it is OFF by default; a server whose lanes finish at different times has nothing to gain from it either.
         inc = int(getattr(self, "batch_vocode_every", 0) or 0)
         if inc > 0 and not device_audio and outputs is None and not self._levelling() and voc.async_ok and hasattr(voc.tok, "decode_tensor_batch") and hasattr(voc.tok, "num_samples_total"):
-            max_new = min(int(gen_kwargs.get("max_new_tokens", 2048)), int(self.talker_graph.engine.max_frames))
+            max_new = min(self._frame_limit(gen_kwargs), int(self.talker_graph.engine.max_frames))
             for rid, codes, info in dec.run(head, source=source, chunk_frames=inc):
                 more = int(getattr(dec, "more_in_poll", 0))
                 voc.inc_add(rid, codes, meta.get(rid), info.pop("codes_ready_event", None), bool(info.get("is_final")), more, max_new)
@@ -1857,19 +1866,17 @@ class FasterQwen3TTS:
         tok = self.model.model.speech_tokenizer
         side = self._vocoder_stream(tok)
         batched = side is not None and hasattr(tok, "decode_tensor_batch")
-        jobs: list = []                                  # the events of one poll, in order: [rid, meta, audio | None, (codes_in, first, ev) | None]
-
         # chunks of different utterances that need the SAME decode shape (the first chunks of lanes that started together: reference + 8
         # frames in, the last 8 frames' samples out) go through one batched launch set on the vocoder stream, STREAM_GROUP at a time.
         # Round 6: a group is LAUNCHED as soon as it is full -- while the host still prepares the next group's inputs -- every group's
         # waveform goes to pinned host memory behind its launch set, and the groups are handed out one by one as their copies land: a
         # wave of 128 first chunks (four groups of 32) used to be prepared as a whole, launched group by group with a host wait after
-        # each, and reached the caller all at once after the last group.  Per utterance the order of the events is unchanged: groups are
-        # handed out in launch order, a launch takes every open class in order of first appearance, markers without audio come last.
-        open_classes: Dict[Any, list] = {}
-        queued: list = []                               # (jobs of the group, pinned waveforms, event, device waveforms kept alive)
-        exact_pending: dict = {}                        # (exact mode) utterance -> (its chunks waiting in open classes, order of the last one's class)
-        class_seq: dict = {}                            # (exact mode) open class -> order of first appearance = launch order
+        # each, and reached the caller all at once after the last group.  The bookkeeping -- the jobs of a poll ``[rid, meta, audio |
+        # None, (codes_in, first, ev, ...) | None]``, their classes, the launches made -- is ``stream_groups.StreamGroups``; ``launch`` and
+        # ``collect`` below are the device work it calls.  Per utterance the order of the events is kept BY THE LAUNCHES, in both modes: a
+        # launch pushes its members' own stages and stream states, so a chunk never joins a class that would launch in front of an
+        # earlier chunk of its utterance that still waits (lanes re-used at staggered frames produce that; the classes up to that
+        # chunk's are launched first).  Groups are handed out in launch order, markers without audio come last.
 
         def launch(key, part):
             _T, first, pf_len = key
@@ -1896,13 +1903,7 @@ class FasterQwen3TTS:
                 finals = [bool(j[1].get("is_final")) for j in part]
                 # a poll that completes two chunks of one shape puts an utterance into a part twice; a stage is pushed once per group
                 # call, so such a part is cut into consecutive runs in which every utterance appears once (nearly always: one run)
-                runs, seen = [[]], set()
-                for k, j in enumerate(part):
-                    if j[0] in seen:
-                        runs.append([])
-                        seen = set()
-                    seen.add(j[0])
-                    runs[-1].append(k)
+                runs = runs_of(part)
                 if lvl is not None:
                     # every utterance's own leveller takes its row and writes a row of the same length: the group stays one tensor,
                     # and the rows of a run go through ONE meter launch, ONE target launch and ONE multiply
@@ -1930,10 +1931,15 @@ class FasterQwen3TTS:
                                 vocs[part[k][0]].limit_release()
                         bufs.append(buf)
                 if staged:
-                    # the rows with an output spec: one time-scale launch, one resample + encode launch per design, one pinned copy
+                    # the rows with an output spec: one time-scale launch, one resample + encode launch per design, one pinned copy --
+                    # per run, as the stages in front: a stage is pushed once per group call
                     from .audio_out import GroupCopy
-                    encoded = (staged, GroupCopy([vocs[part[k][0]]._stage() for k in staged], [wav[k] for k in staged],
-                                                 [bool(part[k][1].get("is_final")) for k in staged]))
+                    encoded = []
+                    for run in runs:
+                        rows = [k for k in run if k in staged]
+                        if rows:
+                            encoded.append((rows, GroupCopy([vocs[part[k][0]]._stage() for k in rows], [wav[k] for k in rows],
+                                                            [finals[k] for k in rows])))
                 if limit is not None:
                     # the rows without an output spec: ONE pinned buffer behind one copy per run, and ONE event
                     host = [None] * len(part)
@@ -1951,67 +1957,35 @@ class FasterQwen3TTS:
                     landed = torch.cuda.Event()
                     landed.record(side)
                 elif staged:
-                    landed = encoded[1].event
-            queued.append((part, host, landed, wav, encoded))
+                    landed = encoded[-1][1].event              # (one stream: the last run's copy lands last)
+            return host, landed, wav, encoded
 
-        def launch_open():
-            exact_pending.clear()
-            class_seq.clear()
-            for key in list(open_classes):
-                members = open_classes.pop(key)
-                for i in range(0, len(members), _SideVocoder.STREAM_GROUP):
-                    launch(key, members[i:i + _SideVocoder.STREAM_GROUP])
+        def collect(part, handle):
+            host, landed, wav, encoded = handle
+            if landed is None:
+                arr = wav                                      # device rows: whoever takes them works on the vocoder stream
+            else:
+                landed.synchronize()
+                arr = ([None if h is None else h.numpy() for h in host] if isinstance(host, list) else
+                       host.numpy() if host is not None else [None] * len(part))
+            for k, j in enumerate(part):
+                j[2] = arr[k]
+            for rows, copy in encoded or ():
+                for k, a in zip(rows, copy.rows()):
+                    v = vocs[part[k][0]]
+                    if v.stage.flac and not v.header_sent:
+                        # a FLAC stream: the utterance's first chunk starts with the stream header (length unknown)
+                        a, v.header_sent = np.concatenate([np.frombuffer(v.stage.header(), dtype=np.uint8), a]), True
+                    part[k][2] = a
+                    if part[k][1].get("is_final"):
+                        self._give_stage(v.stage)
 
-        def add_job(j):
-            jobs.append(j)
-            if j[3] is not None and len(j[3]) > 4:
-                # exact mode: (new codes, drop, ev, None, stream state, frames before the push) -- the class is (min(F, ctx_max), n_new) and the
-                # drop, so every steady-state chunk of every lane falls into one class.  A state is pushed once per call and in order: a
-                # poll that completes several chunks of an utterance puts its k-th waiting chunk into the k-th generation of the class,
-                # and a class that would launch in front of an earlier chunk of the same utterance is not joined -- everything open
-                # is launched first.
-                cnt, last = exact_pending.get(j[0], (0, -1))
-                shape = (min(int(j[3][5]), tok.stream_ctx_max), int(j[3][0].shape[0]))
-                key = ((cnt,) + shape, int(j[3][1]), "exact")
-                if class_seq.get(key, len(class_seq)) <= last:
-                    launch_open()
-                    cnt, key = 0, ((0,) + shape, int(j[3][1]), "exact")
-                exact_pending[j[0]] = (cnt + 1, class_seq.setdefault(key, len(class_seq)))
-                open_classes.setdefault(key, []).append(j)
-                if len(open_classes[key]) >= _SideVocoder.STREAM_GROUP:
-                    launch_open()
-            elif j[3] is not None:
-                pf = j[3][3] if len(j[3]) > 3 else None
-                key = (int(j[3][0].shape[0]), int(j[3][1]), pf.ref_len if pf is not None else 0)
-                open_classes.setdefault(key, []).append(j)
-                if len(open_classes[key]) >= _SideVocoder.STREAM_GROUP:
-                    launch_open()
-
-        def flush():
-            launch_open()
-            plain = [j for j in jobs if j[3] is None]
-            jobs[:] = []
-            groups, queued[:] = list(queued), []
-            for part, host, landed, wav, encoded in groups:
-                if landed is None:
-                    arr = wav                                      # device rows: whoever takes them works on the vocoder stream
-                else:
-                    landed.synchronize()
-                    arr = ([None if h is None else h.numpy() for h in host] if isinstance(host, list) else
-                           host.numpy() if host is not None else [None] * len(part))
-                for k, j in enumerate(part):
-                    j[2] = arr[k]
-                if encoded is not None:
-                    for k, a in zip(encoded[0], encoded[1].rows()):
-                        v = vocs[part[k][0]]
-                        if v.stage.flac and not v.header_sent:
-                            # a FLAC stream: the utterance's first chunk starts with the stream header (length unknown)
-                            a, v.header_sent = np.concatenate([np.frombuffer(v.stage.header(), dtype=np.uint8), a]), True
-                        part[k][2] = a
-                        if part[k][1].get("is_final"):
-                            self._give_stage(v.stage)
-                yield from part
-            yield from plain
+        # exact mode: (new codes, drop, ev, None, stream state, frames before the push) -- the class is (min(F, ctx_max), n_new) and the
+        # drop, so every steady-state chunk of every lane falls into one class; a state is pushed once per call, so the k-th chunk an
+        # utterance adds in a poll goes into the k-th generation of the class (``StreamGroups.key_of``)
+        groups = StreamGroups(launch, collect, _SideVocoder.STREAM_GROUP, getattr(tok, "stream_ctx_max", None))
+        self._stream_group_stats = groups.stats         # the counters of the newest run (jobs, launches, order_launches), nothing else kept
+        add_job, launch_open, flush = groups.add, groups.launch_open, groups.flush
 
         def out(r, m):
             if stamp is not None:
@@ -2127,7 +2101,8 @@ class FasterQwen3TTS:
         """Streaming AND batched: the texts decode in lock-step lanes (as :meth:`generate_voice_clone_batch`) and every
         ``chunk_size`` frames of any utterance yield ``(text_index, audio_chunk, sample_rate, timing)`` -- per utterance
         exactly the chunks :meth:`generate_voice_clone_streaming` would produce for it (same windowing state machine).
-        ``timing``: ``chunk_index``, ``total_steps_so_far``, ``is_final``."""
+        ``timing``: ``chunk_index``, ``total_steps_so_far``, ``is_final``.  ``max_new_tokens``: one value, or a list with one per
+        text (all batch entry points)."""
         nsm = self._resolve_non_streaming_mode(non_streaming_mode, default=False)
         prepared = self._prepare_clone_batch(texts, language, ref_audio, ref_text, xvec_only, nsm, append_silence, instruct,
                                              voice_clone_prompt)
@@ -2346,7 +2321,7 @@ class FasterQwen3TTS:
             return None
         from .leveller import capacity_for
         tok = self.model.model.speech_tokenizer
-        frames = int(gen_kwargs.get("max_new_tokens", 2048))
+        frames = self._frame_limit(gen_kwargs)
         per_seg = int(tok.num_samples_total(frames)) if hasattr(tok, "num_samples_total") else frames * (self.sample_rate * 2 // 25)
         total = sum(per_seg + spec.pause_samples(s.pause, self.sample_rate) for s in segs)
         return capacity_for(total, self.sample_rate)

@@ -20,6 +20,10 @@
 //
 // The workgroup with blockIdx == n_frames, when there is one, only copies the samples behind the last whole block into the object's
 // other tail buffer.
+//
+// Both kernels are one __device__ body each (flac_encode_body, flac_gather_body) behind two __global__ shells: the single kernels, whose
+// blockIdx is the frame, and flac_encode_group_kernel / flac_gather_group_kernel for the pushes of a group of objects of one design
+// (fq3_flac_push_group, at the end of this file), whose workgroups find their (row, frame) in the launch's argument block.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -103,7 +107,8 @@ __device__ __forceinline__ int flac_block_code(int n) {
     }
 }
 
-__global__ __launch_bounds__(kFlacThreads) void flac_encode_kernel(FlacArgs a) {
+// frame f of the launch `a` describes; f == a.n_frames: the tail copy.  Uniform over the workgroup.
+__device__ __forceinline__ void flac_encode_body(const FlacArgs& a, const int f) {
     __shared__ int s_x[kFlacMaxBlock];
     __shared__ uint32_t s_sum[5 * kFlacSegs * (kFlacMaxK + 1)];
     __shared__ uint32_t s_bits[kFlacBitWords];
@@ -113,7 +118,7 @@ __global__ __launch_bounds__(kFlacThreads) void flac_encode_kernel(FlacArgs a) {
     __shared__ uint32_t s_crc[512];
     __shared__ int s_hdr, s_order, s_porder, s_body;
 
-    const int tid = threadIdx.x, f = blockIdx.x;
+    const int tid = threadIdx.x;
     if (f == a.n_frames) {
         for (int i = tid; i < a.tail_len; i += kFlacThreads) a.tail_next[i] = (int16_t)flac_fetch(a, a.tail_from + i);
         return;
@@ -317,32 +322,121 @@ __global__ __launch_bounds__(kFlacThreads) void flac_encode_kernel(FlacArgs a) {
     if (tid == 0) a.sizes[f] = flen;
 }
 
+__global__ __launch_bounds__(kFlacThreads) void flac_encode_kernel(FlacArgs a) { flac_encode_body(a, (int)blockIdx.x); }
+
 // Frames of one launch pair, back to back: out[base + sum sizes[0 .. f)) <- stage slot f.  base = *base_in (null: 0), the bytes the
 // earlier launch pairs of the same push wrote; block 0 writes base + sum of all sizes to *total_out (the other of the object's two
 // counters, so that no block reads what another one writes) and to *n_bytes.
-__global__ __launch_bounds__(kFlacGatherThreads) void flac_gather_kernel(const uint8_t* stage, const int32_t* sizes, int n_frames, int stride,
-                                                                         const int64_t* base_in, int64_t* total_out, int64_t* n_bytes,
-                                                                         uint8_t* out) {
+struct FlacGatherArgs {
+    const uint8_t* stage;
+    const int32_t* sizes;
+    const int64_t* base_in;
+    int64_t* total_out;
+    int64_t* n_bytes;
+    uint8_t* out;
+    int n_frames, stride;
+};
+
+__device__ __forceinline__ void flac_gather_body(const FlacGatherArgs& a, const int f) {
     __shared__ int64_t s_off;
-    const int tid = threadIdx.x, f = blockIdx.x;
+    const int tid = threadIdx.x;
     if (tid < 64) {
-        const int v = tid < n_frames ? sizes[tid] : 0;
+        const int v = tid < a.n_frames ? a.sizes[tid] : 0;
         int pre = tid < f ? v : 0, tot = v;
         for (int d = 32; d >= 1; d >>= 1) {
             pre += __shfl_xor(pre, d);
             tot += __shfl_xor(tot, d);
         }
         if (tid == 0) {
-            const int64_t base = base_in ? *base_in : 0;
+            const int64_t base = a.base_in ? *a.base_in : 0;
             s_off = base + pre;
-            if (f == 0) { *total_out = base + tot; *n_bytes = base + tot; }
+            if (f == 0) { *a.total_out = base + tot; *a.n_bytes = base + tot; }
         }
     }
     __syncthreads();
-    const int len = sizes[f];
-    const uint8_t* src = stage + (size_t)f * stride;
-    uint8_t* dst = out + s_off;
+    const int len = a.sizes[f];
+    const uint8_t* src = a.stage + (size_t)f * a.stride;
+    uint8_t* dst = a.out + s_off;
     for (int i = tid; i < len; i += kFlacGatherThreads) dst[i] = src[i];
+}
+
+__global__ __launch_bounds__(kFlacGatherThreads) void flac_gather_kernel(const uint8_t* stage, const int32_t* sizes, int n_frames, int stride,
+                                                                         const int64_t* base_in, int64_t* total_out, int64_t* n_bytes,
+                                                                         uint8_t* out) {
+    FlacGatherArgs a;
+    a.stage = stage; a.sizes = sizes; a.base_in = base_in; a.total_out = total_out; a.n_bytes = n_bytes; a.out = out;
+    a.n_frames = n_frames; a.stride = stride;
+    flac_gather_body(a, (int)blockIdx.x);
+}
+
+// ---- a group of pushes in one launch pair (fq3_flac_push_group) ----
+// The rows share one design (block size and rate) and differ in everything a push derives from its object's state.  A row of a launch
+// has between 0 and kFlacBatch + 1 workgroups -- its frames of this round, then its tail copy (encode) or, for a push that completes no
+// frame at all, the one that writes its byte count of 0 (gather) -- so the grid is one-dimensional and PACKED: wg0[b] is the first
+// workgroup of row b, wg0[b + 1] - wg0[b] its count, and rows past the group's last hold the grid size.  A workgroup counts the rows
+// that start at or before it; blockIdx is uniform and the table lies in the argument segment, so this is 31 scalar compares on two
+// wide scalar loads, and the row's descriptor is read by scalar loads at a scalar offset.  The descriptors travel BY VALUE, as in
+// audio_kernels.cuh: no table in device memory has to be filled (and kept alive) per call.
+// LDS: the encode body's 51 KB of static LDS admit three workgroups per CU; the group launch brings the frames of all rows to the CUs
+// at once (13 frames a row of a typical chunk: some 420 workgroups for 32 rows) where a row's own launch fills 13 CUs.
+constexpr int kFlacGroupMax = 32;                   // FQ3_STAGE_GROUP_MAX
+
+struct FlacGroupRow {
+    const int16_t* pcm;
+    const int16_t* tail;
+    int16_t* tail_next;
+    uint8_t* stage;
+    int32_t* sizes;
+    int64_t* totals;           // the object's two running byte counts
+    int64_t* n_bytes;
+    uint8_t* out;
+    int64_t avail, tail_from;
+    int tail_n, tail_len;      // tail_len > 0 in the row's last round only
+    int n_frames;              // of this round
+    uint32_t frame0;           // frame number of this round's frame 0
+};
+
+struct FlacGroupArgs {
+    int64_t first;             // logical index of the first sample of this round's frame 0: round * kFlacBatch * block
+    int block, stride, rate_code, rate_hz;
+    int round, pad_;
+    int enc_wg0[kFlacGroupMax], gat_wg0[kFlacGroupMax];
+    FlacGroupRow rows[kFlacGroupMax];
+};
+// hipModuleLaunchKernel / hipLaunchKernelGGL carry at most 4 KB of kernel arguments
+static_assert(sizeof(FlacGroupRow) == 96 && sizeof(FlacGroupArgs) <= 4096, "the descriptors must fit the 4 KB of arguments a launch may carry");
+
+__device__ __forceinline__ int flac_group_row(const int* wg0, const int wg) {
+    int row = 0;
+#pragma unroll
+    for (int b = 1; b < kFlacGroupMax; ++b) row += wg >= wg0[b] ? 1 : 0;          // wg0 does not decrease: the last row that starts at or before wg
+    return row;
+}
+
+__global__ __launch_bounds__(kFlacThreads) void flac_encode_group_kernel(const FlacGroupArgs g) {
+    const int wg = (int)blockIdx.x, row = flac_group_row(g.enc_wg0, wg);
+    const FlacGroupRow& r = g.rows[row];
+    FlacArgs a;
+    a.pcm = r.pcm; a.tail = r.tail; a.tail_next = r.tail_next; a.stage = r.stage; a.sizes = r.sizes;
+    a.first = g.first; a.avail = r.avail; a.tail_from = r.tail_from; a.tail_n = r.tail_n; a.tail_len = r.tail_len;
+    a.block = g.block; a.n_frames = r.n_frames; a.stride = g.stride; a.frame0 = r.frame0;
+    a.rate_code = g.rate_code; a.rate_hz = g.rate_hz;
+    flac_encode_body(a, wg - g.enc_wg0[row]);
+}
+
+__global__ __launch_bounds__(kFlacGatherThreads) void flac_gather_group_kernel(const FlacGroupArgs g) {
+    const int wg = (int)blockIdx.x, row = flac_group_row(g.gat_wg0, wg);
+    const FlacGroupRow& r = g.rows[row];
+    if (r.n_frames == 0) {                                                          // a push that completes no frame: its one workgroup
+        if (threadIdx.x == 0) *r.n_bytes = 0;
+        return;
+    }
+    FlacGatherArgs a;
+    a.stage = r.stage; a.sizes = r.sizes;
+    a.base_in = g.round ? r.totals + ((g.round - 1) & 1) : nullptr;
+    a.total_out = r.totals + (g.round & 1);
+    a.n_bytes = r.n_bytes; a.out = r.out; a.n_frames = r.n_frames; a.stride = g.stride;
+    flac_gather_body(a, wg - g.gat_wg0[row]);
 }
 
 }  // namespace fq3

@@ -1,6 +1,8 @@
 // FLAC output behind the C ABI: lossless compression of the s16 output stage's samples (fq3_audio.hip) on the device.
 //   fq3_flac_design / _header / _count   host only (no HIP call): block size and frame bound, the 42-byte stream header, frame count
 //   fq3_flac_create / _push              streaming encoder: per push one launch pair per 64 frames (encode, then gather)
+//   fq3_flac_push_group                  the pushes of up to 32 objects of one design in ONE launch pair per 64 frames, each row bit for
+//                                        bit its single push
 //
 // The stream: `fLaC`, one STREAMINFO block, then frames of B samples (only the last one of a stream may be shorter), mono, 16 bits,
 // fixed-blocksize numbering.  A frame holds one subframe -- CONSTANT, VERBATIM or FIXED of order 0..4 with partitioned 4-bit Rice
@@ -143,30 +145,58 @@ extern "C" int fq3_flac_reset(fq3_flac* f, void* stream) {
     return 0;
 }
 
+namespace {
+
+// what a push does, worked out from the object's state without changing it
+struct Push {
+    int64_t avail, frames;
+    int keep;                         // the tail this push leaves
+    bool copy_tail;                   // n_in = 0 and no frame: the tail stays where it is
+};
+
+int check_push_(const std::string& who, const fq3_flac* f, const int16_t* pcm, int64_t n_in, int final, const uint8_t* out,
+                int64_t capacity_bytes, Push* q) {
+    if (n_in < 0 || capacity_bytes < 0 || (n_in > 0 && !pcm)) return fq3_fail_(FQ3_EINVAL, who + ": bad input");
+    if (f->finished) return fq3_fail_(FQ3_ESTATE, who + ": the stream has ended; fq3_flac_reset starts the next one");
+    const Plan& p = f->p;
+    if (n_in > kMaxLength - f->n_in) return fq3_fail_(FQ3_EINVAL, who + ": stream above 2^50 samples");
+    q->avail = f->tail_n + n_in;
+    q->frames = frames_(p, q->avail, final);
+    if (f->frame + q->frames > kMaxFrames) return fq3_fail_(FQ3_EINVAL, who + ": stream above 2^31 frames");
+    const int64_t bound = 2 * (int64_t)p.block + 18;
+    if (q->frames > capacity_bytes / bound)
+        return fq3_fail_(FQ3_EINVAL, who + ": " + std::to_string(q->frames) + " frames of at most " + std::to_string(bound) +
+                         " bytes, capacity " + std::to_string(capacity_bytes));
+    if (q->frames > 0 && !out) return fq3_fail_(FQ3_EINVAL, who + ": null output");
+    q->keep = final ? 0 : (int)(q->avail - q->frames * p.block);
+    q->copy_tail = q->keep > 0 && n_in > 0;
+    return 0;
+}
+
+void commit_push_(fq3_flac* f, const Push& q, int64_t n_in, int final) {
+    if (q.copy_tail) f->cur ^= 1;
+    f->tail_n = q.keep;
+    f->n_in += n_in;
+    f->frame += q.frames;
+    if (final) f->finished = true;
+}
+
+}  // namespace
+
 extern "C" int fq3_flac_push(fq3_flac* f, const int16_t* pcm, int64_t n_in, int final, uint8_t* out, int64_t capacity_bytes,
                              int64_t* n_frames, int64_t* n_bytes_dev, void* stream) {
     if (!f || !n_frames || !n_bytes_dev) return fq3_fail_(FQ3_EINVAL, "fq3_flac_push: null argument");
-    if (n_in < 0 || capacity_bytes < 0 || (n_in > 0 && !pcm)) return fq3_fail_(FQ3_EINVAL, "fq3_flac_push: bad input");
-    if (f->finished) return fq3_fail_(FQ3_ESTATE, "fq3_flac_push: the stream has ended; fq3_flac_reset starts the next one");
+    Push q{};
+    if (int rc = check_push_("fq3_flac_push", f, pcm, n_in, final, out, capacity_bytes, &q)) return rc;
     const Plan& p = f->p;
-    if (n_in > kMaxLength - f->n_in) return fq3_fail_(FQ3_EINVAL, "fq3_flac_push: stream above 2^50 samples");
-    const int64_t avail = f->tail_n + n_in;
-    const int64_t frames = frames_(p, avail, final);
-    if (f->frame + frames > kMaxFrames) return fq3_fail_(FQ3_EINVAL, "fq3_flac_push: stream above 2^31 frames");
-    const int64_t bound = 2 * (int64_t)p.block + 18;
-    if (frames > capacity_bytes / bound)
-        return fq3_fail_(FQ3_EINVAL, "fq3_flac_push: " + std::to_string(frames) + " frames of at most " + std::to_string(bound) +
-                         " bytes, capacity " + std::to_string(capacity_bytes));
-    if (frames > 0 && !out) return fq3_fail_(FQ3_EINVAL, "fq3_flac_push: null output");
+    const int64_t frames = q.frames;
     *n_frames = frames;
     hipStream_t s = (hipStream_t)stream;
-    const int keep = final ? 0 : (int)(avail - frames * p.block);                // the tail this push leaves
-    const bool copy_tail = keep > 0 && n_in > 0;                                    // n_in = 0 and no frame: the tail stays where it is
     if (frames == 0) FHIP(hipMemsetAsync(n_bytes_dev, 0, sizeof(int64_t), s));
     FlacArgs k{};
     k.pcm = pcm; k.tail = f->tail[f->cur]; k.tail_next = f->tail[f->cur ^ 1];
     k.stage = f->stage; k.sizes = f->sizes;
-    k.avail = avail; k.tail_n = f->tail_n;
+    k.avail = q.avail; k.tail_n = f->tail_n;
     k.tail_from = frames * p.block; k.tail_len = 0;
     k.block = p.block; k.stride = f->stride;
     k.rate_code = p.rate_code; k.rate_hz = p.rate;
@@ -178,7 +208,7 @@ extern "C" int fq3_flac_push(fq3_flac* f, const int16_t* pcm, int64_t n_in, int 
         k.first = done * p.block;
         k.n_frames = nb;
         k.frame0 = (uint32_t)(f->frame + done);
-        k.tail_len = last && copy_tail ? keep : 0;
+        k.tail_len = last && q.copy_tail ? q.keep : 0;
         const int grid = nb + (k.tail_len > 0 ? 1 : 0);
         if (grid > 0) {
             hipLaunchKernelGGL(flac_encode_kernel, dim3(grid), dim3(kFlacThreads), 0, s, k);
@@ -193,10 +223,82 @@ extern "C" int fq3_flac_push(fq3_flac* f, const int16_t* pcm, int64_t n_in, int 
         done += nb;
         ++pair;
     } while (done < frames);
-    if (copy_tail) f->cur ^= 1;
-    f->tail_n = keep;
-    f->n_in += n_in;
-    f->frame += frames;
-    if (final) f->finished = true;
+    commit_push_(f, q, n_in, final);
+    return 0;
+}
+
+// The pushes of up to FQ3_STAGE_GROUP_MAX objects of one design: per round of 64 frames ONE encode launch and ONE gather launch over the
+// rows that have frames (or a tail to copy, or a byte count of 0 to write) in that round.  Everything a row's workgroups read is what
+// its single push would hand them, so the bytes, the counts and the objects' state are those of B single pushes.
+extern "C" int fq3_flac_push_group(fq3_flac* const* objs, int B, const int16_t* const* pcm, const int64_t* n_in, const int* final,
+                                   uint8_t* const* out, const int64_t* capacity_bytes, int64_t* n_frames, int64_t* const* n_bytes_dev,
+                                   void* stream) {
+    if (B < 0 || B > FQ3_STAGE_GROUP_MAX)
+        return fq3_fail_(FQ3_EINVAL, "fq3_flac_push_group: B = " + std::to_string(B) + "; a group has 0 to " + std::to_string(FQ3_STAGE_GROUP_MAX) + " rows");
+    if (B == 0) return 0;
+    if (!objs || !pcm || !n_in || !final || !out || !capacity_bytes || !n_frames || !n_bytes_dev)
+        return fq3_fail_(FQ3_EINVAL, "fq3_flac_push_group: null array");
+    for (int b = 0; b < B; ++b) {
+        if (!objs[b]) return fq3_fail_(FQ3_EINVAL, "fq3_flac_push_group: row " + std::to_string(b) + ": null object");
+        for (int c = 0; c < b; ++c)
+            if (objs[c] == objs[b]) return fq3_fail_(FQ3_EINVAL, "fq3_flac_push_group: rows " + std::to_string(c) + " and " + std::to_string(b) + " are the same object");
+        if (objs[b]->p.rate != objs[0]->p.rate || objs[b]->p.block != objs[0]->p.block)
+            return fq3_fail_(FQ3_EINVAL, "fq3_flac_push_group: row " + std::to_string(b) + " has another design (sample rate, block size) than row 0");
+    }
+    // every row is checked and planned before any object moves
+    static_assert(FQ3_STAGE_GROUP_MAX == kFlacGroupMax, "the header's limit is the descriptor table's size");
+    Push q[FQ3_STAGE_GROUP_MAX];
+    int64_t rounds = 1;
+    for (int b = 0; b < B; ++b) {
+        const std::string who = "fq3_flac_push_group: row " + std::to_string(b);
+        if (!n_bytes_dev[b]) return fq3_fail_(FQ3_EINVAL, who + ": null n_bytes_dev");
+        if (int rc = check_push_(who, objs[b], pcm[b], n_in[b], final[b], out[b], capacity_bytes[b], &q[b])) return rc;
+        const int64_t need = (q[b].frames + kFlacBatch - 1) / kFlacBatch;
+        if (need > rounds) rounds = need;
+    }
+    const Plan& p = objs[0]->p;
+    hipStream_t s = (hipStream_t)stream;
+    FlacGroupArgs g{};
+    g.block = p.block; g.stride = objs[0]->stride; g.rate_code = p.rate_code; g.rate_hz = p.rate;
+    for (int b = 0; b < B; ++b) {
+        const fq3_flac* f = objs[b];
+        FlacGroupRow& r = g.rows[b];
+        r.pcm = pcm[b]; r.tail = f->tail[f->cur]; r.tail_next = f->tail[f->cur ^ 1];
+        r.stage = f->stage; r.sizes = f->sizes; r.totals = f->totals;
+        r.n_bytes = n_bytes_dev[b]; r.out = out[b];
+        r.avail = q[b].avail; r.tail_from = q[b].frames * p.block; r.tail_n = f->tail_n;
+    }
+    for (int64_t round = 0; round < rounds; ++round) {
+        const int64_t done = round * kFlacBatch;
+        g.first = done * p.block;
+        g.round = (int)round;                                 // below 2^25: a stream has at most 2^31 frames
+        int enc = 0, gat = 0;
+        for (int b = 0; b < B; ++b) {
+            FlacGroupRow& r = g.rows[b];
+            const int64_t frames = q[b].frames, left = frames - done;
+            const int nb = (int)(left < 0 ? 0 : left < kFlacBatch ? left : kFlacBatch);
+            const bool last = round == (frames > 0 ? (frames - 1) / kFlacBatch : 0);
+            r.n_frames = nb;
+            r.frame0 = (uint32_t)(objs[b]->frame + done);
+            r.tail_len = last && q[b].copy_tail ? q[b].keep : 0;
+            g.enc_wg0[b] = enc;
+            g.gat_wg0[b] = gat;
+            enc += nb + (r.tail_len > 0 ? 1 : 0);
+            gat += nb + (round == 0 && frames == 0 ? 1 : 0);  // a push without a frame: the workgroup that writes its byte count of 0
+        }
+        for (int b = B; b < FQ3_STAGE_GROUP_MAX; ++b) { g.enc_wg0[b] = enc; g.gat_wg0[b] = gat; }
+        if (enc > 0) {
+            hipLaunchKernelGGL(flac_encode_group_kernel, dim3(enc), dim3(kFlacThreads), 0, s, g);
+            FHIP(hipGetLastError());
+        }
+        if (gat > 0) {
+            hipLaunchKernelGGL(flac_gather_group_kernel, dim3(gat), dim3(kFlacGatherThreads), 0, s, g);
+            FHIP(hipGetLastError());
+        }
+    }
+    for (int b = 0; b < B; ++b) {
+        n_frames[b] = q[b].frames;
+        commit_push_(objs[b], q[b], n_in[b], final[b]);
+    }
     return 0;
 }

@@ -17,7 +17,7 @@ LIB_PATH = os.path.join(os.path.dirname(_HERE), "lib", "libfq3hip.so")
 
 FQ3_BF16, FQ3_F32, FQ3_BF16X2 = 0, 1, 2
 FQ3_PCM_F32, FQ3_PCM_S16, FQ3_PCM_MULAW, FQ3_PCM_ALAW = 0, 1, 2, 3
-FQ3_STAGE_GROUP_MAX = 32          # rows of one fq3_audio_out_push_group / fq3_tsm_push_group / fq3_leveller_push_group / fq3_limit_push_group
+FQ3_STAGE_GROUP_MAX = 32          # rows of one fq3_audio_out_push_group / fq3_tsm_push_group / fq3_flac_push_group / fq3_leveller_push_group / fq3_limit_push_group
 FQ3_OK, FQ3_EINVAL, FQ3_EHIP, FQ3_ESTATE, FQ3_ETOOLONG, FQ3_EUNSUPPORTED, FQ3_ENOMEM = 0, -1, -2, -3, -4, -5, -6
 
 vp = C.c_void_p
@@ -243,6 +243,9 @@ SIGNATURES = {
     "fq3_flac_destroy": (C.c_int, [vp]),
     "fq3_flac_reset": (C.c_int, [vp, vp]),
     "fq3_flac_push": (C.c_int, [vp, vp, C.c_int64, C.c_int, vp, C.c_int64, C.POINTER(C.c_int64), vp, vp]),
+    # as the two groups above, with one more host array in front of the stream: the rows' device int64 byte counts
+    "fq3_flac_push_group": (C.c_int, [C.POINTER(vp), C.c_int, C.POINTER(vp), C.POINTER(C.c_int64), C.POINTER(C.c_int),
+                                      C.POINTER(vp), C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(vp), vp]),
     "fq3_join_bound": (C.c_int64, [C.POINTER(JoinConfig), C.c_int64, C.c_int64]),
     "fq3_join_create": (C.c_int, [C.POINTER(JoinConfig), C.POINTER(vp)]),
     "fq3_join_destroy": (C.c_int, [vp]),

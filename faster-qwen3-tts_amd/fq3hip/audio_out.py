@@ -414,14 +414,30 @@ def _push_group(stages, pcms, finals):
                               [n for _p, n in ins], [int(r.final) for r in members], [base + r.off if r.need else None for r in members],
                               [r.need for r in members], sp)
             assert got == [r.need for r in members]
-        # FLAC: frame sizes depend on the data, so every flac row's s16 samples go through its own launch pair, into this buffer as well
+        # FLAC: the s16 samples of the flac rows of one (rate, block size) go through ONE launch pair, into this buffer as well: frame
+        # sizes depend on the data, so every row has room for its frames at their bound, behind the 8-byte count the device fills in
+        flac_buckets: dict = {}
         for r in rows:
             if r.flac_off is not None:
-                got = C.c_int64()
-                _lib.check(lib.fq3_flac_push(r.st._flac, C.c_void_p(base + r.off if r.need else None), r.need, int(r.final),
-                                             C.c_void_p(base + r.flac_off + 8 if r.flac_cap else None), r.flac_cap, C.byref(got),
-                                             C.c_void_p(base + r.flac_off), sp))
-                assert got.value == r.frames
+                flac_buckets.setdefault((r.st.out_rate, r.st.flac_block), []).append(r)
+        for members in flac_buckets.values():
+            for i in range(0, len(members), GROUP_MAX):
+                part = members[i: i + GROUP_MAX]
+                B = len(part)
+                if B == 1:                                     # one row: the single push is the shorter way (3 us)
+                    r, one = part[0], C.c_int64()
+                    _lib.check(lib.fq3_flac_push(r.st._flac, C.c_void_p(base + r.off if r.need else None), r.need, int(r.final),
+                                                 C.c_void_p(base + r.flac_off + 8 if r.flac_cap else None), r.flac_cap, C.byref(one),
+                                                 C.c_void_p(base + r.flac_off), sp))
+                    assert one.value == r.frames
+                    continue
+                got = (C.c_int64 * B)()
+                _lib.check(lib.fq3_flac_push_group(
+                    (C.c_void_p * B)(*[r.st._flac.value for r in part]), B, (C.c_void_p * B)(*[base + r.off if r.need else None for r in part]),
+                    (C.c_int64 * B)(*[r.need for r in part]), (C.c_int * B)(*[int(r.final) for r in part]),
+                    (C.c_void_p * B)(*[base + r.flac_off + 8 if r.flac_cap else None for r in part]), (C.c_int64 * B)(*[r.flac_cap for r in part]),
+                    got, (C.c_void_p * B)(*[base + r.flac_off for r in part]), sp))
+                assert list(got) == [r.frames for r in part]
         for r in rows:
             if r.n:
                 r.x.record_stream(s)
@@ -439,8 +455,9 @@ def push_group(stages, pcms, finals) -> list:
     with ONE time-scale launch for the rows that have a speed and ONE resample + encode launch per distinct (rates, encoding) instead
     of one or two launches per row (``fq3_tsm_push_group`` / ``fq3_audio_out_push_group``, up to 32 rows a call).  The stages share a
     device and a stream; ``pcms[i]`` is a float32 device vector or None.  All outputs lie in one device buffer, the rows of a design
-    back to back.  A ``flac`` row takes its s16 half in the group launch and then its own ``fq3_flac_push``; as in ``push``, reading
-    how many bytes its frames took synchronises the stream (once for the call)."""
+    back to back.  The ``flac`` rows take their s16 half in the group launch and then ONE launch pair per (rate, block size)
+    (``fq3_flac_push_group``; section 4.20; a lone row keeps its ``fq3_flac_push``); as in ``push``, reading how many bytes their frames took synchronises the stream (once
+    for the call)."""
     buf, rows, s = _push_group(stages, pcms, finals)
     out = []
     lens = None

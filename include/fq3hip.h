@@ -659,6 +659,27 @@ int fq3_flac_reset(fq3_flac* f, void* stream);
  * stay valid until the stream has run them.  After a final push: FQ3_ESTATE until fq3_flac_reset. */
 int fq3_flac_push(fq3_flac* f, const int16_t* pcm, int64_t n_in, int final, uint8_t* out, int64_t capacity_bytes,
                   int64_t* n_frames, int64_t* n_bytes_dev, void* stream);
+/* The FLAC stage for a GROUP of streams, as fq3_audio_out_push_group / fq3_tsm_push_group above and with their conventions.  Every
+ * array is a HOST array of B entries (n_bytes_dev: B pointers to DEVICE int64s); row b is exactly
+ *     fq3_flac_push(objs[b], pcm[b], n_in[b], final[b], out[b], capacity_bytes[b], &n_frames[b], n_bytes_dev[b], stream)
+ *   Launches.        Frames [64 r, 64 r + 64) of every row that has them are encoded in ONE launch and gathered in ONE more: a launch
+ *                    pair per round r, and the usual chunk needs one round.  A launch no row needs is not made.
+ *   Equality.        The bytes row b writes, n_frames[b], *n_bytes_dev[b] and the state objs[b] is left in are bit for bit those of
+ *                    the single push: a frame is encoded by the same device code.  Group and single pushes mix freely on one object;
+ *                    membership and order of a group may change from push to push.
+ *   All or nothing.  Every row is checked before any object changes (null pointers, negative lengths, capacity below n_frames[b] *
+ *                    max_frame_bytes, the 2^50-sample and 2^31-frame bounds, FQ3_ESTATE after a final push): on an error the code of
+ *                    the first offending row is returned, the message names the row, nothing is launched and no object has moved.
+ *   Limits.          B == 0: returns 0, does nothing.  B < 0, B > FQ3_STAGE_GROUP_MAX, a null array, a null object or the same object
+ *                    twice in one call: FQ3_EINVAL.
+ *   Shared design.   All objects have the same (sample_rate, block size), else FQ3_EINVAL.
+ *                    These, and every check above, are answered before any HIP call.
+ *   Empty rows.      A row that completes no frame costs no encode workgroup (one if it has a tail to copy) and one gather workgroup
+ *                    that sets *n_bytes_dev[b] to 0.
+ *   Asynchrony.      No host synchronisation and no copy: the rows' descriptors travel in the launches' argument blocks. */
+int fq3_flac_push_group(fq3_flac* const* objs, int B, const int16_t* const* pcm, const int64_t* n_in, const int* final,
+                        uint8_t* const* out, const int64_t* capacity_bytes, int64_t* n_frames, int64_t* const* n_bytes_dev,
+                        void* stream);
 
 /* ---- Segment join: the sentences of a long text become one PCM stream on the device ---------------------------------------------
  * In FRONT of the time-scale stage: the stream is a sequence of SEGMENTS (float32 at in_rate, the vocoder's waveforms of the pieces

@@ -21,7 +21,13 @@ pair, plus both forms with the rows landing on the host (one pinned copy against
 synchronise), next to the bf16x2 vocoder's windowed chunk decode for the same group (``decode_tensor_batch`` over B x [25 + 8] frames,
 the protocol of profiles/codec_stream.json).  The two forms' bytes are compared before anything is timed.  Writes
 profiles/stage_group.json.
-usage: audio_out_probe.py [--speed | --encoding flac [--recordings DIR] | --group B] [runs=100] [out.json]"""
+With --encoding flac --group B: the FLAC stage of a lock-step group.  (a) The stage ALONE: 1, 8 and B rows, one streaming chunk of s16
+samples each, pushed into running streams as ONE fq3_flac_push_group (a launch pair) and as single fq3_flac_push calls (a launch pair per
+row), each repeat between its own event pair.  (b) The whole chain with the rows landing on the host, ``push_group_host`` on 8 and B flac
+rows, with the group entry and with the per-row launch sequence it replaces (host clock; the call ends in a synchronise).  The forms
+alternate in three rounds; the medians, every round's median and their spread are written to profiles/flac_group.json.  The forms' bytes
+are compared before anything is timed.
+usage: audio_out_probe.py [--speed | --encoding flac [--recordings DIR | --group B] | --group B] [runs=100] [out.json]"""
 import json
 import os
 import statistics
@@ -308,6 +314,140 @@ def main_group(B, argv):
     print(json.dumps(res, indent=1))
 
 
+class _PerRowFlac:
+    """the library with fq3_flac_push_group answered by one fq3_flac_push per row: the launch sequence of the commit before the group
+    form (a launch pair per flac row behind the grouped s16 launch), rebuilt in this run so that both forms see the same machine"""
+
+    def __init__(self, lib):
+        self._lib = lib
+
+    def __getattr__(self, name):
+        return getattr(self._lib, name)
+
+    def fq3_flac_push_group(self, objs, B, pcm, n_in, final, out, caps, n_frames, n_bytes, sp):
+        import ctypes as C
+        for b in range(B):
+            got = C.c_int64()
+            rc = self._lib.fq3_flac_push(objs[b], pcm[b], n_in[b], final[b], out[b], caps[b], C.byref(got), n_bytes[b], sp)
+            if rc:
+                return rc
+            n_frames[b] = got.value
+        return 0
+
+
+def main_flac_group(N, argv):
+    """(a) the FLAC stage alone: B rows, one streaming chunk of s16 samples each, pushed into RUNNING streams (never final: the tails
+    carry over, a push completes 13 or 14 frames of 1152), as B fq3_flac_push calls and as ONE fq3_flac_push_group, device time between
+    events; (b) the whole chain with the rows on the host, ``push_group_host`` on flac rows, against the per-row launch sequence."""
+    import ctypes as C
+    import time
+    runs = max(20, int(argv[0])) if argv else 40
+    out_path = argv[1] if len(argv) > 1 else os.path.join(ROOT, "profiles", "flac_group.json")
+    rounds = 3
+    g = torch.Generator().manual_seed(3)
+    n = 8 * SAMPLES_PER_FRAME
+    lib = ao._lib.load()
+    t = torch.arange(n, dtype=torch.float64) / 24000.0
+    voiced = sum(0.25 / h * torch.sin(2 * torch.pi * 140.0 * h * t) for h in range(1, 9)) * torch.exp(-3.0 * (t % 0.16))
+    rows_f32 = [(voiced * (0.5 + 0.5 * b / N) + 0.003 * torch.randn(n, generator=g)).float().cuda() for b in range(N)]
+    rows_s16 = [ao.AudioOut(ao.AudioOutSpec(None, "s16"), 24000, "cuda").push(x, final=True) for x in rows_f32]
+    block, bound = ao.flac_design(24000)
+    cap = (n // block + 1) * bound
+    sp = lambda: C.c_void_p(torch.cuda.current_stream().cuda_stream)
+
+    def events(fn):
+        pairs = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(runs)]
+        for e0, e1 in pairs:
+            e0.record(); fn(); e1.record()
+        torch.cuda.synchronize()
+        return [e0.elapsed_time(e1) for e0, e1 in pairs]
+
+    def clock(fn):
+        out = []
+        for _ in range(runs):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter(); fn(); out.append((time.perf_counter() - t0) * 1000)
+        return out
+
+    def measure(cases, how):
+        for fn in cases.values():
+            for _ in range(10):
+                fn()
+        torch.cuda.synchronize()
+        samples = {k: [] for k in cases}
+        for _round in range(rounds):                              # alternating: the forms see the same machine
+            for k, fn in cases.items():
+                samples[k].append(how(fn))
+        out = {}
+        for k, rs in samples.items():
+            per_round = [statistics.median(r) for r in rs]
+            out[k] = {"median_ms": round(statistics.median(v for r in rs for v in r), 4), "per_round_ms": [round(v, 4) for v in per_round],
+                      "spread_ms": round(max(per_round) - min(per_round), 4), "min_ms": round(min(v for r in rs for v in r), 4)}
+        return out
+
+    res = {"device": torch.cuda.get_device_name(0), "runs_per_round": runs, "rounds": rounds, "warmup": 10, "rate": 24000, "block": block,
+           "n_in_per_row": n, "input": "speech-like: decaying harmonics of 140 Hz, noise at -50 dB, another level per row",
+           "unit": "ms per group of rows: median over all repeats; per_round: the median of each alternating round; spread: the largest "
+                   "minus the smallest round median", "stage_alone": [], "whole_chain_rows_on_host": [], "notes": []}
+
+    # (a)
+    for B in sorted({1, 8, N}):
+        objs = [[ao.AudioOut(ao.AudioOutSpec(None, "flac"), 24000, "cuda") for _ in range(B)] for _form in range(2)]
+        bufs = [torch.zeros(B * (8 + cap), dtype=torch.uint8, device="cuda") for _form in range(2)]
+        outs = [[buf.data_ptr() + b * (8 + cap) for b in range(B)] for buf in bufs]
+        h_group = (C.c_void_p * B)(*[st._flac.value for st in objs[0]])
+        pcm = (C.c_void_p * B)(*[x.data_ptr() for x in rows_s16[:B]])
+        lens, finals, caps, got = (C.c_int64 * B)(*([n] * B)), (C.c_int * B)(*([0] * B)), (C.c_int64 * B)(*([cap] * B)), (C.c_int64 * B)()
+        g_out, g_nb = (C.c_void_p * B)(*[p + 8 for p in outs[0]]), (C.c_void_p * B)(*outs[0])
+
+        def group():
+            assert lib.fq3_flac_push_group(h_group, B, pcm, lens, finals, g_out, caps, got, g_nb, sp()) == 0
+
+        def singles():
+            one, s = C.c_int64(), sp()
+            for b, st in enumerate(objs[1]):
+                assert lib.fq3_flac_push(st._flac, pcm[b], n, 0, C.c_void_p(outs[1][b] + 8), cap, C.byref(one), C.c_void_p(outs[1][b]), s) == 0
+
+        group(); singles()
+        torch.cuda.synchronize()
+        assert torch.equal(bufs[0], bufs[1]), "the group form and the single pushes must write the same bytes"
+        m = measure({"fq3_flac_push_group": group, "single fq3_flac_push calls": singles}, events)
+        gm, sm = m["fq3_flac_push_group"], m["single fq3_flac_push calls"]
+        spread = max(gm["spread_ms"], sm["spread_ms"])
+        res["stage_alone"].append({"rows": B, "how": "device events around the call(s)", "launches": {"group": 2, "singles": 2 * B},
+                                   "forms": m, "spread_ms": spread, "singles_over_group": round(sm["median_ms"] / gm["median_ms"], 2)})
+        if B == N:
+            ok = sm["median_ms"] - gm["median_ms"] > spread
+            res["notes"].append(f"B = {B}: the group form takes {gm['median_ms']:.3f} ms, the single pushes {sm['median_ms']:.3f} ms, spread {spread:.3f} ms: "
+                                + ("faster by more than the spread" if ok else "NOT faster by more than the spread"))
+        if B == 1:
+            ok = gm["median_ms"] - sm["median_ms"] <= spread
+            res["notes"].append(f"B = 1: the group form takes {gm['median_ms']:.3f} ms, the single push {sm['median_ms']:.3f} ms, spread {spread:.3f} ms: "
+                                + ("not slower by more than the spread" if ok else "SLOWER by more than the spread: a bucket of one row belongs to the single push"))
+
+    # (b)
+    for B in sorted({8, N} - {1}):
+        stages = [[ao.AudioOut(ao.AudioOutSpec(None, "flac"), 24000, "cuda") for _ in range(B)] for _form in range(2)]
+        stages[1][0]._lib = _PerRowFlac(lib)                      # ``_push_group`` takes the library from its first stage
+        pcms, no = rows_f32[:B], [False] * B
+        a, b = ao.push_group_host(stages[0], pcms, no), ao.push_group_host(stages[1], pcms, no)
+        assert all((u == v).all() for u, v in zip(a, b)), "both launch sequences must give the same bytes"
+        m = measure({"push_group_host, fq3_flac_push_group": lambda: ao.push_group_host(stages[0], pcms, no),
+                     "push_group_host, one fq3_flac_push per row": lambda: ao.push_group_host(stages[1], pcms, no)}, clock)
+        gm, sm = m["push_group_host, fq3_flac_push_group"], m["push_group_host, one fq3_flac_push per row"]
+        res["whole_chain_rows_on_host"].append({"rows": B, "how": "host clock around the call (it ends in a synchronise)",
+                                                "launches": {"group": 3, "per row": 1 + 2 * B}, "forms": m,
+                                                "per_row_over_group": round(sm["median_ms"] / gm["median_ms"], 2)})
+    res["notes"].append("every figure includes the host side of the call (ctypes; in the whole chain also Python and the allocations); the per-row "
+                        "form of the whole chain is the earlier launch sequence rebuilt in this run (the library's group entry answered by one "
+                        "single push per row), not a second build")
+    os.makedirs(os.path.dirname(out_path) or ".", exist_ok=True)
+    with open(out_path, "w") as f:
+        json.dump(res, f, indent=1)
+        f.write("\n")
+    print(json.dumps(res, indent=1))
+
+
 def vocoder_group(g, B, runs):
     """the yardstick for a group: (median single call, back to back per call) ms of the bf16x2 vocoder's windowed chunk decode of B rows"""
     from fq3hip.codec import HipSpeechTokenizer
@@ -325,7 +465,12 @@ def main():
     args = sys.argv[1:]
     if "--group" in args:
         i = args.index("--group")
-        return main_group(int(args[i + 1]), args[:i] + args[i + 2:])
+        B, rest = int(args[i + 1]), args[:i] + args[i + 2:]
+        if "--encoding" in rest:
+            j = rest.index("--encoding")
+            assert rest[j + 1] == "flac", "--encoding flac is the only encoding with a probe of its own"
+            return main_flac_group(B, rest[:j] + rest[j + 2:])
+        return main_group(B, rest)
     if "--encoding" in args:
         i = args.index("--encoding")
         assert args[i + 1] == "flac", "--encoding flac is the only encoding with a probe of its own"

@@ -1,5 +1,6 @@
 // Segment join (fq3_join.hip): leading / trailing silence of every segment removed and a pause of zeros put behind it, on the device,
-// one launch per push, ONE workgroup per launch (the hops of a stream form a chain: what a hop's fate is depends on the hops before it).
+// one launch per push, ONE workgroup per stream (the hops of a stream form a chain: what a hop's fate is depends on the hops before it;
+// the streams of a group do not depend on each other: join_group_kernel walks up to 32 of them side by side, a workgroup each).
 //
 // The stream is cut into hops of H = in_rate / 100 samples, counted from the start of each segment.  A hop is ACTIVE when some sample
 // has |x| >= threshold.  Between pushes the object keeps, on the device, the samples whose fate is still open -- they are always the
@@ -80,7 +81,9 @@ __device__ __forceinline__ void join_zero(float* __restrict__ dst, int64_t n, in
     if (done + tid < n) dst[done + tid] = 0.0f;
 }
 
-__global__ void __launch_bounds__(kJoinThreads) join_kernel(const JoinArgs a) {
+// One push of one stream by one workgroup: the body of the single and of the group kernel, so that a row of a group is the single
+// push instruction for instruction.
+__device__ __forceinline__ void join_push_body(const JoinArgs& a) {
     __shared__ __align__(16) int act[kJoinSlice];
     __shared__ int64_t e_src[kJoinSlice + 2], e_len[kJoinSlice + 2], e_dst[kJoinSlice + 2];      // e_src < 0: zeros
     __shared__ int s_ne, s_phase, s_q, s_rel;
@@ -204,6 +207,24 @@ __global__ void __launch_bounds__(kJoinThreads) join_kernel(const JoinArgs a) {
         a.state[0] = s_phase; a.state[1] = s_q; a.state[2] = s_rel;
         *a.n_out = s_dst;
     }
+}
+
+__global__ void __launch_bounds__(kJoinThreads) join_kernel(const JoinArgs a) { join_push_body(a); }
+
+// The pushes of up to kJoinGroupMax streams in ONE launch (fq3_join_push_group): workgroup b runs row b through the body above.  The
+// rows' descriptors travel in the argument block (32 x 96 bytes, inside the 4 KB that fq3_batch.hip notes as the limit), so there is
+// no table to copy; rows share nothing, each writes its own out / n_out / state / pend_next.
+constexpr int kJoinGroupMax = 32;
+struct JoinGroupArgs {
+    JoinArgs row[kJoinGroupMax];
+    int B;
+};
+static_assert(sizeof(JoinGroupArgs) <= 3200, "the group's descriptors travel as launch arguments: keep them well inside 4 KB");
+
+__global__ void __launch_bounds__(kJoinThreads) join_group_kernel(const JoinGroupArgs g) {
+    const int b = blockIdx.x;
+    if (b >= g.B) return;                                          // (uniform over the workgroup: no barrier is skipped by a part of it)
+    join_push_body(g.row[b]);
 }
 
 }  // namespace fq3

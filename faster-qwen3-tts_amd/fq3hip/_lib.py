@@ -251,6 +251,9 @@ SIGNATURES = {
     "fq3_join_destroy": (C.c_int, [vp]),
     "fq3_join_reset": (C.c_int, [vp, vp]),
     "fq3_join_push": (C.c_int, [vp, vp, C.c_int64, C.c_int, C.c_int64, vp, C.c_int64, vp, vp]),
+    # every array a host array of B entries; the last one holds the rows' device int64 counts
+    "fq3_join_push_group": (C.c_int, [C.POINTER(vp), C.c_int, C.POINTER(vp), C.POINTER(C.c_int64), C.POINTER(C.c_int), C.POINTER(C.c_int64),
+                                      C.POINTER(vp), C.POINTER(C.c_int64), C.POINTER(vp), vp]),
     "fq3_limit_design": (C.c_int, [C.c_int, C.c_double, C.c_double, C.c_double, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_float),
                                    C.POINTER(C.c_float), C.POINTER(C.c_int)]),
     "fq3_limit_count": (C.c_int64, [C.c_int, C.c_double, C.c_int64, C.c_int]),

@@ -282,7 +282,21 @@ def cmd_serve(args, model=None, lines=None):
             continue
         start = time.perf_counter()
         levelled = any(getattr(args, k, None) is not None for k in ("gain_db", "limiter_db", "level"))
-        if len(pending) > 1 and args.mode == "clone" and not levelled:    # (--gain-db / --limiter-db: line by line, as before)
+        if len(pending) > 1 and getattr(args, "long", False) and args.mode in ("clone", "custom") and not levelled:
+            # --long: every line is a text of any length; the segments of all waiting lines share the lanes of ONE lock-step run
+            from .long_form import LongFormSpec
+            spec = _output_spec(args)
+            lkw = dict(lanes=args.lanes, long_form=LongFormSpec(max_chars=args.max_chars), seeds=getattr(args, "seed", None),
+                       **_gen_kwargs(args), **({} if spec is None else dict(output=spec)))
+            if args.mode == "clone":
+                results = model.generate_long_voice_clone_batch(pending, language=args.language, ref_audio=args.ref_audio,
+                                                                ref_text=args.ref_text, xvec_only=args.xvec_only,
+                                                                non_streaming_mode=args.non_streaming_mode, **lkw)
+            else:
+                results = model.generate_long_custom_voice_batch(pending, speaker=args.speaker, language=args.language,
+                                                                 instruct=args.instruct, **lkw)
+            outs = [(r[0][0], r[1]) for r in results]
+        elif len(pending) > 1 and args.mode == "clone" and not levelled:    # (--gain-db / --limiter-db: line by line, as before)
             # --out-rate / --encoding / --speed: the lines decoded together go through the output stage together (``output=``)
             spec = _output_spec(args)
             results = model.generate_voice_clone_batch(pending, language=args.language, ref_audio=args.ref_audio, ref_text=args.ref_text,
@@ -390,6 +404,10 @@ def build_parser():
     s.add_argument("--speaker"); s.add_argument("--instruct")
     s.add_argument("--output-dir", default="outputs")
     s.add_argument("--lanes", type=int, default=1, help="decode up to N waiting lines in lock-step (clone mode)")
+    s.add_argument("--long", action="store_true",
+                   help="every line is a text of any length (long form): with --lanes N the segments of up to N waiting lines share "
+                        "the N lanes of one lock-step run (clone and custom mode)")
+    s.add_argument("--max-chars", type=int, default=240, metavar="N", help="--long: the splitter's budget per segment")
     s.set_defaults(func=cmd_serve)
     return p
 

@@ -6,6 +6,8 @@ trailing silence removed, a pause of zeros per boundary) in front of the existin
 ``LongFormSpec``   the splitter's budget, the pauses and the join parameters; validates without a GPU
 ``SegmentJoin``    one output stream's join state on a device
 ``OrderedJoin``    the ordered hand-over: chunks of later segments wait as device tensors until the earlier segments have ended
+``push_group``     the pushes of many ``SegmentJoin``s in one launch and one copy of their lengths
+``OrderedJoinSet`` many texts' ordered hand-overs fed by one lock-step run: a round of pushes per group call
 
 The default ``threshold``, ``max_chars`` and pauses are NOT measured on real voices (no checkpoint was available); they are
 parameters for that reason."""
@@ -285,6 +287,173 @@ class SegmentJoin:
         n = int(host[:2].view(np.int64)[0])
         self.n_out += n
         return host[_HEAD: _HEAD + n]
+
+
+GROUP_MAX = _lib.FQ3_STAGE_GROUP_MAX
+
+
+def push_group(joins, pcms, ends, pauses) -> list:
+    """``[joins[i].push(pcms[i], ends[i], pauses[i]) for i]`` -- the same device tensors, bit for bit, and the same state and counters
+    on every object -- with ONE launch of one workgroup per row instead of one launch per row (``fq3_join_push_group``, up to 32 rows
+    a call), and ONE synchronisation per call instead of one per row: the rows' lengths lie side by side in one
+    device int64 tensor and reach pinned memory in one copy behind one event.  The joins share a device and a stream and appear once;
+    they may differ in their configuration.  Every row's room is its ``bound()``; the rows of a call lie in one device buffer, each
+    starting on a 16-byte boundary.  A lone row takes its single push.  All or nothing over ANY number of rows: every check the
+    library makes per row (an ended stream, ``end``, the length, the pause) is made here for all rows before the first call."""
+    joins, pcms, ends, pauses = list(joins), list(pcms), [int(e) for e in ends], [int(p) for p in pauses]
+    if not (len(joins) == len(pcms) == len(ends) == len(pauses)):
+        raise ValueError("push_group: one pcm, one end and one pause per join")
+    if len(set(map(id, joins))) != len(joins):
+        raise ValueError("push_group: the same join twice in one call")
+    if not joins:
+        return []
+    if len(joins) == 1:
+        return [joins[0].push(pcms[0], ends[0], pauses[0])]
+    for j, e in zip(joins, ends):
+        # a call takes 32 rows, so what the library would refuse in a later call is refused here, before the first one moves anything:
+        # an ended stream gets the library's own answer (FQ3_ESTATE), as ``push`` gives it; lengths and pauses are checked by
+        # ``bound()`` below, for every row, in front of the first launch
+        if not 0 <= e <= 2:
+            raise ValueError("push_group: end must be 0, 1 or 2")
+        if j.finished:
+            j.push(None, 0, 0)
+    lib, dev, s = joins[0]._lib, joins[0].dev, joins[0]._stream()
+    for j in joins:
+        if j.dev != dev or j._stream().cuda_stream != s.cuda_stream:
+            raise ValueError("push_group: the joins of one call share a device and a stream")
+    out: list = []
+    with torch.cuda.device(dev), torch.cuda.stream(s):
+        xs = []
+        for j, pcm in zip(joins, pcms):
+            x = j._empty if pcm is None else pcm.reshape(-1)
+            if x.dtype != torch.float32 or x.device != dev or not x.is_contiguous():
+                x = x.to(device=dev, dtype=torch.float32).contiguous()
+            xs.append(x)
+        for j, p in zip(joins, pauses):
+            j.bound(0, p)                                          # (the pause range is checked whatever ``end`` says, as in the C call)
+        caps = [j.bound(int(x.numel()), p if e == 1 else 0) for j, x, e, p in zip(joins, xs, ends, pauses)]
+        offs, cursor = [], 0
+        for cap in caps:
+            offs.append(cursor)
+            cursor += (cap + 3) // 4 * 4
+        buf = torch.empty(cursor, dtype=torch.float32, device=dev)
+        lens = torch.empty(len(joins), dtype=torch.int64, device=dev)
+        base, lens_base, sp = buf.data_ptr(), lens.data_ptr(), C.c_void_p(s.cuda_stream)
+        for a in range(0, len(joins), GROUP_MAX):
+            b = min(len(joins), a + GROUP_MAX)
+            B = b - a
+            _lib.check(lib.fq3_join_push_group(
+                (C.c_void_p * B)(*[j._h.value for j in joins[a:b]]), B,
+                (C.c_void_p * B)(*[x.data_ptr() if x.numel() else None for x in xs[a:b]]),
+                (C.c_int64 * B)(*[int(x.numel()) for x in xs[a:b]]), (C.c_int * B)(*ends[a:b]), (C.c_int64 * B)(*pauses[a:b]),
+                (C.c_void_p * B)(*[base + 4 * o for o in offs[a:b]]), (C.c_int64 * B)(*caps[a:b]),
+                (C.c_void_p * B)(*[lens_base + 8 * i for i in range(a, b)]), sp))
+            for j, x, e in zip(joins[a:b], xs[a:b], ends[a:b]):        # the call was accepted as a whole: these rows have moved
+                if x.numel():
+                    x.record_stream(s)
+                j.n_in += int(x.numel())
+                j.finished = j.finished or e == 2
+        host = torch.empty(len(joins), dtype=torch.int64, pin_memory=True)
+        host.copy_(lens, non_blocking=True)
+        landed = torch.cuda.Event()
+        landed.record(s)
+    landed.synchronize()                                           # the one synchronisation: how many samples every row settled
+    for j, o, n in zip(joins, offs, host.tolist()):
+        j.n_out += int(n)
+        out.append(buf[o: o + int(n)])
+    return out
+
+
+class OrderedJoinSet:
+    """``T`` ordered hand-overs (one ``OrderedJoin`` per text, each with its own join, pauses, gains and stages) fed by ONE lock-step
+    run.  ``feed_group([(text, segment, pcm, last), ...])`` takes what a vocoder group produced, in any interleaving of texts and
+    segments, and returns the pieces ``(text, segment, tensor, stream ended)`` that became ready.  Per text the rule is
+    ``OrderedJoin.feed``'s: chunks of segment ``k + 1`` wait until ``k`` has ended, and a text's pieces come strictly in text order.
+    Consecutive ready chunks of one segment go out as ONE push (the join does not depend on how a segment is cut into pushes); round
+    ``r`` then takes the r-th ready push of every text through ONE ``push_group`` and, behind it, through the group call of every
+    stage the texts have: the gains, ``leveller.push_group``, ``limiter.push_group``, ``audio_out.push_group``.  A join appears at
+    most once per round.  ``push_group`` (internal, tests): what joins a round's rows."""
+
+    def __init__(self, ordered: List["OrderedJoin"], push_group=None):
+        self.ordered = list(ordered)
+        if len(set(id(o.join) for o in self.ordered)) != len(self.ordered):
+            raise ValueError("OrderedJoinSet: every text has its own join")
+        self._push_group = push_group
+        self.rounds = 0                                            # group calls made so far (diagnostics)
+
+    def _ready(self, oj: "OrderedJoin") -> list:
+        """what ``OrderedJoin.feed`` would push now: [(segment, pcm or None, last)], the ready chunks of a segment as one push"""
+        pushes = []
+        while oj.cur < oj.n and oj._wait[oj.cur]:
+            q, oj._wait[oj.cur] = oj._wait[oj.cur], []
+            chunks = [pcm.reshape(-1) for pcm, _last in q if pcm is not None and pcm.numel()]
+            pcm = None if not chunks else chunks[0] if len(chunks) == 1 else torch.cat(chunks)
+            done = q[-1][1]
+            pushes.append((oj.cur, pcm, done))
+            if not done:
+                break
+            oj.cur += 1
+        return pushes
+
+    def feed_group(self, items) -> list:
+        items = list(items)
+        for t, k, _pcm, _last in items:                            # every error before any text moves
+            if not 0 <= t < len(self.ordered):
+                raise ValueError(f"text {t} is not one of the {len(self.ordered)} texts")
+            oj = self.ordered[t]
+            if not 0 <= k < oj.n or k < oj.cur:
+                raise ValueError(f"text {t}: segment {k} is not open (current segment {oj.cur} of {oj.n})")
+        ended = {(t, k) for t, oj in enumerate(self.ordered) for k, w in enumerate(oj._wait) if any(last for _pcm, last in w)}
+        for t, k, _pcm, last in items:
+            if (t, k) in ended:
+                raise ValueError(f"text {t}: segment {k} was fed after its last chunk")
+            if last:
+                ended.add((t, k))
+        for t, k, pcm, last in items:
+            self.ordered[t]._wait[k].append((pcm, bool(last)))
+        ready = [(t, self._ready(oj)) for t, oj in enumerate(self.ordered)]
+        for oj in self.ordered:
+            oj.max_waiting = max(oj.max_waiting, sum(len(w) for w in oj._wait))
+        out = []
+        for r in range(max((len(p) for _t, p in ready), default=0)):
+            out.extend(self._round([(t, p[r]) for t, p in ready if len(p) > r]))
+        return out
+
+    def _round(self, rows) -> list:
+        """one push of each of ``rows``' texts -- [(text, (segment, pcm, last))] -- through the join and the stages, group by group"""
+        ojs = [self.ordered[t] for t, _p in rows]
+        ends = [0 if not last else (2 if k == oj.n - 1 else 1) for oj, (_t, (k, _pcm, last)) in zip(ojs, rows)]
+        join = self._push_group if self._push_group is not None else push_group
+        ys = join([oj.join for oj in ojs], [p[1] for _t, p in rows], ends,
+                  [oj.pauses[p[0]] if e == 1 else 0 for oj, (_t, p), e in zip(ojs, rows, ends)])
+        self.rounds += 1
+        finals = [e == 2 for e in ends]
+        for i, (oj, (_t, (k, _pcm, _last))) in enumerate(zip(ojs, rows)):
+            g = oj.gains[k] if isinstance(oj.gains, (list, tuple)) else oj.gains
+            if g is not None:
+                from .loudness import apply_gain
+                ys[i] = apply_gain(ys[i].contiguous(), g, oj.join.stream)
+
+        def through(stage_of, group):
+            at = [i for i, oj in enumerate(ojs) if stage_of(oj) is not None]
+            if at:
+                got = group([stage_of(ojs[i]) for i in at], [ys[i].contiguous() for i in at], [finals[i] for i in at])
+                for i, y in zip(at, got):
+                    ys[i] = y
+        if any(oj.leveller is not None for oj in ojs):
+            from .leveller import push_group as level_group
+            through(lambda oj: oj.leveller, level_group)
+        if any(oj.limiter is not None for oj in ojs):
+            from .limiter import push_group as limit_group
+            through(lambda oj: oj.limiter, limit_group)
+        if any(oj.audio_out is not None for oj in ojs):
+            from .audio_out import push_group as out_group
+            through(lambda oj: oj.audio_out, out_group)
+        return [(t, k, y, e == 2) for (t, (k, _pcm, _last)), y, e in zip(rows, ys, ends)]
+
+    @property
+    def finished(self) -> bool:
+        return all(oj.finished for oj in self.ordered)
 
 
 class OrderedJoin:

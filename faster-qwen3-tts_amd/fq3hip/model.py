@@ -1468,11 +1468,11 @@ class FasterQwen3TTS:
         if pool is not None and len(pool) < self.STAGE_POOL_MAX and not any(st is other for other in pool):
             pool.append(st)
 
-    def _one_shot_output(self, wav) -> Tuple[np.ndarray, int]:
-        """A whole utterance's waveform (device tensor or host array) through the output stage of the open context."""
+    def _one_shot_output(self, wav, spec=None) -> Tuple[np.ndarray, int]:
+        """A whole utterance's waveform (device tensor or host array) through the output stage of the open context (or of ``spec``)."""
         from .audio_out import AudioOut
         dev = torch.device(self.device) if not isinstance(self.device, torch.device) else self.device
-        stage = AudioOut(self._audio_spec, self.sample_rate, wav.device if hasattr(wav, "is_cuda") and wav.is_cuda else dev)
+        stage = AudioOut(self._audio_spec if spec is None else spec, self.sample_rate, wav.device if hasattr(wav, "is_cuda") and wav.is_cuda else dev)
         x = wav.flatten().float() if hasattr(wav, "cpu") else torch.from_numpy(np.ascontiguousarray(wav, dtype=np.float32).reshape(-1))
         out = stage.push_host(x.to(stage.dev), final=True)
         if stage.flac:                 # a whole FLAC file: its header carries the sample count
@@ -1829,7 +1829,7 @@ class FasterQwen3TTS:
         return out
 
     def _run_batch_streaming(self, prepared, gen_kwargs, chunk_size: int, lanes: int, rounds=None, stamp=None, seeds=None,
-                             count: Optional[int] = None, device_audio: bool = False, outputs=None):
+                             count: Optional[int] = None, device_audio: bool = False, outputs=None, group_marks: bool = False):
         """Streaming form of :meth:`_run_batch_full`: yields ``(index, audio_chunk, sample_rate, timing)`` for every
         ``chunk_size`` frames of any utterance -- per utterance exactly the chunks the single-utterance streaming entry point
         would produce (same windowing state machine).  ``timing``: ``chunk_index``, ``total_steps_so_far``, ``is_final``.
@@ -1841,7 +1841,9 @@ class FasterQwen3TTS:
         ``outputs`` (:meth:`_batch_outputs`): utterance i with a spec owns a pooled output stage; behind the gain and the limiter the
         rows of a launch group that have one go through ONE ``audio_out.push_group`` on the vocoder stream and reach pinned memory in
         one copy, and what is yielded for them is the encoded array and the output rate (``flac``: bytes, the stream header in the
-        utterance's first chunk).  What the stage held back leaves with the utterance's final event (``StreamingVocoder.flush``)."""
+        utterance's first chunk).  What the stage held back leaves with the utterance's final event (``StreamingVocoder.flush``).
+        ``group_marks`` (internal, long form over many texts): the events a poll hands out together carry ``group_end`` in their
+        timing, True on the last of them, so that the caller can take them through its own stages as one group."""
         self._refuse_streaming_loudness()
         if not device_audio:
             self._refuse_batch_audio_output()
@@ -1994,6 +1996,16 @@ class FasterQwen3TTS:
 
         rate_of = lambda r: self.sample_rate if outputs is None or outputs[r] is None else outputs[r].out_rate(self.sample_rate)  # noqa: E731
 
+        def marked(events):
+            if not group_marks:
+                return events
+            # the whole poll is collected before its first event goes out: with ``device_audio`` nothing is copied, so nothing is
+            # waited for; a caller that lands copies (``flush`` hands groups out as they land) would wait for the last of them here
+            events = list(events)
+            for i, ev in enumerate(events):
+                ev[1]["group_end"] = i == len(events) - 1
+            return events
+
         for head, source in pairs:
           for rid, codes, info in dec.run(head, source=source, chunk_frames=chunk_size):
             if rid not in vocs:
@@ -2041,9 +2053,9 @@ class FasterQwen3TTS:
                 add_job([rid, out_meta, tail, None])
                 n_chunks[rid] += 1
             if more <= 0:
-                for r, m, audio, _job in flush():
+                for r, m, audio, _job in marked(flush()):
                     yield r, audio, rate_of(r), out(r, m)
-          for r, m, audio, _job in flush():
+          for r, m, audio, _job in marked(flush()):
             yield r, audio, rate_of(r), out(r, m)
 
     @staticmethod
@@ -2292,15 +2304,17 @@ class FasterQwen3TTS:
         join_bound(self.sample_rate, spec.threshold, spec.lead_hops, spec.tail_hops, spec.hold_hops, 0, 0)
         return spec, segs
 
-    def _long_chain(self, spec, segs, stream, level_hops: Optional[int] = None):
-        """The request's ONE output stream: the join stage and, inside ``audio_output``, the chain behind it, all on ``stream``."""
+    def _long_chain(self, spec, segs, stream, level_hops: Optional[int] = None, output=None):
+        """The request's ONE output stream: the join stage and, inside ``audio_output`` (or with ``output``, a text's spec in the
+        many-text form), the chain behind it, all on ``stream``."""
         from .long_form import OrderedJoin, SegmentJoin
         dev = torch.device(self.device) if not isinstance(self.device, torch.device) else self.device
         join = SegmentJoin.from_spec(spec, self.sample_rate, dev, stream=stream)
         chain = None
-        if self._audio_spec is not None:
+        output = self._audio_spec if output is None else output
+        if output is not None:
             from .audio_out import AudioOut
-            chain = AudioOut(self._audio_spec, self.sample_rate, join.dev, stream)
+            chain = AudioOut(output, self.sample_rate, join.dev, stream)
         pauses = [spec.pause_samples(s.pause, self.sample_rate) for s in segs]
         oj = OrderedJoin(join, pauses, chain)
         oj.gains = self._gain_tensor(join.dev)                     # fixed_gain: every joined piece times the one factor
@@ -2447,6 +2461,210 @@ class FasterQwen3TTS:
         prepared = self._prepare_custom_batch([s.text for s in segs], speaker, language, instruct, non_streaming_mode)
         yield from self._run_long_streaming(prepared, segs, spec, self._gen_kwargs(max_new_tokens, min_new_tokens, temperature, top_k,
                                                                                    top_p, do_sample, repetition_penalty), chunk_size, lanes)
+
+    # ---- long form for many texts: the segments of all texts share the lanes of ONE lock-step run ------
+    def _long_batch_setup(self, texts, long_form, seeds, output):
+        """-> (spec, [segments per text], the requests' seeds, the texts' output specs or None): every argument error, each text's
+        ``_long_setup`` included, before anything is prepared or decoded.  The requests are queued text by text; segment ``k`` of a
+        text with seed ``s`` samples with ``s + k``, as ``seeded(s)`` gives the single-text call."""
+        if isinstance(texts, str) or not isinstance(texts, (list, tuple)) or not texts:
+            raise ValueError("texts must be a list of texts that is not empty")
+        self._refuse_batch_audio_output()
+        outputs = self._batch_outputs(output, len(texts))
+        spec, segs = None, []
+        for text in texts:
+            spec, s = self._long_setup(text, long_form)
+            segs.append(s)
+        per_text = expand_seeds(seeds, len(texts))
+        req_seeds = [None if s is None else (s + k) % 2 ** 64 for s, sg in zip(per_text, segs) for k in range(len(sg))]
+        return spec, segs, (req_seeds if seeds is not None else None), outputs
+
+    def _long_batch_chains(self, spec, segs, stream, gen_kwargs, outputs):
+        """one ordered join and chain per text, all on ``stream`` -> (``OrderedJoinSet``, the chains)"""
+        from .long_form import OrderedJoinSet
+        pairs = [self._long_chain(spec, sg, stream, self._long_level_hops(spec, sg, gen_kwargs), None if outputs is None else outputs[t])
+                 for t, sg in enumerate(segs)]
+        return OrderedJoinSet([oj for oj, _c in pairs]), [c for _oj, c in pairs]
+
+    def _run_long_batch_full(self, prepared, segs, spec, gen_kwargs, lanes: int, seeds, outputs) -> List[Tuple[list, int]]:
+        """``_run_long_full`` over many texts: one lock-step run over every segment of every text; round ``k`` joins segment ``k`` of
+        every text that has one in ONE group call on the side vocoder's stream."""
+        counts = [len(sg) for sg in segs]
+        base = [sum(counts[:t]) for t in range(len(segs))]
+        outs, voc = self._run_batch_full(prepared, gen_kwargs, lanes, sum(counts), seeds=seeds, device_audio=True)
+        ojs, _chains = self._long_batch_chains(spec, segs, voc.stream, gen_kwargs, outputs)
+        parts: List[list] = [[] for _ in segs]
+        with (torch.cuda.stream(voc.stream) if voc.stream is not None else contextlib.nullcontext()):
+            for oj in ojs.ordered:
+                oj.audio_out = None                                 # every text's whole stream goes through a one-shot stage below
+                if self._loud is not None:
+                    oj.gains = [None] * oj.n
+            for k in range(max(counts)):
+                rows = []
+                for t, oj in enumerate(ojs.ordered):
+                    if k >= counts[t]:
+                        continue
+                    w = outs[base[t] + k][0][0]
+                    w = w if torch.is_tensor(w) else torch.from_numpy(np.ascontiguousarray(w, dtype=np.float32)).to(oj.join.dev)
+                    if self._loud is not None:
+                        from .loudness import gain_of
+                        oj.gains[k] = gain_of(self._measure(w.reshape(-1).contiguous(), base[t] + k, voc.stream))
+                    rows.append((t, k, w, True))
+                for t, _k, y, _ended in ojs.feed_group(rows):
+                    parts[t].append(y)
+            result = []
+            for t, oj in enumerate(ojs.ordered):
+                pcm = torch.cat(parts[t]) if parts[t] else torch.zeros(0, dtype=torch.float32, device=oj.join.dev)
+                if outputs is not None and outputs[t] is not None:
+                    a, sr = self._one_shot_output(pcm, outputs[t])
+                    result.append(([a], sr))
+                else:
+                    result.append(([pcm.cpu().numpy()], self.sample_rate))
+            return result
+
+    def _run_long_batch_streaming(self, prepared, segs, spec, gen_kwargs, chunk_size: int, lanes: int, seeds, outputs):
+        """``_run_long_streaming`` over many texts: the chunks a poll of the lock-step run hands out together go through ONE
+        ``feed_group``; every text's audio leaves in text order, the texts interleave as they become ready."""
+        self._refuse_streaming_loudness()
+        counts = [len(sg) for sg in segs]
+        where = [(t, k) for t, n in enumerate(counts) for k in range(n)]
+        tok = self.model.model.speech_tokenizer
+        side = self._vocoder_stream(tok)
+        ojs, chains = self._long_batch_chains(spec, segs, side, gen_kwargs, outputs)
+        rates = [c.out_rate if c is not None else self.sample_rate for c in chains]
+        header = [c is not None and c.flac for c in chains]
+        index = [0] * len(segs)
+        dev = ojs.ordered[0].join.dev
+        ctx = (lambda: torch.cuda.stream(side)) if side is not None else contextlib.nullcontext
+
+        def settle(group, steps):
+            with ctx():
+                rows = [(t, k, a if torch.is_tensor(a) else torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32)).to(dev), last)
+                        for t, k, a, last in group]
+                got = ojs.feed_group(rows)
+                # every piece of the group in ONE device buffer (16-byte aligned, whatever each text's encoding) and ONE copy
+                offs, total = [], 0
+                for _t, _k, y, _e in got:
+                    offs.append(total)
+                    total += (int(y.numel()) * y.element_size() + 15) // 16 * 16
+                buf = torch.empty(total, dtype=torch.uint8, device=dev)
+                for o, (_t, _k, y, _e) in zip(offs, got):
+                    if y.numel():
+                        buf[o: o + int(y.numel()) * y.element_size()] = y.contiguous().reshape(-1).view(torch.uint8)
+                host_all = buf.cpu().numpy()
+                pieces = [(t, k, host_all[o: o + int(y.numel()) * y.element_size()].view(torch.empty(0, dtype=y.dtype).numpy().dtype), ended)
+                          for o, (t, k, y, ended) in zip(offs, got)]
+            for t, k, host, ended in pieces:
+                if host.size == 0 and not ended:
+                    continue                                       # a chunk the join stage removed whole (or holds back)
+                if header[t]:
+                    host, header[t] = np.concatenate([np.frombuffer(chains[t].header(), dtype=np.uint8), host]), False
+                yield t, host, rates[t], dict(segment_index=k, n_segments=counts[t], chunk_index=index[t], is_final=ended,
+                                              total_steps_so_far=steps)
+                index[t] += 1
+
+        group, steps = [], 0
+        for rid, audio, _sr, tm in self._run_batch_streaming(prepared, gen_kwargs, chunk_size, lanes, seeds=seeds, count=len(where),
+                                                             device_audio=True, group_marks=True):
+            t, k = where[rid]
+            group.append((t, k, audio, bool(tm.get("is_final"))))
+            steps = int(tm.get("total_steps_so_far", 0))
+            if tm.get("group_end"):
+                yield from settle(group, steps)
+                group = []
+        if group:
+            yield from settle(group, steps)
+
+    def _prepare_long_batch(self, segs, prepare_text):
+        """the requests of every text's segments, text by text; ``prepare_text(t, [segment texts])`` -> that text's prepared requests"""
+        import itertools
+        return itertools.chain.from_iterable([prepare_text(t, [s.text for s in sg]) for t, sg in enumerate(segs)])
+
+    @torch.inference_mode()
+    def generate_long_voice_clone_batch(self, texts: List[str], language: Union[str, List[str]],
+                                        ref_audio: Optional[Union[str, Path]] = None,
+                                        ref_text: str = "", max_new_tokens: int = 2048, min_new_tokens: int = 2,
+                                        temperature: float = 0.9, top_k: int = 50, top_p: float = 1.0, do_sample: bool = True,
+                                        repetition_penalty: float = 1.05, xvec_only: bool = False,
+                                        non_streaming_mode: Optional[bool] = None, append_silence: bool = True,
+                                        instruct: Optional[str] = None, ref_spk: Optional[Union[str, Path]] = None,
+                                        ref_rvq: Optional[Union[str, Path]] = None, ref_spk_emb: Optional[np.ndarray] = None,
+                                        ref_codes: Optional[np.ndarray] = None,
+                                        voice_clone_prompt: Optional[Union[Dict[str, Any], List[Any]]] = None,
+                                        lanes: int = 16, long_form=None, seeds=None, output=None) -> List[Tuple[list, int]]:
+        """:meth:`generate_long_voice_clone` for many texts in ONE lock-step run: every segment of every text is a request, queued
+        text by text, and a lane that finishes one takes the next, whichever text it belongs to.  One ``([waveform], sample_rate)``
+        per text, in input order; text ``t`` equals the single-text call inside ``seeded(seeds[t])``.  ``seeds`` (a list, or an int
+        ``s``: text ``t`` gets ``s + t``) and ``output`` (an ``AudioOutSpec``, or one or None per text) as on the ``*_batch`` entry
+        points, per TEXT; ``language`` may be one per text."""
+        self._reject_ggml_cached_reference_args(ref_spk=ref_spk, ref_rvq=ref_rvq, ref_spk_emb=ref_spk_emb, ref_codes=ref_codes)
+        spec, segs, req_seeds, outputs = self._long_batch_setup(texts, long_form, seeds, output)
+        langs = self._per_text(language, len(texts), "language")
+        nsm = self._resolve_non_streaming_mode(non_streaming_mode, default=False)
+        prepared = self._prepare_long_batch(segs, lambda t, ts: self._prepare_clone_batch(
+            ts, langs[t], ref_audio, ref_text, xvec_only, nsm, append_silence, instruct, voice_clone_prompt))
+        return self._run_long_batch_full(prepared, segs, spec, self._gen_kwargs(max_new_tokens, min_new_tokens, temperature, top_k, top_p,
+                                                                                do_sample, repetition_penalty), lanes, req_seeds, outputs)
+
+    @torch.inference_mode()
+    def generate_long_voice_clone_batch_streaming(self, texts: List[str], language: Union[str, List[str]],
+                                                  ref_audio: Optional[Union[str, Path]] = None,
+                                                  ref_text: str = "", max_new_tokens: int = 2048, min_new_tokens: int = 2,
+                                                  temperature: float = 0.9, top_k: int = 50, top_p: float = 1.0, do_sample: bool = True,
+                                                  repetition_penalty: float = 1.05, chunk_size: int = 12, xvec_only: bool = False,
+                                                  non_streaming_mode: Optional[bool] = None, append_silence: bool = True,
+                                                  instruct: Optional[str] = None, ref_spk: Optional[Union[str, Path]] = None,
+                                                  ref_rvq: Optional[Union[str, Path]] = None, ref_spk_emb: Optional[np.ndarray] = None,
+                                                  ref_codes: Optional[np.ndarray] = None,
+                                                  voice_clone_prompt: Optional[Union[Dict[str, Any], List[Any]]] = None,
+                                                  lanes: int = 16, long_form=None, seeds=None,
+                                                  output=None) -> Generator[Tuple[int, np.ndarray, int, dict], None, None]:
+        """Streaming form of :meth:`generate_long_voice_clone_batch`: yields ``(text_index, audio_chunk, sample_rate, info)``;
+        ``info``: ``segment_index``, ``n_segments``, ``chunk_index``, ``is_final`` (all per text) and ``total_steps_so_far``.  The
+        audio of one text leaves strictly in text order; the texts interleave as they become ready.  ``flac``: the stream header
+        comes in front of a text's first piece."""
+        self._reject_ggml_cached_reference_args(ref_spk=ref_spk, ref_rvq=ref_rvq, ref_spk_emb=ref_spk_emb, ref_codes=ref_codes)
+        self._refuse_streaming_loudness()
+        spec, segs, req_seeds, outputs = self._long_batch_setup(texts, long_form, seeds, output)
+        langs = self._per_text(language, len(texts), "language")
+        nsm = self._resolve_non_streaming_mode(non_streaming_mode, default=False)
+        prepared = self._prepare_long_batch(segs, lambda t, ts: self._prepare_clone_batch(
+            ts, langs[t], ref_audio, ref_text, xvec_only, nsm, append_silence, instruct, voice_clone_prompt))
+        yield from self._run_long_batch_streaming(prepared, segs, spec, self._gen_kwargs(max_new_tokens, min_new_tokens, temperature, top_k,
+                                                                                         top_p, do_sample, repetition_penalty),
+                                                  chunk_size, lanes, req_seeds, outputs)
+
+    @torch.inference_mode()
+    def generate_long_custom_voice_batch(self, texts: List[str], speaker: Union[str, List[str]], language: Union[str, List[str]],
+                                         instruct: Optional[str] = None,
+                                         non_streaming_mode: Optional[bool] = None, max_new_tokens: int = 2048,
+                                         min_new_tokens: int = 2, temperature: float = 0.9, top_k: int = 50, top_p: float = 1.0,
+                                         do_sample: bool = True, repetition_penalty: float = 1.05, lanes: int = 16,
+                                         long_form=None, seeds=None, output=None) -> List[Tuple[list, int]]:
+        """CustomVoice for many texts of any length; see :meth:`generate_long_voice_clone_batch`.  ``speaker`` and ``language`` may
+        be one per text."""
+        spec, segs, req_seeds, outputs = self._long_batch_setup(texts, long_form, seeds, output)
+        spk, langs = self._per_text(speaker, len(texts), "speaker"), self._per_text(language, len(texts), "language")
+        prepared = self._prepare_long_batch(segs, lambda t, ts: self._prepare_custom_batch(ts, spk[t], langs[t], instruct, non_streaming_mode))
+        return self._run_long_batch_full(prepared, segs, spec, self._gen_kwargs(max_new_tokens, min_new_tokens, temperature, top_k, top_p,
+                                                                                do_sample, repetition_penalty), lanes, req_seeds, outputs)
+
+    @torch.inference_mode()
+    def generate_long_custom_voice_batch_streaming(self, texts: List[str], speaker: Union[str, List[str]],
+                                                   language: Union[str, List[str]], instruct: Optional[str] = None,
+                                                   non_streaming_mode: Optional[bool] = None, max_new_tokens: int = 2048,
+                                                   min_new_tokens: int = 2, temperature: float = 0.9, top_k: int = 50,
+                                                   top_p: float = 1.0, do_sample: bool = True, repetition_penalty: float = 1.05,
+                                                   chunk_size: int = 12, lanes: int = 16, long_form=None, seeds=None,
+                                                   output=None) -> Generator[Tuple[int, np.ndarray, int, dict], None, None]:
+        """Streaming form of :meth:`generate_long_custom_voice_batch`."""
+        self._refuse_streaming_loudness()
+        spec, segs, req_seeds, outputs = self._long_batch_setup(texts, long_form, seeds, output)
+        spk, langs = self._per_text(speaker, len(texts), "speaker"), self._per_text(language, len(texts), "language")
+        prepared = self._prepare_long_batch(segs, lambda t, ts: self._prepare_custom_batch(ts, spk[t], langs[t], instruct, non_streaming_mode))
+        yield from self._run_long_batch_streaming(prepared, segs, spec, self._gen_kwargs(max_new_tokens, min_new_tokens, temperature, top_k,
+                                                                                         top_p, do_sample, repetition_penalty),
+                                                  chunk_size, lanes, req_seeds, outputs)
 
     # ---- incremental text (extension: the reference takes the whole text before it starts; fq3hip/text_stream.py) ---------
     @staticmethod

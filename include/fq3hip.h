@@ -717,6 +717,25 @@ int fq3_join_reset(fq3_join* j, void* stream);
  * FQ3_ESTATE until fq3_join_reset. */
 int fq3_join_push(fq3_join* j, const float* pcm, int64_t n_in, int end, int64_t pause_samples, float* out, int64_t capacity,
                   int64_t* n_out_dev, void* stream);
+/* The join for a GROUP of streams, as fq3_audio_out_push_group / fq3_tsm_push_group / fq3_flac_push_group above and with their
+ * conventions.  Every array is a HOST array of B entries (n_out_dev: B pointers to DEVICE int64s); row b is exactly
+ *     fq3_join_push(objs[b], pcm[b], n_in[b], end[b], pause_samples[b], out[b], capacity[b], n_out_dev[b], stream)
+ *   Launches.        ONE launch of B workgroups on `stream`, one per row: a push is a serial walk over its hops by one lane, and the
+ *                    rows of different streams do not depend on each other, so they walk side by side.
+ *   Equality.        The samples row b writes, *n_out_dev[b] and the state objs[b] is left in (on the device and on the host: the
+ *                    partial-hop length, the fresh flag, which pending buffer is next) are bit for bit those of the single push: a
+ *                    row runs the same device code.  Group and single pushes mix freely on one object; membership and order of a
+ *                    group may change from push to push.
+ *   All or nothing.  Every row is checked before any object changes (null pointers, lengths, end in 0..2, the pause range, capacity
+ *                    against fq3_join_bound, FQ3_ESTATE after end == 2): on an error the code of the first offending row is
+ *                    returned, the message names the row, nothing is launched and no object has moved.
+ *   Limits.          B == 0: returns 0, does nothing.  B < 0, B > FQ3_STAGE_GROUP_MAX, a null array, a null object or the same object
+ *                    twice in one call: FQ3_EINVAL, answered before any HIP call.
+ *   No shared design. Each row's descriptor carries its own configuration: the objects may differ in rate, threshold and hops.
+ *   Asynchrony.      No host synchronisation and no copy: the rows' descriptors travel in the launch's argument block. */
+int fq3_join_push_group(fq3_join* const* objs, int B, const float* const* pcm, const int64_t* n_in, const int* end,
+                        const int64_t* pause_samples, float* const* out, const int64_t* capacity,
+                        int64_t* const* n_out_dev, void* stream);
 
 /* ---- Loudness: an ITU-R BS.1770-4 meter (mono, integrated, gated), the gain to a target level, and a gain multiply ----------------
  * On the vocoder's float32 PCM: the MEASURE is taken in front of the join, time-scale and output stages; the gain is applied in front

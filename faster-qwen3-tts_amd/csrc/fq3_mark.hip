@@ -1,0 +1,222 @@
+// Provenance watermark behind the C ABI: float32 mono in at 24 kHz, float32 out, length-preserving -- behind the join, the gains and
+// the leveller, in front of the limiter and the output stage (fq3_limit.hip, fq3_audio.hip; the time-scale stage is part of the
+// output stage, so the model refuses a speed other than 1 together with the mark).
+//   fq3_mark_design / _count   host only (no HIP call): the framing constants, the strength as the device's float, the chip words
+//   fq3_mark_create / _push    ONE launch per push: a workgroup per 15 hops of output plus one that keeps the history
+//   fq3_mark_detect            two launches: the partial sums of every (offset, frame tile), then z[32][128]
+// The host tracks what follows from the lengths alone: samples pushed, samples emitted, which history buffer is current, whether the
+// stream has ended.  The two DFT tables (2 x 256 KB) depend on nothing a caller chooses: one copy per device, made at the first
+// create or detect there and kept for the life of the process.
+#include "../../include/fq3hip.h"
+#include "fq3_common.cuh"
+#include "mark_kernels.cuh"
+
+#include <cmath>
+#include <mutex>
+#include <string>
+#include <vector>
+
+using namespace fq3;
+
+int fq3_fail_(int code, const std::string& m);                 // fq3_api.hip: sets the thread-local error string
+#define KHIP(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) return fq3_fail_(FQ3_EHIP, std::string(#x) + ": " + hipGetErrorString(e_)); } while (0)
+
+namespace {
+
+constexpr double kMinStrength = 0.02, kMaxStrength = 0.3;
+constexpr int64_t kMaxPush = (int64_t)1 << 31;
+constexpr int64_t kMaxDetect = (int64_t)1 << 27;        // 93 minutes at 24 kHz; the partials stay below 2^31 floats
+constexpr int kMaxDevices = 64;
+
+// Philox4x32-10 on the host, as philox4x32_10 in noise_kernels.cuh
+void philox_host_(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1, uint32_t out[4]) {
+    for (int r = 0; r < 10; ++r) {
+        const uint64_t p0 = (uint64_t)kPhiloxM0 * c0, p1 = (uint64_t)kPhiloxM1 * c2;
+        const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c1 ^ k0, n2 = (uint32_t)(p0 >> 32) ^ c3 ^ k1;
+        c0 = n0; c1 = (uint32_t)p1; c2 = n2; c3 = (uint32_t)p0;
+        k0 += kPhiloxW0; k1 += kPhiloxW1;
+    }
+    out[0] = c0; out[1] = c1; out[2] = c2; out[3] = c3;
+}
+
+int strength_(const std::string& who, double strength, float* a) {
+    if (!(strength == 0.0 || (strength >= kMinStrength && strength <= kMaxStrength)))
+        return fq3_fail_(FQ3_EINVAL, who + ": strength is neither 0 nor in [0.02, 0.3]");
+    *a = (float)strength;
+    return 0;
+}
+
+// both tables in fragment order: element (k, n) of a [K][N] operand lies at ((n / 16) * (K / 4) + k / 4) * 64 + (k % 4) * 16 + n % 16
+void tables_(std::vector<float>& fwd, std::vector<float>& inv) {
+    const double pi = 3.14159265358979323846;
+    double w[kMarkN], cs[kMarkN], sn[kMarkN];
+    for (int i = 0; i < kMarkN; ++i) {
+        w[i] = std::sqrt(0.5 - 0.5 * std::cos(2.0 * pi * i / kMarkN));
+        cs[i] = std::cos(2.0 * pi * i / kMarkN);
+        sn[i] = std::sin(2.0 * pi * i / kMarkN);
+    }
+    fwd.assign(kMarkFwdFloats, 0.0f);
+    inv.assign(kMarkInvFloats, 0.0f);
+    for (int i = 0; i < kMarkN; ++i)
+        for (int c = 0; c < 2 * kMarkBins; ++c) {
+            const int bin = kMarkLo + (c & (kMarkBins - 1)), m = (bin * i) & (kMarkN - 1);      // the angle, reduced exactly
+            const double v = c < kMarkBins ? w[i] * cs[m] : -w[i] * sn[m];
+            fwd[((size_t)(c / 16) * (kMarkN / 4) + i / 4) * 64 + (i % 4) * 16 + c % 16] = (float)v;
+            inv[((size_t)(i / 16) * (2 * kMarkBins / 4) + c / 4) * 64 + (c % 4) * 16 + i % 16] = (float)(v * 2.0 / kMarkN);
+        }
+}
+
+// the device's copy of the tables: fwd, then inv
+int device_tables_(const float** out) {
+    static std::mutex mu;
+    static float* dev_tables[kMaxDevices] = {};
+    int dev = -1;
+    KHIP(hipGetDevice(&dev));
+    if (dev < 0 || dev >= kMaxDevices) return fq3_fail_(FQ3_EINVAL, "mark: device index out of range");
+    std::lock_guard<std::mutex> lock(mu);
+    if (!dev_tables[dev]) {
+        std::vector<float> fwd, inv;
+        tables_(fwd, inv);
+        float* p = nullptr;
+        KHIP(hipMalloc((void**)&p, (size_t)(kMarkFwdFloats + kMarkInvFloats) * sizeof(float)));
+        hipError_t e = hipMemcpy(p, fwd.data(), fwd.size() * sizeof(float), hipMemcpyHostToDevice);
+        if (e == hipSuccess) e = hipMemcpy(p + kMarkFwdFloats, inv.data(), inv.size() * sizeof(float), hipMemcpyHostToDevice);
+        if (e != hipSuccess) {
+            (void)hipFree(p);
+            return fq3_fail_(FQ3_EHIP, std::string("mark: table upload: ") + hipGetErrorString(e));
+        }
+        dev_tables[dev] = p;
+    }
+    *out = dev_tables[dev];
+    return 0;
+}
+
+int64_t count_(int64_t total, int final) {
+    if (final) return total;
+    const int64_t hops = total / kMarkH - 1;
+    return hops > 0 ? hops * kMarkH : 0;
+}
+
+int64_t detect_frames_(int64_t n) { return (n + kMarkH - 1) / kMarkH + 1; }
+int64_t detect_tiles_(int64_t n) { return (detect_frames_(n) - 2 + kMarkInner - 1) / kMarkInner; }
+
+}  // namespace
+
+struct fq3_mark {
+    uint64_t key = 0;
+    float a = 0.0f;
+    const float* tables = nullptr;            // the device's shared copy; not owned
+    float* hist[2] = {nullptr, nullptr};      // kMarkKeep floats each
+    int cur = 0;
+    int64_t total = 0, emitted = 0;
+    bool finished = false;
+};
+
+extern "C" int fq3_mark_design(uint64_t key, double strength, int* N, int* H, int* bin_lo, int* n_bins, int* period, float* a,
+                               uint32_t* chip_words) {
+    float af = 0.0f;
+    if (int rc = strength_("fq3_mark_design", strength, &af)) return rc;
+    if (N) *N = kMarkN;
+    if (H) *H = kMarkH;
+    if (bin_lo) *bin_lo = kMarkLo;
+    if (n_bins) *n_bins = kMarkBins;
+    if (period) *period = kMarkPeriod;
+    if (a) *a = af;
+    if (chip_words)
+        for (int c = 0; c < kMarkPeriod / 2; ++c)
+            philox_host_((uint32_t)c, 0u, kMarkSlot, 0u, (uint32_t)(key & 0xffffffffull), (uint32_t)(key >> 32), chip_words + 4 * c);
+    return 0;
+}
+
+extern "C" int64_t fq3_mark_count(int64_t n_in, int final) {
+    if (n_in < 0 || n_in > kMaxPush) return fq3_fail_(FQ3_EINVAL, "fq3_mark_count: n_in outside [0, 2^31]");
+    return count_(n_in, final);
+}
+
+extern "C" int fq3_mark_create(const fq3_mark_config* cfg, fq3_mark** out) {
+    if (!cfg || !out) return fq3_fail_(FQ3_EINVAL, "fq3_mark_create: null argument");
+    float af = 0.0f;
+    if (int rc = strength_("fq3_mark_create", cfg->strength, &af)) return rc;
+    const float* tables = nullptr;
+    if (int rc = device_tables_(&tables)) return rc;
+    fq3_mark* m = new fq3_mark();
+    m->key = cfg->key; m->a = af; m->tables = tables;
+    const hipError_t e = hipMalloc((void**)&m->hist[0], (size_t)(2 * kMarkKeep) * sizeof(float));
+    if (e != hipSuccess) {
+        const std::string msg = std::string("fq3_mark_create: ") + hipGetErrorString(e);
+        (void)hipGetLastError();
+        delete m;
+        return fq3_fail_(FQ3_EHIP, msg);
+    }
+    m->hist[1] = m->hist[0] + kMarkKeep;
+    *out = m;
+    return 0;
+}
+
+extern "C" int fq3_mark_destroy(fq3_mark* m) {
+    if (!m) return 0;
+    if (m->hist[0]) (void)hipFree(m->hist[0]);
+    delete m;
+    return 0;
+}
+
+extern "C" int fq3_mark_reset(fq3_mark* m, void* stream) {
+    if (!m) return fq3_fail_(FQ3_EINVAL, "fq3_mark_reset: null object");
+    (void)stream;                                  // the history needs nothing: its length starts at 0
+    m->total = m->emitted = 0;
+    m->finished = false;
+    return 0;
+}
+
+extern "C" int fq3_mark_push(fq3_mark* m, const float* pcm, int64_t n_in, int final, float* out, int64_t capacity_samples,
+                             int64_t* n_out, void* stream) {
+    if (!m || !n_out) return fq3_fail_(FQ3_EINVAL, "fq3_mark_push: null argument");
+    if (n_in < 0 || n_in > kMaxPush || (n_in > 0 && !pcm)) return fq3_fail_(FQ3_EINVAL, "fq3_mark_push: bad input");
+    if (m->finished) return fq3_fail_(FQ3_ESTATE, "fq3_mark_push: the stream has ended; fq3_mark_reset starts the next one");
+    const int64_t total = m->total + n_in;
+    const int64_t n = count_(total, final) - m->emitted;
+    if (n > capacity_samples || (n > 0 && !out))
+        return fq3_fail_(FQ3_EINVAL, "fq3_mark_push: " + std::to_string(n) + " output samples exceed the capacity of " + std::to_string(capacity_samples));
+    *n_out = n;
+    if (n_in == 0 && !final) return 0;              // nothing completes and nothing changes
+    MarkPushArgs k{};
+    const int64_t n_hist = m->total < kMarkKeep ? m->total : kMarkKeep;
+    k.src = MarkSrc{pcm, m->hist[m->cur], m->total - n_hist, m->total, total};
+    k.hist_next = m->hist[m->cur ^ 1];
+    k.out = out; k.fwd = m->tables; k.inv = m->tables + kMarkFwdFloats;
+    k.o0 = m->emitted; k.n_out = n;
+    k.keep = final ? 0 : (int)(total < kMarkKeep ? total : kMarkKeep);
+    k.a = m->a;
+    k.k0 = (uint32_t)(m->key & 0xffffffffull); k.k1 = (uint32_t)(m->key >> 32);
+    const int64_t hops = (n + kMarkH - 1) / kMarkH, groups = (hops + kMarkHops - 1) / kMarkHops;
+    hipLaunchKernelGGL(mark_embed_kernel, dim3((unsigned)(groups + 1)), dim3(kMarkThreads), 0, (hipStream_t)stream, k);
+    KHIP(hipGetLastError());
+    m->cur ^= 1;
+    m->total = total;
+    m->emitted += n;
+    if (final) m->finished = true;
+    return 0;
+}
+
+extern "C" int64_t fq3_mark_detect_workspace(int64_t n) {
+    if (n < 2 * kMarkH || n > kMaxDetect) return fq3_fail_(FQ3_EINVAL, "fq3_mark_detect_workspace: n outside [512, 2^27]");
+    return (int64_t)kMarkOffsets * detect_tiles_(n) * kMarkPartLd;
+}
+
+extern "C" int fq3_mark_detect(const float* pcm, int64_t n, uint64_t key, float* work, int64_t work_floats, float* z, void* stream) {
+    if (!pcm || !work || !z) return fq3_fail_(FQ3_EINVAL, "fq3_mark_detect: null argument");
+    if (n < 2 * kMarkH || n > kMaxDetect) return fq3_fail_(FQ3_EINVAL, "fq3_mark_detect: n outside [512, 2^27]");
+    const int64_t tiles = detect_tiles_(n);
+    if (work_floats < (int64_t)kMarkOffsets * tiles * kMarkPartLd)
+        return fq3_fail_(FQ3_EINVAL, "fq3_mark_detect: the workspace is smaller than fq3_mark_detect_workspace(n)");
+    const float* tables = nullptr;
+    if (int rc = device_tables_(&tables)) return rc;
+    MarkDetectArgs k{};
+    k.pcm = pcm; k.fwd = tables; k.part = work; k.n = n; k.T = (int)detect_frames_(n);
+    k.k0 = (uint32_t)(key & 0xffffffffull); k.k1 = (uint32_t)(key >> 32);
+    hipLaunchKernelGGL(mark_detect_kernel, dim3((unsigned)tiles, kMarkOffsets), dim3(kMarkThreads), 0, (hipStream_t)stream, k);
+    KHIP(hipGetLastError());
+    hipLaunchKernelGGL(mark_reduce_kernel, dim3(kMarkOffsets), dim3(kMarkPeriod), 0, (hipStream_t)stream, (const float*)work, (int)tiles, z);
+    KHIP(hipGetLastError());
+    return 0;
+}

@@ -14,24 +14,11 @@
 //               (nearest even) and, for a bf16 context, once more to bf16.  Range [5.96e-8, 16.64]: never zero, never infinite.
 #pragma once
 #include "fq3_common.cuh"
+#include "philox.cuh"
 
 namespace fq3 {
 
-constexpr uint32_t kPhiloxM0 = 0xD2511F53u, kPhiloxM1 = 0xCD9E8D57u, kPhiloxW0 = 0x9E3779B9u, kPhiloxW1 = 0xBB67AE85u;
 constexpr uint32_t kNoiseFirstSlot = 0xFFFFFFFFu;
-
-struct Philox4 { uint32_t x, y, z, w; };
-
-__device__ __forceinline__ Philox4 philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1) {
-#pragma unroll
-    for (int r = 0; r < 10; ++r) {
-        const uint32_t hi0 = __umulhi(kPhiloxM0, c0), lo0 = kPhiloxM0 * c0;
-        const uint32_t hi1 = __umulhi(kPhiloxM1, c2), lo1 = kPhiloxM1 * c2;
-        c0 = hi1 ^ c1 ^ k0; c1 = lo1; c2 = hi0 ^ c3 ^ k1; c3 = lo0;
-        k0 += kPhiloxW0; k1 += kPhiloxW1;
-    }
-    return Philox4{c0, c1, c2, c3};
-}
 
 __device__ __forceinline__ float noise_variate(uint32_t word) {
     const double u = (double)(2u * (word >> 9) + 1u) * 0x1p-24;

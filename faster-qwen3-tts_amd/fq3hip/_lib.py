@@ -101,6 +101,10 @@ class LimitStats(C.Structure):
     _fields_ = [("true_peak", C.c_float), ("min_gain_q23", C.c_uint32), ("n_limited", C.c_int64), ("n_bad", C.c_int64)]
 
 
+class MarkConfig(C.Structure):
+    _fields_ = [("key", C.c_uint64), ("strength", C.c_double)]
+
+
 class LoudStats(C.Structure):
     _fields_ = [("mean_power", C.c_double), ("peak", C.c_float), ("gain", C.c_float), ("n_hops", i32), ("n_abs", i32), ("n_rel", i32),
                 ("n_bad", i32), ("valid", i32), ("reserved", i32)]
@@ -285,6 +289,15 @@ SIGNATURES = {
     "fq3_noise_fill": (C.c_int, [vp, C.POINTER(NoiseRing), C.c_int, C.c_int, vp]),
     "fq3_noise_first": (C.c_int, [vp, C.c_uint64, vp, vp]),
     "fq3_noise_words": (C.c_int, [C.c_uint64, C.c_uint32, C.c_uint32, C.c_int, vp, vp]),
+    "fq3_mark_design": (C.c_int, [C.c_uint64, C.c_double, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int),
+                                  C.POINTER(C.c_int), C.POINTER(C.c_float), C.POINTER(C.c_uint32)]),
+    "fq3_mark_count": (C.c_int64, [C.c_int64, C.c_int]),
+    "fq3_mark_create": (C.c_int, [C.POINTER(MarkConfig), C.POINTER(vp)]),
+    "fq3_mark_destroy": (C.c_int, [vp]),
+    "fq3_mark_reset": (C.c_int, [vp, vp]),
+    "fq3_mark_push": (C.c_int, [vp, vp, C.c_int64, C.c_int, vp, C.c_int64, C.POINTER(C.c_int64), vp]),
+    "fq3_mark_detect_workspace": (C.c_int64, [C.c_int64]),
+    "fq3_mark_detect": (C.c_int, [vp, C.c_int64, C.c_uint64, vp, C.c_int64, vp, vp]),
 }
 
 _lib = None

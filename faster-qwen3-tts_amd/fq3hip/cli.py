@@ -162,7 +162,8 @@ def _exact(model, args):
 def _levelled(model, args):
     """``--loudness`` / ``--gain-db``: the model's ``loudness`` or ``fixed_gain`` context (the level set on the device), or a no-op;
     ``--level``: the model's ``leveller`` context (the streaming loudness leveller, behind the gain);
-    ``--limiter-db``: the model's ``limiter`` context around it (the limiter runs behind the gain and the leveller)."""
+    ``--limiter-db``: the model's ``limiter`` context around it (the limiter runs behind the gain and the leveller);
+    ``--watermark-key``: the model's ``watermark`` context (the mark goes in between the leveller and the limiter)."""
     import contextlib
     lufs, gain, ceiling = getattr(args, "loudness", None), getattr(args, "gain_db", None), getattr(args, "limiter_db", None)
     stack = contextlib.ExitStack()
@@ -174,6 +175,8 @@ def _levelled(model, args):
         stack.enter_context(model.leveller(target_lufs=args.level))
     if ceiling is not None:
         stack.enter_context(model.limiter(ceiling_db=ceiling))
+    if getattr(args, "watermark_key", None) is not None:
+        stack.enter_context(model.watermark(args.watermark_key, getattr(args, "watermark_strength", None) or 0.1))
     return stack
 
 
@@ -192,6 +195,13 @@ def check_level_args(parser, args):
         if getattr(args, "level", None) is not None:
             from .leveller import LevelSpec
             LevelSpec(target_lufs=args.level)
+        if getattr(args, "watermark_key", None) is not None:
+            from .watermark import MarkSpec
+            if not MarkSpec(args.watermark_key, getattr(args, "watermark_strength", None) or 0.1).strength:
+                raise ValueError("--watermark-strength is in [0.02, 0.3]")
+            if getattr(args, "speed", None) not in (None, 1.0):
+                raise ValueError("--watermark-key does not go with --speed: the time-scale stage runs behind the mark and would stretch "
+                                 "its frame grid, which defeats the detector")
     except ValueError as exc:
         parser.error(str(exc))
     if getattr(args, "loudness", None) is None:
@@ -203,6 +213,17 @@ def check_level_args(parser, args):
                      "be known before it ends (use --gain-db X)")
     if getattr(args, "gain_db", None) is not None:
         parser.error("--loudness and --gain-db both set the level: give one")
+
+
+def cmd_detect(args):
+    """``detect``: the detector over a WAV file on the device; prints the ``Detection`` and exits 0 when the mark is present, 1 when not"""
+    from .audio_io import read_wav
+    from .watermark import detect
+    pcm, sr = read_wav(args.input)
+    pcm = np.asarray(pcm, dtype=np.float32)
+    det = detect(pcm if pcm.ndim == 1 else pcm.reshape(len(pcm), -1)[:, 0], sr, args.watermark_key)
+    print(det)
+    raise SystemExit(0 if det.present else 1)
 
 
 def _write_output(path, audio, sr, args):
@@ -281,7 +302,7 @@ def cmd_serve(args, model=None, lines=None):
         if not pending:
             continue
         start = time.perf_counter()
-        levelled = any(getattr(args, k, None) is not None for k in ("gain_db", "limiter_db", "level"))
+        levelled = any(getattr(args, k, None) is not None for k in ("gain_db", "limiter_db", "level", "watermark_key"))
         if len(pending) > 1 and getattr(args, "long", False) and args.mode in ("clone", "custom") and not levelled:
             # --long: every line is a text of any length; the segments of all waiting lines share the lanes of ONE lock-step run
             from .long_form import LongFormSpec
@@ -358,6 +379,11 @@ def build_parser():
                         help="streaming loudness leveller on the device: a causal BS.1770 gain that brings the stream to LUFS while it "
                              "runs (zero latency, at most +20 dB); works in every mode, streaming included; it does not limit, so add "
                              "--limiter-db; the defaults behind it are not tuned on real voices (default: off)")
+        sp.add_argument("--watermark-key", type=lambda v: int(v, 0), default=None, metavar="KEY",
+                        help="put a keyed provenance watermark into the audio on the device (KEY: an integer in [0, 2^64), what `detect` "
+                             "needs); single-stream and --long modes, not with --speed or a lock-step --lanes run (default: off)")
+        sp.add_argument("--watermark-strength", type=float, default=None, metavar="A",
+                        help="--watermark-key: the mark's strength, 0.02 to 0.3; NOT tuned on real voices (default: 0.1)")
         if output:
             sp.add_argument("--loudness", type=float, default=None, metavar="LUFS",
                             help="measure the utterance on the device (ITU-R BS.1770-4, integrated) and scale it to LUFS, at most +20 dB and "
@@ -409,6 +435,10 @@ def build_parser():
                         "the N lanes of one lock-step run (clone and custom mode)")
     s.add_argument("--max-chars", type=int, default=240, metavar="N", help="--long: the splitter's budget per segment")
     s.set_defaults(func=cmd_serve)
+    d = sub.add_parser("detect", help="is the watermark of KEY in a WAV file?  prints the Detection")
+    d.add_argument("--input", required=True, help="a WAV file (mono, or the first channel); any rate: resampled to 24 kHz on the device")
+    d.add_argument("--watermark-key", type=lambda v: int(v, 0), required=True, metavar="KEY")
+    d.set_defaults(func=cmd_detect)
     return p
 
 

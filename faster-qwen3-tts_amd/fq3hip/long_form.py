@@ -471,6 +471,7 @@ class OrderedJoin:
         self.gains = None                                          # a 1-element device tensor, or one per segment: see ``_emit``
         self.limiter = None                                        # a ``Limiter`` on the join's stream: the joined stream goes through it
         self.leveller = None                                       # a ``Leveller`` likewise, in front of the limiter
+        self.marker = None                                         # a ``Watermark`` likewise, between the leveller and the limiter
         self.n = len(self.pauses)
         self.cur = 0
         self._wait: List[List] = [[] for _ in range(self.n)]        # per segment: [(device tensor or None, last)]
@@ -487,6 +488,9 @@ class OrderedJoin:
         if self.leveller is not None:
             # the streaming loudness leveller: behind the gains, in front of the limiter; it holds nothing back
             y = self.leveller.push(y.contiguous(), final=end == 2)
+        if self.marker is not None:
+            # the provenance watermark: one mark on the joined stream; its held-back hop comes out at the end, through the limiter
+            y = self.marker.push(y.contiguous(), final=end == 2)
         if self.limiter is not None:
             # behind the gains, in front of the chain: one stream, so the look-ahead is held back once and comes out at the end
             y = self.limiter.push(y.contiguous(), final=end == 2)

@@ -324,8 +324,11 @@ class StreamingVocoder:
     CONTEXT_FRAMES = 25
 
     def __init__(self, tok, ref_codes, chunk_size: int, device, side_stream=None, output=None, exact=False, gain=None, limiter=None,
-                 limiter_pool=None, leveller=None, leveller_pool=None, leveller_hops: int = 0):
+                 limiter_pool=None, leveller=None, leveller_pool=None, leveller_hops: int = 0, mark=None, mark_pool=None):
         self.tok, self.ref_codes, self.side = tok, ref_codes, side_stream
+        # a ``MarkSpec`` (``FasterQwen3TTS.watermark``) or None; its stage and pool as the limiter's, between the leveller and the limiter
+        self.mark_spec, self.mark, self.mark_pool = mark, None, mark_pool
+        refuse_marked_speed(mark, output)
         self.output, self.stage, self.header_sent = output, None, False
         self.gain = gain                  # a 1-element float32 device tensor (``FasterQwen3TTS.fixed_gain``) or None
         # a ``LimiterSpec`` (``FasterQwen3TTS.limiter``) or None; the stage, taken at the first chunk and given back at the last;
@@ -415,9 +418,33 @@ class StreamingVocoder:
             wav = apply_gain(wav.flatten().float().contiguous(), self.gain, self.side)
         if self.level_spec is not None:
             wav = self.level_push(wav.flatten().float().contiguous(), final)
+        if self.mark_spec is not None:
+            wav = self.mark_push(wav.flatten().float().contiguous(), final)
         if self.limit_spec is not None:
             wav = self.limit_push(wav.flatten().float().contiguous(), final)
         return wav
+
+    def mark_push(self, wav, final: bool):
+        """``wav`` (contiguous float32 device vector, or None) through this utterance's watermark: taken at the first chunk -- an idle
+        object of the same key and strength from the model's pool, reset, or a new one, on the vocoder's stream -- and given back
+        behind the final push.  It holds back between 256 and 511 samples until then."""
+        if self.mark is None:
+            try:
+                wm = self.mark_pool.pop() if self.mark_pool else None           # (another thread may take the last one first)
+            except IndexError:
+                wm = None
+            if wm is not None and wm.stream is self.side and wm.spec == self.mark_spec:
+                wm.reset()
+            else:
+                from .watermark import Watermark
+                wm = Watermark(self.mark_spec.key, self.mark_spec.strength, self.dev, self.side)
+            self.mark = wm
+        out = self.mark.push(wav, final)
+        if final:
+            wm, self.mark = self.mark, None
+            if self.mark_pool is not None and len(self.mark_pool) < self.LIMITER_POOL_MAX:
+                self.mark_pool.append(wm)
+        return out
 
     LIMITER_POOL_MAX = 256
 
@@ -543,10 +570,12 @@ class StreamingVocoder:
         if self.level is not None:
             with (contextlib.nullcontext() if self.side is None else torch.cuda.stream(self.side)):
                 self.level_release()                                # (it held nothing back)
-        if self.limit is not None:
-            # the limiter's held-back samples: they go out through the output stage, or as they are
+        if self.mark is not None or self.limit is not None:
+            # the watermark's held-back samples go through the limiter; its held-back samples go out through the output stage, or as they are
             with (contextlib.nullcontext() if self.side is None else torch.cuda.stream(self.side)):
-                tail = self.limit_push(None, True)
+                tail = self.mark_push(None, True) if self.mark is not None else None
+                if self.limit is not None:
+                    tail = self.limit_push(tail, True)
                 if self.output is None:
                     return tail.cpu().numpy(), int(getattr(self.tok, "sample_rate", 24000))
             return self._encoded(tail, True)
@@ -662,7 +691,7 @@ class StreamingVocoder:
             window = flat[start:]
             n_ctx = window.shape[0] - n_new
             new_audio, sr = self._vocode(window, int(round(n_ctx * self.spf)) if n_ctx > 0 else 0, ready_event)
-        if self.gain is not None or self.limit_spec is not None or self.level_spec is not None:
+        if self.gain is not None or self.limit_spec is not None or self.level_spec is not None or self.mark_spec is not None:
             # synchronous tokenizer: its audio is on the host; the chunk is uploaded for the multiply (and the stages behind it)
             wav = self._gained(torch.from_numpy(np.ascontiguousarray(new_audio, dtype=np.float32)).to(self.dev), final)
             return self._encoded(wav, final) if self.output is not None else (wav.cpu().numpy(), sr)
@@ -670,6 +699,14 @@ class StreamingVocoder:
             # synchronous tokenizer: its audio is on the host; the chunk is uploaded for the stage
             return self._encoded(torch.from_numpy(np.ascontiguousarray(new_audio, dtype=np.float32)).to(self.dev), final)
         return new_audio, sr
+
+
+def refuse_marked_speed(mark, output) -> None:
+    """The time-scale stage lives inside the output stage, BEHIND the watermark, and a stretched frame grid defeats the detector: a
+    mark together with a ``speed`` other than 1 is refused, not silently made undetectable."""
+    if mark is not None and output is not None and output.permille != 1000:
+        raise ValueError("watermark() with speed != 1: the time-scale stage runs behind the mark and would stretch its frame grid, which "
+                         "defeats the detector; time-scale the audio without the mark, or mark it at speed 1")
 
 
 class FasterQwen3TTS:
@@ -690,6 +727,7 @@ class FasterQwen3TTS:
         self._loud = None                # the LoudnessSession of an open ``loudness`` context
         self._gain = None                # the factor of an open ``fixed_gain`` context
         self._limit = None               # the LimiterSpec of an open ``limiter`` context
+        self._mark = None                # the MarkSpec of an open ``watermark`` context
         self._lvl = None                 # the LevelSpec of an open ``leveller`` context
         self._last_levelled = None       # the vocoder / leveller of the last levelled stream (``last_level_gain_db``)
         self._seed = None                # the sampling seed of an open ``seeded`` context
@@ -1146,6 +1184,7 @@ class FasterQwen3TTS:
         changes."""
         from .audio_out import AudioOutSpec
         spec = AudioOutSpec(sample_rate, encoding, speed).validate(self.sample_rate)
+        refuse_marked_speed(getattr(self, "_mark", None), spec)
         prev, self._audio_spec = getattr(self, "_audio_spec", None), spec
         try:
             yield spec
@@ -1251,6 +1290,55 @@ class FasterQwen3TTS:
             self._limit = prev
 
     @contextlib.contextmanager
+    def watermark(self, key: int, strength: float = 0.1):
+        """Context manager: inside it the single-stream entry points (``generate_*``, ``generate_*_streaming``, ``stream_*``), the
+        one-shot paths and long form put a keyed provenance watermark into their audio on the device (``fq3hip/watermark.py``,
+        DESIGN.md section 4.22): behind the join, the gains and the leveller, in front of the limiter -- whose ceiling therefore
+        still holds -- and the output stage.  The time-scale stage is part of the output stage, so it would run BEHIND the mark and
+        stretch its frame grid: together with a ``speed`` other than 1 (``audio_output``, a vocoder's ``output=``) the context raises
+        ``ValueError``.  The audio keeps its length; inside a stream the stage holds back 256
+        to 511 samples, which come with the final chunk (or one more, final, chunk).  The marked stream does not depend on how it was
+        cut into chunks beyond what the vocoder's windowing does (``exact_streaming``: not at all).  Long form marks the ONE joined
+        stream.  The ``*_batch`` entry points raise ``ValueError``.  ``key``: an integer in [0, 2^64), what ``detect_watermark``
+        needs; ``strength`` in [0.02, 0.3] (0, the stage's identity, is refused here: the context promises a mark), NOT tuned on real voices.  Yields the ``MarkSpec``.  Outside it nothing changes."""
+        from .watermark import MarkSpec, design
+        spec = MarkSpec(key, strength)
+        design(spec.key, spec.strength)                      # the library's own range checks (host only)
+        if spec.strength == 0.0:
+            raise ValueError("watermark(): strength 0 adds no mark; it is in [0.02, 0.3]")
+        refuse_marked_speed(spec, getattr(self, "_audio_spec", None))
+        if int(self.sample_rate) != 24000:
+            raise ValueError("the watermark is defined at 24 kHz")
+        prev, self._mark = getattr(self, "_mark", None), spec
+        try:
+            yield spec
+        finally:
+            self._mark = prev
+
+    def detect_watermark(self, audio, sr: int, key: int):
+        """Is the mark of ``key`` in ``audio`` (mono, a device tensor or a host array, at ``sr`` Hz)?  -> ``watermark.Detection(z,
+        offset, phase, present)``; ``present`` means ``z >= 6.0``."""
+        from .watermark import detect
+        return detect(audio, int(sr), key, self.device)
+
+    def _refuse_batch_watermark(self) -> None:
+        if getattr(self, "_mark", None) is not None:
+            raise ValueError("the batch entry points do not run the watermark stage yet: call them outside watermark(), or use the "
+                             "single-stream entry points")
+
+    def _marked(self, x, stream=None):
+        """A whole utterance (contiguous float32 device vector) through the open ``watermark`` context's stage on ``stream`` (None:
+        the current one): one object per (device, stream), kept, reset for every utterance."""
+        from .watermark import Watermark
+        s = stream if stream is not None else torch.cuda.current_stream(x.device)
+        marks = self.__dict__.setdefault("_marks", {})
+        key = (str(x.device), s.cuda_stream)
+        if key not in marks or marks[key].spec != self._mark:
+            marks[key] = Watermark(self._mark.key, self._mark.strength, x.device, s)
+        marks[key].reset()
+        return marks[key].push(x, final=True)
+
+    @contextlib.contextmanager
     def leveller(self, target_lufs: float = -16.0, ceiling_db: float = -1.0, max_gain_db: float = 20.0, initial_gain_db: float = 0.0,
                  smooth_hops: int = 10, min_blocks: int = 8):
         """Context manager: inside it every vocoder this model hands out (``streaming_vocoder``, hence every streaming entry point and
@@ -1326,7 +1414,7 @@ class FasterQwen3TTS:
 
     def _levelling(self) -> bool:
         return (getattr(self, "_loud", None) is not None or getattr(self, "_gain", None) is not None or getattr(self, "_limit", None) is not None
-                or getattr(self, "_lvl", None) is not None)
+                or getattr(self, "_lvl", None) is not None or getattr(self, "_mark", None) is not None)
 
     def _refuse_streaming_loudness(self) -> None:
         if getattr(self, "_loud", None) is not None:
@@ -1375,6 +1463,14 @@ class FasterQwen3TTS:
             x = apply_gain(x, gain, stream, out=x if inplace else None)
         if getattr(self, "_lvl", None) is not None:
             x = self._levelled(x, stream, inplace)
+        if getattr(self, "_mark", None) is not None:
+            # (the mark reads its frames' neighbours while other workgroups write: not in place either; ``x`` may be the caller's row)
+            y = self._marked(x, stream)
+            if inplace:
+                with torch.cuda.stream(stream if stream is not None else torch.cuda.current_stream(x.device)):
+                    x.copy_(y)
+            else:
+                x = y
         if getattr(self, "_limit", None) is None:
             return x
         y = self._limited(x, stream)
@@ -1419,6 +1515,9 @@ class FasterQwen3TTS:
             kw["leveller"] = self._lvl
             kw["leveller_pool"] = self.__dict__.setdefault("_leveller_pools", {}).setdefault(self._lvl.pooled, [])
             kw["leveller_hops"] = self._stream_level_hops()
+        if getattr(self, "_mark", None) is not None:
+            kw["mark"] = self._mark
+            kw["mark_pool"] = self.__dict__.setdefault("_mark_pools", {}).setdefault(self._mark, [])
         return kw
 
     def _seed_kw(self) -> dict:
@@ -1483,7 +1582,7 @@ class FasterQwen3TTS:
     def _tail_event(voc, timing: Optional[dict]):
         """After a streaming loop with an output stage: the stage's tail as one more chunk, when the last chunk was not marked final
         (an utterance that ends on a full chunk) -- with that event's timing, no codes, ``is_final``."""
-        if voc.output is None and getattr(voc, "limit_spec", None) is None:
+        if voc.output is None and getattr(voc, "limit_spec", None) is None and getattr(voc, "mark_spec", None) is None:
             return None
         tail, sr = voc.flush()
         if len(tail) == 0:
@@ -1765,6 +1864,7 @@ class FasterQwen3TTS:
         step (``_SideVocoder._encode_group``)."""
         if not device_audio:
             self._refuse_batch_audio_output()
+            self._refuse_batch_watermark()
         seeds = expand_seeds(seeds, count)
         meta: dict = {}
         dec = self._batch_decoder(lanes)
@@ -1847,6 +1947,7 @@ class FasterQwen3TTS:
         self._refuse_streaming_loudness()
         if not device_audio:
             self._refuse_batch_audio_output()
+            self._refuse_batch_watermark()
         gain = None if device_audio else self._gain_tensor()       # (long form multiplies behind the join)
         limit = None if device_audio else getattr(self, "_limit", None)      # (and limits there, as one stream)
         lvl = None if device_audio else getattr(self, "_lvl", None)         # (and levels there, likewise)
@@ -2312,6 +2413,7 @@ class FasterQwen3TTS:
         join = SegmentJoin.from_spec(spec, self.sample_rate, dev, stream=stream)
         chain = None
         output = self._audio_spec if output is None else output
+        refuse_marked_speed(getattr(self, "_mark", None), output)
         if output is not None:
             from .audio_out import AudioOut
             chain = AudioOut(output, self.sample_rate, join.dev, stream)
@@ -2325,6 +2427,10 @@ class FasterQwen3TTS:
             from .leveller import Leveller
             # behind the join and the gains, in front of the limiter: ONE leveller for the joined stream
             oj.leveller = Leveller(self._lvl, self.sample_rate, join.dev, stream, capacity_hops=max(level_hops or 0, 4096))
+        if getattr(self, "_mark", None) is not None:
+            from .watermark import Watermark
+            # behind the join, the gains and the leveller, in front of the limiter: ONE mark on the joined stream
+            oj.marker = Watermark(self._mark.key, self._mark.strength, join.dev, stream)
         self._last_levelled = oj.leveller
         return oj, chain
 
@@ -2470,6 +2576,7 @@ class FasterQwen3TTS:
         if isinstance(texts, str) or not isinstance(texts, (list, tuple)) or not texts:
             raise ValueError("texts must be a list of texts that is not empty")
         self._refuse_batch_audio_output()
+        self._refuse_batch_watermark()
         outputs = self._batch_outputs(output, len(texts))
         spec, segs = None, []
         for text in texts:

@@ -308,7 +308,7 @@ DEFAULT_LOUDNESS_TEXT = "The quick brown fox jumps over the lazy dog, and then i
 def create_app(model, voices: Dict[str, dict], default_voice: Optional[str] = None, scheduler: str = "lock", lanes: int = 8,
                chunk_size: int = 12, worker=None, prefix_cache_rows: int = 0, long_form=None, exact_streaming: bool = False,
                loudness: Optional[float] = None, loudness_text: str = DEFAULT_LOUDNESS_TEXT, limiter_db: Optional[float] = None,
-               level: Optional[float] = None):
+               level: Optional[float] = None, watermark_key: Optional[int] = None, watermark_strength: float = 0.1):
     """``worker``: a ready ``BatchWorker`` (or a stand-in with ``submit`` / ``submit_text``) instead of the one ``scheduler="batch"``
     would start.  ``prefix_cache_rows`` > 0: the model's prefix KV cache (``FasterQwen3TTS.enable_prefix_cache``) with that many rows:
     the engine's cache under the ``lock`` scheduler; under ``batch`` the ``BatchWorker`` started here creates the scheduler's own
@@ -384,10 +384,22 @@ def create_app(model, voices: Dict[str, dict], default_voice: Optional[str] = No
             logger.warning("--level without --limiter-db: the leveller does not limit, a passage louder than everything before it can "
                            "pass the ceiling (add --limiter-db)")
 
+    # ``watermark_key`` (None: off; server-wide, both schedulers and text sessions): every reply carries the keyed provenance mark
+    # (``model.watermark``; every vocoder the model hands out has the stage, the batch worker's per-request ones included), says so in
+    # ``X-Watermark: 1``, and a request with a ``speed`` other than 1 gets 400 (the time-scale stage would run behind the mark)
+    mark_headers = {}
+    if watermark_key is not None:
+        if not hasattr(model, "watermark"):
+            raise ValueError("watermark_key: this model has no watermark() context")
+        app.state.watermark = contextlib.ExitStack()
+        app.state.mark_spec = app.state.watermark.enter_context(model.watermark(watermark_key, float(watermark_strength)))
+        mark_headers = {"X-Watermark": "1"}
+
     def level_cfg(cfg: dict, name: str):
-        """``level``: the request's voice entry with the gain its voice learned and the hook that learns the next -> (cfg, headers)"""
+        """``level``: the request's voice entry with the gain its voice learned and the hook that learns the next -> (cfg, headers);
+        the headers also say that the reply is watermarked"""
         if level is None:
-            return cfg, {}
+            return cfg, dict(mark_headers)
         key = voice_key(cfg, name)
         with sessions_lock:
             start = learned.get(key)
@@ -397,7 +409,7 @@ def create_app(model, voices: Dict[str, dict], default_voice: Optional[str] = No
                 with sessions_lock:
                     learned[key] = round(float(gain_db), 3)
         cfg = dict(cfg, on_level=on_level, **({} if start is None else dict(initial_gain_db=start)))
-        return cfg, ({} if start is None else {"X-Initial-Gain-Db": f"{start:.3f}"})
+        return cfg, dict(mark_headers, **({} if start is None else {"X-Initial-Gain-Db": f"{start:.3f}"}))
 
     if limiter_db is not None:
         if not hasattr(model, "limiter"):
@@ -422,6 +434,9 @@ def create_app(model, voices: Dict[str, dict], default_voice: Optional[str] = No
         is the ``flac`` encoding of the stage (with the request's rate and speed); it is the whole answer's format, so a request that
         also names an ``encoding`` gets 400, and so does ``encoding="flac"`` under another format."""
         from .audio_out import AudioOutSpec
+        if watermark_key is not None and req.speed != 1.0:
+            raise HTTPException(status_code=400, detail="this server watermarks its audio, and the time-scale stage would run behind the "
+                                                        "mark and defeat its detector: 'speed' must be 1")
         if fmt == "flac":
             if req.encoding is not None:
                 raise HTTPException(status_code=400, detail="response_format='flac' is an encoding of its own (the s16 samples, compressed "
@@ -639,6 +654,8 @@ def create_app(model, voices: Dict[str, dict], default_voice: Optional[str] = No
         if limiter_db is not None:
             spec = app.state.limiter_spec                   # the LimiterSpec in force, as the model's context yielded it
             out["limiter"] = {k: float(getattr(spec, k)) for k in ("ceiling_db", "lookahead_ms", "hold_ms")}
+        if watermark_key is not None:
+            out["watermark"] = {"strength": float(app.state.mark_spec.strength)}      # (never the key)
         if level is not None:
             spec = app.state.level_spec                     # the LevelSpec in force, as the model's context yielded it
             with sessions_lock:
@@ -713,6 +730,11 @@ def build_parser():
                    help="calibrate every voice at start-up (one seeded synthesis of --loudness-text, measured on the device by BS.1770) and "
                         "stream its replies with the fixed gain that brings that sentence to LUFS; --scheduler lock only (default: off)")
     p.add_argument("--loudness-text", default=DEFAULT_LOUDNESS_TEXT, metavar="TEXT", help="the calibration sentence of --loudness")
+    p.add_argument("--watermark-key", type=lambda v: int(v, 0), default=None, metavar="KEY",
+                   help="put a keyed provenance watermark into every reply on the device (KEY: an integer in [0, 2^64)); both schedulers "
+                        "and text sessions; replies carry X-Watermark: 1, /health says so; a request's speed must then be 1 (default: off)")
+    p.add_argument("--watermark-strength", type=float, default=0.1, metavar="A",
+                   help="--watermark-key: the mark's strength, 0.02 to 0.3; NOT tuned on real voices (default: 0.1)")
     p.add_argument("--limiter-db", type=float, default=None, metavar="DB",
                    help="server-wide true-peak look-ahead limiter on the device: no sample of any reply leaves above DB dBFS (-20 to 0); both "
                         "schedulers and the text sessions.  With --loudness the two together are the safe way to serve a levelled stream: a "
@@ -734,6 +756,8 @@ def main(argv=None):
         parser.error("--level is a target in LUFS, -40 to -5")
     if args.loudness is not None and args.scheduler == "batch":
         parser.error("--loudness is served by the lock scheduler: add --scheduler lock (the batch worker has no per-request gain yet)")
+    if args.watermark_key is not None and not (0 <= args.watermark_key < 1 << 64 and 0.02 <= args.watermark_strength <= 0.3):
+        parser.error("--watermark-key is an integer in [0, 2^64), --watermark-strength is in [0.02, 0.3]")
     if args.limiter_db is not None and not -20.0 <= args.limiter_db <= 0.0:
         parser.error("--limiter-db is a ceiling in dBFS, -20 to 0")
     if args.voices:
@@ -754,7 +778,8 @@ def main(argv=None):
     logging.basicConfig(level=logging.INFO)
     uvicorn.run(create_app(model, voices, default_voice, args.scheduler, args.lanes, args.chunk_size,
                            prefix_cache_rows=args.prefix_cache_rows, exact_streaming=args.exact_streaming, loudness=args.loudness,
-                           loudness_text=args.loudness_text, limiter_db=args.limiter_db, level=args.level), host=args.host, port=args.port)
+                           loudness_text=args.loudness_text, limiter_db=args.limiter_db, level=args.level,
+                           watermark_key=args.watermark_key, watermark_strength=args.watermark_strength), host=args.host, port=args.port)
 
 
 if __name__ == "__main__":

@@ -1,0 +1,172 @@
+"""A provenance watermark on the device (``fq3_mark_*``): a keyed spread-spectrum mark in the 516 .. 3469 Hz
+band of a float32 stream at 24 kHz, and its detector.  Length-preserving; the marked stream does not depend on how it was cut into
+pushes, bit for bit.  Both run as DFT-as-GEMM on the fp32 matrix cores; there is no CPU fallback.
+
+``design``      the constants and the chip rows of a key (``fq3_mark_design``; no GPU needed)
+``count``       output samples that exist after ``n_in`` input samples (``fq3_mark_count``; no GPU needed)
+``Watermark``   one stream on a device: ``push`` / ``flush`` / ``reset``
+``detect``      ``Detection(z, offset, phase, present)`` of a signal at any rate for a key"""
+from __future__ import annotations
+
+import ctypes as C
+from dataclasses import dataclass
+from typing import Optional
+
+import numpy as np
+import torch
+
+from . import _lib
+
+RATE = 24000
+N, H, PERIOD, N_OFFSETS, OFFSET_STEP = 512, 256, 128, 32, 8
+STRENGTH_RANGE = (0.02, 0.3)
+THRESHOLD = 6.0          # 4096 hypotheses x Q(6.0): about 4e-6 false positives per clip
+
+
+def _key(key) -> int:
+    if isinstance(key, bool) or not isinstance(key, (int, np.integer)) or not 0 <= int(key) < 1 << 64:
+        raise ValueError(f"key must be an integer in [0, 2^64), not {key!r}")
+    return int(key)
+
+
+def _strength(strength) -> float:
+    if isinstance(strength, bool) or not isinstance(strength, (int, float, np.integer, np.floating)) \
+            or not (float(strength) == 0.0 or STRENGTH_RANGE[0] <= float(strength) <= STRENGTH_RANGE[1]):
+        raise ValueError(f"strength must be 0 (the identity) or a number in [{STRENGTH_RANGE[0]}, {STRENGTH_RANGE[1]}], not {strength!r}")
+    return float(strength)
+
+
+@dataclass(frozen=True)
+class MarkSpec:
+    """What ``FasterQwen3TTS.watermark`` keeps: the 64-bit ``key`` and the ``strength`` a (the mark is ``a`` times the band, about
+    ``20 log10(a)`` dB below the voice in that band).  0.1 is NOT tuned on real voices."""
+    key: int
+    strength: float = 0.1
+
+    def __post_init__(self):
+        _key(self.key)
+        _strength(self.strength)
+
+
+def design(key: int, strength: float = 0.1):
+    """``fq3_mark_design`` (host only): -> (a as the device's float32, the chip rows as int8 [128][64] of -1 / +1)."""
+    lib = _lib.load()
+    a, words = C.c_float(), (C.c_uint32 * (2 * PERIOD))()
+    if lib.fq3_mark_design(_key(key), float(strength), None, None, None, None, None, C.byref(a), words) != 0:
+        raise ValueError(lib.fq3_last_error().decode("utf-8", "replace"))
+    w = np.frombuffer(words, dtype=np.uint32).reshape(PERIOD, 2)
+    j = np.arange(64)
+    return np.float32(a.value), (((w[:, j >> 5] >> (j & 31).astype(np.uint32)) & 1).astype(np.int8) * 2 - 1)
+
+
+def count(n_in: int, final: bool) -> int:
+    """``fq3_mark_count``: ``n_in`` when ``final``, else ``max(0, n_in // 256 - 1) * 256``."""
+    lib = _lib.load()
+    n = lib.fq3_mark_count(int(n_in), 1 if final else 0)
+    if n < 0:
+        raise ValueError(lib.fq3_last_error().decode("utf-8", "replace"))
+    return int(n)
+
+
+def _device(device) -> torch.device:
+    dev = torch.device(device) if not isinstance(device, torch.device) else device
+    if dev.type != "cuda":
+        raise ValueError("the watermark runs on the GPU; there is no CPU fallback")
+    return torch.device("cuda", torch.cuda.current_device()) if dev.index is None else dev
+
+
+class Watermark:
+    """One stream through the mark.  ``push(pcm)`` takes the next float32 samples (a device tensor) and returns the samples that
+    became final -- ``count(total so far) - count(before)`` of them, a device tensor, one launch, nothing synchronises;
+    ``push(..., final=True)`` or ``flush()`` ends the stream and hands out what was held back (between 256 and 511 samples).
+    ``reset()`` starts a new stream on the same object.  Work is enqueued on ``stream`` (default: the current stream)."""
+
+    def __init__(self, key: int, strength: float = 0.1, device="cuda", stream=None):
+        self.spec = MarkSpec(_key(key), _strength(strength))
+        self.dev = _device(device)
+        self.stream = stream
+        self._lib = _lib.load()
+        self._h = C.c_void_p()
+        cfg = _lib.MarkConfig(self.spec.key, self.spec.strength)
+        with torch.cuda.device(self.dev):
+            _lib.check(self._lib.fq3_mark_create(C.byref(cfg), C.byref(self._h)))
+        self.n_in, self.n_out, self.finished = 0, 0, False
+
+    def __del__(self):
+        h, self._h = getattr(self, "_h", None), None
+        if h:
+            self._lib.fq3_mark_destroy(h)
+
+    def _stream(self):
+        return self.stream if self.stream is not None else torch.cuda.current_stream(self.dev)
+
+    def reset(self) -> None:
+        _lib.check(self._lib.fq3_mark_reset(self._h, C.c_void_p(self._stream().cuda_stream)))
+        self.n_in, self.n_out, self.finished = 0, 0, False
+
+    def push(self, pcm: Optional[torch.Tensor], final: bool = False) -> torch.Tensor:
+        s = self._stream()
+        with torch.cuda.device(self.dev), torch.cuda.stream(s):
+            x = None if pcm is None else pcm.reshape(-1)
+            if x is not None and (x.dtype != torch.float32 or x.device != self.dev or not x.is_contiguous()):
+                x = x.to(device=self.dev, dtype=torch.float32).contiguous()
+            n = 0 if x is None else int(x.numel())
+            total = self.n_in + n
+            room = max((total if final else max(0, total // H - 1) * H) - self.n_out, 0)
+            out = torch.empty(room, dtype=torch.float32, device=self.dev)
+            got = C.c_int64()
+            _lib.check(self._lib.fq3_mark_push(self._h, C.c_void_p(x.data_ptr() if n else None), n, 1 if final else 0,
+                                               C.c_void_p(out.data_ptr() if room else None), room, C.byref(got), C.c_void_p(s.cuda_stream)))
+            if n:
+                x.record_stream(s)
+            out.record_stream(s)
+        self.n_in = total
+        self.n_out += int(got.value)
+        self.finished = self.finished or bool(final)
+        return out[:got.value]
+
+    def flush(self) -> torch.Tensor:
+        """ends the stream: the held-back samples"""
+        return self.push(None, final=True)
+
+
+@dataclass(frozen=True)
+class Detection:
+    """``z``: the largest detector statistic over 32 sample offsets and 128 frame phases; ``offset`` (samples, a multiple of 8) and
+    ``phase`` where it was found; ``present``: ``z >= 6.0``."""
+    z: float
+    offset: int
+    phase: int
+    present: bool
+
+
+def detect_table(pcm, rate: int, key: int, device="cuda") -> torch.Tensor:
+    """The detector's whole table ``z[32][128]`` (a device tensor): two launches on the current stream.  ``pcm``: a mono signal, a
+    tensor or an array; at another rate than 24 kHz it goes through ``audio_out.resample_device`` first."""
+    dev = _device(pcm.device if isinstance(pcm, torch.Tensor) and pcm.is_cuda else device)
+    lib, key = _lib.load(), _key(key)
+    with torch.cuda.device(dev):
+        if int(rate) != RATE:
+            from .audio_out import resample_device
+            pcm = resample_device(pcm.detach().cpu().numpy() if isinstance(pcm, torch.Tensor) else pcm, int(rate), RATE, dev)
+        x = torch.as_tensor(np.asarray(pcm, dtype=np.float32) if not isinstance(pcm, torch.Tensor) else pcm)
+        x = x.to(device=dev, dtype=torch.float32).reshape(-1).contiguous()
+        n = int(x.numel())
+        need = lib.fq3_mark_detect_workspace(n)
+        if need < 0:
+            raise ValueError(lib.fq3_last_error().decode("utf-8", "replace"))
+        work = torch.empty(int(need), dtype=torch.float32, device=dev)
+        z = torch.empty((N_OFFSETS, PERIOD), dtype=torch.float32, device=dev)
+        s = torch.cuda.current_stream(dev)
+        _lib.check(lib.fq3_mark_detect(C.c_void_p(x.data_ptr()), n, key, C.c_void_p(work.data_ptr()), int(need), C.c_void_p(z.data_ptr()),
+                                       C.c_void_p(s.cuda_stream)))
+        for t in (x, work, z):
+            t.record_stream(s)
+    return z
+
+
+def detect(pcm, rate: int, key: int, device="cuda") -> Detection:
+    """Is the mark of ``key`` in ``pcm``?  One copy brings the table to the host."""
+    z = detect_table(pcm, rate, key, device).cpu().numpy()
+    oi, ph = np.unravel_index(int(np.argmax(z)), z.shape)
+    return Detection(float(z[oi, ph]), int(oi) * OFFSET_STEP, int(ph), bool(z[oi, ph] >= THRESHOLD))

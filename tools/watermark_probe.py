@@ -1,0 +1,112 @@
+#!/usr/bin/env python3
+"""Times the watermark stage (fq3hip/watermark.py: fq3_mark_push, one launch, a workgroup per 15 hops; fq3_mark_detect, two launches)
+ALONE, with HIP events, beside the bf16x2 vocoder's streaming-chunk decode (25 context + 8 new frames, the tail of 8 produced) in the
+same run and on the same stream: stage and vocoder ALTERNATE inside every repeat, each between its own event pair, and the figures are
+medians over the repeats after a warm-up (``loudness_probe.alternate`` holds the method).
+  push    an 8-frame streaming chunk (15 360 samples; one non-final push into a stream that is already running) and a 370-frame
+          utterance (710 400 samples; reset + one final push)
+  detect  over 3 s and over 30 s at 24 kHz
+Also, so that one file holds them: the embed and detect error bounds of tests/test_gpu_watermark.py with the device's errors, and the
+a = 0.1 repeat on the synthetic voiced signal of tests/_mark_ref.py -- SNR and the detector's max z for the marked signal behind s16,
+cropped by 1000 samples, behind a 24 -> 8 -> 24 kHz round trip, unmarked and under another key.  Writes profiles/watermark.json.
+usage: watermark_probe.py [runs=60] [out.json]"""
+import json
+import os
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "faster-qwen3-tts_amd")); sys.path.insert(0, os.path.join(ROOT, "tests"))
+import numpy as np
+import torch
+from fq3hip import watermark as W
+from loudness_probe import SAMPLES_PER_FRAME, alternate, speech_like
+
+KEY, A = 0x0123456789ABCDEF, float(np.float32(0.1))
+
+
+def mark(x, strength=0.1):
+    return W.Watermark(KEY, strength, "cuda").push(torch.from_numpy(np.array(x)).cuda(), final=True).cpu().numpy()
+
+
+def accuracy():
+    """the GPU test's bounds (4 x the numpy-float32 evaluation's deviation from float64) and the device's errors on the same inputs"""
+    import _mark_ref as R
+    rows = {"embed": [], "detect": []}
+    for n in (1, 255, 256, 257, 511, 512, 513, 769, 4000):
+        x = R.voiced(0.2)[300:300 + n]
+        ref = R.embed(x, KEY, A)
+        rows["embed"].append({"n": n, "bound": 4.0 * float(np.max(np.abs(R.embed(x, KEY, A, np.float32) - ref))),
+                              "device_error": float(np.max(np.abs(mark(x).astype(np.float64) - ref)))})
+    x = R.voiced(3.0)
+    y = mark(x)
+    s16 = (np.round(y.astype(np.float64) * 32767.0) / 32767.0).astype(np.float32)
+    for drop in (0, 1000):
+        ref = R.detect_table(s16[drop:], KEY)
+        z = W.detect_table(s16[drop:], 24000, KEY).cpu().numpy()
+        rows["detect"].append({"drop": drop, "bound": 4.0 * float(np.max(np.abs(R.detect_table(s16[drop:], KEY, np.float32) - ref))),
+                               "device_error": float(np.max(np.abs(z - ref))), "max_z_device": float(z.max()), "max_z_ref64": float(ref.max())})
+    from fq3hip.audio_out import resample_device
+    back = resample_device(resample_device(s16, 24000, 8000, "cuda"), 8000, 24000, "cuda")
+    noise = x.astype(np.float64) - y
+    rows["repeat_a_0p1"] = {
+        "signal": "tests/_mark_ref.voiced(3.0): harmonic stack, moving f0, 2.3 Hz envelope, noise floor; NOT a real voice",
+        "snr_db": float(10 * np.log10(np.sum(x.astype(np.float64) ** 2) / np.sum(noise ** 2))),
+        "max_z": {"marked_s16": W.detect(s16, 24000, KEY).z, "cropped_1000": W.detect(s16[1000:], 24000, KEY).z,
+                  "round_trip_24_8_24": W.detect(back, 24000, KEY).z, "at_8_khz": W.detect(resample_device(s16, 24000, 8000, "cuda"), 8000, KEY).z,
+                  "unmarked": W.detect(x, 24000, KEY).z, "other_key": W.detect(s16, 24000, KEY + 1).z,
+                  "marked_6s": W.detect(mark(R.voiced(6.0)), 24000, KEY).z},
+        "threshold": W.THRESHOLD}
+    return rows
+
+
+def main():
+    runs = max(20, int(sys.argv[1])) if len(sys.argv) > 1 else 60
+    out_path = sys.argv[2] if len(sys.argv) > 2 else os.path.join(ROOT, "profiles", "watermark.json")
+    from fq3hip.codec import HipSpeechTokenizer
+    from fq3hip.config import qwen3_tts_0p6b
+    from fq3hip.weights import synth_weights
+    g = torch.Generator().manual_seed(3)
+    cfg = qwen3_tts_0p6b()
+    wts = synth_weights(cfg, 0, torch.bfloat16, parts=("codec",), codec_normalized=True)
+    tok = HipSpeechTokenizer(cfg.codec, wts, "cuda", max_frames=400, precision="bf16x2")
+    codes = torch.randint(0, cfg.codec.codebook_size, (33, 16), generator=g).cuda()
+    first = tok.num_samples_total(33) - 8 * SAMPLES_PER_FRAME
+    chunk, utt = speech_like(8 * SAMPLES_PER_FRAME, g), speech_like(370 * SAMPLES_PER_FRAME, g)
+    sec3, sec30 = speech_like(3 * 24000, g), speech_like(30 * 24000, g)
+    running, whole = W.Watermark(KEY, 0.1, "cuda"), W.Watermark(KEY, 0.1, "cuda")
+    running.push(chunk)                                            # the stream is running: the history is full from here on
+
+    def utterance():
+        whole.reset()
+        return whole.push(utt, final=True)
+    t = alternate({"push chunk": lambda: running.push(chunk), "push utterance": utterance,
+                   "detect 3 s": lambda: W.detect_table(sec3, 24000, KEY), "detect 30 s": lambda: W.detect_table(sec30, 24000, KEY),
+                   "vocoder": lambda: tok.decode_tensor(codes, first)}, runs)
+    voc = t["vocoder"]
+    res = {"device": torch.cuda.get_device_name(0), "runs": runs, "rate": 24000, "frame": W.N, "hop": W.H, "strength": A,
+           "method": "HIP events around each call, the stage's calls and the vocoder alternating inside every repeat, medians",
+           "yardstick": "bf16x2 vocoder, streaming-chunk decode: 25 context + 8 new frames, the tail of 8 produced",
+           "vocoder_chunk_ms": round(voc, 4),
+           "push": [{"input": "streaming chunk, 8 frames", "n_in": int(chunk.numel()), "push": "one push of a running stream",
+                     "workgroups": -(-(int(chunk.numel()) // W.H) // 15) + 1, "ms": round(t["push chunk"], 4),
+                     "share_of_vocoder_chunk": round(t["push chunk"] / voc, 5)},
+                    {"input": "utterance, 370 frames", "n_in": int(utt.numel()), "push": "reset + one final push",
+                     "workgroups": -(-(-(-int(utt.numel()) // W.H)) // 15) + 1, "ms": round(t["push utterance"], 4),
+                     "share_of_vocoder_chunk": round(t["push utterance"] / voc, 5)}],
+           "detect": [{"seconds": s, "n": int(x.numel()), "launches": 2, "ms": round(t[k], 4), "share_of_vocoder_chunk": round(t[k] / voc, 5)}
+                      for s, x, k in ((3, sec3, "detect 3 s"), (30, sec30, "detect 30 s"))],
+           "hold_back_ms": [round(1000 * W.H / 24000, 2), round(1000 * (2 * W.H - 1) / 24000, 2)],
+           "notes": ["an event pair around ONE short launch includes what starting it costs, and the Python wrapper's output allocation "
+                     "lies inside it too; detect's figures include its workspace and table allocations",
+                     "NOT measured: audibility on real voices, robustness to lossy codecs, to a change of time scale after marking "
+                     "(refused by the model: speed != 1 with the mark), and to deliberate removal; the strength 0.1 is not tuned on real voices"]}
+    res["accuracy"] = accuracy()
+    os.makedirs(os.path.dirname(out_path) or ".", exist_ok=True)
+    with open(out_path, "w") as f:
+        json.dump(res, f, indent=1)
+        f.write("\n")
+    print(json.dumps(res, indent=1))
+
+
+if __name__ == "__main__":
+    main()

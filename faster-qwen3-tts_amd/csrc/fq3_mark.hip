@@ -4,6 +4,7 @@
 //   fq3_mark_design / _count   host only (no HIP call): the framing constants, the strength as the device's float, the chip words
 //   fq3_mark_create / _push    ONE launch per push: a workgroup per 15 hops of output plus one that keeps the history
 //   fq3_mark_detect            two launches: the partial sums of every (offset, frame tile), then z[32][128]
+//   fq3_mark_scan              two launches for up to 32 clips: the sums of every block of 16 frames, then a verdict per sliding window
 // The host tracks what follows from the lengths alone: samples pushed, samples emitted, which history buffer is current, whether the
 // stream has ended.  The two DFT tables (2 x 256 KB) depend on nothing a caller chooses: one copy per device, made at the first
 // create or detect there and kept for the life of the process.
@@ -99,6 +100,25 @@ int64_t count_(int64_t total, int final) {
 
 int64_t detect_frames_(int64_t n) { return (n + kMarkH - 1) / kMarkH + 1; }
 int64_t detect_tiles_(int64_t n) { return (detect_frames_(n) - 2 + kMarkInner - 1) / kMarkInner; }
+
+constexpr int kMaxWinBlocks = 4096;
+int64_t scan_blocks_(int64_t n) { return (detect_frames_(n) - 2 + kMarkBlock - 1) / kMarkBlock; }
+int64_t scan_windows_(int64_t nb, int win, int hop) { return nb <= win ? 1 : 1 + (nb - win + hop - 1) / hop; }
+
+int scan_check_(const std::string& who, int win_blocks, int hop_blocks) {
+    if (win_blocks < 1 || win_blocks > kMaxWinBlocks) return fq3_fail_(FQ3_EINVAL, who + ": win_blocks outside [1, 4096]");
+    if (hop_blocks < 1 || hop_blocks > win_blocks) return fq3_fail_(FQ3_EINVAL, who + ": hop_blocks outside [1, win_blocks]");
+    return 0;
+}
+
+int scan_rows_(const std::string& who, int B, const int64_t* n) {
+    if (B < 0 || B > FQ3_STAGE_GROUP_MAX)
+        return fq3_fail_(FQ3_EINVAL, who + ": B = " + std::to_string(B) + "; a call has 0 to " + std::to_string(FQ3_STAGE_GROUP_MAX) + " rows");
+    if (B > 0 && !n) return fq3_fail_(FQ3_EINVAL, who + ": null array");
+    for (int b = 0; b < B; ++b)
+        if (n[b] < 2 * kMarkH || n[b] > kMaxDetect) return fq3_fail_(FQ3_EINVAL, who + ": row " + std::to_string(b) + ": n outside [512, 2^27]");
+    return 0;
+}
 
 }  // namespace
 
@@ -217,6 +237,69 @@ extern "C" int fq3_mark_detect(const float* pcm, int64_t n, uint64_t key, float*
     hipLaunchKernelGGL(mark_detect_kernel, dim3((unsigned)tiles, kMarkOffsets), dim3(kMarkThreads), 0, (hipStream_t)stream, k);
     KHIP(hipGetLastError());
     hipLaunchKernelGGL(mark_reduce_kernel, dim3(kMarkOffsets), dim3(kMarkPeriod), 0, (hipStream_t)stream, (const float*)work, (int)tiles, z);
+    KHIP(hipGetLastError());
+    return 0;
+}
+
+// ---- scan: per-window verdicts of up to 32 clips, two launches per call -----------------------------------------------------------------
+static_assert(sizeof(fq3_mark_window) == sizeof(MarkVerdict), "fq3_mark_window is the window kernel's record");
+static_assert(FQ3_STAGE_GROUP_MAX == kMarkScanMax, "the header's limit is the descriptor table's size");
+
+extern "C" int64_t fq3_mark_scan_windows(int64_t n, int win_blocks, int hop_blocks) {
+    if (n < 2 * kMarkH || n > kMaxDetect) return fq3_fail_(FQ3_EINVAL, "fq3_mark_scan_windows: n outside [512, 2^27]");
+    if (int rc = scan_check_("fq3_mark_scan_windows", win_blocks, hop_blocks)) return rc;
+    return scan_windows_(scan_blocks_(n), win_blocks, hop_blocks);
+}
+
+extern "C" int64_t fq3_mark_scan_workspace(int B, const int64_t* n) {
+    if (int rc = scan_rows_("fq3_mark_scan_workspace", B, n)) return rc;
+    int64_t blocks = 0;
+    for (int b = 0; b < B; ++b) blocks += scan_blocks_(n[b]);
+    return blocks * kMarkBlockDoubles;
+}
+
+extern "C" int fq3_mark_scan(int B, const float* const* pcm, const int64_t* n, const uint64_t* key, int win_blocks, int hop_blocks,
+                             double* work, int64_t work_doubles, fq3_mark_window* out, float* tables, void* stream) {
+    if (int rc = scan_rows_("fq3_mark_scan", B, n)) return rc;
+    if (int rc = scan_check_("fq3_mark_scan", win_blocks, hop_blocks)) return rc;
+    if (B == 0) return 0;
+    if (!pcm || !key || !work || !out) return fq3_fail_(FQ3_EINVAL, "fq3_mark_scan: null argument");
+    MarkScanArgs k{};
+    int64_t blocks = 0, windows = 0;
+    for (int b = 0; b < B; ++b) {
+        if (!pcm[b]) return fq3_fail_(FQ3_EINVAL, "fq3_mark_scan: row " + std::to_string(b) + ": null pointer");
+        MarkScanRow& r = k.rows[b];
+        r.pcm = pcm[b]; r.n = (int)n[b]; r.T = (int)detect_frames_(n[b]); r.NB = (int)scan_blocks_(n[b]);
+        r.W = (int)scan_windows_(r.NB, win_blocks, hop_blocks);
+        r.blk0 = (int)blocks; r.win0 = (int)windows;
+        r.k0 = (uint32_t)(key[b] & 0xffffffffull); r.k1 = (uint32_t)(key[b] >> 32);
+        blocks += r.NB; windows += r.W;
+    }
+    if (work_doubles < blocks * kMarkBlockDoubles)
+        return fq3_fail_(FQ3_EINVAL, "fq3_mark_scan: the workspace is smaller than fq3_mark_scan_workspace(B, n)");
+    const float* dev_tables = nullptr;
+    if (int rc = device_tables_(&dev_tables)) return rc;
+    // The cut into (range of R blocks) x (group of G offsets) changes no result (mark_kernels.cuh): take the coarsest of these that
+    // still gives the machine two workgroups per compute unit, so that few clips spread out and many clips re-use what they staged.
+    static const int cuts[][2] = {{16, 8}, {8, 8}, {8, 4}, {4, 4}, {4, 2}, {2, 2}, {2, 1}};
+    int64_t grid = 0;
+    for (const auto& c : cuts) {
+        k.R = c[0]; k.G = c[1];
+        grid = 0;
+        for (int b = 0; b < B; ++b) grid += (int64_t)((k.rows[b].NB + k.R - 1) / k.R) * (kMarkOffsets / k.G);
+        if (grid >= 512) break;
+    }
+    int64_t at = 0;
+    for (int b = 0; b < kMarkScanMax; ++b) {
+        k.part_wg0[b] = (int)at;
+        k.win_wg0[b] = b < B ? k.rows[b].win0 : (int)windows;
+        if (b < B) at += (int64_t)((k.rows[b].NB + k.R - 1) / k.R) * (kMarkOffsets / k.G);
+    }
+    k.fwd = dev_tables; k.work = work; k.out = reinterpret_cast<MarkVerdict*>(out); k.tables = tables;
+    k.win_blocks = win_blocks; k.hop_blocks = hop_blocks;
+    hipLaunchKernelGGL(mark_scan_blocks_kernel, dim3((unsigned)grid), dim3(kMarkThreads), 0, (hipStream_t)stream, k);
+    KHIP(hipGetLastError());
+    hipLaunchKernelGGL(mark_scan_windows_kernel, dim3((unsigned)windows), dim3(kMarkScanWinThreads), 0, (hipStream_t)stream, k);
     KHIP(hipGetLastError());
     return 0;
 }

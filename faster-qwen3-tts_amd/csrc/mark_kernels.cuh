@@ -237,4 +237,254 @@ __global__ void __launch_bounds__(kMarkPeriod) mark_reduce_kernel(const float* p
     gptr(z)[blockIdx.x * kMarkPeriod + threadIdx.x] = e > 0.0 ? (float)(s / sqrt(e)) : 0.0f;
 }
 
+// ---- Scan: which windows of up to 32 clips carry the mark (fq3_mark_scan; include/fq3hip.h states the windows) -------------------------
+// The detector's sums are kept per BLOCK of 16 d frames (block b: frames 1 + 16 b .. 16 + 16 b, cut at T - 2) instead of per clip, and
+// a window is a sum over blocks: overlapping windows cost nothing in the kernel that does the DFTs.
+//   blocks    one packed 1-D grid over all rows: part_wg0[b] is the first workgroup of row b (rows past the last hold the grid size,
+//             as in flac_kernels.cuh); inside a row a workgroup is (range of R blocks, group of G of the 32 offsets).  It walks the
+//             M tiles bt = b0 .. b1 of its range; tile bt holds L of frames 16 bt .. 16 bt + 15.
+//   staging   the 32 offsets of a tile lie within 248 samples, so ONE run of 18 hops (17 + the offsets' reach) serves every offset of the
+//             group: the forward product of offset o reads the run shifted by o, nothing is staged per offset.  From tile to tile the
+//             run's last two hops are moved to its front inside the LDS and 16 new hops are read: every sample is read from memory once
+//             per workgroup.  d of frame t needs L of t - 1 and t + 1: the last two L rows of a tile are kept per offset (Lp), so tile
+//             bt yields d of frames 16 bt - 1 .. 16 bt + 14 -- the last two frames of block bt - 1 and the first 14 of block bt -- and no
+//             frame's DFT is formed twice inside a range (a range costs one tile more than it has blocks, and not even that at the clip's
+//             end when the tile would hold no frame up to T - 2).
+//   chips     the correlation with the chips is a GEMM as well: g[16 frames][128 chip rows] = d[16][64] . C^T[64][128], K = 64 in 16
+//             steps, wave w the chip rows 32 w .. 32 w + 31.  The B operand is never in memory: lane (fr, fq) of an N tile needs bits
+//             4 ks + fq of ONE chip row, two Philox words it holds in registers for the whole kernel, and makes +-1.0f from a bit per
+//             step.  The products are exact (+-d) and 64 of them are added in fp32 by the matrix core; frame t's contribution to phase p
+//             is g[t][(t + p) mod 128], gathered from the LDS and added in double: 16 adds per phase and tile where mark_detect_kernel
+//             spends 448 converts and adds per thread.
+//   carry     block b's sums are closed by tile b + 1: (first 14 frames, carried in the LDS in double) + (last two frames).  The order
+//             inside a block is fixed and no sum crosses a block, so S and E of a block do not depend on R, G, the range it fell in or
+//             the other rows of the call, bit for bit.
+//   windows   one workgroup per (row, window): the blocks' S and E in ascending order, z = S / sqrt(E), the optional table, and the
+//             verdict (max z, the lowest index among equals) by a shuffle reduction.
+constexpr int kMarkBlock = 16;                      // d frames of a scan block: one M tile
+constexpr int kMarkScanMax = 32;                    // FQ3_STAGE_GROUP_MAX
+constexpr int kMarkScanOffs = 8;                    // most offsets one workgroup walks over a staged run
+constexpr int kMarkScanHops = kMarkRows + 2;        // 17 hops of 16 frames and one more for the offsets' reach (248 samples)
+constexpr int kMarkScanRunLds = kMarkScanHops * (kMarkH + 4);
+constexpr int kMarkDdLd = kMarkBins + 4, kMarkGLd = kMarkPeriod + 4;
+constexpr int kMarkBlockDoubles = kMarkOffsets * kMarkPeriod + kMarkOffsets;     // a block's slot: S[32][128], then E[32]
+constexpr int kMarkScanWinThreads = 256;
+
+struct MarkVerdict { float z; int32_t offset, phase, present; };                // fq3_mark_window
+
+struct MarkScanRow {
+    const float* pcm;
+    int n, T, NB, W;
+    int blk0, win0;            // the row's first block / window in the packed workspace / outputs
+    uint32_t k0, k1;
+};
+
+struct MarkScanArgs {
+    const float* fwd;
+    double* work;              // [sum NB][kMarkBlockDoubles]
+    MarkVerdict* out;          // [sum W]
+    float* tables;             // [sum W][32][128], or null
+    int R, G;                  // blocks per range, offsets per workgroup (G divides 32, G <= kMarkScanOffs)
+    int win_blocks, hop_blocks;
+    int part_wg0[kMarkScanMax], win_wg0[kMarkScanMax];
+    MarkScanRow rows[kMarkScanMax];
+};
+static_assert(sizeof(MarkScanRow) == 40 && sizeof(MarkScanArgs) <= 4096, "the descriptors must fit the 4 KB of arguments a launch may carry");
+
+// mark_forward over the 18-hop run with every frame shifted by o samples: the same products in the same four chains (a copy, so that
+// mark_forward and the kernels built on it stay untouched)
+__device__ __forceinline__ void mark_forward_at(const float* run, const int o, const float* __restrict__ fwd, int wave, int lane, mark_f32x4& re_out,
+                                                mark_f32x4& im_out) {
+    const int fr = lane & 15, fq = lane >> 4;
+    const float* tc = fwd + (size_t)wave * (128 * 64) + lane;
+    const float* ts = fwd + (size_t)(4 + wave) * (128 * 64) + lane;
+    mark_f32x4 re[4], im[4];
+#pragma unroll
+    for (int c = 0; c < 4; ++c) re[c] = im[c] = mark_f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll 2
+    for (int ks = 0; ks < 128; ks += 4)
+#pragma unroll
+        for (int c = 0; c < 4; ++c) {
+            const float a = run[mark_run_at(o + fr * kMarkH + (ks + c) * 4 + fq)];
+            re[c] = __builtin_amdgcn_mfma_f32_16x16x4f32(a, tc[(ks + c) * 64], re[c], 0, 0, 0);
+            im[c] = __builtin_amdgcn_mfma_f32_16x16x4f32(a, ts[(ks + c) * 64], im[c], 0, 0, 0);
+        }
+    re_out = (re[0] + re[1]) + (re[2] + re[3]);
+    im_out = (im[0] + im[1]) + (im[2] + im[3]);
+}
+
+__device__ __forceinline__ int mark_scan_row(const int* wg0, const int wg) {
+    int row = 0;
+#pragma unroll
+    for (int b = 1; b < kMarkScanMax; ++b) row += wg >= wg0[b] ? 1 : 0;         // wg0 does not decrease: the last row that starts at or before wg
+    return row;
+}
+
+__global__ void __launch_bounds__(kMarkThreads) mark_scan_blocks_kernel(const MarkScanArgs a) {
+    __shared__ float run[kMarkScanRunLds];
+    __shared__ float L[kMarkRows * kMarkLLd];
+    __shared__ float Lp[kMarkScanOffs][2][kMarkBins];          // per offset: L of the previous tile's frames 14 and 15
+    __shared__ float Dd[kMarkRows * kMarkDdLd];
+    __shared__ float Gm[kMarkRows * kMarkGLd];
+    __shared__ double cS[kMarkScanOffs][kMarkPeriod];          // per offset: the open block's first 14 frames
+    __shared__ double cE[kMarkScanOffs];
+    __shared__ double Pb[kMarkPeriod];
+    __shared__ double Ew[2][4];
+    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, fr = lane & 15, fq = lane >> 4;
+    const int wg = (int)blockIdx.x, row = mark_scan_row(a.part_wg0, wg);
+    const MarkScanRow& r = a.rows[row];
+    const int local = wg - a.part_wg0[row], groups = kMarkOffsets / a.G;
+    const int og = local % groups, b0 = (local / groups) * a.R, b1 = min(b0 + a.R, r.NB);
+    const MarkSrc src{r.pcm, nullptr, 0, 0, (int64_t)r.n};
+    double* S = gptr(a.work) + (int64_t)r.blk0 * kMarkBlockDoubles;
+    uint32_t cw[2][2];                                                          // the lane's two chip rows, 64 bits each
+#pragma unroll
+    for (int t = 0; t < 2; ++t) {
+        const int crow = 32 * wave + 16 * t + fr;
+        cw[t][0] = mark_chip_word(crow, 0, r.k0, r.k1);
+        cw[t][1] = mark_chip_word(crow, 32, r.k0, r.k1);
+    }
+    const int phase = tid & (kMarkPeriod - 1), hf = tid >> 7;
+    for (int bt = b0; bt <= b1; ++bt) {
+        const int tq0 = kMarkBlock * bt - 1;                                    // row q of the tile's d is frame tq0 + q
+        if (bt == b1 && tq0 > r.T - 2) {                                        // the clip's end: no frame left for the open block
+            for (int oi = 0; oi < a.G; ++oi) {
+                double* slot = S + (int64_t)(bt - 1) * kMarkBlockDoubles;
+                if (hf == 0) slot[(og * a.G + oi) * kMarkPeriod + phase] = cS[oi][phase];
+                if (tid == 0) slot[kMarkOffsets * kMarkPeriod + og * a.G + oi] = cE[oi];
+            }
+            break;
+        }
+        const int64_t base = (int64_t)tq0 * kMarkH;
+        if (bt == b0) {
+            for (int p = tid; p < kMarkScanHops * kMarkH; p += kMarkThreads) run[mark_run_at(p)] = mark_sample(src, base + p);
+        } else {
+            float keep[3];
+#pragma unroll
+            for (int i = 0; i < 3; ++i) keep[i] = run[kMarkRows * (kMarkH + 4) + min(tid + i * kMarkThreads, 2 * (kMarkH + 4) - 1)];
+            __syncthreads();
+#pragma unroll
+            for (int i = 0; i < 3; ++i)
+                if (tid + i * kMarkThreads < 2 * (kMarkH + 4)) run[tid + i * kMarkThreads] = keep[i];
+            for (int p = 2 * kMarkH + tid; p < kMarkScanHops * kMarkH; p += kMarkThreads) run[mark_run_at(p)] = mark_sample(src, base + p);
+        }
+        __syncthreads();
+        for (int oi = 0; oi < a.G; ++oi) {
+            const int oidx = og * a.G + oi;
+            mark_f32x4 re, im;
+            mark_forward_at(run, oidx * kMarkOffsetStep, a.fwd, wave, lane, re, im);
+#pragma unroll
+            for (int q = 0; q < 4; ++q)
+                L[(4 * fq + q) * kMarkLLd + wave * 16 + fr] = logf(sqrtf(re[q] * re[q] + im[q] * im[q]) + 1e-9f);
+            __syncthreads();
+            double eA = 0.0, eB = 0.0;                                          // d^2 of the closing block (rows 0, 1) and of the open one
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                const int q = wave + 4 * i;                                     // d row q from L rows q - 2 .. q, rows -2 and -1 in Lp
+                const float l0 = q >= 2 ? L[max(q - 2, 0) * kMarkLLd + lane] : Lp[oi][q & 1][lane];
+                const float l1 = q >= 1 ? L[max(q - 1, 0) * kMarkLLd + lane] : Lp[oi][1][lane];
+                float d = l1 - 0.5f * (l0 + L[q * kMarkLLd + lane]);
+                d = fminf(fmaxf(d, -2.0f), 2.0f);
+                const bool ok = tq0 + q >= 1 && tq0 + q <= r.T - 2 && (q >= 2 || bt > b0);
+                d = ok ? d : 0.0f;
+                Dd[q * kMarkDdLd + lane] = d;
+                if (q < 2) eA += (double)d * (double)d; else eB += (double)d * (double)d;
+            }
+#pragma unroll
+            for (int m = 32; m > 0; m >>= 1) { eA += __shfl_xor(eA, m); eB += __shfl_xor(eB, m); }
+            if (lane == 0) { Ew[0][wave] = eA; Ew[1][wave] = eB; }
+            __syncthreads();
+            if (tid < 2 * kMarkBins) Lp[oi][tid >> 6][lane] = L[(kMarkRows - 2 + (tid >> 6)) * kMarkLLd + lane];
+            mark_f32x4 g[2][2];
+#pragma unroll
+            for (int t = 0; t < 2; ++t) g[t][0] = g[t][1] = mark_f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+            for (int ks = 0; ks < 16; ++ks) {
+                const float av = Dd[fr * kMarkDdLd + ks * 4 + fq];
+#pragma unroll
+                for (int t = 0; t < 2; ++t) {
+                    const uint32_t clear = (~cw[t][ks >> 3] >> ((ks & 7) * 4 + fq)) & 1u;
+                    g[t][ks & 1] = __builtin_amdgcn_mfma_f32_16x16x4f32(av, __uint_as_float(0x3f800000u | (clear << 31)), g[t][ks & 1], 0, 0, 0);
+                }
+            }
+#pragma unroll
+            for (int t = 0; t < 2; ++t) {
+                const mark_f32x4 gg = g[t][0] + g[t][1];
+#pragma unroll
+                for (int q = 0; q < 4; ++q) Gm[(4 * fq + q) * kMarkGLd + 32 * wave + 16 * t + fr] = gg[q];
+            }
+            __syncthreads();
+            double sumA = 0.0, sumB = 0.0;                                      // rows 0, 1 close block bt - 1; rows 2 .. 15 open block bt
+            if (hf == 0) {
+                for (int q = 0; q < 2; ++q) sumA += (double)Gm[q * kMarkGLd + ((tq0 + q + phase) & (kMarkPeriod - 1))];
+                for (int q = 2; q < 9; ++q) sumB += (double)Gm[q * kMarkGLd + ((tq0 + q + phase) & (kMarkPeriod - 1))];
+            } else {
+                for (int q = 9; q < kMarkRows; ++q) sumB += (double)Gm[q * kMarkGLd + ((tq0 + q + phase) & (kMarkPeriod - 1))];
+                Pb[phase] = sumB;
+            }
+            __syncthreads();
+            double* slot = S + (int64_t)(bt - 1) * kMarkBlockDoubles;           // written only when bt > b0
+            if (hf == 0) {
+                if (bt > b0) slot[oidx * kMarkPeriod + phase] = cS[oi][phase] + sumA;
+                cS[oi][phase] = sumB + Pb[phase];
+            }
+            if (tid == 0) {
+                if (bt > b0) slot[kMarkOffsets * kMarkPeriod + oidx] = cE[oi] + ((Ew[0][0] + Ew[0][1]) + (Ew[0][2] + Ew[0][3]));
+                cE[oi] = (Ew[1][0] + Ew[1][1]) + (Ew[1][2] + Ew[1][3]);
+            }
+        }
+    }
+}
+
+// grid: one workgroup per (row, window), packed as above
+__global__ void __launch_bounds__(kMarkScanWinThreads) mark_scan_windows_kernel(const MarkScanArgs a) {
+    __shared__ double Es[kMarkOffsets];
+    __shared__ float bz[kMarkScanWinThreads / 64];
+    __shared__ int bi[kMarkScanWinThreads / 64];
+    constexpr int kPer = kMarkOffsets * kMarkPeriod / kMarkScanWinThreads;      // 16 table entries per thread
+    const int tid = threadIdx.x, wg = (int)blockIdx.x, row = mark_scan_row(a.win_wg0, wg);
+    const MarkScanRow& r = a.rows[row];
+    const int w = wg - a.win_wg0[row];
+    const int nb = min(r.NB, a.win_blocks), s = min(w * a.hop_blocks, r.NB - nb);
+    const double* S = gptr(a.work) + (int64_t)(r.blk0 + s) * kMarkBlockDoubles;
+    if (tid < kMarkOffsets) {
+        double e = 0.0;
+        for (int b = 0; b < nb; ++b) e += S[(int64_t)b * kMarkBlockDoubles + kMarkOffsets * kMarkPeriod + tid];
+        Es[tid] = e;
+    }
+    double acc[kPer];
+#pragma unroll
+    for (int i = 0; i < kPer; ++i) acc[i] = 0.0;
+    for (int b = 0; b < nb; ++b)
+#pragma unroll
+        for (int i = 0; i < kPer; ++i) acc[i] += S[(int64_t)b * kMarkBlockDoubles + tid + i * kMarkScanWinThreads];
+    __syncthreads();
+    float* tab = a.tables ? gptr(a.tables) + (int64_t)(r.win0 + w) * (kMarkOffsets * kMarkPeriod) : nullptr;
+    float best = 0.0f;
+    int at = 0;
+#pragma unroll
+    for (int i = 0; i < kPer; ++i) {
+        const int idx = tid + i * kMarkScanWinThreads;
+        const double e = Es[idx >> 7];
+        const float z = e > 0.0 ? (float)(acc[i] / sqrt(e)) : 0.0f;
+        if (tab) tab[idx] = z;
+        if (i == 0 || z > best) { best = z; at = idx; }                         // ascending idx: the lowest index among equals stays
+    }
+#pragma unroll
+    for (int m = 32; m > 0; m >>= 1) {
+        const float oz = __shfl_xor(best, m);
+        const int oa = __shfl_xor(at, m);
+        if (oz > best || (oz == best && oa < at)) { best = oz; at = oa; }
+    }
+    if ((tid & 63) == 0) { bz[tid >> 6] = best; bi[tid >> 6] = at; }
+    __syncthreads();
+    if (tid == 0) {
+        for (int v = 1; v < kMarkScanWinThreads / 64; ++v)
+            if (bz[v] > best || (bz[v] == best && bi[v] < at)) { best = bz[v]; at = bi[v]; }
+        MarkVerdict out;
+        out.z = best; out.offset = (at >> 7) * kMarkOffsetStep; out.phase = at & (kMarkPeriod - 1); out.present = best >= 6.0f ? 1 : 0;
+        gptr(a.out)[r.win0 + w] = out;
+    }
+}
+
 }  // namespace fq3

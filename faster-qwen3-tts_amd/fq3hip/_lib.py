@@ -105,6 +105,10 @@ class MarkConfig(C.Structure):
     _fields_ = [("key", C.c_uint64), ("strength", C.c_double)]
 
 
+class MarkWindow(C.Structure):
+    _fields_ = [("z", C.c_float), ("offset", i32), ("phase", i32), ("present", i32)]
+
+
 class LoudStats(C.Structure):
     _fields_ = [("mean_power", C.c_double), ("peak", C.c_float), ("gain", C.c_float), ("n_hops", i32), ("n_abs", i32), ("n_rel", i32),
                 ("n_bad", i32), ("valid", i32), ("reserved", i32)]
@@ -298,6 +302,9 @@ SIGNATURES = {
     "fq3_mark_push": (C.c_int, [vp, vp, C.c_int64, C.c_int, vp, C.c_int64, C.POINTER(C.c_int64), vp]),
     "fq3_mark_detect_workspace": (C.c_int64, [C.c_int64]),
     "fq3_mark_detect": (C.c_int, [vp, C.c_int64, C.c_uint64, vp, C.c_int64, vp, vp]),
+    "fq3_mark_scan_windows": (C.c_int64, [C.c_int64, C.c_int, C.c_int]),
+    "fq3_mark_scan_workspace": (C.c_int64, [C.c_int, C.POINTER(C.c_int64)]),
+    "fq3_mark_scan": (C.c_int, [C.c_int, C.POINTER(vp), C.POINTER(C.c_int64), C.POINTER(C.c_uint64), C.c_int, C.c_int, vp, C.c_int64, vp, vp, vp]),
 }
 
 _lib = None

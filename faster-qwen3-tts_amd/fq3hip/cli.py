@@ -218,12 +218,24 @@ def check_level_args(parser, args):
 def cmd_detect(args):
     """``detect``: the detector over a WAV file on the device; prints the ``Detection`` and exits 0 when the mark is present, 1 when not"""
     from .audio_io import read_wav
-    from .watermark import detect
-    pcm, sr = read_wav(args.input)
-    pcm = np.asarray(pcm, dtype=np.float32)
-    det = detect(pcm if pcm.ndim == 1 else pcm.reshape(len(pcm), -1)[:, 0], sr, args.watermark_key)
-    print(det)
-    raise SystemExit(0 if det.present else 1)
+    from .watermark import detect, scan
+
+    def mono(path):
+        pcm, sr = read_wav(path)
+        pcm = np.asarray(pcm, dtype=np.float32)
+        return (pcm if pcm.ndim == 1 else pcm.reshape(len(pcm), -1)[:, 0]), sr
+    clips = [mono(p) for p in args.input]
+    if args.window is None:
+        dets = [detect(pcm, sr, args.watermark_key) for pcm, sr in clips]
+        for path, det in zip(args.input, dets):
+            print(det if len(dets) == 1 else f"{path}: {det}")
+        raise SystemExit(0 if all(d.present for d in dets) else 1)
+    # --window: every file's sliding windows in one call; one line per window; 0 when some window of every file carries the mark
+    scans = scan([c[0] for c in clips], [c[1] for c in clips], args.watermark_key, args.window, args.hop if args.hop is not None else 1.0)
+    for path, s in zip(args.input, scans):
+        for w in range(len(s.z)):
+            print(f"{path} {s.start_s[w]:.3f} {s.end_s[w]:.3f} z={s.z[w]:.3f} offset={s.offset[w]} phase={s.phase[w]} present={bool(s.present[w])}")
+    raise SystemExit(0 if all(s.present.any() for s in scans) else 1)
 
 
 def _write_output(path, audio, sr, args):
@@ -436,8 +448,13 @@ def build_parser():
     s.add_argument("--max-chars", type=int, default=240, metavar="N", help="--long: the splitter's budget per segment")
     s.set_defaults(func=cmd_serve)
     d = sub.add_parser("detect", help="is the watermark of KEY in a WAV file?  prints the Detection")
-    d.add_argument("--input", required=True, help="a WAV file (mono, or the first channel); any rate: resampled to 24 kHz on the device")
+    d.add_argument("--input", required=True, nargs="+",
+                   help="WAV files (mono, or the first channel); any rate: resampled to 24 kHz on the device")
     d.add_argument("--watermark-key", type=lambda v: int(v, 0), required=True, metavar="KEY")
+    d.add_argument("--window", type=float, default=None, metavar="S",
+                   help="scan: the detector over sliding windows of S seconds (rounded to blocks of 171 ms), all files in one call; "
+                        "prints one line per window: file, start and end in seconds, z, offset, phase, present")
+    d.add_argument("--hop", type=float, default=None, metavar="S", help="--window: seconds between window starts (default: 1)")
     d.set_defaults(func=cmd_detect)
     return p
 

@@ -1321,6 +1321,12 @@ class FasterQwen3TTS:
         from .watermark import detect
         return detect(audio, int(sr), key, self.device)
 
+    def scan_watermark(self, audio, sr, key, window_s: float = 3.0, hop_s: float = 1.0):
+        """WHICH PARTS of ``audio`` (one mono signal or a list of them; ``sr`` and ``key`` one for all or one per clip) carry the mark
+        of ``key``: the detector over sliding windows, all clips in two launches -> ``watermark.Scan`` (a list of them for a list)."""
+        from .watermark import scan
+        return scan(audio, sr, key, window_s, hop_s, device=self.device)
+
     def _refuse_batch_watermark(self) -> None:
         if getattr(self, "_mark", None) is not None:
             raise ValueError("the batch entry points do not run the watermark stage yet: call them outside watermark(), or use the "

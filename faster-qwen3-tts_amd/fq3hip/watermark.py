@@ -5,7 +5,8 @@ pushes, bit for bit.  Both run as DFT-as-GEMM on the fp32 matrix cores; there is
 ``design``      the constants and the chip rows of a key (``fq3_mark_design``; no GPU needed)
 ``count``       output samples that exist after ``n_in`` input samples (``fq3_mark_count``; no GPU needed)
 ``Watermark``   one stream on a device: ``push`` / ``flush`` / ``reset``
-``detect``      ``Detection(z, offset, phase, present)`` of a signal at any rate for a key"""
+``detect``      ``Detection(z, offset, phase, present)`` of a signal at any rate for a key
+``scan``        which sliding windows of one or many clips carry the mark (``fq3_mark_scan``, section 4.23): a ``Scan`` per clip"""
 from __future__ import annotations
 
 import ctypes as C
@@ -170,3 +171,107 @@ def detect(pcm, rate: int, key: int, device="cuda") -> Detection:
     z = detect_table(pcm, rate, key, device).cpu().numpy()
     oi, ph = np.unravel_index(int(np.argmax(z)), z.shape)
     return Detection(float(z[oi, ph]), int(oi) * OFFSET_STEP, int(ph), bool(z[oi, ph] >= THRESHOLD))
+
+
+BLOCK = 16 * H           # samples of a scan block: 16 frames, 171 ms
+SCAN_MAX = _lib.FQ3_STAGE_GROUP_MAX
+_WINDOW = np.dtype([("z", np.float32), ("offset", np.int32), ("phase", np.int32), ("present", np.int32)])
+
+
+@dataclass(frozen=True)
+class Scan:
+    """The windows of one clip: arrays of length ``W``.  ``z`` the largest statistic of window ``w``, ``offset`` / ``phase`` where it
+    was found (the phase is the clip's: frames count from the clip's start in every window), ``present``: ``z >= 6.0`` -- per window
+    the false-positive estimate of ``THRESHOLD`` holds, so a clip of ``W`` windows has about ``W`` times it; ``start_s`` / ``end_s``
+    the window's span in seconds of the 24 kHz signal; ``window_s`` / ``hop_s`` as rounded to whole blocks; ``tables`` the device
+    tensor ``[W][32][128]`` when asked for."""
+    z: np.ndarray
+    offset: np.ndarray
+    phase: np.ndarray
+    present: np.ndarray
+    start_s: np.ndarray
+    end_s: np.ndarray
+    window_s: float
+    hop_s: float
+    tables: Optional[torch.Tensor] = None
+
+
+def scan_blocks(window_s: float, hop_s: float):
+    """seconds -> (win_blocks, hop_blocks): rounded to whole blocks of 4096 samples, 1 <= hop <= win <= 4096"""
+    win = min(max(int(round(float(window_s) * RATE / BLOCK)), 1), 4096)
+    return win, min(max(int(round(float(hop_s) * RATE / BLOCK)), 1), win)
+
+
+def scan_windows(n: int, win_blocks: int, hop_blocks: int) -> int:
+    """``fq3_mark_scan_windows`` (host only): the windows of a clip of ``n`` samples"""
+    lib = _lib.load()
+    w = lib.fq3_mark_scan_windows(int(n), int(win_blocks), int(hop_blocks))
+    if w < 0:
+        raise ValueError(lib.fq3_last_error().decode("utf-8", "replace"))
+    return int(w)
+
+
+def _at_rate(pcm, rate: int, dev) -> torch.Tensor:
+    if int(rate) != RATE:
+        from .audio_out import resample_device
+        pcm = resample_device(pcm.detach().cpu().numpy() if isinstance(pcm, torch.Tensor) else pcm, int(rate), RATE, dev)
+    x = torch.as_tensor(np.asarray(pcm, dtype=np.float32) if not isinstance(pcm, torch.Tensor) else pcm)
+    return x.to(device=dev, dtype=torch.float32).reshape(-1).contiguous()
+
+
+def scan_blocks_device(xs, keys, win_blocks: int, hop_blocks: int, tables: bool = False):
+    """One ``fq3_mark_scan`` call (two launches on the current stream, nothing synchronises) over up to 32 float32 device tensors at
+    24 kHz.  -> (the windows' records as a device uint8 tensor ``[sum W * 16]``, the device tables ``[sum W][32][128]`` or None, the
+    list of ``W``)."""
+    lib, B, dev = _lib.load(), len(xs), xs[0].device
+    ns = (C.c_int64 * B)(*[int(x.numel()) for x in xs])
+    ks = (C.c_uint64 * B)(*[_key(k) for k in keys])
+    ptrs = (C.c_void_p * B)(*[x.data_ptr() for x in xs])
+    ws = [scan_windows(int(n), win_blocks, hop_blocks) for n in ns]
+    with torch.cuda.device(dev):
+        need = lib.fq3_mark_scan_workspace(B, ns)
+        if need < 0:
+            raise ValueError(lib.fq3_last_error().decode("utf-8", "replace"))
+        work = torch.empty(int(need), dtype=torch.float64, device=dev)
+        out = torch.empty(sum(ws) * _WINDOW.itemsize, dtype=torch.uint8, device=dev)
+        tab = torch.empty((sum(ws), N_OFFSETS, PERIOD), dtype=torch.float32, device=dev) if tables else None
+        s = torch.cuda.current_stream(dev)
+        _lib.check(lib.fq3_mark_scan(B, ptrs, ns, ks, int(win_blocks), int(hop_blocks), C.c_void_p(work.data_ptr()), int(need),
+                                     C.c_void_p(out.data_ptr()), C.c_void_p(tab.data_ptr() if tables else None), C.c_void_p(s.cuda_stream)))
+        for t in list(xs) + [work, out] + ([tab] if tables else []):
+            t.record_stream(s)
+    return out, tab, ws
+
+
+def scan(clips, rate, key, window_s: float = 3.0, hop_s: float = 1.0, tables: bool = False, device="cuda"):
+    """WHICH PARTS of the clips carry the mark: the detector over sliding windows of ``window_s`` seconds every ``hop_s`` seconds (both
+    rounded to whole blocks of 171 ms; a clip shorter than the window is one window), all clips of a call in two launches and one pinned
+    copy.  ``clips``: one mono signal or a list of them (tensors or arrays); ``rate`` and ``key``: one for all, or one per clip.  More
+    than 32 clips run in consecutive calls of 32.  -> one ``Scan`` for a single signal, else a list of them."""
+    single = not isinstance(clips, (list, tuple))
+    clips = [clips] if single else list(clips)
+    rates = list(rate) if isinstance(rate, (list, tuple)) else [rate] * len(clips)
+    keys = list(key) if isinstance(key, (list, tuple)) else [key] * len(clips)
+    if not clips or len(rates) != len(clips) or len(keys) != len(clips):
+        raise ValueError("scan: one rate and one key for all clips, or one per clip")
+    first = clips[0]
+    dev = _device(first.device if isinstance(first, torch.Tensor) and first.is_cuda else device)
+    win, hop = scan_blocks(window_s, hop_s)
+    result = []
+    with torch.cuda.device(dev):
+        for at in range(0, len(clips), SCAN_MAX):
+            xs = [_at_rate(c, r, dev) for c, r in zip(clips[at:at + SCAN_MAX], rates[at:at + SCAN_MAX])]
+            out, tab, ws = scan_blocks_device(xs, keys[at:at + SCAN_MAX], win, hop, tables)
+            host = torch.empty(out.shape, dtype=torch.uint8, pin_memory=True)
+            host.copy_(out, non_blocking=True)
+            torch.cuda.current_stream(dev).synchronize()
+            rec, w0 = host.numpy().view(_WINDOW), 0
+            for x, w in zip(xs, ws):
+                nb = -(-(-(-int(x.numel()) // H) - 1) // 16)                   # NB = ceil((T - 2) / 16), T = ceil(n / H) + 1
+                start = np.minimum(np.arange(w) * hop, max(nb - win, 0))
+                end = np.minimum((start + min(win, nb)) * BLOCK, int(x.numel()))
+                r = rec[w0:w0 + w]
+                result.append(Scan(r["z"].copy(), r["offset"].copy(), r["phase"].copy(), r["present"] != 0, start * BLOCK / RATE, end / RATE,
+                                   win * BLOCK / RATE, hop * BLOCK / RATE, tab[w0:w0 + w] if tables else None))
+                w0 += w
+    return result[0] if single else result

@@ -895,6 +895,34 @@ int64_t fq3_mark_detect_workspace(int64_t n);
 /* pcm: n device floats at 24 kHz.  z: 32 x 128 device floats, z[o / 8][phi].  Two launches on `stream` (the partial sums of every
  * (offset, 14-frame tile) into `work`, then their sums in ascending tile order), no host synchronisation. */
 int fq3_mark_detect(const float* pcm, int64_t n, uint64_t key, float* work, int64_t work_floats, float* z, void* stream);
+/* Scan: WHICH PARTS of up to FQ3_STAGE_GROUP_MAX clips carry the mark -- the detector above over sliding windows, all clips of a call
+ * in two launches.  Frames, window, bins, chips, d and the 32 offsets x 128 phases are exactly those of fq3_mark_detect: for a clip of
+ * n samples T = ceil(n / H) + 1, the detector's frames are t = 1 .. T - 2, and the chip row of frame t at phase phi is (t + phi) mod 128
+ * with t counted from the start of the CLIP for every window -- so a window's phase is the clip's phase.
+ *   Block b holds frames 1 + 16 b .. 1 + 16 b + 15, cut at T - 2;  NB = ceil((T - 2) / 16).  A block is 4096 samples (171 ms).
+ *   Windows: win_blocks in [1, 4096], hop_blocks in [1, win_blocks].  NB <= win_blocks: ONE window over all blocks.  Otherwise
+ *   W = 1 + ceil((NB - win_blocks) / hop_blocks) windows, window w over blocks [s_w, s_w + win_blocks), s_w = min(w hop_blocks,
+ *   NB - win_blocks): the last window is pulled back to end at the clip's end and is never shorter.
+ *   z_w[o / 8][phi] = (sum over the window's frames of d[t] . c[(t + phi) mod 128]) / sqrt(sum over the same frames and all 64 bins
+ *   of d^2), 0 where that energy is 0.  Verdict of a window: (max z, its offset in samples, its phase); among equal z the lowest
+ *   (o, phi) index wins, as numpy's argmax does; present = max z >= 6.0.  The threshold is the detector's: the false-positive estimate
+ *   above (4096 Q(6) = 4e-6) now holds PER WINDOW, not per clip -- a clip of W windows has about W times that.
+ * The sums of d c and d^2 of every block are carried in double ((32 x 128 + 32) doubles per block in `work`) and a window adds its
+ * blocks in ascending order; everything in front of them is fp32, and d . c of one frame is summed in fp32 by the matrix core (the
+ * products are exact).  A clip's results do not depend on the other rows of the call, bit for bit. */
+typedef struct fq3_mark_window { float z; int32_t offset, phase, present; } fq3_mark_window;
+/* host only: W for a clip of n samples, n in [512, 2^27]; negative: an FQ3_E* code */
+int64_t fq3_mark_scan_windows(int64_t n, int win_blocks, int hop_blocks);
+/* host only: doubles of device workspace fq3_mark_scan needs for B rows of n[b] samples; negative: an FQ3_E* code */
+int64_t fq3_mark_scan_workspace(int B, const int64_t* n);
+/* pcm, n, key: HOST arrays of B entries: row b is n[b] device floats at 24 kHz (any float alignment) under key[b].  out: DEVICE
+ * records, W_0 of row 0, then W_1 of row 1, ...; tables: NULL, or DEVICE floats [sum W][32][128] in the same order.  TWO launches on
+ * `stream` (every block's sums on one packed grid over all rows, then one workgroup per window), no host synchronisation and no copy:
+ * the rows' descriptors travel in the launches' argument blocks.  All or nothing, answered before any launch: B < 0 or B >
+ * FQ3_STAGE_GROUP_MAX, a null array or row pointer, a length outside [512, 2^27], the window arguments out of range, work_doubles
+ * below fq3_mark_scan_workspace(B, n): FQ3_EINVAL, nothing is launched or written.  B == 0: returns 0, does nothing. */
+int fq3_mark_scan(int B, const float* const* pcm, const int64_t* n, const uint64_t* key, int win_blocks, int hop_blocks,
+                  double* work, int64_t work_doubles, fq3_mark_window* out, float* tables, void* stream);
 
 /* ---- Leveller: a causal BS.1770 gain for a stream that has not ended ------------------------------------------------------------------
  * Float32 mono in, float32 out at the same rate: length-preserving, ZERO latency, and independent of how the stream was cut into

@@ -9,7 +9,8 @@ medians over the repeats after a warm-up (``loudness_probe.alternate`` holds the
 Also, so that one file holds them: the embed and detect error bounds of tests/test_gpu_watermark.py with the device's errors, and the
 a = 0.1 repeat on the synthetic voiced signal of tests/_mark_ref.py -- SNR and the detector's max z for the marked signal behind s16,
 cropped by 1000 samples, behind a 24 -> 8 -> 24 kHz round trip, unmarked and under another key.  Writes profiles/watermark.json.
-usage: watermark_probe.py [runs=60] [out.json]"""
+usage: watermark_probe.py [runs=60] [out.json]
+       watermark_probe.py --scan [runs=30] [out.json]    the scan against one-by-one detect (``scan_main``) -> profiles/mark_scan.json"""
 import json
 import os
 import sys
@@ -108,5 +109,41 @@ def main():
     print(json.dumps(res, indent=1))
 
 
+def scan_main(argv):
+    """--scan: 1, 8 and 32 clips of 3 s and of 30 s through ``scan`` (fq3_mark_scan: two launches and one pinned copy per call)
+    against the same clips through ``detect`` one by one, in the same run: HIP events, the two paths alternating inside every repeat,
+    medians.  'host' rows end with the verdicts on the host (scan's pinned copy; detect's table copy per clip); 'device' rows only
+    enqueue (``scan_blocks_device`` against ``detect_table`` per clip).  Writes profiles/mark_scan.json."""
+    runs = max(10, int(argv[0])) if argv else 30
+    out_path = argv[1] if len(argv) > 1 else os.path.join(ROOT, "profiles", "mark_scan.json")
+    g = torch.Generator().manual_seed(3)
+    win, hop = W.scan_blocks(3.0, 1.0)
+    rows = []
+    for seconds in (3, 30):
+        pool = [speech_like(seconds * 24000, g) for _ in range(32)]
+        for B in (1, 8, 32):
+            clips = pool[:B]
+            t = alternate({"scan host": lambda: W.scan(clips, 24000, KEY),
+                           "detect host": lambda: [W.detect(c, 24000, KEY) for c in clips],
+                           "scan device": lambda: W.scan_blocks_device(clips, [KEY] * B, win, hop),
+                           "detect device": lambda: [W.detect_table(c, 24000, KEY) for c in clips]}, runs)
+            rows.append({"clips": B, "seconds": seconds, "windows_per_clip": W.scan_windows(seconds * 24000, win, hop),
+                         "scan_launches": 2, "detect_launches": 2 * B, **{k.replace(" ", "_") + "_ms": round(v, 4) for k, v in t.items()}})
+            print(rows[-1], flush=True)
+    res = {"device": torch.cuda.get_device_name(0), "runs": runs, "rate": 24000, "win_blocks": win, "hop_blocks": hop,
+           "method": "HIP events around each path, scan and one-by-one detect alternating inside every repeat, medians",
+           "rows": rows,
+           "notes": ["scan answers a verdict per window (and per clip), detect one per clip: the same DFT work, more answers",
+                     "the event pairs include the Python wrappers' allocations; the 'host' rows include a stream synchronise",
+                     "NOT measured: detection of short marked passages in real speech; whether 3 s is the right window"]}
+    os.makedirs(os.path.dirname(out_path) or ".", exist_ok=True)
+    with open(out_path, "w") as f:
+        json.dump(res, f, indent=1)
+        f.write("\n")
+
+
 if __name__ == "__main__":
-    main()
+    if "--scan" in sys.argv[1:]:
+        scan_main([a for a in sys.argv[1:] if a != "--scan"])
+    else:
+        main()

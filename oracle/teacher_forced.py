@@ -26,13 +26,14 @@ def load_case(npz, prefix: str):
     return {k: npz[f"{prefix}_{k}"] for k in ("codes", "t_margin", "t_top1", "p_margin", "p_top1")}
 
 
-def forced_decisions(eng, cfg, tie, tth, tpe, codes: np.ndarray, graph: bool = True):
-    """Run prefill + len(codes) teacher-forced frames.  Returns int64 [N, 16] HIP decisions aligned with `codes`."""
+def forced_decisions(eng, cfg, tie, tth, tpe, codes: np.ndarray, graph: bool = True, n_pad: int = 0):
+    """Run prefill + len(codes) teacher-forced frames.  Returns int64 [N, 16] HIP decisions aligned with `codes`.
+    ``n_pad``: the prompt's left padding (its first rows are masked keys and the rope positions start after them)."""
     dev = eng.device
     N, G = codes.shape
     V, eos = cfg.talker.vocab_size, cfg.codec_eos_token_id
     greedy = dict(temperature=1.0, top_k=0, top_p=1.0, do_sample=False)
-    logits, hidden = eng.prefill(tie[0].to(dev).contiguous())
+    logits, hidden = eng.prefill(tie[0].to(dev).contiguous(), n_pad=n_pad)
     tok0 = eng.sample(logits, sup_lo=max(0, V - 1024), sup_hi=V, keep_id=eos, suppress_eos=True, **greedy)
     forced = torch.zeros(N + 1, G, dtype=torch.int32)
     forced[:N] = torch.from_numpy(codes.astype(np.int32))

@@ -47,10 +47,10 @@ from fq3hip.config import qwen3_tts_0p6b, qwen3_tts_1p7b
 from fq3hip.weights import synth_weights, synth_prompt
 
 
-def _note(key, val):
+def _note(key, val, name="parity_fulldepth.json"):
     d = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "gpurun_out")
     os.makedirs(d, exist_ok=True)
-    p = os.path.join(d, "parity_fulldepth.json")
+    p = os.path.join(d, name)
     cur = {}
     if os.path.exists(p):
         try:

@@ -3,6 +3,7 @@
 // output stage, so the model refuses a speed other than 1 together with the mark).
 //   fq3_mark_design / _count   host only (no HIP call): the framing constants, the strength as the device's float, the chip words
 //   fq3_mark_create / _push    ONE launch per push: a workgroup per 15 hops of output plus one that keeps the history
+//   fq3_mark_push_group        the pushes of up to 32 objects in ONE launch on a packed grid, each row bit for bit its single push
 //   fq3_mark_detect            two launches: the partial sums of every (offset, frame tile), then z[32][128]
 //   fq3_mark_scan              two launches for up to 32 clips: the sums of every block of 16 frames, then a verdict per sliding window
 // The host tracks what follows from the lengths alone: samples pushed, samples emitted, which history buffer is current, whether the
@@ -188,33 +189,105 @@ extern "C" int fq3_mark_reset(fq3_mark* m, void* stream) {
     return 0;
 }
 
+namespace {
+
+// the single push's checks; nothing moves.  *n: the samples the push emits
+int check_push_(const std::string& who, const fq3_mark* m, const float* pcm, int64_t n_in, int final, const float* out, int64_t capacity_samples,
+                int64_t* n) {
+    if (n_in < 0 || n_in > kMaxPush || (n_in > 0 && !pcm)) return fq3_fail_(FQ3_EINVAL, who + ": bad input");
+    if (m->finished) return fq3_fail_(FQ3_ESTATE, who + ": the stream has ended; fq3_mark_reset starts the next one");
+    *n = count_(m->total + n_in, final) - m->emitted;
+    if (*n > capacity_samples || (*n > 0 && !out))
+        return fq3_fail_(FQ3_EINVAL, who + ": " + std::to_string(*n) + " output samples exceed the capacity of " + std::to_string(capacity_samples));
+    return 0;
+}
+
+bool has_work_(int64_t n_in, int final) { return n_in > 0 || final; }    // else nothing completes and nothing changes
+
+// what the kernel needs of a checked push
+void plan_push_(const fq3_mark* m, const float* pcm, int64_t n_in, int final, float* out, int64_t n, MarkPushArgs* k) {
+    const int64_t total = m->total + n_in;
+    const int64_t n_hist = m->total < kMarkKeep ? m->total : kMarkKeep;
+    k->src = MarkSrc{pcm, m->hist[m->cur], m->total - n_hist, m->total, total};
+    k->hist_next = m->hist[m->cur ^ 1];
+    k->out = out; k->fwd = m->tables; k->inv = m->tables + kMarkFwdFloats;
+    k->o0 = m->emitted; k->n_out = n;
+    k->keep = final ? 0 : (int)(total < kMarkKeep ? total : kMarkKeep);
+    k->a = m->a;
+    k->k0 = (uint32_t)(m->key & 0xffffffffull); k->k1 = (uint32_t)(m->key >> 32);
+}
+
+// workgroups of a push that emits n samples: one per 15 hops, and the one that keeps the history
+int64_t push_grid_(int64_t n) {
+    const int64_t hops = (n + kMarkH - 1) / kMarkH;
+    return (hops + kMarkHops - 1) / kMarkHops + 1;
+}
+
+void commit_push_(fq3_mark* m, int64_t n_in, int64_t n, int final) {
+    m->cur ^= 1;
+    m->total += n_in;
+    m->emitted += n;
+    if (final) m->finished = true;
+}
+
+}  // namespace
+
 extern "C" int fq3_mark_push(fq3_mark* m, const float* pcm, int64_t n_in, int final, float* out, int64_t capacity_samples,
                              int64_t* n_out, void* stream) {
     if (!m || !n_out) return fq3_fail_(FQ3_EINVAL, "fq3_mark_push: null argument");
-    if (n_in < 0 || n_in > kMaxPush || (n_in > 0 && !pcm)) return fq3_fail_(FQ3_EINVAL, "fq3_mark_push: bad input");
-    if (m->finished) return fq3_fail_(FQ3_ESTATE, "fq3_mark_push: the stream has ended; fq3_mark_reset starts the next one");
-    const int64_t total = m->total + n_in;
-    const int64_t n = count_(total, final) - m->emitted;
-    if (n > capacity_samples || (n > 0 && !out))
-        return fq3_fail_(FQ3_EINVAL, "fq3_mark_push: " + std::to_string(n) + " output samples exceed the capacity of " + std::to_string(capacity_samples));
+    int64_t n = 0;
+    if (int rc = check_push_("fq3_mark_push", m, pcm, n_in, final, out, capacity_samples, &n)) return rc;
     *n_out = n;
-    if (n_in == 0 && !final) return 0;              // nothing completes and nothing changes
+    if (!has_work_(n_in, final)) return 0;
     MarkPushArgs k{};
-    const int64_t n_hist = m->total < kMarkKeep ? m->total : kMarkKeep;
-    k.src = MarkSrc{pcm, m->hist[m->cur], m->total - n_hist, m->total, total};
-    k.hist_next = m->hist[m->cur ^ 1];
-    k.out = out; k.fwd = m->tables; k.inv = m->tables + kMarkFwdFloats;
-    k.o0 = m->emitted; k.n_out = n;
-    k.keep = final ? 0 : (int)(total < kMarkKeep ? total : kMarkKeep);
-    k.a = m->a;
-    k.k0 = (uint32_t)(m->key & 0xffffffffull); k.k1 = (uint32_t)(m->key >> 32);
-    const int64_t hops = (n + kMarkH - 1) / kMarkH, groups = (hops + kMarkHops - 1) / kMarkHops;
-    hipLaunchKernelGGL(mark_embed_kernel, dim3((unsigned)(groups + 1)), dim3(kMarkThreads), 0, (hipStream_t)stream, k);
+    plan_push_(m, pcm, n_in, final, out, n, &k);
+    hipLaunchKernelGGL(mark_embed_kernel, dim3((unsigned)push_grid_(n)), dim3(kMarkThreads), 0, (hipStream_t)stream, k);
     KHIP(hipGetLastError());
-    m->cur ^= 1;
-    m->total = total;
-    m->emitted += n;
-    if (final) m->finished = true;
+    commit_push_(m, n_in, n, final);
+    return 0;
+}
+
+static_assert(FQ3_STAGE_GROUP_MAX == kMarkGroupMax, "the header's limit is the descriptor table's size");
+
+extern "C" int fq3_mark_push_group(fq3_mark* const* objs, int B, const float* const* pcm, const int64_t* n_in, const int* final,
+                                   float* const* out, const int64_t* capacity_samples, int64_t* n_out, void* stream) {
+    if (B < 0 || B > FQ3_STAGE_GROUP_MAX)
+        return fq3_fail_(FQ3_EINVAL, "fq3_mark_push_group: B = " + std::to_string(B) + "; a group has 0 to " + std::to_string(FQ3_STAGE_GROUP_MAX) + " rows");
+    if (B == 0) return 0;
+    if (!objs || !pcm || !n_in || !final || !out || !capacity_samples || !n_out) return fq3_fail_(FQ3_EINVAL, "fq3_mark_push_group: null array");
+    for (int b = 0; b < B; ++b) {
+        if (!objs[b]) return fq3_fail_(FQ3_EINVAL, "fq3_mark_push_group: row " + std::to_string(b) + ": null object");
+        for (int c = 0; c < b; ++c)
+            if (objs[c] == objs[b]) return fq3_fail_(FQ3_EINVAL, "fq3_mark_push_group: rows " + std::to_string(c) + " and " + std::to_string(b) + " are the same object");
+        if (objs[b]->tables != objs[0]->tables)
+            return fq3_fail_(FQ3_EINVAL, "fq3_mark_push_group: row " + std::to_string(b) + " was created on another device than row 0");
+    }
+    // every row is checked and planned before any object moves
+    MarkGroupArgs g{};
+    int64_t cnt[FQ3_STAGE_GROUP_MAX], grid = 0;
+    for (int b = 0; b < B; ++b) {
+        if (int rc = check_push_("fq3_mark_push_group: row " + std::to_string(b), objs[b], pcm[b], n_in[b], final[b], out[b], capacity_samples[b], &cnt[b]))
+            return rc;
+        g.wg0[b] = (int)grid;
+        if (!has_work_(n_in[b], final[b])) continue;
+        MarkPushArgs k{};
+        plan_push_(objs[b], pcm[b], n_in[b], final[b], out[b], cnt[b], &k);
+        MarkGroupRow& r = g.rows[b];
+        r.src = k.src; r.hist_next = k.hist_next; r.out = k.out; r.o0 = k.o0; r.n_out = k.n_out;
+        r.keep = k.keep; r.a = k.a; r.k0 = k.k0; r.k1 = k.k1;
+        grid += push_grid_(cnt[b]);
+    }
+    if (grid > 0x7fffffff) return fq3_fail_(FQ3_EINVAL, "fq3_mark_push_group: the rows of one call need more than 2^31 workgroups");
+    for (int b = B; b <= kMarkGroupMax; ++b) g.wg0[b] = (int)grid;
+    if (grid > 0) {
+        g.fwd = objs[0]->tables; g.inv = objs[0]->tables + kMarkFwdFloats;
+        hipLaunchKernelGGL(mark_embed_group_kernel, dim3((unsigned)grid), dim3(kMarkThreads), 0, (hipStream_t)stream, g);
+        KHIP(hipGetLastError());
+    }
+    for (int b = 0; b < B; ++b) {
+        n_out[b] = cnt[b];
+        if (has_work_(n_in[b], final[b])) commit_push_(objs[b], n_in[b], cnt[b], final[b]);
+    }
     return 0;
 }
 

@@ -108,18 +108,19 @@ struct MarkPushArgs {
     uint32_t k0, k1;
 };
 
-// grid: ceil(ceil(n_out / H) / 15) workgroups of 15 hops, and one more that keeps the history
-__global__ void __launch_bounds__(kMarkThreads) mark_embed_kernel(const MarkPushArgs a) {
+// One push seen from workgroup wg of its n_wg: ceil(ceil(n_out / H) / 15) workgroups of 15 hops, and one more that keeps the history.
+// Nothing in it looks at the grid, so the single kernel and the group kernel run the same code on a row.
+__device__ __forceinline__ void mark_embed_body(const MarkPushArgs& a, const int wg, const int n_wg) {
     __shared__ float run[kMarkRunLds];
     __shared__ float D[kMarkRows * kMarkDLd];
     __shared__ float E[kMarkRows * kMarkELd];
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, fr = lane & 15, fq = lane >> 4;
-    if (blockIdx.x == gridDim.x - 1) {
+    if (wg == n_wg - 1) {
         float* hn = gptr(a.hist_next);
         for (int i = tid; i < a.keep; i += kMarkThreads) hn[i] = mark_sample(a.src, a.src.total - a.keep + i);
         return;
     }
-    const int64_t hop0 = a.o0 / kMarkH + (int64_t)blockIdx.x * kMarkHops;       // frame f of the tile is frame hop0 + f of the stream
+    const int64_t hop0 = a.o0 / kMarkH + (int64_t)wg * kMarkHops;               // frame f of the tile is frame hop0 + f of the stream
     mark_stage(a.src, (hop0 - 1) * kMarkH, run);
     __syncthreads();
     mark_f32x4 re, im;
@@ -157,6 +158,47 @@ __global__ void __launch_bounds__(kMarkThreads) mark_embed_kernel(const MarkPush
         const float x = run[mark_run_at((q + 1) * kMarkH + tid)];
         out[n - a.o0] = (x + E[q * kMarkELd + kMarkH + tid]) + E[(q + 1) * kMarkELd + tid];
     }
+}
+
+__global__ void __launch_bounds__(kMarkThreads) mark_embed_kernel(const MarkPushArgs a) { mark_embed_body(a, (int)blockIdx.x, (int)gridDim.x); }
+
+// ---- The pushes of up to 32 streams in ONE launch (fq3_mark_push_group) -----------------------------------------------------------------
+// One packed 1-D grid over all rows: row b owns workgroups wg0[b] .. wg0[b + 1] - 1 -- its single push's grid, the history workgroup
+// last -- and none when its push is empty and not final, so wg0 may hold equal neighbours.  A workgroup finds its row with the
+// wave-uniform walk of mark_scan_row (the LAST row that starts at or before it, which steps over rows of no workgroups; entries past
+// the last row hold the grid size), copies that row's descriptor out of the argument block into scalar registers and runs the single
+// push's body on it: the tables travel once, key and strength per row.  The identity contract above makes a row's output and next
+// history those of its single push, bit for bit, whatever the other rows are and wherever the row falls in the grid.
+constexpr int kMarkGroupMax = 32;                   // FQ3_STAGE_GROUP_MAX
+
+struct MarkGroupRow {
+    MarkSrc src;
+    float* hist_next;
+    float* out;
+    int64_t o0, n_out;
+    int keep;
+    float a;
+    uint32_t k0, k1;
+};
+
+struct MarkGroupArgs {
+    const float* fwd;
+    const float* inv;
+    int wg0[kMarkGroupMax + 1];                     // first workgroup of row b; wg0[b >= B] is the grid size
+    MarkGroupRow rows[kMarkGroupMax];
+};
+static_assert(sizeof(MarkGroupRow) == 88 && sizeof(MarkGroupArgs) <= 4096, "the descriptors must fit the 4 KB of arguments a launch may carry");
+
+__global__ void __launch_bounds__(kMarkThreads) mark_embed_group_kernel(const MarkGroupArgs g) {
+    const int wg = (int)blockIdx.x;
+    int row = 0;
+#pragma unroll
+    for (int b = 1; b < kMarkGroupMax; ++b) row += wg >= g.wg0[b] ? 1 : 0;       // wg0 does not decrease: the last row that starts at or before wg
+    const MarkGroupRow& r = g.rows[row];
+    MarkPushArgs a;
+    a.src = r.src; a.hist_next = r.hist_next; a.out = r.out; a.fwd = g.fwd; a.inv = g.inv;
+    a.o0 = r.o0; a.n_out = r.n_out; a.keep = r.keep; a.a = r.a; a.k0 = r.k0; a.k1 = r.k1;
+    mark_embed_body(a, wg - g.wg0[row], g.wg0[row + 1] - g.wg0[row]);
 }
 
 struct MarkDetectArgs {

@@ -300,6 +300,9 @@ SIGNATURES = {
     "fq3_mark_destroy": (C.c_int, [vp]),
     "fq3_mark_reset": (C.c_int, [vp, vp]),
     "fq3_mark_push": (C.c_int, [vp, vp, C.c_int64, C.c_int, vp, C.c_int64, C.POINTER(C.c_int64), vp]),
+    # host arrays of B entries, as fq3_limit_push_group
+    "fq3_mark_push_group": (C.c_int, [C.POINTER(vp), C.c_int, C.POINTER(vp), C.POINTER(C.c_int64), C.POINTER(C.c_int),
+                                      C.POINTER(vp), C.POINTER(C.c_int64), C.POINTER(C.c_int64), vp]),
     "fq3_mark_detect_workspace": (C.c_int64, [C.c_int64]),
     "fq3_mark_detect": (C.c_int, [vp, C.c_int64, C.c_uint64, vp, C.c_int64, vp, vp]),
     "fq3_mark_scan_windows": (C.c_int64, [C.c_int64, C.c_int, C.c_int]),

@@ -314,8 +314,15 @@ def cmd_serve(args, model=None, lines=None):
         if not pending:
             continue
         start = time.perf_counter()
-        levelled = any(getattr(args, k, None) is not None for k in ("gain_db", "limiter_db", "level", "watermark_key"))
-        if len(pending) > 1 and getattr(args, "long", False) and args.mode in ("clone", "custom") and not levelled:
+        levelled = any(getattr(args, k, None) is not None for k in ("gain_db", "limiter_db", "level"))
+        # --watermark-key in a lock-step clone run: the batch takes the mark as a keyword, the lines vocoded together in one launch.
+        # With --long the lines go one by one, as before, inside the model's watermark context (the long-form batch entry points
+        # take no mark), and so do the custom and design modes
+        mkw, long = {}, bool(getattr(args, "long", False))
+        if getattr(args, "watermark_key", None) is not None:
+            from .watermark import MarkSpec
+            mkw = dict(watermark=MarkSpec(args.watermark_key, getattr(args, "watermark_strength", None) or 0.1))
+        if len(pending) > 1 and long and args.mode in ("clone", "custom") and not levelled and not mkw:
             # --long: every line is a text of any length; the segments of all waiting lines share the lanes of ONE lock-step run
             from .long_form import LongFormSpec
             spec = _output_spec(args)
@@ -329,12 +336,12 @@ def cmd_serve(args, model=None, lines=None):
                 results = model.generate_long_custom_voice_batch(pending, speaker=args.speaker, language=args.language,
                                                                  instruct=args.instruct, **lkw)
             outs = [(r[0][0], r[1]) for r in results]
-        elif len(pending) > 1 and args.mode == "clone" and not levelled:    # (--gain-db / --limiter-db: line by line, as before)
+        elif len(pending) > 1 and args.mode == "clone" and not levelled and not (mkw and long):    # (--gain-db / --limiter-db: line by line, as before)
             # --out-rate / --encoding / --speed: the lines decoded together go through the output stage together (``output=``)
             spec = _output_spec(args)
             results = model.generate_voice_clone_batch(pending, language=args.language, ref_audio=args.ref_audio, ref_text=args.ref_text,
                                                        xvec_only=args.xvec_only, non_streaming_mode=args.non_streaming_mode,
-                                                       lanes=args.lanes, **_gen_kwargs(args), **({} if spec is None else dict(output=spec)))
+                                                       lanes=args.lanes, **_gen_kwargs(args), **({} if spec is None else dict(output=spec)), **mkw)
             outs = [(r[0][0], r[1]) for r in results]
         else:
             with _levelled(model, args), _output_stage(model, args), _exact(model, args):
@@ -393,7 +400,8 @@ def build_parser():
                              "--limiter-db; the defaults behind it are not tuned on real voices (default: off)")
         sp.add_argument("--watermark-key", type=lambda v: int(v, 0), default=None, metavar="KEY",
                         help="put a keyed provenance watermark into the audio on the device (KEY: an integer in [0, 2^64), what `detect` "
-                             "needs); single-stream and --long modes, not with --speed or a lock-step --lanes run (default: off)")
+                             "needs); single-stream and --long modes, not with --speed; a lock-step `serve --lanes N` run in clone mode without --long marks "
+                             "the lines decoded together in one launch, every other mode marks line by line (default: off)")
         sp.add_argument("--watermark-strength", type=float, default=None, metavar="A",
                         help="--watermark-key: the mark's strength, 0.02 to 0.3; NOT tuned on real voices (default: 0.1)")
         if output:

@@ -371,7 +371,8 @@ class OrderedJoinSet:
     ``OrderedJoin.feed``'s: chunks of segment ``k + 1`` wait until ``k`` has ended, and a text's pieces come strictly in text order.
     Consecutive ready chunks of one segment go out as ONE push (the join does not depend on how a segment is cut into pushes); round
     ``r`` then takes the r-th ready push of every text through ONE ``push_group`` and, behind it, through the group call of every
-    stage the texts have: the gains, ``leveller.push_group``, ``limiter.push_group``, ``audio_out.push_group``.  A join appears at
+    stage the texts have: the gains, ``leveller.push_group``, ``watermark.push_group``, ``limiter.push_group``,
+    ``audio_out.push_group``.  A join appears at
     most once per round.  ``push_group`` (internal, tests): what joins a round's rows."""
 
     def __init__(self, ordered: List["OrderedJoin"], push_group=None):
@@ -443,6 +444,10 @@ class OrderedJoinSet:
         if any(oj.leveller is not None for oj in ojs):
             from .leveller import push_group as level_group
             through(lambda oj: oj.leveller, level_group)
+        if any(oj.marker is not None for oj in ojs):
+            # one mark per text on its joined stream, each under its own key: ONE launch for the round's rows
+            from .watermark import push_group as mark_group
+            through(lambda oj: oj.marker, mark_group)
         if any(oj.limiter is not None for oj in ojs):
             from .limiter import push_group as limit_group
             through(lambda oj: oj.limiter, limit_group)

@@ -77,6 +77,19 @@ class _SideVocoder:
         # behind ``level`` -- the utterances vocoded together in ONE ``audio_out.push_group`` -- and the model's ``(take, give)`` of
         # pooled stages
         self.outputs, self.stages = None, None
+        # ``watermark=`` of the batch entry points: {key: MarkSpec} and the model's ``mark_rows(specs, rows, stream)``, which marks
+        # the utterances vocoded together in ONE launch; ``level`` then stops in front of the limiter and ``limit(key, row)`` is the
+        # model's limiter step behind the mark (None outside ``limiter()``)
+        self.marks, self.mark_rows, self.limit = None, None, None
+
+    def _marked(self, keys, pcms) -> None:
+        """the rows that have a mark through it, in place, then every row through ``limit``"""
+        at = [j for j, k in enumerate(keys) if k in self.marks]
+        if at:
+            self.mark_rows([self.marks[keys[j]] for j in at], [pcms[j] for j in at], self.stream)
+        if self.limit is not None:
+            for k, pcm in zip(keys, pcms):
+                self.limit(k, pcm)
 
     def _spec(self, key):
         return self.outputs.get(key) if self.outputs else None
@@ -106,6 +119,11 @@ class _SideVocoder:
             a = a[int(ref_len / max(codes.shape[0], 1) * len(a)):] if ref_len > 0 else a
             if self.level is not None:
                 a = _to_numpy(self.level(key, a))
+            if self.marks:
+                # synchronous tokenizer: its audio is on the host; the utterance is uploaded for the mark
+                x = torch.from_numpy(np.ascontiguousarray(_to_numpy(a), dtype=np.float32).reshape(-1)).to(self.dev)
+                self._marked([key], [x])
+                a = x.cpu().numpy()
             if self._spec(key) is not None:
                 # synchronous tokenizer: its audio is on the host; the utterance is uploaded for the stage
                 a = self._encode_group([key], [torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32)).to(self.dev)])[0]
@@ -119,6 +137,9 @@ class _SideVocoder:
             pcm = self.tok.decode_tensor(codes, cut, prefix=pf) if pf is not None else self.tok.decode_tensor(codes, cut)
             if self.level is not None:
                 pcm = self.level(key, pcm)
+            if self.marks:
+                pcm = pcm.float().contiguous()
+                self._marked([key], [pcm.reshape(-1)])
             host = None
             if self._spec(key) is not None:
                 host = self._encode_group([key], [pcm])[0]
@@ -176,6 +197,9 @@ class _SideVocoder:
                         pcm = pcm.float().contiguous()
                         for j, (key, _c, _r) in enumerate(part):
                             self.level(key, pcm[j])                 # row by row, in place: every utterance has its own gain
+                    if self.marks:
+                        pcm = pcm.float().contiguous()
+                        self._marked([key for key, _c, _r in part], [pcm[j].reshape(-1) for j in range(len(part))])
                     host = None
                     staged = [j for j, (key, _c, _r) in enumerate(part) if self._spec(key) is not None]
                     enc = dict(zip(staged, self._encode_group([part[j][0] for j in staged], [pcm[j] for j in staged]))) if staged else {}
@@ -428,6 +452,13 @@ class StreamingVocoder:
         """``wav`` (contiguous float32 device vector, or None) through this utterance's watermark: taken at the first chunk -- an idle
         object of the same key and strength from the model's pool, reset, or a new one, on the vocoder's stream -- and given back
         behind the final push.  It holds back between 256 and 511 samples until then."""
+        out = self.mark_take().push(wav, final)
+        if final:
+            self.mark_release()
+        return out
+
+    def mark_take(self):
+        """This utterance's watermark, taken at the first chunk as the limiter is (``limit_take``); ``mark_release`` is the other half."""
         if self.mark is None:
             try:
                 wm = self.mark_pool.pop() if self.mark_pool else None           # (another thread may take the last one first)
@@ -439,12 +470,12 @@ class StreamingVocoder:
                 from .watermark import Watermark
                 wm = Watermark(self.mark_spec.key, self.mark_spec.strength, self.dev, self.side)
             self.mark = wm
-        out = self.mark.push(wav, final)
-        if final:
-            wm, self.mark = self.mark, None
-            if self.mark_pool is not None and len(self.mark_pool) < self.LIMITER_POOL_MAX:
-                self.mark_pool.append(wm)
-        return out
+        return self.mark
+
+    def mark_release(self) -> None:
+        wm, self.mark = self.mark, None
+        if wm is not None and self.mark_pool is not None and len(self.mark_pool) < self.LIMITER_POOL_MAX:
+            self.mark_pool.append(wm)
 
     LIMITER_POOL_MAX = 256
 
@@ -1299,7 +1330,8 @@ class FasterQwen3TTS:
         ``ValueError``.  The audio keeps its length; inside a stream the stage holds back 256
         to 511 samples, which come with the final chunk (or one more, final, chunk).  The marked stream does not depend on how it was
         cut into chunks beyond what the vocoder's windowing does (``exact_streaming``: not at all).  Long form marks the ONE joined
-        stream.  The ``*_batch`` entry points raise ``ValueError``.  ``key``: an integer in [0, 2^64), what ``detect_watermark``
+        stream.  The ``*_batch`` entry points raise ``ValueError`` inside it: they take ``watermark=`` (one ``MarkSpec``, or one or
+        None per text), every row under its own key, the rows of a vocoder group in one launch.  ``key``: an integer in [0, 2^64), what ``detect_watermark``
         needs; ``strength`` in [0.02, 0.3] (0, the stage's identity, is refused here: the context promises a mark), NOT tuned on real voices.  Yields the ``MarkSpec``.  Outside it nothing changes."""
         from .watermark import MarkSpec, design
         spec = MarkSpec(key, strength)
@@ -1329,8 +1361,8 @@ class FasterQwen3TTS:
 
     def _refuse_batch_watermark(self) -> None:
         if getattr(self, "_mark", None) is not None:
-            raise ValueError("the batch entry points do not run the watermark stage yet: call them outside watermark(), or use the "
-                             "single-stream entry points")
+            raise ValueError("the batch entry points take their marks as watermark= (one MarkSpec, or one or None per text: the rows of "
+                             "a batch belong to different callers and the context carries one key): call them outside watermark()")
 
     def _marked(self, x, stream=None):
         """A whole utterance (contiguous float32 device vector) through the open ``watermark`` context's stage on ``stream`` (None:
@@ -1450,10 +1482,10 @@ class FasterQwen3TTS:
         sess.put(key, buf)
         return buf
 
-    def _level(self, wav, key=None, stream=None, inplace: bool = False):
+    def _level(self, wav, key=None, stream=None, inplace: bool = False, limit: bool = True):
         """A whole utterance's waveform (device tensor or host array) as the open ``loudness`` / ``fixed_gain`` / ``limiter`` contexts
         want it: a float32 device vector, measured and scaled, or multiplied by the fixed factor, and then limited.  Outside all of
-        them: ``wav`` itself."""
+        them: ``wav`` itself.  ``limit=False`` (the batch with ``watermark=``): the limiter is left to the caller, behind the mark."""
         if not self._levelling():
             return wav
         from .loudness import apply_gain, gain_of
@@ -1477,7 +1509,7 @@ class FasterQwen3TTS:
                     x.copy_(y)
             else:
                 x = y
-        if getattr(self, "_limit", None) is None:
+        if getattr(self, "_limit", None) is None or not limit:
             return x
         y = self._limited(x, stream)
         if not inplace:
@@ -1551,6 +1583,62 @@ class FasterQwen3TTS:
                 raise ValueError(f"output must be an AudioOutSpec, or a list with one AudioOutSpec or None per text, not {type(sp).__name__}")
         specs = [None if sp is None else sp.validate(self.sample_rate) for sp in specs]
         return specs if any(sp is not None for sp in specs) else None
+
+    def _batch_stage_kw(self, output, watermark, n: int) -> dict:
+        """``output=`` and ``watermark=`` of a batch entry point, validated, as the keywords of ``_run_batch_*``"""
+        outputs = self._batch_outputs(output, n)
+        return dict(outputs=outputs, marks=self._batch_marks(watermark, n, outputs))
+
+    def _batch_marks(self, watermark, n: int, outputs=None) -> Optional[list]:
+        """``watermark=`` of the batch entry points -> None, or one ``MarkSpec`` or None per text: each row is marked under its own
+        key and strength (rows of one batch belong to different callers; the ``watermark()`` context carries one key and keeps
+        refusing the batch).  Every argument error surfaces here, before anything is prepared or decoded: the context itself, a
+        wrong length or type, a strength of 0, a rate other than 24 kHz, a marked row whose ``output`` has a ``speed`` other than 1."""
+        self._refuse_batch_watermark()
+        if watermark is None:
+            return None
+        from .watermark import MarkSpec
+        specs = self._per_text(watermark, n, "watermark")
+        for sp in specs:
+            if sp is not None and not isinstance(sp, MarkSpec):
+                raise ValueError(f"watermark must be a MarkSpec, or a list with one MarkSpec or None per text, not {type(sp).__name__}")
+            if sp is not None and sp.strength == 0.0:
+                raise ValueError("watermark=: strength 0 adds no mark; it is in [0.02, 0.3]")
+        if not any(sp is not None for sp in specs):
+            return None
+        if int(self.sample_rate) != 24000:
+            raise ValueError("the watermark is defined at 24 kHz")
+        for i, sp in enumerate(specs):
+            refuse_marked_speed(sp, None if outputs is None else outputs[i])
+        return specs
+
+    def _take_mark(self, spec, stream):
+        """A ``Watermark`` of ``spec`` on ``stream`` for one utterance of a batched run: an idle one from the model's pool (the one
+        the streaming vocoders use), reset, or a new one."""
+        pool = self.__dict__.setdefault("_mark_pools", {}).setdefault(spec, [])
+        try:
+            wm = pool.pop()
+        except IndexError:
+            wm = None
+        if wm is not None and wm.stream is stream and wm.spec == spec:
+            wm.reset()
+            return wm
+        from .watermark import Watermark
+        return Watermark(spec.key, spec.strength, self.device, stream)
+
+    def _mark_rows(self, specs, rows, stream) -> None:
+        """Whole utterances (contiguous float32 device vectors, ``rows[i]`` under ``specs[i]``) through the mark, IN PLACE (it keeps
+        the length): one ``fq3_mark_push_group`` launch per 32 rows on ``stream``, each row final."""
+        from .watermark import _push_group as mark_group
+        marks = [self._take_mark(sp, stream) for sp in specs]
+        with (torch.cuda.stream(stream) if stream is not None else contextlib.nullcontext()):
+            buf, spans = mark_group(marks, rows, [True] * len(rows))
+            for row, (off, cnt) in zip(rows, spans):
+                row.copy_(buf[off:off + cnt])                       # (the mark reads its frames' neighbours: it cannot run in place)
+        for wm in marks:
+            pool = self._mark_pools[wm.spec]
+            if len(pool) < self.STAGE_POOL_MAX:
+                pool.append(wm)
 
     STAGE_POOL_MAX = 256
 
@@ -1860,14 +1948,15 @@ class FasterQwen3TTS:
         return head, pull
 
     def _run_batch_full(self, prepared, gen_kwargs, lanes: int, count: int, seeds=None, device_audio: bool = False,
-                        outputs=None) -> List[Tuple[list, int]]:
+                        outputs=None, marks=None) -> List[Tuple[list, int]]:
         """The lock-step decode of ``count`` prepared utterances (see :meth:`_batch_feed`) through ``lanes`` lanes, every finished
         utterance vocoded on the side stream (the reference's share of an ICL waveform is cut by not producing it,
         model.py:927-930).  One ``([waveform], sample_rate)`` per entry, in input order.  ``device_audio`` (internal, long form): the
         waveforms are handed out as device tensors valid on the side vocoder's stream -- ``(out, voc)`` is returned -- and the caller
         runs the output chain itself.  ``outputs`` (:meth:`_batch_outputs`): utterance i with a spec comes back as
         ``([encoded array], output rate)`` -- the utterances vocoded together go through the output stage together, behind the levelling
-        step (``_SideVocoder._encode_group``)."""
+        step (``_SideVocoder._encode_group``).  ``marks`` (:meth:`_batch_marks`): the utterances vocoded together that have a
+        ``MarkSpec`` are marked whole in ONE launch (``_mark_rows``), behind the gains and the leveller, in front of the limiter."""
         if not device_audio:
             self._refuse_batch_audio_output()
             self._refuse_batch_watermark()
@@ -1899,13 +1988,19 @@ class FasterQwen3TTS:
         if self._levelling() and not device_audio:
             # between the decode and the pinned copy, on the vocoder's stream (long form levels behind the join instead)
             voc.level = lambda key, wav: self._level(wav, key, voc.stream, inplace=True)
+        if marks is not None:
+            voc.marks, voc.mark_rows = {i: sp for i, sp in enumerate(marks) if sp is not None}, self._mark_rows
+            if voc.level is not None and getattr(self, "_limit", None) is not None:
+                # the limiter runs behind the mark: ``level`` stops in front of it and the rows are limited after the group call
+                voc.level = lambda key, wav: self._level(wav, key, voc.stream, inplace=True, limit=False)
+                voc.limit = lambda key, wav: wav.copy_(self._limited(wav, voc.stream))
         # batch_vocode_every (attribute; default 0 = vocode an utterance when it has ended; N > 0 = produce the waveform in slices every N
         # frames while the utterance still decodes -- exact, see _SideVocoder.inc_add -- so that what is left at the end is the last slice
         # only).  Measured on MI355X (profiles/r04_batch_e2e_vocode_every_*.txt): the slices contend with the latency-bound lock-step
         # frames for more than they save at the end -- 64 lanes x 128 utterances, 0.6B: 561x at 0, 537x at 64, 552x at 100; 1.7B: 458x vs
         # 443x -- so it is OFF by default; a server whose lanes finish at different times has nothing to gain from it either.
         inc = int(getattr(self, "batch_vocode_every", 0) or 0)
-        if inc > 0 and not device_audio and outputs is None and not self._levelling() and voc.async_ok and hasattr(voc.tok, "decode_tensor_batch") and hasattr(voc.tok, "num_samples_total"):
+        if inc > 0 and not device_audio and outputs is None and marks is None and not self._levelling() and voc.async_ok and hasattr(voc.tok, "decode_tensor_batch") and hasattr(voc.tok, "num_samples_total"):
             max_new = min(self._frame_limit(gen_kwargs), int(self.talker_graph.engine.max_frames))
             for rid, codes, info in dec.run(head, source=source, chunk_frames=inc):
                 more = int(getattr(dec, "more_in_poll", 0))
@@ -1935,7 +2030,8 @@ class FasterQwen3TTS:
         return out
 
     def _run_batch_streaming(self, prepared, gen_kwargs, chunk_size: int, lanes: int, rounds=None, stamp=None, seeds=None,
-                             count: Optional[int] = None, device_audio: bool = False, outputs=None, group_marks: bool = False):
+                             count: Optional[int] = None, device_audio: bool = False, outputs=None, group_marks: bool = False,
+                             marks=None):
         """Streaming form of :meth:`_run_batch_full`: yields ``(index, audio_chunk, sample_rate, timing)`` for every
         ``chunk_size`` frames of any utterance -- per utterance exactly the chunks the single-utterance streaming entry point
         would produce (same windowing state machine).  ``timing``: ``chunk_index``, ``total_steps_so_far``, ``is_final``.
@@ -1949,7 +2045,10 @@ class FasterQwen3TTS:
         one copy, and what is yielded for them is the encoded array and the output rate (``flac``: bytes, the stream header in the
         utterance's first chunk).  What the stage held back leaves with the utterance's final event (``StreamingVocoder.flush``).
         ``group_marks`` (internal, long form over many texts): the events a poll hands out together carry ``group_end`` in their
-        timing, True on the last of them, so that the caller can take them through its own stages as one group."""
+        timing, True on the last of them, so that the caller can take them through its own stages as one group.
+        ``marks`` (:meth:`_batch_marks`): utterance i with a ``MarkSpec`` owns a pooled ``Watermark`` under its own key; the marked
+        rows of a launch group go through ONE ``fq3_mark_push_group`` launch between the leveller's group call and the limiter's.  The
+        mark holds back 256 to 511 samples until the utterance's final chunk, so rows leave with their own lengths."""
         self._refuse_streaming_loudness()
         if not device_audio:
             self._refuse_batch_audio_output()
@@ -2026,6 +2125,25 @@ class FasterQwen3TTS:
                                 vocs[part[k][0]].level_release()
                 host = landed = encoded = None
                 staged = [k for k, j in enumerate(part) if vocs[j[0]].output is not None]
+                # rows whose length changes lie back to back in device buffers: ``place[k]`` is (offset in the buffers' concatenation, count)
+                whole, bufs, place = wav, [], [None] * len(part)
+                marked_rows = [k for k, j in enumerate(part) if vocs[j[0]].mark_spec is not None]
+                if marked_rows:
+                    # every marked utterance's own watermark takes its row, under its own key: ONE launch per run.  A row comes back
+                    # shorter by the 256 to 511 samples the mark holds back, or longer at the end; rows without a mark pass untouched
+                    from .watermark import _push_group as mark_group
+                    wav = [whole[k] for k in range(len(part))]
+                    for run in runs:
+                        rows = [k for k in run if k in marked_rows]
+                        if not rows:
+                            continue
+                        buf, spans = mark_group([vocs[part[k][0]].mark_take() for k in rows], [whole[k] for k in rows],
+                                                [finals[k] for k in rows])
+                        for k, (off, cnt) in zip(rows, spans):
+                            wav[k], place[k] = buf[off:off + cnt], (sum(int(b.numel()) for b in bufs) + off, cnt)
+                            if finals[k]:
+                                vocs[part[k][0]].mark_release()
+                        bufs.append(buf)
                 if limit is not None:
                     # every utterance's own limiter takes its row: the rows come back shorter by what it holds back, or longer at the
                     # end.  ONE launch per run; the rows lie back to back in the run's device buffer
@@ -2049,15 +2167,22 @@ class FasterQwen3TTS:
                         if rows:
                             encoded.append((rows, GroupCopy([vocs[part[k][0]]._stage() for k in rows], [wav[k] for k in rows],
                                                             [finals[k] for k in rows])))
-                if limit is not None:
-                    # the rows without an output spec: ONE pinned buffer behind one copy per run, and ONE event
+                if limit is not None or marked_rows:
+                    # the rows without an output spec: ONE pinned buffer behind one copy per run, and ONE event.  Without a limiter the
+                    # rows that have no mark kept their place in the group's tensor: they alone are gathered and follow in one more copy
                     host = [None] * len(part)
                     if len(staged) < len(part):
-                        pinned, at = torch.empty(sum(int(b.numel()) for b in bufs), dtype=torch.float32, pin_memory=True), 0
+                        plain = [k for k in range(len(part)) if place[k] is None and k not in staged]
+                        held, width = sum(int(b.numel()) for b in bufs), int(whole.shape[1])
+                        pinned, at = torch.empty(held + len(plain) * width, dtype=torch.float32, pin_memory=True), 0
                         for buf in bufs:
                             pinned[at:at + int(buf.numel())].copy_(buf, non_blocking=True)
                             at += int(buf.numel())
-                        host = [None if k in staged else pinned[place[k][0]:place[k][0] + place[k][1]] for k in range(len(part))]
+                        if plain:
+                            pinned[held:].copy_(whole[plain].reshape(-1), non_blocking=True)
+                        slot = {k: held + i * width for i, k in enumerate(plain)}
+                        host = [None if k in staged else pinned[place[k][0]:place[k][0] + place[k][1]] if place[k] is not None
+                                else pinned[slot[k]:slot[k] + width] for k in range(len(part))]
                     landed = torch.cuda.Event()
                     landed.record(side)
                 elif not device_audio and len(staged) < len(part):
@@ -2120,6 +2245,9 @@ class FasterQwen3TTS:
                              else self.streaming_vocoder(meta[rid], chunk_size))
                 if outputs is not None and outputs[rid] is not None:
                     vocs[rid].output, vocs[rid].stage = outputs[rid], self._take_stage(outputs[rid], side)
+                if marks is not None and marks[rid] is not None:
+                    vocs[rid].mark_spec = marks[rid]
+                    vocs[rid].mark_pool = self.__dict__.setdefault("_mark_pools", {}).setdefault(marks[rid], [])
                 n_chunks[rid] = 0
             ev = info.pop("codes_ready_event", None)
             final = bool(info.get("is_final"))
@@ -2134,7 +2262,7 @@ class FasterQwen3TTS:
                     else:
                         add_job([rid, out_meta, None, (inp, first, ev, vocs[rid].last_prefix)])
                 else:
-                    staged = limit is not None or lvl is not None or vocs[rid].output is not None
+                    staged = limit is not None or lvl is not None or vocs[rid].output is not None or vocs[rid].mark_spec is not None
                     audio, _sr = vocs[rid].push(codes, ev, final=final) if staged else vocs[rid].push(codes, ev)
                     if final and vocs[rid].output is not None:
                         self._give_stage(vocs[rid].stage)
@@ -2153,7 +2281,7 @@ class FasterQwen3TTS:
                     if vocs[rid].stage.flac and not vocs[rid].header_sent:
                         tail, vocs[rid].header_sent = np.concatenate([np.frombuffer(vocs[rid].stage.header(), dtype=np.uint8), tail]), True
                     self._give_stage(vocs[rid].stage)
-                elif limit is not None and vocs[rid].limit is not None:
+                elif (limit is not None and vocs[rid].limit is not None) or vocs[rid].mark_spec is not None:
                     launch_open()                                  # the utterance's chunks that still wait go in front of its tail
                     held, _sr = vocs[rid].flush()
                     tail = held if len(held) else tail
@@ -2195,17 +2323,19 @@ class FasterQwen3TTS:
                                    non_streaming_mode: Optional[bool] = None, append_silence: bool = True,
                                    instruct: Optional[str] = None,
                                    voice_clone_prompt: Optional[Union[Dict[str, Any], List[Any]]] = None,
-                                   lanes: int = 8, seeds=None, output=None) -> List[Tuple[list, int]]:
+                                   lanes: int = 8, watermark=None, seeds=None, output=None) -> List[Tuple[list, int]]:
         """Voice cloning of several texts with one voice: up to ``lanes`` (<= 128) utterances decode in lock-step over
         one pass of the weights per frame (``fq3_batch_*``), finished lanes are refilled from the queue.  Returns one
         ``([np.float32 waveform], sample_rate)`` per text, in input order; each utterance follows exactly the
-        single-utterance semantics of :meth:`generate_voice_clone`, nucleus sampling (``top_p < 1``) included."""
+        single-utterance semantics of :meth:`generate_voice_clone`, nucleus sampling (``top_p < 1``) included.  ``watermark`` (all
+        batch entry points): a ``watermark.MarkSpec``, or a list with one or None per text -- each text's audio carries its own keyed
+        mark (``FasterQwen3TTS.watermark`` describes it), the texts vocoded together in one launch."""
         nsm = self._resolve_non_streaming_mode(non_streaming_mode, default=False)
         prepared = self._prepare_clone_batch(texts, language, ref_audio, ref_text, xvec_only, nsm, append_silence, instruct,
                                              voice_clone_prompt)
         return self._run_batch_full(prepared, self._gen_kwargs(max_new_tokens, min_new_tokens, temperature, top_k, top_p, do_sample,
                                                                repetition_penalty), lanes, len(texts), seeds=seeds,
-                                    outputs=self._batch_outputs(output, len(texts)))
+                                    **self._batch_stage_kw(output, watermark, len(texts)))
 
     @torch.inference_mode()
     def generate_voice_clone_batch_streaming(self, texts: List[str], language: Union[str, List[str]] = "English",
@@ -2216,7 +2346,7 @@ class FasterQwen3TTS:
                                              non_streaming_mode: Optional[bool] = None, append_silence: bool = True,
                                              instruct: Optional[str] = None,
                                              voice_clone_prompt: Optional[Union[Dict[str, Any], List[Any]]] = None,
-                                             lanes: int = 8, seeds=None, output=None) -> Generator[Tuple[int, np.ndarray, int, dict], None, None]:
+                                             lanes: int = 8, watermark=None, seeds=None, output=None) -> Generator[Tuple[int, np.ndarray, int, dict], None, None]:
         """Streaming AND batched: the texts decode in lock-step lanes (as :meth:`generate_voice_clone_batch`) and every
         ``chunk_size`` frames of any utterance yield ``(text_index, audio_chunk, sample_rate, timing)`` -- per utterance
         exactly the chunks :meth:`generate_voice_clone_streaming` would produce for it (same windowing state machine).
@@ -2227,7 +2357,7 @@ class FasterQwen3TTS:
                                              voice_clone_prompt)
         yield from self._run_batch_streaming(prepared, self._gen_kwargs(max_new_tokens, min_new_tokens, temperature, top_k, top_p,
                                                                          do_sample, repetition_penalty), chunk_size, lanes,
-                                             seeds=seeds, count=len(texts), outputs=self._batch_outputs(output, len(texts)))
+                                             seeds=seeds, count=len(texts), **self._batch_stage_kw(output, watermark, len(texts)))
 
     def _prepare_custom_batch(self, texts, speaker, language, instruct, non_streaming_mode):
         n = len(texts)
@@ -2248,7 +2378,7 @@ class FasterQwen3TTS:
                                     instruct: Optional[Union[str, List[Optional[str]]]] = None,
                                     non_streaming_mode: Optional[bool] = None, max_new_tokens: int = 2048, min_new_tokens: int = 2,
                                     temperature: float = 0.9, top_k: int = 50, top_p: float = 1.0, do_sample: bool = True,
-                                    repetition_penalty: float = 1.05, lanes: int = 16, seeds=None, output=None) -> List[Tuple[list, int]]:
+                                    repetition_penalty: float = 1.05, lanes: int = 16, watermark=None, seeds=None, output=None) -> List[Tuple[list, int]]:
         """CustomVoice for several texts (BASELINE configs[3]: many concurrent utterances of a CustomVoice model): every
         utterance is prepared exactly like :meth:`generate_custom_voice` (speaker-id prompt, model.py:1139-1326; ``speaker`` /
         ``language`` / ``instruct`` may be one value or one per text) and up to ``lanes`` of them decode in lock-step over one pass of
@@ -2256,7 +2386,7 @@ class FasterQwen3TTS:
         prepared = self._prepare_custom_batch(texts, speaker, language, instruct, non_streaming_mode)
         return self._run_batch_full(prepared, self._gen_kwargs(max_new_tokens, min_new_tokens, temperature, top_k, top_p, do_sample,
                                                                repetition_penalty), lanes, len(texts), seeds=seeds,
-                                    outputs=self._batch_outputs(output, len(texts)))
+                                    **self._batch_stage_kw(output, watermark, len(texts)))
 
     @torch.inference_mode()
     def generate_custom_voice_batch_streaming(self, texts: List[str], speaker: Union[str, List[str]],
@@ -2265,23 +2395,23 @@ class FasterQwen3TTS:
                                               non_streaming_mode: Optional[bool] = None, max_new_tokens: int = 2048,
                                               min_new_tokens: int = 2, temperature: float = 0.9, top_k: int = 50, top_p: float = 1.0,
                                               do_sample: bool = True, repetition_penalty: float = 1.05, chunk_size: int = 12,
-                                              lanes: int = 16, seeds=None, output=None) -> Generator[Tuple[int, np.ndarray, int, dict], None, None]:
+                                              lanes: int = 16, watermark=None, seeds=None, output=None) -> Generator[Tuple[int, np.ndarray, int, dict], None, None]:
         """Streaming form of :meth:`generate_custom_voice_batch`: ``(text_index, audio_chunk, sample_rate, timing)`` per chunk."""
         prepared = self._prepare_custom_batch(texts, speaker, language, instruct, non_streaming_mode)
         yield from self._run_batch_streaming(prepared, self._gen_kwargs(max_new_tokens, min_new_tokens, temperature, top_k, top_p,
                                                                          do_sample, repetition_penalty), chunk_size, lanes,
-                                             seeds=seeds, count=len(texts), outputs=self._batch_outputs(output, len(texts)))
+                                             seeds=seeds, count=len(texts), **self._batch_stage_kw(output, watermark, len(texts)))
 
     @torch.inference_mode()
     def generate_voice_design_batch(self, texts: List[str], instruct: Union[str, List[str]], language: Union[str, List[str]] = "English",
                                     non_streaming_mode: Optional[bool] = None, max_new_tokens: int = 2048, min_new_tokens: int = 2,
                                     temperature: float = 0.9, top_k: int = 50, top_p: float = 1.0, do_sample: bool = True,
-                                    repetition_penalty: float = 1.05, lanes: int = 16, seeds=None, output=None) -> List[Tuple[list, int]]:
+                                    repetition_penalty: float = 1.05, lanes: int = 16, watermark=None, seeds=None, output=None) -> List[Tuple[list, int]]:
         """VoiceDesign for several texts in lock-step lanes; every utterance prepared like :meth:`generate_voice_design`."""
         return self._run_batch_full(self._prepare_design_batch(texts, instruct, language, non_streaming_mode),
                                     self._gen_kwargs(max_new_tokens, min_new_tokens, temperature, top_k, top_p, do_sample, repetition_penalty),
                                     lanes, len(texts), seeds=seeds,
-                                    outputs=self._batch_outputs(output, len(texts)))
+                                    **self._batch_stage_kw(output, watermark, len(texts)))
 
     def _prepare_design_batch(self, texts, instruct, language, non_streaming_mode):
         n = len(texts)
@@ -2301,12 +2431,12 @@ class FasterQwen3TTS:
                                               language: Union[str, List[str]] = "English", non_streaming_mode: Optional[bool] = None,
                                               max_new_tokens: int = 2048, min_new_tokens: int = 2, temperature: float = 0.9,
                                               top_k: int = 50, top_p: float = 1.0, do_sample: bool = True, repetition_penalty: float = 1.05,
-                                              chunk_size: int = 12, lanes: int = 16, seeds=None, output=None) -> Generator[Tuple[int, np.ndarray, int, dict], None, None]:
+                                              chunk_size: int = 12, lanes: int = 16, watermark=None, seeds=None, output=None) -> Generator[Tuple[int, np.ndarray, int, dict], None, None]:
         """Streaming form of :meth:`generate_voice_design_batch`: ``(text_index, audio_chunk, sample_rate, timing)`` per chunk."""
         prepared = self._prepare_design_batch(texts, instruct, language, non_streaming_mode)
         yield from self._run_batch_streaming(prepared, self._gen_kwargs(max_new_tokens, min_new_tokens, temperature, top_k, top_p,
                                                                          do_sample, repetition_penalty), chunk_size, lanes,
-                                             seeds=seeds, count=len(texts), outputs=self._batch_outputs(output, len(texts)))
+                                             seeds=seeds, count=len(texts), **self._batch_stage_kw(output, watermark, len(texts)))
 
     @torch.inference_mode()
     def generate_voice_clone_streaming(self, text: str, language: str, ref_audio: Optional[Union[str, Path]] = None,
@@ -2411,15 +2541,17 @@ class FasterQwen3TTS:
         join_bound(self.sample_rate, spec.threshold, spec.lead_hops, spec.tail_hops, spec.hold_hops, 0, 0)
         return spec, segs
 
-    def _long_chain(self, spec, segs, stream, level_hops: Optional[int] = None, output=None):
+    def _long_chain(self, spec, segs, stream, level_hops: Optional[int] = None, output=None, mark=None):
         """The request's ONE output stream: the join stage and, inside ``audio_output`` (or with ``output``, a text's spec in the
-        many-text form), the chain behind it, all on ``stream``."""
+        many-text form), the chain behind it, all on ``stream``.  ``mark``: a text's ``MarkSpec`` in the many-text form (None: the open
+        ``watermark`` context's, if any)."""
         from .long_form import OrderedJoin, SegmentJoin
         dev = torch.device(self.device) if not isinstance(self.device, torch.device) else self.device
         join = SegmentJoin.from_spec(spec, self.sample_rate, dev, stream=stream)
         chain = None
         output = self._audio_spec if output is None else output
-        refuse_marked_speed(getattr(self, "_mark", None), output)
+        mark = getattr(self, "_mark", None) if mark is None else mark
+        refuse_marked_speed(mark, output)
         if output is not None:
             from .audio_out import AudioOut
             chain = AudioOut(output, self.sample_rate, join.dev, stream)
@@ -2433,10 +2565,10 @@ class FasterQwen3TTS:
             from .leveller import Leveller
             # behind the join and the gains, in front of the limiter: ONE leveller for the joined stream
             oj.leveller = Leveller(self._lvl, self.sample_rate, join.dev, stream, capacity_hops=max(level_hops or 0, 4096))
-        if getattr(self, "_mark", None) is not None:
+        if mark is not None:
             from .watermark import Watermark
             # behind the join, the gains and the leveller, in front of the limiter: ONE mark on the joined stream
-            oj.marker = Watermark(self._mark.key, self._mark.strength, join.dev, stream)
+            oj.marker = Watermark(mark.key, mark.strength, join.dev, stream)
         self._last_levelled = oj.leveller
         return oj, chain
 
@@ -2592,20 +2724,24 @@ class FasterQwen3TTS:
         req_seeds = [None if s is None else (s + k) % 2 ** 64 for s, sg in zip(per_text, segs) for k in range(len(sg))]
         return spec, segs, (req_seeds if seeds is not None else None), outputs
 
-    def _long_batch_chains(self, spec, segs, stream, gen_kwargs, outputs):
-        """one ordered join and chain per text, all on ``stream`` -> (``OrderedJoinSet``, the chains)"""
+    def _long_batch_chains(self, spec, segs, stream, gen_kwargs, outputs, marks=None):
+        """one ordered join and chain per text (and one mark, for a text that has a ``MarkSpec``), all on ``stream`` ->
+        (``OrderedJoinSet``, the chains)"""
         from .long_form import OrderedJoinSet
-        pairs = [self._long_chain(spec, sg, stream, self._long_level_hops(spec, sg, gen_kwargs), None if outputs is None else outputs[t])
+        pairs = [self._long_chain(spec, sg, stream, self._long_level_hops(spec, sg, gen_kwargs), None if outputs is None else outputs[t],
+                                   None if marks is None else marks[t])
                  for t, sg in enumerate(segs)]
         return OrderedJoinSet([oj for oj, _c in pairs]), [c for _oj, c in pairs]
 
-    def _run_long_batch_full(self, prepared, segs, spec, gen_kwargs, lanes: int, seeds, outputs) -> List[Tuple[list, int]]:
+    def _run_long_batch_full(self, prepared, segs, spec, gen_kwargs, lanes: int, seeds, outputs, marks=None) -> List[Tuple[list, int]]:
         """``_run_long_full`` over many texts: one lock-step run over every segment of every text; round ``k`` joins segment ``k`` of
-        every text that has one in ONE group call on the side vocoder's stream."""
+        every text that has one in ONE group call on the side vocoder's stream.  ``marks`` (``_batch_marks`` over the texts): one
+        mark per text on its joined stream, a round's rows in one launch.  The public entry points do not hand any in yet: their
+        signatures are the single-text twins' plus ``seeds`` and ``output``."""
         counts = [len(sg) for sg in segs]
         base = [sum(counts[:t]) for t in range(len(segs))]
         outs, voc = self._run_batch_full(prepared, gen_kwargs, lanes, sum(counts), seeds=seeds, device_audio=True)
-        ojs, _chains = self._long_batch_chains(spec, segs, voc.stream, gen_kwargs, outputs)
+        ojs, _chains = self._long_batch_chains(spec, segs, voc.stream, gen_kwargs, outputs, marks)
         parts: List[list] = [[] for _ in segs]
         with (torch.cuda.stream(voc.stream) if voc.stream is not None else contextlib.nullcontext()):
             for oj in ojs.ordered:
@@ -2635,7 +2771,7 @@ class FasterQwen3TTS:
                     result.append(([pcm.cpu().numpy()], self.sample_rate))
             return result
 
-    def _run_long_batch_streaming(self, prepared, segs, spec, gen_kwargs, chunk_size: int, lanes: int, seeds, outputs):
+    def _run_long_batch_streaming(self, prepared, segs, spec, gen_kwargs, chunk_size: int, lanes: int, seeds, outputs, marks=None):
         """``_run_long_streaming`` over many texts: the chunks a poll of the lock-step run hands out together go through ONE
         ``feed_group``; every text's audio leaves in text order, the texts interleave as they become ready."""
         self._refuse_streaming_loudness()
@@ -2643,7 +2779,7 @@ class FasterQwen3TTS:
         where = [(t, k) for t, n in enumerate(counts) for k in range(n)]
         tok = self.model.model.speech_tokenizer
         side = self._vocoder_stream(tok)
-        ojs, chains = self._long_batch_chains(spec, segs, side, gen_kwargs, outputs)
+        ojs, chains = self._long_batch_chains(spec, segs, side, gen_kwargs, outputs, marks)
         rates = [c.out_rate if c is not None else self.sample_rate for c in chains]
         header = [c is not None and c.flac for c in chains]
         index = [0] * len(segs)
@@ -2943,7 +3079,7 @@ class FasterQwen3TTS:
         return BatchRequest(rid, talker, tie, tam, tie.new_zeros(1, 0, tie.shape[-1]), tpe, config, dict(gen_kwargs),
                             text_feeder=feeder, tts_eos_id=int(m.config.tts_eos_token_id), seed=seed)
 
-    def _run_text_batch_streaming(self, text_iters, prepares, gen_kwargs, chunk_size: int, lanes: int, seeds=None, outputs=None):
+    def _run_text_batch_streaming(self, text_iters, prepares, gen_kwargs, chunk_size: int, lanes: int, seeds=None, outputs=None, marks=None):
         """Shared back half of the ``stream_*_batch`` entry points.  A request enters the scheduler when its first token exists;
         streams whose first token has not arrived wait beside it and do not block the others."""
         import threading
@@ -2979,14 +3115,14 @@ class FasterQwen3TTS:
             if timing.get("chunk_index") == 0 and feeders[i].t_first is not None:
                 timing["first_text_ms"] = (time.time() - feeders[i].t_first) * 1000      # first piece received -> first audio
 
-        yield from self._run_batch_streaming(None, gen_kwargs, chunk_size, lanes, rounds=rounds, stamp=stamp, outputs=outputs)
+        yield from self._run_batch_streaming(None, gen_kwargs, chunk_size, lanes, rounds=rounds, stamp=stamp, outputs=outputs, marks=marks)
 
     @torch.inference_mode()
     def stream_custom_voice_batch(self, text_iters, speaker: Union[str, List[str]], language: Union[str, List[str]] = "English",
                                   instruct: Optional[Union[str, List[Optional[str]]]] = None, chunk_size: int = 12,
                                   max_new_tokens: int = 2048, min_new_tokens: int = 2, temperature: float = 0.9, top_k: int = 50,
                                   top_p: float = 1.0, do_sample: bool = True, repetition_penalty: float = 1.05,
-                                  lanes: int = 16, seeds=None, output=None) -> Generator[Tuple[int, np.ndarray, int, dict], None, None]:
+                                  lanes: int = 16, watermark=None, seeds=None, output=None) -> Generator[Tuple[int, np.ndarray, int, dict], None, None]:
         """``generate_custom_voice_batch_streaming(..., non_streaming_mode=False)`` for texts that are still arriving: every element of
         ``text_iters`` is an iterable of ``str`` pieces or a ``TextFeeder`` (an LLM's token stream per utterance), and up to ``lanes``
         of them decode in lock-step while their text comes in.  Yields ``(index, audio_chunk, sample_rate, timing)``; per utterance the
@@ -3003,13 +3139,13 @@ class FasterQwen3TTS:
         yield from self._run_text_batch_streaming(text_iters, [prep(*a) for a in zip(spks, langs, inss)],
                                                   self._gen_kwargs(max_new_tokens, min_new_tokens, temperature, top_k, top_p, do_sample,
                                                                    repetition_penalty), chunk_size, lanes, seeds=seeds,
-                                                  outputs=self._batch_outputs(output, len(text_iters)))
+                                                  **self._batch_stage_kw(output, watermark, len(text_iters)))
 
     @torch.inference_mode()
     def stream_voice_design_batch(self, text_iters, instruct: Union[str, List[str]], language: Union[str, List[str]] = "English",
                                   chunk_size: int = 12, max_new_tokens: int = 2048, min_new_tokens: int = 2, temperature: float = 0.9,
                                   top_k: int = 50, top_p: float = 1.0, do_sample: bool = True, repetition_penalty: float = 1.05,
-                                  lanes: int = 16, seeds=None, output=None) -> Generator[Tuple[int, np.ndarray, int, dict], None, None]:
+                                  lanes: int = 16, watermark=None, seeds=None, output=None) -> Generator[Tuple[int, np.ndarray, int, dict], None, None]:
         """``generate_voice_design_batch_streaming(..., non_streaming_mode=False)`` for texts that are still arriving (see
         :meth:`stream_custom_voice_batch`)."""
         n = len(text_iters)
@@ -3023,7 +3159,7 @@ class FasterQwen3TTS:
         yield from self._run_text_batch_streaming(text_iters, [prep(*a) for a in zip(inss, langs)],
                                                   self._gen_kwargs(max_new_tokens, min_new_tokens, temperature, top_k, top_p, do_sample,
                                                                    repetition_penalty), chunk_size, lanes, seeds=seeds,
-                                                  outputs=self._batch_outputs(output, len(text_iters)))
+                                                  **self._batch_stage_kw(output, watermark, len(text_iters)))
 
     @torch.inference_mode()
     def stream_voice_clone_batch(self, text_iters, language: Union[str, List[str]] = "English",
@@ -3032,7 +3168,7 @@ class FasterQwen3TTS:
                                  do_sample: bool = True, repetition_penalty: float = 1.05, xvec_only: bool = True,
                                  append_silence: bool = True, instruct: Optional[str] = None,
                                  voice_clone_prompt: Optional[Union[Dict[str, Any], List[Any]]] = None,
-                                 lanes: int = 16, seeds=None, output=None) -> Generator[Tuple[int, np.ndarray, int, dict], None, None]:
+                                 lanes: int = 16, watermark=None, seeds=None, output=None) -> Generator[Tuple[int, np.ndarray, int, dict], None, None]:
         """``generate_voice_clone_batch_streaming(..., non_streaming_mode=False)`` for texts that are still arriving, one x-vector-only
         voice for all of them.  An ICL voice is refused with the message of :meth:`stream_voice_clone`."""
         why = self._refuse_icl_text_stream(xvec_only, voice_clone_prompt)
@@ -3050,4 +3186,4 @@ class FasterQwen3TTS:
         yield from self._run_text_batch_streaming(text_iters, [prep(l) for l in langs],
                                                   self._gen_kwargs(max_new_tokens, min_new_tokens, temperature, top_k, top_p, do_sample,
                                                                    repetition_penalty), chunk_size, lanes, seeds=seeds,
-                                                  outputs=self._batch_outputs(output, len(text_iters)))
+                                                  **self._batch_stage_kw(output, watermark, len(text_iters)))

@@ -890,6 +890,26 @@ int fq3_mark_reset(fq3_mark* m, void* stream);               /* a new stream on 
  * final push: FQ3_ESTATE until fq3_mark_reset. */
 int fq3_mark_push(fq3_mark* m, const float* pcm, int64_t n_in, int final, float* out, int64_t capacity_samples, int64_t* n_out,
                   void* stream);
+/* The mark for a GROUP of streams, as fq3_limit_push_group below and with its conventions.  Every array is a HOST array of B entries;
+ * row b is exactly
+ *     fq3_mark_push(objs[b], pcm[b], n_in[b], final[b], out[b], capacity_samples[b], &n_out[b], stream)
+ *   Equality.        What row b writes, n_out[b] and the history objs[b] keeps are bit for bit those of the single push, whatever the
+ *                    other rows are and wherever the row falls in the grid: the same device code computes them, and each delta_t is a
+ *                    function of frame t's 512 samples alone.  Rows may differ in key and strength.  Group and single pushes mix
+ *                    freely on one object; membership and order may change from call to call.
+ *   Launches.        At most ONE for the whole call, on one packed grid: row b owns ceil(ceil(n_out[b] / H) / 15) + 1 workgroups (the
+ *                    last keeps the history; a row that completes no hop still has that one), and none when n_in[b] == 0 and it is
+ *                    not final.  No launch when no row needs one.  No host synchronisation and no copy: the rows' descriptors travel
+ *                    in the launch's argument block.  n_out[b] follows from the lengths alone.  pcm[b] and out[b] must stay valid
+ *                    until the stream has run the call.
+ *   All or nothing.  Every row is checked before any object changes: first the call's own limits below over all rows, then row by
+ *                    row the single push's own checks (FQ3_ESTATE after a final push, FQ3_EINVAL for bad input or capacity), of
+ *                    which the first failing row's code is returned.  On any error nothing is launched and no object has moved.
+ *   Limits.          B == 0: returns 0, does nothing.  B < 0, B > FQ3_STAGE_GROUP_MAX, a null array, a null object, the same object
+ *                    twice in one call, or objects created on different devices: FQ3_EINVAL.  Range and null errors are answered
+ *                    before any HIP call. */
+int fq3_mark_push_group(fq3_mark* const* objs, int B, const float* const* pcm, const int64_t* n_in, const int* final,
+                        float* const* out, const int64_t* capacity_samples, int64_t* n_out, void* stream);
 /* floats of device workspace fq3_mark_detect needs for n samples, n in [512, 2^27]; negative: an FQ3_E* code */
 int64_t fq3_mark_detect_workspace(int64_t n);
 /* pcm: n device floats at 24 kHz.  z: 32 x 128 device floats, z[o / 8][phi].  Two launches on `stream` (the partial sums of every

@@ -10,7 +10,8 @@ Also, so that one file holds them: the embed and detect error bounds of tests/te
 a = 0.1 repeat on the synthetic voiced signal of tests/_mark_ref.py -- SNR and the detector's max z for the marked signal behind s16,
 cropped by 1000 samples, behind a 24 -> 8 -> 24 kHz round trip, unmarked and under another key.  Writes profiles/watermark.json.
 usage: watermark_probe.py [runs=60] [out.json]
-       watermark_probe.py --scan [runs=30] [out.json]    the scan against one-by-one detect (``scan_main``) -> profiles/mark_scan.json"""
+       watermark_probe.py --scan [runs=30] [out.json]    the scan against one-by-one detect (``scan_main``) -> profiles/mark_scan.json
+       watermark_probe.py --group 1,8,32 [runs=60] [out.json]    the group push against single pushes (``group_main``) -> profiles/mark_group.json"""
 import json
 import os
 import sys
@@ -142,8 +143,60 @@ def scan_main(argv):
         f.write("\n")
 
 
+def group_main(argv):
+    """--group 1,8,32: for every row count B, one 8-frame chunk (15 360 samples) per row pushed into B running streams, each under
+    its own key -- ``push_group`` (fq3_mark_push_group: one launch) against the same chunks through ``Watermark.push`` row by row on
+    a second set of streams, in the same run: HIP events, the two paths alternating inside every repeat, medians and quartiles (the
+    quartiles are the run's own spread).  Writes profiles/mark_group.json."""
+    import statistics
+    from loudness_probe import event_ms
+    counts = [int(v) for v in argv[0].split(",")]
+    runs = max(20, int(argv[1])) if len(argv) > 1 else 60
+    out_path = argv[2] if len(argv) > 2 else os.path.join(ROOT, "profiles", "mark_group.json")
+    g = torch.Generator().manual_seed(3)
+    pool = [speech_like(8 * SAMPLES_PER_FRAME, g) for _ in range(max(counts))]
+    rows = []
+    for B in counts:
+        chunks = pool[:B]
+        grouped, singles = [[W.Watermark(KEY + b, 0.1, "cuda") for b in range(B)] for _ in range(2)]
+        fns = {"group": lambda: W.push_group(grouped, chunks, [False] * B),
+               "single": lambda: [m.push(c) for m, c in zip(singles, chunks)]}
+        for _ in range(8):                                         # warm-up; the streams are running from here on
+            for fn in fns.values():
+                fn()
+        torch.cuda.synchronize()
+        marks = {k: [] for k in fns}
+        for _ in range(runs):
+            for k, fn in fns.items():
+                marks[k].append(event_ms(fn))
+            torch.cuda.synchronize()
+        row = {"rows": B, "n_in_per_row": int(chunks[0].numel()), "group_launches": 1, "single_launches": B,
+               "group_workgroups": B * (-(-(int(chunks[0].numel()) // W.H) // 15) + 1)}
+        for k, v in marks.items():
+            ms = sorted(a.elapsed_time(b) for a, b in v)
+            q = statistics.quantiles(ms, n=4)
+            row.update({k + "_ms": round(statistics.median(ms), 4), k + "_p25_ms": round(q[0], 4), k + "_p75_ms": round(q[2], 4)})
+        row["single_over_group"] = round(row["single_ms"] / row["group_ms"], 3)
+        rows.append(row)
+        print(row, flush=True)
+    res = {"device": torch.cuda.get_device_name(0), "runs": runs, "rate": 24000,
+           "method": "HIP events around each path, the group call and the row-by-row pushes alternating inside every repeat; medians, "
+                     "with the quartiles as the run's own spread",
+           "rows": rows,
+           "notes": ["the event pairs include the Python wrappers' output allocations: one per group call, one per single push",
+                     "at 32 rows every workgroup streams the 512 KB of DFT tables from L2",
+                     "NOT measured: the end-to-end factor of a 128-lane batch with watermark="]}
+    os.makedirs(os.path.dirname(out_path) or ".", exist_ok=True)
+    with open(out_path, "w") as f:
+        json.dump(res, f, indent=1)
+        f.write("\n")
+
+
 if __name__ == "__main__":
-    if "--scan" in sys.argv[1:]:
+    if "--group" in sys.argv[1:]:
+        at = sys.argv.index("--group")
+        group_main(sys.argv[at + 1:])
+    elif "--scan" in sys.argv[1:]:
         scan_main([a for a in sys.argv[1:] if a != "--scan"])
     else:
         main()

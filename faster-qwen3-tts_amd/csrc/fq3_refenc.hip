@@ -25,6 +25,7 @@
 #define FQ3_SKINNY_EXTERN           // skinny_gemm.cuh: the weight-stationary GEMM kernels are instantiated in fq3_prefill.hip only
 #include "../../include/fq3hip.h"
 #include "refenc_kernels.cuh"
+#include "spkgroup_kernels.cuh"
 
 #include <algorithm>
 #include <cmath>
@@ -45,6 +46,7 @@ struct fq3_refenc {
     std::map<std::string, int64_t> wn;
     float* ws = nullptr; size_t ws_floats = 0, ws_used = 0;
     float* books = nullptr;                    // prepared codebooks: per level emb [K][D] then embT [D][K]
+    float* frag = nullptr;                     // fragment-major copies of the DFT table and the mel basis (the speaker group's front end)
     bool tok_ready = false, spk_ready = false;
 };
 
@@ -89,6 +91,7 @@ extern "C" int fq3_refenc_destroy(fq3_refenc* r) {
     (void)hipDeviceSynchronize();
     if (r->ws) (void)hipFree(r->ws);
     if (r->books) (void)hipFree(r->books);
+    if (r->frag) (void)hipFree(r->frag);
     delete r;
     return FQ3_OK;
 }
@@ -102,6 +105,23 @@ extern "C" int fq3_refenc_bind(fq3_refenc* r, const char* name, const void* ptr,
 static bool has_prefix(const fq3_refenc* r, const char* p) {
     auto it = r->w.lower_bound(p);
     return it != r->w.end() && it->first.compare(0, strlen(p), p) == 0;
+}
+
+// the fragment-major tables of the speaker group's front end, [dft 2 NB x n_fft | mel basis mel_dim x NB]: packed by finalize, which
+// waits for them, so that a group call on any stream finds them complete
+static int spk_frag_prepare(fq3_refenc* r, hipStream_t s) {
+    const auto& c = r->cfg;
+    const float *dft = nullptr, *basis = nullptr;
+    int e;
+    const size_t nd = (size_t)2 * c.n_bins_padded * c.n_fft, nb = (size_t)c.mel_dim * c.n_bins_padded;
+    if ((e = need(r, "speaker_encoder.mel.dft", (int64_t)nd, &dft)) || (e = need(r, "speaker_encoder.mel.basis", (int64_t)nb, &basis))) return e;
+    float* f = nullptr;
+    if (hipMalloc((void**)&f, (nd + nb) * sizeof(float)) != hipSuccess) { (void)hipGetLastError(); return rfail(FQ3_ENOMEM, "speaker group: operand tables"); }
+    hipLaunchKernelGGL(spk_frag_pack_kernel, dim3((unsigned)((nd + 255) / 256)), dim3(256), 0, s, dft, f, 2 * c.n_bins_padded, c.n_fft);
+    hipLaunchKernelGGL(spk_frag_pack_kernel, dim3((unsigned)((nb + 255) / 256)), dim3(256), 0, s, basis, f + nd, c.mel_dim, c.n_bins_padded);
+    if (hipGetLastError() != hipSuccess) { (void)hipFree(f); return rfail(FQ3_EHIP, "speaker group: packing the operand tables"); }
+    r->frag = f;
+    return FQ3_OK;
 }
 
 extern "C" int fq3_refenc_finalize(fq3_refenc* r, void* stream) {
@@ -130,9 +150,12 @@ extern "C" int fq3_refenc_finalize(fq3_refenc* r, void* stream) {
     }
     if (has_prefix(r, "speaker_encoder.")) {
         const int NB = g.n_bins_padded;
+        if (r->frag) { (void)hipDeviceSynchronize(); (void)hipFree(r->frag); r->frag = nullptr; }       // (a group call on any stream may still read them)
         if ((e = need(r, "speaker_encoder.mel.dft", (int64_t)2 * NB * g.n_fft, nullptr))) return e;
         if ((e = need(r, "speaker_encoder.mel.basis", (int64_t)g.mel_dim * NB, nullptr))) return e;
         if ((e = need(r, "speaker_encoder.fc.weight", (int64_t)g.enc_dim * 2 * g.enc_channels[g.n_enc - 1], nullptr))) return e;
+        if ((e = spk_frag_prepare(r, s))) return e;
+        RHIP(hipStreamSynchronize(s));
         r->spk_ready = true;
     }
     if (!r->tok_ready && !r->spk_ready) return rfail(FQ3_ESTATE, "no encoder.* or speaker_encoder.* weights bound");
@@ -147,13 +170,18 @@ extern "C" int64_t fq3_refenc_num_frames(const fq3_refenc* r, int64_t n) {
     return ceil_div(n, 2);
 }
 
-// bump allocator over one lazily grown device workspace (grown only between calls, after a stream sync)
+// bump allocator over one lazily grown device workspace (grown only between calls, after a stream sync).  A refused growth
+// (FQ3_ENOMEM) leaves the object without a workspace but usable: the next call allocates again.
 static int ws_reserve(fq3_refenc* r, size_t floats, hipStream_t s) {
     r->ws_used = 0;
     if (floats <= r->ws_floats) return 0;
     RHIP(hipStreamSynchronize(s));
     if (r->ws) { (void)hipFree(r->ws); r->ws = nullptr; r->ws_floats = 0; }
-    RHIP(hipMalloc((void**)&r->ws, floats * sizeof(float)));
+    if (hipMalloc((void**)&r->ws, floats * sizeof(float)) != hipSuccess) {
+        (void)hipGetLastError();
+        r->ws = nullptr;
+        return rfail(FQ3_ENOMEM, "reference-audio workspace: " + std::to_string(floats * sizeof(float)) + " bytes");
+    }
     r->ws_floats = floats;
     return 0;
 }
@@ -392,6 +420,191 @@ extern "C" int fq3_refenc_speaker(fq3_refenc* r, const float* pcm, int64_t n, fl
     { GemmArgs a = gemm(A1, Ac, F, F, Ac, W(S + "asp.conv.weight"), Cm, W(S + "asp.conv.bias"), Lg, Cm); if (err) return err; gemm_launch<float>(a, s); }
     hipLaunchKernelGGL(col_stats_kernel, dim3((Cm + 63) / 64), dim3(64 * kStatSlices), 0, s, (const float*)Hm, Cm, (const float*)Lg, Cm, pooled, pooled + Cm, F, Cm, 1e-12f);
     { GemmArgs a = gemm(pooled, 2 * Cm, 1, 1, 2 * Cm, W(S + "fc.weight"), g.enc_dim, W(S + "fc.bias"), embed, g.enc_dim); if (err) return err; gemm_launch<float>(a, s); }
+    RHIP(hipGetLastError());
+    return FQ3_OK;
+}
+
+// ---- speaker encoder, group form -------------------------------------------------------------------
+//   fq3_refenc_speaker_group   the x-vectors of 1..32 clips of different lengths, in a number of launches that does not depend on
+//                              the number of clips (spkgroup_kernels.cuh states the row spaces and the kernels)
+//   fq3_refenc_similarity      cosines of embedding pairs, one launch
+// The stack is fq3_refenc_speaker's, layer for layer and rounding point for rounding point: the dense products run once over all
+// clips' rows through the same fp32 tap GEMM, the per-clip parts (reflect padding, statistics, gates) through the group kernels, and
+// the M = 1 products of the single call (SE gates, the pooled [mean | std] projections, the final linear) become M = rows products.
+namespace {
+
+struct SpkPlan {
+    SpkGroupArgs g{};
+    int rows = 0, gap = 0;
+    int64_t sumF = 0, M = 0;            // compact rows, gapped rows
+    size_t floats = 0;                  // workspace
+};
+
+// Validates everything the host can see and lays the rows out; launches nothing.  pcm may be null (the workspace query).
+int spk_plan(const fq3_refenc* r, const float* const* pcm, const int64_t* n, int rows, SpkPlan& p) {
+    if (!r || !n) return rfail(FQ3_EINVAL, "null argument");
+    if (rows < 1 || rows > kSpkGroupMax) return rfail(FQ3_EINVAL, "rows must be in 1.." + std::to_string(kSpkGroupMax) + " (got " + std::to_string(rows) + ")");
+    const auto& c = r->cfg;
+    const int pad = (c.n_fft - c.hop) / 2;
+    for (int i = 0; i < c.n_enc; ++i) p.gap = std::max(p.gap, (c.enc_kernel_sizes[i] - 1) * c.enc_dilations[i]);
+    p.rows = p.g.n_rows = rows;
+    for (int b = 0; b < rows; ++b) {
+        if (pcm && !pcm[b]) return rfail(FQ3_EINVAL, "row " + std::to_string(b) + ": null clip");
+        if (n[b] <= pad || n[b] < c.hop || n[b] > (int64_t)1 << 26)
+            return rfail(FQ3_EINVAL, "row " + std::to_string(b) + ": clip too short (or too long) for the mel front end");
+        SpkRow& d = p.g.rows[b];
+        d.pcm = pcm ? pcm[b] : nullptr;
+        d.n = (int)n[b];
+        d.F = (int)((n[b] + 2 * pad - c.n_fft) / c.hop + 1);
+        d.frow = (int)p.sumF; d.prow = (int)p.M;
+        p.sumF += d.F; p.M += d.F + p.gap;
+        if (p.M > (int64_t)1 << 30) return rfail(FQ3_ETOOLONG, "row " + std::to_string(b) + ": the group has more frames than one call takes");
+    }
+    const size_t M = (size_t)p.M, Cb = c.enc_channels[0], Cm = c.enc_channels[c.n_enc - 1], Cs = Cb / c.res2net_scale;
+    p.floats = (size_t)p.sumF * c.mel_dim + M * std::max<size_t>(c.mel_dim, Cs) + 4 * M * Cb + 3 * M * Cm + M * c.attn_channels +
+               (size_t)rows * 16 * Cm + 64 * 16;
+    return FQ3_OK;
+}
+
+// first workgroups of a launch in which row b owns per(b) workgroups; returns the grid size
+template <typename F>
+unsigned spk_grid(SpkGroupArgs& g, F per) {
+    int64_t at = 0;
+    for (int b = 0; b <= kSpkGroupMax; ++b) {
+        g.wg0[b] = (int)at;
+        if (b < g.n_rows) at += per(g.rows[b]);
+    }
+    return (unsigned)at;
+}
+
+size_t mel_lds_bytes(const fq3_refenc_config& c) {
+    return ((size_t)(kMelTile - 1 + c.n_fft / c.hop) * (c.hop + kSpkLdPad) + (size_t)kMelTile * (c.n_bins_padded + kSpkLdPad)) * sizeof(float);
+}
+
+}  // namespace
+
+extern "C" int64_t fq3_refenc_speaker_group_workspace(const fq3_refenc* r, const int64_t* n, int rows) {
+    SpkPlan p;
+    const int e = spk_plan(r, nullptr, n, rows, p);
+    return e ? e : (int64_t)(p.floats * sizeof(float));
+}
+
+extern "C" int fq3_refenc_speaker_group(fq3_refenc* r, const float* const* pcm, const int64_t* n, int rows, float* embeds, void* stream) {
+    if (!r || !pcm || !n || !embeds) return rfail(FQ3_EINVAL, "null argument");
+    if (!r->spk_ready) return rfail(FQ3_ESTATE, "speaker-encoder weights not finalized");
+    SpkPlan p;
+    int err = spk_plan(r, pcm, n, rows, p);
+    if (err) return err;
+    const auto& c = r->cfg;
+    if (c.n_fft % 16 || c.hop % 16 || c.n_bins_padded % 16 || c.mel_dim % 16) return rfail(FQ3_EUNSUPPORTED, "speaker group: front-end sizes must be multiples of 16");
+    hipStream_t s = (hipStream_t)stream;
+    // every weight is looked up before the first launch: all or nothing
+    auto W = [&](const std::string& name) -> const float* { const float* q = nullptr; if (!err) err = need(r, name, 0, &q); return q; };
+    const std::string S = "speaker_encoder.";
+    const int nblk = c.n_enc - 2, scale = c.res2net_scale;
+    struct Blk { const float *t1w, *t1b, *t2w, *t2b, *s1w, *s1b, *s2w, *s2b; std::vector<const float*> rw, rb; };
+    std::vector<Blk> blk(nblk);
+    const float *w0 = W(S + "blocks.0.conv.weight"), *b0 = W(S + "blocks.0.conv.bias");
+    for (int b = 1; b <= nblk; ++b) {
+        const std::string Bk = S + "blocks." + std::to_string(b) + ".";
+        Blk& k = blk[b - 1];
+        k.t1w = W(Bk + "tdnn1.conv.weight"); k.t1b = W(Bk + "tdnn1.conv.bias"); k.t2w = W(Bk + "tdnn2.conv.weight"); k.t2b = W(Bk + "tdnn2.conv.bias");
+        k.s1w = W(Bk + "se_block.conv1.weight"); k.s1b = W(Bk + "se_block.conv1.bias"); k.s2w = W(Bk + "se_block.conv2.weight"); k.s2b = W(Bk + "se_block.conv2.bias");
+        for (int i = 1; i < scale; ++i) {
+            const std::string Rn = Bk + "res2net_block.blocks." + std::to_string(i - 1) + ".conv.";
+            k.rw.push_back(W(Rn + "weight")); k.rb.push_back(W(Rn + "bias"));
+        }
+    }
+    const float *mfw = W(S + "mfa.conv.weight"), *mfb = W(S + "mfa.conv.bias");
+    const float *awm = W(S + "asp.tdnn.conv.weight_ms"), *awh = W(S + "asp.tdnn.conv.weight_h"), *awb = W(S + "asp.tdnn.conv.bias");
+    const float *acw = W(S + "asp.conv.weight"), *acb = W(S + "asp.conv.bias"), *fcw = W(S + "fc.weight"), *fcb = W(S + "fc.bias");
+    if (err) return err;
+    const size_t lds = mel_lds_bytes(c);
+    if (!lds_limit_at_least<spk_logmel_group_kernel>(lds)) return rfail(FQ3_EUNSUPPORTED, "speaker group: the front end's tile does not fit this device's LDS");
+    if (!r->frag) return rfail(FQ3_ESTATE, "speaker-encoder weights not finalized");
+    if ((err = ws_reserve(r, p.floats, s))) return err;
+
+    const int M = (int)p.M, rowsN = rows, NB = c.n_bins_padded;
+    const int Cb = c.enc_channels[0], Cm = c.enc_channels[c.n_enc - 1], Cs = Cb / scale, Ac = c.attn_channels, Se = c.se_channels;
+    float* mel = take(r, (size_t)p.sumF * c.mel_dim); float* padbuf = take(r, (size_t)M * std::max(c.mel_dim, Cs));
+    float* X0 = take(r, (size_t)M * Cb); float* U = take(r, (size_t)M * Cb); float* R = take(r, (size_t)M * Cb); float* V = take(r, (size_t)M * Cb);
+    float* Cat = take(r, (size_t)M * Cm); float* Hm = take(r, (size_t)M * Cm); float* Lg = take(r, (size_t)M * Cm); float* A1 = take(r, (size_t)M * Ac);
+    float* vec = take(r, (size_t)rowsN * 16 * Cm);
+    if (!vec) return rfail(FQ3_ESTATE, "internal: workspace accounting");
+    float* mean = vec; float* gate1 = vec + (size_t)rowsN * Cm; float* gate = vec + (size_t)rowsN * 2 * Cm;
+    float* ms = vec + (size_t)rowsN * 3 * Cm;          // [rows][mean | std]
+    float* bias2 = vec + (size_t)rowsN * 5 * Cm;       // [rows][Ac]
+    float* pooled = vec + (size_t)rowsN * 6 * Cm;      // [rows][mean | std]
+    SpkGroupArgs& g = p.g;
+
+    // one TDNN layer over all rows: the clips' reflect-padded rows back to back, then the tap GEMM (1x1 layers read x itself)
+    auto tdnn = [&](const float* x, int ldx, const float* x2, int ldx2, int compact, int Cin, int k, int dil, const float* w, const float* bias, int Cout, float* y, int ldy) {
+        const float* A = x; int lda = ldx;
+        const int pad = (k - 1) * dil / 2;
+        if (k > 1 || x2 || compact) {
+            const unsigned grid = spk_grid(g, [&](const SpkRow& d) { return ((int64_t)(d.F + 2 * pad) * (Cin / 4) + 255) / 256; });
+            hipLaunchKernelGGL(spk_pad_group_kernel, dim3(grid), dim3(256), 0, s, g, x, ldx, x2, ldx2, compact, padbuf, Cin, pad);
+            A = padbuf; lda = Cin;
+        }
+        GemmArgs a = gemm(A, lda, M, M, Cin, w, Cout, bias, y, ldy);
+        a.n_taps = k; for (int i = 0; i < k; ++i) a.tap_off[i] = i * dil;
+        a.act = 4;
+        gemm_launch<float>(a, s);
+    };
+    auto stats = [&](const float* x, int ldx, const float* logits, int ldl, float* mu, float* sd, int ldo, int C, float eps) {
+        const int cblocks = (C + 63) / 64;
+        const unsigned grid = spk_grid(g, [&](const SpkRow&) { return (int64_t)cblocks; });
+        hipLaunchKernelGGL(spk_stats_group_kernel, dim3(grid), dim3(64 * kStatSlices), 0, s, g, x, ldx, logits, ldl, mu, sd, ldo, C, eps);
+    };
+    auto small = [&](const float* A, int K, const float* w, const float* bias, int N, float* y, int act) {      // the per-clip vectors: M = rows
+        GemmArgs a = gemm(A, K, rowsN, rowsN, K, w, N, bias, y, N); a.act = act; gemm_launch<float>(a, s);
+    };
+
+    // ---- log-mel of every clip: one launch ----
+    {
+        const unsigned grid = spk_grid(g, [&](const SpkRow& d) { return (int64_t)(d.F + kMelTile - 1) / kMelTile; });
+        hipLaunchKernelGGL(spk_logmel_group_kernel, dim3(grid), dim3(kMelWaves * 64), lds, s, g, (const float*)r->frag,
+                           (const float*)(r->frag + (size_t)2 * NB * c.n_fft), mel, c.n_fft, c.hop, NB, c.mel_dim);
+    }
+    // ---- ECAPA-TDNN over the gapped rows ----
+    tdnn(mel, c.mel_dim, nullptr, 0, 1, c.mel_dim, c.enc_kernel_sizes[0], c.enc_dilations[0], w0, b0, Cb, X0, Cb);
+    const float* xin = X0; int ldin = Cb;
+    for (int b = 1; b <= nblk; ++b) {
+        const Blk& k = blk[b - 1];
+        const int ks = c.enc_kernel_sizes[b], dil = c.enc_dilations[b];
+        tdnn(xin, ldin, nullptr, 0, 0, Cb, 1, 1, k.t1w, k.t1b, Cb, U, Cb);
+        hipLaunchKernelGGL(pad_rows_kernel, el((size_t)M * Cs), dim3(256), 0, s, (const float*)U, Cb, (const float*)nullptr, 0, R, Cb, M, Cs, 0, M, 0);
+        for (int i = 1; i < scale; ++i)
+            tdnn(U + i * Cs, Cb, i >= 2 ? R + (i - 1) * Cs : nullptr, Cb, 0, Cs, ks, dil, k.rw[i - 1], k.rb[i - 1], Cs, R + i * Cs, Cb);
+        tdnn(R, Cb, nullptr, 0, 0, Cb, 1, 1, k.t2w, k.t2b, Cb, V, Cb);
+        stats(V, Cb, nullptr, 0, mean, nullptr, Cb, Cb, 0.f);
+        small(mean, Cb, k.s1w, k.s1b, Se, gate1, 4);
+        small(gate1, Se, k.s2w, k.s2b, Cb, gate, 7);
+        float* dst = Cat + (size_t)(b - 1) * Cb;
+        const unsigned grid = spk_grid(g, [&](const SpkRow& d) { return ((int64_t)d.F * (Cb / 4) + 255) / 256; });
+        hipLaunchKernelGGL((spk_rowvec_group_kernel<0>), dim3(grid), dim3(256), 0, s, g, (const float*)V, Cb, (const float*)gate, Cb, xin, ldin, dst, Cm, Cb);
+        xin = dst; ldin = Cm;
+    }
+    tdnn(Cat, Cm, nullptr, 0, 0, Cm, 1, 1, mfw, mfb, Cm, Hm, Cm);
+    // ---- attentive statistics pooling: a clip's [mean | std] part of the attention input is a bias of its own rows ----
+    stats(Hm, Cm, nullptr, 0, ms, ms + Cm, 2 * Cm, Cm, 1e-12f);
+    small(ms, 2 * Cm, awm, awb, Ac, bias2, 0);
+    { GemmArgs a = gemm(Hm, Cm, M, M, Cm, awh, Ac, nullptr, A1, Ac); gemm_launch<float>(a, s); }
+    {
+        const unsigned grid = spk_grid(g, [&](const SpkRow& d) { return ((int64_t)d.F * (Ac / 4) + 255) / 256; });
+        hipLaunchKernelGGL((spk_rowvec_group_kernel<1>), dim3(grid), dim3(256), 0, s, g, (const float*)A1, Ac, (const float*)bias2, Ac, (const float*)nullptr, 0, A1, Ac, Ac);
+    }
+    { GemmArgs a = gemm(A1, Ac, M, M, Ac, acw, Cm, acb, Lg, Cm); gemm_launch<float>(a, s); }
+    stats(Hm, Cm, Lg, Cm, pooled, pooled + Cm, 2 * Cm, Cm, 1e-12f);
+    small(pooled, 2 * Cm, fcw, fcb, c.enc_dim, embeds, 0);
+    RHIP(hipGetLastError());
+    return FQ3_OK;
+}
+
+extern "C" int fq3_refenc_similarity(const float* a, const float* b, int rows, int dim, float* out, void* stream) {
+    if (!a || !b || !out) return rfail(FQ3_EINVAL, "null argument");
+    if (rows < 1 || dim < 1) return rfail(FQ3_EINVAL, "rows and dim must be positive");
+    hipLaunchKernelGGL(spk_cosine_kernel, dim3((rows + 3) / 4), dim3(256), 0, (hipStream_t)stream, a, b, out, rows, dim);
     RHIP(hipGetLastError());
     return FQ3_OK;
 }

@@ -188,11 +188,12 @@ __global__ void dft_mag_kernel(const float* __restrict__ spec, float* __restrict
 // mean[c] = sum w x, std[c] = sqrt(max(sum w (x - mean)^2, eps)); either output may be null.  The softmax subtracts the column's
 // maximum logit before expf (logits beyond +88 would overflow fp32 otherwise); the variance is the biased one, about the fp32 mean.
 constexpr int kStatSlices = 16;
-__global__ __launch_bounds__(64 * kStatSlices) void col_stats_kernel(const float* __restrict__ x, int ldx, const float* __restrict__ logits, int ldl,
-                                                        float* __restrict__ mean, float* __restrict__ stdv, int T, int C, float eps) {
+// (the body: channel block `cblk` of one clip; spk_stats_group_kernel runs it per (clip, channel block) on the clip's own rows)
+__device__ __forceinline__ void col_stats_body(const float* __restrict__ x, int ldx, const float* __restrict__ logits, int ldl,
+                                               float* __restrict__ mean, float* __restrict__ stdv, int T, int C, float eps, int cblk) {
     __shared__ float red[kStatSlices][64];
     const int cl = threadIdx.x & 63, part = threadIdx.x >> 6;
-    const int c = blockIdx.x * 64 + cl;
+    const int c = cblk * 64 + cl;
     const bool ok = c < C;
     const int cc = ok ? c : C - 1;
     auto reduce = [&](float v, bool is_max) {
@@ -228,6 +229,10 @@ __global__ __launch_bounds__(64 * kStatSlices) void col_stats_kernel(const float
     }
     const float var = reduce(s2, false);
     if (ok && part == 0) stdv[c] = sqrtf(fmaxf(var, eps));
+}
+__global__ __launch_bounds__(64 * kStatSlices) void col_stats_kernel(const float* __restrict__ x, int ldx, const float* __restrict__ logits, int ldl,
+                                                        float* __restrict__ mean, float* __restrict__ stdv, int T, int C, float eps) {
+    col_stats_body(x, ldx, logits, ldl, mean, stdv, T, C, eps, (int)blockIdx.x);
 }
 
 // squeeze-excitation output: y[t][c] = x[t][c] * gate[c] + res[t][c]

@@ -238,6 +238,22 @@ def cmd_detect(args):
     raise SystemExit(0 if all(s.present.any() for s in scans) else 1)
 
 
+def cmd_verify(args):
+    """``verify``: the cosine between the speaker embedding of every WAV file and that of ``--ref``, one per line.  No threshold is
+    applied (none is known: it depends on the checkpoint and has to be calibrated on real voices), so the exit status is always 0."""
+    from .audio_io import read_wav
+
+    def mono(path):
+        pcm, sr = read_wav(path)
+        pcm = np.asarray(pcm, dtype=np.float32)
+        return (pcm if pcm.ndim == 1 else pcm.reshape(len(pcm), -1)[:, 0]), sr
+    model = load_model(args)
+    clips = [mono(p) for p in args.files]
+    cos = model.speaker_similarity([c[0] for c in clips], [c[1] for c in clips], args.ref)
+    for path, v in zip(args.files, cos):
+        print(f"{path}: {v:.6f}")
+
+
 def _write_output(path, audio, sr, args):
     """float32 audio as 16-bit PCM (as ever); what the output stage encoded (int16, G.711 bytes, a FLAC stream) as it is."""
     import os
@@ -464,6 +480,11 @@ def build_parser():
                         "prints one line per window: file, start and end in seconds, z, offset, phase, present")
     d.add_argument("--hop", type=float, default=None, metavar="S", help="--window: seconds between window starts (default: 1)")
     d.set_defaults(func=cmd_detect)
+    v = sub.add_parser("verify", help="how close is the voice of WAV files to a reference?  prints one cosine per file (no threshold)")
+    v.add_argument("--model", default="Qwen/Qwen3-TTS-12Hz-0.6B-Base", help="local checkpoint directory (its speaker encoder is used)")
+    v.add_argument("--ref", required=True, metavar="REF.wav", help="the reference voice")
+    v.add_argument("files", nargs="+", metavar="WAV", help="WAV files (mono, or the first channel); any rate: resampled to 24 kHz on the device")
+    v.set_defaults(func=cmd_verify)
     return p
 
 

@@ -81,6 +81,29 @@ class _SideVocoder:
         # the utterances vocoded together in ONE launch; ``level`` then stops in front of the limiter and ``limit(key, row)`` is the
         # model's limiter step behind the mark (None outside ``limiter()``)
         self.marks, self.mark_rows, self.limit = None, None, None
+        # ``verify=`` of the batch entry points: {key: reference speaker embedding} and the model's ``score_rows(refs, rows)``, which
+        # scores the utterances vocoded together in ONE speaker-group call and one cosine launch; ``scores[key] = (pinned, index)``
+        self.verify, self.score_rows, self.scores = None, None, {}
+
+    VERIFY_MIN = 1024       # samples below which an utterance is not scored (the speaker encoder's front end needs one window)
+
+    def _scored(self, keys, pcms) -> None:
+        """the rows that have a reference embedding through ``score_rows`` (on the current stream); the cosines go to the host in ONE
+        pinned copy, complete when the group's event is"""
+        at = [j for j, k in enumerate(keys) if self.verify.get(k) is not None and pcms[j].numel() >= self.VERIFY_MIN]
+        if not at:
+            return
+        cos = self.score_rows([self.verify[keys[j]] for j in at], [pcms[j].reshape(-1) for j in at])
+        host = torch.empty(cos.shape, dtype=torch.float32, pin_memory=True) if cos.is_cuda else cos
+        if cos.is_cuda:
+            host.copy_(cos, non_blocking=True)
+        for i, j in enumerate(at):
+            self.scores[keys[j]] = (host, i)
+
+    def score(self, key) -> Optional[float]:
+        """after ``collect``: the cosine of utterance ``key``, or None when it was not scored"""
+        hit = self.scores.get(key)
+        return None if hit is None else float(hit[0][hit[1]])
 
     def _marked(self, keys, pcms) -> None:
         """the rows that have a mark through it, in place, then every row through ``limit``"""
@@ -124,6 +147,8 @@ class _SideVocoder:
                 x = torch.from_numpy(np.ascontiguousarray(_to_numpy(a), dtype=np.float32).reshape(-1)).to(self.dev)
                 self._marked([key], [x])
                 a = x.cpu().numpy()
+            if self.verify:
+                self._scored([key], [torch.from_numpy(np.ascontiguousarray(_to_numpy(a), dtype=np.float32).reshape(-1)).to(self.dev)])
             if self._spec(key) is not None:
                 # synchronous tokenizer: its audio is on the host; the utterance is uploaded for the stage
                 a = self._encode_group([key], [torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32)).to(self.dev)])[0]
@@ -140,6 +165,8 @@ class _SideVocoder:
             if self.marks:
                 pcm = pcm.float().contiguous()
                 self._marked([key], [pcm.reshape(-1)])
+            if self.verify:
+                self._scored([key], [pcm])
             host = None
             if self._spec(key) is not None:
                 host = self._encode_group([key], [pcm])[0]
@@ -200,6 +227,8 @@ class _SideVocoder:
                     if self.marks:
                         pcm = pcm.float().contiguous()
                         self._marked([key for key, _c, _r in part], [pcm[j].reshape(-1) for j in range(len(part))])
+                    if self.verify:
+                        self._scored([key for key, _c, _r in part], [pcm[j] for j in range(len(part))])
                     host = None
                     staged = [j for j, (key, _c, _r) in enumerate(part) if self._spec(key) is not None]
                     enc = dict(zip(staged, self._encode_group([part[j][0] for j in staged], [pcm[j] for j in staged]))) if staged else {}
@@ -1359,6 +1388,20 @@ class FasterQwen3TTS:
         from .watermark import scan
         return scan(audio, sr, key, window_s, hop_s, device=self.device)
 
+    def speaker_similarity(self, audio, sr, ref):
+        """Does ``audio`` sound like ``ref``?  The cosine between speaker embeddings (the ECAPA-TDNN x-vector the voice-clone prompt
+        is built from), computed on the device (``fq3hip/speaker_check.py``).  ``audio``: one mono waveform or a
+        list of them (device tensors or host arrays at ``sr`` Hz, one rate or one per clip; another rate than 24 kHz goes through
+        ``audio_out.resample_device``) -- every 32 clips are analysed in one group call.  ``ref``: a WAV path, ``(array, sr)``, a
+        ``voice_clone_prompt`` (its stored ``ref_spk_embedding`` is used, nothing is recomputed) or a raw embedding.  Returns a float
+        (a list of floats for a list); all of them reach the host behind one pinned copy.  NO threshold is chosen: what cosine
+        separates the same voice from another depends on the checkpoint and has to be calibrated on real voices."""
+        from .speaker_check import speaker_similarity
+        an = getattr(self.model, "ref_analyzer", None)
+        if an is None or not an.has_speaker:
+            raise NotImplementedError("this weight table has no speaker_encoder.* tensors: speaker embeddings cannot be computed here")
+        return speaker_similarity(an, audio, sr, ref, self.model._reference_wave)
+
     def _refuse_batch_watermark(self) -> None:
         if getattr(self, "_mark", None) is not None:
             raise ValueError("the batch entry points take their marks as watermark= (one MarkSpec, or one or None per text: the rows of "
@@ -1588,6 +1631,26 @@ class FasterQwen3TTS:
         """``output=`` and ``watermark=`` of a batch entry point, validated, as the keywords of ``_run_batch_*``"""
         outputs = self._batch_outputs(output, n)
         return dict(outputs=outputs, marks=self._batch_marks(watermark, n, outputs))
+
+    def _batch_verify(self, verify, n: int, embedding) -> dict:
+        """``verify=`` of the non-streaming batch entry points -> the ``verify`` keyword of ``_run_batch_full``, or nothing at all for
+        None (the call is then the one it was).  True: every utterance is scored against ``embedding()``, the speaker embedding its
+        request is prompted with (None: the request has none, its score is None).  Every argument error surfaces here."""
+        if verify is None:
+            return {}
+        if verify is not True:
+            raise ValueError("verify must be None or True")
+        an = getattr(self.model, "ref_analyzer", None)
+        if an is None or not an.has_speaker:
+            raise NotImplementedError("verify=True needs the speaker encoder: this weight table has no speaker_encoder.* tensors")
+        return dict(verify=[embedding() if embedding is not None else None] * n)
+
+    def _score_rows(self, refs, rows):
+        """The utterances of one vocoder group (float32 device vectors at 24 kHz) against their requests' embeddings: one
+        ``speaker_embeddings`` call and one ``similarity`` launch on the current stream -> the cosines, on the device."""
+        an = self.model.ref_analyzer
+        e = an.speaker_embeddings(rows)
+        return an.similarity(e, torch.stack([torch.as_tensor(r).detach().to(device=e.device, dtype=torch.float32).reshape(-1) for r in refs]))
 
     def _batch_marks(self, watermark, n: int, outputs=None) -> Optional[list]:
         """``watermark=`` of the batch entry points -> None, or one ``MarkSpec`` or None per text: each row is marked under its own
@@ -1948,7 +2011,7 @@ class FasterQwen3TTS:
         return head, pull
 
     def _run_batch_full(self, prepared, gen_kwargs, lanes: int, count: int, seeds=None, device_audio: bool = False,
-                        outputs=None, marks=None) -> List[Tuple[list, int]]:
+                        outputs=None, marks=None, verify=None) -> List[Tuple[list, int]]:
         """The lock-step decode of ``count`` prepared utterances (see :meth:`_batch_feed`) through ``lanes`` lanes, every finished
         utterance vocoded on the side stream (the reference's share of an ICL waveform is cut by not producing it,
         model.py:927-930).  One ``([waveform], sample_rate)`` per entry, in input order.  ``device_audio`` (internal, long form): the
@@ -1956,7 +2019,10 @@ class FasterQwen3TTS:
         runs the output chain itself.  ``outputs`` (:meth:`_batch_outputs`): utterance i with a spec comes back as
         ``([encoded array], output rate)`` -- the utterances vocoded together go through the output stage together, behind the levelling
         step (``_SideVocoder._encode_group``).  ``marks`` (:meth:`_batch_marks`): the utterances vocoded together that have a
-        ``MarkSpec`` are marked whole in ONE launch (``_mark_rows``), behind the gains and the leveller, in front of the limiter."""
+        ``MarkSpec`` are marked whole in ONE launch (``_mark_rows``), behind the gains and the leveller, in front of the limiter.
+        ``verify`` (:meth:`_batch_verify`): one reference speaker embedding or None per entry -- the utterances vocoded together are
+        scored on the device, as they leave for the host, in one speaker-group call (``_score_rows``), and every entry comes back as
+        ``([waveform], sample_rate, cosine or None)``."""
         if not device_audio:
             self._refuse_batch_audio_output()
             self._refuse_batch_watermark()
@@ -1994,13 +2060,15 @@ class FasterQwen3TTS:
                 # the limiter runs behind the mark: ``level`` stops in front of it and the rows are limited after the group call
                 voc.level = lambda key, wav: self._level(wav, key, voc.stream, inplace=True, limit=False)
                 voc.limit = lambda key, wav: wav.copy_(self._limited(wav, voc.stream))
+        if verify is not None:
+            voc.verify, voc.score_rows, voc.scores = dict(enumerate(verify)), self._score_rows, {}
         # batch_vocode_every (attribute; default 0 = vocode an utterance when it has ended; N > 0 = produce the waveform in slices every N
         # frames while the utterance still decodes -- exact, see _SideVocoder.inc_add -- so that what is left at the end is the last slice
         # only).  Measured on MI355X (profiles/r04_batch_e2e_vocode_every_*.txt): the slices contend with the latency-bound lock-step
         # frames for more than they save at the end -- 64 lanes x 128 utterances, 0.6B: 561x at 0, 537x at 64, 552x at 100; 1.7B: 458x vs
         # 443x -- so it is OFF by default; a server whose lanes finish at different times has nothing to gain from it either.
         inc = int(getattr(self, "batch_vocode_every", 0) or 0)
-        if inc > 0 and not device_audio and outputs is None and marks is None and not self._levelling() and voc.async_ok and hasattr(voc.tok, "decode_tensor_batch") and hasattr(voc.tok, "num_samples_total"):
+        if inc > 0 and not device_audio and outputs is None and marks is None and verify is None and not self._levelling() and voc.async_ok and hasattr(voc.tok, "decode_tensor_batch") and hasattr(voc.tok, "num_samples_total"):
             max_new = min(self._frame_limit(gen_kwargs), int(self.talker_graph.engine.max_frames))
             for rid, codes, info in dec.run(head, source=source, chunk_frames=inc):
                 more = int(getattr(dec, "more_in_poll", 0))
@@ -2027,6 +2095,9 @@ class FasterQwen3TTS:
             return out, voc
         for rid, a in voc.collect():
             out[rid] = ([a], voc.sample_rate if outputs is None else rate_of(rid))
+        if verify is not None:
+            out = [o + (voc.score(rid),) for rid, o in enumerate(out)]
+            voc.verify, voc.score_rows, voc.scores = None, None, {}
         return out
 
     def _run_batch_streaming(self, prepared, gen_kwargs, chunk_size: int, lanes: int, rounds=None, stamp=None, seeds=None,
@@ -2323,19 +2394,26 @@ class FasterQwen3TTS:
                                    non_streaming_mode: Optional[bool] = None, append_silence: bool = True,
                                    instruct: Optional[str] = None,
                                    voice_clone_prompt: Optional[Union[Dict[str, Any], List[Any]]] = None,
-                                   lanes: int = 8, watermark=None, seeds=None, output=None) -> List[Tuple[list, int]]:
+                                   lanes: int = 8, verify=None, watermark=None, seeds=None, output=None) -> List[Tuple[list, int]]:
         """Voice cloning of several texts with one voice: up to ``lanes`` (<= 128) utterances decode in lock-step over
         one pass of the weights per frame (``fq3_batch_*``), finished lanes are refilled from the queue.  Returns one
         ``([np.float32 waveform], sample_rate)`` per text, in input order; each utterance follows exactly the
         single-utterance semantics of :meth:`generate_voice_clone`, nucleus sampling (``top_p < 1``) included.  ``watermark`` (all
         batch entry points): a ``watermark.MarkSpec``, or a list with one or None per text -- each text's audio carries its own keyed
-        mark (``FasterQwen3TTS.watermark`` describes it), the texts vocoded together in one launch."""
+        mark (``FasterQwen3TTS.watermark`` describes it), the texts vocoded together in one launch.  ``verify`` (the three
+        non-streaming batch entry points): None, the default, changes nothing; True scores every utterance against the speaker
+        embedding its request is prompted with -- the utterances vocoded together in one speaker-group call on the device, while their
+        waveforms are still there -- and every result becomes ``([waveform], sample_rate, cosine)``.  The
+        cosine is None for a request without a speaker embedding (VoiceDesign; a CustomVoice speaker is a row of the codec
+        embedding, not the x-vector of a reference clip).  NO threshold is chosen: it depends on the checkpoint and real voices."""
         nsm = self._resolve_non_streaming_mode(non_streaming_mode, default=False)
         prepared = self._prepare_clone_batch(texts, language, ref_audio, ref_text, xvec_only, nsm, append_silence, instruct,
                                              voice_clone_prompt)
+        prompted = lambda: self._resolve_voice_clone_prompt(input_ids=[None], ref_audio=ref_audio, ref_text=ref_text, xvec_only=xvec_only,  # noqa: E731
+                                                            append_silence=append_silence, voice_clone_prompt=voice_clone_prompt)[0]["ref_spk_embedding"][0]
         return self._run_batch_full(prepared, self._gen_kwargs(max_new_tokens, min_new_tokens, temperature, top_k, top_p, do_sample,
                                                                repetition_penalty), lanes, len(texts), seeds=seeds,
-                                    **self._batch_stage_kw(output, watermark, len(texts)))
+                                    **self._batch_stage_kw(output, watermark, len(texts)), **self._batch_verify(verify, len(texts), prompted))
 
     @torch.inference_mode()
     def generate_voice_clone_batch_streaming(self, texts: List[str], language: Union[str, List[str]] = "English",
@@ -2378,7 +2456,8 @@ class FasterQwen3TTS:
                                     instruct: Optional[Union[str, List[Optional[str]]]] = None,
                                     non_streaming_mode: Optional[bool] = None, max_new_tokens: int = 2048, min_new_tokens: int = 2,
                                     temperature: float = 0.9, top_k: int = 50, top_p: float = 1.0, do_sample: bool = True,
-                                    repetition_penalty: float = 1.05, lanes: int = 16, watermark=None, seeds=None, output=None) -> List[Tuple[list, int]]:
+                                    repetition_penalty: float = 1.05, lanes: int = 16, verify=None, watermark=None, seeds=None,
+                                    output=None) -> List[Tuple[list, int]]:
         """CustomVoice for several texts (BASELINE configs[3]: many concurrent utterances of a CustomVoice model): every
         utterance is prepared exactly like :meth:`generate_custom_voice` (speaker-id prompt, model.py:1139-1326; ``speaker`` /
         ``language`` / ``instruct`` may be one value or one per text) and up to ``lanes`` of them decode in lock-step over one pass of
@@ -2386,7 +2465,7 @@ class FasterQwen3TTS:
         prepared = self._prepare_custom_batch(texts, speaker, language, instruct, non_streaming_mode)
         return self._run_batch_full(prepared, self._gen_kwargs(max_new_tokens, min_new_tokens, temperature, top_k, top_p, do_sample,
                                                                repetition_penalty), lanes, len(texts), seeds=seeds,
-                                    **self._batch_stage_kw(output, watermark, len(texts)))
+                                    **self._batch_stage_kw(output, watermark, len(texts)), **self._batch_verify(verify, len(texts), None))
 
     @torch.inference_mode()
     def generate_custom_voice_batch_streaming(self, texts: List[str], speaker: Union[str, List[str]],
@@ -2406,12 +2485,13 @@ class FasterQwen3TTS:
     def generate_voice_design_batch(self, texts: List[str], instruct: Union[str, List[str]], language: Union[str, List[str]] = "English",
                                     non_streaming_mode: Optional[bool] = None, max_new_tokens: int = 2048, min_new_tokens: int = 2,
                                     temperature: float = 0.9, top_k: int = 50, top_p: float = 1.0, do_sample: bool = True,
-                                    repetition_penalty: float = 1.05, lanes: int = 16, watermark=None, seeds=None, output=None) -> List[Tuple[list, int]]:
+                                    repetition_penalty: float = 1.05, lanes: int = 16, verify=None, watermark=None, seeds=None,
+                                    output=None) -> List[Tuple[list, int]]:
         """VoiceDesign for several texts in lock-step lanes; every utterance prepared like :meth:`generate_voice_design`."""
         return self._run_batch_full(self._prepare_design_batch(texts, instruct, language, non_streaming_mode),
                                     self._gen_kwargs(max_new_tokens, min_new_tokens, temperature, top_k, top_p, do_sample, repetition_penalty),
                                     lanes, len(texts), seeds=seeds,
-                                    **self._batch_stage_kw(output, watermark, len(texts)))
+                                    **self._batch_stage_kw(output, watermark, len(texts)), **self._batch_verify(verify, len(texts), None))
 
     def _prepare_design_batch(self, texts, instruct, language, non_streaming_mode):
         n = len(texts)

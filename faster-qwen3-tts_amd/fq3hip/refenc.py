@@ -129,6 +129,26 @@ def pack_ref_audio_weights(W: Weights, rc: RefAudioConfig) -> Weights:
     return out
 
 
+def ref_config_struct(rc: RefAudioConfig) -> "L.RefEncConfig":
+    """``RefAudioConfig`` -> the C ABI's ``fq3_refenc_config``."""
+    cc = L.RefEncConfig()
+    cc.num_filters, cc.n_ratios = rc.num_filters, len(rc.ratios)
+    for i, v in enumerate(rc.ratios):
+        cc.ratios[i] = v
+    cc.kernel_size, cc.last_kernel_size, cc.residual_kernel_size = rc.kernel_size, rc.last_kernel_size, rc.residual_kernel_size
+    cc.n_residual_layers, cc.dilation_growth_rate, cc.compress = rc.num_residual_layers, rc.dilation_growth_rate, rc.compress
+    cc.hidden, cc.n_layers, cc.n_heads, cc.head_dim = rc.hidden_size, rc.num_hidden_layers, rc.num_attention_heads, rc.head_dim
+    cc.inter, cc.sliding_window, cc.norm_eps = rc.intermediate_size, rc.sliding_window, rc.norm_eps
+    cc.num_quantizers, cc.num_semantic = rc.num_quantizers, rc.num_semantic_quantizers
+    cc.codebook_size, cc.codebook_dim, cc.max_positions = rc.codebook_size, rc.codebook_dim, rc.max_positions
+    cc.mel_dim, cc.n_fft, cc.hop, cc.n_bins_padded = rc.mel_dim, rc.n_fft, rc.hop_size, rc.n_bins_padded
+    cc.n_enc = len(rc.enc_channels)
+    for i in range(cc.n_enc):
+        cc.enc_channels[i], cc.enc_kernel_sizes[i], cc.enc_dilations[i] = rc.enc_channels[i], rc.enc_kernel_sizes[i], rc.enc_dilations[i]
+    cc.attn_channels, cc.res2net_scale, cc.se_channels, cc.enc_dim = rc.enc_attention_channels, rc.enc_res2net_scale, rc.enc_se_channels, rc.enc_dim
+    return cc
+
+
 class HipRefAudioAnalyzer:
     """24 kHz mono waveform -> reference codes / speaker embedding, on the HIP kernels."""
 
@@ -136,21 +156,7 @@ class HipRefAudioAnalyzer:
         self.lib = L.load()
         self.cfg, self.device = rc, torch.device(device)
         self.sample_rate = int(rc.sample_rate)
-        cc = L.RefEncConfig()
-        cc.num_filters, cc.n_ratios = rc.num_filters, len(rc.ratios)
-        for i, v in enumerate(rc.ratios):
-            cc.ratios[i] = v
-        cc.kernel_size, cc.last_kernel_size, cc.residual_kernel_size = rc.kernel_size, rc.last_kernel_size, rc.residual_kernel_size
-        cc.n_residual_layers, cc.dilation_growth_rate, cc.compress = rc.num_residual_layers, rc.dilation_growth_rate, rc.compress
-        cc.hidden, cc.n_layers, cc.n_heads, cc.head_dim = rc.hidden_size, rc.num_hidden_layers, rc.num_attention_heads, rc.head_dim
-        cc.inter, cc.sliding_window, cc.norm_eps = rc.intermediate_size, rc.sliding_window, rc.norm_eps
-        cc.num_quantizers, cc.num_semantic = rc.num_quantizers, rc.num_semantic_quantizers
-        cc.codebook_size, cc.codebook_dim, cc.max_positions = rc.codebook_size, rc.codebook_dim, rc.max_positions
-        cc.mel_dim, cc.n_fft, cc.hop, cc.n_bins_padded = rc.mel_dim, rc.n_fft, rc.hop_size, rc.n_bins_padded
-        cc.n_enc = len(rc.enc_channels)
-        for i in range(cc.n_enc):
-            cc.enc_channels[i], cc.enc_kernel_sizes[i], cc.enc_dilations[i] = rc.enc_channels[i], rc.enc_kernel_sizes[i], rc.enc_dilations[i]
-        cc.attn_channels, cc.res2net_scale, cc.se_channels, cc.enc_dim = rc.enc_attention_channels, rc.enc_res2net_scale, rc.enc_se_channels, rc.enc_dim
+        cc = ref_config_struct(rc)
         self.h = L.vp()
         with torch.cuda.device(self.device):
             L.check(self.lib.fq3_refenc_create(C.byref(cc), C.byref(self.h)))
@@ -198,3 +204,42 @@ class HipRefAudioAnalyzer:
             L.check(self.lib.fq3_refenc_speaker(self.h, x.data_ptr(), x.numel(), emb.data_ptr(), mel.data_ptr() if mel is not None else None,
                                                 torch.cuda.current_stream(self.device).cuda_stream))
         return (emb, mel) if return_mel else emb
+
+    GROUP_MAX = 32                                                         # rows of one fq3_refenc_speaker_group call
+
+    def speaker_embeddings(self, clips) -> torch.Tensor:
+        """The x-vectors of many 24 kHz clips of different lengths -> ``FloatTensor[len(clips), enc_dim]`` on the device.
+
+        One ``fq3_refenc_speaker_group`` call per slice of 32 clips: the number of launches does not depend on how many clips a
+        slice holds, and a clip's embedding does not depend on its neighbours or its place among them."""
+        xs = [self._wave(c) for c in clips]
+        out = torch.empty(len(xs), self.cfg.enc_dim, dtype=torch.float32, device=self.device)
+        for lo in range(0, len(xs), self.GROUP_MAX):
+            part = xs[lo: lo + self.GROUP_MAX]
+            ptrs = (L.vp * len(part))(*[x.data_ptr() for x in part])
+            lens = (C.c_int64 * len(part))(*[x.numel() for x in part])
+            self._group_call(ptrs, lens, len(part), out[lo:].data_ptr())
+        return out
+
+    def _group_call(self, ptrs, lens, rows: int, out_ptr: int) -> None:
+        with torch.cuda.device(self.device):
+            L.check(self.lib.fq3_refenc_speaker_group(self.h, ptrs, lens, rows, out_ptr, torch.cuda.current_stream(self.device).cuda_stream))
+
+    def similarity(self, a, b) -> torch.Tensor:
+        """Cosine of embedding pairs on the device: ``a`` and ``b`` are ``[rows, dim]`` (or one ``[dim]`` vector, which is
+        compared with every row of the other) -> ``FloatTensor[rows]``.  A zero vector gives 0.  No threshold is chosen here:
+        what cosine separates two voices depends on the checkpoint and has to be calibrated on real voices."""
+        a = torch.as_tensor(a).to(device=self.device, dtype=torch.float32)
+        b = torch.as_tensor(b).to(device=self.device, dtype=torch.float32)
+        a, b = a.reshape(-1, a.shape[-1]), b.reshape(-1, b.shape[-1])
+        if a.shape[-1] != b.shape[-1]:
+            raise ValueError(f"embedding sizes differ: {a.shape[-1]} vs {b.shape[-1]}")
+        rows = max(a.shape[0], b.shape[0])
+        if a.shape[0] not in (1, rows) or b.shape[0] not in (1, rows) or rows < 1:
+            raise ValueError(f"cannot pair {a.shape[0]} embeddings with {b.shape[0]}")
+        a, b = a.expand(rows, -1).contiguous(), b.expand(rows, -1).contiguous()
+        out = torch.empty(rows, dtype=torch.float32, device=self.device)
+        with torch.cuda.device(self.device):
+            L.check(self.lib.fq3_refenc_similarity(a.data_ptr(), b.data_ptr(), rows, a.shape[-1], out.data_ptr(),
+                                                   torch.cuda.current_stream(self.device).cuda_stream))
+        return out

@@ -522,6 +522,17 @@ int fq3_refenc_encode(fq3_refenc* r, const float* pcm, int64_t n, int64_t* codes
 /* pcm float32[n] (device, 24 kHz mono) -> embed float32[enc_dim] (device); mel (optional, may be null) receives the
  * log-mel frames float32[n / hop][mel_dim] the encoder consumed */
 int fq3_refenc_speaker(fq3_refenc* r, const float* pcm, int64_t n, float* embed, float* mel, void* stream);
+/* Group form: the x-vectors of `rows` clips of different lengths in a number of launches that does not depend on rows.
+ * rows in 1..32; pcm[i]: device float32[n[i]] at 24 kHz; embeds: device float32[rows][enc_dim].  All or nothing: every
+ * argument is validated on the host before the first launch (null pointers, rows out of range, a clip shorter than the
+ * single call accepts -> FQ3_EINVAL with the row named in fq3_last_error).  Workspace grows like fq3_refenc_speaker's;
+ * FQ3_ENOMEM leaves the object usable.  A clip's embedding does not depend on the other rows or on its place among them.
+ * fq3_refenc_speaker_group_workspace: host only, the bytes of device workspace such a call needs (negative: an FQ3_E* code). */
+int64_t fq3_refenc_speaker_group_workspace(const fq3_refenc* r, const int64_t* n, int rows);
+int fq3_refenc_speaker_group(fq3_refenc* r, const float* const* pcm, const int64_t* n, int rows, float* embeds, void* stream);
+/* out[i] = cosine of a[i][0..dim) and b[i][0..dim) for i < rows (device float32, fp32 sums in a fixed order); a zero vector on
+ * either side gives 0.  What cosine separates two voices depends on the checkpoint: this library chooses no threshold. */
+int fq3_refenc_similarity(const float* a, const float* b, int rows, int dim, float* out, void* stream);
 
 /* ---- audio output stage: resample and encode the vocoder's PCM before it leaves the device ----------------------------------
  * The vocoder writes float32 PCM at the model's rate (24 kHz).  This stage turns it, on the device and in ONE launch per chunk, into

@@ -26,6 +26,7 @@
 #include "../../include/fq3hip.h"
 #include "refenc_kernels.cuh"
 #include "spkgroup_kernels.cuh"
+#include "tokgroup_kernels.cuh"
 
 #include <algorithm>
 #include <cmath>
@@ -327,6 +328,247 @@ extern "C" int fq3_refenc_encode(fq3_refenc* r, const float* pcm, int64_t n, int
         case 1024: FQ3_RVQ(4, 1); break;
         case 2048: FQ3_RVQ(4, 2); break;
         default: FQ3_RVQ(4, 4); break;
+    }
+    RHIP(hipGetLastError());
+    return FQ3_OK;
+}
+
+// ---- speech-tokenizer encoder, group form ----------------------------------------------------------------------
+//   fq3_refenc_encode_group   the codes of 1..32 clips of different lengths, in a number of launches that does not depend on the
+//                             number of clips (tokgroup_kernels.cuh states the row space and the kernels)
+// The stack is fq3_refenc_encode's, layer for layer: every conv and linear runs once over all clips' packed rows through the same fp32
+// tap GEMM with the same operands in the same K order, the front conv, RoPE, attention, the replicate padding and the RVQ through group
+// kernels that share the single kernels' bodies or arithmetic.  Every clip's codes equal its single call's bit for bit.
+namespace {
+
+constexpr int64_t kTokGroupMaxSamples = 65535 * 64;            // packed 24 kHz rows of one call (gaps included): the fp32 GEMM walks them in
+                                                               // 64-row tiles on the y dimension of its grid, which ends at 65535
+
+struct TokPlan {
+    TokGroupArgs g{};
+    int rows = 0, g25 = 0, maxT25 = 0;
+    int64_t P = 1, M25 = 0, Q = 0, sumT5 = 0;                   // samples per 25 Hz row; packed 25 Hz rows; replicate-padded rows; frames
+    size_t per = 0, floats = 0;                                 // one of the four buffers; the workspace
+};
+
+// Validates everything the host can see and lays the slots out; launches nothing.  pcm / codes may be null (the workspace query).
+int tok_plan(const fq3_refenc* r, const float* const* pcm, const int64_t* n, int64_t* const* codes, int rows, TokPlan& p) {
+    if (!r || !n) return rfail(FQ3_EINVAL, "null argument");
+    if (rows < 1 || rows > kTokGroupMax) return rfail(FQ3_EINVAL, "rows must be in 1.." + std::to_string(kTokGroupMax) + " (got " + std::to_string(rows) + ")");
+    const auto& c = r->cfg;
+    // the gap in 25 Hz rows: the widest reach of any stage, in samples, rounded up to whole rows
+    int64_t reach = 0, R = 1;
+    int dmax = 1;
+    for (int j = 1; j < c.n_residual_layers; ++j) dmax *= c.dilation_growth_rate;
+    for (int i = 0; i < c.n_ratios; ++i) {
+        reach = std::max(reach, R * std::max<int64_t>((int64_t)(c.residual_kernel_size - 1) * dmax, c.ratios[i]));
+        R *= c.ratios[i];
+    }
+    p.P = R;
+    reach = std::max(reach, R * (c.last_kernel_size - 1));
+    p.g25 = (int)ceil_div(reach, R);
+    p.rows = p.g.n_rows = rows;
+    const int QD = c.n_heads * c.head_dim;
+    for (int b = 0; b < rows; ++b) {
+        if (pcm && !pcm[b]) return rfail(FQ3_EINVAL, "row " + std::to_string(b) + ": null clip");
+        if (codes && !codes[b]) return rfail(FQ3_EINVAL, "row " + std::to_string(b) + ": null codes");
+        if (n[b] < 1 || n[b] > (int64_t)1 << 26) return rfail(FQ3_EINVAL, "row " + std::to_string(b) + ": sample count");
+        int64_t t25 = n[b];
+        for (int i = 0; i < c.n_ratios; ++i) t25 = ceil_div(t25, c.ratios[i]);
+        if (t25 > c.max_positions) return rfail(FQ3_ETOOLONG, "row " + std::to_string(b) + ": reference clip longer than the encoder's position table");
+        TokRow& d = p.g.rows[b];
+        d.pcm = pcm ? pcm[b] : nullptr; d.codes = codes ? codes[b] : nullptr;
+        d.n = (int)n[b]; d.t25 = (int)t25; d.t5 = (int)ceil_div(t25, 2);
+        d.lo25 = (int)p.M25;
+        d.p25 = (int)((p.M25 + p.g25 + 1) & ~(int64_t)1);
+        d.q = (int)p.Q;
+        p.M25 = d.p25 + t25; p.Q += 2 + 2 * d.t5; p.sumT5 += d.t5;
+        p.maxT25 = std::max(p.maxT25, d.t25);
+        if (p.M25 * p.P > kTokGroupMaxSamples) return rfail(FQ3_ETOOLONG, "row " + std::to_string(b) + ": the group has more rows than one call takes");
+    }
+    size_t per = 0, ch = (size_t)c.num_filters;
+    R = 1;
+    for (int i = 0; i <= c.n_ratios; ++i) {                     // [rows][channels] of every stage of the conv stack
+        per = std::max(per, (size_t)(p.M25 * p.P / R) * ch);
+        if (i < c.n_ratios) { R *= c.ratios[i]; ch *= 2; }
+    }
+    per = std::max(per, (size_t)p.M25 * std::max(std::max(3 * QD, c.inter), 2 * c.hidden));
+    per = std::max(per, (size_t)p.Q * std::max(c.hidden, 2 * c.codebook_dim));
+    p.per = per + 256;
+    p.floats = 4 * p.per + 1024;
+    return FQ3_OK;
+}
+
+// first workgroups of a launch in which row b owns per(b) workgroups; returns the grid size
+template <typename F>
+unsigned tok_grid(TokGroupArgs& g, F per) {
+    int64_t at = 0;
+    for (int b = 0; b <= kTokGroupMax; ++b) {
+        g.wg0[b] = (int)at;
+        if (b < g.n_rows) at += per(g.rows[b]);
+    }
+    return (unsigned)at;
+}
+
+// zero the rows of buf [M25 P / R][C] that belong to no clip; t[b] = clip b's length at this stage
+void tok_clear(const TokPlan& p, const int64_t* t, int64_t R, float* buf, int C, hipStream_t s) {
+    TokSpans sp{};
+    int64_t at = 0, end = 0;
+    for (int j = 0; j <= kTokGroupMax; ++j) {
+        const int64_t lo = end, hi = j < p.rows ? p.g.rows[j].p25 * p.P / R : (j == p.rows ? p.M25 * p.P / R : end);
+        sp.lo[j] = (int)lo; sp.hi[j] = (int)hi; sp.wg0[j] = (int)at;
+        at += ((hi - lo) * (C / 4) + 255) / 256;
+        if (j < p.rows) end = hi + t[j];
+    }
+    sp.wg0[kTokGroupMax + 1] = (int)at;
+    if (at) hipLaunchKernelGGL(tok_clear_kernel, dim3((unsigned)at), dim3(256), 0, s, sp, buf, C);
+}
+
+}  // namespace
+
+extern "C" int64_t fq3_refenc_encode_group_workspace(const fq3_refenc* r, const int64_t* n, int rows) {
+    TokPlan p;
+    const int e = tok_plan(r, nullptr, n, nullptr, rows, p);
+    return e ? e : (int64_t)(p.floats * sizeof(float));
+}
+
+extern "C" int fq3_refenc_encode_group(fq3_refenc* r, const float* const* pcm, const int64_t* n, int rows, int64_t* const* codes, void* stream) {
+    if (!r || !pcm || !n || !codes) return rfail(FQ3_EINVAL, "null argument");
+    if (!r->tok_ready) return rfail(FQ3_ESTATE, "speech-tokenizer encoder weights not finalized");
+    TokPlan p;
+    int err = tok_plan(r, pcm, n, codes, rows, p);
+    if (err) return err;
+    const auto& c = r->cfg;
+    if (c.num_filters > 1024) return rfail(FQ3_EUNSUPPORTED, "encode group: num_filters above 1024");
+    hipStream_t s = (hipStream_t)stream;
+    // every weight is looked up before the first launch: all or nothing
+    auto W = [&](const std::string& name) -> const float* { const float* q = nullptr; if (!err) err = need(r, name, 0, &q); return q; };
+    const std::string E = "encoder.encoder.layers.";
+    struct Cv { const float *w, *b; };
+    auto conv = [&](const std::string& base) { return Cv{W(base + ".weight"), W(base + ".bias")}; };
+    std::vector<Cv> res1, res3, down;
+    const Cv cin = conv(E + "0.conv");
+    int li = 1;
+    for (int st = 0; st < c.n_ratios; ++st) {
+        for (int j = 0; j < c.n_residual_layers; ++j, ++li) {
+            res1.push_back(conv(E + std::to_string(li) + ".block.1.conv"));
+            res3.push_back(conv(E + std::to_string(li) + ".block.3.conv"));
+        }
+        ++li;
+        down.push_back(conv(E + std::to_string(li) + ".conv"));
+        ++li;
+    }
+    ++li;
+    const Cv last = conv(E + std::to_string(li) + ".conv");
+    struct Ly { const float *ln1w, *ln1b, *ln2w, *ln2b, *wqkv, *wo, *w1, *w2, *ls1, *ls2; };
+    std::vector<Ly> ly(c.n_layers);
+    for (int l = 0; l < c.n_layers; ++l) {
+        const std::string L = "encoder.encoder_transformer.layers." + std::to_string(l) + ".";
+        ly[l] = Ly{W(L + "input_layernorm.weight"), W(L + "input_layernorm.bias"), W(L + "post_attention_layernorm.weight"), W(L + "post_attention_layernorm.bias"),
+                   W(L + "self_attn.qkv.weight"), W(L + "self_attn.o_proj.weight"), W(L + "mlp.fc1.weight"), W(L + "mlp.fc2.weight"),
+                   W(L + "self_attn_layer_scale.scale"), W(L + "mlp_layer_scale.scale")};
+    }
+    const float *cosT = W("encoder.rope.cos"), *sinT = W("encoder.rope.sin");
+    const float *wds = W("encoder.downsample.conv.weight"), *wproj = W("encoder.quantizer.input_proj.weight");
+    if (err) return err;
+    if ((err = ws_reserve(r, p.floats, s))) return err;
+    float* A = take(r, p.per); float* B = take(r, p.per); float* Cb = take(r, p.per); float* Dd = take(r, p.per);
+    if (!Dd) return rfail(FQ3_ESTATE, "internal: workspace accounting");
+    TokGroupArgs& g = p.g;
+    int64_t t[kTokGroupMax] = {};                                // every clip's length at the current stage
+    for (int b = 0; b < rows; ++b) t[b] = g.rows[b].n;
+
+    // ---- conv_in over every slot: raw -> A, ELU -> B, zeros in the rows of no clip ----
+    int C = c.num_filters;
+    int64_t R = 1;                                              // samples per row of the current stage
+    {
+        const unsigned grid = tok_grid(g, [&](const TokRow& d) { return ceil_div((int64_t)(d.p25 + d.t25 - d.lo25) * p.P, kTokTile); });
+        hipLaunchKernelGGL(tok_conv_in_group_kernel, dim3(grid), dim3(256), 0, s, g, cin.w, cin.b, A, B, C, c.kernel_size, (int)p.P);
+    }
+    float *H = A, *Ecur = B, *Eother = Dd;
+    for (int st = 0, ri = 0; st < c.n_ratios; ++st) {
+        const int rr = c.ratios[st], Cm = C / c.compress, M = (int)(p.M25 * p.P / R);
+        for (int j = 0; j < c.n_residual_layers; ++j, ++ri) {
+            int dil = 1;
+            for (int q = 0; q < j; ++q) dil *= c.dilation_growth_rate;
+            const int k = c.residual_kernel_size;
+            GemmArgs a = gemm(Ecur, C, M, M, C, res1[ri].w, Cm, res1[ri].b, Cb, Cm);
+            a.n_taps = k; for (int i = 0; i < k; ++i) a.tap_off[i] = -(k - 1 - i) * dil;
+            a.act = 5;
+            gemm_launch<float>(a, s);
+            GemmArgs b = gemm(Cb, Cm, M, M, Cm, res3[ri].w, C, res3[ri].b, H, C);
+            b.res = H; b.ldr = C; b.Y2 = Ecur; b.act2 = 1;
+            gemm_launch<float>(b, s);
+            tok_clear(p, t, R, Ecur, C, s);                     // the 1x1 product wrote ELU(bias + skip) into the gap rows
+        }
+        // strided conv on the [M / r][r C] view: every clip starts on a view row, its tail rows are zero (tok_clear above / conv_in)
+        GemmArgs a = gemm(Ecur, rr * C, M / rr, M / rr, rr * C, down[st].w, 2 * C, down[st].b, H, 2 * C);
+        a.n_taps = 2; a.tap_off[0] = -1; a.tap_off[1] = 0;
+        a.Y2 = Eother; a.act2 = 1;
+        gemm_launch<float>(a, s);
+        std::swap(Ecur, Eother);
+        R *= rr; C *= 2;
+        for (int b = 0; b < rows; ++b) t[b] = ceil_div(t[b], rr);
+        tok_clear(p, t, R, Ecur, C, s);
+    }
+    const int M25 = (int)p.M25, Hd = c.hidden, QD = c.n_heads * c.head_dim;
+    {   // last conv -> X [M25][hidden] in Cb
+        const int k = c.last_kernel_size;
+        GemmArgs a = gemm(Ecur, C, M25, M25, C, last.w, Hd, last.b, Cb, Hd);
+        a.n_taps = k; for (int i = 0; i < k; ++i) a.tap_off[i] = -(k - 1 - i);
+        gemm_launch<float>(a, s);
+    }
+    // ---- transformer over the packed rows; LayerNorm and the products are row-local, RoPE and attention per clip ----
+    float* X = Cb; float* N1 = A; float* QKV = B; float* AT = Dd;
+    {   // attention writes the clips' rows of AT only: AT is zeroed once, so that the gap rows of X stay finite through the layers
+        TokSpans all{};
+        all.hi[0] = M25; all.wg0[0] = 0;
+        const int wgs = (int)ceil_div((int64_t)M25 * (QD / 4), 256);
+        for (int j = 1; j <= kTokGroupMax + 1; ++j) all.wg0[j] = wgs;
+        hipLaunchKernelGGL(tok_clear_kernel, dim3((unsigned)wgs), dim3(256), 0, s, all, AT, QD);
+    }
+    const int NP = (std::min(c.sliding_window, p.maxT25) + 63) / 64;
+    const float sc = 1.0f / sqrtf((float)c.head_dim);
+    for (int l = 0; l < c.n_layers; ++l) {
+        const Ly& w = ly[l];
+        hipLaunchKernelGGL((layernorm_rows_kernel<float>), dim3((M25 + 3) / 4), dim3(256), 0, s, (const float*)X, w.ln1w, w.ln1b, N1, 0, M25, Hd, c.norm_eps);
+        gemm_launch<float>(gemm(N1, Hd, M25, M25, Hd, w.wqkv, 3 * QD, nullptr, QKV, 3 * QD), s);
+        {
+            const int per_row = 2 * c.n_heads * (c.head_dim / 2);
+            const unsigned grid = tok_grid(g, [&](const TokRow& d) { return ceil_div((int64_t)d.t25 * per_row, 256); });
+            hipLaunchKernelGGL(tok_rope_group_kernel, dim3(grid), dim3(256), 0, s, g, QKV, cosT, sinT, QD, c.head_dim);
+        }
+        const dim3 ag(tok_grid(g, [&](const TokRow& d) { return (int64_t)(d.t25 + 3) / 4; }), c.n_heads);
+#define FQ3_TOK_ATTN(HD, NPV) hipLaunchKernelGGL((tok_attn_group_kernel<HD, NPV>), ag, dim3(256), 0, s, g, (const float*)QKV, AT, c.n_heads, c.sliding_window, sc)
+#define FQ3_TOK_ATTN_HD(HD) do { if (NP <= 1) FQ3_TOK_ATTN(HD, 1); else if (NP == 2) FQ3_TOK_ATTN(HD, 2); else if (NP == 3) FQ3_TOK_ATTN(HD, 3); else FQ3_TOK_ATTN(HD, 4); } while (0)
+        if (c.head_dim == 32) FQ3_TOK_ATTN_HD(32); else if (c.head_dim == 64) FQ3_TOK_ATTN_HD(64); else FQ3_TOK_ATTN_HD(128);
+        { GemmArgs a = gemm(AT, QD, M25, M25, QD, w.wo, Hd, nullptr, X, Hd); a.scale = w.ls1; a.res = X; a.ldr = Hd; gemm_launch<float>(a, s); }
+        hipLaunchKernelGGL((layernorm_rows_kernel<float>), dim3((M25 + 3) / 4), dim3(256), 0, s, (const float*)X, w.ln2w, w.ln2b, N1, 0, M25, Hd, c.norm_eps);
+        { GemmArgs a = gemm(N1, Hd, M25, M25, Hd, w.w1, c.inter, nullptr, QKV, c.inter); a.act = 1; gemm_launch<float>(a, s); }
+        { GemmArgs a = gemm(QKV, c.inter, M25, M25, c.inter, w.w2, Hd, nullptr, X, Hd); a.scale = w.ls2; a.res = X; a.ldr = Hd; gemm_launch<float>(a, s); }
+    }
+    // ---- stride-2 conv over every clip's replicate-padded rows: clip b's frame f is view row q_b / 2 + f ----
+    const int V = (int)(p.Q / 2);
+    {
+        const unsigned grid = tok_grid(g, [&](const TokRow& d) { return ceil_div((int64_t)(2 + 2 * d.t5) * (Hd / 4), 256); });
+        hipLaunchKernelGGL(tok_pad_group_kernel, dim3(grid), dim3(256), 0, s, g, (const float*)X, A, Hd);
+        GemmArgs a = gemm(A, 2 * Hd, V, V, 2 * Hd, wds, Hd, nullptr, B, Hd);
+        a.n_taps = 2; a.tap_off[0] = 0; a.tap_off[1] = 1;
+        gemm_launch<float>(a, s);
+    }
+    // ---- split residual VQ: both input projections as one GEMM, then one workgroup per (clip, frame, quantizer group) ----
+    const int D = c.codebook_dim, K = c.codebook_size;
+    gemm_launch<float>(gemm(B, Hd, V, V, Hd, wproj, 2 * D, nullptr, Dd, 2 * D), s);
+    RvqEncArgs ra{}; ra.nq = c.num_quantizers; ra.n_sem = c.num_semantic; ra.K = K; ra.D = D;
+    for (int lv = 0; lv < c.num_quantizers; ++lv) { ra.emb[lv] = r->books + (size_t)lv * 2 * K * D; ra.embT[lv] = ra.emb[lv] + (size_t)K * D; }
+    const dim3 rg(tok_grid(g, [&](const TokRow& d) { return (int64_t)d.t5; }), 2);
+#define FQ3_TOK_RVQ(V_, P_) hipLaunchKernelGGL((tok_rvq_group_kernel<V_, P_>), rg, dim3(256), D * sizeof(float), s, g, ra, (const float*)Dd)
+    switch (K) {
+        case 256: FQ3_TOK_RVQ(1, 1); break;
+        case 512: FQ3_TOK_RVQ(1, 2); break;
+        case 1024: FQ3_TOK_RVQ(4, 1); break;
+        case 2048: FQ3_TOK_RVQ(4, 2); break;
+        default: FQ3_TOK_RVQ(4, 4); break;
     }
     RHIP(hipGetLastError());
     return FQ3_OK;

@@ -46,11 +46,13 @@ __global__ void pad_rows_kernel(const float* __restrict__ src1, int ld1, const f
 
 // Causal sliding-window attention over qkv [T][3*QD] with up to NP * 64 keys per query (Mimi: window 250, head_dim 64).
 // Same shape as swa_attn_kernel (one wave per (query, head), one key per lane and pass), generalised to NP passes.
+// (the body: queries 4 * qblk .. of head h of ONE clip whose rows start at qkv / out; tok_attn_group_kernel runs it per clip)
 template <int HD, int NP>
-__global__ __launch_bounds__(256) void win_attn_kernel(const float* __restrict__ qkv, float* __restrict__ out, int Tn, int NH, int window, float scale) {
+__device__ __forceinline__ void win_attn_body(const float* __restrict__ qkv, float* __restrict__ out, int Tn, int NH, int window, float scale,
+                                              int qblk, int h) {
     __shared__ float qs[4][HD];
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    const int q = blockIdx.x * 4 + wave, h = blockIdx.y;
+    const int q = qblk * 4 + wave;
     const int QD = NH * HD;
     const bool live = q < Tn;
     const int qq = live ? q : Tn - 1;
@@ -97,6 +99,10 @@ __global__ __launch_bounds__(256) void win_attn_kernel(const float* __restrict__
     if (lane < HD) op[lane] = o0 / l;
     if (HD > 64) op[lane + 64] = o1 / l;
 }
+template <int HD, int NP>
+__global__ __launch_bounds__(256) void win_attn_kernel(const float* __restrict__ qkv, float* __restrict__ out, int Tn, int NH, int window, float scale) {
+    win_attn_body<HD, NP>(qkv, out, Tn, NH, window, scale, (int)blockIdx.x, (int)blockIdx.y);
+}
 
 // codebook = embed_sum / clamp(cluster_usage, eps) (modeling_mimi.py:980-983), stored both ways: emb [K][D] and embT [D][K]
 __global__ void codebook_prepare_kernel(const float* __restrict__ embed_sum, const float* __restrict__ usage,
@@ -117,15 +123,16 @@ __global__ void codebook_prepare_kernel(const float* __restrict__ embed_sum, con
 // them in flight), and the d loop is unrolled so that 4 * PER loads per thread overlap -- the scan is bound by the
 // codebook bytes a CU can pull from L2 (2 MB per level at K = 2048, D = 256).
 struct RvqEncArgs { const float* emb[32]; const float* embT[32]; int nq; int n_sem; int K; int D; };
+// (the body: one frame, prow = its [2D] projection row, crow = its [nq] codes; tok_rvq_group_kernel runs it per (clip, frame))
 template <int VEC, int PER>
-__global__ __launch_bounds__(256) void rvq_encode_kernel(RvqEncArgs a, const float* __restrict__ proj /*[T][2D]*/, int64_t* __restrict__ codes /*[T][nq]*/) {
+__device__ __forceinline__ void rvq_encode_body(const RvqEncArgs& a, const float* __restrict__ prow, int64_t* __restrict__ crow, int part) {
     extern __shared__ float rsm[];
     float* res = rsm;                       // [D]
     __shared__ float best_d[4]; __shared__ int best_i[4]; __shared__ int winner;
-    const int t = blockIdx.x, part = blockIdx.y, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int lvl0 = part == 0 ? 0 : a.n_sem, lvl1 = part == 0 ? a.n_sem : a.nq;
     const int D = a.D, K = a.K;
-    for (int d = tid; d < D; d += 256) res[d] = proj[(size_t)t * 2 * D + (size_t)part * D + d];
+    for (int d = tid; d < D; d += 256) res[d] = prow[(size_t)part * D + d];
     __syncthreads();
     for (int lv = lvl0; lv < lvl1; ++lv) {
         const float* eT = a.embT[lv] + tid * VEC;
@@ -164,13 +171,17 @@ __global__ __launch_bounds__(256) void rvq_encode_kernel(RvqEncArgs a, const flo
             float d0 = best_d[0]; int i0 = best_i[0];
             for (int w = 1; w < 4; ++w) if (best_d[w] < d0 || (best_d[w] == d0 && best_i[w] < i0)) { d0 = best_d[w]; i0 = best_i[w]; }
             winner = i0;
-            codes[(size_t)t * a.nq + lv] = i0;
+            crow[lv] = i0;
         }
         __syncthreads();
         const float* e = a.emb[lv] + (size_t)winner * D;
         for (int d = tid; d < D; d += 256) res[d] -= e[d];
         __syncthreads();
     }
+}
+template <int VEC, int PER>
+__global__ __launch_bounds__(256) void rvq_encode_kernel(RvqEncArgs a, const float* __restrict__ proj /*[T][2D]*/, int64_t* __restrict__ codes /*[T][nq]*/) {
+    rvq_encode_body<VEC, PER>(a, proj + (size_t)blockIdx.x * 2 * a.D, codes + (size_t)blockIdx.x * a.nq, (int)blockIdx.y);
 }
 
 // |X|: spec [F][2*NB] = (re | im) of the windowed DFT -> mag [F][NB] = sqrt(re^2 + im^2 + 1e-9) (BigVGAN-style mel front end)

@@ -224,6 +224,8 @@ SIGNATURES = {
     "fq3_refenc_finalize": (C.c_int, [vp, vp]),
     "fq3_refenc_num_frames": (C.c_int64, [vp, C.c_int64]),
     "fq3_refenc_encode": (C.c_int, [vp, vp, C.c_int64, vp, vp]),
+    "fq3_refenc_encode_group_workspace": (C.c_int64, [vp, C.POINTER(C.c_int64), C.c_int]),
+    "fq3_refenc_encode_group": (C.c_int, [vp, C.POINTER(vp), C.POINTER(C.c_int64), C.c_int, C.POINTER(vp), vp]),
     "fq3_refenc_speaker": (C.c_int, [vp, vp, C.c_int64, vp, vp, vp]),
     "fq3_refenc_speaker_group_workspace": (C.c_int64, [vp, C.POINTER(C.c_int64), C.c_int]),
     "fq3_refenc_speaker_group": (C.c_int, [vp, C.POINTER(vp), C.POINTER(C.c_int64), C.c_int, vp, vp]),

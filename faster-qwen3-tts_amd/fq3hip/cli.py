@@ -254,6 +254,26 @@ def cmd_verify(args):
         print(f"{path}: {v:.6f}")
 
 
+def cmd_enroll(args):
+    """``enroll``: the voice-clone prompts of many reference clips through ``create_voice_clone_prompts`` (two group calls for all of
+    them), written into ``--out`` under the keys a later ``--voice-cache DIR --ref-audio A.wav`` looks up: one entry per clip."""
+    from .voice_cache import VoiceRefCache, export_voice_clone_prompt
+    texts = None
+    if args.ref_text_file:
+        with open(args.ref_text_file, encoding="utf-8") as f:
+            texts = [line.strip() for line in f.read().splitlines()]
+        if len(texts) != len(args.files) or not all(texts):
+            raise SystemExit(f"ERROR: --ref-text-file needs one non-empty line per clip ({len(args.files)} clips, {len(texts)} lines)")
+    model = load_model(args)
+    xvec = texts is None
+    entries = [model._voice_cache_entry(p, xvec, True) for p in args.files]       # (audio at 24 kHz, key, metadata, silence, identity)
+    items = model.create_voice_clone_prompts([en[0] for en in entries], texts, x_vector_only_mode=xvec)
+    cache = VoiceRefCache(args.out)
+    for path, en, item in zip(args.files, entries, items):
+        key = export_voice_clone_prompt(cache, en[0], item, append_silence=en[3], model_identity=en[4], ref_text=item.ref_text or "")
+        print(f"{path}: {key}")
+
+
 def _write_output(path, audio, sr, args):
     """float32 audio as 16-bit PCM (as ever); what the output stage encoded (int16, G.711 bytes, a FLAC stream) as it is."""
     import os
@@ -485,6 +505,13 @@ def build_parser():
     v.add_argument("--ref", required=True, metavar="REF.wav", help="the reference voice")
     v.add_argument("files", nargs="+", metavar="WAV", help="WAV files (mono, or the first channel); any rate: resampled to 24 kHz on the device")
     v.set_defaults(func=cmd_verify)
+    e = sub.add_parser("enroll", help="analyse many reference voices in one pass and write their prompts into a voice cache directory")
+    e.add_argument("--model", default="Qwen/Qwen3-TTS-12Hz-0.6B-Base", help="local checkpoint directory")
+    e.add_argument("--out", required=True, metavar="DIR", help="the voice cache directory (what --voice-cache reads)")
+    e.add_argument("--ref-text-file", metavar="FILE", help="one transcript line per WAV file: ICL prompts (embedding and reference "
+                   "codes); without it the prompts are x-vector only")
+    e.add_argument("files", nargs="+", metavar="WAV", help="reference clips")
+    e.set_defaults(func=cmd_enroll)
     return p
 
 

@@ -170,7 +170,8 @@ class HipSpeechTokenizer:
 
     def encode(self, audio, sr: int = None):
         """Upstream ``speech_tokenizer.encode(audio, sr)`` [recalled]: -> object with ``audio_codes`` = list of
-        ``LongTensor[T, 16]``.  ``audio`` is one waveform (or a list of them) at ``sr`` Hz."""
+        ``LongTensor[T, 16]``.  ``audio`` is one waveform (or a list of them) at ``sr`` Hz.  Two or more waveforms go through the
+        encoder's group call (``HipRefAudioAnalyzer.encode_many``): the same codes bit for bit, in one pass."""
         from types import SimpleNamespace
         an = getattr(self, "_analyzer", None)
         if an is None:
@@ -178,11 +179,11 @@ class HipSpeechTokenizer:
         from .audio_io import resample
         import numpy as np
         items = audio if isinstance(audio, (list, tuple)) else [audio]
-        out = []
+        waves = []
         for a in items:
             a = np.asarray(a.detach().cpu().numpy() if hasattr(a, "detach") else a, dtype=np.float32).reshape(-1)
-            out.append(an.encode(resample(a, int(sr or self.sample_rate), self.sample_rate)))
-        return SimpleNamespace(audio_codes=out)
+            waves.append(resample(a, int(sr or self.sample_rate), self.sample_rate))
+        return SimpleNamespace(audio_codes=an.encode_many(waves) if len(waves) >= 2 else [an.encode(w) for w in waves])
 
     def set_option(self, key: str, value: int):
         """``fq3_codec_set_option``: "fuse_units" 0|1|2 (two GEMMs per residual unit | the 96-channel block's units fused into one launch

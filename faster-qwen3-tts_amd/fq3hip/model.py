@@ -1402,6 +1402,15 @@ class FasterQwen3TTS:
             raise NotImplementedError("this weight table has no speaker_encoder.* tensors: speaker embeddings cannot be computed here")
         return speaker_similarity(an, audio, sr, ref, self.model._reference_wave)
 
+    def create_voice_clone_prompts(self, ref_audios, ref_texts=None, x_vector_only_mode=False):
+        """Enrol many voices at once: one ``VoiceClonePromptItem`` per reference clip (a WAV path, ``(array, sr)`` or a 24 kHz
+        waveform each), both halves of every prompt from two group calls whose launch counts do not depend on the number of clips
+        (DESIGN.md sections 4.25 and 4.26).  ``ref_texts`` and ``x_vector_only_mode``: one value for all clips or one per clip;
+        x-vector-only clips are left out of the encoder's group.  The reference codes equal the single method's
+        (``model.create_voice_clone_prompt``) bit for bit.  The x-vectors are the speaker group's: they agree with the single call's
+        within the bound section 4.25 states and are not bit-identical to them."""
+        return self.model.create_voice_clone_prompts(ref_audios, ref_texts, x_vector_only_mode)
+
     def _refuse_batch_watermark(self) -> None:
         if getattr(self, "_mark", None) is not None:
             raise ValueError("the batch entry points take their marks as watermark= (one MarkSpec, or one or None per text: the rows of "

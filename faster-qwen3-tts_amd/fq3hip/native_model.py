@@ -281,6 +281,38 @@ class NativeQwen3TTS:
         return [VoiceClonePromptItem(ref_code=codes, ref_spk_embedding=spk, x_vector_only_mode=bool(x_vector_only_mode),
                                      icl_mode=icl, ref_text=ref_text if icl else None)]
 
+    def create_voice_clone_prompts(self, ref_audios, ref_texts=None, x_vector_only_mode=False) -> List[VoiceClonePromptItem]:
+        """``create_voice_clone_prompt`` for many reference clips: one ``VoiceClonePromptItem`` per clip, both halves from group calls.
+        ``ref_texts`` and ``x_vector_only_mode`` are one value for all clips or one per clip; the rules per clip are the single
+        method's.  The reference codes come from ``encode_many`` over the ICL clips (x-vector-only clips are left out of that group)
+        and equal the single method's bit for bit.  The x-vectors are the speaker group's (``speaker_embeddings``): they agree with
+        the single call's within the bound DESIGN.md section 4.25 states and are NOT bit-identical to them."""
+        an = self.ref_analyzer
+        if an is None or not an.has_speaker:
+            raise NotImplementedError(
+                "This weight table has no speaker_encoder.* / encoder.* tensors, so reference audio cannot be analysed here. "
+                "Pass voice_clone_prompt=dict(ref_spk_embedding=[...], ref_code=[...], x_vector_only_mode=[...], icl_mode=[...]) "
+                "or serve ref_audio from a voice-reference cache (FasterQwen3TTS.set_voice_ref_cache).")
+        ref_audios = list(ref_audios)
+        n = len(ref_audios)
+        per_clip = lambda v: list(v) if isinstance(v, (list, tuple)) else [v] * n
+        texts, xvec = per_clip(ref_texts if ref_texts is not None else ""), [bool(v) for v in per_clip(x_vector_only_mode)]
+        if len(texts) != n or len(xvec) != n:
+            raise ValueError(f"{n} reference clips, {len(texts)} ref_texts, {len(xvec)} x_vector_only_mode values")
+        for a, t, x in zip(ref_audios, texts, xvec):
+            if a is None:
+                raise ValueError("ref_audio is required")
+            if not x and not t:
+                raise ValueError("ref_text is required when x_vector_only_mode=False (ICL mode).")
+        if not all(xvec) and not an.has_encoder:
+            raise NotImplementedError("ICL mode needs the speech tokenizer's encoder.* tensors; use x_vector_only_mode=True")
+        waves = [self._reference_wave(a) for a in ref_audios]
+        spk = an.speaker_embeddings(waves).to(self.dtype) if n else []
+        icl = [i for i in range(n) if not xvec[i]]
+        codes = dict(zip(icl, an.encode_many([waves[i] for i in icl]))) if icl else {}
+        return [VoiceClonePromptItem(ref_code=codes.get(i), ref_spk_embedding=spk[i], x_vector_only_mode=xvec[i], icl_mode=not xvec[i],
+                                     ref_text=None if xvec[i] else texts[i]) for i in range(n)]
+
     @staticmethod
     def _prompt_items_to_voice_clone_prompt(items: List[Any]) -> Dict[str, Any]:
         return dict(ref_code=[it.ref_code for it in items], ref_spk_embedding=[it.ref_spk_embedding for it in items],

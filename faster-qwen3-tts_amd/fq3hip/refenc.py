@@ -225,6 +225,37 @@ class HipRefAudioAnalyzer:
         with torch.cuda.device(self.device):
             L.check(self.lib.fq3_refenc_speaker_group(self.h, ptrs, lens, rows, out_ptr, torch.cuda.current_stream(self.device).cuda_stream))
 
+    def encode_many(self, clips) -> list:
+        """``speech_tokenizer.encode`` of many 24 kHz clips of different lengths -> one ``LongTensor[T_b, num_quantizers]`` per clip.
+
+        One ``fq3_refenc_encode_group`` call per slice of clips: a slice ends after 32 clips or where one more clip would pass the
+        call's cap on packed rows, whichever comes first.  The number of launches of a call does not depend on how many clips it
+        holds, nothing is synchronised between slices, and every clip's codes equal ``encode(clip)`` bit for bit."""
+        xs = [self._wave(c) for c in clips]
+        if any(x.numel() < 1 for x in xs):
+            raise ValueError("an empty clip cannot be encoded")
+        out = [torch.empty(self.num_frames(x.numel()), self.cfg.num_quantizers, dtype=torch.long, device=self.device) for x in xs]
+        lo = 0
+        while lo < len(xs):
+            hi = min(lo + self.GROUP_MAX, len(xs))
+            while hi - lo > 1 and not self._encode_group_fits([x.numel() for x in xs[lo:hi]]):
+                hi -= 1
+            rows = hi - lo
+            ptrs = (L.vp * rows)(*[x.data_ptr() for x in xs[lo:hi]])
+            lens = (C.c_int64 * rows)(*[x.numel() for x in xs[lo:hi]])
+            dst = (L.vp * rows)(*[o.data_ptr() for o in out[lo:hi]])
+            self._encode_group_call(ptrs, lens, rows, dst)
+            lo = hi
+        return out
+
+    def _encode_group_fits(self, lens) -> bool:
+        """Host only: do clips of these lengths stay under the group call's cap on packed rows?  (Any other refusal is left to the call.)"""
+        return int(self.lib.fq3_refenc_encode_group_workspace(self.h, (C.c_int64 * len(lens))(*lens), len(lens))) != L.FQ3_ETOOLONG
+
+    def _encode_group_call(self, ptrs, lens, rows: int, dst) -> None:
+        with torch.cuda.device(self.device):
+            L.check(self.lib.fq3_refenc_encode_group(self.h, ptrs, lens, rows, dst, torch.cuda.current_stream(self.device).cuda_stream))
+
     def similarity(self, a, b) -> torch.Tensor:
         """Cosine of embedding pairs on the device: ``a`` and ``b`` are ``[rows, dim]`` (or one ``[dim]`` vector, which is
         compared with every row of the other) -> ``FloatTensor[rows]``.  A zero vector gives 0.  No threshold is chosen here:

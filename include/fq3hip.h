@@ -519,6 +519,16 @@ int fq3_refenc_finalize(fq3_refenc* r, void* stream);
 int64_t fq3_refenc_num_frames(const fq3_refenc* r, int64_t n_samples);
 /* pcm float32[n] (device, 24 kHz mono) -> codes int64[num_frames][num_quantizers] (device) */
 int fq3_refenc_encode(fq3_refenc* r, const float* pcm, int64_t n, int64_t* codes, void* stream);
+/* Group form: the codes of `rows` clips of different lengths in a number of launches that does not depend on rows.
+ * rows in 1..32; pcm[i]: device float32[n[i]] at 24 kHz; codes[i]: device int64[fq3_refenc_num_frames(n[i])][num_quantizers].
+ * Every clip's codes equal those of its own fq3_refenc_encode call bit for bit, whatever the other rows are and wherever it
+ * sits among them.  All or nothing: every argument is validated on the host before the first launch (null pointers, rows out
+ * of range, a sample count the single call refuses -> FQ3_EINVAL; a clip longer than the position table, or a group whose
+ * packed rows pass 65535 * 64 samples, gaps included -> FQ3_ETOOLONG; the row is named in fq3_last_error).  Workspace grows like
+ * fq3_refenc_encode's; FQ3_ENOMEM leaves the object usable.
+ * fq3_refenc_encode_group_workspace: host only, the bytes of device workspace such a call needs (negative: an FQ3_E* code). */
+int64_t fq3_refenc_encode_group_workspace(const fq3_refenc* r, const int64_t* n, int rows);
+int fq3_refenc_encode_group(fq3_refenc* r, const float* const* pcm, const int64_t* n, int rows, int64_t* const* codes, void* stream);
 /* pcm float32[n] (device, 24 kHz mono) -> embed float32[enc_dim] (device); mel (optional, may be null) receives the
  * log-mel frames float32[n / hop][mel_dim] the encoder consumed */
 int fq3_refenc_speaker(fq3_refenc* r, const float* pcm, int64_t n, float* embed, float* mel, void* stream);

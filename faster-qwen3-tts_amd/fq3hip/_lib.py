@@ -313,6 +313,16 @@ SIGNATURES = {
     "fq3_mark_scan_windows": (C.c_int64, [C.c_int64, C.c_int, C.c_int]),
     "fq3_mark_scan_workspace": (C.c_int64, [C.c_int, C.POINTER(C.c_int64)]),
     "fq3_mark_scan": (C.c_int, [C.c_int, C.POINTER(vp), C.POINTER(C.c_int64), C.POINTER(C.c_uint64), C.c_int, C.c_int, vp, C.c_int64, vp, vp, vp]),
+    "fq3_voices_create": (C.c_int, [C.c_int, C.c_int64, C.POINTER(vp)]),
+    "fq3_voices_destroy": (C.c_int, [vp]),
+    "fq3_voices_count": (C.c_int64, [vp]),
+    "fq3_voices_add": (C.c_int64, [vp, vp, C.c_int64, vp]),
+    "fq3_voices_drop": (C.c_int, [vp, C.c_int64, vp]),
+    "fq3_voices_reset": (C.c_int, [vp]),
+    "fq3_voices_search_workspace": (C.c_int64, [vp, C.c_int, C.c_int]),
+    "fq3_voices_search": (C.c_int, [vp, vp, C.c_int, C.c_int, vp, vp, vp]),
+    "fq3_voices_slab_rows": (C.c_int, [vp]),
+    "fq3_voices_set_option": (C.c_int, [vp, C.c_char_p, C.c_int]),
 }
 
 _lib = None

@@ -264,14 +264,60 @@ def cmd_enroll(args):
             texts = [line.strip() for line in f.read().splitlines()]
         if len(texts) != len(args.files) or not all(texts):
             raise SystemExit(f"ERROR: --ref-text-file needs one non-empty line per clip ({len(args.files)} clips, {len(texts)} lines)")
+    blocklist, refuse = getattr(args, "blocklist", None), getattr(args, "refuse_above", None)
+    if (blocklist is None) != (refuse is None):
+        raise SystemExit("ERROR: --blocklist and --refuse-above go together (no threshold is assumed)")
     model = load_model(args)
     xvec = texts is None
     entries = [model._voice_cache_entry(p, xvec, True) for p in args.files]       # (audio at 24 kHz, key, metadata, silence, identity)
     items = model.create_voice_clone_prompts([en[0] for en in entries], texts, x_vector_only_mode=xvec)
+    if blocklist is not None:                                                     # on the x-vectors just computed, before anything is written
+        from .voice_library import VoiceLibrary
+        near = model.nearest_voices(list(items), 24000, VoiceLibrary.load(blocklist, args.device), 1)
+        hits = [(p, n[0]) for p, n in zip(args.files, near) if n and n[0][1] >= refuse]
+        for p, (name, cos) in hits:
+            print(f"REFUSED {p}: {name} {cos:.6f}")
+        if hits:
+            raise SystemExit(3)
     cache = VoiceRefCache(args.out)
     for path, en, item in zip(args.files, entries, items):
         key = export_voice_clone_prompt(cache, en[0], item, append_silence=en[3], model_identity=en[4], ref_text=item.ref_text or "")
         print(f"{path}: {key}")
+
+
+def _mono_files(paths):
+    from .audio_io import read_wav
+    clips = []
+    for path in paths:
+        pcm, sr = read_wav(path)
+        pcm = np.asarray(pcm, dtype=np.float32)
+        clips.append((pcm if pcm.ndim == 1 else pcm.reshape(len(pcm), -1)[:, 0], sr))
+    return clips
+
+
+def cmd_voices(args):
+    """``voices build``: the x-vectors of the WAV files (group calls) into a library file, named by their paths.
+    ``voices search``: per file its ``--k`` nearest library voices, one ``file: name cosine`` line each; with ``--refuse-above C`` the
+    exit status is 3 when any file's nearest cosine is >= C (no threshold is assumed without it: the exit status is then 0)."""
+    from .voice_library import VoiceLibrary
+    import torch
+    model = load_model(args)
+    if args.voices_command == "build":                                            # the x-vectors enrolment computes: two group calls' first half
+        items = model.create_voice_clone_prompts(list(args.files), None, x_vector_only_mode=True)
+        embeds = torch.stack([torch.as_tensor(it.ref_spk_embedding).float().reshape(-1) for it in items])
+        lib = VoiceLibrary(embeds.shape[1], max(len(items), 1024), args.device)
+        lib.add(embeds, list(args.files))
+        lib.save(args.out)
+        print(f"Wrote {args.out} ({len(lib)} voices)")
+        return
+    clips = _mono_files(args.files)
+    lib = VoiceLibrary.load(args.lib, args.device)
+    near = model.nearest_voices([c[0] for c in clips], [c[1] for c in clips], lib, args.k)
+    for path, found in zip(args.files, near):
+        for name, cos in found:
+            print(f"{path}: {name} {cos:.6f}")
+    if args.refuse_above is not None and any(f and f[0][1] >= args.refuse_above for f in near):
+        raise SystemExit(3)
 
 
 def _write_output(path, audio, sr, args):
@@ -511,7 +557,24 @@ def build_parser():
     e.add_argument("--ref-text-file", metavar="FILE", help="one transcript line per WAV file: ICL prompts (embedding and reference "
                    "codes); without it the prompts are x-vector only")
     e.add_argument("files", nargs="+", metavar="WAV", help="reference clips")
+    e.add_argument("--blocklist", metavar="LIB.npz", help="a voice library (`voices build`) of voices that must not be enrolled; needs --refuse-above")
+    e.add_argument("--refuse-above", type=float, default=None, metavar="C",
+                   help="--blocklist: write nothing and exit 3 when a clip's nearest blocklist voice has a cosine >= C (no default: the "
+                        "threshold depends on the checkpoint)")
     e.set_defaults(func=cmd_enroll)
+    vo = sub.add_parser("voices", help="a library of enrolled voices: build it from WAV files, find the nearest voices of WAV files in it")
+    vsub = vo.add_subparsers(dest="voices_command", required=True)
+    vb = vsub.add_parser("build", help="the x-vectors of WAV files into LIB.npz, named by their paths")
+    vb.add_argument("--out", required=True, metavar="LIB.npz")
+    vs = vsub.add_parser("search", help="per WAV file its nearest library voices: `file: name cosine` (ranked on the device)")
+    vs.add_argument("--lib", required=True, metavar="LIB.npz")
+    vs.add_argument("--k", type=int, default=1, help="voices per file, 1 to 16 (default 1)")
+    vs.add_argument("--refuse-above", type=float, default=None, metavar="C",
+                    help="exit 3 when any file's nearest cosine is >= C (no default: the threshold depends on the checkpoint)")
+    for sp in (vb, vs):
+        sp.add_argument("--model", default="Qwen/Qwen3-TTS-12Hz-0.6B-Base", help="local checkpoint directory (its speaker encoder is used)")
+        sp.add_argument("files", nargs="+", metavar="WAV", help="WAV files (mono, or the first channel); any rate")
+        sp.set_defaults(func=cmd_voices)
     return p
 
 

@@ -1402,6 +1402,17 @@ class FasterQwen3TTS:
             raise NotImplementedError("this weight table has no speaker_encoder.* tensors: speaker embeddings cannot be computed here")
         return speaker_similarity(an, audio, sr, ref, self.model._reference_wave)
 
+    def nearest_voices(self, audio, sr, library, k=1):
+        """Is this voice already in ``library`` (a ``voice_library.VoiceLibrary``: the enrolled voices, or a list of voices that must
+        not be cloned)?  ``audio`` / ``sr`` as for ``speaker_similarity``; a clip may also be a ``voice_clone_prompt``, a prompt item or
+        a raw embedding wrapped in ``speaker_check.StoredEmbedding``, used as stored.  Returns per clip the ``k``
+        nearest voices ``[(name, cosine), ...]``, best first, ranked on the device (``fq3_voices_search``).  NO threshold is chosen."""
+        from .speaker_check import nearest_voices
+        an = getattr(self.model, "ref_analyzer", None)
+        if an is None or not an.has_speaker:
+            raise NotImplementedError("this weight table has no speaker_encoder.* tensors: speaker embeddings cannot be computed here")
+        return nearest_voices(an, audio, sr, library, k)
+
     def create_voice_clone_prompts(self, ref_audios, ref_texts=None, x_vector_only_mode=False):
         """Enrol many voices at once: one ``VoiceClonePromptItem`` per reference clip (a WAV path, ``(array, sr)`` or a 24 kHz
         waveform each), both halves of every prompt from two group calls whose launch counts do not depend on the number of clips

@@ -225,6 +225,11 @@ class HipRefAudioAnalyzer:
         with torch.cuda.device(self.device):
             L.check(self.lib.fq3_refenc_speaker_group(self.h, ptrs, lens, rows, out_ptr, torch.cuda.current_stream(self.device).cuda_stream))
 
+    def nearest(self, clips, library, k: int = 1) -> list:
+        """The ``k`` nearest voices of ``library`` (a ``voice_library.VoiceLibrary``) for every 24 kHz clip: the clips through
+        ``speaker_embeddings`` (group calls), then ``library.search`` -> per clip ``[(name, cosine), ...]``, best first."""
+        return library.search(self.speaker_embeddings(clips), k) if len(clips) else []
+
     def encode_many(self, clips) -> list:
         """``speech_tokenizer.encode`` of many 24 kHz clips of different lengths -> one ``LongTensor[T_b, num_quantizers]`` per clip.
 

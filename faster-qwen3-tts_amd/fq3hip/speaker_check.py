@@ -43,6 +43,41 @@ def reference_embedding(ref):
     return emb
 
 
+class StoredEmbedding:
+    """A raw speaker embedding given where a clip is expected (``nearest_voices``): a 1-D array there is always a waveform, so an
+    embedding says what it is.  ``reference_embedding`` reads it like a prompt item."""
+
+    def __init__(self, embedding):
+        self.ref_spk_embedding = embedding
+
+
+def nearest_voices(analyzer, audio, sr, library, k: int = 1) -> list:
+    """The ``k`` nearest voices of ``library`` (``voice_library.VoiceLibrary``) for ``audio``: one clip or a list of them, each a mono
+    waveform at ``sr`` Hz (one rate or one per clip; another rate than 24 kHz goes through the device resampler), or something that
+    carries its embedding, which is used as stored (``reference_embedding``): a ``voice_clone_prompt`` dict, a prompt item, or a raw
+    embedding wrapped in ``StoredEmbedding``.  The waveforms share the analyser's group calls, all queries one ``library.search``.
+    Returns ``[(name, cosine), ...]`` best first (a list of those for a list)."""
+    one = not isinstance(audio, (list, tuple))
+    clips = [audio] if one else list(audio)
+    if not clips:
+        return []
+    rates = list(sr) if isinstance(sr, (list, tuple)) else [sr] * len(clips)
+    if len(rates) != len(clips):
+        raise ValueError("sr must be one rate or one per clip")
+    stored = [reference_embedding(x) if isinstance(x, dict) or hasattr(x, "ref_spk_embedding") else None for x in clips]
+    waves = []
+    for x, r, e in zip(clips, rates, stored):
+        if e is None:
+            if int(r) != RATE:
+                from .audio_out import resample_device
+                x = resample_device(x.detach().cpu().numpy() if isinstance(x, torch.Tensor) else x, int(r), RATE, analyzer.device)
+            waves.append(x)
+    fresh = iter(analyzer.speaker_embeddings(waves)) if waves else iter(())
+    q = torch.stack([next(fresh).to(analyzer.device) if e is None else e.to(device=analyzer.device, dtype=torch.float32) for e in stored])
+    out = library.search(q, k)
+    return out[0] if one else out
+
+
 def speaker_similarity(analyzer, audio, sr, ref, reference_wave: Callable) -> Union[float, List[float]]:
     """Cosine between the speaker embedding of ``audio`` (one mono waveform or a list of them, device tensors or host arrays at ``sr``
     Hz -- one rate or one per clip) and that of ``ref``.  ``reference_wave``: what turns an audio ``ref`` into 24 kHz mono (the

@@ -1092,6 +1092,38 @@ int fq3_noise_first(fq3_ctx* ctx, uint64_t seed, void* out, void* stream);
  * (device uint32[V]).  Needs no context. */
 int fq3_noise_words(uint64_t seed, uint32_t frame, uint32_t slot, int V, uint32_t* out, void* stream);
 
+/* ---- voice library: the nearest enrolled voices of up to 32 query embeddings, on the device -----------------------------------
+ * Additive: nothing above changes and fq3_abi_version stays what it was.
+ * A table of up to `capacity` speaker embeddings of `dim` floats (dim a multiple of 16 in [16, 8192], capacity in [1, 2^22]) kept on
+ * the current device, every row scaled to unit length when it is added (fp32 sum of squares in a fixed order; a zero row stays
+ * zero).  A row's stored values depend on the row alone.  A search returns, per query, the k rows of largest cosine, ordered by
+ * (cosine descending, index ascending): idx int32[rows][k] and cos float32[rows][k], best first; slots beyond the number of live
+ * rows hold idx -1 and cos -2.  A row's cosine against a query is one fixed chain of fp32 matrix-core products in ascending K: it is
+ * bit-identical whatever the library's size, the row's position, the other queries of the call and the slab size.  A zero query or a
+ * zero row scores exactly 0; a row or query with a NaN is never returned.  No threshold is chosen here.
+ *   create    FQ3_EINVAL for a null out or a dim / capacity out of range (before any HIP call); FQ3_ENOMEM when the device refuses.
+ *   add       embeds: device float32[rows][dim]; ONE launch on `stream`; returns the index of the first new row, or a negative code:
+ *             FQ3_EINVAL (null, rows < 1), FQ3_ENOMEM when rows exceed what is free -- nothing is added, the object stays usable.
+ *   drop      the row is never returned again; other indices do not move.  FQ3_EINVAL for an index outside [0, count).
+ *   reset     empties the library (synchronises the device).
+ *   search    q: device float32[rows][dim], rows in 1..32, k in 1..16, else FQ3_EINVAL; all or nothing, checked before the first
+ *             launch.  THREE launches on `stream` whatever the library's size, rows and k; no host synchronisation.  The query
+ *             operand and the partial results are the object's: one search at a time per object.
+ *   search_workspace   host only: the bytes of the object's workspace such a call uses (negative: an FQ3_E* code).
+ *   slab_rows / set_option   library rows per workgroup of the scan ("slab_rows": 128, 256 (default) or 512; another name or value:
+ *             FQ3_EINVAL).  A launch parameter: no result depends on it. */
+typedef struct fq3_voices fq3_voices;
+int fq3_voices_create(int dim, int64_t capacity, fq3_voices** out);
+int fq3_voices_destroy(fq3_voices* v);
+int64_t fq3_voices_count(const fq3_voices* v);
+int64_t fq3_voices_add(fq3_voices* v, const float* embeds, int64_t rows, void* stream);
+int fq3_voices_drop(fq3_voices* v, int64_t index, void* stream);
+int fq3_voices_reset(fq3_voices* v);
+int64_t fq3_voices_search_workspace(const fq3_voices* v, int rows, int k);
+int fq3_voices_search(fq3_voices* v, const float* q, int rows, int k, int32_t* idx, float* cos, void* stream);
+int fq3_voices_slab_rows(const fq3_voices* v);
+int fq3_voices_set_option(fq3_voices* v, const char* name, int value);
+
 #ifdef __cplusplus
 }
 #endif

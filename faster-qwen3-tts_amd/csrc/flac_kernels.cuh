@@ -439,4 +439,392 @@ __global__ __launch_bounds__(kFlacGatherThreads) void flac_gather_group_kernel(c
     flac_gather_body(a, wg - g.gat_wg0[row]);
 }
 
+// ---- LPC subframes (fq3_flac_set_option "lpc_order" = M in 1 .. 8; the rule in include/fq3hip.h) ----
+// flac_encode_lpc_kernel: ONE workgroup of THIRTEEN waves per block, one wave per predictor candidate: wave c < 5 is FIXED order c,
+// wave 5 + (o - 1) is LPC order o.  A FIXED predictor is an LPC predictor with binomial coefficients and shift 0, so every wave
+// runs the same residual  x[i] - ((sum_j q[j] x[i-1-j]) >> s)  from its row of one coefficient table in LDS.
+//   (1) x is staged as in the fixed kernel and, beside it, the windowed y (integers only; the window has no table);
+//   (2) wave l <= M sums lag l of the autocorrelation over the block in int64 (exact; a shuffle tree inside the wave);
+//   (3) one lane of wave 5 runs Levinson-Durbin in double -- every operation rounded on its own, in the order the rule lists -- and
+//       quantises every order to 12 bits; waves 0 .. 4 do not wait for it, they are in (4) meanwhile;
+//   (4) lane g of wave c keeps the 15 Rice sums of segment g at candidate c in registers, and they STAY there: a partition's sums are
+//       its first segment's after the neighbours were added by __shfl_down (orders 6 .. 0), its cost is a wave sum.  Between staging
+//       and choice the candidates need no LDS and no workgroup barrier of their own; a wave without a candidate falls through;
+//   (5) thread 0 takes the cheapest (candidate, partition order) and writes the subframe header; the writer, the CRC-16 tree and the
+//       store are the fixed kernel's steps at this workgroup's width.
+// A term u >> k of a Rice sum is capped at 2^25 and a sum at 2^31 - 1: an LPC residual reaches 2^30, and 72 of them leave 32 bits.  A
+// capped sum belongs to a (partition, k) of 2^25 bits or more, exact or not: more than any frame that is not VERBATIM (16 n < 2^17).
+constexpr int kLpcMaxOrder = 8;
+constexpr int kLpcPrecision = 12;
+constexpr int kLpcMinBlock = 64;                     // shorter (last) blocks are fixed-only
+constexpr int kLpcCands = 5 + kLpcMaxOrder;
+constexpr int kLpcThreads = 64 * kLpcCands;
+constexpr int kLpcCrcSlots = 1024;                   // the CRC tree's width: the power of two above kLpcThreads
+constexpr uint32_t kLpcTermCap = 1u << 25;
+
+__device__ __forceinline__ int lpc_order_of(int c) { return c < 5 ? c : c - 4; }
+
+// coefficient j of the FIXED predictor of order o: (-1)^j C(o, j + 1)
+__device__ __forceinline__ int flac_fixed_coeff(int o, int j) {
+    if (j >= o) return 0;
+    int b = 1;
+    for (int t = 0; t <= j; ++t) b = b * (o - t) / (t + 1);
+    return (j & 1) ? -b : b;
+}
+
+// i >= o.  |q| <= 2^11, |x| <= 2^15, o <= 8: |sum| <= 2^29, so int32 holds it.
+__device__ __forceinline__ int lpc_residual(const int* x, const int (&q)[kLpcMaxOrder], int o, int s, int i) {
+    int sum = 0;
+#pragma unroll
+    for (int j = 0; j < kLpcMaxOrder; ++j)
+        if (j < o) sum += q[j] * x[i - 1 - j];
+    return x[i] - (sum >> s);
+}
+
+// the fixed kernel's step (1) header, as a function: -> its length in bytes
+__device__ __forceinline__ int lpc_frame_header(const FlacArgs& a, int f, int n, uint32_t* bits) {
+    const int bc = flac_block_code(n);
+    uint32_t pos = 0, crc = 0;
+    auto put = [&](uint32_t b) {
+        flac_put(bits, pos, b, 8);
+        pos += 8;
+        crc ^= b;
+        for (int j = 0; j < 8; ++j) crc = ((crc << 1) ^ ((crc & 0x80u) ? 0x07u : 0u)) & 0xFFu;
+    };
+    put(0xFF); put(0xF8); put((uint32_t)(bc << 4 | a.rate_code)); put(0x08);
+    const uint32_t v = a.frame0 + (uint32_t)f;
+    if (v < 0x80u) {
+        put(v);
+    } else {
+        int nb = 2;
+        while (nb < 6 && v >= (1u << (5 * nb + 1))) ++nb;
+        put(((0xFF00u >> nb) & 0xFFu) | (v >> (6 * (nb - 1))));
+        for (int j = nb - 2; j >= 0; --j) put(0x80u | ((v >> (6 * j)) & 0x3Fu));
+    }
+    if (bc == 6) put((uint32_t)(n - 1));
+    if (bc == 7) { put((uint32_t)(n - 1) >> 8); put((uint32_t)(n - 1) & 0xFFu); }
+    if (a.rate_code == 13) { put((uint32_t)a.rate_hz >> 8); put((uint32_t)a.rate_hz & 0xFFu); }
+    const uint32_t c8 = crc;
+    put(c8);
+    return (int)(pos >> 3);
+}
+
+// Levinson-Durbin on R[0 .. M] and the quantisation of every order, by ONE lane: row o - 1 of q / shift receives order o, the
+// result has bit o - 1 set where that order is a candidate.  The products and differences are written as plain operators under
+// `fp contract(off)`, not as __dmul_rn / __dsub_rn: those are inline `x * y` / `x - y` compiled under the translation unit's
+// contraction mode, and a product and a difference that meet after inlining may then be fused.  Under the pragma no operation of
+// this function carries the permission to contract, so each is rounded on its own; the f64 division is the correctly rounded one.
+// Every loop is unrolled so that a[], nw[] and r[] are registers (no scratch).
+__device__ __forceinline__ uint32_t lpc_coefficients(const int64_t* R, const int M, int* q, int* shift) {
+#pragma clang fp contract(off)
+    double r[kLpcMaxOrder + 1], a[kLpcMaxOrder], nw[kLpcMaxOrder];
+#pragma unroll
+    for (int l = 0; l <= kLpcMaxOrder; ++l) r[l] = l <= M ? (double)R[l] : 0.0;      // below 2^53: exact
+    double err = r[0];
+    uint32_t mask = 0;
+    bool go = true;
+#pragma unroll
+    for (int i = 0; i < kLpcMaxOrder; ++i) {
+        go = go && i < M && err > 0.0 && isfinite(err);
+        if (go) {
+            double acc = r[i + 1];
+#pragma unroll
+            for (int j = 0; j < i; ++j) acc = acc - a[j] * r[i - j];
+            const double k = acc / err;
+#pragma unroll
+            for (int j = 0; j < i; ++j) nw[j] = a[j] - k * a[i - 1 - j];
+            nw[i] = k;
+            double cmax = 0.0;
+            bool finite = true;
+#pragma unroll
+            for (int j = 0; j <= i; ++j) {
+                a[j] = nw[j];
+                finite = finite && isfinite(a[j]);
+                cmax = fmax(cmax, fabs(a[j]));
+            }
+            err = err * (1.0 - k * k);
+            int e = 0;
+            (void)frexp(cmax, &e);
+            const int s = 11 - e < 15 ? 11 - e : 15;
+            if (finite && cmax != 0.0 && s >= 0) {
+                const double scale = (double)(1 << s);                               // a power of two: the product is exact
+#pragma unroll
+                for (int j = 0; j <= i; ++j) {
+                    const double v = rint(a[j] * scale);                             // ties to even
+                    q[i * kLpcMaxOrder + j] = (int)(v < -2048.0 ? -2048.0 : v > 2047.0 ? 2047.0 : v);
+                }
+                shift[i] = s;
+                mask |= 1u << i;
+            }
+        }
+    }
+    return mask;
+}
+
+// Steps (4): the Rice sums of candidate c (this wave's), every legal partition order's k per partition into bestk and its cost
+// into cost[c * 7 + p].  Wave-local: shuffles, no barrier.
+__device__ __forceinline__ void lpc_candidate_costs(const int* x, const int* qtab, const int n, const int pmax, const int c, const int s,
+                                                    const int g, uint8_t* bestk, uint32_t* cost) {
+    const int o = lpc_order_of(c);
+    int q[kLpcMaxOrder];
+#pragma unroll
+    for (int j = 0; j < kLpcMaxOrder; ++j) q[j] = qtab[c * kLpcMaxOrder + j];
+    uint32_t acc[kFlacMaxK + 1];
+#pragma unroll
+    for (int k = 0; k <= kFlacMaxK; ++k) acc[k] = 0;
+    {
+        const int size = n >> pmax, sub = kFlacSegs >> pmax, per = (size + sub - 1) / sub;
+        const int part = g >> (6 - pmax), j = g & (sub - 1);
+        int lo = part * size + (j * per < size ? j * per : size);
+        const int hi = part * size + ((j + 1) * per < size ? (j + 1) * per : size);
+        lo = lo < o ? o : lo;
+        for (int i = lo; i < hi; ++i) {                                              // at most 72 samples: 72 * 2^25 < 2^32
+            const uint32_t u = flac_fold(lpc_residual(x, q, o, s, i));
+#pragma unroll
+            for (int k = 0; k <= kFlacMaxK; ++k) {
+                const uint32_t t = u >> k;
+                acc[k] += t < kLpcTermCap ? t : kLpcTermCap;
+            }
+        }
+    }
+#pragma unroll
+    for (int k = 0; k <= kFlacMaxK; ++k) acc[k] = acc[k] < kFlacSat ? acc[k] : kFlacSat;
+    for (int p = 6; p >= 0; --p) {
+        const int span = kFlacSegs >> p;
+        if (p <= pmax && (n >> p) > o) {                                             // uniform over the wave
+            uint32_t bits = 0;
+            if ((g & (span - 1)) == 0) {
+                const int part = g / span;
+                const uint32_t cnt = (uint32_t)((n >> p) - (part == 0 ? o : 0));
+                uint32_t best = 0xFFFFFFFFu;
+                int bk = 0;
+#pragma unroll
+                for (int k = 0; k <= kFlacMaxK; ++k) {
+                    const uint32_t b = cnt * (uint32_t)(1 + k) + acc[k];
+                    if (b < best) { best = b; bk = k; }
+                }
+                bestk[(c * 7 + p) * kFlacSegs + part] = (uint8_t)bk;
+                bits = 4u + (best < (1u << 24) ? best : (1u << 24));
+            }
+            for (int d = 32; d >= 1; d >>= 1) bits += __shfl_xor(bits, d);           // at most 64 (2^24 + 4)
+            if (g == 0) cost[c * 7 + p] = bits;
+        }
+        if (p > 0) {
+#pragma unroll
+            for (int k = 0; k <= kFlacMaxK; ++k) {
+                const uint32_t s2 = acc[k] + __shfl_down(acc[k], span);              // both below 2^31; only a partition's first lane matters
+                acc[k] = s2 < kFlacSat ? s2 : kFlacSat;
+            }
+        }
+    }
+}
+
+// frame f of the launch `a` describes, with LPC candidates up to order M >= 1; f == a.n_frames: the tail copy
+__device__ __forceinline__ void flac_encode_lpc_body(const FlacArgs& a, const int f, const int M) {
+    __shared__ int s_x[kFlacMaxBlock];
+    __shared__ int s_y[kFlacMaxBlock];
+    __shared__ uint32_t s_bits[kFlacBitWords];
+    __shared__ uint32_t s_cost[kLpcCands * 7];
+    __shared__ uint8_t s_bestk[kLpcCands * 7 * kFlacSegs];
+    __shared__ int s_q[kLpcCands * kLpcMaxOrder];
+    __shared__ int s_shift[kLpcCands];
+    __shared__ int64_t s_R[kLpcMaxOrder + 1];
+    __shared__ uint32_t s_scan[kLpcCands];
+    __shared__ uint32_t s_crc[kLpcCrcSlots];
+    __shared__ uint32_t s_lpc, s_base;
+    __shared__ int s_hdr, s_cand, s_porder, s_body;
+
+    const int tid = threadIdx.x;
+    if (f == a.n_frames) {
+        for (int i = tid; i < a.tail_len; i += kLpcThreads) a.tail_next[i] = (int16_t)flac_fetch(a, a.tail_from + i);
+        return;
+    }
+    const int64_t start = a.first + (int64_t)f * a.block;
+    const int n = (int)(a.avail - start < a.block ? a.avail - start : a.block);
+    const bool lpc = n >= kLpcMinBlock;
+
+    // (1)  w = 32768 in the middle half; d samples into a quarter at either end: 32768 - floor(32768 d^2 / (t + 1)^2), t = n / 4
+    {
+        const int t = n >> 2;
+        const uint64_t t2 = (uint64_t)(t + 1) * (uint64_t)(t + 1);
+        for (int i = tid; i < n; i += kLpcThreads) {
+            const int x = flac_fetch(a, start + i);
+            s_x[i] = x;
+            const int d = i < t ? t - i : i >= n - t ? i - (n - 1 - t) : 0;
+            const int w = 32768 - (int)((uint64_t)32768 * (uint64_t)(d * d) / t2);   // d <= 1152
+            s_y[i] = (x * w + 2048) >> 12;                                           // |x w| <= 2^30; |y| <= 2^18
+        }
+    }
+    for (int i = tid; i < (2 * n + 18 + 3) / 4 + 1; i += kLpcThreads) s_bits[i] = 0;
+    if (tid < kLpcCands * 7) s_cost[tid] = 0;
+    if (tid < kLpcCands * kLpcMaxOrder) s_q[tid] = tid < 5 * kLpcMaxOrder ? flac_fixed_coeff(tid / kLpcMaxOrder, tid % kLpcMaxOrder) : 0;
+    if (tid < kLpcCands) s_shift[tid] = 0;
+    __syncthreads();
+    if (tid == 0) s_hdr = lpc_frame_header(a, f, n, s_bits);
+    int differs = 0;
+    for (int i = tid; i < n; i += kLpcThreads) differs |= s_x[i] != s_x[0];
+    const int varied = __syncthreads_or(differs);
+    const int hdr = s_hdr;
+
+    if (!varied) {
+        if (tid == 0) {
+            flac_put(s_bits, (uint32_t)hdr * 8 + 8, (uint32_t)s_x[0] & 0xFFFFu, 16);
+            s_body = hdr + 3;
+        }
+    } else {
+        const int c = tid >> 6, g = tid & 63;
+        const int omax = n - 1 < 4 ? n - 1 : 4;
+        int pmax = __builtin_ctz((unsigned)n);
+        pmax = pmax > 6 ? 6 : pmax;
+        // (2)  R[l] = sum_i y[i] y[i + l] < 4608 * 2^36
+        if (lpc && c <= M) {
+            int64_t sum = 0;
+            for (int i = g; i + c < n; i += 64) sum += (int64_t)s_y[i] * (int64_t)s_y[i + c];
+            for (int d = 32; d >= 1; d >>= 1) sum += __shfl_xor(sum, d);
+            if (g == 0) s_R[c] = sum;
+        }
+        __syncthreads();
+        // (3) beside (4) for the FIXED candidates
+        if (tid == 5 * 64) s_lpc = lpc ? lpc_coefficients(s_R, M, &s_q[5 * kLpcMaxOrder], &s_shift[5]) : 0u;
+        if (c < 5 && c <= omax) lpc_candidate_costs(s_x, s_q, n, pmax, c, 0, g, s_bestk, s_cost);
+        __syncthreads();
+        // (4) for the LPC candidates that exist (n >= 64 > o)
+        const uint32_t have = s_lpc;
+        if (c >= 5 && ((have >> (c - 5)) & 1u)) lpc_candidate_costs(s_x, s_q, n, pmax, c, s_shift[c], g, s_bestk, s_cost);
+        __syncthreads();
+        // (5) ascending candidates, then ascending p, strictly cheaper: ties go to FIXED, then the lower order, then the lower p
+        if (tid == 0) {
+            uint32_t best = 0xFFFFFFFFu;
+            int bc = 0, bp = 0;
+            for (int cc = 0; cc < kLpcCands; ++cc) {
+                const int oo = lpc_order_of(cc);
+                if (cc < 5 ? oo > omax : !((have >> (cc - 5)) & 1u)) continue;
+                const uint32_t head = cc < 5 ? 16u * oo + 6u : 16u * oo + 9u + (uint32_t)kLpcPrecision * oo + 6u;
+                for (int p = 0; p <= pmax; ++p)
+                    if ((n >> p) > oo) {
+                        const uint32_t cost = head + s_cost[cc * 7 + p];
+                        if (cost < best) { best = cost; bc = cc; bp = p; }
+                    }
+            }
+            const bool verbatim = best >= 16u * (uint32_t)n;
+            s_cand = verbatim ? -1 : bc;
+            s_porder = bp;
+            uint32_t pos = (uint32_t)hdr * 8;
+            if (verbatim) {
+                flac_put(s_bits, pos, 0x02u, 8);
+            } else {
+                const int bo = lpc_order_of(bc);
+                flac_put(s_bits, pos, (uint32_t)((bc < 5 ? 8 | bo : 0x20 | (bo - 1)) << 1), 8);
+                pos += 8;
+                for (int i = 0; i < bo; ++i, pos += 16) flac_put(s_bits, pos, (uint32_t)s_x[i] & 0xFFFFu, 16);
+                if (bc >= 5) {
+                    flac_put(s_bits, pos, (uint32_t)(kLpcPrecision - 1), 4);
+                    flac_put(s_bits, pos + 4, (uint32_t)s_shift[bc], 5);
+                    pos += 9;
+                    for (int j = 0; j < bo; ++j, pos += kLpcPrecision)
+                        flac_put(s_bits, pos, (uint32_t)s_q[bc * kLpcMaxOrder + j] & 0xFFFu, kLpcPrecision);
+                }
+                flac_put(s_bits, pos, (uint32_t)bp, 6);
+                s_base = pos + 6;
+            }
+        }
+        __syncthreads();
+        const int cand = s_cand, porder = s_porder;
+        if (cand < 0) {
+            for (int i = tid; i < n; i += kLpcThreads) flac_put(s_bits, (uint32_t)(hdr + 1 + 2 * i) * 8, (uint32_t)s_x[i] & 0xFFFFu, 16);
+            if (tid == 0) s_body = hdr + 1 + 2 * n;
+        } else {
+            const int order = lpc_order_of(cand), s = s_shift[cand];
+            int q[kLpcMaxOrder];
+#pragma unroll
+            for (int j = 0; j < kLpcMaxOrder; ++j) q[j] = s_q[cand * kLpcMaxOrder + j];
+            const int size = n >> porder;
+            const uint8_t* ks = &s_bestk[(cand * 7 + porder) * kFlacSegs];
+            const int per = (n - order + kLpcThreads - 1) / kLpcThreads;
+            const int c0 = order + tid * per < n ? order + tid * per : n;
+            const int c1 = c0 + per < n ? c0 + per : n;
+            uint32_t local = 0;                                                      // the frame has fewer than 16 n bits
+            for (int i = c0; i < c1; ++i) {
+                const int part = i / size, k = ks[part];
+                if (i == order || i == part * size) local += 4;
+                local += (flac_fold(lpc_residual(s_x, q, order, s, i)) >> k) + 1u + (uint32_t)k;
+            }
+            uint32_t incl = local;
+            for (int d = 1; d < 64; d <<= 1) {
+                const uint32_t up = __shfl_up(incl, d);
+                if (g >= d) incl += up;
+            }
+            if (g == 63) s_scan[c] = incl;
+            __syncthreads();
+            uint32_t before = 0, total = 0;
+            for (int w = 0; w < kLpcCands; ++w) {
+                const uint32_t t = s_scan[w];
+                before += w < c ? t : 0u;
+                total += t;
+            }
+            const uint32_t base = s_base;
+            uint32_t pos = base + before + incl - local;
+            for (int i = c0; i < c1; ++i) {
+                const int part = i / size, k = ks[part];
+                if (i == order || i == part * size) { flac_put(s_bits, pos, (uint32_t)k, 4); pos += 4; }
+                const uint32_t u = flac_fold(lpc_residual(s_x, q, order, s, i));
+                pos += u >> k;
+                flac_put(s_bits, pos, (1u << k) | (u & ((1u << k) - 1u)), k + 1);
+                pos += (uint32_t)k + 1u;
+            }
+            if (tid == 0) s_body = (int)((base + total + 7) >> 3);
+        }
+    }
+    __syncthreads();
+    // CRC-16 as in the fixed kernel, kLpcThreads slices in a tree of kLpcCrcSlots.  A frame never passes the bound of 2 n + 18 bytes;
+    // the minimum only keeps the store below inside the staging slot should a length ever be wrong.
+    const int len = s_body < 2 * n + 16 ? s_body : 2 * n + 16;
+    {
+        const int lb = (len + kLpcThreads - 1) / kLpcThreads;
+        const int e = len - tid * lb, b = e - lb < 0 ? 0 : e - lb;
+        uint32_t crc = 0;
+        for (int i = b; i < e; ++i) {
+            crc ^= ((s_bits[i >> 2] >> (24 - 8 * (i & 3))) & 0xFFu) << 8;
+            for (int j = 0; j < 8; ++j) crc = (crc << 1) ^ ((crc & 0x8000u) ? 0x18005u : 0u);
+        }
+        s_crc[tid] = crc & 0xFFFFu;
+        if (tid + kLpcThreads < kLpcCrcSlots) s_crc[tid + kLpcThreads] = 0;
+        uint32_t m = 1;
+        for (int i = 0; i < 8 * lb; ++i) m = (m << 1) ^ ((m & 0x8000u) ? 0x18005u : 0u);
+        m &= 0xFFFFu;
+        __syncthreads();
+        for (int h = 1; h < kLpcCrcSlots; h <<= 1) {
+            uint32_t v = 0;
+            const bool mine = (tid & (2 * h - 1)) == 0 && tid + h < kLpcCrcSlots;
+            if (mine) v = flac_mulmod(s_crc[tid + h], m) ^ s_crc[tid];
+            __syncthreads();
+            if (mine) s_crc[tid] = v;
+            __syncthreads();
+            m = flac_mulmod(m, m);
+        }
+        if (tid == 0) flac_put(s_bits, (uint32_t)len * 8, s_crc[0], 16);
+    }
+    __syncthreads();
+    const int flen = len + 2;
+    uint32_t* dst = reinterpret_cast<uint32_t*>(a.stage + (size_t)f * a.stride);
+    for (int w = tid; w < (flen + 3) / 4; w += kLpcThreads) dst[w] = __builtin_bswap32(s_bits[w]);
+    if (tid == 0) a.sizes[f] = flen;
+}
+
+__global__ __launch_bounds__(kLpcThreads) void flac_encode_lpc_kernel(FlacArgs a, int lpc_order) {
+    flac_encode_lpc_body(a, (int)blockIdx.x, lpc_order);
+}
+
+// the group twin, on flac_encode_group_kernel's packed grid
+__global__ __launch_bounds__(kLpcThreads) void flac_encode_lpc_group_kernel(const FlacGroupArgs g, int lpc_order) {
+    const int wg = (int)blockIdx.x, row = flac_group_row(g.enc_wg0, wg);
+    const FlacGroupRow& r = g.rows[row];
+    FlacArgs a;
+    a.pcm = r.pcm; a.tail = r.tail; a.tail_next = r.tail_next; a.stage = r.stage; a.sizes = r.sizes;
+    a.first = g.first; a.avail = r.avail; a.tail_from = r.tail_from; a.tail_n = r.tail_n; a.tail_len = r.tail_len;
+    a.block = g.block; a.n_frames = r.n_frames; a.stride = g.stride; a.frame0 = r.frame0;
+    a.rate_code = g.rate_code; a.rate_hz = g.rate_hz;
+    flac_encode_lpc_body(a, wg - g.enc_wg0[row], lpc_order);
+}
+
 }  // namespace fq3

@@ -3,6 +3,8 @@
 //   fq3_flac_create / _push              streaming encoder: per push one launch pair per 64 frames (encode, then gather)
 //   fq3_flac_push_group                  the pushes of up to 32 objects of one design in ONE launch pair per 64 frames, each row bit for
 //                                        bit its single push
+//   fq3_flac_set_option                  "lpc_order" = M: 0 keeps the kernels above; 1 .. 8 adds LPC subframes of order 1 .. M
+//                                        (flac_encode_lpc_kernel and its group twin; the gather launch is the same)
 //
 // The stream: `fLaC`, one STREAMINFO block, then frames of B samples (only the last one of a stream may be shorter), mono, 16 bits,
 // fixed-blocksize numbering.  A frame holds one subframe -- CONSTANT, VERBATIM or FIXED of order 0..4 with partitioned 4-bit Rice
@@ -68,6 +70,8 @@ struct fq3_flac {
     int cur = 0, tail_n = 0;
     int64_t n_in = 0, frame = 0;      // cumulative input samples / frames of the current stream
     bool finished = false;
+    bool started = false;             // a push since the last reset: the options are fixed for the utterance
+    int lpc_order = 0;                // 0: CONSTANT / VERBATIM / FIXED only
 };
 
 extern "C" int fq3_flac_design(int sample_rate, int block_size, int* block, int* max_frame_bytes) {
@@ -141,7 +145,17 @@ extern "C" int fq3_flac_reset(fq3_flac* f, void* stream) {
     (void)stream;                     // nothing to enqueue: an empty tail reads no buffer
     f->n_in = f->frame = 0;
     f->tail_n = 0;
-    f->finished = false;
+    f->finished = f->started = false;
+    return 0;
+}
+
+extern "C" int fq3_flac_set_option(fq3_flac* f, const char* name, int value) {
+    if (!f || !name) return fq3_fail_(FQ3_EINVAL, "fq3_flac_set_option: null argument");
+    if (std::strcmp(name, "lpc_order") != 0) return fq3_fail_(FQ3_EINVAL, std::string("fq3_flac_set_option: unknown option '") + name + "'");
+    if (value < 0 || value > kLpcMaxOrder)
+        return fq3_fail_(FQ3_EINVAL, "fq3_flac_set_option: lpc_order " + std::to_string(value) + " is outside [0, " + std::to_string(kLpcMaxOrder) + "]");
+    if (f->started) return fq3_fail_(FQ3_ESTATE, "fq3_flac_set_option: the utterance has begun; fq3_flac_reset comes first");
+    f->lpc_order = value;
     return 0;
 }
 
@@ -178,6 +192,7 @@ void commit_push_(fq3_flac* f, const Push& q, int64_t n_in, int final) {
     f->tail_n = q.keep;
     f->n_in += n_in;
     f->frame += q.frames;
+    f->started = true;
     if (final) f->finished = true;
 }
 
@@ -211,7 +226,8 @@ extern "C" int fq3_flac_push(fq3_flac* f, const int16_t* pcm, int64_t n_in, int 
         k.tail_len = last && q.copy_tail ? q.keep : 0;
         const int grid = nb + (k.tail_len > 0 ? 1 : 0);
         if (grid > 0) {
-            hipLaunchKernelGGL(flac_encode_kernel, dim3(grid), dim3(kFlacThreads), 0, s, k);
+            if (f->lpc_order > 0) hipLaunchKernelGGL(flac_encode_lpc_kernel, dim3(grid), dim3(kLpcThreads), 0, s, k, f->lpc_order);
+            else hipLaunchKernelGGL(flac_encode_kernel, dim3(grid), dim3(kFlacThreads), 0, s, k);
             FHIP(hipGetLastError());
         }
         if (nb > 0) {
@@ -244,6 +260,8 @@ extern "C" int fq3_flac_push_group(fq3_flac* const* objs, int B, const int16_t* 
             if (objs[c] == objs[b]) return fq3_fail_(FQ3_EINVAL, "fq3_flac_push_group: rows " + std::to_string(c) + " and " + std::to_string(b) + " are the same object");
         if (objs[b]->p.rate != objs[0]->p.rate || objs[b]->p.block != objs[0]->p.block)
             return fq3_fail_(FQ3_EINVAL, "fq3_flac_push_group: row " + std::to_string(b) + " has another design (sample rate, block size) than row 0");
+        if (objs[b]->lpc_order != objs[0]->lpc_order)
+            return fq3_fail_(FQ3_EINVAL, "fq3_flac_push_group: row " + std::to_string(b) + " has another lpc_order than row 0");
     }
     // every row is checked and planned before any object moves
     static_assert(FQ3_STAGE_GROUP_MAX == kFlacGroupMax, "the header's limit is the descriptor table's size");
@@ -288,7 +306,8 @@ extern "C" int fq3_flac_push_group(fq3_flac* const* objs, int B, const int16_t* 
         }
         for (int b = B; b < FQ3_STAGE_GROUP_MAX; ++b) { g.enc_wg0[b] = enc; g.gat_wg0[b] = gat; }
         if (enc > 0) {
-            hipLaunchKernelGGL(flac_encode_group_kernel, dim3(enc), dim3(kFlacThreads), 0, s, g);
+            if (objs[0]->lpc_order > 0) hipLaunchKernelGGL(flac_encode_lpc_group_kernel, dim3(enc), dim3(kLpcThreads), 0, s, g, objs[0]->lpc_order);
+            else hipLaunchKernelGGL(flac_encode_group_kernel, dim3(enc), dim3(kFlacThreads), 0, s, g);
             FHIP(hipGetLastError());
         }
         if (gat > 0) {

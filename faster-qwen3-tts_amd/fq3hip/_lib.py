@@ -255,6 +255,7 @@ SIGNATURES = {
     "fq3_flac_create": (C.c_int, [C.POINTER(FlacConfig), C.POINTER(vp)]),
     "fq3_flac_destroy": (C.c_int, [vp]),
     "fq3_flac_reset": (C.c_int, [vp, vp]),
+    "fq3_flac_set_option": (C.c_int, [vp, C.c_char_p, C.c_int]),
     "fq3_flac_push": (C.c_int, [vp, vp, C.c_int64, C.c_int, vp, C.c_int64, C.POINTER(C.c_int64), vp, vp]),
     # as the two groups above, with one more host array in front of the stream: the rows' device int64 byte counts
     "fq3_flac_push_group": (C.c_int, [C.POINTER(vp), C.c_int, C.POINTER(vp), C.POINTER(C.c_int64), C.POINTER(C.c_int),

@@ -39,7 +39,7 @@ def wav_header_for(sample_rate: int, encoding: str, data_len: int = 0xFFFFFFFF) 
     ``fmt`` chunk and a ``fact`` chunk with the sample count.  ``data_len = 0xFFFFFFFF``: a stream of unknown size."""
     if encoding == "s16":
         return wav_header(sample_rate, data_len)
-    if encoding == "flac":
+    if encoding in ("flac", "flac_lpc"):
         raise ValueError("a FLAC stream is not WAV data: it starts with its own header (flac_header), and the output stage hands it out "
                          "with that header in front")
     if encoding not in _G711_TAGS:

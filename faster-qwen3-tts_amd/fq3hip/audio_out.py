@@ -4,7 +4,8 @@ telephony, 16 kHz s16, 44.1 / 48 kHz -- and only those bytes cross the bus.  The
 into chunks.  A ``speed`` other than 1 puts the time-scale stage in front (``fq3_tsm_*``: WSOLA, one more
 launch per chunk; duration changes, pitch does not), with the same contract.  The ``flac`` encoding puts the
 FLAC stage behind the s16 encoder (``fq3_flac_*``: lossless, a launch pair per chunk): what leaves the chain
-then is FLAC frames, and the 42-byte stream header comes from the host (``flac_header``).
+then is FLAC frames, and the 42-byte stream header comes from the host (``flac_header``).  ``flac_lpc`` is the same stage with LPC
+subframes up to order 8 (``fq3_flac_set_option``): a smaller stream, the same samples.
 
 ``AudioOutSpec``  what a caller asks for (rate, encoding, speed); host only, validates without a GPU
 ``AudioOut``      one stream's time-scale + resampler + encoder state on a device
@@ -22,19 +23,26 @@ import torch
 
 from . import _lib
 
-# ``flac`` is the s16 encoding followed by the FLAC stage: the output stage itself runs in FQ3_PCM_S16
+# ``flac`` / ``flac_lpc`` are the s16 encoding followed by the FLAC stage: the output stage itself runs in FQ3_PCM_S16
 ENCODINGS = {"f32": _lib.FQ3_PCM_F32, "s16": _lib.FQ3_PCM_S16, "mulaw": _lib.FQ3_PCM_MULAW, "alaw": _lib.FQ3_PCM_ALAW,
-             "flac": _lib.FQ3_PCM_S16}
-_DTYPES = {"f32": torch.float32, "s16": torch.int16, "mulaw": torch.uint8, "alaw": torch.uint8, "flac": torch.uint8}
-NUMPY_DTYPES = {"f32": np.float32, "s16": np.dtype("<i2"), "mulaw": np.uint8, "alaw": np.uint8, "flac": np.uint8}
+             "flac": _lib.FQ3_PCM_S16, "flac_lpc": _lib.FQ3_PCM_S16}
+_DTYPES = {"f32": torch.float32, "s16": torch.int16, "mulaw": torch.uint8, "alaw": torch.uint8, "flac": torch.uint8,
+           "flac_lpc": torch.uint8}
+NUMPY_DTYPES = {"f32": np.float32, "s16": np.dtype("<i2"), "mulaw": np.uint8, "alaw": np.uint8, "flac": np.uint8, "flac_lpc": np.uint8}
+FLAC_LPC_ORDERS = {"flac": 0, "flac_lpc": 8}      # the encodings of the FLAC stage and the ``lpc_order`` each sets
 FLAC_HEADER_BYTES = 42
 MIN_SPEED, MAX_SPEED = 0.25, 4.0
 
 
+def is_flac(encoding) -> bool:
+    """whether ``encoding`` goes through the FLAC stage (its output is a FLAC stream's bytes, not samples)"""
+    return encoding in FLAC_LPC_ORDERS
+
+
 @dataclass(frozen=True)
 class AudioOutSpec:
-    """``sample_rate`` None: the model's rate.  ``encoding``: ``f32`` | ``s16`` | ``mulaw`` | ``alaw`` | ``flac`` (the s16 samples, losslessly
-    compressed; the output is bytes, not samples).  ``speed`` in [0.25, 4.0], applied in per-mille steps; 1.0: no time-scale stage at
+    """``sample_rate`` None: the model's rate.  ``encoding``: ``f32`` | ``s16`` | ``mulaw`` | ``alaw`` | ``flac`` | ``flac_lpc`` (the s16 samples,
+    losslessly compressed, without or with LPC subframes; the output is bytes, not samples).  ``speed`` in [0.25, 4.0], applied in per-mille steps; 1.0: no time-scale stage at
     all."""
     sample_rate: Optional[int] = None
     encoding: str = "f32"
@@ -63,7 +71,7 @@ class AudioOutSpec:
         """Raises ``ValueError`` with the library's reason when the resampler refuses ``in_rate -> sample_rate`` or the time-scale
         stage refuses ``in_rate``, or the FLAC stage the output rate (host only)."""
         design(int(in_rate), self.out_rate(in_rate), bank=False)
-        if self.encoding == "flac":
+        if is_flac(self.encoding):
             flac_design(self.out_rate(in_rate))
         if self.permille != 1000:
             tsm_design(int(in_rate), self.permille, window=False)
@@ -166,11 +174,12 @@ class AudioOut:
         if self.dev.index is None:
             self.dev = torch.device("cuda", torch.cuda.current_device())
         self.stream, self.zero = stream, int(zero_crossings)
-        self.dtype = torch.int16 if spec.encoding == "flac" else _DTYPES[spec.encoding]      # what the resample + encode launch writes
+        self.dtype = torch.int16 if is_flac(spec.encoding) else _DTYPES[spec.encoding]      # what the resample + encode launch writes
         self.permille = spec.permille
         self._lib = _lib.load()
         self._h = self._tsm = self._flac = None
-        self.flac = spec.encoding == "flac"
+        self.flac = is_flac(spec.encoding)
+        self.lpc_order = FLAC_LPC_ORDERS.get(spec.encoding, 0)
         # speed alone (the model's rate, float32): the time-scale stage writes the output itself, no second launch
         self._encode = self.permille == 1000 or self.out_rate != self.in_rate or spec.encoding != "f32"
         with torch.cuda.device(self.dev):
@@ -182,6 +191,8 @@ class AudioOut:
             if self.flac:
                 self.flac_block, self.flac_bound = flac_design(self.out_rate, flac_block)
                 self._flac = self._create(self._lib.fq3_flac_create, _lib.FlacConfig(self.out_rate, self.flac_block))
+                if self.lpc_order:
+                    _lib.check(self._lib.fq3_flac_set_option(self._flac, b"lpc_order", self.lpc_order))
         self.n_in = self.n_mid = self.n_out = self.n_samples = 0
         self.finished = False
         self._empty = torch.empty(0, dtype=torch.float32, device=self.dev)
@@ -243,7 +254,7 @@ class AudioOut:
     def header(self, total: int = 0) -> bytes:
         """``flac``: the stream header (``total`` samples; 0: unknown) that goes in front of everything ``push`` returns."""
         if not self.flac:
-            raise ValueError("only the flac encoding has a stream header")
+            raise ValueError("only the flac encodings have a stream header")
         return flac_header(self.out_rate, self.flac_block, total)
 
     def _push_flac(self, pcm: Optional[torch.Tensor], final: bool):
@@ -414,12 +425,12 @@ def _push_group(stages, pcms, finals):
                               [n for _p, n in ins], [int(r.final) for r in members], [base + r.off if r.need else None for r in members],
                               [r.need for r in members], sp)
             assert got == [r.need for r in members]
-        # FLAC: the s16 samples of the flac rows of one (rate, block size) go through ONE launch pair, into this buffer as well: frame
+        # FLAC: the s16 samples of the flac rows of one (rate, block size, lpc_order) go through ONE launch pair, into this buffer as well: frame
         # sizes depend on the data, so every row has room for its frames at their bound, behind the 8-byte count the device fills in
         flac_buckets: dict = {}
         for r in rows:
             if r.flac_off is not None:
-                flac_buckets.setdefault((r.st.out_rate, r.st.flac_block), []).append(r)
+                flac_buckets.setdefault((r.st.out_rate, r.st.flac_block, r.st.lpc_order), []).append(r)
         for members in flac_buckets.values():
             for i in range(0, len(members), GROUP_MAX):
                 part = members[i: i + GROUP_MAX]
@@ -455,7 +466,7 @@ def push_group(stages, pcms, finals) -> list:
     with ONE time-scale launch for the rows that have a speed and ONE resample + encode launch per distinct (rates, encoding) instead
     of one or two launches per row (``fq3_tsm_push_group`` / ``fq3_audio_out_push_group``, up to 32 rows a call).  The stages share a
     device and a stream; ``pcms[i]`` is a float32 device vector or None.  All outputs lie in one device buffer, the rows of a design
-    back to back.  The ``flac`` rows take their s16 half in the group launch and then ONE launch pair per (rate, block size)
+    back to back.  The ``flac`` rows take their s16 half in the group launch and then ONE launch pair per (rate, block size, lpc_order)
     (``fq3_flac_push_group``; section 4.20; a lone row keeps its ``fq3_flac_push``); as in ``push``, reading how many bytes their frames took synchronises the stream (once
     for the call)."""
     buf, rows, s = _push_group(stages, pcms, finals)

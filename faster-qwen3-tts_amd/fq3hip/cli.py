@@ -320,12 +320,18 @@ def cmd_voices(args):
         raise SystemExit(3)
 
 
+def _is_flac(encoding):
+    """``flac`` / ``flac_lpc``: the output is a FLAC file's bytes"""
+    from .audio_out import is_flac
+    return is_flac(encoding)
+
+
 def _write_output(path, audio, sr, args):
     """float32 audio as 16-bit PCM (as ever); what the output stage encoded (int16, G.711 bytes, a FLAC stream) as it is."""
     import os
     from .audio_io import write_wav, write_wav_encoded
     enc = getattr(args, "encoding", None)
-    if enc == "flac":
+    if _is_flac(enc):
         if not path.lower().endswith(".flac"):
             print(f"WARNING: {path} receives a FLAC stream; a .flac name would say so")
         os.makedirs(os.path.dirname(path) or ".", exist_ok=True)
@@ -361,7 +367,7 @@ def cmd_once(args, model=None, lines=None):
         audio, sr = synthesize_text_stream(model, args, _stdin_pieces(lines)) if text_stdin else synthesize(model, args, args.text)
     total = time.perf_counter() - start
     _write_output(args.output, audio, sr, args)
-    if getattr(args, "encoding", None) == "flac":              # bytes, not samples: the duration is inside the stream
+    if _is_flac(getattr(args, "encoding", None)):              # bytes, not samples: the duration is inside the stream
         print(f"Wrote {args.output} ({len(audio)} bytes of FLAC in {total:.2f}s)")
         return
     dur = len(audio) / sr if sr else 0.0
@@ -430,7 +436,7 @@ def cmd_serve(args, model=None, lines=None):
                 outs = [synthesize(model, args, t) for t in pending]
         total = time.perf_counter() - start
         for audio, sr in outs:
-            flac = getattr(args, "encoding", None) == "flac"
+            flac = _is_flac(getattr(args, "encoding", None))
             out_path = os.path.join(args.output_dir, f"out_{idx:04d}.{'flac' if flac else 'wav'}")
             idx += 1
             _write_output(out_path, audio, sr, args)
@@ -465,9 +471,10 @@ def build_parser():
                              "(default: the reference's 25-frame windowing)")
         sp.add_argument("--out-rate", type=int, default=None, metavar="HZ",
                         help="output sample rate, resampled on the device (e.g. 8000, 16000, 44100, 48000; default: the model's)")
-        sp.add_argument("--encoding", default=None, choices=["f32", "s16", "mulaw", "alaw", "flac"],
+        sp.add_argument("--encoding", default=None, choices=["f32", "s16", "mulaw", "alaw", "flac", "flac_lpc"],
                         help="sample encoding done on the device; mulaw / alaw write a G.711 WAV, flac a FLAC file of the s16 samples, "
-                             "compressed on the device (default: float32, written as 16-bit)")
+                             "compressed on the device, flac_lpc the same with LPC subframes: a smaller file "
+                             "(default: float32, written as 16-bit)")
         sp.add_argument("--speed", type=float, default=None, metavar="X",
                         help="speaking rate, 0.25 to 4.0, time-scaled on the device: duration changes, pitch does not (default: 1.0)")
         sp.add_argument("--gain-db", type=float, default=None, metavar="X",

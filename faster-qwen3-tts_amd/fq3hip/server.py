@@ -308,7 +308,8 @@ DEFAULT_LOUDNESS_TEXT = "The quick brown fox jumps over the lazy dog, and then i
 def create_app(model, voices: Dict[str, dict], default_voice: Optional[str] = None, scheduler: str = "lock", lanes: int = 8,
                chunk_size: int = 12, worker=None, prefix_cache_rows: int = 0, long_form=None, exact_streaming: bool = False,
                loudness: Optional[float] = None, loudness_text: str = DEFAULT_LOUDNESS_TEXT, limiter_db: Optional[float] = None,
-               level: Optional[float] = None, watermark_key: Optional[int] = None, watermark_strength: float = 0.1):
+               level: Optional[float] = None, watermark_key: Optional[int] = None, watermark_strength: float = 0.1,
+               flac_lpc: bool = False):
     """``worker``: a ready ``BatchWorker`` (or a stand-in with ``submit`` / ``submit_text``) instead of the one ``scheduler="batch"``
     would start.  ``prefix_cache_rows`` > 0: the model's prefix KV cache (``FasterQwen3TTS.enable_prefix_cache``) with that many rows:
     the engine's cache under the ``lock`` scheduler; under ``batch`` the ``BatchWorker`` started here creates the scheduler's own
@@ -330,7 +331,9 @@ def create_app(model, voices: Dict[str, dict], default_voice: Optional[str] = No
     not limit -- without ``limiter_db`` one warning says so).  Per-voice memory: when a stream ends with a valid measure, its last
     target gain is remembered under the voice's key (``voice_key``) and the voice's next request starts from it as
     ``initial_gain_db``; that reply carries ``X-Initial-Gain-Db`` and ``/health`` lists what was learned.  The memory is a dict in
-    this process, nothing is written to disk.  Not together with ``loudness``.  The leveller's defaults are not tuned on real voices."""
+    this process, nothing is written to disk.  Not together with ``loudness``.  The leveller's defaults are not tuned on real voices.
+    ``flac_lpc``: ``response_format="flac"`` is answered with the stage's ``flac_lpc`` encoding (LPC subframes: the same samples in
+    fewer bytes); the request schema does not change, ``/health`` reports the flag."""
     from fastapi import FastAPI, HTTPException
     from .long_form import LongFormSpec
     long_spec = long_form if long_form is not None else LongFormSpec()
@@ -433,7 +436,7 @@ def create_app(model, voices: Dict[str, dict], default_voice: Optional[str] = No
         path).  400 for an unknown encoding, a rate the resampler refuses or a speed outside [0.25, 4.0].  ``response_format="flac"``
         is the ``flac`` encoding of the stage (with the request's rate and speed); it is the whole answer's format, so a request that
         also names an ``encoding`` gets 400, and so does ``encoding="flac"`` under another format."""
-        from .audio_out import AudioOutSpec
+        from .audio_out import AudioOutSpec, is_flac
         if watermark_key is not None and req.speed != 1.0:
             raise HTTPException(status_code=400, detail="this server watermarks its audio, and the time-scale stage would run behind the "
                                                         "mark and defeat its detector: 'speed' must be 1")
@@ -442,13 +445,13 @@ def create_app(model, voices: Dict[str, dict], default_voice: Optional[str] = No
                 raise HTTPException(status_code=400, detail="response_format='flac' is an encoding of its own (the s16 samples, compressed "
                                                             "losslessly): leave 'encoding' out")
             try:
-                return AudioOutSpec(req.sample_rate, "flac", req.speed).validate(sample_rate)
+                return AudioOutSpec(req.sample_rate, "flac_lpc" if flac_lpc else "flac", req.speed).validate(sample_rate)
             except ValueError as exc:
                 raise HTTPException(status_code=400, detail=str(exc))
         if req.sample_rate is None and req.encoding is None and req.speed == 1.0:
             return None
         enc = (req.encoding or "s16").lower()
-        if enc == "flac":
+        if is_flac(enc):
             raise HTTPException(status_code=400, detail="encoding 'flac' is asked for with response_format='flac'")
         try:
             return AudioOutSpec(req.sample_rate, "s16" if enc == "f32" else enc, req.speed).validate(sample_rate)
@@ -648,6 +651,8 @@ def create_app(model, voices: Dict[str, dict], default_voice: Optional[str] = No
             out["prefix_cache"] = prefix_cache.stats()
         if exact_streaming:
             out["exact_streaming"] = True
+        if flac_lpc:
+            out["flac_lpc"] = True
         if loudness is not None:
             out["loudness"] = {"target_lufs": float(loudness),
                                "voices": {g["voice"]: {k: g[k] for k in ("gain_db", "lufs", "calibrated")} for g in gains.values()}}
@@ -744,6 +749,9 @@ def build_parser():
                         "gain, zero latency); both schedulers and the text sessions.  A voice's next request starts from the gain its last "
                         "stream ended with (X-Initial-Gain-Db; kept in memory only).  It does not limit: add --limiter-db.  Its defaults are "
                         "not tuned on real voices (default: off)")
+    p.add_argument("--flac-lpc", action="store_true",
+                   help="answer response_format=flac with LPC subframes (the stage's flac_lpc encoding): the same samples in fewer bytes "
+                        "(default: off)")
     return p
 
 
@@ -779,7 +787,8 @@ def main(argv=None):
     uvicorn.run(create_app(model, voices, default_voice, args.scheduler, args.lanes, args.chunk_size,
                            prefix_cache_rows=args.prefix_cache_rows, exact_streaming=args.exact_streaming, loudness=args.loudness,
                            loudness_text=args.loudness_text, limiter_db=args.limiter_db, level=args.level,
-                           watermark_key=args.watermark_key, watermark_strength=args.watermark_strength), host=args.host, port=args.port)
+                           watermark_key=args.watermark_key, watermark_strength=args.watermark_strength, flac_lpc=args.flac_lpc),
+                host=args.host, port=args.port)
 
 
 if __name__ == "__main__":

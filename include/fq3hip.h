@@ -657,7 +657,27 @@ int fq3_tsm_push_group(fq3_tsm* const* objs, int B, const float* const* pcm, con
  *     per partition the Rice parameter k in 0 .. 14 that minimises count (1 + k) + sum(u >> k), u = (r << 1) ^ (r >> 31), lowest k
  *     on ties; cost = 16 o + 6 + sum over partitions of (4 + that minimum); the cheapest (o, p), ties to the lower o, then the lower p;
  *   - that cost >= 16 n: VERBATIM.
- * A frame is therefore never longer than 2 n + 18 bytes. */
+ * A frame is therefore never longer than 2 n + 18 bytes.
+ *
+ * With the option lpc_order = M in 1 .. 8 (fq3_flac_set_option; 0, the default, is the rule above and its kernels) a block of
+ * n >= 64 samples x also has LPC candidates; CONSTANT and the FIXED candidates are as above, a shorter (last) block is fixed-only.
+ *   - Window, integers only: t = n / 4; w[i] = 32768 for t <= i < n - t, else 32768 - floor(32768 d d / ((t + 1) (t + 1))) with
+ *     d = t - i at the front and d = i - (n - 1 - t) at the back (64 bits); y[i] = (x[i] w[i] + 2048) >> 12, arithmetic.
+ *   - R[l] = sum_i y[i] y[i + l], l = 0 .. M, in int64: exact, below 2^53, so exact as doubles too.
+ *   - Levinson-Durbin in IEEE double, every operation rounded on its own (no fused multiply-add), in this order.  err = R[0]; for
+ *     i = 0 .. M - 1, while err is finite and > 0:  acc = R[i + 1];  for j = 0 .. i - 1 in order: acc = acc - a[j] * R[i - j];
+ *     k = acc / err;  new[j] = a[j] - k * a[i - 1 - j] (j < i, from the old a), new[i] = k;  a = new;  err = err * (1 - k * k).
+ *     a[0 .. i] then predicts at order o = i + 1: x^[m] = sum_j a[j] x[m - 1 - j].
+ *   - Quantisation to 12 bits without error feedback: cmax = max |a[j]|; order o is a candidate when every a[j] is finite,
+ *     cmax != 0 and s = min(15, 11 - e) >= 0, where frexp(cmax) = (m, e), m in [0.5, 1).  q[j] = rint(a[j] * 2^s), ties to even,
+ *     clamped to [-2048, 2047].
+ *   - Residual r[m] = x[m] - ((sum_j q[j] x[m - 1 - j]) >> s) for m >= o, arithmetic shift; the sum stays below 2^29 (int32).
+ *   - LPC candidates: the orders o in 1 .. M that exist, with the partition orders and Rice parameters of the FIXED candidates;
+ *     cost = 16 o + 9 + 12 o + 6 + sum over partitions of (4 + minimum)  (9: four bits of precision - 1, five of s).
+ *   - The cheapest candidate of all; ties go to FIXED before LPC, then to the lower o, then to the lower p; cost >= 16 n: VERBATIM.
+ *     The frame bound does not change.
+ * An LPC subframe is standard FLAC: the byte (0x20 | (o - 1)) << 1, o warm-up samples of 16 bits, 4 bits 11, 5 bits s, o
+ * coefficients of 12 bits (two's complement, q[0] first), then the residual as for FIXED.  The stream stays in the FLAC subset. */
 typedef struct fq3_flac fq3_flac;
 typedef struct fq3_flac_config { int sample_rate, block_size; } fq3_flac_config;      /* block_size 0: the default */
 /* host only: the block size in force and the frame bound 2 * block + 18 */
@@ -672,6 +692,9 @@ int fq3_flac_create(const fq3_flac_config* cfg, fq3_flac** out);
 int fq3_flac_destroy(fq3_flac* f);                           /* NULL -> 0 */
 /* a new utterance on the same object (nothing is enqueued) */
 int fq3_flac_reset(fq3_flac* f, void* stream);
+/* host only: the one option is "lpc_order", 0 .. 8 (above).  NULL, another name or value: FQ3_EINVAL.  Between an utterance's first
+ * push and the next fq3_flac_reset: FQ3_ESTATE.  The option survives fq3_flac_reset. */
+int fq3_flac_set_option(fq3_flac* f, const char* name, int value);
 /* pcm: n_in device int16 (n_in may be 0), the next samples of the stream; final != 0: the stream ends with them.  out: device bytes
  * at any alignment.  *n_frames (host) = the frames this push completes, known before the launch; capacity_bytes below
  * *n_frames * max_frame_bytes: FQ3_EINVAL and nothing is launched.  The frames are written back to back from out[0];
@@ -693,7 +716,7 @@ int fq3_flac_push(fq3_flac* f, const int16_t* pcm, int64_t n_in, int final, uint
  *                    the first offending row is returned, the message names the row, nothing is launched and no object has moved.
  *   Limits.          B == 0: returns 0, does nothing.  B < 0, B > FQ3_STAGE_GROUP_MAX, a null array, a null object or the same object
  *                    twice in one call: FQ3_EINVAL.
- *   Shared design.   All objects have the same (sample_rate, block size), else FQ3_EINVAL.
+ *   Shared design.   All objects have the same (sample_rate, block size) and the same lpc_order, else FQ3_EINVAL.
  *                    These, and every check above, are answered before any HIP call.
  *   Empty rows.      A row that completes no frame costs no encode workgroup (one if it has a tail to copy) and one gather workgroup
  *                    that sets *n_bytes_dev[b] to 0.

@@ -27,7 +27,13 @@ row), each repeat between its own event pair.  (b) The whole chain with the rows
 rows, with the group entry and with the per-row launch sequence it replaces (host clock; the call ends in a synchronise).  The forms
 alternate in three rounds; the medians, every round's median and their spread are written to profiles/flac_group.json.  The forms' bytes
 are compared before anything is timed.
-usage: audio_out_probe.py [--speed | --encoding flac [--recordings DIR | --group B] | --group B] [runs=100] [out.json]"""
+With --encoding flac_lpc [--group B]: the FLAC stage alone with LPC subframes (lpc_order 8) beside the fixed-only stage, timed in one
+session in alternating rounds (one fq3_flac_push, or one fq3_flac_push_group of B rows), with the vocoder's chunk decode as the yardstick;
+with --recordings DIR the two reference encoders' bytes over every integer-PCM WAV under DIR (CPU).  All write profiles/flac_lpc.json,
+each its own key.
+
+usage: audio_out_probe.py [--speed | --encoding flac [--recordings DIR | --group B] | --encoding flac_lpc [--recordings DIR | --group B] |
+                           --group B] [runs=100] [out.json]"""
 import json
 import os
 import statistics
@@ -448,6 +454,107 @@ def main_flac_group(N, argv):
     print(json.dumps(res, indent=1))
 
 
+def _flac_lpc_ratio_of_file(path):
+    import numpy as np
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import _flac_lpc_ref as L
+    import _flac_ref as R
+    from fq3hip import audio_io
+    audio, sr = audio_io.read_wav(path)
+    x = np.frombuffer(audio_io.to_pcm16(audio), dtype="<i2")
+    stats = []
+    lpc, fixed = 42 + len(L.encode_frames(x, sr, 0, 8, stats)), len(R.encode(x, sr))
+    orders = [s[1] for s in stats if s[0] == "lpc"]
+    return {"file": os.path.basename(path), "sample_rate": sr, "seconds": round(len(x) / sr, 2), "s16_bytes": 2 * len(x),
+            "fixed_bytes": fixed, "lpc_bytes": lpc, "fixed_ratio": round(fixed / (2 * len(x)), 4), "lpc_ratio": round(lpc / (2 * len(x)), 4),
+            "frames": len(stats), "lpc_frames_by_order": [orders.count(o) for o in range(1, 9)]}
+
+
+def main_flac_lpc_recordings(root, out_path):
+    """CPU side: the LPC reference encoder (M = 8) and the fixed-only one over the same recordings, in one run (the device writes the
+    same bytes as either: tests/test_gpu_flac_lpc.py, tests/test_gpu_flac.py)"""
+    from concurrent.futures import ProcessPoolExecutor
+    from fq3hip import audio_io
+    readable = []
+    for d, _, files in sorted(os.walk(root)):
+        for p in (os.path.join(d, f) for f in sorted(files) if f.lower().endswith(".wav")):
+            try:
+                audio_io.read_wav(p)
+                readable.append(p)
+            except ValueError:
+                pass
+    with ProcessPoolExecutor(max_workers=min(8, os.cpu_count() or 1)) as ex:
+        rows = list(ex.map(_flac_lpc_ratio_of_file, readable))
+    total = lambda k: sum(r[k] for r in rows)
+    med = lambda k: sorted(r[k] for r in rows)[len(rows) // 2]
+    _merge(out_path, {"cpu_reference_encoders_over_recordings": {
+        "side": "CPU (numpy reference encoders, lpc_order 8 and fixed-only; byte-identical to the device stage by the GPU tests)",
+        "n_files": len(rows), "fixed_ratio_total": round(total("fixed_bytes") / total("s16_bytes"), 4),
+        "lpc_ratio_total": round(total("lpc_bytes") / total("s16_bytes"), 4), "fixed_ratio_median": med("fixed_ratio"),
+        "lpc_ratio_median": med("lpc_ratio"), "lpc_ratio_min": min(r["lpc_ratio"] for r in rows),
+        "lpc_ratio_max": max(r["lpc_ratio"] for r in rows), "lpc_over_fixed_total": round(total("lpc_bytes") / total("fixed_bytes"), 4),
+        "files_where_lpc_is_not_smaller": [r["file"] for r in rows if r["lpc_bytes"] >= r["fixed_bytes"]], "files": rows}})
+
+
+def main_flac_lpc(argv, B):
+    """The FLAC stage ALONE with lpc_order 8 beside the fixed-only stage (the parent commit's kernels, unchanged) in the same session: B
+    rows (1: fq3_flac_push; more: ONE fq3_flac_push_group), one streaming chunk of s16 samples each, pushed into running streams; device
+    time between events, a warm-up, three alternating rounds, medians; the vocoder's chunk decode of B rows is the yardstick."""
+    import ctypes as C
+    runs = max(20, int(argv[0])) if argv else 50
+    out_path = argv[1] if len(argv) > 1 else os.path.join(ROOT, "profiles", "flac_lpc.json")
+    g = torch.Generator().manual_seed(3)
+    n = 8 * SAMPLES_PER_FRAME
+    lib = ao._lib.load()
+    t = torch.arange(n, dtype=torch.float64) / 24000.0
+    voiced = sum(0.25 / h * torch.sin(2 * torch.pi * 140.0 * h * t) for h in range(1, 9)) * torch.exp(-3.0 * (t % 0.16))
+    rows = [ao.AudioOut(ao.AudioOutSpec(None, "s16"), 24000, "cuda").push(
+        (voiced * (0.5 + 0.5 * b / B) + 0.003 * torch.randn(n, generator=g)).float().cuda(), final=True) for b in range(B)]
+    block, bound = ao.flac_design(24000)
+    cap = (n // block + 1) * bound
+    slot = (8 + cap + 7) // 8 * 8                                 # a row's int64 byte count, then its frames
+    pcm = (C.c_void_p * B)(*[x.data_ptr() for x in rows])
+    lens, finals, caps, got = (C.c_int64 * B)(*([n] * B)), (C.c_int * B)(*([0] * B)), (C.c_int64 * B)(*([cap] * B)), (C.c_int64 * B)()
+    forms, nbytes = {}, {}
+    for enc in ("flac", "flac_lpc"):
+        objs = [ao.AudioOut(ao.AudioOutSpec(None, enc), 24000, "cuda") for _ in range(B)]
+        buf = torch.zeros(B * slot, dtype=torch.uint8, device="cuda")
+        outs = [buf.data_ptr() + b * slot for b in range(B)]
+        hs, o_ptr, n_ptr = (C.c_void_p * B)(*[st._flac.value for st in objs]), (C.c_void_p * B)(*[p + 8 for p in outs]), (C.c_void_p * B)(*outs)
+
+        def push(objs=objs, hs=hs, o_ptr=o_ptr, n_ptr=n_ptr):
+            s = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+            if B == 1:
+                assert lib.fq3_flac_push(hs[0], pcm[0], n, 0, o_ptr[0], cap, C.byref(C.c_int64()), n_ptr[0], s) == 0
+            else:
+                assert lib.fq3_flac_push_group(hs, B, pcm, lens, finals, o_ptr, caps, got, n_ptr, s) == 0
+        forms[enc] = (push, objs, buf)
+    for push, _, _ in forms.values():
+        for _ in range(10):
+            push()
+    torch.cuda.synchronize()
+    samples = {k: [] for k in forms}
+    for _round in range(3):
+        for k, (push, _, buf) in forms.items():
+            pairs = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(runs)]
+            for e0, e1 in pairs:
+                e0.record(); push(); e1.record()
+            torch.cuda.synchronize()
+            samples[k].append([e0.elapsed_time(e1) for e0, e1 in pairs])
+            nbytes[k] = int(sum(int(buf[b * slot: b * slot + 8].view(torch.int64).item()) for b in range(B)))
+    voc_single, voc_stream = vocoder_chunk(g, runs) if B == 1 else vocoder_group(g, B, runs)
+    res = {"device": torch.cuda.get_device_name(0), "rows": B, "runs_per_round": runs, "rounds": 3, "warmup": 10, "n_in_per_row": n,
+           "block": block, "input": "speech-like: decaying harmonics of 140 Hz, noise at -50 dB", "how": "device events around the call",
+           "vocoder_bf16x2_chunk_ms": {"median_single_call": round(voc_single, 4), "back_to_back_per_call": round(voc_stream, 4)}, "forms": {}}
+    for k, rs in samples.items():
+        per_round = [statistics.median(r) for r in rs]
+        med = statistics.median(v for r in rs for v in r)
+        res["forms"][k] = {"median_ms": round(med, 4), "per_round_ms": [round(v, 4) for v in per_round],
+                           "spread_ms": round(max(per_round) - min(per_round), 4), "fraction_of_vocoder_chunk": round(med / voc_single, 4),
+                           "bytes_of_the_last_push": nbytes[k], "s16_bytes": 2 * n * B}
+    _merge(out_path, {"time_single_push" if B == 1 else f"time_group_of_{B}": res})
+
+
 def vocoder_group(g, B, runs):
     """the yardstick for a group: (median single call, back to back per call) ms of the bf16x2 vocoder's windowed chunk decode of B rows"""
     from fq3hip.codec import HipSpeechTokenizer
@@ -468,13 +575,20 @@ def main():
         B, rest = int(args[i + 1]), args[:i] + args[i + 2:]
         if "--encoding" in rest:
             j = rest.index("--encoding")
-            assert rest[j + 1] == "flac", "--encoding flac is the only encoding with a probe of its own"
+            if rest[j + 1] == "flac_lpc":
+                return main_flac_lpc(rest[:j] + rest[j + 2:], B)
+            assert rest[j + 1] == "flac", "--encoding flac and flac_lpc are the only encodings with a probe of their own"
             return main_flac_group(B, rest[:j] + rest[j + 2:])
         return main_group(B, rest)
     if "--encoding" in args:
         i = args.index("--encoding")
-        assert args[i + 1] == "flac", "--encoding flac is the only encoding with a probe of its own"
+        assert args[i + 1] in ("flac", "flac_lpc"), "--encoding flac and flac_lpc are the only encodings with a probe of their own"
         rest = args[:i] + args[i + 2:]
+        if args[i + 1] == "flac_lpc":
+            if "--recordings" in rest:
+                j = rest.index("--recordings")
+                return main_flac_lpc_recordings(rest[j + 1], os.path.join(ROOT, "profiles", "flac_lpc.json"))
+            return main_flac_lpc(rest, 1)
         if "--recordings" in rest:
             j = rest.index("--recordings")
             root, rest = rest[j + 1], rest[:j] + rest[j + 2:]

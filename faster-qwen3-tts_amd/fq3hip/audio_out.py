@@ -519,6 +519,12 @@ class GroupCopy:
         return out
 
 
+def behind_header(stage, a: np.ndarray, total: int = 0) -> np.ndarray:
+    """``flac``: the bytes ``a`` with ``stage``'s stream header in front of them -- a stream's first chunk (``total`` 0: the length is
+    not known yet), or a whole file (``total``: its sample count)."""
+    return np.concatenate([np.frombuffer(stage.header(total), dtype=np.uint8), a])
+
+
 def push_group_host(stages, pcms, finals) -> list:
     """``push_group`` with the results on the host -- ``[stages[i].push_host(pcms[i], finals[i]) for i]`` -- all rows in one pinned
     copy and one synchronisation (``GroupCopy`` is the form that does not wait)."""

@@ -19,7 +19,7 @@ import numpy as np
 import torch
 
 from .loudness import LoudnessSession
-from .stream_groups import StreamGroups, runs_of, window_plan
+from .stream_groups import window_plan
 
 logger = logging.getLogger(__name__)
 
@@ -48,7 +48,8 @@ class _Encoded:
         """the encoded utterance (waits for the copy); ``flac``: the whole file, its header carries the sample count"""
         a, st = self.copy.rows()[self.index], self.stage
         if st.flac:
-            a = np.concatenate([np.frombuffer(st.header(st.n_samples), dtype=np.uint8), a])
+            from .audio_out import behind_header
+            a = behind_header(st, a, st.n_samples)
         else:
             a = a.copy()
         self.give(st)
@@ -620,7 +621,8 @@ class StreamingVocoder:
             out = st.push_host(wav, final)
         if st.flac and not self.header_sent:
             # a FLAC stream: the utterance's first chunk starts with the stream header (length unknown); the chunks are bytes
-            out, self.header_sent = np.concatenate([np.frombuffer(st.header(), dtype=np.uint8), out]), True
+            from .audio_out import behind_header
+            out, self.header_sent = behind_header(st, out), True
         return out, st.out_rate
 
     def flush(self):
@@ -731,18 +733,11 @@ class StreamingVocoder:
             rc = self.ref_codes
             inp = self._cat([self._ref_on(flat.device), flat], ready_event) if rc is not None else flat
             ref_len = rc.shape[0] if rc is not None else 0
-            if self.side is not None:
-                # model.py:1095-1100 without materialising what is thrown away: audio[cut:][prev_len:]
-                n_audio = self.tok.num_samples_total(inp.shape[0])
-                cut = int(ref_len / max(inp.shape[0], 1) * n_audio) if ref_len else 0
-                new_audio, sr = self._vocode(inp, cut + self.prev_len, ready_event)
-                gen_len = n_audio - cut
-            else:
-                audio, sr = self._vocode(inp, 0, ready_event)
-                if ref_len:
-                    audio = audio[int(ref_len / max(inp.shape[0], 1) * len(audio)):]
-                new_audio = audio[self.prev_len:]
-                gen_len = len(audio)
+            audio, sr = self._vocode(inp, 0, ready_event)
+            if ref_len:
+                audio = audio[int(ref_len / max(inp.shape[0], 1) * len(audio)):]
+            new_audio = audio[self.prev_len:]
+            gen_len = len(audio)
             self.prev_len = gen_len
             if n_total >= self.min_cal:
                 self.spf = gen_len / n_total
@@ -1744,15 +1739,19 @@ class FasterQwen3TTS:
         if pool is not None and len(pool) < self.STAGE_POOL_MAX and not any(st is other for other in pool):
             pool.append(st)
 
+    def _out_rate(self, outputs, rid) -> int:
+        """the rate utterance ``rid`` of a batch leaves at: its output spec's (``outputs``: :meth:`_batch_outputs`), else the model's"""
+        return self.sample_rate if outputs is None or outputs[rid] is None else outputs[rid].out_rate(self.sample_rate)
+
     def _one_shot_output(self, wav, spec=None) -> Tuple[np.ndarray, int]:
         """A whole utterance's waveform (device tensor or host array) through the output stage of the open context (or of ``spec``)."""
-        from .audio_out import AudioOut
+        from .audio_out import AudioOut, behind_header
         dev = torch.device(self.device) if not isinstance(self.device, torch.device) else self.device
         stage = AudioOut(self._audio_spec if spec is None else spec, self.sample_rate, wav.device if hasattr(wav, "is_cuda") and wav.is_cuda else dev)
         x = wav.flatten().float() if hasattr(wav, "cpu") else torch.from_numpy(np.ascontiguousarray(wav, dtype=np.float32).reshape(-1))
         out = stage.push_host(x.to(stage.dev), final=True)
         if stage.flac:                 # a whole FLAC file: its header carries the sample count
-            out = np.concatenate([np.frombuffer(stage.header(stage.n_samples), dtype=np.uint8), out])
+            out = behind_header(stage, out, stage.n_samples)
         return out, stage.out_rate
 
     @staticmethod
@@ -2058,7 +2057,6 @@ class FasterQwen3TTS:
         voc.device_only = bool(device_audio)
         if outputs is not None:
             voc.outputs, voc.stages = {i: sp for i, sp in enumerate(outputs) if sp is not None}, (self._take_stage, self._give_stage)
-        rate_of = lambda rid: self.sample_rate if outputs is None or outputs[rid] is None else outputs[rid].out_rate(self.sample_rate)  # noqa: E731
 
         def nothing(rid):
             """an utterance without a single frame: one zero sample, through its stage if it has one"""
@@ -2068,7 +2066,7 @@ class FasterQwen3TTS:
             if voc.stream is not None:
                 voc.stream.wait_stream(torch.cuda.current_stream(voc.dev))
             a = voc._encode_group([rid], [z])[0].array()
-            return [a], rate_of(rid)
+            return [a], self._out_rate(outputs, rid)
         if self._loud is not None:
             self._loud.begin(count)
         if self._levelling() and not device_audio:
@@ -2114,7 +2112,7 @@ class FasterQwen3TTS:
                 out[rid] = ([a], voc.sample_rate)
             return out, voc
         for rid, a in voc.collect():
-            out[rid] = ([a], voc.sample_rate if outputs is None else rate_of(rid))
+            out[rid] = ([a], voc.sample_rate if outputs is None else self._out_rate(outputs, rid))
         if verify is not None:
             out = [o + (voc.score(rid),) for rid, o in enumerate(out)]
             voc.verify, voc.score_rows, voc.scores = None, None, {}
@@ -2144,245 +2142,16 @@ class FasterQwen3TTS:
         if not device_audio:
             self._refuse_batch_audio_output()
             self._refuse_batch_watermark()
-        gain = None if device_audio else self._gain_tensor()       # (long form multiplies behind the join)
-        limit = None if device_audio else getattr(self, "_limit", None)      # (and limits there, as one stream)
-        lvl = None if device_audio else getattr(self, "_lvl", None)         # (and levels there, likewise)
         if seeds is not None:
             # the ``seeds=`` keyword of the public entry points is expanded HERE and in _run_batch_full, nowhere else; a caller that
             # builds its own requests (``rounds``) seeds them itself
             if rounds is not None or count is None:
                 raise ValueError("seeds= goes with `prepared` and its `count`; requests made by `rounds` carry their own seed")
             seeds = expand_seeds(seeds, count)
-        meta: dict = {}
-        vocs, n_chunks = {}, {}
-        dec = self._batch_decoder(lanes)
-        # ``batch_first_wave_streaming`` (attribute, default None = one request per lane): requests prepared and prefilled in front of the
-        # first frame, the others joining at the following frame boundaries.  MEASURED (profiles/r05_ttfa_first_wave.txt): a smaller
-        # first wave does not buy its members a lower latency -- the prefills of the followers run beside their first frames and
-        # stretch them (128 lanes: p25 305 ms / p50 395 ms at a wave of 32 against 340 ms for everybody at once) -- so the default stays.
-        dec.first_wave = getattr(self, "batch_first_wave_streaming", None)
-        pairs = rounds(dec, meta) if rounds is not None else [self._batch_feed(prepared, gen_kwargs, len(dec.lanes), meta, dec.first_wave, seeds)]
-        tok = self.model.model.speech_tokenizer
-        side = self._vocoder_stream(tok)
-        batched = side is not None and hasattr(tok, "decode_tensor_batch")
-        # chunks of different utterances that need the SAME decode shape (the first chunks of lanes that started together: reference + 8
-        # frames in, the last 8 frames' samples out) go through one batched launch set on the vocoder stream, STREAM_GROUP at a time.
-        # Round 6: a group is LAUNCHED as soon as it is full -- while the host still prepares the next group's inputs -- every group's
-        # waveform goes to pinned host memory behind its launch set, and the groups are handed out one by one as their copies land: a
-        # wave of 128 first chunks (four groups of 32) used to be prepared as a whole, launched group by group with a host wait after
-        # each, and reached the caller all at once after the last group.  The bookkeeping -- the jobs of a poll ``[rid, meta, audio |
-        # None, (codes_in, first, ev, ...) | None]``, their classes, the launches made -- is ``stream_groups.StreamGroups``; ``launch`` and
-        # ``collect`` below are the device work it calls.  Per utterance the order of the events is kept BY THE LAUNCHES, in both modes: a
-        # launch pushes its members' own stages and stream states, so a chunk never joins a class that would launch in front of an
-        # earlier chunk of its utterance that still waits (lanes re-used at staggered frames produce that; the classes up to that
-        # chunk's are launched first).  Groups are handed out in launch order, markers without audio come last.
-
-        def launch(key, part):
-            _T, first, pf_len = key
-            for j in part:
-                if j[3][2] is not None:
-                    side.wait_event(j[3][2])
-                else:
-                    side.wait_stream(torch.cuda.current_stream(torch.device(self.device)))
-            with torch.cuda.stream(side):
-                exact = pf_len == "exact"
-                pfs = [j[3][3] for j in part] if not exact and pf_len > 0 else None      # (phase 1 behind ICL references: the voices' cached front-end states)
-                if exact:
-                    # exact mode: the group's stream states take their new frames in one push; `first` = samples in front of an ICL cut's floor
-                    wav = tok.stream_push([j[3][4] for j in part], torch.stack([j[3][0] for j in part]))[:, first:]
-                elif len(part) == 1:
-                    wav = (tok.decode_tensor(part[0][3][0], first, prefix=pfs[0]) if pfs else tok.decode_tensor(part[0][3][0], first)).reshape(1, -1)
-                else:
-                    stacked = torch.stack([j[3][0] for j in part])
-                    wav = tok.decode_tensor_batch(stacked, first, prefixes=pfs) if pfs else tok.decode_tensor_batch(stacked, first)
-                wav = wav.float()
-                if gain is not None:
-                    from .loudness import apply_gain
-                    wav = apply_gain(wav.contiguous(), gain, side)
-                finals = [bool(j[1].get("is_final")) for j in part]
-                # a poll that completes two chunks of one shape puts an utterance into a part twice; a stage is pushed once per group
-                # call, so such a part is cut into consecutive runs in which every utterance appears once (nearly always: one run)
-                runs = runs_of(part)
-                if lvl is not None:
-                    # every utterance's own leveller takes its row and writes a row of the same length: the group stays one tensor,
-                    # and the rows of a run go through ONE meter launch, ONE target launch and ONE multiply
-                    from .leveller import push_group as level_group
-                    rows, wav = wav, torch.empty(wav.shape, dtype=torch.float32, device=wav.device)
-                    for run in runs:
-                        level_group([vocs[part[k][0]].level_take() for k in run], [rows[k] for k in run], [finals[k] for k in run],
-                                    outs=[wav[k] for k in run])
-                        for k in run:
-                            if finals[k]:
-                                vocs[part[k][0]].level_release()
-                host = landed = encoded = None
-                staged = [k for k, j in enumerate(part) if vocs[j[0]].output is not None]
-                # rows whose length changes lie back to back in device buffers: ``place[k]`` is (offset in the buffers' concatenation, count)
-                whole, bufs, place = wav, [], [None] * len(part)
-                marked_rows = [k for k, j in enumerate(part) if vocs[j[0]].mark_spec is not None]
-                if marked_rows:
-                    # every marked utterance's own watermark takes its row, under its own key: ONE launch per run.  A row comes back
-                    # shorter by the 256 to 511 samples the mark holds back, or longer at the end; rows without a mark pass untouched
-                    from .watermark import _push_group as mark_group
-                    wav = [whole[k] for k in range(len(part))]
-                    for run in runs:
-                        rows = [k for k in run if k in marked_rows]
-                        if not rows:
-                            continue
-                        buf, spans = mark_group([vocs[part[k][0]].mark_take() for k in rows], [whole[k] for k in rows],
-                                                [finals[k] for k in rows])
-                        for k, (off, cnt) in zip(rows, spans):
-                            wav[k], place[k] = buf[off:off + cnt], (sum(int(b.numel()) for b in bufs) + off, cnt)
-                            if finals[k]:
-                                vocs[part[k][0]].mark_release()
-                        bufs.append(buf)
-                if limit is not None:
-                    # every utterance's own limiter takes its row: the rows come back shorter by what it holds back, or longer at the
-                    # end.  ONE launch per run; the rows lie back to back in the run's device buffer
-                    from .limiter import _push_group as limit_group
-                    src, wav, bufs, place = wav, [None] * len(part), [], [None] * len(part)
-                    for run in runs:
-                        buf, spans, _s = limit_group([vocs[part[k][0]].limit_take() for k in run], [src[k] for k in run],
-                                                     [finals[k] for k in run])
-                        for k, (off, cnt) in zip(run, spans):
-                            wav[k], place[k] = buf[off:off + cnt], (sum(int(b.numel()) for b in bufs) + off, cnt)
-                            if finals[k]:
-                                vocs[part[k][0]].limit_release()
-                        bufs.append(buf)
-                if staged:
-                    # the rows with an output spec: one time-scale launch, one resample + encode launch per design, one pinned copy --
-                    # per run, as the stages in front: a stage is pushed once per group call
-                    from .audio_out import GroupCopy
-                    encoded = []
-                    for run in runs:
-                        rows = [k for k in run if k in staged]
-                        if rows:
-                            encoded.append((rows, GroupCopy([vocs[part[k][0]]._stage() for k in rows], [wav[k] for k in rows],
-                                                            [finals[k] for k in rows])))
-                if limit is not None or marked_rows:
-                    # the rows without an output spec: ONE pinned buffer behind one copy per run, and ONE event.  Without a limiter the
-                    # rows that have no mark kept their place in the group's tensor: they alone are gathered and follow in one more copy
-                    host = [None] * len(part)
-                    if len(staged) < len(part):
-                        plain = [k for k in range(len(part)) if place[k] is None and k not in staged]
-                        held, width = sum(int(b.numel()) for b in bufs), int(whole.shape[1])
-                        pinned, at = torch.empty(held + len(plain) * width, dtype=torch.float32, pin_memory=True), 0
-                        for buf in bufs:
-                            pinned[at:at + int(buf.numel())].copy_(buf, non_blocking=True)
-                            at += int(buf.numel())
-                        if plain:
-                            pinned[held:].copy_(whole[plain].reshape(-1), non_blocking=True)
-                        slot = {k: held + i * width for i, k in enumerate(plain)}
-                        host = [None if k in staged else pinned[place[k][0]:place[k][0] + place[k][1]] if place[k] is not None
-                                else pinned[slot[k]:slot[k] + width] for k in range(len(part))]
-                    landed = torch.cuda.Event()
-                    landed.record(side)
-                elif not device_audio and len(staged) < len(part):
-                    host = torch.empty(wav.shape, dtype=wav.dtype, pin_memory=True)
-                    host.copy_(wav, non_blocking=True)
-                    landed = torch.cuda.Event()
-                    landed.record(side)
-                elif staged:
-                    landed = encoded[-1][1].event              # (one stream: the last run's copy lands last)
-            return host, landed, wav, encoded
-
-        def collect(part, handle):
-            host, landed, wav, encoded = handle
-            if landed is None:
-                arr = wav                                      # device rows: whoever takes them works on the vocoder stream
-            else:
-                landed.synchronize()
-                arr = ([None if h is None else h.numpy() for h in host] if isinstance(host, list) else
-                       host.numpy() if host is not None else [None] * len(part))
-            for k, j in enumerate(part):
-                j[2] = arr[k]
-            for rows, copy in encoded or ():
-                for k, a in zip(rows, copy.rows()):
-                    v = vocs[part[k][0]]
-                    if v.stage.flac and not v.header_sent:
-                        # a FLAC stream: the utterance's first chunk starts with the stream header (length unknown)
-                        a, v.header_sent = np.concatenate([np.frombuffer(v.stage.header(), dtype=np.uint8), a]), True
-                    part[k][2] = a
-                    if part[k][1].get("is_final"):
-                        self._give_stage(v.stage)
-
-        # exact mode: (new codes, drop, ev, None, stream state, frames before the push) -- the class is (min(F, ctx_max), n_new) and the
-        # drop, so every steady-state chunk of every lane falls into one class; a state is pushed once per call, so the k-th chunk an
-        # utterance adds in a poll goes into the k-th generation of the class (``StreamGroups.key_of``)
-        groups = StreamGroups(launch, collect, _SideVocoder.STREAM_GROUP, getattr(tok, "stream_ctx_max", None))
-        self._stream_group_stats = groups.stats         # the counters of the newest run (jobs, launches, order_launches), nothing else kept
-        add_job, launch_open, flush = groups.add, groups.launch_open, groups.flush
-
-        def out(r, m):
-            if stamp is not None:
-                stamp(r, m)
-            return m
-
-        rate_of = lambda r: self.sample_rate if outputs is None or outputs[r] is None else outputs[r].out_rate(self.sample_rate)  # noqa: E731
-
-        def marked(events):
-            if not group_marks:
-                return events
-            # the whole poll is collected before its first event goes out: with ``device_audio`` nothing is copied, so nothing is
-            # waited for; a caller that lands copies (``flush`` hands groups out as they land) would wait for the last of them here
-            events = list(events)
-            for i, ev in enumerate(events):
-                ev[1]["group_end"] = i == len(events) - 1
-            return events
-
-        for head, source in pairs:
-          for rid, codes, info in dec.run(head, source=source, chunk_frames=chunk_size):
-            if rid not in vocs:
-                vocs[rid] = (StreamingVocoder(tok, meta[rid], chunk_size, self.device, side, **self._exact_kw()) if device_audio
-                             else self.streaming_vocoder(meta[rid], chunk_size))
-                if outputs is not None and outputs[rid] is not None:
-                    vocs[rid].output, vocs[rid].stage = outputs[rid], self._take_stage(outputs[rid], side)
-                if marks is not None and marks[rid] is not None:
-                    vocs[rid].mark_spec = marks[rid]
-                    vocs[rid].mark_pool = self.__dict__.setdefault("_mark_pools", {}).setdefault(marks[rid], [])
-                n_chunks[rid] = 0
-            ev = info.pop("codes_ready_event", None)
-            final = bool(info.get("is_final"))
-            more = int(getattr(dec, "more_in_poll", 0))
-            out_meta = dict(chunk_index=n_chunks[rid], total_steps_so_far=int(info.get("total_steps_so_far", 0)),
-                            is_final=final, chunk_steps=0 if codes is None else int(codes.shape[0]))
-            if codes is not None and codes.shape[0] > 0:
-                if batched:
-                    inp, first = vocs[rid].prepare(codes, ev)
-                    if vocs[rid].exact:
-                        add_job([rid, out_meta, None, (inp, first, ev, None, vocs[rid].cstream, vocs[rid].frames_before)])
-                    else:
-                        add_job([rid, out_meta, None, (inp, first, ev, vocs[rid].last_prefix)])
-                else:
-                    staged = limit is not None or lvl is not None or vocs[rid].output is not None or vocs[rid].mark_spec is not None
-                    audio, _sr = vocs[rid].push(codes, ev, final=final) if staged else vocs[rid].push(codes, ev)
-                    if final and vocs[rid].output is not None:
-                        self._give_stage(vocs[rid].stage)
-                    add_job([rid, out_meta, audio, None])
-                n_chunks[rid] += 1
-            elif final:
-                tail = np.zeros(1 if codes is None else 0, dtype=np.float32)
-                if lvl is not None and vocs[rid].level is not None:
-                    launch_open()                                  # the utterance's chunks that still wait end its leveller's stream
-                    with (contextlib.nullcontext() if side is None else torch.cuda.stream(side)):
-                        vocs[rid].level_release()
-                if vocs[rid].output is not None:
-                    # what the output stage (and a limiter in front of it) held back leaves as this event's audio
-                    launch_open()
-                    tail, _sr = vocs[rid].flush()
-                    if vocs[rid].stage.flac and not vocs[rid].header_sent:
-                        tail, vocs[rid].header_sent = np.concatenate([np.frombuffer(vocs[rid].stage.header(), dtype=np.uint8), tail]), True
-                    self._give_stage(vocs[rid].stage)
-                elif (limit is not None and vocs[rid].limit is not None) or vocs[rid].mark_spec is not None:
-                    launch_open()                                  # the utterance's chunks that still wait go in front of its tail
-                    held, _sr = vocs[rid].flush()
-                    tail = held if len(held) else tail
-                add_job([rid, out_meta, tail, None])
-                n_chunks[rid] += 1
-            if more <= 0:
-                for r, m, audio, _job in marked(flush()):
-                    yield r, audio, rate_of(r), out(r, m)
-          for r, m, audio, _job in marked(flush()):
-            yield r, audio, rate_of(r), out(r, m)
+        # the run itself -- the event loop, and the device work of a launch group as one step per audio stage -- is a per-run object
+        from .batch_stream import BatchStreamRun
+        yield from BatchStreamRun(self, prepared, gen_kwargs, chunk_size, lanes, rounds, stamp, seeds, device_audio, outputs,
+                                  group_marks, marks).events()
 
     @staticmethod
     def _per_text(value, n: int, what: str) -> list:
@@ -2713,6 +2482,7 @@ class FasterQwen3TTS:
     def _run_long_streaming(self, prepared, segs, spec, gen_kwargs, chunk_size: int, lanes: int):
         """Streaming form: the chunks of the lanes' utterances stay device tensors on the vocoder stream; the chunks of segment k + 1
         wait until segment k has ended; what leaves is one stream in text order.  Segment 0 streams as it decodes."""
+        from .audio_out import behind_header
         n = len(segs)
         self._refuse_streaming_loudness()
         tok = self.model.model.speech_tokenizer
@@ -2731,7 +2501,7 @@ class FasterQwen3TTS:
                 if host.size == 0 and not ended:
                     continue                                       # a chunk the join stage removed whole (or holds back)
                 if header:
-                    host, header = np.concatenate([np.frombuffer(chain.header(), dtype=np.uint8), host]), False
+                    host, header = behind_header(chain, host), False
                 yield host, sr, dict(segment_index=k, n_segments=n, chunk_index=index, is_final=ended,
                                      total_steps_so_far=int(tm.get("total_steps_so_far", 0)))
                 index += 1
@@ -2874,6 +2644,7 @@ class FasterQwen3TTS:
     def _run_long_batch_streaming(self, prepared, segs, spec, gen_kwargs, chunk_size: int, lanes: int, seeds, outputs, marks=None):
         """``_run_long_streaming`` over many texts: the chunks a poll of the lock-step run hands out together go through ONE
         ``feed_group``; every text's audio leaves in text order, the texts interleave as they become ready."""
+        from .audio_out import behind_header
         self._refuse_streaming_loudness()
         counts = [len(sg) for sg in segs]
         where = [(t, k) for t, n in enumerate(counts) for k in range(n)]
@@ -2907,7 +2678,7 @@ class FasterQwen3TTS:
                 if host.size == 0 and not ended:
                     continue                                       # a chunk the join stage removed whole (or holds back)
                 if header[t]:
-                    host, header[t] = np.concatenate([np.frombuffer(chains[t].header(), dtype=np.uint8), host]), False
+                    host, header[t] = behind_header(chains[t], host), False
                 yield t, host, rates[t], dict(segment_index=k, n_segments=counts[t], chunk_index=index[t], is_final=ended,
                                               total_steps_so_far=steps)
                 index[t] += 1

@@ -1,14 +1,17 @@
 """The launch-group layer of batch streaming (``FasterQwen3TTS._run_batch_streaming``), host bookkeeping only: which chunks of one
 poll of the lock-step decode go through ONE batched vocoder launch set, in which order the launch sets are made, and in which order
-their chunks are handed out.  The device work comes in as two callables, so the layer runs -- and is tested -- without a GPU
-(``tests/test_stream_groups_cpu.py``).
+their chunks are handed out.  The device work comes in as two callables -- ``launch`` and ``collect`` of
+``batch_stream.BatchStreamRun`` -- so the layer runs -- and is tested -- without a GPU (``tests/test_stream_groups_cpu.py``).
 
 A job is the list ``[rid, meta, audio | None, decode | None]``:
 
-* ``decode`` of the windowed path: ``(codes_in, first_sample, ready_event[, prefix])`` -- what ``StreamingVocoder.prepare`` returned;
-* ``decode`` of the exact path: ``(new_codes, drop, ready_event, None, stream_state, frames_before)``;
+* ``decode`` of the windowed path: a ``WindowDecode(codes, first, ready, prefix)`` -- what ``StreamingVocoder.prepare`` returned,
+  the event behind which the codes are ready, and the cached front-end state the decode may use (a plain tuple may end at ``ready``);
+* ``decode`` of the exact path: an ``ExactDecode(codes, drop, ready, prefix, state, frames_before)`` -- ``prefix`` is always None;
 * ``decode = None``: an event that needs no launch (its ``audio`` is already there).  Per utterance only its LAST event may be one
   (the final marker), unless no job at all has a decode (a synchronous tokenizer: everything leaves in the order it came).
+
+The records are tuples on purpose: the two paths are told apart by their length (``key_of`` / ``add``).
 
 Order.  Jobs that need the same decode shape share a class; classes are launched in order of first
 appearance, ``group`` jobs at a time, and a launch also pushes every member's own leveller, limiter, output stage or codec stream
@@ -22,7 +25,25 @@ state.  So per utterance LAUNCH order is state order, and the layer keeps it equ
   utterance adds in a poll goes into the k-th generation of its class: a stream state is pushed once per call).
 
 Groups are handed out in launch order, markers without a decode last."""
-from typing import Any, Callable, Dict, List, Optional
+from typing import Any, Callable, Dict, List, NamedTuple, Optional, Sequence, Tuple
+
+
+class WindowDecode(NamedTuple):
+    """a windowed chunk's decode: ``waveform(codes)[first:]`` is its audio"""
+    codes: Any
+    first: int
+    ready: Any                    # the event behind which ``codes`` are ready, or None (wait for the decode stream)
+    prefix: Any                   # phase 1 behind an ICL reference: the voice's cached front-end state, else None
+
+
+class ExactDecode(NamedTuple):
+    """an exact chunk's decode: ``state`` takes the new frames ``codes``, the push's samples from ``drop`` on are its audio"""
+    codes: Any
+    drop: int
+    ready: Any
+    prefix: None
+    state: Any                    # the utterance's codec stream state
+    frames_before: int            # frames the state held before this push
 
 
 def window_plan(n_total: int, n_new: int, ref_len: int, prev_len: int, spf: Optional[float], min_cal: int, context: int,
@@ -56,6 +77,40 @@ def runs_of(part: list) -> List[List[int]]:
         seen.add(j[0])
         runs[-1].append(k)
     return runs
+
+
+def push_runs(runs: Sequence[Sequence[int]], wav: Sequence, finals: Sequence[bool], take: Callable[[int], Any],
+              release: Callable[[int], None], group_fn: Callable):
+    """A stage whose rows change their length (the watermark, the limiter), pushed once per run: ``runs`` holds, per run, the rows
+    that take part (a run without any is skipped); ``take(k)`` is row k's own stage object, ``release(k)`` gives it back behind the
+    row's final push; ``group_fn(objects, rows, finals)`` is the stage's ONE launch for a run and returns the run's device buffer and
+    each row's ``(offset, count)`` in it first, whatever else behind them.  Returns ``(wav, bufs, place)``: the rows with those that
+    took part replaced by their slice of a buffer, the runs' buffers, and per row its ``(offset, count)`` in the buffers' concatenation
+    -- None for a row that took no part."""
+    wav, bufs, place, at = list(wav), [], [None] * len(wav), 0
+    for rows in runs:
+        if not rows:
+            continue
+        buf, spans = group_fn([take(k) for k in rows], [wav[k] for k in rows], [finals[k] for k in rows])[:2]
+        for k, (off, cnt) in zip(rows, spans):
+            wav[k], place[k] = buf[off:off + cnt], (at + off, cnt)
+            if finals[k]:
+                release(k)
+        bufs.append(buf)
+        at += int(buf.numel())
+    return wav, bufs, place
+
+
+def landing_plan(n_rows: int, width: int, place: Sequence[Optional[Tuple[int, int]]], buf_sizes: Sequence[int], staged):
+    """Which span of a launch group's ONE pinned buffer each row gets, no tensors involved.  The buffer holds the run buffers of
+    ``push_runs`` back to back (``buf_sizes``) and behind them, ``width`` samples each, the plain rows: those without a ``place`` that
+    are not ``staged`` (rows with an output spec reach the host through their stage's own copy).  Returns ``(length, spans)``:
+    ``spans[k]`` is row k's ``(offset, count)`` in the buffer, None for a staged row."""
+    held = sum(buf_sizes)
+    plain = [k for k in range(n_rows) if place[k] is None and k not in staged]
+    slot = {k: held + i * width for i, k in enumerate(plain)}
+    spans = [None if k in staged else place[k] if place[k] is not None else (slot[k], width) for k in range(n_rows)]
+    return held + len(plain) * width, spans
 
 
 class StreamGroups:

@@ -1,5 +1,6 @@
 """GPU: mark_embed_group_kernel behind fq3_mark_push_group.  The yardstick is twin ``Watermark`` objects driven
 by single pushes only: a row of a group equals its single push bit for bit, state included.  One case against the float64 reference."""
+import contextlib
 import ctypes as C
 import functools
 
@@ -112,6 +113,29 @@ def test_batch_streaming_marks_each_row_under_its_own_key():
             assert torch.equal(got[i], torch.from_numpy(want)) and not torch.equal(got[i], plain[i]), i
     assert torch.equal(got[1], plain[1])
     assert [m.detect_watermark(got[i].numpy(), 24000, k).present for i, k in ((0, sa.key), (1, sa.key), (2, sa.key), (0, sb.key))] == [True, False, False, False]
+
+
+def test_marked_staged_and_plain_rows_share_launches_behind_a_limiter():
+    """Frame limits 8 / 38 / 30 on two lanes at chunks of 4 frames (the shape of test_stream_groups_cpu.NAMED: the lane of text 0 is
+    re-used by text 2 while text 1 decodes), a limiter on: text 0 is marked and lands in the limiter's buffers, text 1 leaves through
+    its own s16 stage, text 2 is plain.  Every utterance is its own single stream under the same settings, bit for bit."""
+    from fq3hip.audio_out import AudioOutSpec
+    m, sa, s16, budgets = _model(), W.MarkSpec(0x0123456789ABCDEF, 0.1), AudioOutSpec(16000, "s16"), [8, 38, 30]
+    kw = dict(KW, min_new_tokens=min(budgets))
+    with m.limiter():
+        ev = {i: [] for i in range(3)}
+        for i, arr, _sr, _tm in m.generate_custom_voice_batch_streaming(TEXTS, "bob", "English", non_streaming_mode=False, lanes=2,
+                                                                        chunk_size=4, seeds=0, watermark=[sa, None, None],
+                                                                        output=[None, s16, None], **dict(kw, max_new_tokens=budgets)):
+            ev[i].append(np.asarray(arr).copy())
+        print(m._stream_group_stats, [[len(a) for a in ev[i]] for i in range(3)])
+        for i, ctx in enumerate((m.watermark(sa.key, sa.strength), m.audio_output(16000, "s16"), contextlib.nullcontext())):
+            with m.seeded(i), ctx:
+                want = np.concatenate([np.asarray(a).copy() for a, _sr, _tm in m.generate_custom_voice_streaming(
+                    TEXTS[i], "bob", "English", chunk_size=4, non_streaming_mode=False, **dict(kw, max_new_tokens=budgets[i]))])
+            got = np.concatenate(ev[i])
+            assert got.dtype == want.dtype == (np.dtype("<i2") if i == 1 else np.float32), i
+            assert torch.equal(torch.from_numpy(got), torch.from_numpy(want)), (i, len(got), len(want))
 
 
 def test_one_shot_batch_refusals_and_long_form():

@@ -13,7 +13,7 @@ import pytest
 import torch
 
 import fq3hip.batching as Bt
-from fq3hip.stream_groups import StreamGroups, runs_of, window_plan
+from fq3hip.stream_groups import StreamGroups, landing_plan, push_runs, runs_of, window_plan
 from test_batching_cpu import FakeBatch, FakeLaneEngine, LookAheadBatch, _req
 
 GROUP = 32                       # _SideVocoder.STREAM_GROUP (asserted against the product below)
@@ -356,3 +356,70 @@ def test_window_plan_is_the_references_windowing():
                     want = (total - n_new - ctx, ctx + n_new, int(round(ctx * spf)) if ctx else 0, prev, spf)
                 assert got == want
                 _start, _n_in, _first, prev, spf = got
+
+
+# ---- the landing plan and the ragged stages of a launch (``landing_plan`` / ``push_runs``) -------------------------------------------
+# The expected spans are worked out by hand from the launch as it was written inline: the run buffers lie back to back at the front
+# of the one pinned buffer, the plain rows (no place, not staged) follow them ``width`` samples each, a staged row gets nothing.
+
+def _fake_stage(keep, extra=()):
+    """a group function shaped as ``limiter._push_group`` (``extra``: its third value) / ``watermark._push_group``: the row of object
+    ``o`` comes back as its first ``keep[o]`` samples, the rows of a call packed back to back"""
+    calls = []
+
+    def group_fn(objs, rows, finals):
+        calls.append((list(objs), list(finals)))
+        cnts = [keep[o] for o in objs]
+        buf = torch.cat([r[:c] for r, c in zip(rows, cnts)]) if cnts else torch.zeros(0)
+        return (buf, [(sum(cnts[:i]), c) for i, c in enumerate(cnts)]) + tuple(extra)
+
+    group_fn.calls = calls
+    return group_fn
+
+
+def _rows(n, width=4):
+    return torch.arange(n * width, dtype=torch.float32).reshape(n, width)
+
+
+def test_landing_plan_marked_plain_and_staged_row_without_a_limiter():
+    assert landing_plan(3, 4, [(0, 2), None, None], [2], {2}) == (2 + 4, [(0, 2), (2, 4), None])
+
+
+def test_landing_plan_two_runs_behind_a_limiter():
+    """buffers of 5 and 3 samples: the second run's rows are offset by 5, and nothing follows the buffers"""
+    whole, released = _rows(3), []
+    fn = _fake_stage({0: 3, 1: 2, 2: 3}, extra=("state",))
+    wav, bufs, place = push_runs([[0, 1], [2]], whole, [False, True, True], lambda k: k, released.append, fn)
+    assert [int(b.numel()) for b in bufs] == [5, 3] and place == [(0, 3), (3, 2), (5, 3)]
+    assert fn.calls == [([0, 1], [False, True]), ([2], [True])] and released == [1, 2]
+    assert landing_plan(3, 4, place, [5, 3], set()) == (8, [(0, 3), (3, 2), (5, 3)])
+    pinned = torch.cat(bufs)
+    for k, (off, cnt) in enumerate(place):
+        assert torch.equal(pinned[off:off + cnt], whole[k][:cnt]) and torch.equal(wav[k], whole[k][:cnt])
+
+
+def test_landing_plan_a_row_held_back_whole_keeps_an_empty_span():
+    whole = _rows(3)
+    wav, bufs, place = push_runs([[0, 1, 2]], whole, [False] * 3, lambda k: k, None, _fake_stage({0: 3, 1: 0, 2: 2}, extra=(None,)))
+    assert place == [(0, 3), (3, 0), (3, 2)] and wav[1].numel() == 0
+    assert landing_plan(3, 4, place, [5], set()) == (5, [(0, 3), (3, 0), (3, 2)])
+
+
+def test_landing_plan_every_row_staged():
+    assert landing_plan(2, 4, [(0, 3), (3, 1)], [4], {0, 1}) == (4, [None, None])
+    assert landing_plan(2, 4, [None, None], [], {0, 1}) == (0, [None, None])
+
+
+def test_landing_plan_plain_rows_follow_all_buffers():
+    """no limiter; an utterance stands in the part twice, so its marked rows fall into two runs: the plain row in front of them
+    lands behind both buffers.  A run without a marked row makes no call and no buffer."""
+    whole, released = _rows(3), []
+    fn = _fake_stage({1: 2, 2: 4})
+    wav, bufs, place = push_runs([[1], [2]], whole, [False, False, True], lambda k: k, released.append, fn)
+    assert place == [None, (0, 2), (2, 4)] and released == [2] and torch.equal(wav[0], whole[0])
+    assert landing_plan(3, 4, place, [2, 4], set()) == (6 + 4, [(6, 4), (0, 2), (2, 4)])
+    fn = _fake_stage({2: 3})
+    wav, bufs, place = push_runs([[], [2]], whole, [False] * 3, lambda k: k, None, fn)
+    assert len(fn.calls) == 1 and place == [None, None, (0, 3)]
+    assert landing_plan(3, 4, place, [3], set()) == (3 + 8, [(3, 4), (7, 4), (0, 3)])
+    assert landing_plan(3, 4, place, [3], {0}) == (3 + 4, [None, (3, 4), (0, 3)])
